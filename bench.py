@@ -26,9 +26,16 @@ binds it: `bound` and `hbm_counter_frac` / `valu_issue_frac` / `lanes_active` co
 rocprofv3 PMC profile of the same command (profiles/rNN_per_kernel.json, labelled profile-derived, like
 `traffic`), and `l2_frac` (34.5 TB/s) is given beside them.
 
-Timing: the K-step region (exactly --steps frames, barrier + synchronize on both sides) is run `--repeats` R
-times back to back (default 50: the driver's --steps 20 is ONE 1.4 ms launch sequence, far too short a
-sample on its own); `value` and `ms_per_step` are the MEDIAN region's, config.repeats has min / max / first.
+Timing: the timed region is exactly K = --steps frames (barrier + synchronize on both sides), run once by
+default. `--repeats` R > 1 runs it R times back to back (R x K timed frames); `value` and `ms_per_step` are
+then the MEDIAN region's, config.repeats has min / max / first.
+
+--dump-outputs DIR: after the timed region, what its last step computed — the float4 {r, g, b, z} framebuffer
+of the frames of the last launch sequence, what rtu_render_frames_device hands its caller — goes to DIR/*.npy
+(float32, at most 64 MB): all of it when it fits (frames_rgbz.npy, [frames, H, W, 4]), else the first frame
+whole (frame0_rgbz.npy, [H, W, 4]) and 2^20 pixels of all frames drawn without replacement by a generator
+seeded with 0, in index order (frames_rgbz_sample.npy, [2^20, 4]). N>1: rank 0 writes frame 0 as gathered
+and assembled. The inputs are the same from run to run (the committed scene blob, the turntable cameras).
 
 N=1: python bench.py.  N>1: launched by torch.distributed.run, one rank per GPU; the frame is sharded by
 interleaved 8-row bands (band b -> rank b % N, scene replicated, no data-path collective) and every batch
@@ -103,13 +110,33 @@ def orbit_camera(cam, degrees):
     return c
 
 
+DUMP_LIMIT = 64 << 20    # bytes --dump-outputs may write
+DUMP_SAMPLE = 1 << 20    # pixels of the seeded sample when the last step's frames exceed DUMP_LIMIT
+
+
+def dump_last_step(buf, nb, rows, W):
+    """The nb frames [rows][W] float4 at the start of buf (the last timed launch sequence's output) -> {name: host array}."""
+    import torch
+    frames = buf.view(-1)[:nb * rows * W * 4].view(nb, rows, W, 4)
+    if frames.numel() * 4 <= DUMP_LIMIT:
+        return {"frames_rgbz": frames.cpu().numpy()}
+    out = {}
+    if rows * W * 16 <= DUMP_LIMIT - DUMP_SAMPLE * 16:
+        out["frame0_rgbz"] = frames[0].cpu().numpy()
+    idx = np.sort(np.random.default_rng(0).choice(nb * rows * W, DUMP_SAMPLE, replace=False))
+    out["frames_rgbz_sample"] = frames.view(-1, 4)[torch.from_numpy(idx).to(buf.device)].cpu().numpy()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=320)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--repeats", type=int, default=50,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the timed K-step region is run this many times back to back; value / ms_per_step are the median region's (min, max and the first in config.repeats)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float32, at most 64 MB; see the module docstring)")
     ap.add_argument("--tag", default=WORKLOAD_TAG, help="golden tag to render (default: the headline workload)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host threads of the cpu_baseline leg (0 = every core this process may use: its affinity mask, capped by the cgroup CPU quota)")
@@ -446,6 +473,20 @@ def main():
         gold = np.load(os.path.join(gdir, "golden.npz"))
         z_ok = (hashlib.sha256(np.ascontiguousarray(zimg8).tobytes()).hexdigest() == meta["sha256_zbuffer_u8"]
                 and int(np.abs(rgb8.astype(np.int32) - gold["result_u8"].astype(np.int32)).max()) <= 1)
+
+    if args.dump_outputs and rank == 0:
+        if dist:  # frame 0 of the last gathered batch, as assembled on the root above
+            if out4:
+                dump = {"result_u8": rgb8, "zbuffer_u8": zimg8}
+            elif packed:
+                dump = {"z": img[..., 3], "result_u8": rgb8}
+            else:
+                dump = {"frame0_rgbz": img}
+        else:
+            dump = dump_last_step(shards[(len(batches) - 1) % C], batches[-1], rows, W)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
     # -- the single-frame configuration: one frame per launch sequence (what BeginRender() of one image costs) ----------
     single = None

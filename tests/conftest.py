@@ -9,7 +9,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 GOLDEN = os.path.join(REPO, "tests", "golden")
-REFERENCE = "/root/reference"  # exists only in the authoring container, never on the GPU box
+MAC_PREFIX = "/Users/Peter/GitRepos/RayTracer-Utah"  # the directory the reference's scene files name their meshes and textures by
 
 SMALL_TAGS = ["p1_256", "p4_240x135", "teapot2_240x135", "p11_240x135"]
 FULL_TAGS = ["p3s_800x600", "p4_1080", "teapot2_1080", "p11_1080"]
@@ -32,6 +32,73 @@ def instantiate_scene(rel, dst):
             data = data.replace(b"@DIR@", str(dst).encode())
         open(os.path.join(str(dst), name), "wb").write(data)
     return os.path.join(str(dst), os.path.basename(rel))
+
+
+def write_png_rgb(path, rgb, filters):
+    """8-bit RGB PNG of rgb ([h, w, 3] uint8) with filters[y] (0-4) as the filter type of row y: with the filter types of
+    an existing file this reproduces that file's filtered byte stream exactly (only the deflate layer can differ)."""
+    import struct
+    import zlib
+    h, w, _ = rgb.shape
+    x = rgb.reshape(h, w * 3).astype(np.int32)
+    a = np.zeros_like(x)
+    a[:, 3:] = x[:, :-3]   # the byte one pixel to the left
+    b = np.zeros_like(x)
+    b[1:] = x[:-1]         # the byte above
+    c = np.zeros_like(x)
+    c[1:] = a[:-1]         # above and to the left
+    pa, pb, pc = np.abs(b - c), np.abs(a - c), np.abs(a + b - 2 * c)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+    pred = [np.zeros_like(x), a, b, (a + b) >> 1, paeth]
+    f = np.asarray(filters, np.int32)
+    rows = np.take_along_axis(np.stack(pred), f[None, :, None].repeat(w * 3, axis=2), axis=0)[0]
+    body = np.concatenate([f[:, None], (x - rows) & 255], axis=1).astype(np.uint8).tobytes()
+
+    def chunk(typ, data):
+        return struct.pack(">I", len(data)) + typ + data + struct.pack(">I", zlib.crc32(typ + data) & 0xFFFFFFFF)
+    with open(path, "wb") as out:
+        out.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+                  chunk(b"IDAT", zlib.compress(body, 9)) + chunk(b"IEND", b""))
+
+
+def texture_pixels(pkg, scene, i):
+    """Texture i of a loaded scene as [h, w, 3] uint8 (RtuTexture, include/rtu_scene.h); None without pixels."""
+    import ctypes
+
+    class Tex(ctypes.Structure):
+        _fields_ = [("type", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                    ("rgb", ctypes.c_void_p), ("color1", ctypes.c_float * 3), ("color2", ctypes.c_float * 3)]
+    t = Tex.from_address(scene.desc.textures + i * ctypes.sizeof(Tex))
+    if not t.rgb:  # a checker, or a file that failed to load
+        return None
+    return np.ctypeslib.as_array((ctypes.c_uint8 * (t.width * t.height * 3)).from_address(t.rgb)).reshape(t.height, t.width, 3).copy()
+
+
+@pytest.fixture(scope="session")
+def scene_files(tmp_path_factory, pkg):
+    """The reference's scene files (tests/golden/SceneFiles, written by make_goldens.py SceneFiles) as a tree
+    <root>/SceneFiles/..., .obj files unpacked: load them with Scene.from_xml(path, MAC_PREFIX, <root>).
+    The PNG textures are too large to store: each is written back from the pixels the reference decoded from it
+    (a texture of a golden scene blob) with the filter type of every row of the original file (textures.json)."""
+    import gzip
+    import shutil
+    root = tmp_path_factory.mktemp("reference")
+    src = os.path.join(GOLDEN, "SceneFiles")
+    for d, _, names in os.walk(src):
+        out = os.path.join(str(root), "SceneFiles", os.path.relpath(d, src))
+        os.makedirs(out, exist_ok=True)
+        for name in names:
+            if name.endswith(".gz"):
+                with gzip.open(os.path.join(d, name), "rb") as f, open(os.path.join(out, name[:-3]), "wb") as g:
+                    shutil.copyfileobj(f, g)
+            elif name != "textures.json":
+                shutil.copyfile(os.path.join(d, name), os.path.join(out, name))
+    for rel, t in json.load(open(os.path.join(src, "textures.json"))).items():
+        scene = pkg.Scene.from_blob_file(os.path.join(GOLDEN, t["tag"], "scene.rtus.gz"))
+        write_png_rgb(os.path.join(str(root), "SceneFiles", rel), texture_pixels(pkg, scene, t["texture"]), [int(v) for v in t["filters"]])
+    return str(root)
+
+
 # stochastic effects (SURVEY row f1), recipe S: glossy + soft + textured; depth of field; glossy + soft; 12 soft lights + glossy refraction; teapot + soft;
 # glossy under a hard light (Project11/scene_glossy.xml: with it every scene file of the reference has a fixture)
 SAMPLED_TAGS = ["p10_s4_160x120", "p9_s3_160x120", "p11gs_s2_160x90", "p11x86_s1_120x90", "teapot1_s2_160x90", "p11g_s2_160x90"]

@@ -15,6 +15,11 @@ SURVEY.md §8c; "recipe S" for the scenes with stochastic effects) and stores DA
   meta.json       resolution, ray counters, sha256 of the full float z / rgb /
                   8-bit buffers
 
+`make_goldens.py SceneFiles` copies the reference's scene files that the loader tests read (tests/test_host.py,
+tests/test_oracle.py) to tests/golden/SceneFiles/: every scene XML and the meshes they name, .obj files gzipped;
+for the PNG textures only the filter type of each row and which texture of a golden blob holds their pixels
+(textures.json), from which the tests write them back. They are the inputs of the fixtures above, so the loader is checked without the reference tree.
+
 No reference source text is copied; the fixtures are inputs and outputs.
 """
 import gzip, hashlib, json, os, shutil, subprocess, sys
@@ -43,6 +48,8 @@ CONFIGS = [
     ("p5low_200x150", "Project5/scene-low.xml", 200, 150, True),
     ("p11simple_200x150", "Project11/scene_simple.xml", 200, 150, True),
     ("p13_200x150", "Project13/scene.xml", 200, 150, True),
+    # a resolution no other fixture renders this scene at (tests/test_oracle.py test_oracle_vs_live_reference_build)
+    ("p5_176x132", "Project5/scene.xml", 176, 132, True),
     # textures ("next" row f2): checkerboards, two 1024x1024 PNGs (mesh diffuse, background, environment)
     ("p7_200x150", "Project7/scene.xml", 200, 150, True),
     # stochastic effects ("next" row f1), recipe S: the 7th field is samples per pixel. The reference is built
@@ -65,12 +72,72 @@ CONFIGS = [
 ]
 
 
+# the files the scene XMLs name (absolute macOS paths, remapped to the copy by the tests); Teapot/ink*.png do not exist
+SCENE_ASSETS = ["Project5/teapot.obj", "Project5/teapot-low.obj", "Project5/plane.obj", "Project7/teapot.obj"]
+# too large to store: rebuilt by the tests (conftest.scene_files) from the pixels of a golden blob's texture and the
+# filter type of each row of the file, recorded in SceneFiles/textures.json
+SCENE_TEXTURES = {"Project7/bricks.png": "p7_200x150", "Project7/clouds.png": "p7_200x150"}
+
+
+def png_rows(path):
+    """(inflated IDAT stream, filter type of every row) of an 8-bit RGB PNG."""
+    import struct
+    import zlib
+    d, pos, idat = open(path, "rb").read(), 8, b""
+    while pos < len(d):
+        n, typ = struct.unpack(">I4s", d[pos:pos + 8])
+        if typ == b"IHDR":
+            w, h, depth, ctype, _, _, interlace = struct.unpack(">IIBBBBB", d[pos + 8:pos + 8 + n])
+            assert (depth, ctype, interlace) == (8, 2, 0), path
+        elif typ == b"IDAT":
+            idat += d[pos + 8:pos + 8 + n]
+        pos += 12 + n
+    raw = zlib.decompress(idat)
+    return raw, "".join(str(raw[y * (w * 3 + 1)]) for y in range(h))
+
+
+def copy_scene_files():
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import tempfile
+    import __graft_entry__
+    from conftest import read_png, texture_pixels, write_png_rgb
+    pkg = __graft_entry__.load_package()
+    src = os.path.join(os.environ.get("REF", "/root/reference"), "SceneFiles")
+    dst = os.path.join(HERE, "SceneFiles")
+    rels = sorted(os.path.relpath(os.path.join(d, f), src) for d, _, fs in os.walk(src) for f in fs if f.endswith(".xml"))
+    for rel in rels + SCENE_ASSETS:
+        os.makedirs(os.path.dirname(os.path.join(dst, rel)), exist_ok=True)
+        if rel.endswith(".obj"):
+            with open(os.path.join(src, rel), "rb") as f, gzip.GzipFile(os.path.join(dst, rel + ".gz"), "wb", mtime=0) as g:
+                g.write(f.read())
+        else:
+            shutil.copyfile(os.path.join(src, rel), os.path.join(dst, rel))
+    textures = {}
+    for rel, tag in sorted(SCENE_TEXTURES.items()):
+        raw, filters = png_rows(os.path.join(src, rel))
+        scene = pkg.Scene.from_blob_file(os.path.join(HERE, tag, "scene.rtus.gz"))
+        pixels = read_png(os.path.join(src, rel))
+        i = [k for k in range(scene.desc.n_textures) if np.array_equal(texture_pixels(pkg, scene, k), pixels)][0]
+        with tempfile.TemporaryDirectory() as tmp:  # what the tests will write must be the original's filtered stream
+            write_png_rgb(os.path.join(tmp, "t.png"), texture_pixels(pkg, scene, i), [int(v) for v in filters])
+            assert png_rows(os.path.join(tmp, "t.png"))[0] == raw, rel
+        textures[rel] = {"tag": tag, "texture": i, "filters": filters}
+    json.dump(textures, open(os.path.join(dst, "textures.json"), "w"), indent=1, sort_keys=True)
+    print("SceneFiles", len(rels), "scene files,", len(SCENE_ASSETS), "meshes,", len(textures), "textures")
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def main():
     only = set(sys.argv[1:])
+    if "SceneFiles" in only:
+        copy_scene_files()
+        only.discard("SceneFiles")
+        if not only:
+            return
     for cfg in CONFIGS:
         tag, scene, W, H, full = cfg[:5]
         spp = cfg[5] if len(cfg) > 5 else 0

@@ -9,9 +9,8 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ALL_TAGS, LOCAL_SCENES, REFERENCE, REPO, SAMPLED_TAGS, SMALL_TAGS, TEX_TAGS, instantiate_scene, read_png
+from conftest import ALL_TAGS, LOCAL_SCENES, MAC_PREFIX, REPO, SAMPLED_TAGS, SMALL_TAGS, TEX_TAGS, instantiate_scene, read_png
 
-MAC_PREFIX = "/Users/Peter/GitRepos/RayTracer-Utah"
 SCENES = {
     "p1_256": "Project1Example.xml", "p3s_800x600": "Project3Simple.xml", "p4_1080": "Project4.xml",
     "teapot2_1080": "Teapot/scene2.xml", "p11_1080": "Project11/scene.xml", "p4_240x135": "Project4.xml",
@@ -84,14 +83,13 @@ def test_blob_rejects_garbage(pkg, golden):
         pkg.Scene.from_blob_bytes(bytes(huge))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="scene files only exist in the authoring container")
 @pytest.mark.parametrize("tag", [t for t in ALL_TAGS + TEX_TAGS + SAMPLED_TAGS if t not in LOCAL_SCENES])
-def test_loader_matches_reference_scene_values(pkg, golden, tag):
+def test_loader_matches_reference_scene_values(pkg, golden, scene_files, tag):
     """Own XML + OBJ reader + BVH build vs the blob dumped from the reference's in-memory
     scene graph after ITS LoadScene(): every float of every node/material/light/camera,
     every mesh array and every BVH node identical."""
     g = golden(tag)
-    s = pkg.Scene.from_xml(os.path.join(REFERENCE, "SceneFiles", SCENES[tag]), MAC_PREFIX, REFERENCE)
+    s = pkg.Scene.from_xml(os.path.join(scene_files, "SceneFiles", SCENES[tag]), MAC_PREFIX, scene_files)
     s.set_resolution(g.width, g.height)
     assert s.to_blob_bytes() == g.scene(pkg).to_blob_bytes()
 

@@ -1,12 +1,12 @@
 """CPU-only: the oracle (oracle/rtu_oracle.cpp) against the golden vectors generated
 from the compiled reference (tests/golden/make_goldens.py). This is what pins the
-oracle on a machine without /root/reference."""
+oracle on a machine without the reference tree."""
 import os
 
 import numpy as np
 import pytest
 
-from conftest import PATH_TAGS, REFERENCE, SAMPLED_TAGS, SMALL_TAGS, TEX_TAGS, read_png, sha256
+from conftest import PATH_TAGS, SAMPLED_TAGS, SMALL_TAGS, TEX_TAGS, read_png, sha256
 
 
 @pytest.mark.parametrize("tag", SMALL_TAGS + TEX_TAGS)
@@ -91,26 +91,30 @@ def test_oracle_rejects_stochastic_scenes(pkg, orc, golden):
     orc.render(scene, 16, 16)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the authoring container")
-def test_oracle_vs_live_reference_build(pkg, orc, tmp_path):
-    """Where the reference is present: run oracle/_ref/ref_render (the reference's own
-    functions) on a scene/resolution that is NOT among the goldens and compare all bits."""
+def test_oracle_vs_live_reference_build(pkg, orc, golden, scene_files, tmp_path):
+    """The reference's own functions (oracle/_ref/ref_render) on a scene / resolution that no other test renders
+    (tag p5_176x132, stored by make_goldens.py) against the oracle, all bits. Where the reference harness is built
+    it is run live on the stored scene files as well, and must reproduce the stored output."""
+    import gzip
     import subprocess
-    from conftest import REPO
+    from conftest import MAC_PREFIX, REPO
+    g = golden("p5_176x132")
+    W, H = g.width, g.height
+    out, _ = orc.render(g.scene(pkg), W, H, threads=4)
+    assert np.array_equal(out[..., 3].view(np.uint32), g.npz["z"].view(np.uint32))
+    assert np.array_equal(out[..., :3].view(np.uint32), g.npz["rgb"].view(np.uint32))
     exe = os.path.join(REPO, "oracle", "_ref", "ref_render")
     if not os.path.exists(exe):
-        pytest.skip("oracle/_ref not built")
+        return
     xml = tmp_path / "scene.xml"
-    src = open(os.path.join(REFERENCE, "SceneFiles", "Project5", "scene.xml")).read()
-    xml.write_text(src.replace("/Users/Peter/GitRepos/RayTracer-Utah", REFERENCE))
-    W, H = 200, 150
+    src = open(os.path.join(scene_files, "SceneFiles", "Project5", "scene.xml")).read()
+    xml.write_text(src.replace(MAC_PREFIX, scene_files))
     subprocess.check_call([exe, str(xml), str(W), str(H), str(tmp_path), "4"], stdout=subprocess.DEVNULL)
-    scene = pkg.Scene.from_blob_file(str(tmp_path / "scene.rtus"))
-    out, _ = orc.render(scene, W, H, threads=4)
+    assert (tmp_path / "scene.rtus").read_bytes() == gzip.open(os.path.join(g.dir, "scene.rtus.gz")).read()
     z = np.fromfile(tmp_path / "z.f32", np.float32).reshape(H, W)
     rgb = np.fromfile(tmp_path / "rgb.f32", np.float32).reshape(H, W, 3)
-    assert np.array_equal(out[..., 3].view(np.uint32), z.view(np.uint32))
-    assert np.array_equal(out[..., :3].view(np.uint32), rgb.view(np.uint32))
+    assert np.array_equal(z.view(np.uint32), g.npz["z"].view(np.uint32))
+    assert np.array_equal(rgb.view(np.uint32), g.npz["rgb"].view(np.uint32))
 
 
 # ---- recipe S: stochastic effects (SURVEY row f1) -------------------------------------------------
