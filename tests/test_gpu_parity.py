@@ -1561,7 +1561,14 @@ def test_stage2_of_the_primary_phase_beside_the_recursion_levels(pkg, ctx, golde
             t = ctx.touched(False)
             for i in range(n):
                 assert np.array_equal(out[i].view(np.uint32), singles[i].view(np.uint32)), "flags %d, touched-bytes mode: frame %d differs" % (flags, i)
-            assert ("k_tail(side)" in t or t.get("k_primary2", {}).get("rays", 0) > 0)
+            nl = (ctypes.c_uint32 * pkg.KERNEL_SLOTS)()
+            n_slots = pkg.hip.rtu_get_touched_launches(ctx._h, nl, pkg.KERNEL_SLOTS)
+            side = nl[[pkg.hip.rtu_kernel_slot_name(k).decode() for k in range(n_slots)].index("k_tail(side)")]
+            if flags == 0:
+                assert side >= 1, "side mode was not taken"
+            else:
+                assert side == 0 and "k_tail(side)" not in t, "side mode taken under rtu_debug_flags 8192"
+                assert t.get("k_primary2", {}).get("rays", 0) > 0  # stage 2 of the primary phase in the launch stream
             if flags == 0:
                 assert "k_primary2" in t and "k_primary2c" not in t  # the long list: one lane per ray
                 _, deferred = ctx.frame_counts()
