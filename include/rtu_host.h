@@ -13,6 +13,8 @@
  *   rtu_image_from_rgbz     <- gamma + Color24 store             RenderFunctions.cpp:152-160
  *   rtu_image_compute_zimg  <- RenderImage::ComputeZBufferImage  ExternalLibrary/scene.h:590-612
  *   rtu_image_save_png      <- RenderImage::SaveImage/SaveZImage ExternalLibrary/scene.h:633-654
+ *   rtu_image_compute_sample_count_img / rtu_image_save_sample_count_png
+ *                           <- ComputeSampleCountImage / SaveSampleCountImage  scene.h:614-640
  *   rtu_begin_render / rtu_stop_render / rtu_render_wait
  *                           <- BeginRender()/StopRender()        main.cpp:66-72, viewport.cpp:36-37
  */
@@ -20,6 +22,7 @@
 #define RTU_HOST_H_INCLUDED
 
 #include "rtu_scene.h"
+#include "rtu_render.h"  /* RtuAdaptiveDesc */
 
 #ifdef __cplusplus
 extern "C" {
@@ -74,6 +77,14 @@ void      rtu_image_from_rgbz(RtuImage* img, const float* rgbz, int row0, int nr
 void      rtu_image_compute_zimg(RtuImage* img);
 int       rtu_image_save_png(const RtuImage* img, const char* path);   /* 8-bit RGB */
 int       rtu_image_save_zpng(const RtuImage* img, const char* path);  /* 8-bit grey */
+/* uchar sampleCount[] (scene.h:545): the samples each pixel took, W*H, zero after create; fill rows from a count image
+ * (rtu_render_frame_adaptive). ComputeSampleCountImage (scene.h:614-635): 255 * (c - smin) / (smax - smin) in integers, all 0 when
+ * smax == smin; returns smax. The sample-count image is NULL before it is computed; the PNG is 8-bit grey (SaveSampleCountImage). */
+uint8_t*  rtu_image_sample_count(RtuImage* img);
+void      rtu_image_fill_sample_count(RtuImage* img, const uint8_t* counts, int row0, int nrows);
+int       rtu_image_compute_sample_count_img(RtuImage* img);
+uint8_t*  rtu_image_sample_count_image(RtuImage* img);
+int       rtu_image_save_sample_count_png(const RtuImage* img, const char* path);
 /* Generic 8-bit PNG writer (comp = 1 or 3). */
 int       rtu_write_png(const char* path, const uint8_t* data, int width, int height, int comp);
 
@@ -97,6 +108,13 @@ RtuRenderJob* rtu_begin_render_sampled(const RtuScene* scene, RtuImage* img,
 RtuRenderJob* rtu_begin_render_paths(const RtuScene* scene, RtuImage* img,
                                      const int* device_ids, int n_devices, int samples,
                                      const char* result_png, const char* zbuffer_png);
+/* Adaptive sampling (rtu_render_frame_adaptive): `samples` is the maximum per pixel (1 .. 255), gather_bounces 0 (recipe S) or 4
+ * (recipe P), adaptive NULL = rtu_adaptive_defaults. One context per listed device (ids may repeat), each rendering its shard;
+ * rows and sample counts are assembled into img. Then main.cpp:59-63: Result.png, ZBuffer.png and — the lines the reference leaves
+ * commented out — ComputeSampleCountImage + SampleCount.png (any path may be NULL to skip). rtu_stop_render cancels between batches. */
+RtuRenderJob* rtu_begin_render_adaptive(const RtuScene* scene, RtuImage* img, const int* device_ids, int n_devices, int samples,
+                                        int gather_bounces, const RtuAdaptiveDesc* adaptive, const char* result_png,
+                                        const char* zbuffer_png, const char* samplecount_png);
 void      rtu_stop_render(RtuRenderJob* job);      /* cooperative cancel between bands */
 int       rtu_render_wait(RtuRenderJob* job);      /* join; 0 or negative error code */
 /* After the job (joins): how the shards reached the host — 1 one context; 2 several contexts, asynchronous copies into one

@@ -199,6 +199,43 @@ int  rtu_render_frame(RtuContext* ctx, const RtuFrameDesc* frame, float* h_rgbz,
  * incomplete and renders them again. */
 int  rtu_frame_status(RtuContext* ctx);
 
+/* ---- Adaptive sampling: recipes S / P that stop sampling a pixel once its samples agree ------------------------------------------
+ * What the reference's sample loop declares next to maxSampleSize (RenderFunctions.cpp:26-29: minSampleSize = 8, targetVariance = 0.005,
+ * sampleIncrement = 1) and what RenderImage::sampleCount / ComputeSampleCountImage keep (scene.h:545-546, 614-635).
+ * An adaptive frame is a recipe S or P frame (samples >= 1, gather_bounces 0 or 4); frame.samples is the MAXIMUM per pixel, in [1, 255]
+ * (the reference stores counts as uchar). Sample i of a pixel is the sample i of the fixed render with frame.samples samples: the same
+ * key, the same pixel offset. Per pixel and channel, in binary32 with every operation rounded, in sample order:
+ *     s += x (the sum of the fixed render), q += x * x;
+ * at each checkpoint n = min_samples + k * increment < frame.samples: m = s / n, var = (q - s * m) / (n - 1) (n as float; n == 1:
+ * var = +inf). The pixel STOPS at n when var <= target_variance for r, g and b, otherwise at frame.samples. Its rgb is s / n, its z the
+ * mean z over the samples among its first n that hit, its count n. The decision depends on the pixel's own samples only — never on how
+ * the samples are grouped into batches — so a pixel that stops at n is, bit for bit, the mean of the first n samples of the fixed render.
+ * A pixel that has stopped is not traced any more: its rays are never spawned. */
+#define RTU_MAX_BATCH 16  /* samples rendered by one launch sequence of recipes S / P, at most */
+typedef struct RtuAdaptiveDesc {
+    int32_t min_samples;      /* first checkpoint, in [1, samples] (minSampleSize) */
+    int32_t increment;        /* >= 1 (sampleIncrement) */
+    float   target_variance;  /* >= 0, +inf allowed (every pixel stops at min_samples); NaN refused (targetVariance) */
+    int32_t max_batch;        /* samples per launch sequence, at most: 0 = the library's choice, else 1 .. RTU_MAX_BATCH (no effect on results) */
+} RtuAdaptiveDesc;
+/* The reference's constants: 8, 1, 0.005f, 0. */
+int  rtu_adaptive_defaults(RtuAdaptiveDesc* out);
+/* Render this shard adaptively and copy it to the host: h_rgbz as rtu_render_frame (rtu_shard_rows * width float4), h_counts
+ * (may be NULL) the samples each pixel took (rtu_shard_rows * width bytes). Synchronous; stats (may be NULL) selects the counting
+ * variant as for rtu_render_frame. shard_rank / shard_count are honoured (keys are global: the shards assemble to the single-GPU
+ * image). The cancel flag is polled between batches. RTU_ERR_ARG: samples outside [1, 255], gather_bounces not 0 / 4, min_samples
+ * outside [1, samples], increment < 1, a NaN or negative target, max_batch outside [0, RTU_MAX_BATCH]. */
+int  rtu_render_frame_adaptive(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, float* h_rgbz, uint8_t* h_counts,
+                               RtuStats* stats);
+/* The same into DEVICE memory (d_rgbz as rtu_render_frame_device, d_counts rtu_shard_rows * width bytes, may be NULL), queued on
+ * hip_stream; like a sampled rtu_render_frame_device it synchronises per batch (the host sizes the next batch's launch from the
+ * number of tiles still sampling). rtu_frame_status afterwards as for a single frame. */
+int  rtu_render_frame_adaptive_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, void* d_rgbz, void* d_counts,
+                                      void* hip_stream);
+/* Diagnostic: render samples [first, first + n) of the FIXED recipe S / P frame `frame` and copy their images — what the accumulator
+ * adds, n x rtu_shard_rows x width float4 {r, g, b, z}, z = RTU_BIGFLOAT for a miss — to h_out. Synchronous. */
+int  rtu_debug_sample_images(RtuContext* ctx, const RtuFrameDesc* frame, int first, int n, float* h_out);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. A single launch sequence (a frame of

@@ -144,7 +144,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_upload_scene", "rtu_validate_scene", "rtu_frame_setup", "rtu_shard_rows", "rtu_shard_max_rows", "rtu_shard_global_row",
                "rtu_render_frame_device", "rtu_render_frames_device", "rtu_pack_image_device", "rtu_minmax_z_device", "rtu_pack_output_device", "rtu_render_frame", "rtu_frame_status", "rtu_render_timeline", "rtu_frame_counts", "rtu_timeline_exits", "rtu_mesh_info", "rtu_light_list_info", "rtu_debug_light_list", "rtu_debug_light_list_free", "rtu_debug_walk_stack_limit", "rtu_debug_node_bounds", "rtu_debug_flags", "rtu_set_sequences_in_flight", "rtu_debug_tail_from", "rtu_get_stats", "rtu_get_touched", "rtu_get_touched_launches", "rtu_touched_bytes", "rtu_kernel_slot_name", "rtu_probe_kernel", "rtu_probe_read", "rtu_time_render", "rtu_selftest_division", "rtu_selftest_primitives", "rtu_context_stream", "rtu_context_device", "rtu_context_sync", "rtu_host_alloc_pinned", "rtu_host_free_pinned", "rtu_copy_to_host_async", "rtu_device_alloc",
                "rtu_device_free", "rtu_copy_to_host", "rtu_device_info", "rtu_set_cancel_flag", "rtu_create_context_multi", "rtu_destroy_context_multi",
-               "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind"]
+               "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind",
+               "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -187,6 +188,28 @@ _sig(hip, "rtu_selftest_division", _I, _P, ctypes.c_ulonglong, ctypes.c_ulonglon
 _sig(hip, "rtu_device_alloc", _P, _P, ctypes.c_size_t)
 _sig(hip, "rtu_device_free", None, _P, _P)
 _sig(hip, "rtu_copy_to_host", _I, _P, _P, _P, ctypes.c_size_t)
+
+
+class RtuAdaptiveDesc(ctypes.Structure):
+    _fields_ = [("min_samples", ctypes.c_int32), ("increment", ctypes.c_int32), ("target_variance", ctypes.c_float), ("max_batch", ctypes.c_int32)]
+
+
+RTU_MAX_BATCH = 16
+_sig(hip, "rtu_adaptive_defaults", _I, ctypes.POINTER(RtuAdaptiveDesc))
+_sig(hip, "rtu_render_frame_adaptive", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P, ctypes.POINTER(RtuStats))
+_sig(hip, "rtu_render_frame_adaptive_device", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P, _P)
+_sig(hip, "rtu_debug_sample_images", _I, _P, ctypes.POINTER(RtuFrameDesc), _I, _I, _P)
+
+
+def adaptive_defaults(**overrides):
+    """RtuAdaptiveDesc with the reference's constants (min_samples 8, increment 1, target_variance 0.005, max_batch 0), then `overrides`."""
+    d = RtuAdaptiveDesc()
+    rc = hip.rtu_adaptive_defaults(ctypes.byref(d))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_adaptive_defaults")
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
 
 
 class RtuDeviceInfo(ctypes.Structure):
@@ -260,7 +283,9 @@ HOST_SYMBOLS = ["rtu_scene_load_xml", "rtu_scene_clone", "rtu_scene_load_blob", 
                 "rtu_image_free", "rtu_image_width", "rtu_image_height", "rtu_image_pixels", "rtu_image_zbuffer",
                 "rtu_image_zimage", "rtu_image_num_rendered", "rtu_image_is_done", "rtu_image_from_rgbz",
                 "rtu_image_compute_zimg", "rtu_image_save_png", "rtu_image_save_zpng", "rtu_write_png",
-                "rtu_begin_render", "rtu_begin_render_sampled", "rtu_begin_render_paths", "rtu_stop_render", "rtu_render_wait", "rtu_render_gather_kind", "rtu_render_job_free"]
+                "rtu_begin_render", "rtu_begin_render_sampled", "rtu_begin_render_paths", "rtu_stop_render", "rtu_render_wait", "rtu_render_gather_kind", "rtu_render_job_free",
+                "rtu_image_sample_count", "rtu_image_fill_sample_count", "rtu_image_compute_sample_count_img", "rtu_image_sample_count_image",
+                "rtu_image_save_sample_count_png", "rtu_begin_render_adaptive"]
 _sig(host, "rtu_scene_load_xml", _P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
 _sig(host, "rtu_scene_clone", _P, _P)
 _sig(host, "rtu_scene_load_blob", _P, _P, ctypes.c_size_t)
@@ -293,6 +318,13 @@ _sig(host, "rtu_stop_render", None, _P)
 _sig(host, "rtu_render_wait", _I, _P)
 _sig(host, "rtu_render_gather_kind", _I, _P)
 _sig(host, "rtu_render_job_free", None, _P)
+_sig(host, "rtu_image_sample_count", _P, _P)
+_sig(host, "rtu_image_fill_sample_count", None, _P, _P, _I, _I)
+_sig(host, "rtu_image_compute_sample_count_img", _I, _P)
+_sig(host, "rtu_image_sample_count_image", _P, _P)
+_sig(host, "rtu_image_save_sample_count_png", _I, _P, ctypes.c_char_p)
+_sig(host, "rtu_begin_render_adaptive", _P, _P, _P, ctypes.POINTER(_I), _I, _I, _I, ctypes.POINTER(RtuAdaptiveDesc), ctypes.c_char_p, ctypes.c_char_p,
+     ctypes.c_char_p)
 
 
 class Scene:
@@ -444,6 +476,28 @@ class Context:
 
     def render_device(self, frame, d_ptr, stream=None):
         self._check(hip.rtu_render_frame_device(self._h, ctypes.byref(frame), d_ptr, stream))
+
+    def render_adaptive(self, frame, adaptive=None, stats=False):
+        """Adaptive sampling (recipe S / P, frame.samples = the maximum per pixel): returns (rgbz float32 [rows, W, 4],
+        counts uint8 [rows, W] — the samples each pixel took —, stats dict or None). adaptive: RtuAdaptiveDesc (None: the defaults)."""
+        import numpy as np
+        if adaptive is None:
+            adaptive = adaptive_defaults()
+        rows = hip.rtu_shard_rows(ctypes.byref(frame))
+        out = np.empty((rows, frame.width, 4), np.float32)
+        counts = np.empty((rows, frame.width), np.uint8)
+        st = RtuStats() if stats else None
+        self._check(hip.rtu_render_frame_adaptive(self._h, ctypes.byref(frame), ctypes.byref(adaptive), out.ctypes.data, counts.ctypes.data,
+                                                  ctypes.byref(st) if stats else None))
+        return out, counts, (st.as_dict() if stats else None)
+
+    def sample_images(self, frame, first, n):
+        """The images of samples [first, first + n) of the fixed recipe S / P frame: float32 [n, rows, W, 4], what the accumulator adds."""
+        import numpy as np
+        rows = hip.rtu_shard_rows(ctypes.byref(frame))
+        out = np.empty((n, rows, frame.width, 4), np.float32)
+        self._check(hip.rtu_debug_sample_images(self._h, ctypes.byref(frame), first, n, out.ctypes.data))
+        return out
 
     def render_frames_device(self, frames, d_ptr, stream=None):
         """Frames in flight: len(frames) frames of recipe W in one launch sequence, images consecutive at d_ptr."""
@@ -623,6 +677,31 @@ class Image:
         if not p:
             return None
         return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (self.height, self.width)).copy()
+
+    def sample_count(self):
+        import numpy as np
+        p = host.rtu_image_sample_count(self._h)
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (self.height, self.width)).copy()
+
+    def fill_sample_count(self, counts, row0=0):
+        import numpy as np
+        a = np.ascontiguousarray(counts, dtype=np.uint8)
+        host.rtu_image_fill_sample_count(self._h, a.ctypes.data, row0, a.shape[0])
+
+    def compute_sample_count_image(self):
+        """ComputeSampleCountImage: returns smax."""
+        return host.rtu_image_compute_sample_count_img(self._h)
+
+    def sample_count_image(self):
+        import numpy as np
+        p = host.rtu_image_sample_count_image(self._h)
+        if not p:
+            return None
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (self.height, self.width)).copy()
+
+    def save_sample_count(self, path):
+        if host.rtu_image_save_sample_count_png(self._h, path.encode()) != 0:
+            raise RtuError(RTU_ERR_ARG, "cannot write " + path)
 
     def save(self, result_png=None, zbuffer_png=None):
         if result_png and host.rtu_image_save_png(self._h, result_png.encode()) != 0:

@@ -563,14 +563,25 @@ __device__ __forceinline__ void primary_stage1(const KernelArgs& a, uint32_t n_t
     for (uint32_t btile = blockIdx.x * 4u + wave; btile < n_tiles; btile += gridDim.x * 4u) {  // whole wavefronts
         // (two scalar divisions per tile; replacing them by additions and carries from a per-wavefront decomposition of the stride was
         // measured: no faster — six more scalar registers in a kernel that already spills them)
-        const uint32_t sidx = (SMPD || BATD) ? btile / a.tiles_per_image : 0u;  // batched launches: n_tiles = batch x tiles of the image
-        const uint32_t tile = btile - sidx * a.tiles_per_image;
+        uint32_t sidx = (SMPD || BATD) ? btile / a.tiles_per_image : 0u;  // batched launches: n_tiles = batch x tiles of the image
+        uint32_t tile = btile - sidx * a.tiles_per_image;
+        bool lane_on = true;
+        if constexpr (SMPD) {
+            if (a.act_list != nullptr) {
+                // ADAPTIVE sampling (KernelArgs::act_list): n_tiles = batch x act_n list entries {tile, lane mask} of the tiles that still
+                // have a pixel sampling; a pixel that has stopped is an invalid lane — no ray, no frame, no record, no counter
+                sidx = btile / a.act_n;
+                const RTU_CONST uint32_t* ent = as_const(reinterpret_cast<const uint32_t*>(a.act_list)) + 4u * (size_t)(btile - sidx * a.act_n);  // wave-uniform: scalar loads
+                tile = ent[0];
+                lane_on = (((unsigned long long)ent[3] << 32 | ent[2]) >> lane) & 1ull;
+            }
+        }
         const uint32_t band_local = tile / a.tiles_x;
         const uint32_t tx = tile - band_local * a.tiles_x;
         const int x = (int)(tx * 8 + (lane & 7));
         const int ly = (int)(band_local * RTU_BAND_ROWS + (lane >> 3));                                              // row inside the shard
         const int y = (int)((band_local * a.frame.shard_count + a.frame.shard_rank) * RTU_BAND_ROWS + (lane >> 3));  // global row
-        const bool valid = x < a.frame.width && y < a.frame.height;
+        const bool valid = x < a.frame.width && y < a.frame.height && lane_on;
         const uint32_t pix = ((SMPD || BATD) ? sidx * a.batch_pixels : 0u) + (uint32_t)ly * (uint32_t)a.frame.width + (uint32_t)x;
         if (!STATS && !SMPD && !GID && a.occ != nullptr) {
             // TILE OCCUPANCY (k_tile_occ): no pixel of this tile is inside any node's screen rectangle (or marked tile of a mesh's

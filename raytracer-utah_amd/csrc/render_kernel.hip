@@ -122,6 +122,95 @@ __global__ void __launch_bounds__(256) k_resolve(const float4* acc, const uint32
 }
 }  // namespace
 
+// ---- adaptive sampling (rtu_render_frame_adaptive): per pixel s += x, q += x * x in sample order, stop at the first checkpoint ------
+// n = min_samples + k * increment < max_samples with (q - s * m) / (n - 1) <= target for r, g and b (m = s / n); rtu_render.h
+namespace {
+__global__ void __launch_bounds__(64) k_adaptive_init(uint4* list, uint32_t tiles, uint32_t tiles_x, int width, int height, int shard_rank, int shard_count) {
+    const uint32_t tile = blockIdx.x * 64u + threadIdx.x;
+    if (tile >= tiles) return;
+    const uint32_t band_local = tile / tiles_x, tx = tile - band_local * tiles_x;
+    const int x0 = (int)(tx * 8u), y0 = (int)((band_local * (uint32_t)shard_count + (uint32_t)shard_rank) * RTU_BAND_ROWS);
+    unsigned long long m = 0;  // the lanes of primary_stage1 that lie inside the image
+    for (int l = 0; l < 64; l++)
+        if (x0 + (l & 7) < width && y0 + (l >> 3) < height) m |= 1ull << l;
+    list[tile] = make_uint4(tile, 0u, (uint32_t)m, (uint32_t)(m >> 32));
+}
+
+__device__ __forceinline__ bool adaptive_passes(const float4& s, const float4& q, uint32_t n, float target) {
+    if (n == 1u) return target == __builtin_inff();  // var = +inf
+    const float fn = (float)n, fn1 = (float)(n - 1u);
+    // every operation rounded on its own (__f*_rn: no contraction), in the order of the statement in rtu_render.h
+    const float vr = __fsub_rn(q.x, __fmul_rn(s.x, s.x / fn)) / fn1;
+    const float vg = __fsub_rn(q.y, __fmul_rn(s.y, s.y / fn)) / fn1;
+    const float vb = __fsub_rn(q.z, __fmul_rn(s.z, s.z / fn)) / fn1;
+    return vr <= target && vg <= target && vb <= target;
+}
+
+// one wavefront per entry of the active-tile list, one lane per pixel of its 8x8 tile
+__global__ void __launch_bounds__(256) k_adaptive_step(AdaptiveStep p) {
+    const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (e >= p.n_in) return;
+    if (p.skip_if[0] | p.skip_if[1] | p.skip_if_side[0] | p.skip_if_side[1]) return;  // incomplete batch: rendered again, then added
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint4 ent = p.list_in[e];
+    const bool on = (((unsigned long long)ent.w << 32 | ent.z) >> lane) & 1ull;
+    const uint32_t band_local = ent.x / p.tiles_x, tx = ent.x - band_local * p.tiles_x;
+    const uint32_t pix = (band_local * RTU_BAND_ROWS + (lane >> 3)) * (uint32_t)p.width + tx * 8u + (lane & 7u);
+    bool more = false;
+    if (on) {
+        float4 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = s;
+        uint32_t h = 0, n = 0;
+        if (!p.first) { s = p.acc[pix]; q = p.sq[pix]; h = p.hits[pix]; n = p.counts[pix]; }
+        more = true;
+        for (uint32_t b = 0; b < p.batch && more; b++) {  // the samples of the batch in their order, up to the pixel's stop
+            const float4 v = p.samples[(size_t)b * p.pixels + pix];
+            s.x = __fadd_rn(s.x, v.x); s.y = __fadd_rn(s.y, v.y); s.z = __fadd_rn(s.z, v.z);                   // k_accumulate's sum
+            q.x = __fadd_rn(q.x, __fmul_rn(v.x, v.x)); q.y = __fadd_rn(q.y, __fmul_rn(v.y, v.y)); q.z = __fadd_rn(q.z, __fmul_rn(v.z, v.z));
+            if (v.w != RTU_BIGFLOAT) { s.w += v.w; h++; }
+            n++;
+            if (n >= p.max_samples) more = false;
+            else if (n >= p.min_samples && (n - p.min_samples) % p.increment == 0u && adaptive_passes(s, q, n, p.target)) more = false;
+        }
+        p.acc[pix] = s;
+        p.sq[pix] = q;
+        p.hits[pix] = h;
+        p.counts[pix] = (uint8_t)n;
+    }
+    const unsigned long long m = __ballot(more);
+    if (lane == 0u && m) {  // one append per wavefront
+        const uint32_t k = atomicAdd(p.n_out, 1u);
+        p.list_out[k] = make_uint4(ent.x, 0u, (uint32_t)m, (uint32_t)(m >> 32));
+    }
+}
+
+__global__ void __launch_bounds__(256) k_resolve_counts(const float4* acc, const uint32_t* hits, const uint8_t* counts, float4* out, uint8_t* counts_out, uint32_t pixels) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= pixels) return;
+    const float4 s = acc[i];
+    const uint32_t h = hits[i];
+    const uint8_t c = counts[i];
+    const float S = (float)c;
+    out[i] = make_float4(s.x / S, s.y / S, s.z / S, h ? s.w / (float)h : RTU_BIGFLOAT);
+    if (counts_out) counts_out[i] = c;
+}
+}  // namespace
+
+int rtu_launch_adaptive_init(uint4* list, uint32_t tiles, uint32_t tiles_x, int width, int height, int shard_rank, int shard_count, hipStream_t stream) {
+    if (tiles == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_adaptive_init, dim3((tiles + 63u) / 64u), dim3(64), 0, stream, list, tiles, tiles_x, width, height, shard_rank, shard_count);
+    return (int)hipGetLastError();
+}
+int rtu_launch_adaptive_step(const AdaptiveStep& p, hipStream_t stream) {
+    if (p.n_in == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_adaptive_step, dim3((p.n_in + 3u) / 4u), dim3(256), 0, stream, p);
+    return (int)hipGetLastError();
+}
+int rtu_launch_resolve_counts(const float4* acc, const uint32_t* hits, const uint8_t* counts, float4* out, uint8_t* counts_out, uint32_t pixels, hipStream_t stream) {
+    if (pixels == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_resolve_counts, dim3((pixels + 255u) / 256u), dim3(256), 0, stream, acc, hits, counts, out, counts_out, pixels);
+    return (int)hipGetLastError();
+}
+
 // ---- RenderImage content on the device: Color24 pixels + float z (RenderFunctions.cpp:152-160, cyColor.h:226,245) ----
 namespace {
 __device__ __forceinline__ uint8_t float_to_byte(float r) {  // Color24(Color): Clamp(int(c * 255)), cvttss2si semantics

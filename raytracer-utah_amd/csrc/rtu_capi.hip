@@ -59,6 +59,13 @@ struct RtuContext {
     uint32_t* acc_hits = nullptr;
     size_t    acc_pixels = 0;
     float4*   sample_buf = nullptr;      // the images of one batch of samples, [sample][pixel]
+    float4*   ad_sq = nullptr;           // adaptive sampling (rtu_render_frame_adaptive): sums of squares and sample counts per pixel
+    uint8_t*  ad_counts = nullptr;
+    size_t    ad_pixels = 0;
+    uint4*    ad_list[2] = {};           // ... the active-tile lists {tile, 0, lane mask}, double-buffered, and their lengths
+    size_t    ad_list_cap = 0;           // entries of each
+    uint32_t* ad_n = nullptr;            // [2] on the device
+    uint32_t* ad_n_host = nullptr;       // pinned: the length of the list the next batch walks
     size_t    sample_buf_pixels = 0;
     float4*   gi_h = nullptr;            // recipe P: chain records [5 depths][4][chains], results [2][chains]
     float4*   gi_res = nullptr;
@@ -1012,8 +1019,11 @@ float halton(int index, int base) {
 // recipe S into d_out as [sample][pixel of the shard].
 // frames_batch: `batch` frames of recipe W with their own cameras (frame == &frames_batch[0]).
 // gi_mode RTU_LAUNCH_CHAIN / RTU_LAUNCH_SHADE: one step of recipe P at chain depth gi_depth (render_sampled).
+// adaptive: a launch of an adaptive frame (hint keys of its own: its shape changes every batch); act_list / act_n: the active-tile list
+// its primary phase walks (KernelArgs::act_list), nullptr for every tile (act_n then only keys the hints).
 int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, int sample_index = 0, int batch = 1,
-           const RtuFrameDesc* frames_batch = nullptr, int gi_mode = RTU_LAUNCH_ALL, int gi_depth = 0) {
+           const RtuFrameDesc* frames_batch = nullptr, int gi_mode = RTU_LAUNCH_ALL, int gi_depth = 0, bool adaptive = false,
+           const uint4* act_list = nullptr, uint32_t act_n = 0) {
     uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
     uint32_t bands = (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
     uint32_t n_tiles = tiles_x * bands * (uint32_t)batch;
@@ -1033,6 +1043,10 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
             RTU_HIP(ctx, hipMalloc((void**)&ctx->gi_res, chains * 2 * sizeof(float4)));
             ctx->gi_chains = chains;
         }
+        // adaptive: the chains of stopped pixels are not traced; a zero depth-0 record is "no hit" to every later depth, k_gi_roots
+        // and k_gi_final
+        if (act_list && gi_mode == RTU_LAUNCH_CHAIN && gi_depth == 0)
+            RTU_HIP(ctx, hipMemsetAsync(ctx->gi_h + chains, 0, chains * sizeof(float4), stream));
     }
     const int stats = frame->collect_stats;  // 0 fast, 1 reference counting, 2 touched bytes of the fast variant
     if (stats && zero_counters) {
@@ -1096,7 +1110,11 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     a.n_meshes = ctx->n_meshes;
     // the cut level for k_tail: what a launch of the same shape showed last time (a hint: any value renders the same image, a
     // wrong one is refused on the device and reported like an overflow); rtu_debug_tail_from overrides it once
-    const uint64_t tail_key = ((uint64_t)n_tiles << 8) | (uint64_t)((frame->samples ? 2 : 0) | (frames_batch ? 4 : 0) | (gi ? 8 : 0));
+    // (adaptive frames: keys of their own — the fixed path's hints are not theirs — by the power of two of the tiles still sampling,
+    // so that a batch learns from batches of about its size and the maps stay small)
+    const uint32_t act_tiles = act_n ? act_n * (uint32_t)batch : n_tiles;
+    const uint64_t tail_key = adaptive ? ((uint64_t)(32 - __builtin_clz(act_tiles | 1u)) << 8) | (uint64_t)(16 | 2 | (gi ? 8 : 0))
+                                       : ((uint64_t)n_tiles << 8) | (uint64_t)((frame->samples ? 2 : 0) | (frames_batch ? 4 : 0) | (gi ? 8 : 0));
     int hint = RTU_MAX_LEVELS;
     bool forced = false;
     if (ctx->tail_hint != 0) { hint = ctx->tail_hint; ctx->tail_hint = 0; forced = true; }
@@ -1150,6 +1168,9 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         a.gi_depth = (uint32_t)gi_depth;
         a.gi_total = pixels * (uint32_t)batch;
     }
+    const uint32_t launch_tiles = act_list ? act_n * (uint32_t)batch : n_tiles;
+    a.act_list = act_list;
+    a.act_n = act_n;
     // side mode (rtu_device.h KernelArgs::fcnt0): recipe W's fast variant on a scene with meshes, unless this launch shape has shown that
     // its stage 2 makes more frames than a k_tail launch takes (rtu_debug_flags 8192: never — results must not change)
     // Only where it pays and cannot surprise: every mesh node's material is childless (stage 2's frames are then the rare hits whose
@@ -1200,14 +1221,14 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         probe.ev1 = ctx->probe_ev[2 * ctx->probe_used + 1];
     }
     if (gi_mode == RTU_LAUNCH_SHADE && gi_depth == 0) {
-        hipError_t e0 = (hipError_t)rtu_launch_frame(a, n_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
+        hipError_t e0 = (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
         if (probing && probe_recorded) ctx->probe_used++;
         if (e0 != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e0));
         e0 = (hipError_t)rtu_launch_gi_final(a, stream);  // harmless if this step has to be repeated: it only reads the results
         if (e0 != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e0));
         return RTU_OK;
     }
-    hipError_t e = (hipError_t)rtu_launch_frame(a, n_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
+    hipError_t e = (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
     if (probing && probe_recorded) ctx->probe_used++;
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     return RTU_OK;
@@ -1320,16 +1341,56 @@ int check_overflow(RtuContext* ctx, bool* overflow) {
     return RTU_OK;
 }
 
+// What render_sampled does besides the fixed-count mean of frame->samples samples.
+struct SampledRun {
+    const RtuAdaptiveDesc* ad = nullptr;  // adaptive sampling (validated): stop every pixel at its first checkpoint that passes
+    uint8_t* d_counts = nullptr;          // ... and write its count here (may be nullptr)
+    float*   h_dump = nullptr;            // rtu_debug_sample_images: copy the images of samples [first, end) here, accumulate nothing
+    int      first = 0, end = 0;
+};
+
+int ensure_adaptive(RtuContext* ctx, size_t pixels, size_t tiles) {  // grow-only, like acc
+    if (pixels > ctx->ad_pixels) {
+        if (ctx->ad_sq) (void)hipFree(ctx->ad_sq);
+        if (ctx->ad_counts) (void)hipFree(ctx->ad_counts);
+        ctx->ad_sq = nullptr;
+        ctx->ad_counts = nullptr;
+        ctx->ad_pixels = 0;
+        RTU_HIP(ctx, hipMalloc((void**)&ctx->ad_sq, pixels * sizeof(float4)));
+        RTU_HIP(ctx, hipMalloc((void**)&ctx->ad_counts, pixels));
+        ctx->ad_pixels = pixels;
+    }
+    if (tiles > ctx->ad_list_cap) {
+        for (uint4*& l : ctx->ad_list) {
+            if (l) (void)hipFree(l);
+            l = nullptr;
+        }
+        ctx->ad_list_cap = 0;
+        for (uint4*& l : ctx->ad_list) RTU_HIP(ctx, hipMalloc((void**)&l, tiles * sizeof(uint4)));
+        ctx->ad_list_cap = tiles;
+    }
+    if (!ctx->ad_n) RTU_HIP(ctx, hipMalloc((void**)&ctx->ad_n, 2 * sizeof(uint32_t)));
+    if (!ctx->ad_n_host) RTU_HIP(ctx, hipHostMalloc((void**)&ctx->ad_n_host, sizeof(uint32_t), hipHostMallocDefault));
+    return RTU_OK;
+}
+
 // Recipe S: one launch sequence per batch of samples (as many as fit 2^25 pixels, at most RTU_MAX_BATCH),
 // each checked for frame-capacity overflow before its images are added to the accumulators in sample
 // order; the mean goes to d_out. Synchronises per batch.
-int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters) {
+// Adaptive (run->ad): the primary phase of a batch walks the list of tiles that still have a pixel sampling; k_adaptive_step,
+// queued behind the batch and ahead of the batch's synchronisation, adds the samples of those pixels up to their stop and writes
+// the next list, whose length the host reads in that same synchronisation. A batch that has to be rendered again (capacity) is
+// not added (the step kernel sees the overflow flags the host will see).
+int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, const SampledRun* run = nullptr) {
     const size_t pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
     if (pixels == 0) return RTU_OK;
     const bool gi = frame->gather_bounces != 0;
+    const RtuAdaptiveDesc* ad = run ? run->ad : nullptr;
+    float* const h_dump = run ? run->h_dump : nullptr;
     static const int kGiLog2 = [] { const char* e = getenv("RTU_GI_BATCH_LOG2"); return e ? atoi(e) : 25; }();  // tuning knob (23 / 24 / 25: 138.2 / 131.9 / 130.6 ms for config 5 at 64 spp)
     int batch = (int)(((size_t)1 << (gi ? kGiLog2 : 25)) / pixels);  // recipe P keeps 22 float4 per chain and two roots per chain hit (a larger batch buys nothing: measured)
     if (batch > RTU_MAX_BATCH) batch = RTU_MAX_BATCH;
+    if (ad && ad->max_batch > 0 && batch > ad->max_batch) batch = ad->max_batch;
     if (batch > frame->samples) batch = frame->samples;
     if (batch < 1) batch = 1;
     if (pixels > ctx->acc_pixels) {
@@ -1349,14 +1410,64 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
         RTU_HIP(ctx, hipMalloc((void**)&ctx->sample_buf, pixels * (size_t)batch * sizeof(float4)));
         ctx->sample_buf_pixels = pixels * (size_t)batch;
     }
+    const uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
+    const uint32_t tiles = tiles_x * (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
+    if (ad) {
+        int rc = ensure_adaptive(ctx, pixels, tiles);
+        if (rc != RTU_OK) return rc;
+    }
+    int cur = 0;          // adaptive: the list the next batch walks ...
+    uint32_t n_act = 0;   // ... and its length
+    auto adaptive_start = [&]() -> int {  // (again after the counting variant starts over)
+        cur = 0;
+        n_act = tiles;
+        hipError_t e = (hipError_t)rtu_launch_adaptive_init(ctx->ad_list[0], tiles, tiles_x, frame->width, frame->height, frame->shard_rank, frame->shard_count, stream);
+        return e == hipSuccess ? RTU_OK : fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    };
+    auto adaptive_step = [&](int i, int nb) -> int {
+        RTU_HIP(ctx, hipMemsetAsync(ctx->ad_n + (cur ^ 1), 0, sizeof(uint32_t), stream));
+        AdaptiveStep p;
+        p.samples = ctx->sample_buf;
+        p.acc = ctx->acc;
+        p.sq = ctx->ad_sq;
+        p.hits = ctx->acc_hits;
+        p.counts = ctx->ad_counts;
+        p.list_in = ctx->ad_list[cur];
+        p.list_out = ctx->ad_list[cur ^ 1];
+        p.n_out = ctx->ad_n + (cur ^ 1);
+        p.skip_if = &ctx->fcnt->overflow;
+        p.skip_if_side = &ctx->fcnt_side->overflow;
+        p.n_in = n_act;
+        p.batch = (uint32_t)nb;
+        p.first = i == 0 ? 1u : 0u;
+        p.pixels = (uint32_t)pixels;
+        p.width = frame->width;
+        p.height = frame->height;
+        p.shard_rank = frame->shard_rank;
+        p.shard_count = frame->shard_count;
+        p.tiles_x = tiles_x;
+        p.min_samples = (uint32_t)ad->min_samples;
+        p.increment = (uint32_t)ad->increment;
+        p.max_samples = (uint32_t)frame->samples;
+        p.target = ad->target_variance;
+        hipError_t e = (hipError_t)rtu_launch_adaptive_step(p, stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->ad_n_host, ctx->ad_n + (cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        return RTU_OK;
+    };
+    const uint4* no_list = nullptr;
+    const int i_begin = h_dump ? run->first : 0, i_end = h_dump ? run->end : frame->samples;
     int rounds = 0;
-    for (int i = 0; i < frame->samples; i += batch) {
+    for (int i = i_begin; i < i_end; i += batch) {
         if (ctx->cancel && *ctx->cancel) return fail(ctx, RTU_ERR_CANCELLED, "cancelled after %d of %d samples", i, frame->samples);  // StopRender(), main.cpp:70-72
-        int nb = frame->samples - i < batch ? frame->samples - i : batch;
+        int nb = i_end - i < batch ? i_end - i : batch;
         while (!gi) {
-            nb = frame->samples - i < batch ? frame->samples - i : batch;  // (i may have been reset below)
-            int rc = launch(ctx, frame, ctx->sample_buf, stream, zero_counters && i == 0, i, nb);
+            nb = i_end - i < batch ? i_end - i : batch;  // (i may have been reset below)
+            int rc;
+            if (ad && i == 0 && (rc = adaptive_start()) != RTU_OK) return rc;
+            rc = launch(ctx, frame, ctx->sample_buf, stream, zero_counters && i == 0, i, nb, nullptr, RTU_LAUNCH_ALL, 0, ad != nullptr, ad ? ctx->ad_list[cur] : no_list, n_act);
             if (rc != RTU_OK) return rc;
+            if (ad && (rc = adaptive_step(i, nb)) != RTU_OK) return rc;
             RTU_HIP(ctx, hipStreamSynchronize(stream));
             bool overflow = false;
             if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
@@ -1365,10 +1476,14 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
             if (frame->collect_stats) { i = 0; zero_counters = true; }  // the counters of the dropped pass are in the totals: start again
         }
         if (gi) {
+            int rc;
+            if (ad && i == 0 && (rc = adaptive_start()) != RTU_OK) return rc;
             // recipe P: the chain of gather rays first (depth 0 = the primary ray), then the Shade() trees from the
             // deepest hit up — each depth's AmbientLight needs the results of the depth below (k_gi_roots)
+            // (adaptive: depth 0 walks the active tiles; the deeper depths run over every chain, a stopped one ends at once)
             for (int k = 0; k <= RTU_GI_BOUNCES; k++) {
-                int rc = launch(ctx, frame, ctx->sample_buf, stream, zero_counters && i == 0 && k == 0, i, nb, nullptr, RTU_LAUNCH_CHAIN, k);
+                rc = launch(ctx, frame, ctx->sample_buf, stream, zero_counters && i == 0 && k == 0, i, nb, nullptr, RTU_LAUNCH_CHAIN, k, ad != nullptr,
+                            ad && k == 0 ? ctx->ad_list[cur] : no_list, ad ? n_act : 0u);
                 if (rc != RTU_OK) return rc;
             }
             // the five shading steps are queued back to back; ONE host synchronisation per batch reads the (sticky) overflow
@@ -1376,23 +1491,52 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
             // grown capacities: its chain records do not depend on them.
             for (;;) {
                 for (int k = RTU_GI_BOUNCES; k >= 0; k--) {
-                    int rc = launch(ctx, frame, ctx->sample_buf, stream, false, i, nb, nullptr, RTU_LAUNCH_SHADE, k);
+                    rc = launch(ctx, frame, ctx->sample_buf, stream, false, i, nb, nullptr, RTU_LAUNCH_SHADE, k, ad != nullptr, no_list, ad ? n_act : 0u);
                     if (rc != RTU_OK) return rc;
                 }
+                if (ad && (rc = adaptive_step(i, nb)) != RTU_OK) return rc;
                 RTU_HIP(ctx, hipStreamSynchronize(stream));
                 bool overflow = false;
-                int rc = check_overflow(ctx, &overflow);
+                rc = check_overflow(ctx, &overflow);
                 if (rc != RTU_OK) return rc;
                 if (!overflow) break;
                 if (frame->collect_stats) return fail(ctx, RTU_ERR_CAPACITY, "recipe P with counters: frame records ran out; render once without counters first");
                 if (++rounds > 8 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", rounds);
             }
         }
+        if (ad) {
+            cur ^= 1;
+            n_act = *ctx->ad_n_host;  // (read in the batch's synchronisation)
+            if (n_act == 0) break;    // every pixel has stopped
+            continue;
+        }
+        if (h_dump) {
+            RTU_HIP(ctx, hipMemcpyAsync(h_dump + (size_t)(i - i_begin) * pixels * 4u, ctx->sample_buf, (size_t)nb * pixels * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            RTU_HIP(ctx, hipStreamSynchronize(stream));
+            continue;
+        }
         hipError_t e = (hipError_t)rtu_launch_accumulate(ctx->sample_buf, (uint32_t)nb, ctx->acc, ctx->acc_hits, (uint32_t)pixels, i == 0, stream);
         if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     }
-    hipError_t e = (hipError_t)rtu_launch_resolve(ctx->acc, ctx->acc_hits, d_out, (uint32_t)pixels, (uint32_t)frame->samples, stream);
+    if (h_dump) return RTU_OK;
+    hipError_t e = ad ? (hipError_t)rtu_launch_resolve_counts(ctx->acc, ctx->acc_hits, ctx->ad_counts, d_out, run->d_counts, (uint32_t)pixels, stream)
+                      : (hipError_t)rtu_launch_resolve(ctx->acc, ctx->acc_hits, d_out, (uint32_t)pixels, (uint32_t)frame->samples, stream);
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+// The arguments of an adaptive frame (rtu_render.h): a recipe S / P frame with 1 .. 255 samples and a valid RtuAdaptiveDesc.
+int check_adaptive(RtuContext* ctx, const RtuFrameDesc* f, const RtuAdaptiveDesc* ad) {
+    if (!f) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
+    if (f->samples < 1 || f->samples > 255) return fail(ctx, RTU_ERR_ARG, "an adaptive frame has 1 .. 255 samples per pixel at most (frame.samples)");
+    int rc = check_frame(ctx, f);
+    if (rc != RTU_OK) return rc;
+    if (!ad) return fail(ctx, RTU_ERR_ARG, "adaptive is NULL");
+    if (ad->min_samples < 1 || ad->min_samples > f->samples) return fail(ctx, RTU_ERR_ARG, "min_samples is 1 .. frame.samples");
+    if (ad->increment < 1) return fail(ctx, RTU_ERR_ARG, "increment is >= 1");
+    if (!(ad->target_variance >= 0.0f)) return fail(ctx, RTU_ERR_ARG, "target_variance is >= 0 (or +inf)");
+    if (ad->max_batch < 0 || ad->max_batch > RTU_MAX_BATCH) return fail(ctx, RTU_ERR_ARG, "max_batch is 0 .. %d", RTU_MAX_BATCH);
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
     return RTU_OK;
 }
 
@@ -1484,6 +1628,12 @@ void rtu_destroy_context(RtuContext* ctx) {
     if (ctx->acc) (void)hipFree(ctx->acc);
     if (ctx->acc_hits) (void)hipFree(ctx->acc_hits);
     if (ctx->sample_buf) (void)hipFree(ctx->sample_buf);
+    if (ctx->ad_sq) (void)hipFree(ctx->ad_sq);
+    if (ctx->ad_counts) (void)hipFree(ctx->ad_counts);
+    for (uint4* l : ctx->ad_list)
+        if (l) (void)hipFree(l);
+    if (ctx->ad_n) (void)hipFree(ctx->ad_n);
+    if (ctx->ad_n_host) (void)hipHostFree(ctx->ad_n_host);
     if (ctx->gi_h) (void)hipFree(ctx->gi_h);
     if (ctx->gi_res) (void)hipFree(ctx->gi_res);
     if (ctx->counters) (void)hipFree(ctx->counters);
@@ -2009,6 +2159,82 @@ int rtu_render_frame(RtuContext* ctx, const RtuFrameDesc* frame, float* h_rgbz, 
     if (bytes) RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->fb, bytes, hipMemcpyDeviceToHost));
     if (stats) return rtu_get_stats(ctx, stats);
     return RTU_OK;
+}
+
+int rtu_adaptive_defaults(RtuAdaptiveDesc* out) {
+    if (!out) return RTU_ERR_ARG;
+    out->min_samples = 8;           // minSampleSize, RenderFunctions.cpp:27
+    out->increment = 1;             // sampleIncrement, :29
+    out->target_variance = 0.005f;  // targetVariance, :28
+    out->max_batch = 0;
+    return RTU_OK;
+}
+
+namespace {
+int ensure_fb(RtuContext* ctx, size_t bytes) {
+    if (bytes > ctx->fb_bytes) {
+        if (ctx->fb) (void)hipFree(ctx->fb);
+        ctx->fb = nullptr;
+        ctx->fb_bytes = 0;
+        RTU_HIP(ctx, hipMalloc((void**)&ctx->fb, bytes));
+        ctx->fb_bytes = bytes;
+    }
+    return RTU_OK;
+}
+}  // namespace
+
+int rtu_render_frame_adaptive_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, void* d_rgbz, void* d_counts,
+                                     void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = check_adaptive(ctx, frame, adaptive);
+    if (rc != RTU_OK) return rc;
+    if (!d_rgbz && rtu_shard_rows(frame) > 0) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    SampledRun run;
+    run.ad = adaptive;
+    run.d_counts = (uint8_t*)d_counts;
+    return render_sampled(ctx, frame, (float4*)d_rgbz, (hipStream_t)hip_stream, true, &run);
+}
+
+int rtu_render_frame_adaptive(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, float* h_rgbz, uint8_t* h_counts,
+                              RtuStats* stats) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = check_adaptive(ctx, frame, adaptive);
+    if (rc != RTU_OK) return rc;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
+    if ((rc = ensure_fb(ctx, pixels * sizeof(float4))) != RTU_OK) return rc;
+    RtuFrameDesc f = *frame;
+    if (stats) f.collect_stats = 1;
+    SampledRun run;
+    run.ad = adaptive;
+    if ((rc = render_sampled(ctx, &f, ctx->fb, ctx->stream, true, &run)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (pixels) {
+        RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->fb, pixels * sizeof(float4), hipMemcpyDeviceToHost));
+        if (h_counts) RTU_HIP(ctx, hipMemcpy(h_counts, ctx->ad_counts, pixels, hipMemcpyDeviceToHost));
+    }
+    if (stats) return rtu_get_stats(ctx, stats);
+    return RTU_OK;
+}
+
+int rtu_debug_sample_images(RtuContext* ctx, const RtuFrameDesc* frame, int first, int n, float* h_out) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (frame && frame->samples < 1) return fail(ctx, RTU_ERR_ARG, "a recipe S / P frame (samples >= 1)");
+    int rc = check_frame(ctx, frame);
+    if (rc != RTU_OK) return rc;
+    if (first < 0 || n < 1 || first > frame->samples - n) return fail(ctx, RTU_ERR_ARG, "samples [first, first + n) must lie in [0, frame.samples)");
+    if (!h_out) return fail(ctx, RTU_ERR_ARG, "h_out is NULL");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RtuFrameDesc f = *frame;
+    f.collect_stats = 0;
+    SampledRun run;
+    run.h_dump = h_out;
+    run.first = first;
+    run.end = first + n;
+    return render_sampled(ctx, &f, nullptr, ctx->stream, true, &run);
 }
 
 int rtu_frame_status(RtuContext* ctx) {

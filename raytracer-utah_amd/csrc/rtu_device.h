@@ -183,7 +183,7 @@ struct DevScene {
 // children become frames of level L+1, and results are combined bottom-up in the
 // reference's exact term order.
 #define RTU_MAX_LEVELS        (RTU_MAX_BOUNCE + 1)
-#define RTU_MAX_BATCH 16          // samples of recipe S rendered by one launch sequence
+// RTU_MAX_BATCH (rtu_render.h): samples of recipe S rendered by one launch sequence
 #define RTU_MAX_FRAME_BATCH 128   // frames of recipe W rendered by one launch sequence (== RTU_MAX_FRAMES_IN_FLIGHT)
 #define RTU_MAX_SHADOW_LIGHTS 13  // non-ambient lights (a ray id keeps 4 bits for lights + 3 secondary slots); more => RTU_ERR_UNSUPPORTED
 
@@ -351,6 +351,11 @@ struct KernelArgs {
     // a batch of FRAMES of recipe W (rtu_render_frames_device): the same index space, one camera per frame
     uint32_t     frame_batch;       // 0: no
     const BatchCam* cam;            // [batch] in device memory (copied there on the launch stream, ahead of the kernels)
+    // ADAPTIVE sampling (rtu_render_frame_adaptive, recipes S / P): the tiles that still have a pixel sampling, {tile of the shard, 0,
+    // lane mask low, high} (k_adaptive_step); the primary phase walks batch x act_n entries instead of batch x tiles_per_image and
+    // treats a lane outside the mask as outside the image. nullptr: every tile, every pixel (the fixed-count path)
+    const uint4* act_list;
+    uint32_t     act_n, pad_act;
 };
 
 // Enqueue one frame (primary pass, then per level: trace, consume; then combine
@@ -376,6 +381,28 @@ int rtu_launch_gi_final(const KernelArgs& args, hipStream_t stream);
 // recipe S: add one sample's image to the accumulators / write the mean
 int rtu_launch_accumulate(const float4* samples, uint32_t batch, float4* acc, uint32_t* hits, uint32_t pixels, bool first, hipStream_t stream);
 int rtu_launch_resolve(const float4* acc, const uint32_t* hits, float4* out, uint32_t pixels, uint32_t samples, hipStream_t stream);
+// adaptive sampling (render_kernel.hip): the first active-tile list of a shard (every tile, its in-image lanes); one batch of samples
+// added per pixel of the listed tiles up to the first checkpoint that passes, the tiles still sampling appended to list_out (count in
+// *n_out, which must be zero); the mean over each pixel's own count
+struct AdaptiveStep {
+    const float4* samples;          // [batch][pixel of the shard]
+    float4* acc;                    // rgb sum, z sum
+    float4* sq;                     // sums of squares (rgb)
+    uint32_t* hits;
+    uint8_t* counts;
+    const uint4* list_in;
+    uint4* list_out;
+    uint32_t* n_out;
+    const uint32_t* skip_if;        // FrameCounters::overflow, tail_declined: a batch the host will render again changes nothing
+    const uint32_t* skip_if_side;
+    uint32_t n_in, batch, first, pixels;
+    int32_t width, height, shard_rank, shard_count;
+    uint32_t tiles_x, min_samples, increment, max_samples;
+    float target;
+};
+int rtu_launch_adaptive_init(uint4* list, uint32_t tiles, uint32_t tiles_x, int width, int height, int shard_rank, int shard_count, hipStream_t stream);
+int rtu_launch_adaptive_step(const AdaptiveStep& p, hipStream_t stream);
+int rtu_launch_resolve_counts(const float4* acc, const uint32_t* hits, const uint8_t* counts, float4* out, uint8_t* counts_out, uint32_t pixels, hipStream_t stream);
 
 // gamma + Color24 + z of a float4 image: the content of the reference's RenderImage
 int rtu_launch_pack_image(const float4* rgbz, unsigned long long pixels, float* z_out, unsigned char* rgb_out, hipStream_t stream);

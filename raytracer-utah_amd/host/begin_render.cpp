@@ -65,9 +65,89 @@ void run_job(RtuRenderJob* job, const RtuSceneDesc* desc, RtuImage* img, std::ve
     job->result.store(rc);
 }
 
+// Adaptive sampling (rtu_begin_render_adaptive): one context per listed device, shard r of n on the r-th, each on a host thread of its
+// own (rtu_render_frame_adaptive is synchronous); then the rows and counts of every shard go into the image, and main.cpp:59-63.
+void run_adaptive_job(RtuRenderJob* job, const RtuSceneDesc* desc, RtuImage* img, std::vector<int> devices, int samples, int gather_bounces,
+                      RtuAdaptiveDesc ad, std::string result_png, std::string zbuffer_png, std::string samplecount_png) {
+    const int W = rtu_image_width(img), H = rtu_image_height(img), n = (int)devices.size();
+    RtuFrameDesc frame;
+    int rc = rtu_frame_setup(&desc->camera, W, H, &frame);
+    if (rc != RTU_OK) {
+        job->error = rtu_error_string(rc);
+        job->result.store(rc);
+        return;
+    }
+    frame.samples = samples;
+    frame.gather_bounces = gather_bounces;
+    frame.shard_count = n;
+    std::vector<RtuFrameDesc> frames(n, frame);
+    std::vector<std::vector<float>> rgbz(n);
+    std::vector<std::vector<uint8_t>> counts(n);
+    std::vector<int> rcs(n, RTU_OK);
+    std::vector<std::string> errors(n);
+    std::vector<std::thread> workers;
+    for (int r = 0; r < n; r++) {
+        frames[r].shard_rank = r;
+        const size_t pixels = (size_t)rtu_shard_rows(&frames[r]) * (size_t)W;
+        rgbz[r].resize(pixels * 4);
+        counts[r].resize(pixels);
+        workers.emplace_back([&, r]() {
+            int e = RTU_OK;
+            RtuContext* ctx = rtu_create_context(devices[r], &e);
+            if (!ctx) { rcs[r] = e != RTU_OK ? e : RTU_ERR_HIP; errors[r] = rtu_error_string(rcs[r]); return; }
+            e = rtu_set_cancel_flag(ctx, &job->cancel);
+            if (e == RTU_OK) e = rtu_upload_scene(ctx, desc);
+            if (e == RTU_OK) e = rtu_render_frame_adaptive(ctx, &frames[r], &ad, rgbz[r].data(), counts[r].data(), nullptr);
+            if (e != RTU_OK) errors[r] = rtu_last_error(ctx);
+            rcs[r] = e;
+            rtu_destroy_context(ctx);
+        });
+    }
+    for (std::thread& t : workers) t.join();
+    for (int r = 0; r < n && rc == RTU_OK; r++)
+        if (rcs[r] != RTU_OK) { rc = rcs[r]; job->error = errors[r]; }
+    if (rc == RTU_OK) {
+        for (int r = 0; r < n; r++)
+            for (int lr = 0; lr < rtu_shard_rows(&frames[r]); lr++) {
+                const int row = rtu_shard_global_row(&frames[r], lr);
+                rtu_image_from_rgbz(img, rgbz[r].data() + (size_t)lr * W * 4, row, 1);
+                rtu_image_fill_sample_count(img, counts[r].data() + (size_t)lr * W, row, 1);
+            }
+        job->gather_kind.store(n == 1 ? 1 : 2);
+        // main.cpp:59-63 (the last two lines are commented out in the reference)
+        if (!result_png.empty() && rtu_image_save_png(img, result_png.c_str()) != 0) { rc = RTU_ERR_ARG; job->error = "cannot write " + result_png; }
+        rtu_image_compute_zimg(img);
+        if (rc == RTU_OK && !zbuffer_png.empty() && rtu_image_save_zpng(img, zbuffer_png.c_str()) != 0) { rc = RTU_ERR_ARG; job->error = "cannot write " + zbuffer_png; }
+        rtu_image_compute_sample_count_img(img);
+        if (rc == RTU_OK && !samplecount_png.empty() && rtu_image_save_sample_count_png(img, samplecount_png.c_str()) != 0) {
+            rc = RTU_ERR_ARG;
+            job->error = "cannot write " + samplecount_png;
+        }
+    }
+    job->result.store(rc);
+}
+
 }  // namespace
 
 extern "C" {
+
+RtuRenderJob* rtu_begin_render_adaptive(const RtuScene* scene, RtuImage* img, const int* device_ids, int n_devices, int samples,
+                                        int gather_bounces, const RtuAdaptiveDesc* adaptive, const char* result_png,
+                                        const char* zbuffer_png, const char* samplecount_png) {
+    if (!scene || !img || !device_ids || n_devices < 1 || samples < 1 || samples > 255 || (gather_bounces != 0 && gather_bounces != 4)) {
+        rtu::set_error("rtu_begin_render_adaptive: bad arguments");
+        return nullptr;
+    }
+    RtuAdaptiveDesc ad;
+    if (adaptive) ad = *adaptive;
+    else rtu_adaptive_defaults(&ad);
+    RtuRenderJob* job = new RtuRenderJob;
+    std::vector<int> devs(device_ids, device_ids + n_devices);
+    job->thread = std::thread(run_adaptive_job, job, rtu_scene_desc(scene), img, devs, samples, gather_bounces, ad,
+                              std::string(result_png ? result_png : ""), std::string(zbuffer_png ? zbuffer_png : ""),
+                              std::string(samplecount_png ? samplecount_png : ""));
+    return job;  // returns immediately, as BeginRender() must
+}
 
 static RtuRenderJob* begin(const RtuScene* scene, RtuImage* img, const int* device_ids, int n_devices, int samples, int gather_bounces,
                            const char* result_png, const char* zbuffer_png) {

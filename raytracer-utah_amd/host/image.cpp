@@ -17,6 +17,8 @@ struct RtuImage {
     std::vector<uint8_t> img;       // Color24[W*H]
     std::vector<float>   zbuffer;   // float[W*H]
     std::vector<uint8_t> zimg;      // empty until computed
+    std::vector<uint8_t> sample_count;      // uchar sampleCount[W*H] (scene.h:545), zeroed at create
+    std::vector<uint8_t> sample_count_img;  // empty until computed
     std::atomic<int>     num_rendered{0};
 };
 
@@ -88,6 +90,7 @@ RtuImage* rtu_image_create(int width, int height) {
     im->height = height;
     im->img.assign((size_t)width * height * 3, 0);
     im->zbuffer.assign((size_t)width * height, RTU_BIGFLOAT);
+    im->sample_count.assign((size_t)width * height, 0);
     return im;
 }
 
@@ -97,6 +100,8 @@ int rtu_image_height(const RtuImage* img) { return img ? img->height : 0; }
 uint8_t* rtu_image_pixels(RtuImage* img) { return img ? img->img.data() : nullptr; }
 float* rtu_image_zbuffer(RtuImage* img) { return img ? img->zbuffer.data() : nullptr; }
 uint8_t* rtu_image_zimage(RtuImage* img) { return (img && !img->zimg.empty()) ? img->zimg.data() : nullptr; }
+uint8_t* rtu_image_sample_count(RtuImage* img) { return img ? img->sample_count.data() : nullptr; }
+uint8_t* rtu_image_sample_count_image(RtuImage* img) { return (img && !img->sample_count_img.empty()) ? img->sample_count_img.data() : nullptr; }
 int rtu_image_num_rendered(const RtuImage* img) { return img ? img->num_rendered.load() : 0; }
 int rtu_image_is_done(const RtuImage* img) { return img && img->num_rendered.load() >= img->width * img->height; }
 
@@ -140,6 +145,37 @@ void rtu_image_compute_zimg(RtuImage* img) {
             img->zimg[i] = float_to_byte(f);  // int(f*255) clamped to [0,255]
         }
     }
+}
+
+void rtu_image_fill_sample_count(RtuImage* img, const uint8_t* counts, int row0, int nrows) {
+    if (!img || !counts || row0 < 0 || nrows <= 0 || row0 + nrows > img->height) return;
+    memcpy(img->sample_count.data() + (size_t)row0 * img->width, counts, (size_t)nrows * img->width);
+}
+
+// RenderImage::ComputeSampleCountImage (scene.h:614-635): the counts stretched over [0, 255], all zero when they are all equal
+int rtu_image_compute_sample_count_img(RtuImage* img) {
+    if (!img) return -1;
+    const size_t size = (size_t)img->width * img->height;
+    img->sample_count_img.assign(size, 0);
+    uint8_t smin = 255, smax = 0;
+    for (size_t i = 0; i < size; i++) {
+        if (smin > img->sample_count[i]) smin = img->sample_count[i];
+        if (smax < img->sample_count[i]) smax = img->sample_count[i];
+    }
+    if (smax != smin) {
+        for (size_t i = 0; i < size; i++) {
+            int c = (255 * (img->sample_count[i] - smin)) / (smax - smin);
+            if (c < 0) c = 0;
+            if (c > 255) c = 255;
+            img->sample_count_img[i] = (uint8_t)c;
+        }
+    }
+    return smax;
+}
+
+int rtu_image_save_sample_count_png(const RtuImage* img, const char* path) {  // SaveSampleCountImage, scene.h:640
+    if (!img || img->sample_count_img.empty()) return -1;
+    return rtu_write_png(path, img->sample_count_img.data(), img->width, img->height, 1);
 }
 
 int rtu_image_save_png(const RtuImage* img, const char* path) {
