@@ -45,6 +45,11 @@ lib.rtu_oracle_render_samples.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(OracleStats), ctypes.c_int]
 lib.rtu_oracle_render_paths.restype = ctypes.c_int
 lib.rtu_oracle_render_paths.argtypes = lib.rtu_oracle_render_samples.argtypes
+lib.rtu_oracle_render_sample_images.restype = ctypes.c_int
+lib.rtu_oracle_render_sample_images.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_int]
+lib.rtu_oracle_render_adaptive.restype = ctypes.c_int
+lib.rtu_oracle_render_adaptive.argtypes = ([ctypes.c_void_p] + [ctypes.c_int] * 8 + [ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 4 +
+                                           [ctypes.POINTER(OracleStats), ctypes.c_int])
 lib.rtu_oracle_portable_acos.restype = None
 lib.rtu_oracle_portable_acos.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
 lib.rtu_oracle_portable_sincos.restype = None
@@ -116,6 +121,44 @@ def render_paths(scene, width, height, spp, stream=STREAM_KEYED, trig=TRIG_PORTA
     if rc != 0:
         raise OracleError(rc)
     return out, st.as_dict()
+
+
+def sample_images(scene, width, height, spp, first, n, gi=False, threads=1, row0=0, nrows=None):
+    """Samples [first, first + n) of the fixed spp-sample frame of recipe S (gi False) or P (gi True), keyed stream, portable trig:
+    float32 [n, rows, W, 4] {r, g, b, z}, z = RTU_BIGFLOAT for a miss (what rtu_debug_sample_images returns)."""
+    if nrows is None:
+        nrows = height - row0
+    out = np.empty((n, nrows, width, 4), np.float32)
+    rc = lib.rtu_oracle_render_sample_images(scene.desc_ptr, width, height, row0, nrows, spp, 1 if gi else 0, first, n, out.ctypes.data, threads)
+    if rc != 0:
+        raise OracleError(rc)
+    return out
+
+
+def render_adaptive(scene, width, height, spp, min_samples, increment, target, gi=False, trace_batch=1, counts_in=None, threads=1,
+                    row0=0, nrows=None):
+    """Adaptive recipe S / P as include/rtu_render.h states it (keyed stream, portable trig). Returns (rgbz float32 [rows, W, 4],
+    counts uint8 [rows, W] — the rule's —, margin float32 [rows, W], stats dict). counts_in (uint8 [rows, W]): each pixel returns the
+    mean of its first counts_in samples instead of the rule's. margin: the smallest |max var - target| over the checkpoints the
+    rule evaluated up to its stop (relative to target when 0 < target < inf). trace_batch: a pixel stopped at n is traced on, for the
+    counters only, to min(spp, trace_batch * ceil(n / trace_batch)), as the device does with batches of that size (1: nothing more)."""
+    if nrows is None:
+        nrows = height - row0
+    out = np.empty((nrows, width, 4), np.float32)
+    counts = np.empty((nrows, width), np.uint8)
+    margin = np.empty((nrows, width), np.float32)
+    cin = None
+    if counts_in is not None:
+        cin = np.ascontiguousarray(counts_in, np.uint8)
+        if cin.shape != (nrows, width):
+            raise ValueError("counts_in has shape %s, not %s" % (cin.shape, (nrows, width)))
+    st = OracleStats()
+    rc = lib.rtu_oracle_render_adaptive(scene.desc_ptr, width, height, row0, nrows, spp, 1 if gi else 0, min_samples, increment, target,
+                                        trace_batch, cin.ctypes.data if cin is not None else None,
+                                        out.ctypes.data, counts.ctypes.data, margin.ctypes.data, ctypes.byref(st), threads)
+    if rc != 0:
+        raise OracleError(rc)
+    return out, counts, margin, st.as_dict()
 
 
 def portable_acos(x):

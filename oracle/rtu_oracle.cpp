@@ -836,12 +836,25 @@ inline float halton(int index, int base) {
     return r;
 }
 
+// Adaptive sampling as include/rtu_render.h states it (rtu_oracle_render_adaptive). Arrays are indexed by pixel of the rows rendered.
+struct Adaptive {
+    int min_samples, increment;
+    float target;
+    int trace_batch;             // samples the device traces per batch: a stopped pixel is traced on to the end of its batch
+    const uint8_t* counts_in;    // nullptr: the pixel returns the mean up to the rule's stop; else the mean of its first counts_in[p]
+    uint8_t* counts_out;         // the rule's count
+    float* margin_out;           // min over the rule's checkpoints of |max var - target| (relative when 0 < target < inf); may be nullptr
+};
+
 struct Sampling {
     int spp;          // 0: recipe W (one ray through the pixel centre); S >= 1: recipe S, the sample loop of Render()
     bool sequential, libm_trig;
     bool gi;          // recipe P: recipe S plus the Monte-Carlo gather of Render() (:129-134)
     bool per_pixel;   // work distribution: false = chunks of rows; true = the reference's PixelIterator (PixelIterator.h:25-38):
                       // one shared atomic counter, ONE PIXEL per fetch, x = i % W, y = i / W
+    const Adaptive* ad;         // recipes S / P: stop each pixel by the adaptive rule (nullptr: the mean of all spp samples)
+    int first, n_images;        // n_images > 0: write the {r,g,b,z} of samples [first, first + n_images) to `images`, no mean
+    float* images;
 };
 
 void render_rows(const RtuSceneDesc* s, const CamFrame& cf, int W, int H, std::atomic<int>* next_row, int y_begin,
@@ -890,11 +903,24 @@ void render_rows(const RtuSceneDesc* s, const CamFrame& cf, int W, int H, std::a
                 }
                 // recipe S: the sample loop of Render() (RenderFunctions.cpp:73-151) with spp in place of
                 // maxSampleSize, direct lighting only, every sample traced and shaded in turn.
+                // Adaptive (sm.ad): the same samples, summed in the same order, up to the pixel's stop; the sample images
+                // (sm.n_images): the same samples, written one by one.
                 const float pixelIncrement = (float)(1.0 / sm.spp);  // :68
-                C3 pixelValuesSum = mkc(0, 0, 0);
+                const size_t p = (size_t)(y - y_begin) * W + x;
+                const Adaptive* ad = sm.ad;
+                C3 pixelValuesSum = mkc(0, 0, 0), sq = mkc(0, 0, 0);
                 float zSum = 0.0f;
                 int numOfHits = 0;
-                for (int index = 0; index < sm.spp; index++) {
+                bool live = true;                                // adaptive: the rule has not stopped the pixel yet
+                int stop = sm.spp;                               // ... the rule's count
+                const int ret = ad && ad->counts_in ? ad->counts_in[p] : 0;  // the count whose mean is returned (0: the rule's)
+                bool have = false;                               // ... and that mean has been taken
+                C3 retSum = mkc(0, 0, 0);
+                float retZ = 0.0f;
+                int retHits = 0;
+                float margin = INFINITY;
+                int index_end = sm.n_images ? sm.first + sm.n_images : sm.spp;
+                for (int index = sm.n_images ? sm.first : 0; index < index_end; index++) {
                     const uint32_t key = sample_key((uint32_t)(x + W * y), (uint32_t)index);
                     cx.seq_key = key;
                     cx.seq_counter = 0;
@@ -914,10 +940,9 @@ void render_rows(const RtuSceneDesc* s, const CamFrame& cf, int W, int H, std::a
                     Hit h = new_hit();
                     cx.st.primary_rays++;
                     C3 c;
-                    if (trace(cx, ray, 0, h)) {  // :103
+                    const bool hit = trace(cx, ray, 0, h);  // :103
+                    if (hit) {
                         cx.st.primary_hits++;
-                        zSum += h.z;  // :109
-                        numOfHits++;
                         if (sm.gi && s->nodes[h.node].material_id >= 0) {  // recipe P: :129-135
                             C3 indirect = monte_carlo(cx, h, RTU_GI_BOUNCES, key, scene_lights);
                             RtuLight amb = ambient_light(indirect);
@@ -930,10 +955,62 @@ void render_rows(const RtuSceneDesc* s, const CamFrame& cf, int W, int H, std::a
                     } else {
                         c = background_sample(*s, x, y);  // :145
                     }
+                    if (sm.n_images) {
+                        float* im = sm.images + 4 * ((size_t)(index - sm.first) * (size_t)(y_end - y_begin) * W + p);
+                        im[0] = c.r; im[1] = c.g; im[2] = c.b; im[3] = hit ? h.z : RTU_BIGFLOAT;
+                        continue;
+                    }
+                    const int n = index + 1;
+                    if (ad && !live && n > ret) continue;  // traced past the stop (the rest of the device's batch): counters only
                     pixelValuesSum += c;  // :148
+                    if (hit) {
+                        zSum += h.z;  // :109
+                        numOfHits++;
+                    }
+                    if (!ad) continue;
+                    sq += c * c;
+                    // rtu_render.h: a checkpoint n = min_samples + k * increment < spp stops the pixel when
+                    // (q - s * (s / n)) / (n - 1) <= target for r, g and b; n == 1: var = +inf
+                    if (live && n < sm.spp && n >= ad->min_samples && (n - ad->min_samples) % ad->increment == 0) {
+                        float vmax = INFINITY;
+                        if (n > 1) {
+                            const float fn = (float)n, fn1 = (float)(n - 1);
+                            const float vr = (sq.r - pixelValuesSum.r * (pixelValuesSum.r / fn)) / fn1;
+                            const float vg = (sq.g - pixelValuesSum.g * (pixelValuesSum.g / fn)) / fn1;
+                            const float vb = (sq.b - pixelValuesSum.b * (pixelValuesSum.b / fn)) / fn1;
+                            vmax = smax(smax(vr, vg), vb);
+                            if (ad->target < INFINITY) {  // (at +inf, and at n == 1, the decision is exact)
+                                double d = fabs((double)vmax - (double)ad->target);
+                                if (ad->target > 0) d /= (double)ad->target;
+                                if (d < margin) margin = (float)d;
+                            }
+                        }
+                        if (vmax <= ad->target) {
+                            live = false;
+                            stop = n;
+                        }
+                    }
+                    if (n == sm.spp) live = false;
+                    if (!have && (ret ? n == ret : !live)) {
+                        retSum = pixelValuesSum; retZ = zSum; retHits = numOfHits;
+                        have = true;
+                    }
+                    if (!live && have && index_end == sm.spp) {  // the device traces a pixel on to the end of the batch it stopped in
+                        const int B = ad->trace_batch;
+                        const long long last = (long long)B * ((n + B - 1) / B);
+                        index_end = last < sm.spp ? (int)last : sm.spp;
+                    }
+                }
+                if (sm.n_images) continue;
+                int count = sm.spp;
+                if (ad) {
+                    ad->counts_out[p] = (uint8_t)stop;
+                    if (ad->margin_out) ad->margin_out[p] = margin;
+                    pixelValuesSum = retSum; zSum = retZ; numOfHits = retHits;
+                    count = ret ? ret : stop;
                 }
                 // :152 (Color /= float divides) and the z of the commented-out :115
-                o[0] = pixelValuesSum.r / (float)sm.spp; o[1] = pixelValuesSum.g / (float)sm.spp; o[2] = pixelValuesSum.b / (float)sm.spp;
+                o[0] = pixelValuesSum.r / (float)count; o[1] = pixelValuesSum.g / (float)count; o[2] = pixelValuesSum.b / (float)count;
                 o[3] = numOfHits ? zSum / (float)numOfHits : RTU_BIGFLOAT;
             }
         }
@@ -993,7 +1070,7 @@ static int render_impl(const RtuSceneDesc* scene, int width, int height, int row
 
 int rtu_oracle_render_rows(const RtuSceneDesc* scene, int width, int height, int row0, int nrows, float* rgbz_out,
                            RtuOracleStats* stats, int threads) {
-    Sampling sm = {0, false, false, false, false};
+    Sampling sm = {0, false, false, false, false, nullptr, 0, 0, nullptr};
     return render_impl(scene, width, height, row0, nrows, rgbz_out, stats, threads, sm);
 }
 
@@ -1002,7 +1079,7 @@ int rtu_oracle_render_samples(const RtuSceneDesc* scene, int width, int height, 
     if (spp < 1 || (stream != RTU_ORACLE_STREAM_KEYED && stream != RTU_ORACLE_STREAM_SEQUENTIAL) ||
         (trig != RTU_ORACLE_TRIG_PORTABLE && trig != RTU_ORACLE_TRIG_LIBM))
         return RTU_ORACLE_ERR_ARG;
-    Sampling sm = {spp, stream == RTU_ORACLE_STREAM_SEQUENTIAL, trig == RTU_ORACLE_TRIG_LIBM, false, false};
+    Sampling sm = {spp, stream == RTU_ORACLE_STREAM_SEQUENTIAL, trig == RTU_ORACLE_TRIG_LIBM, false, false, nullptr, 0, 0, nullptr};
     return render_impl(scene, width, height, row0, nrows, rgbz_out, stats, threads, sm);
 }
 
@@ -1011,7 +1088,28 @@ int rtu_oracle_render_paths(const RtuSceneDesc* scene, int width, int height, in
     if (spp < 1 || (stream != RTU_ORACLE_STREAM_KEYED && stream != RTU_ORACLE_STREAM_SEQUENTIAL) ||
         (trig != RTU_ORACLE_TRIG_PORTABLE && trig != RTU_ORACLE_TRIG_LIBM))
         return RTU_ORACLE_ERR_ARG;
-    Sampling sm = {spp, stream == RTU_ORACLE_STREAM_SEQUENTIAL, trig == RTU_ORACLE_TRIG_LIBM, true, false};
+    Sampling sm = {spp, stream == RTU_ORACLE_STREAM_SEQUENTIAL, trig == RTU_ORACLE_TRIG_LIBM, true, false, nullptr, 0, 0, nullptr};
+    return render_impl(scene, width, height, row0, nrows, rgbz_out, stats, threads, sm);
+}
+
+int rtu_oracle_render_sample_images(const RtuSceneDesc* scene, int width, int height, int row0, int nrows, int spp, int gi, int first,
+                                    int n, float* out, int threads) {
+    if (spp < 1 || first < 0 || n < 1 || first > spp - n || !out) return RTU_ORACLE_ERR_ARG;
+    Sampling sm = {spp, false, false, gi != 0, false, nullptr, first, n, out};
+    return render_impl(scene, width, height, row0, nrows, out, nullptr, threads, sm);  // (no mean is written: `out` stands in for it)
+}
+
+int rtu_oracle_render_adaptive(const RtuSceneDesc* scene, int width, int height, int row0, int nrows, int spp, int gi, int min_samples,
+                               int increment, float target, int trace_batch, const uint8_t* counts_in, float* rgbz_out, uint8_t* counts_out,
+                               float* margin_out, RtuOracleStats* stats, int threads) {
+    if (spp < 1 || spp > 255 || min_samples < 1 || min_samples > spp || increment < 1 || !(target >= 0.0f) || trace_batch < 1 || !counts_out)
+        return RTU_ORACLE_ERR_ARG;
+    if (width <= 0 || row0 < 0 || nrows < 0 || row0 + nrows > height) return RTU_ORACLE_ERR_ARG;
+    if (counts_in)
+        for (size_t i = 0; i < (size_t)nrows * width; i++)
+            if (counts_in[i] < 1 || counts_in[i] > spp) return RTU_ORACLE_ERR_ARG;
+    Adaptive ad = {min_samples, increment, target, trace_batch, counts_in, counts_out, margin_out};
+    Sampling sm = {spp, false, false, gi != 0, false, &ad, 0, 0, nullptr};
     return render_impl(scene, width, height, row0, nrows, rgbz_out, stats, threads, sm);
 }
 
@@ -1033,7 +1131,7 @@ void rtu_oracle_debug_all_triangles(int on) { g_all_triangles = on != 0; }
 
 int rtu_oracle_render_scheduled(const RtuSceneDesc* scene, int width, int height, float* rgbz_out, RtuOracleStats* stats, int threads,
                                 int per_pixel_schedule) {
-    Sampling sm = {0, false, false, false, per_pixel_schedule != 0};
+    Sampling sm = {0, false, false, false, per_pixel_schedule != 0, nullptr, 0, 0, nullptr};
     return render_impl(scene, width, height, 0, height, rgbz_out, stats, threads, sm);
 }
 

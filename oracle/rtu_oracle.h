@@ -53,6 +53,21 @@ int  rtu_oracle_render_samples(const RtuSceneDesc* scene, int width, int height,
  * with 4 bounces and 1 sample, :549-590; cosine-weighted hemisphere sampling, :320-337). */
 int  rtu_oracle_render_paths(const RtuSceneDesc* scene, int width, int height, int row0, int nrows, int spp,
                              int stream, int trig, float* rgbz_out, RtuOracleStats* stats, int threads);
+/* The samples [first, first + n) of the fixed spp-sample frame of recipe S (gi 0) or P (gi 1), keyed stream and portable trig:
+ * out holds n x nrows x width float4 {r, g, b, z}, z = RTU_BIGFLOAT for a miss — what the device's rtu_debug_sample_images returns. */
+int  rtu_oracle_render_sample_images(const RtuSceneDesc* scene, int width, int height, int row0, int nrows, int spp, int gi, int first,
+                                     int n, float* out, int threads);
+/* Adaptive sampling of recipe S / P as include/rtu_render.h states it (keyed stream, portable trig): binary32 sums s, q in sample
+ * order; at each checkpoint n = min_samples + k * increment < spp the pixel stops when (q - s * (s / n)) / (n - 1) <= target for r,
+ * g and b (n == 1: +inf). counts_out: the rule's count per pixel. rgbz_out: the mean of the first counts_in[p] samples (counts_in
+ * NULL: of the rule's count), z the mean over the hits among them. margin_out (may be NULL): per pixel, the smallest
+ * |max(var_r, var_g, var_b) - target| over the checkpoints the rule evaluated up to its stop, divided by target when
+ * 0 < target < inf; +inf when no checkpoint could go either way. trace_batch B: a pixel that stops at n is traced and shaded on,
+ * for the counters only, to min(spp, B * ceil(n / B)) — what the device traces with batches of B samples; with counts_in NULL
+ * the stats then equal the device's counting variant (with counts_in they count the samples traced for the larger of the two counts). */
+int  rtu_oracle_render_adaptive(const RtuSceneDesc* scene, int width, int height, int row0, int nrows, int spp, int gi, int min_samples,
+                                int increment, float target, int trace_batch, const uint8_t* counts_in, float* rgbz_out,
+                                uint8_t* counts_out, float* margin_out, RtuOracleStats* stats, int threads);
 /* Test hook: 1 = test every triangle of a mesh whatever its boxes say (NOT the reference's algorithm; see rtu_oracle.cpp). */
 void rtu_oracle_debug_all_triangles(int on);
 void rtu_oracle_portable_sincos(const float* t, int n, float* sin_out, float* cos_out);
