@@ -415,6 +415,25 @@ int  rtu_selftest_division(RtuContext* ctx, unsigned long long n_pairs, unsigned
 int  rtu_selftest_primitives(RtuContext* ctx, unsigned long long n_rays, unsigned long long seed,
                              unsigned long long* mismatches_out);
 
+/* Debug: the texture arithmetic of the kernels on n inputs, by the very __device__ functions the kernels call, for
+ * bit-for-bit comparison with the oracle (tests/test_gpu_texcoords.py). h_in holds RTU_TEXOP_IN(op) floats per input,
+ * h_out receives RTU_TEXOP_OUT(op). ATAN2F: {y, x} -> atan2f(y, x); ASINF: x -> asinf(x); SPHERE_UV: a unit normal ->
+ * the sphere's uvw (objFunctions.cpp:38-41); ENV_UVW: a direction -> the uvw of SampleEnvironment (scene.h:425-431);
+ * TILE_CLAMP: uvw -> Texture::TileClamp(uvw); TEXTURE: uvw -> Sample(uvw) of texture `index` of the uploaded scene;
+ * MAP: uvw -> TextureMap::Sample(uvw) of material map `index` (4 * material + RTU_MAP_*), the background map (-1) or
+ * the environment map (-2) of the uploaded scene. TEXTURE / MAP refuse (RTU_ERR_ARG) a scene without textures and a map
+ * that is not present. The arrays are copied through the device in chunks. */
+#define RTU_TEXOP_ATAN2F     0
+#define RTU_TEXOP_ASINF      1
+#define RTU_TEXOP_SPHERE_UV  2
+#define RTU_TEXOP_ENV_UVW    3
+#define RTU_TEXOP_TILE_CLAMP 4
+#define RTU_TEXOP_TEXTURE    5
+#define RTU_TEXOP_MAP        6
+#define RTU_TEXOP_IN(op)  ((op) == RTU_TEXOP_ATAN2F ? 2 : (op) == RTU_TEXOP_ASINF ? 1 : 3)
+#define RTU_TEXOP_OUT(op) ((op) <= RTU_TEXOP_ASINF ? 1 : 3)
+int  rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, unsigned long long n, float* h_out);
+
 /* Device memory helpers so a C/C++ host needs no HIP headers. */
 /* The context's own stream (a hipStream_t as void*) and device: a multi-GPU host (host/begin_render.cpp) renders every shard on
  * its context's stream and queues the collection — RCCL send / receive or an asynchronous copy into pinned host memory — behind

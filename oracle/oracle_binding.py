@@ -57,6 +57,14 @@ lib.rtu_oracle_portable_sincos.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes
 for _n, _k in (("rtu_oracle_rand31", 2), ("rtu_oracle_sample_key", 2), ("rtu_oracle_child_key", 2)):
     getattr(lib, _n).restype = ctypes.c_uint32
     getattr(lib, _n).argtypes = [ctypes.c_uint32] * _k
+lib.rtu_oracle_texcoords.restype = ctypes.c_int
+lib.rtu_oracle_texcoords.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int]
+for _n in ("rtu_oracle_portable_libm", "rtu_oracle_host_libm"):
+    getattr(lib, _n).restype = None
+    getattr(lib, _n).argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+lib.rtu_oracle_check_portable.restype = ctypes.c_longlong
+lib.rtu_oracle_check_portable.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
+FN_ASINF, FN_ATANF, FN_ATAN2F = 0, 1, 2
 STREAM_KEYED, STREAM_SEQUENTIAL = 0, 1
 TRIG_PORTABLE, TRIG_LIBM = 0, 1
 
@@ -192,3 +200,37 @@ def postprocess(rgbz):
     zi = np.empty((h, w), np.uint8)
     lib.rtu_oracle_postprocess(a.ctypes.data, w, h, rgb.ctypes.data, z.ctypes.data, zi.ctypes.data)
     return rgb, z, zi
+
+
+# the op codes of rtu_oracle_texcoords are those of the device's rtu_debug_texcoords (TEXOP_* of the package)
+TEXOP_ATAN2F, TEXOP_ASINF, TEXOP_SPHERE_UV, TEXOP_ENV_UVW, TEXOP_TILE_CLAMP, TEXOP_TEXTURE, TEXOP_MAP = range(7)
+_TEXOP_IN = (2, 1, 3, 3, 3, 3, 3)
+_TEXOP_OUT = (1, 1, 3, 3, 3, 3, 3)
+
+
+def texcoords(op, x, index=0, scene=None, threads=8):
+    """The oracle's texture arithmetic (libm atan2f / asinf, sphere uv, environment uvw, tile_clamp, texture_sample,
+    map_sample) on the inputs x: float32 [n, out] (or [n]), the layout of the package's Context.texcoords."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    n = x.size // _TEXOP_IN[op]
+    out = np.empty((n, _TEXOP_OUT[op]) if _TEXOP_OUT[op] > 1 else (n,), np.float32)
+    rc = lib.rtu_oracle_texcoords(scene.desc_ptr if scene is not None else None, op, index, x.ctypes.data, n, out.ctypes.data, threads)
+    if rc != 0:
+        raise OracleError(rc)
+    return out
+
+
+def libm(fn, x, portable):
+    """asinf / atanf / atan2f (FN_*; atan2f takes pairs {y, x}) of the host libm, or of the oracle's restatement."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    n = x.size // (2 if fn == FN_ATAN2F else 1)
+    out = np.empty(n, np.float32)
+    (lib.rtu_oracle_portable_libm if portable else lib.rtu_oracle_host_libm)(fn, x.ctypes.data, n, out.ctypes.data)
+    return out
+
+
+def check_portable(fn, first, count, seed=0, threads=8):
+    """Restatement against the host libm on `count` inputs (see rtu_oracle.h): (mismatches, first failing input bits)."""
+    fb = (ctypes.c_uint32 * 2)()
+    n = lib.rtu_oracle_check_portable(fn, first, count, seed, threads, fb)
+    return int(n), (int(fb[0]), int(fb[1]))

@@ -242,11 +242,12 @@ inline float bvh_box(const Ray& r, const RtuBvhNode& n, float t_max) {
 
 // ---------------------------------------------------------------------------
 // Sphere::IntersectRay (objFunctions.cpp:15-104)
-inline void sphere_uv(Hit& h) {  // :38-41 (atan2f/asinf float, the rest fp64)
-    float u = (float)(0.5 - (double)atan2f(h.N.x, h.N.y) / (2 * M_PI));
-    float v = (float)(0.5 + (double)asinf(h.N.z) / M_PI);
-    h.uvw = mk(u, v, 0);
+inline V3 sphere_uvw(V3 N) {  // :38-41 (atan2f/asinf float: libm's, as the reference calls them; the rest fp64)
+    float u = (float)(0.5 - (double)atan2f(N.x, N.y) / (2 * M_PI));
+    float v = (float)(0.5 + (double)asinf(N.z) / M_PI);
+    return mk(u, v, 0);
 }
+inline void sphere_uv(Hit& h) { h.uvw = sphere_uvw(h.N); }
 bool sphere_hit(const Ray& ray, Hit& h) {
     if (!box_hit(ray, mk(-1, -1, -1), mk(1, 1, 1), RTU_BIGFLOAT)) return false;  // :17, objects.h:25
     float a = dot(ray.dir, ray.dir);
@@ -572,13 +573,15 @@ inline C3 background_sample(const RtuSceneDesc& s, int x, int y) {
     return env_color_sample(s, s.background, s.background_map, mk((float)x / s.camera.img_width, (float)y / s.camera.img_height, 0));
 }
 // environment.SampleEnvironment(dir), scene.h:425-431
-inline C3 env_sample(const RtuSceneDesc& s, V3 dir) {
-    if (!s.environment.has_map) return ldc(s.environment.color);
+inline V3 env_uvw(V3 dir) {
     float z = asinf(-dir.z) / float(M_PI) + 0.5f;
     float x = dir.x / (float)(fabs(dir.x) + fabs(dir.y));
     float y = dir.y / (float)(fabs(dir.x) + fabs(dir.y));
-    V3 uvw = mk(0.5f, 0.5f, 0.0f) + (mk(0.5f, 0.5f, 0) * x + mk(-0.5f, 0.5f, 0) * y) * z;
-    return env_color_sample(s, s.environment, s.environment_map, uvw);
+    return mk(0.5f, 0.5f, 0.0f) + (mk(0.5f, 0.5f, 0) * x + mk(-0.5f, 0.5f, 0) * y) * z;
+}
+inline C3 env_sample(const RtuSceneDesc& s, V3 dir) {
+    if (!s.environment.has_map) return ldc(s.environment.color);
+    return env_color_sample(s, s.environment, s.environment_map, env_uvw(dir));
 }
 
 // The LightList a Shade() call receives: the scene's lights, or the one AmbientLight that MonteCarlo()
@@ -1036,6 +1039,134 @@ int check_scene(const RtuSceneDesc* s, bool stochastic_ok) {
     return 0;
 }
 
+
+// ---------------------------------------------------------------------------
+// atanf, atan2f and asinf of the host libm restated: glibc's binary32 s_atanf.c, e_atan2f.c and e_asinf.c
+// (fdlibm-derived), with the constants of the x86-64 libm.so.6, in IEEE binary32 operations and bit tests only.
+// Recipe W keeps calling libm, as the reference does; the device uses a copy of these three functions
+// (raytracer-utah_amd/csrc/rtu_intersect.h), and rtu_oracle_check_portable below proves this copy equal to libm on
+// every float (asinf on [-1, 1], atanf everywhere) and on 2^32 atan2f pairs (tests/test_oracle_texcoords.py).
+inline int32_t fbits(float f) { int32_t i; memcpy(&i, &f, 4); return i; }
+inline float bitsf(int32_t i) { float f; memcpy(&f, &i, 4); return f; }
+float portable_atanf(float x) {
+    const int32_t hx = fbits(x), ix = hx & 0x7fffffff;
+    if (ix >= 0x4c000000) {  // |x| >= 2^25, inf, NaN
+        if (ix > 0x7f800000) return x + x;
+        return hx > 0 ? 0x1.921fb4p+0f + 0x1.4442dp-24f : -0x1.921fb4p+0f - 0x1.4442dp-24f;
+    }
+    int id;
+    if (ix < 0x3ee00000) {                // |x| < 0.4375
+        if (ix < 0x31000000) return x;    // |x| < 2^-29
+        id = -1;
+    } else {
+        x = fabsf(x);
+        if (ix < 0x3f980000) {            // |x| < 1.1875
+            if (ix < 0x3f300000) { id = 0; x = (2.0f * x - 1.0f) / (2.0f + x); }
+            else { id = 1; x = (x - 1.0f) / (x + 1.0f); }
+        } else if (ix < 0x401c0000) {     // |x| < 2.4375
+            id = 2; x = (x - 1.5f) / (1.0f + 1.5f * x);
+        } else {
+            id = 3; x = -1.0f / x;
+        }
+    }
+    const float z = x * x, w = z * z;
+    const float s1 = z * (0x1.555556p-2f + w * (0x1.24924ap-3f + w * (0x1.745cdcp-4f + w * (0x1.10d66ap-4f + w * (0x1.97b4b2p-5f + w * 0x1.0ad3aep-6f)))));
+    const float s2 = w * (-0x1.99999ap-3f + w * (-0x1.c71c7p-4f + w * (-0x1.3b0f2ap-4f + w * (-0x1.dde2d6p-5f + w * -0x1.2b4442p-5f))));
+    if (id < 0) return x - x * (s1 + s2);
+    const float hi = id == 0 ? 0x1.dac67p-2f : id == 1 ? 0x1.921fb4p-1f : id == 2 ? 0x1.f730bcp-1f : 0x1.921fb4p+0f;   // atan(0.5, 1, 1.5, inf)
+    const float lo = id == 0 ? 0x1.586ed2p-28f : id == 1 ? 0x1.4442dp-25f : id == 2 ? 0x1.281f68p-25f : 0x1.4442dp-24f;
+    const float r = hi - ((x * (s1 + s2) - lo) - x);
+    return hx < 0 ? -r : r;
+}
+float portable_atan2f(float y, float x) {
+    const float pi = 0x1.921fb6p+1f, pi_lo = -0x1.777a5cp-24f, pi_o_2 = 0x1.921fb6p+0f, pi_o_4 = 0x1.921fb6p-1f, tiny = 0x1.4484cp-100f;
+    const int32_t hx = fbits(x), ix = hx & 0x7fffffff, hy = fbits(y), iy = hy & 0x7fffffff;
+    if (ix > 0x7f800000 || iy > 0x7f800000) return x + y;
+    if (hx == 0x3f800000) return portable_atanf(y);
+    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);  // 2 * sign(x) + sign(y)
+    if (iy == 0) return m == 2 ? pi + tiny : m == 3 ? -pi - tiny : y;
+    if (ix == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    if (ix == 0x7f800000) {
+        if (iy == 0x7f800000) return m == 0 ? pi_o_4 + tiny : m == 1 ? -pi_o_4 - tiny : m == 2 ? 3.0f * pi_o_4 + tiny : -3.0f * pi_o_4 - tiny;
+        return m == 0 ? 0.0f : m == 1 ? -0.0f : m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (iy == 0x7f800000) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int k = (iy - ix) >> 23;
+    float z;
+    if (k > 60) z = pi_o_2 + 0.5f * pi_lo;      // |y/x| > 2^60
+    else if (hx < 0 && k < -60) z = 0.0f;       // |y|/x < -2^60
+    else z = portable_atanf(fabsf(y / x));
+    if (m == 0) return z;
+    if (m == 1) return -z;
+    if (m == 2) return pi - (z - pi_lo);
+    return (z - pi_lo) - pi;
+}
+float portable_asinf(float x) {
+    const float pio2_hi = 0x1.921fb6p+0f, pio2_lo = -0x1.777a5cp-25f, pio4_hi = 0x1.921fb6p-1f;
+    const float p0 = 0x1.5555c8p-3f, p1 = 0x1.3301e4p-4f, p2 = 0x1.747e4ap-5f, p3 = 0x1.8c283cp-6f, p4 = 0x1.596d28p-5f;
+    const int32_t hx = fbits(x), ix = hx & 0x7fffffff;
+    if (ix == 0x3f800000) return x * pio2_hi + x * pio2_lo;  // asin(+-1) = +-pi/2
+    if (ix > 0x3f800000) return (x - x) / (x - x);           // |x| > 1: NaN
+    if (ix < 0x3f000000) {                                    // |x| < 0.5
+        if (ix < 0x32000000) return x;                        // |x| < 2^-27
+        const float t = x * x;
+        const float w = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+        return x + x * w;
+    }
+    const float t = (1.0f - fabsf(x)) * 0.5f;
+    const float p = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+    const float s = sqrtf(t);
+    float r;
+    if (ix >= 0x3f79999a) {                                   // |x| > 0.975
+        r = pio2_hi - (2.0f * (s + s * p) - pio2_lo);
+    } else {
+        const float w = bitsf(fbits(s) & (int32_t)0xfffff000);
+        const float c = (t - w * w) / (s + w);
+        const float pp = 2.0f * s * p - (pio2_lo - 2.0f * c);
+        const float q = pio4_hi - 2.0f * w;
+        r = pio4_hi - (pp - q);
+    }
+    return hx > 0 ? r : -r;
+}
+// equal as results: the same bits, or both NaN (a NaN's sign and payload are not part of the contract)
+inline bool same_result(float a, float b) { return fbits(a) == fbits(b) || (a != a && b != b); }
+inline uint64_t splitmix64(uint64_t x) {
+    x += 0x9e3779b97f4a7c15ull;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+// The i-th atan2f pair of the check: four families in turn. 0: any two bit patterns (every exponent, subnormals, inf,
+// NaN); 1: the x and y of a random unit vector (what the kernels pass); 2: |y| and |x| a few ulp apart (the diagonals,
+// where atanf's reduction switches); 3: exponents within 70 of each other (the |y/x| = 2^+-60 cut-offs).
+void atan2f_pair(uint64_t seed, uint64_t i, float& y, float& x) {
+    const uint64_t h = splitmix64(seed ^ splitmix64(i)), g = splitmix64(h);
+    const uint32_t a = (uint32_t)h, b = (uint32_t)(h >> 32), c = (uint32_t)g;
+    switch (i & 3) {
+    case 0: y = bitsf((int32_t)a); x = bitsf((int32_t)b); break;
+    case 1: {
+        const float u = (float)(a >> 8) * 0x1p-23f - 1.0f, v = (float)(b >> 8) * 0x1p-23f - 1.0f, w = (float)(c >> 8) * 0x1p-23f - 1.0f;
+        const float n = sqrtf(u * u + v * v + w * w);
+        if (n > 0) { x = u / n; y = v / n; } else { x = 1; y = 0; }
+        if (c & 1) { x = v / sqrtf(u * u + v * v); y = u / sqrtf(u * u + v * v); }  // a unit vector of the xy plane
+        break;
+    }
+    case 2: {
+        const int32_t e = (int32_t)(a % 254u + 1u) << 23, mant = (int32_t)(b & 0x7fffff);
+        const int32_t d = (int32_t)(c % 17u) - 8;
+        y = bitsf(e | mant | (int32_t)(c & 0x80000000u));
+        x = bitsf(((e | mant) + d) | (int32_t)((c << 1) & 0x80000000u));
+        break;
+    }
+    default: {
+        const int32_t ex = (int32_t)(a % 254u + 1u), ey = ex + (int32_t)(c % 141u) - 70;
+        const int32_t ey_ok = ey < 1 ? 0 : ey > 254 ? 254 : ey;
+        x = bitsf((ex << 23) | (int32_t)(b & 0x7fffff) | (int32_t)(a & 0x80000000u));
+        y = bitsf((ey_ok << 23) | ((int32_t)((b >> 9) ^ c) & 0x7fffff) | (int32_t)(c & 0x80000000u));
+        break;
+    }
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -1111,6 +1242,93 @@ int rtu_oracle_render_adaptive(const RtuSceneDesc* scene, int width, int height,
     Adaptive ad = {min_samples, increment, target, trace_batch, counts_in, counts_out, margin_out};
     Sampling sm = {spp, false, false, gi != 0, false, &ad, 0, 0, nullptr};
     return render_impl(scene, width, height, row0, nrows, rgbz_out, stats, threads, sm);
+}
+
+// Texture arithmetic of the oracle (the functions recipe W calls, libm included) on n inputs: the counterpart of the
+// device's rtu_debug_texcoords, for bit-for-bit comparison.
+int rtu_oracle_texcoords(const RtuSceneDesc* scene, int op, int index, const float* in, long long n, float* out, int threads) {
+    if (op < RTU_ORACLE_TEXOP_ATAN2F || op > RTU_ORACLE_TEXOP_MAP || n < 0 || (n && (!in || !out))) return RTU_ORACLE_ERR_ARG;
+    const RtuTexture* tex = nullptr;
+    const RtuTexMap* map = nullptr;
+    if (op == RTU_ORACLE_TEXOP_TEXTURE || op == RTU_ORACLE_TEXOP_MAP) {
+        if (!scene || scene->n_textures == 0) return RTU_ORACLE_ERR_ARG;
+        if (op == RTU_ORACLE_TEXOP_TEXTURE) {
+            if (index < 0 || (uint32_t)index >= scene->n_textures) return RTU_ORACLE_ERR_ARG;
+            tex = scene->textures + index;
+        } else if (index == -1 || index == -2) {
+            map = index == -1 ? &scene->background_map : &scene->environment_map;
+        } else {
+            if (index < 0 || !scene->material_maps || (uint32_t)index >= 4u * scene->n_materials) return RTU_ORACLE_ERR_ARG;
+            map = scene->material_maps + index;
+        }
+        if (map && (!map->present || map->texture >= (int32_t)scene->n_textures)) return RTU_ORACLE_ERR_ARG;  // only maps that are there
+    }
+    auto work = [&](long long b, long long e) {
+        for (long long i = b; i < e; i++) {
+            if (op == RTU_ORACLE_TEXOP_ATAN2F) { out[i] = atan2f(in[2 * i], in[2 * i + 1]); continue; }
+            if (op == RTU_ORACLE_TEXOP_ASINF) { out[i] = asinf(in[i]); continue; }
+            const V3 a = mk(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+            float r[3];
+            if (op == RTU_ORACLE_TEXOP_TEXTURE || op == RTU_ORACLE_TEXOP_MAP) {
+                const C3 c = tex ? texture_sample(*tex, a) : map_sample(*scene, *map, a);
+                r[0] = c.r; r[1] = c.g; r[2] = c.b;
+            } else {
+                const V3 v = op == RTU_ORACLE_TEXOP_SPHERE_UV ? sphere_uvw(a) : op == RTU_ORACLE_TEXOP_ENV_UVW ? env_uvw(a) : tile_clamp(a);
+                r[0] = v.x; r[1] = v.y; r[2] = v.z;
+            }
+            memcpy(out + 3 * i, r, sizeof r);
+        }
+    };
+    if (threads < 1) threads = 1;
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) th.emplace_back(work, n * t / threads, n * (t + 1) / threads);
+    for (auto& t : th) t.join();
+    return 0;
+}
+
+void rtu_oracle_portable_libm(int fn, const float* in, long long n, float* out) {
+    for (long long i = 0; i < n; i++)
+        out[i] = fn == RTU_ORACLE_FN_ASINF ? portable_asinf(in[i]) : fn == RTU_ORACLE_FN_ATANF ? portable_atanf(in[i]) : portable_atan2f(in[2 * i], in[2 * i + 1]);
+}
+void rtu_oracle_host_libm(int fn, const float* in, long long n, float* out) {
+    for (long long i = 0; i < n; i++)
+        out[i] = fn == RTU_ORACLE_FN_ASINF ? asinf(in[i]) : fn == RTU_ORACLE_FN_ATANF ? atanf(in[i]) : atan2f(in[2 * i], in[2 * i + 1]);
+}
+
+long long rtu_oracle_check_portable(int fn, uint64_t first, uint64_t count, uint64_t seed, int threads, uint32_t* first_bad) {
+    if (fn < RTU_ORACLE_FN_ASINF || fn > RTU_ORACLE_FN_ATAN2F) return -1;
+    if (threads < 1) threads = 1;
+    std::atomic<long long> bad(0);
+    std::atomic<uint64_t> lowest(~0ull);  // the smallest failing index
+    auto work = [&](uint64_t b, uint64_t e) {
+        long long nb = 0;
+        uint64_t lo = ~0ull;
+        for (uint64_t i = b; i < e; i++) {
+            bool ok;
+            if (fn == RTU_ORACLE_FN_ATAN2F) {
+                float y, x;
+                atan2f_pair(seed, first + i, y, x);
+                ok = same_result(portable_atan2f(y, x), atan2f(y, x));
+            } else {
+                const float x = bitsf((int32_t)(uint32_t)(first + i));
+                ok = fn == RTU_ORACLE_FN_ASINF ? same_result(portable_asinf(x), asinf(x)) : same_result(portable_atanf(x), atanf(x));
+            }
+            if (!ok) { nb++; if (i < lo) lo = i; }
+        }
+        bad += nb;
+        uint64_t cur = lowest.load();
+        while (lo < cur && !lowest.compare_exchange_weak(cur, lo)) {}
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) th.emplace_back(work, count * t / threads, count * (t + 1) / threads);
+    for (auto& t : th) t.join();
+    if (first_bad) {
+        const uint64_t i = lowest.load();
+        if (i == ~0ull) first_bad[0] = first_bad[1] = 0;
+        else if (fn == RTU_ORACLE_FN_ATAN2F) { float y, x; atan2f_pair(seed, first + i, y, x); first_bad[0] = (uint32_t)fbits(y); first_bad[1] = (uint32_t)fbits(x); }
+        else { first_bad[0] = (uint32_t)(first + i); first_bad[1] = 0; }
+    }
+    return bad.load();
 }
 
 void rtu_oracle_portable_acos(const float* x, int n, float* out) {

@@ -75,6 +75,29 @@ void rtu_oracle_portable_acos(const float* x, int n, float* out);
 uint32_t rtu_oracle_rand31(uint32_t key, uint32_t idx);
 uint32_t rtu_oracle_sample_key(uint32_t pixel, uint32_t sample);
 uint32_t rtu_oracle_child_key(uint32_t key, uint32_t slot);
+/* The texture arithmetic recipe W uses, on n inputs: the counterpart of the device's rtu_debug_texcoords (same op codes,
+ * same layouts; see include/rtu_render.h). ATAN2F / ASINF / SPHERE_UV / ENV_UVW call the host libm's atan2f and asinf, as
+ * the reference does. TEXTURE / MAP need a textured `scene`: texture `index`, or material map `index` (-1 background,
+ * -2 environment), which must be present (RTU_ORACLE_ERR_ARG otherwise, as the device's RTU_ERR_ARG). */
+#define RTU_ORACLE_TEXOP_ATAN2F     0
+#define RTU_ORACLE_TEXOP_ASINF      1
+#define RTU_ORACLE_TEXOP_SPHERE_UV  2
+#define RTU_ORACLE_TEXOP_ENV_UVW    3
+#define RTU_ORACLE_TEXOP_TILE_CLAMP 4
+#define RTU_ORACLE_TEXOP_TEXTURE    5
+#define RTU_ORACLE_TEXOP_MAP        6
+int  rtu_oracle_texcoords(const RtuSceneDesc* scene, int op, int index, const float* in, long long n, float* out, int threads);
+/* The restatements of glibc's asinf / atanf / atan2f that the device uses (rtu_oracle.cpp), and the host libm's own
+ * functions, on n inputs (atan2f: n pairs {y, x}). */
+#define RTU_ORACLE_FN_ASINF  0
+#define RTU_ORACLE_FN_ATANF  1
+#define RTU_ORACLE_FN_ATAN2F 2
+void rtu_oracle_portable_libm(int fn, const float* in, long long n, float* out);
+void rtu_oracle_host_libm(int fn, const float* in, long long n, float* out);
+/* Restatement against the host libm on `count` inputs: for ASINF / ATANF the floats with bit patterns first .. first +
+ * count - 1, for ATAN2F the pairs first .. first + count - 1 of a seeded generator (rtu_oracle.cpp atan2f_pair). Counts
+ * results that differ (NaN equals NaN); first_bad[2] gets the lowest failing input (bits of x, or of y and x). */
+long long rtu_oracle_check_portable(int fn, uint64_t first, uint64_t count, uint64_t seed, int threads, uint32_t* first_bad);
 /* pos, origin, u, v of the image plane (RenderFunctions.cpp:243-269). */
 int  rtu_oracle_camera_frame(const RtuCamera* cam, int width, int height, float out12[12]);
 /* gamma + Color24 + z-image; any output pointer may be NULL. */

@@ -145,7 +145,7 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_render_frame_device", "rtu_render_frames_device", "rtu_pack_image_device", "rtu_minmax_z_device", "rtu_pack_output_device", "rtu_render_frame", "rtu_frame_status", "rtu_render_timeline", "rtu_frame_counts", "rtu_timeline_exits", "rtu_mesh_info", "rtu_light_list_info", "rtu_debug_light_list", "rtu_debug_light_list_free", "rtu_debug_walk_stack_limit", "rtu_debug_node_bounds", "rtu_debug_flags", "rtu_set_sequences_in_flight", "rtu_debug_tail_from", "rtu_get_stats", "rtu_get_touched", "rtu_get_touched_launches", "rtu_touched_bytes", "rtu_kernel_slot_name", "rtu_probe_kernel", "rtu_probe_read", "rtu_time_render", "rtu_selftest_division", "rtu_selftest_primitives", "rtu_context_stream", "rtu_context_device", "rtu_context_sync", "rtu_host_alloc_pinned", "rtu_host_free_pinned", "rtu_copy_to_host_async", "rtu_device_alloc",
                "rtu_device_free", "rtu_copy_to_host", "rtu_device_info", "rtu_set_cancel_flag", "rtu_create_context_multi", "rtu_destroy_context_multi",
                "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind",
-               "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images"]
+               "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -199,6 +199,11 @@ _sig(hip, "rtu_adaptive_defaults", _I, ctypes.POINTER(RtuAdaptiveDesc))
 _sig(hip, "rtu_render_frame_adaptive", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P, ctypes.POINTER(RtuStats))
 _sig(hip, "rtu_render_frame_adaptive_device", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P, _P)
 _sig(hip, "rtu_debug_sample_images", _I, _P, ctypes.POINTER(RtuFrameDesc), _I, _I, _P)
+_sig(hip, "rtu_debug_texcoords", _I, _P, _I, _I, _P, ctypes.c_ulonglong, _P)
+# rtu_debug_texcoords operations (include/rtu_render.h RTU_TEXOP_*) and the floats per input / output of each
+TEXOP_ATAN2F, TEXOP_ASINF, TEXOP_SPHERE_UV, TEXOP_ENV_UVW, TEXOP_TILE_CLAMP, TEXOP_TEXTURE, TEXOP_MAP = range(7)
+TEXOP_IN = (2, 1, 3, 3, 3, 3, 3)
+TEXOP_OUT = (1, 1, 3, 3, 3, 3, 3)
 
 
 def adaptive_defaults(**overrides):
@@ -497,6 +502,16 @@ class Context:
         rows = hip.rtu_shard_rows(ctypes.byref(frame))
         out = np.empty((n, rows, frame.width, 4), np.float32)
         self._check(hip.rtu_debug_sample_images(self._h, ctypes.byref(frame), first, n, out.ctypes.data))
+        return out
+
+    def texcoords(self, op, x, index=0):
+        """The kernels' texture arithmetic (TEXOP_*) on the inputs x (float32, TEXOP_IN[op] per input, any leading shape):
+        float32 [n, TEXOP_OUT[op]] (n for ATAN2F / ASINF). TEXTURE / MAP read texture / map `index` of the uploaded scene."""
+        import numpy as np
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        n = x.size // TEXOP_IN[op]
+        out = np.empty((n, TEXOP_OUT[op]) if TEXOP_OUT[op] > 1 else (n,), np.float32)
+        self._check(hip.rtu_debug_texcoords(self._h, op, index, x.ctypes.data, n, out.ctypes.data))
         return out
 
     def render_frames_device(self, frames, d_ptr, stream=None):

@@ -214,10 +214,7 @@ int rtu_launch_resolve_counts(const float4* acc, const uint32_t* hits, const uin
 // ---- RenderImage content on the device: Color24 pixels + float z (RenderFunctions.cpp:152-160, cyColor.h:226,245) ----
 namespace {
 __device__ __forceinline__ uint8_t float_to_byte(float r) {  // Color24(Color): Clamp(int(c * 255)), cvttss2si semantics
-    const float v = r * 255;
-    int i;
-    if (!(v > -2147483904.0f && v < 2147483648.0f)) i = (int)0x80000000;
-    else i = (int)v;
+    const int i = cvtt_i32(r * 255);
     return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
 }
 __global__ void __launch_bounds__(256) k_pack_image(const float4* rgbz, unsigned long long pixels, float* z_out, uint8_t* rgb_out) {
@@ -322,6 +319,31 @@ int rtu_launch_selftest_fdiv(unsigned long long n_pairs, unsigned long long seed
 
 int rtu_launch_selftest_prims(unsigned long long n_rays, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t stream) {
     hipLaunchKernelGGL(k_selftest_prims, dim3(4096), dim3(256), 0, stream, n_rays, seed, d_mismatches);
+    return (int)hipGetLastError();
+}
+
+// rtu_debug_texcoords: the texture arithmetic of the kernels, by the same __device__ functions, on n inputs of
+// RTU_TEXOP_IN(op) floats each; RTU_TEXOP_OUT(op) floats out per input. `tex` has been checked by the caller.
+__global__ void __launch_bounds__(256) k_debug_texcoords(DevScene s, int op, const DevTexture* tex, const RtuTexMap* map,
+                                                         const float* in, float* out, unsigned long long n) {
+    for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) {
+        if (op == RTU_TEXOP_ATAN2F) { out[i] = portable_atan2f(in[2 * i], in[2 * i + 1]); continue; }
+        if (op == RTU_TEXOP_ASINF) { out[i] = portable_asinf(in[i]); continue; }
+        const f3 a = mk3(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+        f3 r;
+        if (op == RTU_TEXOP_SPHERE_UV) r = sphere_uv(a);
+        else if (op == RTU_TEXOP_ENV_UVW) r = env_uvw(a);
+        else if (op == RTU_TEXOP_TILE_CLAMP) r = tile_clamp(a);
+        else if (op == RTU_TEXOP_TEXTURE) r = texture_sample(*tex, a);
+        else r = map_sample(s, *map, a);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+int rtu_launch_debug_texcoords(const DevScene& s, int op, const DevTexture* tex, const RtuTexMap* map, const float* in, float* out,
+                               unsigned long long n, hipStream_t stream) {
+    if (n == 0) return (int)hipSuccess;
+    const unsigned long long blocks = (n + 255u) / 256u;
+    hipLaunchKernelGGL(k_debug_texcoords, dim3((unsigned)(blocks < 8192u ? blocks : 8192u)), dim3(256), 0, stream, s, op, tex, map, in, out, n);
     return (int)hipGetLastError();
 }
 

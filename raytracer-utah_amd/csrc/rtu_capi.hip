@@ -27,6 +27,8 @@ struct RtuContext {
 
     // scene
     bool     has_scene = false;
+    uint32_t n_textures = 0;              // of the uploaded scene, and a host copy of its material maps: rtu_debug_texcoords
+    std::vector<RtuTexMap> mat_maps_host; //   checks a texture / map before the kernel reads it
     std::vector<void*> scene_allocs;
     DevScene dscene{};
     uint32_t bvh_stack_needed = 1;
@@ -792,6 +794,8 @@ int validate(RtuContext* ctx, const RtuSceneDesc* s) {
         if (t.type != RTU_TEX_FILE && t.type != RTU_TEX_CHECKER) return fail(ctx, RTU_ERR_ARG, "texture %u: unknown type", i);
         if (t.type == RTU_TEX_FILE && (t.width < 0 || t.height < 0 || ((size_t)t.width * t.height > 0 && !t.rgb)))
             return fail(ctx, RTU_ERR_ARG, "texture %u: bad image", i);
+        // one side 0, the other not: TextureFile::Sample divides by the 0 (the reference faults) and reads an image that is not there
+        if (t.type == RTU_TEX_FILE && (t.width == 0) != (t.height == 0)) return fail(ctx, RTU_ERR_ARG, "texture %u: %d x %d image", i, t.width, t.height);
     }
     auto map_ok = [&](const RtuTexMap& m) { return !m.present || m.texture < (int32_t)s->n_textures; };
     if (!map_ok(s->background_map) || !map_ok(s->environment_map)) return fail(ctx, RTU_ERR_ARG, "background/environment map: bad texture index");
@@ -1914,6 +1918,9 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     for (uint32_t i = 0; i < s->n_materials && !ctx->scene_stochastic; i++)
         if (s->materials[i].reflection_glossiness > 0 || s->materials[i].refraction_glossiness > 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "a glossy bounce"; }
     ctx->bvh_stack_needed = stack_needed;
+    ctx->n_textures = s->n_textures;
+    ctx->mat_maps_host.clear();
+    if (s->n_textures > 0 && s->material_maps) ctx->mat_maps_host.assign(s->material_maps, s->material_maps + (size_t)s->n_materials * 4);
     ctx->has_scene = true;
     return RTU_OK;
 }
@@ -2482,6 +2489,49 @@ int rtu_selftest_primitives(RtuContext* ctx, unsigned long long n_rays, unsigned
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "selftest launch: %s", hipGetErrorString(e));
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     RTU_HIP(ctx, hipMemcpy(mismatches_out, ctx->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return RTU_OK;
+}
+
+int rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, unsigned long long n, float* h_out) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (op < RTU_TEXOP_ATAN2F || op > RTU_TEXOP_MAP) return fail(ctx, RTU_ERR_ARG, "unknown texcoords op %d", op);
+    if (n && (!h_in || !h_out)) return fail(ctx, RTU_ERR_ARG, "h_in / h_out is NULL");
+    const DevTexture* tex = nullptr;
+    RtuTexMap map;  // checked here, on the host: the kernel samples it as map_sample does, without looking at `present`
+    const DevScene& s = ctx->dscene;
+    if (op == RTU_TEXOP_TEXTURE || op == RTU_TEXOP_MAP) {
+        if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+        if (ctx->n_textures == 0) return fail(ctx, RTU_ERR_ARG, "the uploaded scene has no textures");
+        if (op == RTU_TEXOP_TEXTURE) {
+            if (index < 0 || (uint32_t)index >= ctx->n_textures) return fail(ctx, RTU_ERR_ARG, "texture %d: the scene has %u", index, ctx->n_textures);
+            tex = s.textures + index;
+        } else {
+            if (index == -1 || index == -2) map = index == -1 ? s.bg_map : s.env_map;
+            else if (index >= 0 && (size_t)index < ctx->mat_maps_host.size()) map = ctx->mat_maps_host[index];
+            else return fail(ctx, RTU_ERR_ARG, "no material map %d", index);
+            if (!map.present || map.texture >= (int32_t)ctx->n_textures) return fail(ctx, RTU_ERR_ARG, "map %d is not present", index);
+        }
+    }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned long long chunk = 1ull << 22;
+    const int nin = RTU_TEXOP_IN(op), nout = RTU_TEXOP_OUT(op);
+    float *d_in = nullptr, *d_out = nullptr;
+    RtuTexMap* d_map = nullptr;  // the kernel reads the map from device memory
+    hipError_t e = hipMalloc(&d_in, sizeof(float) * nin * chunk);
+    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * nout * chunk);
+    if (e == hipSuccess && op == RTU_TEXOP_MAP) e = hipMalloc(&d_map, sizeof map);
+    if (e == hipSuccess && op == RTU_TEXOP_MAP) e = hipMemcpy(d_map, &map, sizeof map, hipMemcpyHostToDevice);
+    for (unsigned long long done = 0; e == hipSuccess && done < n; done += chunk) {
+        const unsigned long long m = n - done < chunk ? n - done : chunk;
+        e = hipMemcpyAsync(d_in, h_in + nin * done, sizeof(float) * nin * m, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = (hipError_t)rtu_launch_debug_texcoords(s, op, tex, d_map, d_in, d_out, m, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_out + nout * done, d_out, sizeof(float) * nout * m, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    (void)hipFree(d_map);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "texcoords: %s", hipGetErrorString(e));
     return RTU_OK;
 }
 

@@ -17,6 +17,11 @@
 #include "rtu_render.h"
 #include "rtu_vec.h"
 
+// int(float) as the reference's casts compile on x86 (cvttss2si): INT_MIN for NaN and for values outside the int range.
+// AMDGPU's v_cvt_i32_f32 saturates and maps NaN to 0, and out of range the C++ cast is undefined. Textures
+// (rtu_intersect.h tile_clamp / texture_sample) and Color24 (render_kernel.hip float_to_byte) use it.
+__device__ __forceinline__ int cvtt_i32(float v) { return (v > -2147483904.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000; }
+
 // Wave-uniform scene data (nodes, lights, materials, mesh headers) is read through
 // the CONSTANT address space so the compiler emits scalar loads (s_load) into SGPRs
 // instead of 64 identical vector loads.
@@ -413,5 +418,7 @@ int rtu_launch_pack_output(const float4* rgbz, uint32_t pixels_per_frame, uint32
 
 int rtu_launch_selftest_prims(unsigned long long n_rays, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t stream);
 int rtu_launch_selftest_fdiv(unsigned long long n_pairs, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t stream);
+int rtu_launch_debug_texcoords(const DevScene& s, int op, const DevTexture* tex, const RtuTexMap* map, const float* in, float* out,
+                               unsigned long long n, hipStream_t stream);
 
 #endif

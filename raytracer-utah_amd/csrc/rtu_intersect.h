@@ -208,6 +208,101 @@ template <bool LITERAL> __device__ __forceinline__ bool gt_001(float x) { return
 template <bool LITERAL> __device__ __forceinline__ bool le_001(float x) { return LITERAL ? (double)x <= 0.001 : x < 0.001f; }
 __device__ __forceinline__ bool gt_00001(float x) { return x > 0.00001f; }
 
+// atanf, atan2f and asinf as the host libm computes them (glibc's binary32 s_atanf.c, e_atan2f.c and e_asinf.c,
+// fdlibm-derived; the constants are those of the x86-64 libm.so.6). They feed discrete decisions: a checkerboard
+// edge (u <= 0.5 after the map transform) and the texel of a file texture. The device library's functions are
+// other algorithms and differ from glibc's in the last bit on a share of inputs, so sphere uv and the environment
+// direction use these: IEEE binary32 operations and bit tests only. The oracle's copies (oracle/rtu_oracle.cpp)
+// equal the host libm on every float (tests/test_oracle_texcoords.py); the device equals the oracle
+// (tests/test_gpu_texcoords.py).
+__device__ __forceinline__ float portable_atanf(float x) {
+    const int32_t hx = __float_as_int(x), ix = hx & 0x7fffffff;
+    if (ix >= 0x4c000000) {  // |x| >= 2^25, inf, NaN
+        if (ix > 0x7f800000) return x + x;
+        return hx > 0 ? 0x1.921fb4p+0f + 0x1.4442dp-24f : -0x1.921fb4p+0f - 0x1.4442dp-24f;
+    }
+    int id;
+    if (ix < 0x3ee00000) {                // |x| < 0.4375
+        if (ix < 0x31000000) return x;    // |x| < 2^-29
+        id = -1;
+    } else {
+        x = fabsf(x);
+        if (ix < 0x3f980000) {            // |x| < 1.1875
+            if (ix < 0x3f300000) { id = 0; x = (2.0f * x - 1.0f) / (2.0f + x); }
+            else { id = 1; x = (x - 1.0f) / (x + 1.0f); }
+        } else if (ix < 0x401c0000) {     // |x| < 2.4375
+            id = 2; x = (x - 1.5f) / (1.0f + 1.5f * x);
+        } else {
+            id = 3; x = -1.0f / x;
+        }
+    }
+    const float z = x * x, w = z * z;
+    const float s1 = z * (0x1.555556p-2f + w * (0x1.24924ap-3f + w * (0x1.745cdcp-4f + w * (0x1.10d66ap-4f + w * (0x1.97b4b2p-5f + w * 0x1.0ad3aep-6f)))));
+    const float s2 = w * (-0x1.99999ap-3f + w * (-0x1.c71c7p-4f + w * (-0x1.3b0f2ap-4f + w * (-0x1.dde2d6p-5f + w * -0x1.2b4442p-5f))));
+    if (id < 0) return x - x * (s1 + s2);
+    const float hi = id == 0 ? 0x1.dac67p-2f : id == 1 ? 0x1.921fb4p-1f : id == 2 ? 0x1.f730bcp-1f : 0x1.921fb4p+0f;   // atan(0.5, 1, 1.5, inf)
+    const float lo = id == 0 ? 0x1.586ed2p-28f : id == 1 ? 0x1.4442dp-25f : id == 2 ? 0x1.281f68p-25f : 0x1.4442dp-24f;
+    const float r = hi - ((x * (s1 + s2) - lo) - x);
+    return hx < 0 ? -r : r;
+}
+__device__ __forceinline__ float portable_atan2f(float y, float x) {
+    const float pi = 0x1.921fb6p+1f, pi_lo = -0x1.777a5cp-24f, pi_o_2 = 0x1.921fb6p+0f, pi_o_4 = 0x1.921fb6p-1f, tiny = 0x1.4484cp-100f;
+    const int32_t hx = __float_as_int(x), ix = hx & 0x7fffffff, hy = __float_as_int(y), iy = hy & 0x7fffffff;
+    if (ix > 0x7f800000 || iy > 0x7f800000) return x + y;
+    if (hx == 0x3f800000) return portable_atanf(y);
+    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);  // 2 * sign(x) + sign(y)
+    if (iy == 0) return m == 2 ? pi + tiny : m == 3 ? -pi - tiny : y;
+    if (ix == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    if (ix == 0x7f800000) {
+        if (iy == 0x7f800000) return m == 0 ? pi_o_4 + tiny : m == 1 ? -pi_o_4 - tiny : m == 2 ? 3.0f * pi_o_4 + tiny : -3.0f * pi_o_4 - tiny;
+        return m == 0 ? 0.0f : m == 1 ? -0.0f : m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (iy == 0x7f800000) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int k = (iy - ix) >> 23;
+    float z;
+    if (k > 60) z = pi_o_2 + 0.5f * pi_lo;      // |y/x| > 2^60
+    else if (hx < 0 && k < -60) z = 0.0f;       // |y|/x < -2^60
+    else z = portable_atanf(fabsf(y / x));
+    if (m == 0) return z;
+    if (m == 1) return -z;
+    if (m == 2) return pi - (z - pi_lo);
+    return (z - pi_lo) - pi;
+}
+__device__ __forceinline__ float portable_asinf(float x) {
+    const float pio2_hi = 0x1.921fb6p+0f, pio2_lo = -0x1.777a5cp-25f, pio4_hi = 0x1.921fb6p-1f;
+    const float p0 = 0x1.5555c8p-3f, p1 = 0x1.3301e4p-4f, p2 = 0x1.747e4ap-5f, p3 = 0x1.8c283cp-6f, p4 = 0x1.596d28p-5f;
+    const int32_t hx = __float_as_int(x), ix = hx & 0x7fffffff;
+    if (ix == 0x3f800000) return x * pio2_hi + x * pio2_lo;  // asin(+-1) = +-pi/2
+    if (ix > 0x3f800000) return (x - x) / (x - x);           // |x| > 1: NaN
+    if (ix < 0x3f000000) {                                    // |x| < 0.5
+        if (ix < 0x32000000) return x;                        // |x| < 2^-27
+        const float t = x * x;
+        const float w = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+        return x + x * w;
+    }
+    const float t = (1.0f - fabsf(x)) * 0.5f;
+    const float p = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+    const float s = sqrtf(t);
+    float r;
+    if (ix >= 0x3f79999a) {                                   // |x| > 0.975
+        r = pio2_hi - (2.0f * (s + s * p) - pio2_lo);
+    } else {
+        const float w = __int_as_float(__float_as_int(s) & (int32_t)0xfffff000);
+        const float c = (t - w * w) / (s + w);
+        const float pp = 2.0f * s * p - (pio2_lo - 2.0f * c);
+        const float q = pio4_hi - 2.0f * w;
+        r = pio4_hi - (pp - q);
+    }
+    return hx > 0 ? r : -r;
+}
+// Sphere::IntersectRay's texture coordinates of a unit normal (objFunctions.cpp:38-41): atan2f / asinf in binary32, the
+// rest in binary64. Shared by every kernel that intersects spheres and by rtu_debug_texcoords.
+__device__ __forceinline__ f3 sphere_uv(f3 N) {
+    const float u = (float)(0.5 - (double)portable_atan2f(N.x, N.y) / (2 * 3.14159265358979323846));
+    const float v = (float)(0.5 + (double)portable_asinf(N.z) / 3.14159265358979323846);
+    return mk3(u, v, 0);
+}
+
 template <bool LITERAL>
 __device__ __forceinline__ bool sphere_hit_t(const Ray& ray, Hit& h, bool tex = false) {
     if (LITERAL && !box_hit(ray, mk3(-1, -1, -1), mk3(1, 1, 1), RTU_BIGFLOAT)) return false;
@@ -249,11 +344,7 @@ __device__ __forceinline__ bool sphere_hit_t(const Ray& ray, Hit& h, bool tex = 
             f3 nn = norm3(temp);
             h.N = h.front ? nn : -nn;
             h.p = temp;
-            if (tex) {  // :38-41: atan2f / asinf in binary32, the rest in binary64
-                const float u = (float)(0.5 - (double)atan2f(h.N.x, h.N.y) / (2 * 3.14159265358979323846));
-                const float v = (float)(0.5 + (double)asinf(h.N.z) / 3.14159265358979323846);
-                h.uvw = mk3(u, v, 0);
-            }
+            if (tex) h.uvw = sphere_uv(h.N);  // :38-41
         }
         return ret;
     }
@@ -1205,9 +1296,11 @@ __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool sha
 // tiling (texture.cpp:95-121), TextureChecker::Sample (:125-133), TextureMap::Sample (scene.h:382),
 // TexturedColor::Sample / SampleEnvironment (:421-431). Point sampling: the reference's Shade()
 // calls Sample(hInfo.uvw) without derivatives. Same float operations as the reference; only
-// atan2f / asinf (sphere uv, environment direction) are the device library's.
+// atan2f / asinf (sphere uv, environment direction) are glibc's restated (portable_atan2f, portable_asinf above).
+// The reference's int(float) casts go through cvtt_i32 (rtu_device.h): an .obj's vt values (read with %f: 3e9, inf and
+// nan are accepted), a tiny map scale or the 0/0 of env_uvw reach NaN and values outside the int range.
 __device__ __forceinline__ f3 tile_clamp(f3 uvw) {
-    f3 u = mk3(uvw.x - (float)(int)uvw.x, uvw.y - (float)(int)uvw.y, uvw.z - (float)(int)uvw.z);
+    f3 u = mk3(uvw.x - (float)cvtt_i32(uvw.x), uvw.y - (float)cvtt_i32(uvw.y), uvw.z - (float)cvtt_i32(uvw.z));
     if (u.x < 0) u.x += 1;
     if (u.y < 0) u.y += 1;
     if (u.z < 0) u.z += 1;
@@ -1224,13 +1317,14 @@ __device__ __forceinline__ f3 texture_sample(const DevTexture& t, f3 uvw) {
     const int width = t.width, height = t.height;
     if (width + height == 0) return mk3(0, 0, 0);
     const float x = (float)width * u.x, y = (float)height * u.y;
-    int ix = (int)x, iy = (int)y;
+    int ix = cvtt_i32(x), iy = cvtt_i32(y);
     const float fx = x - (float)ix, fy = y - (float)iy;
-    if (ix < 0) ix -= (ix / width - 1) * width;
+    // ix -= (ix / width - 1) * width in x86's wrapping int arithmetic (ix == INT_MIN overflows it): the result lies in [1, width]
+    if (ix < 0) ix = (int)((uint32_t)ix - ((uint32_t)(ix / width) - 1u) * (uint32_t)width);
     if (ix >= width) ix -= (ix / width) * width;
     int ixp = ix + 1;
     if (ixp >= width) ixp -= width;
-    if (iy < 0) iy -= (iy / height - 1) * height;
+    if (iy < 0) iy = (int)((uint32_t)iy - ((uint32_t)(iy / height) - 1u) * (uint32_t)height);
     if (iy >= height) iy -= (iy / height) * height;
     int iyp = iy + 1;
     if (iyp >= height) iyp -= height;
@@ -1263,13 +1357,16 @@ __device__ __forceinline__ f3 background_sample(const DevScene& s, int x, int y)
     return env_color_sample(s, s.bg, s.bg_map, mk3((float)x / (float)s.img_w, (float)y / (float)s.img_h, 0));
 }
 // environment.SampleEnvironment(dir), scene.h:425-431
-__device__ __forceinline__ f3 env_sample(const DevScene& s, f3 dir) {
-    if (!s.env.has_map) return ld3(s.environment);
-    const float z = asinf(-dir.z) / 3.14159265358979323846f + 0.5f;
+// (the uvw alone: also rtu_debug_texcoords). dir.x == dir.y == 0 divides 0 by 0: uvw is NaN, as in the reference.
+__device__ __forceinline__ f3 env_uvw(f3 dir) {
+    const float z = portable_asinf(-dir.z) / 3.14159265358979323846f + 0.5f;
     const float den = (float)((double)fabsf(dir.x) + (double)fabsf(dir.y));  // fabs() of a float promotes to double
     const float x = dir.x / den, y = dir.y / den;
-    const f3 uvw = mk3(0.5f, 0.5f, 0.0f) + (mk3(0.5f, 0.5f, 0) * x + mk3(-0.5f, 0.5f, 0) * y) * z;
-    return env_color_sample(s, s.env, s.env_map, uvw);
+    return mk3(0.5f, 0.5f, 0.0f) + (mk3(0.5f, 0.5f, 0) * x + mk3(-0.5f, 0.5f, 0) * y) * z;
+}
+__device__ __forceinline__ f3 env_sample(const DevScene& s, f3 dir) {
+    if (!s.env.has_map) return ld3(s.environment);
+    return env_color_sample(s, s.env, s.env_map, env_uvw(dir));
 }
 
 // ---- sample streams of recipe S (include/rtu_render.h states the contract) -----------------
