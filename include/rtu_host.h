@@ -55,6 +55,16 @@ const RtuSceneDesc* rtu_scene_desc(const RtuScene* scene);
 void      rtu_scene_set_resolution(RtuScene* scene, int width, int height);
 void      rtu_scene_free(RtuScene* scene);
 
+/* Move things in a loaded scene (then rtu_update_scene, rtu_render.h). Each appends one more operation to node `node`'s
+ * transformation with the loader's own arithmetic (Transformation::Scale / Rotate / Translate, scene.h:244-247): the node's
+ * tm / itm / pos equal a load of the XML with that operation appended to the node's transform. rotate normalises the axis as
+ * LoadTransform does (xmlload.cpp:274); the angle is in degrees. set_light replaces light `index`, normalising a direct light's
+ * direction as DirectLight::SetDirection does. 0, or -1 for a bad index / NULL. */
+int       rtu_scene_node_scale(RtuScene* scene, uint32_t node, float sx, float sy, float sz);
+int       rtu_scene_node_rotate(RtuScene* scene, uint32_t node, float ax, float ay, float az, float degrees);
+int       rtu_scene_node_translate(RtuScene* scene, uint32_t node, float x, float y, float z);
+int       rtu_scene_set_light(RtuScene* scene, uint32_t index, const RtuLight* light);
+
 const char* rtu_host_last_error(void);
 
 /* ---- output side: RenderImage mirror ------------------------------------ */

@@ -44,6 +44,7 @@ extern "C" {
 #define RTU_ERR_NO_DEVICE   (-6)  /* no such GPU */
 #define RTU_ERR_CAPACITY    (-7)  /* more Shade() frames than provisioned (see rtu_frame_status) */
 #define RTU_ERR_CANCELLED   (-8)  /* the caller's cancel flag was raised (rtu_set_cancel_flag, RtuProgress): StopRender(), main.cpp:70-72 */
+#define RTU_ERR_SCENE_SHAPE (-9)  /* rtu_update_scene: not the shape of the uploaded scene (rtu_last_error names the first difference) */
 
 #define RTU_BAND_ROWS 8  /* image rows per band; one wavefront renders an 8x8 pixel tile */
 
@@ -133,6 +134,23 @@ int  rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* scene);
  * range-checked so that a malformed scene is an error code, never an out-of-bounds access on the GPU. Pure host
  * code, needs no GPU and no context; the message goes to err_buf (may be NULL). */
 int  rtu_validate_scene(const RtuSceneDesc* scene, char* err_buf, size_t err_len);
+
+/* Change the uploaded scene in place: node transformations (tm / itm / pos) and materials, every field of every light (type and
+ * count too, within the limits of rtu_upload_scene), material values and material_maps, background / environment, camera. The
+ * SHAPE must be the uploaded scene's: the same n_nodes and, per node, parent, obj_type, mesh_id, depth and subtree_end; the same
+ * n_meshes and, per mesh, nv, nf, nvn, nvt and n_bvh_nodes; the same n_textures and, per texture, type, width and height; the
+ * same n_materials; material_maps present in both or in neither. Otherwise RTU_ERR_SCENE_SHAPE. The mesh and texture arrays
+ * of `scene` are not read beyond those headers: the copies uploaded before are used (vertex edits and new images need
+ * rtu_upload_scene). The acceleration structures of the meshes and the textures stay; node records, node-level bounds, cover
+ * meshes and occluder lists of shadow rays (built on the GPU, equal to what rtu_upload_scene builds for the same scene),
+ * materials, lights and launch hints are rebuilt. RTU_ERR_NO_SCENE before any upload; a scene rtu_upload_scene would refuse
+ * gets the same code. A refused update leaves the context as it was. Synchronous: waits for every launch in flight on the
+ * context's streams first, so a batch enqueued before the call renders the old scene. */
+int  rtu_update_scene(RtuContext* ctx, const RtuSceneDesc* scene);
+
+/* The shape check of rtu_update_scene on its own: RTU_OK when `b` has the shape of `a`, else RTU_ERR_SCENE_SHAPE with the first
+ * difference in err_buf (may be NULL); RTU_ERR_ARG for a missing array. Pure host code. */
+int  rtu_scene_shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b, char* err_buf, size_t err_len);
 
 /* Fill width/height, cam_pos/origin/u/v from the camera (fp64 tan chain of
  * RenderFunctions.cpp:247 evaluated on the host, once per frame), single shard,
@@ -268,6 +286,7 @@ int         rtu_multi_size(const RtuMultiContext* m);
 RtuContext* rtu_multi_context(RtuMultiContext* m, int i);            /* the i-th GPU's context (diagnostics, rtu_debug_*) */
 const char* rtu_multi_last_error(const RtuMultiContext* m);
 int         rtu_multi_upload_scene(RtuMultiContext* m, const RtuSceneDesc* scene);
+int         rtu_multi_update_scene(RtuMultiContext* m, const RtuSceneDesc* scene);  /* rtu_update_scene on every context */
 int         rtu_multi_render_frame(RtuMultiContext* m, const RtuFrameDesc* frame, float* h_rgbz, const RtuProgress* progress);
 /* How the shards of the last rtu_multi_render_frame reached the host: 1 one context; 2 several contexts, asynchronous copies into
  * one pinned buffer, all in flight together; 3 RCCL (grouped ncclSend / ncclRecv to the first GPU, then one copy). */
@@ -350,6 +369,13 @@ typedef struct RtuLightListDump {
 } RtuLightListDump;
 int  rtu_debug_light_list(const RtuSceneDesc* scene, uint32_t light_slot, uint32_t cover_slot, RtuLightListDump* out);
 void rtu_debug_light_list_free(RtuLightListDump* dump);
+/* Test hook: the list the context holds now (index as in rtu_light_list_info), copied back from the GPU into the same layout
+ * (free with rtu_debug_light_list_free). Synchronous. */
+int  rtu_debug_context_light_list(RtuContext* ctx, uint32_t index, RtuLightListDump* out);
+/* Diagnostic: on != 0 times the phases of the device builder of later rtu_update_scene calls with HIP events (it synchronises
+ * between phases); ms_out5 (may be NULL) gets the milliseconds spent since the previous call: {cover meshes and their extents,
+ * corner pass, count passes, fill and offsets, radix sort}. */
+int  rtu_debug_update_timing(RtuContext* ctx, int on, float* ms_out5);
 
 /* Diagnostic: Shade() frames per recursion level (6 values) and rays deferred to stage 2 per phase
  * (7 values: primary, then levels 0..5) of the most recent frame (fast variant). Synchronises. */

@@ -33,11 +33,14 @@ RTU_ERR_NO_SCENE = -5
 RTU_ERR_NO_DEVICE = -6
 RTU_ERR_CAPACITY = -7
 RTU_ERR_CANCELLED = -8
+RTU_ERR_SCENE_SHAPE = -9
 
 
 class RtuError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
+        if code == RTU_ERR_SCENE_SHAPE:
+            msg = "scene shape differs from the uploaded scene: " + msg
         super().__init__("rtu error %d: %s" % (code, msg))
 
 
@@ -142,7 +145,7 @@ def _sig(lib, name, restype, *argtypes):
 # ---- rtu_render.h ----------------------------------------------------------
 HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rtu_destroy_context", "rtu_last_error",
                "rtu_upload_scene", "rtu_validate_scene", "rtu_frame_setup", "rtu_shard_rows", "rtu_shard_max_rows", "rtu_shard_global_row",
-               "rtu_render_frame_device", "rtu_render_frames_device", "rtu_pack_image_device", "rtu_minmax_z_device", "rtu_pack_output_device", "rtu_render_frame", "rtu_frame_status", "rtu_render_timeline", "rtu_frame_counts", "rtu_timeline_exits", "rtu_mesh_info", "rtu_light_list_info", "rtu_debug_light_list", "rtu_debug_light_list_free", "rtu_debug_walk_stack_limit", "rtu_debug_node_bounds", "rtu_debug_flags", "rtu_set_sequences_in_flight", "rtu_debug_tail_from", "rtu_get_stats", "rtu_get_touched", "rtu_get_touched_launches", "rtu_touched_bytes", "rtu_kernel_slot_name", "rtu_probe_kernel", "rtu_probe_read", "rtu_time_render", "rtu_selftest_division", "rtu_selftest_primitives", "rtu_context_stream", "rtu_context_device", "rtu_context_sync", "rtu_host_alloc_pinned", "rtu_host_free_pinned", "rtu_copy_to_host_async", "rtu_device_alloc",
+               "rtu_render_frame_device", "rtu_render_frames_device", "rtu_pack_image_device", "rtu_minmax_z_device", "rtu_pack_output_device", "rtu_render_frame", "rtu_frame_status", "rtu_render_timeline", "rtu_frame_counts", "rtu_timeline_exits", "rtu_mesh_info", "rtu_light_list_info", "rtu_debug_light_list", "rtu_update_scene", "rtu_multi_update_scene", "rtu_scene_shape_diff", "rtu_debug_context_light_list", "rtu_debug_update_timing", "rtu_debug_light_list_free", "rtu_debug_walk_stack_limit", "rtu_debug_node_bounds", "rtu_debug_flags", "rtu_set_sequences_in_flight", "rtu_debug_tail_from", "rtu_get_stats", "rtu_get_touched", "rtu_get_touched_launches", "rtu_touched_bytes", "rtu_kernel_slot_name", "rtu_probe_kernel", "rtu_probe_read", "rtu_time_render", "rtu_selftest_division", "rtu_selftest_primitives", "rtu_context_stream", "rtu_context_device", "rtu_context_sync", "rtu_host_alloc_pinned", "rtu_host_free_pinned", "rtu_copy_to_host_async", "rtu_device_alloc",
                "rtu_device_free", "rtu_copy_to_host", "rtu_device_info", "rtu_set_cancel_flag", "rtu_create_context_multi", "rtu_destroy_context_multi",
                "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind",
                "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords"]
@@ -250,6 +253,33 @@ class RtuLightListDump(ctypes.Structure):
 
 _sig(hip, "rtu_debug_light_list", _I, _P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(RtuLightListDump))
 _sig(hip, "rtu_debug_light_list_free", None, ctypes.POINTER(RtuLightListDump))
+_sig(hip, "rtu_update_scene", _I, _P, _P)
+_sig(hip, "rtu_multi_update_scene", _I, _P, _P)
+_sig(hip, "rtu_scene_shape_diff", _I, _P, _P, ctypes.c_char_p, ctypes.c_size_t)
+_sig(hip, "rtu_debug_context_light_list", _I, _P, ctypes.c_uint32, ctypes.POINTER(RtuLightListDump))
+_sig(hip, "rtu_debug_update_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
+
+
+def scene_shape_diff(a, b):
+    """Pure host code: None when scene b has the shape of scene a (rtu_update_scene would take b after a), else the first difference."""
+    buf = ctypes.create_string_buffer(256)
+    rc = hip.rtu_scene_shape_diff(a.desc_ptr, b.desc_ptr, buf, len(buf))
+    if rc == RTU_OK:
+        return None
+    if rc != RTU_ERR_SCENE_SHAPE:
+        raise RtuError(rc, buf.value.decode())
+    return buf.value.decode()
+
+
+def _dump_dict(d):
+    import numpy as np
+    if not d.usable:
+        return None
+    n = d.G * d.G + 1
+    return {"G": d.G, "point": bool(d.point), "X": np.array(list(d.X)), "Y": np.array(list(d.Y)), "Z": np.array(list(d.Z)), "L": np.array(list(d.L)),
+            "u0": d.u0, "v0": d.v0, "su": d.su, "sv": d.sv, "node": d.node, "light": d.light,
+            "cell_off": np.ctypeslib.as_array(d.cell_off, (n,)).copy(), "entry_face": np.ctypeslib.as_array(d.entry_face, (max(d.n_entries, 1),))[:d.n_entries].copy(),
+            "entry_zmin": np.ctypeslib.as_array(d.entry_zmin, (max(d.n_entries, 1),))[:d.n_entries].copy()}
 
 
 def light_list(scene, light_slot, cover_slot):
@@ -290,7 +320,8 @@ HOST_SYMBOLS = ["rtu_scene_load_xml", "rtu_scene_clone", "rtu_scene_load_blob", 
                 "rtu_image_compute_zimg", "rtu_image_save_png", "rtu_image_save_zpng", "rtu_write_png",
                 "rtu_begin_render", "rtu_begin_render_sampled", "rtu_begin_render_paths", "rtu_stop_render", "rtu_render_wait", "rtu_render_gather_kind", "rtu_render_job_free",
                 "rtu_image_sample_count", "rtu_image_fill_sample_count", "rtu_image_compute_sample_count_img", "rtu_image_sample_count_image",
-                "rtu_image_save_sample_count_png", "rtu_begin_render_adaptive"]
+                "rtu_image_save_sample_count_png", "rtu_begin_render_adaptive", "rtu_scene_node_scale", "rtu_scene_node_rotate",
+                "rtu_scene_node_translate", "rtu_scene_set_light"]
 _sig(host, "rtu_scene_load_xml", _P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
 _sig(host, "rtu_scene_clone", _P, _P)
 _sig(host, "rtu_scene_load_blob", _P, _P, ctypes.c_size_t)
@@ -301,6 +332,11 @@ _sig(host, "rtu_blob_free", None, _P)
 _sig(host, "rtu_scene_desc", ctypes.POINTER(RtuSceneDesc), _P)
 _sig(host, "rtu_scene_set_resolution", None, _P, _I, _I)
 _sig(host, "rtu_scene_free", None, _P)
+_F = ctypes.c_float
+_sig(host, "rtu_scene_node_scale", _I, _P, ctypes.c_uint32, _F, _F, _F)
+_sig(host, "rtu_scene_node_rotate", _I, _P, ctypes.c_uint32, _F, _F, _F, _F)
+_sig(host, "rtu_scene_node_translate", _I, _P, ctypes.c_uint32, _F, _F, _F)
+_sig(host, "rtu_scene_set_light", _I, _P, ctypes.c_uint32, _P)
 _sig(host, "rtu_host_last_error", ctypes.c_char_p)
 _sig(host, "rtu_image_create", _P, _I, _I)
 _sig(host, "rtu_image_free", None, _P)
@@ -379,6 +415,26 @@ class Scene:
     def set_resolution(self, w, h):
         host.rtu_scene_set_resolution(self._h, w, h)
 
+    def _ok(self, rc, what):
+        if rc != 0:
+            raise RtuError(RTU_ERR_ARG, what)
+
+    def node_scale(self, node, sx, sy=None, sz=None):
+        """One more Transformation::Scale on node `node` (then Context.update)."""
+        self._ok(host.rtu_scene_node_scale(self._h, node, sx, sx if sy is None else sy, sx if sz is None else sz), "node_scale: bad node")
+
+    def node_rotate(self, node, axis, degrees):
+        """One more Transformation::Rotate about `axis` (normalised as the loader does), in degrees."""
+        self._ok(host.rtu_scene_node_rotate(self._h, node, axis[0], axis[1], axis[2], degrees), "node_rotate: bad node")
+
+    def node_translate(self, node, offset):
+        """One more Transformation::Translate."""
+        self._ok(host.rtu_scene_node_translate(self._h, node, offset[0], offset[1], offset[2]), "node_translate: bad node")
+
+    def set_light(self, index, light):
+        """Replace light `index` with an RtuLight-layout ctypes structure (a direct light's direction is normalised)."""
+        self._ok(host.rtu_scene_set_light(self._h, index, ctypes.byref(light)), "set_light: bad index")
+
     def close(self):
         if self._h:
             host.rtu_scene_free(self._h)
@@ -422,6 +478,10 @@ class MultiContext:
 
     def upload(self, scene):
         self._check(hip.rtu_multi_upload_scene(self._h, scene.desc_ptr))
+
+    def update(self, scene):
+        """rtu_update_scene on every GPU's context: same shape, new placement / lights / materials / camera."""
+        self._check(hip.rtu_multi_update_scene(self._h, scene.desc_ptr))
 
     def context_handle(self, i):
         return hip.rtu_multi_context(self._h, i)
@@ -468,6 +528,25 @@ class Context:
 
     def upload(self, scene):
         self._check(hip.rtu_upload_scene(self._h, scene.desc_ptr))
+
+    def update(self, scene):
+        """rtu_update_scene: the uploaded scene moved, relit or re-coloured (same shape); waits for launches in flight."""
+        self._check(hip.rtu_update_scene(self._h, scene.desc_ptr))
+
+    def light_list(self, index):
+        """The occluder list the context holds now (index as in light_lists()), copied back: the dict of light_list()."""
+        d = RtuLightListDump()
+        self._check(hip.rtu_debug_context_light_list(self._h, index, ctypes.byref(d)))
+        try:
+            return _dump_dict(d)
+        finally:
+            hip.rtu_debug_light_list_free(ctypes.byref(d))
+
+    def update_timing(self, on=True):
+        """Time the device builder's phases in later updates; returns the ms spent per phase since the previous call."""
+        o = (ctypes.c_float * 5)()
+        self._check(hip.rtu_debug_update_timing(self._h, int(on), o))
+        return dict(zip(("cover", "extent", "count", "fill", "sort"), list(o)))
 
     def render(self, frame, stats=False):
         """Render this shard; returns (rgbz float32 [rows, W, 4], stats dict or None)."""

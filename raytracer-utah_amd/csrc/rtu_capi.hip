@@ -4,6 +4,7 @@
 // float computations (triangle normals, camera frame) round exactly like the
 // reference's CPU code.
 #include "rtu_device.h"
+#include "rtu_lightlist.h"
 
 #include <algorithm>
 #include <array>
@@ -29,7 +30,21 @@ struct RtuContext {
     bool     has_scene = false;
     uint32_t n_textures = 0;              // of the uploaded scene, and a host copy of its material maps: rtu_debug_texcoords
     std::vector<RtuTexMap> mat_maps_host; //   checks a texture / map before the kernel reads it
-    std::vector<void*> scene_allocs;
+    std::vector<void*> scene_allocs;      // meshes and textures: live until the next upload
+    struct PlaceBuf { void* p = nullptr; size_t cap = 0; };
+    std::vector<PlaceBuf> place;          // what depends on node transformations, lights and materials, by slot (place_scene): an
+                                          //   update rewrites these in place, growing one only when it is too small
+    // the shape of the uploaded scene (rtu_update_scene refuses any other) and what an update builds from
+    std::vector<RtuNode> shape_nodes;
+    std::vector<RtuMesh> shape_meshes;       // headers only: the arrays stay NULL
+    std::vector<RtuTexture> shape_textures;  // likewise
+    uint32_t shape_materials = 0;
+    bool     shape_maps = false;
+    std::vector<std::vector<uint32_t>> fast_elements;  // per mesh: slot of the fast tree's leaf order -> face
+    std::vector<DevMesh> dmeshes;            // host copy of the device mesh records (their f / v arrays)
+    std::vector<const uint32_t*> slot_of;    // per mesh, device: face -> slot of the fast tree
+    std::vector<DevLightMask> lmask_host;    // host copy of DevScene::lmask (rtu_debug_context_light_list)
+    LlBuilder* llb = nullptr;                // the device builder of the occluder lists (rtu_scene_update.hip)
     DevScene dscene{};
     uint32_t bvh_stack_needed = 1;
 
@@ -139,7 +154,38 @@ int fail(RtuContext* ctx, int code, const char* fmt, ...) {
 void free_scene(RtuContext* ctx) {
     for (void* p : ctx->scene_allocs) (void)hipFree(p);
     ctx->scene_allocs.clear();
+    for (RtuContext::PlaceBuf& b : ctx->place) (void)hipFree(b.p);
+    ctx->place.clear();
     ctx->has_scene = false;
+}
+
+// placement buffers by slot
+enum { P_NODES, P_MATERIALS, P_LIGHTS, P_MATMAPS, P_LMASK, P_COVER, P_LIST = P_COVER + RTU_MAX_COVER,
+       P_SLOTS = P_LIST + 2 * RTU_LMASK_LIGHTS * RTU_MAX_COVER };
+
+int ensure_place(RtuContext* ctx, int slot, size_t bytes, void** out) {
+    if (ctx->place.size() < (size_t)P_SLOTS) ctx->place.resize(P_SLOTS);
+    RtuContext::PlaceBuf& b = ctx->place[(size_t)slot];
+    if (bytes == 0) bytes = 16;  // keep pointers valid for empty arrays
+    if (b.cap < bytes) {
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.cap = 0;
+        RTU_HIP(ctx, hipMalloc(&b.p, bytes));
+        b.cap = bytes;
+    }
+    *out = b.p;
+    return RTU_OK;
+}
+
+template <class T>
+int place_upload(RtuContext* ctx, int slot, const T* src, size_t count, const T** dst) {
+    void* d = nullptr;
+    int rc = ensure_place(ctx, slot, sizeof(T) * count, &d);
+    *dst = static_cast<const T*>(d);
+    if (rc != RTU_OK) return rc;
+    if (count) RTU_HIP(ctx, hipMemcpy(d, src, sizeof(T) * count, hipMemcpyHostToDevice));
+    return RTU_OK;
 }
 
 template <class T>
@@ -557,173 +603,142 @@ struct HostLightList {
     DevLightMask m;                 // frame, offsets, scale, G, point (the device pointers stay null here)
     std::vector<uint32_t> off, ent;
 };
+}  // namespace
+
+// ---- the scalar decisions of rtu_lightlist.h ----
+bool ll_frame(const RtuLight& l, const double lo[3], const double hi[3], LlFrame& F) {
+    memset(&F, 0, sizeof F);
+    const bool point = l.type == RTU_LIGHT_POINT;
+    F.point = point ? 1 : 0;
+    double* L = F.L;
+    double* Z = F.Z;
+    double* X = F.X;
+    double* Y = F.Y;
+    if (point) {
+        for (int k = 0; k < 3; k++) { L[k] = l.vec[k]; Z[k] = 0.5 * (lo[k] + hi[k]) - L[k]; }
+    } else {
+        for (int k = 0; k < 3; k++) Z[k] = l.vec[k];
+    }
+    const double zl = std::sqrt(Z[0] * Z[0] + Z[1] * Z[1] + Z[2] * Z[2]);
+    if (!(zl > 0) || !std::isfinite(zl)) return false;
+    for (int k = 0; k < 3; k++) Z[k] /= zl;
+    int ax = std::fabs(Z[0]) <= std::fabs(Z[1]) ? (std::fabs(Z[0]) <= std::fabs(Z[2]) ? 0 : 2) : (std::fabs(Z[1]) <= std::fabs(Z[2]) ? 1 : 2);
+    double A[3] = {0, 0, 0};
+    A[ax] = 1;
+    X[0] = Z[1] * A[2] - Z[2] * A[1]; X[1] = Z[2] * A[0] - Z[0] * A[2]; X[2] = Z[0] * A[1] - Z[1] * A[0];
+    const double xl = std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
+    for (int k = 0; k < 3; k++) X[k] /= xl;
+    Y[0] = Z[1] * X[2] - Z[2] * X[1]; Y[1] = Z[2] * X[0] - Z[0] * X[2]; Y[2] = Z[0] * X[1] - Z[1] * X[0];
+    return true;
+}
+
+uint32_t ll_first_grid(size_t nf) {
+    // grid size: a triangle of an evenly tessellated surface spans ~ G / sqrt(nf / 2) cells; aim at six of them
+    uint32_t G = 64;
+    static const double kSpan = [] { const char* e = getenv("RTU_LGRID_SPAN"); return e ? atof(e) : 6.0; }();  // tuning knob (any value renders the same image)
+    while (G < RTU_LGRID_MAX && (double)G < kSpan * std::sqrt((double)nf * 0.5)) G *= 2;
+    return G;
+}
+
+bool ll_extent_ok(double U0, double U1, double V0, double V1, double& mag) {
+    if (!(U1 > U0) || !(V1 > V0)) return false;
+    mag = std::max(std::max(std::fabs(U0), std::fabs(U1)), std::max(std::fabs(V0), std::fabs(V1)));
+    return !(!std::isfinite(mag) || (U1 - U0) < 1e-4 * mag || (V1 - V0) < 1e-4 * mag);
+}
+
+bool ll_grid_at(uint32_t G, double U0, double U1, double V0, double V1, double ratio, double mag, LlGrid& g) {
+    memset(&g, 0, sizeof g);
+    g.G = G;
+    // the grid spans the extent plus two cells on every side
+    g.du = (U1 - U0) / ((double)G - 4); g.dv = (V1 - V0) / ((double)G - 4);
+    g.gu0 = U0 - 2 * g.du; g.gv0 = V0 - 2 * g.dv;
+    // the device's binary32 cell coordinate: (dot(p - L, X) [/ depth] - u0) * su — every operand good to a few ulp
+    const double coord = 16e-7 * ratio * (1.0 + mag);
+    const double err_cells = std::max(coord / g.du, coord / g.dv) + 4e-7 * (double)G;
+    if (!(err_cells < 0.25)) return false;
+    g.S0 = 0.25 + err_cells;
+    return true;
+}
+
+void ll_mask(const LlFrame& F, const LlGrid& g, DevLightMask& m) {
+    for (int k = 0; k < 3; k++) { m.X[k] = (float)F.X[k]; m.Y[k] = (float)F.Y[k]; m.Z[k] = (float)F.Z[k]; m.L[k] = (float)F.L[k]; }
+    m.u0 = (float)g.gu0; m.v0 = (float)g.gv0; m.su = (float)(1.0 / g.du); m.sv = (float)(1.0 / g.dv);
+    m.point = F.point ? 1u : 0u;
+    m.G = g.G;
+}
+
+namespace {
+
 bool compute_light_list(const RtuLight& l, const CoverMesh& cm, float wscale, HostLightList& out) {
     DevLightMask& m = out.m;
     memset(&m, 0, sizeof m);
     std::vector<uint32_t>& off = out.off;
     std::vector<uint32_t>& ent = out.ent;
-    const double r3 = 1.7320508075688772;
-    const bool point = l.type == RTU_LIGHT_POINT;
-    {
     const std::vector<float4>& boxes = cm.boxes;
-            const size_t nf = boxes.size() / 2;
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    const size_t nf = boxes.size() / 2;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (size_t f = 0; f < nf; f++) {
+        const float4 a = boxes[2 * f], b = boxes[2 * f + 1];
+        const double al[3] = {a.x, a.y, a.z}, bh[3] = {b.x, b.y, b.z};
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], al[k]); hi[k] = std::max(hi[k], bh[k]); }
+    }
+    LlFrame F;
+    if (!ll_frame(l, lo, hi, F)) return false;  // unusable
+    // per triangle: the rectangle of its widened box in the light's (u, v) — the extent of the grid, and the check that
+    // everything the list stands for lies in front of the pinhole
+    double U0 = 1e300, U1 = -1e300, V0 = 1e300, V1 = -1e300, ratio = 1.0;
+    std::vector<double> wid_of(nf);
+    for (size_t f = 0; f < nf; f++) {
+        wid_of[f] = ll_face_wid(boxes[2 * f], boxes[2 * f + 1], wscale);
+        if (!ll_face_corners(boxes[2 * f], boxes[2 * f + 1], wid_of[f], F, U0, U1, V0, V1, ratio)) return false;
+    }
+    double mag;
+    if (!ll_extent_ok(U0, U1, V0, V1, mag)) return false;
+    LlGrid g;
+    for (uint32_t G = ll_first_grid(nf);; G /= 2) {
+        if (G < 16u) return false;
+        if (!ll_grid_at(G, U0, U1, V0, V1, ratio, mag, g)) continue;  // (a coarser grid has larger cells)
+        off.assign((size_t)G * G + 1, 0u);
+        size_t total = 0;
+        bool too_many = false;
+        for (int pass = 0; pass < 2 && !too_many; pass++) {
+            if (pass == 1) {
+                uint32_t run = 0;
+                for (size_t i = 0; i < (size_t)G * G; i++) { const uint32_t n = off[i]; off[i] = run; run += n; }
+                off[(size_t)G * G] = run;
+                ent.assign(2 * total, 0u);
+            }
             for (size_t f = 0; f < nf; f++) {
-                const float4 a = boxes[2 * f], b = boxes[2 * f + 1];
-                const double al[3] = {a.x, a.y, a.z}, bh[3] = {b.x, b.y, b.z};
-                for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], al[k]); hi[k] = std::max(hi[k], bh[k]); }
-            }
-            double L[3] = {0, 0, 0}, Z[3];
-            if (point) {
-                for (int k = 0; k < 3; k++) { L[k] = l.vec[k]; Z[k] = 0.5 * (lo[k] + hi[k]) - L[k]; }
-            } else {
-                for (int k = 0; k < 3; k++) Z[k] = l.vec[k];
-            }
-            const double zl = std::sqrt(Z[0] * Z[0] + Z[1] * Z[1] + Z[2] * Z[2]);
-            if (!(zl > 0) || !std::isfinite(zl)) return false;  // unusable
-            for (int k = 0; k < 3; k++) Z[k] /= zl;
-            int ax = std::fabs(Z[0]) <= std::fabs(Z[1]) ? (std::fabs(Z[0]) <= std::fabs(Z[2]) ? 0 : 2) : (std::fabs(Z[1]) <= std::fabs(Z[2]) ? 1 : 2);
-            double A[3] = {0, 0, 0};
-            A[ax] = 1;
-            double X[3] = {Z[1] * A[2] - Z[2] * A[1], Z[2] * A[0] - Z[0] * A[2], Z[0] * A[1] - Z[1] * A[0]};
-            const double xl = std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
-            for (int k = 0; k < 3; k++) X[k] /= xl;
-            const double Y[3] = {Z[1] * X[2] - Z[2] * X[1], Z[2] * X[0] - Z[0] * X[2], Z[0] * X[1] - Z[1] * X[0]};
-            // per triangle: the rectangle of its widened box in the light's (u, v) — the extent of the grid, and the check that
-            // everything the list stands for lies in front of the pinhole
-            double U0 = 1e300, U1 = -1e300, V0 = 1e300, V1 = -1e300, ratio = 1.0;
-            bool ok = true;
-            std::vector<double> wid_of(nf);
-            for (size_t f = 0; f < nf && ok; f++) {
-                const float4 a = boxes[2 * f], b = boxes[2 * f + 1];
-                const double al[3] = {a.x, a.y, a.z}, bh[3] = {b.x, b.y, b.z};
-                double big = 0;
-                for (int k = 0; k < 3; k++) big = std::max(big, std::max(std::fabs(al[k]), std::fabs(bh[k])));
-                const double wid = 1e-4 * (double)wscale + 1e-5 * big;
-                wid_of[f] = wid;
-                for (int cn = 0; cn < 8; cn++) {
-                    const double q[3] = {((cn & 1) ? bh[0] + wid : al[0] - wid) - L[0], ((cn & 2) ? bh[1] + wid : al[1] - wid) - L[1],
-                                         ((cn & 4) ? bh[2] + wid : al[2] - wid) - L[2]};
-                    double u = q[0] * X[0] + q[1] * X[1] + q[2] * X[2], v = q[0] * Y[0] + q[1] * Y[1] + q[2] * Y[2];
-                    if (point) {
-                        const double depth = q[0] * Z[0] + q[1] * Z[1] + q[2] * Z[2];
-                        const double len = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-                        if (!(depth > 1e-3 * len)) { ok = false; break; }  // (within 89.94 degrees of the axis: tan stays below 1000)
-                        ratio = std::max(ratio, len / depth);
-                        u /= depth; v /= depth;
+                LlFaceCells c;
+                ll_face_cells(cm.verts.data() + 9 * f, wid_of[f], F, g, wscale, c);
+                const uint32_t slot = cm.slot_of[f];
+                for (int y = c.y0; y <= c.y1; y++)
+                    for (int x = c.x0; x <= c.x1; x++) {
+                        if (!ll_cell_in(c, x, y)) continue;
+                        const size_t cell = (size_t)y * G + (size_t)x;
+                        if (pass == 0) { off[cell]++; total++; }
+                        else { const uint32_t at = off[cell]++; ent[2 * (size_t)at] = slot; ent[2 * (size_t)at + 1] = c.zbits; }
                     }
-                    U0 = std::min(U0, u); U1 = std::max(U1, u); V0 = std::min(V0, v); V1 = std::max(V1, v);
-                }
+                if (pass == 0 && total > RTU_LLIST_MAX_ENTRIES) { too_many = true; break; }
             }
-            if (!ok || !(U1 > U0) || !(V1 > V0)) return false;
-            const double mag = std::max(std::max(std::fabs(U0), std::fabs(U1)), std::max(std::fabs(V0), std::fabs(V1)));
-            if (!std::isfinite(mag) || (U1 - U0) < 1e-4 * mag || (V1 - V0) < 1e-4 * mag) return false;  // no extent a float lookup could resolve
-            // grid size: a triangle of an evenly tessellated surface spans ~ G / sqrt(nf / 2) cells; aim at six of them
-            uint32_t G = 64;
-            static const double kSpan = [] { const char* e = getenv("RTU_LGRID_SPAN"); return e ? atof(e) : 6.0; }();  // tuning knob (any value renders the same image)
-            while (G < RTU_LGRID_MAX && (double)G < kSpan * std::sqrt((double)nf * 0.5)) G *= 2;
-            for (;; G /= 2) {
-                if (G < 16u) { ok = false; break; }
-                // the grid spans the extent plus two cells on every side
-                const double du = (U1 - U0) / ((double)G - 4), dv = (V1 - V0) / ((double)G - 4);
-                const double gu0 = U0 - 2 * du, gv0 = V0 - 2 * dv;
-                // the device's binary32 cell coordinate: (dot(p - L, X) [/ depth] - u0) * su — every operand good to a few ulp
-                const double coord = 16e-7 * ratio * (1.0 + mag);
-                const double err_cells = std::max(coord / du, coord / dv) + 4e-7 * (double)G;
-                if (!(err_cells < 0.25)) continue;  // (a coarser grid has larger cells)
-                const double S0 = 0.25 + err_cells;
-                off.assign((size_t)G * G + 1, 0u);
-                size_t total = 0;
-                bool too_many = false;
-                for (int pass = 0; pass < 2 && !too_many; pass++) {
-                    if (pass == 1) {
-                        uint32_t run = 0;
-                        for (size_t i = 0; i < (size_t)G * G; i++) { const uint32_t n = off[i]; off[i] = run; run += n; }
-                        off[(size_t)G * G] = run;
-                        ent.assign(2 * total, 0u);
-                    }
-                    for (size_t f = 0; f < nf; f++) {
-                        const double* w = cm.verts.data() + 9 * f;
-                        double pu[3], pv[3], dmin = 1e300, umax = 0, vmax = 0;
-                        for (int k = 0; k < 3; k++) {
-                            const double q[3] = {w[3 * k] - L[0], w[3 * k + 1] - L[1], w[3 * k + 2] - L[2]};
-                            double u = q[0] * X[0] + q[1] * X[1] + q[2] * X[2], v = q[0] * Y[0] + q[1] * Y[1] + q[2] * Y[2];
-                            if (point) {
-                                const double depth = q[0] * Z[0] + q[1] * Z[1] + q[2] * Z[2];
-                                dmin = std::min(dmin, depth);
-                                u /= depth; v /= depth;
-                            }
-                            pu[k] = (u - gu0) / du; pv[k] = (v - gv0) / dv;  // in cells
-                            umax = std::max(umax, std::fabs(u)); vmax = std::max(vmax, std::fabs(v));
-                        }
-                        const double wd = wid_of[f] * r3;
-                        double Su, Sv;
-                        if (point) { Su = wd * (1.0 + umax) / (dmin - wd) / du; Sv = wd * (1.0 + vmax) / (dmin - wd) / dv; }  // (dmin > wd: the box corners passed above)
-                        else { Su = wd / du; Sv = wd / dv; }
-                        const double S = S0 + std::max(Su, Sv);
-                        const double bu0 = std::min(pu[0], std::min(pu[1], pu[2])) - S, bu1 = std::max(pu[0], std::max(pu[1], pu[2])) + S;
-                        const double bv0 = std::min(pv[0], std::min(pv[1], pv[2])) - S, bv1 = std::max(pv[0], std::max(pv[1], pv[2])) + S;
-                        int x0 = (int)std::floor(bu0), x1 = (int)std::floor(bu1), y0 = (int)std::floor(bv0), y1 = (int)std::floor(bv1);
-                        x0 = std::max(x0, 0); y0 = std::max(y0, 0);
-                        x1 = std::min(x1, (int)G - 1); y1 = std::min(y1, (int)G - 1);
-                        // the triangle's edges as separating lines: a cell (a square of half-width 0.5 + S about its centre) lies
-                        // beyond edge i when n_i . (centre - v_i) > (|n_i.x| + |n_i.y|) (0.5 + S), n_i the outward normal
-                        const double area2 = (pu[1] - pu[0]) * (pv[2] - pv[0]) - (pu[2] - pu[0]) * (pv[1] - pv[0]);
-                        const bool edges = std::fabs(area2) > 1e-9;  // (an edge-on triangle has no inside: its bounding box is all there is)
-                        double nx[3], ny[3], nd[3];
-                        for (int i = 0; i < 3; i++) {
-                            const int k = (i + 1) % 3;
-                            const double ex = pu[k] - pu[i], ey = pv[k] - pv[i];
-                            const double sg = area2 > 0 ? 1.0 : -1.0;
-                            nx[i] = sg * ey; ny[i] = -sg * ex;  // outward for a counter-clockwise triangle (area2 > 0)
-                            nd[i] = (std::fabs(nx[i]) + std::fabs(ny[i])) * (0.5 + S);
-                        }
-                        const uint32_t slot = cm.slot_of[f];
-                        // the depth (along Z) in front of which an origin cannot see this triangle at all — every point of it, the cull
-                        // margin and the rounding of the device's own depth included, lies beyond (entries are sorted by it)
-                        double zmin = 1e300;
-                        for (int k = 0; k < 3; k++) zmin = std::min(zmin, (w[3 * k] - L[0]) * Z[0] + (w[3 * k + 1] - L[1]) * Z[1] + (w[3 * k + 2] - L[2]) * Z[2]);
-                        zmin -= wd + 8e-6 * (r3 * (double)wscale + std::fabs(L[0]) + std::fabs(L[1]) + std::fabs(L[2]));
-                        float zf = (float)zmin;
-                        if ((double)zf > zmin) zf = std::nextafter(zf, -INFINITY);
-                        uint32_t zbits;
-                        memcpy(&zbits, &zf, 4);
-                        for (int y = y0; y <= y1; y++)
-                            for (int x = x0; x <= x1; x++) {
-                                bool out = false;
-                                if (edges)
-                                    for (int i = 0; i < 3 && !out; i++)
-                                        out = nx[i] * ((double)x + 0.5 - pu[i]) + ny[i] * ((double)y + 0.5 - pv[i]) > nd[i];
-                                if (out) continue;
-                                const size_t cell = (size_t)y * G + (size_t)x;
-                                if (pass == 0) { off[cell]++; total++; }
-                                else { const uint32_t at = off[cell]++; ent[2 * (size_t)at] = slot; ent[2 * (size_t)at + 1] = zbits; }
-                            }
-                        if (pass == 0 && total > ((size_t)32 << 20)) { too_many = true; break; }
-                    }
-                }
-                if (too_many) continue;
-                // pass 1 advanced every offset to the end of its cell: shift back
-                for (size_t i = (size_t)G * G; i > 0; i--) off[i] = off[i - 1];
-                off[0] = 0;
-                {   // nearest to the light first: a walk of the list ends at the first entry that lies beyond the ray's origin
-                    std::vector<std::pair<float, uint32_t>> tmp;
-                    for (size_t cell = 0; cell < (size_t)G * G; cell++) {
-                        const uint32_t b = off[cell], e = off[cell + 1];
-                        if (e - b < 2u) continue;
-                        tmp.clear();
-                        for (uint32_t i = b; i < e; i++) { float z; memcpy(&z, &ent[2 * (size_t)i + 1], 4); tmp.push_back({z, ent[2 * (size_t)i]}); }
-                        std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<float, uint32_t>& a, const std::pair<float, uint32_t>& b2) { return a.first < b2.first; });
-                        for (uint32_t i = b; i < e; i++) { memcpy(&ent[2 * (size_t)i + 1], &tmp[i - b].first, 4); ent[2 * (size_t)i] = tmp[i - b].second; }
-                    }
-                }
-                for (int k = 0; k < 3; k++) { m.X[k] = (float)X[k]; m.Y[k] = (float)Y[k]; m.Z[k] = (float)Z[k]; m.L[k] = (float)L[k]; }
-                m.u0 = (float)gu0; m.v0 = (float)gv0; m.su = (float)(1.0 / du); m.sv = (float)(1.0 / dv);
-                m.point = point ? 1u : 0u;
-                m.G = G;
-                break;
+        }
+        if (too_many) continue;
+        // pass 1 advanced every offset to the end of its cell: shift back
+        for (size_t i = (size_t)G * G; i > 0; i--) off[i] = off[i - 1];
+        off[0] = 0;
+        {   // nearest to the light first: a walk of the list ends at the first entry that lies beyond the ray's origin
+            std::vector<std::pair<float, uint32_t>> tmp;
+            for (size_t cell = 0; cell < (size_t)G * G; cell++) {
+                const uint32_t b = off[cell], e = off[cell + 1];
+                if (e - b < 2u) continue;
+                tmp.clear();
+                for (uint32_t i = b; i < e; i++) { float z; memcpy(&z, &ent[2 * (size_t)i + 1], 4); tmp.push_back({z, ent[2 * (size_t)i]}); }
+                std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<float, uint32_t>& a, const std::pair<float, uint32_t>& b2) { return a.first < b2.first; });
+                for (uint32_t i = b; i < e; i++) { memcpy(&ent[2 * (size_t)i + 1], &tmp[i - b].first, 4); ent[2 * (size_t)i] = tmp[i - b].second; }
             }
-            if (!ok) return false;
+        }
+        ll_mask(F, g, m);
+        break;
     }
     m.usable = 1u;
     return true;
@@ -731,25 +746,25 @@ bool compute_light_list(const RtuLight& l, const CoverMesh& cm, float wscale, Ho
 
 // The triangles of mesh node `node` in world space: every vertex through the chain p -> tm p + pos in binary64; per face its three
 // vertices and their box rounded outwards. fast_elements: slot of the mesh's fast tree -> face.
+LlChain node_chain(const RtuSceneDesc* s, uint32_t node) {
+    LlChain c;
+    memset(&c, 0, sizeof c);
+    for (int j = (int)node; j >= 0 && c.n < RTU_MAX_NODE_DEPTH; j = s->nodes[j].parent, c.n++) {
+        memcpy(c.tm[c.n], s->nodes[j].tm, sizeof c.tm[0]);
+        memcpy(c.pos[c.n], s->nodes[j].pos, sizeof c.pos[0]);
+    }
+    return c;
+}
+
 void make_cover_mesh(const RtuSceneDesc* s, uint32_t node, const std::vector<uint32_t>& fast_elements, CoverMesh& cm) {
     const RtuMesh& m = s->meshes[s->nodes[node].mesh_id];
+    const LlChain chain = node_chain(s, node);
     cm.boxes.assign((size_t)m.nf * 2, make_float4(0, 0, 0, 0));
     cm.verts.assign((size_t)m.nf * 9, 0.0);
     for (uint32_t f = 0; f < m.nf; f++) {
-        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-        for (int v = 0; v < 3; v++) {
-            const float* lp = m.v + 3 * (size_t)m.f[3 * (size_t)f + v];
-            double p[3] = {lp[0], lp[1], lp[2]};
-            for (int j = (int)node; j >= 0; j = s->nodes[j].parent) {
-                const RtuNode& t = s->nodes[j];
-                const double q[3] = {p[0] * t.tm[0] + p[1] * t.tm[3] + p[2] * t.tm[6] + t.pos[0], p[0] * t.tm[1] + p[1] * t.tm[4] + p[2] * t.tm[7] + t.pos[1],
-                                     p[0] * t.tm[2] + p[1] * t.tm[5] + p[2] * t.tm[8] + t.pos[2]};
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-            for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[k]); cm.verts[9 * (size_t)f + 3 * v + k] = p[k]; }
-        }
-        cm.boxes[2 * (size_t)f] = make_float4(std::nextafter((float)lo[0], -INFINITY), std::nextafter((float)lo[1], -INFINITY), std::nextafter((float)lo[2], -INFINITY), 0.0f);
-        cm.boxes[2 * (size_t)f + 1] = make_float4(std::nextafter((float)hi[0], INFINITY), std::nextafter((float)hi[1], INFINITY), std::nextafter((float)hi[2], INFINITY), 0.0f);
+        const uint32_t* fv = m.f + 3 * (size_t)f;
+        ll_cover_face(chain, m.v + 3 * (size_t)fv[0], m.v + 3 * (size_t)fv[1], m.v + 3 * (size_t)fv[2], cm.verts.data() + 9 * (size_t)f,
+                      cm.boxes[2 * (size_t)f], cm.boxes[2 * (size_t)f + 1]);
     }
     cm.slot_of.assign(m.nf, 0u);
     for (uint32_t sl = 0; sl < (uint32_t)fast_elements.size(); sl++) cm.slot_of[fast_elements[sl]] = sl;
@@ -772,24 +787,84 @@ int build_light_lists(RtuContext* ctx, const RtuSceneDesc* s, const std::vector<
             m = hl.m;
             m.usable = 0u;
             int rc;
-            if ((rc = upload(ctx, hl.off.data(), hl.off.size(), &m.cell_off)) != RTU_OK) return rc;
-            if ((rc = upload(ctx, hl.ent.data(), hl.ent.size(), &m.cell_tri)) != RTU_OK) return rc;
+            const int slot = P_LIST + 2 * (int)(j * nc + c);
+            if ((rc = place_upload(ctx, slot, hl.off.data(), hl.off.size(), &m.cell_off)) != RTU_OK) return rc;
+            if ((rc = place_upload(ctx, slot + 1, hl.ent.data(), hl.ent.size(), &m.cell_tri)) != RTU_OK) return rc;
             m.usable = 1u;
             uint32_t longest = 0;
             for (size_t i = 0; i < (size_t)m.G * m.G; i++) longest = std::max(longest, hl.off[i + 1] - hl.off[i]);
             ctx->light_list_info.push_back({(uint32_t)j, c, m.G, (uint32_t)(hl.ent.size() / 2), longest});
         }
-    return upload(ctx, masks.data(), masks.size(), &ds.lmask);
+    ctx->lmask_host = masks;
+    return place_upload(ctx, P_LMASK, masks.data(), masks.size(), &ds.lmask);
+}
+
+// The same lists built on the GPU (rtu_scene_update.hip) from the cover meshes already there: `covers` per masked mesh node,
+// `lohi` the box extents of each. Same decisions, same order, same lists.
+int build_light_lists_device(RtuContext* ctx, const RtuSceneDesc* s, const std::vector<LlCover>& covers, const std::vector<double>& lohi, float wscale,
+                             DevScene& ds) {
+    ds.lmask = nullptr;
+    ctx->lmask_host.clear();
+    std::vector<uint32_t> lights;
+    for (uint32_t i = 0; i < s->n_lights && lights.size() < RTU_LMASK_LIGHTS; i++)
+        if (s->lights[i].type != RTU_LIGHT_AMBIENT) lights.push_back(i);
+    const uint32_t nc = (uint32_t)covers.size();
+    if (lights.empty() || nc == 0) return RTU_OK;
+    std::vector<DevLightMask> masks(lights.size() * nc);
+    memset(masks.data(), 0, masks.size() * sizeof(DevLightMask));
+    std::vector<LlFrame> frames;
+    std::vector<int> pair_cover, pair_of;  // pairs with a frame: their cover node and their index j * nc + c
+    for (size_t j = 0; j < lights.size(); j++)
+        for (uint32_t c = 0; c < nc; c++) {
+            LlFrame F;
+            if (!ll_frame(s->lights[lights[j]], &lohi[6 * c], &lohi[6 * c + 3], F)) continue;
+            frames.push_back(F);
+            pair_cover.push_back((int)c);
+            pair_of.push_back((int)(j * nc + c));
+        }
+    std::vector<double> ext(6 * frames.size() + 6);
+    RTU_HIP(ctx, ll_build_extents(ctx->llb, ctx->stream, covers.data(), pair_cover.data(), frames.data(), (int)frames.size(), wscale, ext.data()));
+    for (size_t p = 0; p < frames.size(); p++) {
+        const double* e = &ext[6 * p];
+        double mag;
+        if (e[5] == 0.0 || !ll_extent_ok(e[0], e[1], e[2], e[3], mag)) continue;
+        const int c = pair_cover[p];
+        const LlCover& cv = covers[(size_t)c];
+        LlGrid g;
+        for (uint32_t G = ll_first_grid(cv.nf); G >= 16u; G /= 2) {
+            if (!ll_grid_at(G, e[0], e[1], e[2], e[3], e[4], mag, g)) continue;
+            size_t entries = 0;
+            RTU_HIP(ctx, ll_count(ctx->llb, ctx->stream, cv, c, frames[p], g, wscale, &entries));
+            if (entries > RTU_LLIST_MAX_ENTRIES) continue;
+            DevLightMask& m = masks[(size_t)pair_of[p]];
+            ll_mask(frames[p], g, m);
+            const int slot = P_LIST + 2 * pair_of[p];
+            void *off = nullptr, *ent = nullptr;
+            int rc;
+            if ((rc = ensure_place(ctx, slot, sizeof(uint32_t) * ((size_t)G * G + 1), &off)) != RTU_OK) return rc;
+            if ((rc = ensure_place(ctx, slot + 1, sizeof(uint32_t) * 2 * entries, &ent)) != RTU_OK) return rc;
+            uint32_t longest = 0;
+            RTU_HIP(ctx, ll_fill(ctx->llb, ctx->stream, cv, g, (uint32_t*)off, (uint32_t*)ent, &longest));
+            m.cell_off = (const uint32_t*)off;
+            m.cell_tri = (const uint32_t*)ent;
+            m.usable = 1u;
+            ctx->light_list_info.push_back({(uint32_t)(pair_of[p] / (int)nc), (uint32_t)c, G, (uint32_t)entries, longest});
+            break;
+        }
+    }
+    ctx->lmask_host = masks;
+    return place_upload(ctx, P_LMASK, masks.data(), masks.size(), &ds.lmask);
 }
 
 // Reject anything the kernel's indexing does not expect, so that a malformed
-// scene is an error code and never an out-of-bounds access on the GPU.
-int validate(RtuContext* ctx, const RtuSceneDesc* s) {
+// scene is an error code and never an out-of-bounds access on the GPU. placement: the mesh and texture arrays are the uploaded
+// ones (rtu_update_scene): only what an update may change is checked.
+int validate(RtuContext* ctx, const RtuSceneDesc* s, bool placement = false) {
     if (!s || !s->nodes || s->n_nodes == 0) return fail(ctx, RTU_ERR_ARG, "scene has no nodes");
     if (s->n_materials && !s->materials) return fail(ctx, RTU_ERR_ARG, "materials is NULL");
     if (s->n_lights && !s->lights) return fail(ctx, RTU_ERR_ARG, "lights is NULL");
     if (s->n_meshes && !s->meshes) return fail(ctx, RTU_ERR_ARG, "meshes is NULL");
-    for (uint32_t i = 0; i < s->n_textures; i++) {
+    for (uint32_t i = 0; i < s->n_textures && !placement; i++) {
         const RtuTexture& t = s->textures[i];
         if (t.type != RTU_TEX_FILE && t.type != RTU_TEX_CHECKER) return fail(ctx, RTU_ERR_ARG, "texture %u: unknown type", i);
         if (t.type == RTU_TEX_FILE && (t.width < 0 || t.height < 0 || ((size_t)t.width * t.height > 0 && !t.rgb)))
@@ -826,7 +901,7 @@ int validate(RtuContext* ctx, const RtuSceneDesc* s) {
             return fail(ctx, RTU_ERR_ARG, "node %u: bad mesh id", i);
         if (n.material_id >= (int)s->n_materials) return fail(ctx, RTU_ERR_ARG, "node %u: bad material id", i);
     }
-    for (uint32_t mi = 0; mi < s->n_meshes; mi++) {
+    for (uint32_t mi = 0; mi < s->n_meshes && !placement; mi++) {
         const RtuMesh& m = s->meshes[mi];
         if (!m.v || !m.f || !m.vn || !m.fn || !m.bvh || !m.elements)
             return fail(ctx, RTU_ERR_ARG, "mesh %u: missing array (normals are required, objects.h:56)", mi);
@@ -1581,6 +1656,7 @@ const char* rtu_error_string(int err) {
         case RTU_ERR_NO_DEVICE: return "no such GPU";
         case RTU_ERR_CAPACITY: return "recursion frame capacity exceeded";
         case RTU_ERR_CANCELLED: return "cancelled";
+        case RTU_ERR_SCENE_SHAPE: return "scene shape differs from the uploaded scene";
     }
     return "unknown error";
 }
@@ -1619,6 +1695,7 @@ void rtu_destroy_context(RtuContext* ctx) {
     if (ctx->aux_ev1) (void)hipEventDestroy(ctx->aux_ev1);
     if (ctx->fcnt_side) (void)hipFree(ctx->fcnt_side);
     free_scene(ctx);
+    ll_builder_destroy(ctx->llb);
     free_levels(ctx);
     if (ctx->fcnt) (void)hipFree(ctx->fcnt);
     if (ctx->tl) (void)hipFree(ctx->tl);
@@ -1660,14 +1737,16 @@ int rtu_validate_scene(const RtuSceneDesc* s, char* err_buf, size_t err_len) {
     return rc;
 }
 
-int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
-    if (!ctx) return RTU_ERR_ARG;
-    int rc = validate(ctx, s);
-    if (rc != RTU_OK) return rc;
-    RTU_HIP(ctx, hipSetDevice(ctx->device));
-    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    free_scene(ctx);
+}  // extern "C"
 
+namespace {
+
+// Everything that depends on where things are placed, on the lights or on the materials, into the placement buffers: nodes,
+// node-level bounds, cover meshes, plane quads, occluder lists, materials, lights, and the host flags derived from them. Mesh and
+// texture records of ctx->dscene stay. on_device: cover meshes and occluder lists from the meshes already in HBM
+// (rtu_scene_update.hip; s->meshes is then read for its headers only); otherwise on the host from s->meshes.
+int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
+    int rc;
     // scene-graph nodes with their ancestor chains
     std::vector<DevNode> nodes(s->n_nodes);
     for (uint32_t i = 0; i < s->n_nodes; i++) {
@@ -1689,13 +1768,209 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         }
     }
 
+
     const float wscale = world_bounds(s, nodes);
+    DevScene ds = ctx->dscene;
+    if ((rc = place_upload(ctx, P_NODES, nodes.data(), nodes.size(), &ds.nodes)) != RTU_OK) return rc;
+    if ((rc = place_upload(ctx, P_MATERIALS, s->materials, (size_t)s->n_materials, &ds.materials)) != RTU_OK) return rc;
+    if ((rc = place_upload(ctx, P_LIGHTS, s->lights, (size_t)s->n_lights, &ds.lights)) != RTU_OK) return rc;
+    if (ds.textured) {
+        if (s->material_maps)
+            if ((rc = place_upload(ctx, P_MATMAPS, s->material_maps, (size_t)s->n_materials * 4, &ds.mat_maps)) != RTU_OK) return rc;
+        ds.bg_map = s->background_map;
+        ds.env_map = s->environment_map;
+    }
+    ds.bg = s->background;
+    ds.env = s->environment;
+    ds.img_w = s->camera.img_width;
+    ds.img_h = s->camera.img_height;
+    ds.wscale = wscale;
+    ds.nol_ok = 1;
+    for (uint32_t i = 0; i < s->n_lights; i++)
+        for (int k = 0; k < 3; k++)
+            if (!(std::fabs(s->lights[i].intensity[k]) < 1e15f)) ds.nol_ok = 0;
+    ds.n_cover = 0;
+    ctx->cover_faces = 0;
+    std::vector<CoverMesh> cover_host;  // per masked mesh node: the world-space boxes and vertices of its triangles
+    std::vector<LlCover> cover_dev;     // ... or where the device builder finds and puts them
+    for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++) {
+        if (s->nodes[i].obj_type == RTU_OBJ_TRIMESH && ds.n_cover < RTU_MAX_COVER) {
+            const uint32_t c = ds.n_cover++;
+            const int mid = s->nodes[i].mesh_id;
+            const uint32_t nf = s->meshes[mid].nf;
+            ds.cover_node[c] = (int32_t)i;
+            if (nf > ctx->cover_faces) ctx->cover_faces = nf;
+            void* box = nullptr;
+            if ((rc = ensure_place(ctx, P_COVER + (int)c, sizeof(float4) * 2 * (size_t)nf, &box)) != RTU_OK) return rc;
+            ds.cover_box[c] = (const float4*)box;
+            ds.cover_nf[c] = nf;
+            if (on_device) {
+                LlCover cv;
+                cv.f = ctx->dmeshes[(size_t)mid].f;
+                cv.v = ctx->dmeshes[(size_t)mid].v;
+                cv.slot_of = ctx->slot_of[(size_t)mid];
+                cv.nf = nf;
+                cv.chain = node_chain(s, i);
+                cv.boxes = (float4*)box;
+                cover_dev.push_back(cv);
+            } else {
+                CoverMesh cm;
+                make_cover_mesh(s, i, ctx->fast_elements[(size_t)mid], cm);
+                RTU_HIP(ctx, hipMemcpy(box, cm.boxes.data(), sizeof(float4) * cm.boxes.size(), hipMemcpyHostToDevice));
+                cover_host.push_back(std::move(cm));
+            }
+        }
+    }
+    std::vector<double> lohi(6 * (size_t)ds.n_cover + 6);
+    if (on_device) RTU_HIP(ctx, ll_build_covers(ctx->llb, ctx->stream, cover_dev.data(), (int)cover_dev.size(), lohi.data()));
+    // plane nodes with a coverage mask: the corners of the node's unit square in world space (k_plane_cover)
+    ds.n_pcover = 0;
+    for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++) {
+        if (s->nodes[i].obj_type != RTU_OBJ_PLANE || ds.n_pcover >= RTU_MAX_PCOVER) continue;
+        static const double sq[4][2] = {{-1, -1}, {1, -1}, {1, 1}, {-1, 1}};
+        float quad[4][3];
+        bool finite = true;
+        for (int c = 0; c < 4; c++) {
+            double p[3] = {sq[c][0], sq[c][1], 0.0};
+            for (int j = (int)i; j >= 0; j = s->nodes[j].parent) {
+                const RtuNode& t = s->nodes[j];
+                const double q[3] = {p[0] * t.tm[0] + p[1] * t.tm[3] + p[2] * t.tm[6] + t.pos[0], p[0] * t.tm[1] + p[1] * t.tm[4] + p[2] * t.tm[7] + t.pos[1],
+                                     p[0] * t.tm[2] + p[1] * t.tm[5] + p[2] * t.tm[8] + t.pos[2]};
+                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+            }
+            for (int k = 0; k < 3; k++) { quad[c][k] = (float)p[k]; finite = finite && std::isfinite(quad[c][k]); }
+        }
+        if (!finite) continue;  // NaN / infinite transformation: no mask (the node's rectangle is the whole image as well)
+        ds.pcover_node[ds.n_pcover] = (int32_t)i;
+        memcpy(ds.pcover_quad[ds.n_pcover], quad, sizeof quad);
+        ds.n_pcover++;
+    }
+    ctx->light_list_info.clear();
+    rc = on_device ? build_light_lists_device(ctx, s, cover_dev, lohi, wscale, ds) : build_light_lists(ctx, s, cover_host, wscale, ds);
+    if (rc != RTU_OK) return rc;
+    ds.obj_mask = 0;
+    for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++)
+        if (s->nodes[i].obj_type != RTU_OBJ_NONE) ds.obj_mask |= 1ull << i;
+    ds.n_lights = s->n_lights;
+    env_value(s->background, ds.background);
+    env_value(s->environment, ds.environment);
+    ctx->dscene = ds;
+    ctx->nsl = 0;
+    for (uint32_t i = 0; i < s->n_lights; i++)
+        if (s->lights[i].type != RTU_LIGHT_AMBIENT) {
+            if (ctx->nsl < RTU_FI_NOL_LIGHTS) {
+                for (int k = 0; k < 3; k++) ctx->nol_light[ctx->nsl][k] = s->lights[i].vec[k];
+                ctx->nol_light[ctx->nsl][3] = s->lights[i].type == RTU_LIGHT_DIRECT ? 1.0f : 0.0f;
+            }
+            ctx->shadow_light[ctx->nsl++] = (int32_t)i;
+        }
+    memset(ctx->want_cap_s, 0, sizeof ctx->want_cap_s);
+    ctx->want_defer_s = 0;
+    ctx->tail_hint = 0;
+    ctx->tail_hints.clear();
+    ctx->list_hints.clear();
+    ctx->mesh_hits_childless = true;
+    for (uint32_t i = 0; i < s->n_nodes; i++) {
+        const RtuNode& nd = s->nodes[i];
+        if (nd.obj_type != RTU_OBJ_TRIMESH || nd.material_id < 0) continue;
+        const RtuMaterial& mm = s->materials[nd.material_id];
+        for (int k = 0; k < 3; k++)
+            if (mm.reflection[k] != 0 || mm.refraction[k] != 0) ctx->mesh_hits_childless = false;
+    }
+    ctx->side_off.clear();
+    ctx->side_frames.clear();
+    ctx->occ_hints.clear();
+    ctx->any_recursive_material = false;
+    for (uint32_t i = 0; i < s->n_materials; i++) {
+        const RtuMaterial& mm = s->materials[i];
+        for (int k = 0; k < 3; k++)
+            if (mm.reflection[k] != 0 || mm.refraction[k] != 0) ctx->any_recursive_material = true;
+    }
+    ctx->scene_stochastic = false;
+    ctx->stochastic_what.clear();
+    if (s->camera.dof != 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "depth of field"; }
+    for (uint32_t i = 0; i < s->n_lights && !ctx->scene_stochastic; i++)
+        if (s->lights[i].type == RTU_LIGHT_POINT && s->lights[i].size > 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "a soft shadow"; }
+    for (uint32_t i = 0; i < s->n_materials && !ctx->scene_stochastic; i++)
+        if (s->materials[i].reflection_glossiness > 0 || s->materials[i].refraction_glossiness > 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "a glossy bounce"; }
+    ctx->n_textures = s->n_textures;
+    ctx->mat_maps_host.clear();
+    if (s->n_textures > 0 && s->material_maps) ctx->mat_maps_host.assign(s->material_maps, s->material_maps + (size_t)s->n_materials * 4);
+    return RTU_OK;
+}
+
+// what rtu_update_scene keeps fixed (rtu_render.h): "" or the first difference between the uploaded scene `a` and `b`
+std::string shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b) {
+    char buf[200];
+    if (a->n_nodes != b->n_nodes) { snprintf(buf, sizeof buf, "n_nodes %u != %u", b->n_nodes, a->n_nodes); return buf; }
+    for (uint32_t i = 0; i < a->n_nodes; i++) {
+        const RtuNode &x = a->nodes[i], &y = b->nodes[i];
+        const char* what = x.parent != y.parent ? "parent" : x.obj_type != y.obj_type ? "obj_type" : x.mesh_id != y.mesh_id ? "mesh_id"
+                         : x.depth != y.depth ? "depth" : x.subtree_end != y.subtree_end ? "subtree_end" : nullptr;
+        if (what) { snprintf(buf, sizeof buf, "node %u: %s differs", i, what); return buf; }
+    }
+    if (a->n_meshes != b->n_meshes) { snprintf(buf, sizeof buf, "n_meshes %u != %u", b->n_meshes, a->n_meshes); return buf; }
+    for (uint32_t i = 0; i < a->n_meshes; i++) {
+        const RtuMesh &x = a->meshes[i], &y = b->meshes[i];
+        const char* what = x.nv != y.nv ? "nv" : x.nf != y.nf ? "nf" : x.nvn != y.nvn ? "nvn" : x.nvt != y.nvt ? "nvt"
+                         : x.n_bvh_nodes != y.n_bvh_nodes ? "n_bvh_nodes" : nullptr;
+        if (what) { snprintf(buf, sizeof buf, "mesh %u: %s differs", i, what); return buf; }
+    }
+    if (a->n_textures != b->n_textures) { snprintf(buf, sizeof buf, "n_textures %u != %u", b->n_textures, a->n_textures); return buf; }
+    for (uint32_t i = 0; i < a->n_textures; i++) {
+        const RtuTexture &x = a->textures[i], &y = b->textures[i];
+        const char* what = x.type != y.type ? "type" : x.width != y.width ? "width" : x.height != y.height ? "height" : nullptr;
+        if (what) { snprintf(buf, sizeof buf, "texture %u: %s differs", i, what); return buf; }
+    }
+    if (a->n_materials != b->n_materials) { snprintf(buf, sizeof buf, "n_materials %u != %u", b->n_materials, a->n_materials); return buf; }
+    if ((a->material_maps != nullptr) != (b->material_maps != nullptr)) return "material_maps present in one scene only";
+    return "";
+}
+
+// the arrays shape_diff reads must be there
+int shape_args(RtuContext* ctx, const RtuSceneDesc* s) {
+    if (!s || !s->nodes || s->n_nodes == 0) return fail(ctx, RTU_ERR_ARG, "scene has no nodes");
+    if (s->n_meshes && !s->meshes) return fail(ctx, RTU_ERR_ARG, "meshes is NULL");
+    if (s->n_textures && !s->textures) return fail(ctx, RTU_ERR_ARG, "textures is NULL");
+    return RTU_OK;
+}
+
+// the uploaded scene's shape as a description (headers only)
+RtuSceneDesc shape_desc(const RtuContext* ctx) {
+    static const RtuTexMap present{};
+    RtuSceneDesc d;
+    memset(&d, 0, sizeof d);
+    d.n_nodes = (uint32_t)ctx->shape_nodes.size();
+    d.nodes = ctx->shape_nodes.data();
+    d.n_meshes = (uint32_t)ctx->shape_meshes.size();
+    d.meshes = ctx->shape_meshes.data();
+    d.n_textures = (uint32_t)ctx->shape_textures.size();
+    d.textures = ctx->shape_textures.data();
+    d.n_materials = ctx->shape_materials;
+    d.material_maps = ctx->shape_maps ? &present : nullptr;
+    return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = validate(ctx, s);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->aux_stream) RTU_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
+    free_scene(ctx);
+    ctx->slot_of.clear();
 
     // meshes
     std::vector<RtuContext::MeshInfo> mesh_info;
     std::vector<DevMesh> meshes(s->n_meshes);
     std::vector<uint32_t> fast_nodes(s->n_meshes, 0);
     std::vector<std::vector<uint32_t>> fast_elements(s->n_meshes);  // per mesh: slot of the fast tree's leaf order -> face
+    std::vector<uint32_t> slot_of;
     uint32_t stack_needed = 1;
     for (uint32_t mi = 0; mi < s->n_meshes; mi++) {
         const RtuMesh& m = s->meshes[mi];
@@ -1742,6 +2017,11 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         if ((rc = upload(ctx, tri.data(), tri.size(), &d.fast.tri)) != RTU_OK) return rc;
         if ((rc = upload(ctx, sah.elements.data(), sah.elements.size(), &d.fast.elements)) != RTU_OK) return rc;
         fast_elements[mi] = sah.elements;
+        slot_of.assign(m.nf, 0u);  // its inverse, for the device builder of rtu_update_scene
+        for (uint32_t sl = 0; sl < (uint32_t)sah.elements.size(); sl++) slot_of[sah.elements[sl]] = sl;
+        const uint32_t* d_slot_of = nullptr;
+        if ((rc = upload(ctx, slot_of.data(), slot_of.size(), &d_slot_of)) != RTU_OK) return rc;
+        ctx->slot_of.push_back(d_slot_of);
         std::vector<float4> wide8;
         build_wide8(sah, sub_first, sub_total, wide8);
         if ((rc = upload(ctx, wide8.data(), wide8.size(), &d.bvh8)) != RTU_OK) return rc;
@@ -1788,9 +2068,6 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
 
     DevScene ds;
     memset(&ds, 0, sizeof ds);
-    if ((rc = upload(ctx, nodes.data(), nodes.size(), &ds.nodes)) != RTU_OK) return rc;
-    if ((rc = upload(ctx, s->materials, (size_t)s->n_materials, &ds.materials)) != RTU_OK) return rc;
-    if ((rc = upload(ctx, s->lights, (size_t)s->n_lights, &ds.lights)) != RTU_OK) return rc;
     if ((rc = upload(ctx, meshes.data(), meshes.size(), &ds.meshes)) != RTU_OK) return rc;
     // textures
     ds.textured = (s->n_textures > 0) ? 1u : 0u;
@@ -1807,65 +2084,10 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
                 if ((rc = upload(ctx, t.rgb, (size_t)t.width * t.height * 3, &o.rgb)) != RTU_OK) return rc;
         }
         if ((rc = upload(ctx, texs.data(), texs.size(), &ds.textures)) != RTU_OK) return rc;
-        if (s->material_maps)
-            if ((rc = upload(ctx, s->material_maps, (size_t)s->n_materials * 4, &ds.mat_maps)) != RTU_OK) return rc;
-        ds.bg_map = s->background_map;
-        ds.env_map = s->environment_map;
     }
-    ds.bg = s->background;
-    ds.env = s->environment;
-    ds.img_w = s->camera.img_width;
-    ds.img_h = s->camera.img_height;
     ctx->textured = ds.textured != 0;
     ds.n_nodes = s->n_nodes;
     ds.walk_stack_limit = 0xFFFFu;
-    ds.wscale = wscale;
-    ds.nol_ok = 1;
-    for (uint32_t i = 0; i < s->n_lights; i++)
-        for (int k = 0; k < 3; k++)
-            if (!(std::fabs(s->lights[i].intensity[k]) < 1e15f)) ds.nol_ok = 0;
-    ds.n_cover = 0;
-    ctx->cover_faces = 0;
-    std::vector<CoverMesh> cover_host;  // per masked mesh node: the world-space boxes and vertices of its triangles
-    for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++) {
-        if (s->nodes[i].obj_type == RTU_OBJ_TRIMESH && ds.n_cover < RTU_MAX_COVER) {
-            ds.cover_node[ds.n_cover++] = (int32_t)i;
-            const RtuMesh& m = s->meshes[s->nodes[i].mesh_id];
-            if (m.nf > ctx->cover_faces) ctx->cover_faces = m.nf;
-            CoverMesh cm;
-            make_cover_mesh(s, i, fast_elements[s->nodes[i].mesh_id], cm);
-            if ((rc = upload(ctx, cm.boxes.data(), cm.boxes.size(), &ds.cover_box[ds.n_cover - 1])) != RTU_OK) return rc;
-            ds.cover_nf[ds.n_cover - 1] = m.nf;
-            cover_host.push_back(std::move(cm));
-        }
-    }
-    // plane nodes with a coverage mask: the corners of the node's unit square in world space (k_plane_cover)
-    ds.n_pcover = 0;
-    for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++) {
-        if (s->nodes[i].obj_type != RTU_OBJ_PLANE || ds.n_pcover >= RTU_MAX_PCOVER) continue;
-        static const double sq[4][2] = {{-1, -1}, {1, -1}, {1, 1}, {-1, 1}};
-        float quad[4][3];
-        bool finite = true;
-        for (int c = 0; c < 4; c++) {
-            double p[3] = {sq[c][0], sq[c][1], 0.0};
-            for (int j = (int)i; j >= 0; j = s->nodes[j].parent) {
-                const RtuNode& t = s->nodes[j];
-                const double q[3] = {p[0] * t.tm[0] + p[1] * t.tm[3] + p[2] * t.tm[6] + t.pos[0], p[0] * t.tm[1] + p[1] * t.tm[4] + p[2] * t.tm[7] + t.pos[1],
-                                     p[0] * t.tm[2] + p[1] * t.tm[5] + p[2] * t.tm[8] + t.pos[2]};
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-            for (int k = 0; k < 3; k++) { quad[c][k] = (float)p[k]; finite = finite && std::isfinite(quad[c][k]); }
-        }
-        if (!finite) continue;  // NaN / infinite transformation: no mask (the node's rectangle is the whole image as well)
-        ds.pcover_node[ds.n_pcover] = (int32_t)i;
-        memcpy(ds.pcover_quad[ds.n_pcover], quad, sizeof quad);
-        ds.n_pcover++;
-    }
-    ctx->light_list_info.clear();
-    if ((rc = build_light_lists(ctx, s, cover_host, wscale, ds)) != RTU_OK) return rc;
-    ds.obj_mask = 0;
-    for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++)
-        if (s->nodes[i].obj_type != RTU_OBJ_NONE) ds.obj_mask |= 1ull << i;
     ds.node_bounds = 1;
     {   // screen rectangles of the node-level bounds, one set per frame in flight (written by k_node_rects on every launch)
         void* d = nullptr;
@@ -1873,56 +2095,59 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         ctx->scene_allocs.push_back(d);
         ctx->node_rects = static_cast<int4*>(d);
     }
-    ds.n_lights = s->n_lights;
-    env_value(s->background, ds.background);
-    env_value(s->environment, ds.environment);
-    ctx->dscene = ds;
-    ctx->nsl = 0;
-    for (uint32_t i = 0; i < s->n_lights; i++)
-        if (s->lights[i].type != RTU_LIGHT_AMBIENT) {
-            if (ctx->nsl < RTU_FI_NOL_LIGHTS) {
-                for (int k = 0; k < 3; k++) ctx->nol_light[ctx->nsl][k] = s->lights[i].vec[k];
-                ctx->nol_light[ctx->nsl][3] = s->lights[i].type == RTU_LIGHT_DIRECT ? 1.0f : 0.0f;
-            }
-            ctx->shadow_light[ctx->nsl++] = (int32_t)i;
-        }
-    memset(ctx->want_cap_s, 0, sizeof ctx->want_cap_s);
-    ctx->want_defer_s = 0;
-    ctx->tail_hint = 0;
-    ctx->tail_hints.clear();
-    ctx->list_hints.clear();
     ctx->n_meshes = s->n_meshes;
     ctx->mesh_info = mesh_info;
-    ctx->mesh_hits_childless = true;
-    for (uint32_t i = 0; i < s->n_nodes; i++) {
-        const RtuNode& nd = s->nodes[i];
-        if (nd.obj_type != RTU_OBJ_TRIMESH || nd.material_id < 0) continue;
-        const RtuMaterial& mm = s->materials[nd.material_id];
-        for (int k = 0; k < 3; k++)
-            if (mm.reflection[k] != 0 || mm.refraction[k] != 0) ctx->mesh_hits_childless = false;
-    }
-    ctx->side_off.clear();
-    ctx->side_frames.clear();
-    ctx->occ_hints.clear();
-    ctx->any_recursive_material = false;
-    for (uint32_t i = 0; i < s->n_materials; i++) {
-        const RtuMaterial& mm = s->materials[i];
-        for (int k = 0; k < 3; k++)
-            if (mm.reflection[k] != 0 || mm.refraction[k] != 0) ctx->any_recursive_material = true;
-    }
-    ctx->scene_stochastic = false;
-    ctx->stochastic_what.clear();
-    if (s->camera.dof != 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "depth of field"; }
-    for (uint32_t i = 0; i < s->n_lights && !ctx->scene_stochastic; i++)
-        if (s->lights[i].type == RTU_LIGHT_POINT && s->lights[i].size > 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "a soft shadow"; }
-    for (uint32_t i = 0; i < s->n_materials && !ctx->scene_stochastic; i++)
-        if (s->materials[i].reflection_glossiness > 0 || s->materials[i].refraction_glossiness > 0) { ctx->scene_stochastic = true; ctx->stochastic_what = "a glossy bounce"; }
     ctx->bvh_stack_needed = stack_needed;
-    ctx->n_textures = s->n_textures;
-    ctx->mat_maps_host.clear();
-    if (s->n_textures > 0 && s->material_maps) ctx->mat_maps_host.assign(s->material_maps, s->material_maps + (size_t)s->n_materials * 4);
+    // the shape (rtu_update_scene) and what an update builds from
+    ctx->shape_nodes.assign(s->nodes, s->nodes + s->n_nodes);
+    ctx->shape_meshes.assign(s->meshes, s->meshes + s->n_meshes);
+    for (RtuMesh& m : ctx->shape_meshes) { m.v = nullptr; m.f = nullptr; m.vn = nullptr; m.fn = nullptr; m.vt = nullptr; m.ft = nullptr; m.bvh = nullptr; m.elements = nullptr; }
+    ctx->shape_textures.assign(s->textures, s->textures + s->n_textures);
+    for (RtuTexture& t : ctx->shape_textures) t.rgb = nullptr;
+    ctx->shape_materials = s->n_materials;
+    ctx->shape_maps = s->material_maps != nullptr;
+    ctx->fast_elements = std::move(fast_elements);
+    ctx->dmeshes = meshes;
+    ctx->dscene = ds;
+    if ((rc = place_scene(ctx, s, false)) != RTU_OK) return rc;
     ctx->has_scene = true;
     return RTU_OK;
+}
+
+int rtu_update_scene(RtuContext* ctx, const RtuSceneDesc* s) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    // everything is checked before anything is written: a refused update leaves the context as it was
+    int rc = shape_args(ctx, s);
+    if (rc != RTU_OK) return rc;
+    const RtuSceneDesc up = shape_desc(ctx);
+    const std::string diff = shape_diff(&up, s);
+    if (!diff.empty()) return fail(ctx, RTU_ERR_SCENE_SHAPE, "not the uploaded scene's shape: %s", diff.c_str());
+    RtuSceneDesc placed = *s;  // the mesh and texture arrays are the uploaded ones: only their headers are read
+    placed.meshes = ctx->shape_meshes.data();
+    placed.textures = ctx->shape_textures.data();
+    if ((rc = validate(ctx, &placed, true)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers rewritten below
+    if (ctx->aux_stream) RTU_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
+    if (!ctx->llb) ctx->llb = ll_builder_create();
+    if ((rc = place_scene(ctx, &placed, true)) != RTU_OK) {
+        free_scene(ctx);  // half placed: nothing to render from
+        return rc;
+    }
+    return RTU_OK;
+}
+
+int rtu_scene_shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b, char* err_buf, size_t err_len) {
+    RtuContext tmp;  // plain host state: nothing here touches a GPU
+    int rc = shape_args(&tmp, a);
+    if (rc == RTU_OK) rc = shape_args(&tmp, b);
+    if (rc == RTU_OK) {
+        const std::string d = shape_diff(a, b);
+        if (!d.empty()) rc = fail(&tmp, RTU_ERR_SCENE_SHAPE, "%s", d.c_str());
+    }
+    if (err_buf && err_len) snprintf(err_buf, err_len, "%s", tmp.error.c_str());
+    return rc;
 }
 
 // CalculateImageOrigin + the u,v of CalculateCurrentPoint (RenderFunctions.cpp:243-269)
@@ -2436,6 +2661,52 @@ void rtu_debug_light_list_free(RtuLightListDump* d) {
     if (!d) return;
     free(d->cell_off); free(d->entry_face); free(d->entry_zmin);
     d->cell_off = nullptr; d->entry_face = nullptr; d->entry_zmin = nullptr;
+}
+
+int rtu_debug_context_light_list(RtuContext* ctx, uint32_t index, RtuLightListDump* out) {
+    if (!ctx || !out) return RTU_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (index >= ctx->light_list_info.size()) return fail(ctx, RTU_ERR_ARG, "no list %u", index);
+    const RtuContext::LightListInfo& li = ctx->light_list_info[index];
+    const uint32_t nc = ctx->dscene.n_cover;
+    const DevLightMask& m = ctx->lmask_host[(size_t)li.light * nc + li.cover];
+    const int node = ctx->dscene.cover_node[li.cover];
+    const std::vector<uint32_t>& elements = ctx->fast_elements[(size_t)ctx->shape_nodes[(size_t)node].mesh_id];
+    out->node = node;
+    out->light = ctx->shadow_light[li.light];
+    out->usable = 1;
+    out->G = m.G;
+    out->point = m.point;
+    memcpy(out->X, m.X, sizeof out->X); memcpy(out->Y, m.Y, sizeof out->Y); memcpy(out->Z, m.Z, sizeof out->Z); memcpy(out->L, m.L, sizeof out->L);
+    out->u0 = m.u0; out->v0 = m.v0; out->su = m.su; out->sv = m.sv;
+    out->n_entries = li.entries;
+    const size_t n_off = (size_t)m.G * m.G + 1;
+    std::vector<uint32_t> ent(2 * (size_t)li.entries);
+    out->cell_off = (uint32_t*)malloc(n_off * sizeof(uint32_t));
+    out->entry_face = (uint32_t*)malloc(((size_t)li.entries + 1) * sizeof(uint32_t));
+    out->entry_zmin = (float*)malloc(((size_t)li.entries + 1) * sizeof(float));
+    if (!out->cell_off || !out->entry_face || !out->entry_zmin) { rtu_debug_light_list_free(out); return RTU_ERR_ARG; }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipMemcpy(out->cell_off, m.cell_off, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!ent.empty()) RTU_HIP(ctx, hipMemcpy(ent.data(), m.cell_tri, ent.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < li.entries; e++) {
+        const uint32_t slot = ent[2 * e];
+        out->entry_face[e] = slot < elements.size() ? elements[slot] : 0xFFFFFFFFu;  // slot of the fast tree -> face of the mesh
+        memcpy(&out->entry_zmin[e], &ent[2 * e + 1], 4);
+    }
+    return RTU_OK;
+}
+
+int rtu_debug_update_timing(RtuContext* ctx, int on, float* ms_out5) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!ctx->llb) ctx->llb = ll_builder_create();
+    LlTimes t;
+    ll_get_times(ctx->llb, &t, true);
+    if (ms_out5) { ms_out5[0] = t.cover_ms; ms_out5[1] = t.extent_ms; ms_out5[2] = t.count_ms; ms_out5[3] = t.fill_ms; ms_out5[4] = t.sort_ms; }
+    (void)hipSetDevice(ctx->device);
+    ll_set_timing(ctx->llb, on != 0);
+    return RTU_OK;
 }
 
 int rtu_light_list_info(const RtuContext* ctx, uint32_t index, uint32_t* out5) {

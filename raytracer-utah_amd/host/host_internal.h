@@ -48,6 +48,10 @@ struct Scene {
 
 }  // namespace rtu
 
+struct RtuScene {
+    rtu::Scene* impl;
+};
+
 extern "C" RtuScene* rtu_scene_wrap(rtu::Scene* s);
 
 #endif

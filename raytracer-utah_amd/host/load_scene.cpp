@@ -652,3 +652,62 @@ extern "C" RtuScene* rtu_scene_load_xml(const char* xml_path, const char* remap_
     }
     return rtu_scene_wrap(s);
 }
+
+// ---- moving things in a loaded scene: one more Transformation::Scale / Rotate / Translate on a flattened node ----
+namespace {
+
+rtu::Scene* scene_of(RtuScene* scene) { return scene ? scene->impl : nullptr; }
+
+// Transformation::Transform (scene.h:246) on the node's tm / pos, itm from the new tm
+int node_transform(RtuScene* scene, uint32_t node, const rtu::Matrix3& m) {
+    rtu::Scene* s = scene_of(scene);
+    if (!s || node >= s->nodes.size()) return -1;
+    RtuNode& n = s->nodes[node];
+    rtu::Matrix3 tm, itm;
+    memcpy(tm.data, n.tm, sizeof tm.data);
+    rtu::Point3 pos(n.pos[0], n.pos[1], n.pos[2]);
+    tm = m * tm;
+    pos = m * pos;
+    tm.GetInverse(itm);
+    memcpy(n.tm, tm.data, sizeof n.tm);
+    memcpy(n.itm, itm.data, sizeof n.itm);
+    n.pos[0] = pos.x; n.pos[1] = pos.y; n.pos[2] = pos.z;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rtu_scene_node_scale(RtuScene* scene, uint32_t node, float sx, float sy, float sz) {
+    rtu::Matrix3 m;  // Transformation::Scale
+    m.Zero();
+    m.data[0] = sx; m.data[4] = sy; m.data[8] = sz;
+    return node_transform(scene, node, m);
+}
+
+extern "C" int rtu_scene_node_rotate(RtuScene* scene, uint32_t node, float ax, float ay, float az, float degrees) {
+    const rtu::Point3 axis = rtu::GetNormalized(rtu::Point3(ax, ay, az));  // LoadTransform: s.Normalize()
+    rtu::Matrix3 m;  // Transformation::Rotate
+    m.SetRotation(axis, degrees * (float)M_PI / 180.0f);
+    return node_transform(scene, node, m);
+}
+
+extern "C" int rtu_scene_node_translate(RtuScene* scene, uint32_t node, float x, float y, float z) {
+    rtu::Scene* s = scene_of(scene);
+    if (!s || node >= s->nodes.size()) return -1;
+    RtuNode& n = s->nodes[node];  // Transformation::Translate: pos = pos + p
+    const rtu::Point3 pos = rtu::Point3(n.pos[0], n.pos[1], n.pos[2]) + rtu::Point3(x, y, z);
+    n.pos[0] = pos.x; n.pos[1] = pos.y; n.pos[2] = pos.z;
+    return 0;
+}
+
+extern "C" int rtu_scene_set_light(RtuScene* scene, uint32_t index, const RtuLight* light) {
+    rtu::Scene* s = scene_of(scene);
+    if (!s || !light || index >= s->lights.size()) return -1;
+    RtuLight l = *light;
+    if (l.type == RTU_LIGHT_DIRECT) {  // DirectLight::SetDirection
+        const rtu::Point3 d = rtu::GetNormalized(rtu::Point3(l.vec[0], l.vec[1], l.vec[2]));
+        l.vec[0] = d.x; l.vec[1] = d.y; l.vec[2] = d.z;
+    }
+    s->lights[index] = l;
+    return 0;
+}

@@ -308,10 +308,6 @@ static Scene* from_blob(const void* blob, size_t size) {
 
 }  // namespace rtu
 
-struct RtuScene {
-    rtu::Scene* impl;
-};
-
 extern "C" {
 
 const char* rtu_host_last_error(void) { return rtu::g_last_error.c_str(); }
