@@ -460,6 +460,10 @@ int  rtu_selftest_primitives(RtuContext* ctx, unsigned long long n_rays, unsigne
 #define RTU_TEXOP_OUT(op) ((op) <= RTU_TEXOP_ASINF ? 1 : 3)
 int  rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, unsigned long long n, float* h_out);
 
+/* Debug: device allocations the library has made for its own buffers so far (every context together, the whole process).
+ * rtu_device_alloc is not counted. */
+unsigned long long rtu_debug_device_allocations(void);
+
 /* Device memory helpers so a C/C++ host needs no HIP headers. */
 /* The context's own stream (a hipStream_t as void*) and device: a multi-GPU host (host/begin_render.cpp) renders every shard on
  * its context's stream and queues the collection — RCCL send / receive or an asynchronous copy into pinned host memory — behind

@@ -148,7 +148,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_render_frame_device", "rtu_render_frames_device", "rtu_pack_image_device", "rtu_minmax_z_device", "rtu_pack_output_device", "rtu_render_frame", "rtu_frame_status", "rtu_render_timeline", "rtu_frame_counts", "rtu_timeline_exits", "rtu_mesh_info", "rtu_light_list_info", "rtu_debug_light_list", "rtu_update_scene", "rtu_multi_update_scene", "rtu_scene_shape_diff", "rtu_debug_context_light_list", "rtu_debug_update_timing", "rtu_debug_light_list_free", "rtu_debug_walk_stack_limit", "rtu_debug_node_bounds", "rtu_debug_flags", "rtu_set_sequences_in_flight", "rtu_debug_tail_from", "rtu_get_stats", "rtu_get_touched", "rtu_get_touched_launches", "rtu_touched_bytes", "rtu_kernel_slot_name", "rtu_probe_kernel", "rtu_probe_read", "rtu_time_render", "rtu_selftest_division", "rtu_selftest_primitives", "rtu_context_stream", "rtu_context_device", "rtu_context_sync", "rtu_host_alloc_pinned", "rtu_host_free_pinned", "rtu_copy_to_host_async", "rtu_device_alloc",
                "rtu_device_free", "rtu_copy_to_host", "rtu_device_info", "rtu_set_cancel_flag", "rtu_create_context_multi", "rtu_destroy_context_multi",
                "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind",
-               "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords"]
+               "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords",
+               "rtu_debug_device_allocations"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -203,6 +204,7 @@ _sig(hip, "rtu_render_frame_adaptive", _I, _P, ctypes.POINTER(RtuFrameDesc), cty
 _sig(hip, "rtu_render_frame_adaptive_device", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P, _P)
 _sig(hip, "rtu_debug_sample_images", _I, _P, ctypes.POINTER(RtuFrameDesc), _I, _I, _P)
 _sig(hip, "rtu_debug_texcoords", _I, _P, _I, _I, _P, ctypes.c_ulonglong, _P)
+_sig(hip, "rtu_debug_device_allocations", ctypes.c_ulonglong)
 # rtu_debug_texcoords operations (include/rtu_render.h RTU_TEXOP_*) and the floats per input / output of each
 TEXOP_ATAN2F, TEXOP_ASINF, TEXOP_SPHERE_UV, TEXOP_ENV_UVW, TEXOP_TILE_CLAMP, TEXOP_TEXTURE, TEXOP_MAP = range(7)
 TEXOP_IN = (2, 1, 3, 3, 3, 3, 3)

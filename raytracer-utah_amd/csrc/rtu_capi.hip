@@ -3,6 +3,7 @@
 // kernel launch. Compiled by hipcc with -ffp-contract=off so the few host-side
 // float computations (triangle normals, camera frame) round exactly like the
 // reference's CPU code.
+#include "rtu_devbuf.h"
 #include "rtu_device.h"
 #include "rtu_lightlist.h"
 
@@ -30,9 +31,8 @@ struct RtuContext {
     bool     has_scene = false;
     uint32_t n_textures = 0;              // of the uploaded scene, and a host copy of its material maps: rtu_debug_texcoords
     std::vector<RtuTexMap> mat_maps_host; //   checks a texture / map before the kernel reads it
-    std::vector<void*> scene_allocs;      // meshes and textures: live until the next upload
-    struct PlaceBuf { void* p = nullptr; size_t cap = 0; };
-    std::vector<PlaceBuf> place;          // what depends on node transformations, lights and materials, by slot (place_scene): an
+    std::vector<DevBuf<char>> scene_allocs;  // meshes and textures: live until the next upload
+    std::vector<DevBuf<char>> place;      // what depends on node transformations, lights and materials, by slot (place_scene): an
                                           //   update rewrites these in place, growing one only when it is too small
     // the shape of the uploaded scene (rtu_update_scene refuses any other) and what an update builds from
     std::vector<RtuNode> shape_nodes;
@@ -49,16 +49,15 @@ struct RtuContext {
     uint32_t bvh_stack_needed = 1;
 
     // per-frame resources (grown on demand, reused)
-    std::vector<void*> level_allocs;
+    std::vector<DevBuf<char>> level_allocs;  // the storage of lv, lv_side and the defer lists
     LevelBuffers lv[RTU_MAX_LEVELS] = {};
-    uint32_t level_cap0 = 0;        // pixels the level buffers were sized for
     uint32_t level_nsl = 0;
     uint32_t want_cap_s[RTU_MAX_LEVELS] = {};  // per-shard capacity wanted for levels >= 1 (grown from the counts of an overflowed frame)
     uint32_t want_defer_s = 0;
-    FrameCounters* fcnt = nullptr;
+    DevBuf<FrameCounters> fcnt;
     uint32_t* defer_list = nullptr;
     uint32_t  defer_cap_s = 0;
-    FrameCounters* fcnt_side = nullptr;      // side mode: counters of the primary phase's defer list and of the side level arrays
+    DevBuf<FrameCounters> fcnt_side;         // side mode: counters of the primary phase's defer list and of the side level arrays
     int sequences_in_flight = 1;             // rtu_set_sequences_in_flight: launch sequences the caller keeps in flight on this GPU (all its contexts together)
     uint32_t* defer_list0 = nullptr;         // the primary phase's own defer list
     uint32_t  defer_cap0_s = 0;
@@ -72,21 +71,16 @@ struct RtuContext {
     bool     textured = false;
     bool     scene_stochastic = false;   // soft shadows / glossy bounces / depth of field: recipe S only
     std::string stochastic_what;
-    float4*   acc = nullptr;             // recipe S accumulators: rgb sum + z sum, hit count
-    uint32_t* acc_hits = nullptr;
-    size_t    acc_pixels = 0;
-    float4*   sample_buf = nullptr;      // the images of one batch of samples, [sample][pixel]
-    float4*   ad_sq = nullptr;           // adaptive sampling (rtu_render_frame_adaptive): sums of squares and sample counts per pixel
-    uint8_t*  ad_counts = nullptr;
-    size_t    ad_pixels = 0;
-    uint4*    ad_list[2] = {};           // ... the active-tile lists {tile, 0, lane mask}, double-buffered, and their lengths
-    size_t    ad_list_cap = 0;           // entries of each
-    uint32_t* ad_n = nullptr;            // [2] on the device
-    uint32_t* ad_n_host = nullptr;       // pinned: the length of the list the next batch walks
-    size_t    sample_buf_pixels = 0;
-    float4*   gi_h = nullptr;            // recipe P: chain records [5 depths][4][chains], results [2][chains]
-    float4*   gi_res = nullptr;
-    size_t    gi_chains = 0;
+    DevBuf<float4>   acc;                // recipe S accumulators: rgb sum + z sum, hit count
+    DevBuf<uint32_t> acc_hits;
+    DevBuf<float4>   sample_buf;         // the images of one batch of samples, [sample][pixel]
+    DevBuf<float4>   ad_sq;              // adaptive sampling (rtu_render_frame_adaptive): sums of squares and sample counts per pixel
+    DevBuf<uint8_t>  ad_counts;
+    DevBuf<uint4>    ad_list[2];         // ... the active-tile lists {tile, 0, lane mask}, double-buffered, and their lengths
+    DevBuf<uint32_t> ad_n;               // [2] on the device
+    PinnedBuf<uint32_t> ad_n_host;       // pinned: the length of the list the next batch walks
+    DevBuf<float4>   gi_h;               // recipe P: chain records [5 depths][4][chains], results [2][chains]
+    DevBuf<float4>   gi_res;
     bool      want_gi = false;           // level buffers carry famb
     // k_tail: the recursion level from which the previous frame of this scene was almost empty (a hint —
     // any value renders the same image); last_tail_from: what the most recent frame was launched with
@@ -99,9 +93,8 @@ struct RtuContext {
     uint32_t nsl = 0;
     int32_t  shadow_light[RTU_MAX_SHADOW_LIGHTS] = {};
     float    nol_light[RTU_FI_NOL_LIGHTS][4] = {};
-    float4* fb = nullptr;
-    size_t  fb_bytes = 0;
-    unsigned long long* counters = nullptr;  // 11 x u64 (RtuStats), or the touched-bytes table [RTU_TL_KERNELS][RTU_TOUCH_STRIDE]
+    DevBuf<float4> fb;
+    DevBuf<unsigned long long> counters;     // 11 x u64 (RtuStats), or the touched-bytes table [RTU_TL_KERNELS][RTU_TOUCH_STRIDE]
     uint32_t slot_launches[RTU_TL_KERNELS] = {};  // touched-bytes mode: launches per slot that went into the table (rtu_get_touched_launches)
     // probe: HIP events around the launches of one timeline slot (rtu_probe_kernel)
     static const int kProbePairs = 64;
@@ -115,19 +108,17 @@ struct RtuContext {
     // stream ahead of the kernels (stream order protects d_cams; an event per slot protects the slot from being rewritten
     // while its copy is still pending)
     static const int kCamSlots = 16;
-    BatchCam* d_cams = nullptr;
-    BatchCam* h_cams = nullptr;
+    DevBuf<BatchCam> d_cams;
+    PinnedBuf<BatchCam> h_cams;
     hipEvent_t cam_ev[kCamSlots] = {};
     int cam_slot = 0;
     uint32_t dbg = 0;
     const volatile int* cancel = nullptr;    // rtu_set_cancel_flag: polled between the launch sequences of a sampled frame
-    uint32_t* cover = nullptr;               // coverage masks of primary rays (KernelArgs::cover), grown on demand
-    size_t    cover_cap = 0;                 // in words
+    DevBuf<uint32_t> cover;                  // coverage masks of primary rays (KernelArgs::cover), grown on demand
     uint32_t  cover_faces = 0;
-    uint32_t* occ = nullptr;                 // tile occupancy of primary rays (KernelArgs::occ), grown on demand
-    size_t    occ_cap = 0;                   // in words
+    DevBuf<uint32_t> occ;                    // tile occupancy of primary rays (KernelArgs::occ), grown on demand
     int4* node_rects = nullptr;              // [RTU_MAX_FRAME_BATCH][n_nodes] screen rectangles of the node-level bounds (k_node_rects); owned by the scene
-    unsigned long long* tl = nullptr;        // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
+    DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
 
@@ -152,9 +143,7 @@ int fail(RtuContext* ctx, int code, const char* fmt, ...) {
     } while (0)
 
 void free_scene(RtuContext* ctx) {
-    for (void* p : ctx->scene_allocs) (void)hipFree(p);
     ctx->scene_allocs.clear();
-    for (RtuContext::PlaceBuf& b : ctx->place) (void)hipFree(b.p);
     ctx->place.clear();
     ctx->has_scene = false;
 }
@@ -165,16 +154,9 @@ enum { P_NODES, P_MATERIALS, P_LIGHTS, P_MATMAPS, P_LMASK, P_COVER, P_LIST = P_C
 
 int ensure_place(RtuContext* ctx, int slot, size_t bytes, void** out) {
     if (ctx->place.size() < (size_t)P_SLOTS) ctx->place.resize(P_SLOTS);
-    RtuContext::PlaceBuf& b = ctx->place[(size_t)slot];
-    if (bytes == 0) bytes = 16;  // keep pointers valid for empty arrays
-    if (b.cap < bytes) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        RTU_HIP(ctx, hipMalloc(&b.p, bytes));
-        b.cap = bytes;
-    }
-    *out = b.p;
+    DevBuf<char>& b = ctx->place[(size_t)slot];
+    RTU_HIP(ctx, b.grow(bytes ? bytes : 16));  // keep pointers valid for empty arrays
+    *out = b.get();
     return RTU_OK;
 }
 
@@ -188,16 +170,23 @@ int place_upload(RtuContext* ctx, int slot, const T* src, size_t count, const T*
     return RTU_OK;
 }
 
+// a new device allocation of `bytes`, owned by `list` (the scene's or the level arrays' storage) until it is cleared
+template <class T>
+int alloc_owned(RtuContext* ctx, std::vector<DevBuf<char>>& list, size_t bytes, T** dst) {
+    list.emplace_back();
+    RTU_HIP(ctx, list.back().grow(bytes));
+    *dst = reinterpret_cast<T*>(list.back().get());
+    return RTU_OK;
+}
+
 template <class T>
 int upload(RtuContext* ctx, const T* src, size_t count, const T** dst) {
     *dst = nullptr;
-    size_t bytes = sizeof(T) * count;
-    if (bytes == 0) bytes = 16;  // keep pointers valid for empty arrays
-    void* d = nullptr;
-    RTU_HIP(ctx, hipMalloc(&d, bytes));
-    ctx->scene_allocs.push_back(d);
+    T* d = nullptr;
+    int rc = alloc_owned(ctx, ctx->scene_allocs, count ? sizeof(T) * count : 16, &d);  // keep pointers valid for empty arrays
+    if (rc != RTU_OK) return rc;
     if (count) RTU_HIP(ctx, hipMemcpy(d, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    *dst = static_cast<const T*>(d);
+    *dst = d;
     return RTU_OK;
 }
 
@@ -973,22 +962,40 @@ int check_frame(RtuContext* ctx, const RtuFrameDesc* f) {
 }
 
 void free_levels(RtuContext* ctx) {
-    for (void* p : ctx->level_allocs) (void)hipFree(p);
     ctx->level_allocs.clear();
     memset(ctx->lv, 0, sizeof ctx->lv);
     memset(ctx->lv_side, 0, sizeof ctx->lv_side);
     ctx->defer_list0 = nullptr;
     ctx->defer_cap0_s = 0;
-    ctx->level_cap0 = 0;
 }
 
 template <class T>
 int alloc_level(RtuContext* ctx, T** dst, size_t count) {
-    void* d = nullptr;
-    RTU_HIP(ctx, hipMalloc(&d, sizeof(T) * (count ? count : 1)));
-    ctx->level_allocs.push_back(d);
-    *dst = static_cast<T*>(d);
-    return RTU_OK;
+    return alloc_owned(ctx, ctx->level_allocs, sizeof(T) * (count ? count : 1), dst);
+}
+
+// one set of level arrays, cap_s frames per shard: famb only if `amb`, fuv / fsuv only for a textured scene
+int alloc_level_set(RtuContext* ctx, LevelBuffers& lv, size_t cap_s, bool amb) {
+    const size_t cap = cap_s * RTU_SHARDS;
+    int rc = RTU_OK;
+    auto a = [&](auto** dst, size_t count) { if (rc == RTU_OK) rc = alloc_level(ctx, dst, count); };
+    a(&lv.fa, cap);
+    a(&lv.fb, cap);
+    a(&lv.fc, cap);
+    a(&lv.fres, cap);
+    a(&lv.fchild, cap);
+    a(&lv.fsh, cap * (ctx->nsl ? ctx->nsl : 1));
+    a(&lv.fslot, cap * 6);
+    a(&lv.fpend, cap);
+    if (amb) a(&lv.famb, cap);
+    if (ctx->textured) {
+        a(&lv.fuv, cap);
+        a(&lv.fsuv, cap * 3);
+    }
+    a(&lv.lmain, cap);
+    a(&lv.lrefl, cap);
+    if (rc == RTU_OK) lv.cap_s = (uint32_t)cap_s;
+    return rc;
 }
 
 // Frame arrays of every recursion level (rtu_device.h). Level 0 holds at most one frame per
@@ -996,7 +1003,7 @@ int alloc_level(RtuContext* ctx, T** dst, size_t count) {
 // and is grown to what an overflowed frame reported (check_overflow): a frame can hold up to 3^L frames per pixel at level L in
 // theory, a tenth of a frame per pixel in the reference's scenes. (Round 3: every level as large as level 0 was 80 GB per context
 // with 32 frames of 1920 x 1080 in flight — a fourth context on one GPU ran out of memory; now 30 GB.)
-int ensure_levels(RtuContext* ctx, uint32_t pixels, uint32_t n_tiles, bool gi = false) {
+int ensure_levels(RtuContext* ctx, uint32_t n_tiles, bool gi = false) {
     if (gi) ctx->want_gi = true;
     // one shard of level 0 receives the frames of every RTU_SHARDS-th 8x8 tile of the launch (ragged right /
     // bottom tiles included), so level 0 cannot overflow
@@ -1032,26 +1039,8 @@ int ensure_levels(RtuContext* ctx, uint32_t pixels, uint32_t n_tiles, bool gi = 
     for (int L = 0; L < RTU_MAX_LEVELS; L++) total += want[L] * RTU_SHARDS * (size_t)(16 * 11 + 4 * (ctx->nsl ? ctx->nsl : 1) + 12);
     if (total > ((size_t)160 << 30)) return fail(ctx, RTU_ERR_CAPACITY, "the recursion of this frame needs %zu GB of frame records", total >> 30);
     for (int L = 0; L < RTU_MAX_LEVELS; L++) {
-        LevelBuffers& lv = ctx->lv[L];
-        size_t cap_s = want[L];
-        size_t cap = cap_s * RTU_SHARDS;
-        if (cap > 0x0FFFFFF0u) return fail(ctx, RTU_ERR_CAPACITY, "more than 2^28 frames in one recursion level");
-        if ((rc = alloc_level(ctx, &lv.fa, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fb, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fc, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fres, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fchild, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fsh, cap * (ctx->nsl ? ctx->nsl : 1))) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fslot, cap * 6)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fpend, cap)) != RTU_OK) return rc;
-        if (ctx->want_gi && (rc = alloc_level(ctx, &lv.famb, cap)) != RTU_OK) return rc;
-        if (ctx->textured) {
-            if ((rc = alloc_level(ctx, &lv.fuv, cap)) != RTU_OK) return rc;
-            if ((rc = alloc_level(ctx, &lv.fsuv, cap * 3)) != RTU_OK) return rc;
-        }
-        if ((rc = alloc_level(ctx, &lv.lmain, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.lrefl, cap)) != RTU_OK) return rc;
-        lv.cap_s = (uint32_t)cap_s;
+        if (want[L] * RTU_SHARDS > 0x0FFFFFF0u) return fail(ctx, RTU_ERR_CAPACITY, "more than 2^28 frames in one recursion level");
+        if ((rc = alloc_level_set(ctx, ctx->lv[L], want[L], ctx->want_gi)) != RTU_OK) return rc;
     }
     if ((rc = alloc_level(ctx, &ctx->defer_list, dcap_s * RTU_SHARDS)) != RTU_OK) return rc;
     ctx->defer_cap_s = (uint32_t)dcap_s;
@@ -1059,26 +1048,8 @@ int ensure_levels(RtuContext* ctx, uint32_t pixels, uint32_t n_tiles, bool gi = 
     // KernelArgs::fcnt0): small — a k_tail launch refuses more than RTU_TAIL_DECLINE frames anyway
     if ((rc = alloc_level(ctx, &ctx->defer_list0, cap_s0_alloc * RTU_SHARDS)) != RTU_OK) return rc;
     ctx->defer_cap0_s = (uint32_t)cap_s0_alloc;
-    for (int L = 0; L < RTU_MAX_LEVELS; L++) {
-        LevelBuffers& lv = ctx->lv_side[L];
-        const size_t cap_s = 256, cap = cap_s * RTU_SHARDS;
-        if ((rc = alloc_level(ctx, &lv.fa, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fb, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fc, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fres, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fchild, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fsh, cap * (ctx->nsl ? ctx->nsl : 1))) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fslot, cap * 6)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.fpend, cap)) != RTU_OK) return rc;
-        if (ctx->textured) {
-            if ((rc = alloc_level(ctx, &lv.fuv, cap)) != RTU_OK) return rc;
-            if ((rc = alloc_level(ctx, &lv.fsuv, cap * 3)) != RTU_OK) return rc;
-        }
-        if ((rc = alloc_level(ctx, &lv.lmain, cap)) != RTU_OK) return rc;
-        if ((rc = alloc_level(ctx, &lv.lrefl, cap)) != RTU_OK) return rc;
-        lv.cap_s = (uint32_t)cap_s;
-    }
-    ctx->level_cap0 = pixels;
+    for (int L = 0; L < RTU_MAX_LEVELS; L++)
+        if ((rc = alloc_level_set(ctx, ctx->lv_side[L], 256, false)) != RTU_OK) return rc;
     ctx->level_nsl = ctx->nsl;
     return RTU_OK;
 }
@@ -1109,32 +1080,25 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     uint32_t pixels = (uint32_t)rtu_shard_rows(frame) * (uint32_t)frame->width;
     const bool gi = gi_mode != RTU_LAUNCH_ALL;
     // recipe P: every chain hit is the root of two Shade() trees
-    int rc = ensure_levels(ctx, pixels * (uint32_t)batch, gi ? 2u * (n_tiles + RTU_SHARDS) : n_tiles, gi);
+    int rc = ensure_levels(ctx, gi ? 2u * (n_tiles + RTU_SHARDS) : n_tiles, gi);
     if (rc != RTU_OK) return rc;
     if (gi) {
         const size_t chains = (size_t)pixels * (size_t)batch;
-        if (chains > ctx->gi_chains) {
-            if (ctx->gi_h) (void)hipFree(ctx->gi_h);
-            if (ctx->gi_res) (void)hipFree(ctx->gi_res);
-            ctx->gi_h = ctx->gi_res = nullptr;
-            ctx->gi_chains = 0;
-            RTU_HIP(ctx, hipMalloc((void**)&ctx->gi_h, chains * (RTU_GI_BOUNCES + 1) * 4 * sizeof(float4)));
-            RTU_HIP(ctx, hipMalloc((void**)&ctx->gi_res, chains * 2 * sizeof(float4)));
-            ctx->gi_chains = chains;
-        }
+        RTU_HIP(ctx, ctx->gi_h.grow(chains * (RTU_GI_BOUNCES + 1) * 4));
+        RTU_HIP(ctx, ctx->gi_res.grow(chains * 2));
         // adaptive: the chains of stopped pixels are not traced; a zero depth-0 record is "no hit" to every later depth, k_gi_roots
         // and k_gi_final
         if (act_list && gi_mode == RTU_LAUNCH_CHAIN && gi_depth == 0)
-            RTU_HIP(ctx, hipMemsetAsync(ctx->gi_h + chains, 0, chains * sizeof(float4), stream));
+            RTU_HIP(ctx, hipMemsetAsync(ctx->gi_h.get() + chains, 0, chains * sizeof(float4), stream));
     }
     const int stats = frame->collect_stats;  // 0 fast, 1 reference counting, 2 touched bytes of the fast variant
     if (stats && zero_counters) {
-        RTU_HIP(ctx, hipMemsetAsync(ctx->counters, 0, kCounterBytes, stream));
+        RTU_HIP(ctx, hipMemsetAsync(ctx->counters.get(), 0, kCounterBytes, stream));
         memset(ctx->slot_launches, 0, sizeof ctx->slot_launches);
     }
     // the append counters start at zero; `overflow` is STICKY — launches only ever set it, check_overflow reads and clears
     // it — so that a frame that ran out of capacity is reported even when later launch sequences were queued behind it
-    RTU_HIP(ctx, hipMemsetAsync(ctx->fcnt, 0, offsetof(FrameCounters, overflow), stream));
+    RTU_HIP(ctx, hipMemsetAsync(ctx->fcnt.get(), 0, offsetof(FrameCounters, overflow), stream));
     KernelArgs a;
     memset(&a, 0, sizeof a);
     a.scene = ctx->dscene;
@@ -1142,16 +1106,16 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     if (!ctx->any_recursive_material) a.frame.max_bounce = 0;  // no reflection/refraction anywhere: Shade() never recurses
     a.out = d_out;
     memcpy(a.lv, ctx->lv, sizeof a.lv);
-    a.fcnt = ctx->fcnt;
-    a.tl = ctx->stamp_next ? ctx->tl : nullptr;
+    a.fcnt = ctx->fcnt.get();
+    a.tl = ctx->stamp_next ? ctx->tl.get() : nullptr;
     a.defer_list = ctx->defer_list;
     a.defer_cap_s = ctx->defer_cap_s;
     a.defer_list0 = ctx->defer_list0;
     a.defer_cap0_s = ctx->defer_cap0_s;
-    a.fcnt0 = ctx->fcnt;
+    a.fcnt0 = ctx->fcnt.get();
     a.dbg = ctx->dbg;
     a.scene.dbg = ctx->dbg;
-    a.counters = stats ? ctx->counters : nullptr;
+    a.counters = stats ? ctx->counters.get() : nullptr;
     a.host_launches = stats == 2 ? ctx->slot_launches : nullptr;
     a.node_rects = (stats != 1 && frame->samples == 0 && ctx->dscene.node_bounds) ? ctx->node_rects : nullptr;
     if (a.node_rects && (ctx->dscene.n_cover + ctx->dscene.n_pcover) && !gi && ((size_t)((frame->width + 7) / 8) * (size_t)((frame->height + 7) / 8) + 31u) / 32u <= 12288u) {  // (the mask has to fit k_mesh_cover's LDS copy)
@@ -1159,29 +1123,21 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         a.cover_words = (a.tiles_xf * (uint32_t)((frame->height + 7) / 8) + 31u) / 32u;
         a.cover_faces = ctx->cover_faces;
         const size_t need = (size_t)batch * (ctx->dscene.n_cover + ctx->dscene.n_pcover) * (1u + a.cover_words);
-        if (need > ctx->cover_cap) {
+        if (need > ctx->cover.size()) {
             RTU_HIP(ctx, hipStreamSynchronize(stream));  // (first launch at this size only) nothing may still read the old masks
-            if (ctx->cover) (void)hipFree(ctx->cover);
-            ctx->cover = nullptr;
-            ctx->cover_cap = 0;
-            RTU_HIP(ctx, hipMalloc((void**)&ctx->cover, need * sizeof(uint32_t)));
-            ctx->cover_cap = need;
+            RTU_HIP(ctx, ctx->cover.grow(need));
         }
-        RTU_HIP(ctx, hipMemsetAsync(ctx->cover, 0, need * sizeof(uint32_t), stream));
-        a.cover = ctx->cover;
+        RTU_HIP(ctx, hipMemsetAsync(ctx->cover.get(), 0, need * sizeof(uint32_t), stream));
+        a.cover = ctx->cover.get();
     }
     if (a.node_rects && !gi && ctx->dscene.n_nodes <= 64u && stats != 1 && !(ctx->dbg & 256u)) {  // tile occupancy: every word is written by k_tile_occ on this launch
         a.occ_words = ((tiles_x * bands + 63u) / 64u) * 2u;
         const size_t need = (size_t)batch * a.occ_words;
-        if (need > ctx->occ_cap) {
+        if (need > ctx->occ.size()) {
             RTU_HIP(ctx, hipStreamSynchronize(stream));  // (first launch at this size only) nothing may still read the old words
-            if (ctx->occ) (void)hipFree(ctx->occ);
-            ctx->occ = nullptr;
-            ctx->occ_cap = 0;
-            RTU_HIP(ctx, hipMalloc((void**)&ctx->occ, need * sizeof(uint32_t)));
-            ctx->occ_cap = need;
+            RTU_HIP(ctx, ctx->occ.grow(need));
         }
-        a.occ = a.occ_words ? ctx->occ : nullptr;  // (a shard without rows has no tiles: nothing is launched at all)
+        a.occ = a.occ_words ? ctx->occ.get() : nullptr;  // (a shard without rows has no tiles: nothing is launched at all)
     }
     a.tiles_x = tiles_x;
     a.tiles_per_image = tiles_x * bands;
@@ -1222,28 +1178,28 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         a.batch = (uint32_t)batch;
         a.batch_pixels = pixels;
         a.tiles_per_image = tiles_x * bands;
-        if (!ctx->d_cams) {
-            RTU_HIP(ctx, hipMalloc((void**)&ctx->d_cams, sizeof(BatchCam) * RTU_MAX_FRAME_BATCH));
-            RTU_HIP(ctx, hipHostMalloc((void**)&ctx->h_cams, sizeof(BatchCam) * RTU_MAX_FRAME_BATCH * RtuContext::kCamSlots, hipHostMallocDefault));
+        if (!ctx->d_cams.get()) {
+            RTU_HIP(ctx, ctx->d_cams.grow(RTU_MAX_FRAME_BATCH));
+            RTU_HIP(ctx, ctx->h_cams.grow((size_t)RTU_MAX_FRAME_BATCH * RtuContext::kCamSlots));
             for (hipEvent_t& e : ctx->cam_ev) RTU_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         const int slot = ctx->cam_slot;
         ctx->cam_slot = (slot + 1) % RtuContext::kCamSlots;
         RTU_HIP(ctx, hipEventSynchronize(ctx->cam_ev[slot]));  // the copy that last read this slot (16 launches ago) is done; a fresh event is "done"
-        BatchCam* hc = ctx->h_cams + (size_t)slot * RTU_MAX_FRAME_BATCH;
+        BatchCam* hc = ctx->h_cams.get() + (size_t)slot * RTU_MAX_FRAME_BATCH;
         for (int b = 0; b < batch; b++) {
             memcpy(hc[b].pos, frames_batch[b].cam_pos, sizeof hc[b].pos);
             memcpy(hc[b].origin, frames_batch[b].origin, sizeof hc[b].origin);
             memcpy(hc[b].u, frames_batch[b].u, sizeof hc[b].u);
             memcpy(hc[b].v, frames_batch[b].v, sizeof hc[b].v);
         }
-        RTU_HIP(ctx, hipMemcpyAsync(ctx->d_cams, hc, sizeof(BatchCam) * (size_t)batch, hipMemcpyHostToDevice, stream));
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->d_cams.get(), hc, sizeof(BatchCam) * (size_t)batch, hipMemcpyHostToDevice, stream));
         RTU_HIP(ctx, hipEventRecord(ctx->cam_ev[slot], stream));
-        a.cam = ctx->d_cams;
+        a.cam = ctx->d_cams.get();
     }
     if (gi) {
-        a.gi_h = ctx->gi_h;
-        a.gi_res = ctx->gi_res;
+        a.gi_h = ctx->gi_h.get();
+        a.gi_res = ctx->gi_res.get();
         a.gi_depth = (uint32_t)gi_depth;
         a.gi_total = pixels * (uint32_t)batch;
     }
@@ -1272,12 +1228,12 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
             RTU_HIP(ctx, hipEventCreateWithFlags(&ctx->aux_ev1, hipEventDisableTiming));
         }
         a.side = 1;
-        a.fcnt0 = ctx->fcnt_side;
+        a.fcnt0 = ctx->fcnt_side.get();
         memcpy(a.lv_side, ctx->lv_side, sizeof a.lv_side);
         a.aux_stream = ctx->aux_stream;
         a.aux_ev0 = ctx->aux_ev0;
         a.aux_ev1 = ctx->aux_ev1;
-        RTU_HIP(ctx, hipMemsetAsync(ctx->fcnt_side, 0, offsetof(FrameCounters, overflow), stream));  // (ahead of k_primary, which fills its defer counters)
+        RTU_HIP(ctx, hipMemsetAsync(ctx->fcnt_side.get(), 0, offsetof(FrameCounters, overflow), stream));  // (ahead of k_primary, which fills its defer counters)
         ctx->last_side = true;
     }
     // k_primary's grid (render_impl.h launch_all): few, long-lived workgroups when the last launch of this shape found most tiles empty
@@ -1354,22 +1310,22 @@ void learn_tail(RtuContext* ctx, const FrameCounters& h, const FrameCounters* si
 int check_overflow(RtuContext* ctx, bool* overflow) {
     std::unique_ptr<FrameCounters> hp(new FrameCounters);  // a quarter of a megabyte: not on the stack
     FrameCounters& h = *hp;
-    RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt, sizeof h, hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt.get(), sizeof h, hipMemcpyDeviceToHost));
     // side mode: stage 2 of the primary phase made more frames than its k_tail launch takes (or than the side arrays hold): the
     // frames of this report are incomplete, and this launch shape goes without side mode from now on
     std::unique_ptr<FrameCounters> sp;
     bool side_failed = false;
     {
         uint32_t flags[2] = {0, 0};
-        RTU_HIP(ctx, hipMemcpy(flags, &ctx->fcnt_side->overflow, sizeof flags, hipMemcpyDeviceToHost));
+        RTU_HIP(ctx, hipMemcpy(flags, &ctx->fcnt_side.get()->overflow, sizeof flags, hipMemcpyDeviceToHost));
         if (flags[0] || flags[1]) {
             side_failed = true;
             ctx->side_off[ctx->last_tail_key] = true;
-            RTU_HIP(ctx, hipMemset(&ctx->fcnt_side->overflow, 0, 2 * sizeof(uint32_t)));
+            RTU_HIP(ctx, hipMemset(&ctx->fcnt_side.get()->overflow, 0, 2 * sizeof(uint32_t)));
         }
         if (ctx->last_side) {
             sp.reset(new FrameCounters);
-            RTU_HIP(ctx, hipMemcpy(sp.get(), ctx->fcnt_side, sizeof(FrameCounters), hipMemcpyDeviceToHost));
+            RTU_HIP(ctx, hipMemcpy(sp.get(), ctx->fcnt_side.get(), sizeof(FrameCounters), hipMemcpyDeviceToHost));
             ctx->side_frames[ctx->last_tail_key] = stage2_total(*sp);
             static const bool kSideVerbose = getenv("RTU_SIDE_VERBOSE") != nullptr;  // diagnostics: what side mode's stage 2 made, per status check
             if (kSideVerbose) {
@@ -1392,7 +1348,7 @@ int check_overflow(RtuContext* ctx, bool* overflow) {
         learn_tail(ctx, h, sp.get());
         return RTU_OK;
     }
-    RTU_HIP(ctx, hipMemset(&ctx->fcnt->overflow, 0, 2 * sizeof(uint32_t)));  // reported: the next status starts clean (overflow, tail_declined)
+    RTU_HIP(ctx, hipMemset(&ctx->fcnt.get()->overflow, 0, 2 * sizeof(uint32_t)));  // reported: the next status starts clean (overflow, tail_declined)
     if (h.tail_declined) ctx->tail_hints[ctx->last_tail_key] = RTU_MAX_LEVELS;  // this shape is rendered level by level from now on
     if (!h.overflow) return RTU_OK;  // nothing ran out of capacity: render again, that is all
     bool grew = false;
@@ -1429,27 +1385,11 @@ struct SampledRun {
 };
 
 int ensure_adaptive(RtuContext* ctx, size_t pixels, size_t tiles) {  // grow-only, like acc
-    if (pixels > ctx->ad_pixels) {
-        if (ctx->ad_sq) (void)hipFree(ctx->ad_sq);
-        if (ctx->ad_counts) (void)hipFree(ctx->ad_counts);
-        ctx->ad_sq = nullptr;
-        ctx->ad_counts = nullptr;
-        ctx->ad_pixels = 0;
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->ad_sq, pixels * sizeof(float4)));
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->ad_counts, pixels));
-        ctx->ad_pixels = pixels;
-    }
-    if (tiles > ctx->ad_list_cap) {
-        for (uint4*& l : ctx->ad_list) {
-            if (l) (void)hipFree(l);
-            l = nullptr;
-        }
-        ctx->ad_list_cap = 0;
-        for (uint4*& l : ctx->ad_list) RTU_HIP(ctx, hipMalloc((void**)&l, tiles * sizeof(uint4)));
-        ctx->ad_list_cap = tiles;
-    }
-    if (!ctx->ad_n) RTU_HIP(ctx, hipMalloc((void**)&ctx->ad_n, 2 * sizeof(uint32_t)));
-    if (!ctx->ad_n_host) RTU_HIP(ctx, hipHostMalloc((void**)&ctx->ad_n_host, sizeof(uint32_t), hipHostMallocDefault));
+    RTU_HIP(ctx, ctx->ad_sq.grow(pixels));
+    RTU_HIP(ctx, ctx->ad_counts.grow(pixels));
+    for (DevBuf<uint4>& l : ctx->ad_list) RTU_HIP(ctx, l.grow(tiles));
+    RTU_HIP(ctx, ctx->ad_n.grow(2));
+    RTU_HIP(ctx, ctx->ad_n_host.grow(1));
     return RTU_OK;
 }
 
@@ -1472,23 +1412,9 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
     if (ad && ad->max_batch > 0 && batch > ad->max_batch) batch = ad->max_batch;
     if (batch > frame->samples) batch = frame->samples;
     if (batch < 1) batch = 1;
-    if (pixels > ctx->acc_pixels) {
-        if (ctx->acc) (void)hipFree(ctx->acc);
-        if (ctx->acc_hits) (void)hipFree(ctx->acc_hits);
-        ctx->acc = nullptr;
-        ctx->acc_hits = nullptr;
-        ctx->acc_pixels = 0;
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->acc, pixels * sizeof(float4)));
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->acc_hits, pixels * sizeof(uint32_t)));
-        ctx->acc_pixels = pixels;
-    }
-    if (pixels * (size_t)batch > ctx->sample_buf_pixels) {
-        if (ctx->sample_buf) (void)hipFree(ctx->sample_buf);
-        ctx->sample_buf = nullptr;
-        ctx->sample_buf_pixels = 0;
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->sample_buf, pixels * (size_t)batch * sizeof(float4)));
-        ctx->sample_buf_pixels = pixels * (size_t)batch;
-    }
+    RTU_HIP(ctx, ctx->acc.grow(pixels));
+    RTU_HIP(ctx, ctx->acc_hits.grow(pixels));
+    RTU_HIP(ctx, ctx->sample_buf.grow(pixels * (size_t)batch));
     const uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
     const uint32_t tiles = tiles_x * (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
     if (ad) {
@@ -1500,22 +1426,22 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
     auto adaptive_start = [&]() -> int {  // (again after the counting variant starts over)
         cur = 0;
         n_act = tiles;
-        hipError_t e = (hipError_t)rtu_launch_adaptive_init(ctx->ad_list[0], tiles, tiles_x, frame->width, frame->height, frame->shard_rank, frame->shard_count, stream);
+        hipError_t e = (hipError_t)rtu_launch_adaptive_init(ctx->ad_list[0].get(), tiles, tiles_x, frame->width, frame->height, frame->shard_rank, frame->shard_count, stream);
         return e == hipSuccess ? RTU_OK : fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     };
     auto adaptive_step = [&](int i, int nb) -> int {
-        RTU_HIP(ctx, hipMemsetAsync(ctx->ad_n + (cur ^ 1), 0, sizeof(uint32_t), stream));
+        RTU_HIP(ctx, hipMemsetAsync(ctx->ad_n.get() + (cur ^ 1), 0, sizeof(uint32_t), stream));
         AdaptiveStep p;
-        p.samples = ctx->sample_buf;
-        p.acc = ctx->acc;
-        p.sq = ctx->ad_sq;
-        p.hits = ctx->acc_hits;
-        p.counts = ctx->ad_counts;
-        p.list_in = ctx->ad_list[cur];
-        p.list_out = ctx->ad_list[cur ^ 1];
-        p.n_out = ctx->ad_n + (cur ^ 1);
-        p.skip_if = &ctx->fcnt->overflow;
-        p.skip_if_side = &ctx->fcnt_side->overflow;
+        p.samples = ctx->sample_buf.get();
+        p.acc = ctx->acc.get();
+        p.sq = ctx->ad_sq.get();
+        p.hits = ctx->acc_hits.get();
+        p.counts = ctx->ad_counts.get();
+        p.list_in = ctx->ad_list[cur].get();
+        p.list_out = ctx->ad_list[cur ^ 1].get();
+        p.n_out = ctx->ad_n.get() + (cur ^ 1);
+        p.skip_if = &ctx->fcnt.get()->overflow;
+        p.skip_if_side = &ctx->fcnt_side.get()->overflow;
         p.n_in = n_act;
         p.batch = (uint32_t)nb;
         p.first = i == 0 ? 1u : 0u;
@@ -1531,7 +1457,7 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
         p.target = ad->target_variance;
         hipError_t e = (hipError_t)rtu_launch_adaptive_step(p, stream);
         if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-        RTU_HIP(ctx, hipMemcpyAsync(ctx->ad_n_host, ctx->ad_n + (cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->ad_n_host.get(), ctx->ad_n.get() + (cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         return RTU_OK;
     };
     const uint4* no_list = nullptr;
@@ -1544,7 +1470,7 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
             nb = i_end - i < batch ? i_end - i : batch;  // (i may have been reset below)
             int rc;
             if (ad && i == 0 && (rc = adaptive_start()) != RTU_OK) return rc;
-            rc = launch(ctx, frame, ctx->sample_buf, stream, zero_counters && i == 0, i, nb, nullptr, RTU_LAUNCH_ALL, 0, ad != nullptr, ad ? ctx->ad_list[cur] : no_list, n_act);
+            rc = launch(ctx, frame, ctx->sample_buf.get(), stream, zero_counters && i == 0, i, nb, nullptr, RTU_LAUNCH_ALL, 0, ad != nullptr, ad ? ctx->ad_list[cur].get() : no_list, n_act);
             if (rc != RTU_OK) return rc;
             if (ad && (rc = adaptive_step(i, nb)) != RTU_OK) return rc;
             RTU_HIP(ctx, hipStreamSynchronize(stream));
@@ -1561,8 +1487,8 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
             // deepest hit up — each depth's AmbientLight needs the results of the depth below (k_gi_roots)
             // (adaptive: depth 0 walks the active tiles; the deeper depths run over every chain, a stopped one ends at once)
             for (int k = 0; k <= RTU_GI_BOUNCES; k++) {
-                rc = launch(ctx, frame, ctx->sample_buf, stream, zero_counters && i == 0 && k == 0, i, nb, nullptr, RTU_LAUNCH_CHAIN, k, ad != nullptr,
-                            ad && k == 0 ? ctx->ad_list[cur] : no_list, ad ? n_act : 0u);
+                rc = launch(ctx, frame, ctx->sample_buf.get(), stream, zero_counters && i == 0 && k == 0, i, nb, nullptr, RTU_LAUNCH_CHAIN, k, ad != nullptr,
+                            ad && k == 0 ? ctx->ad_list[cur].get() : no_list, ad ? n_act : 0u);
                 if (rc != RTU_OK) return rc;
             }
             // the five shading steps are queued back to back; ONE host synchronisation per batch reads the (sticky) overflow
@@ -1570,7 +1496,7 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
             // grown capacities: its chain records do not depend on them.
             for (;;) {
                 for (int k = RTU_GI_BOUNCES; k >= 0; k--) {
-                    rc = launch(ctx, frame, ctx->sample_buf, stream, false, i, nb, nullptr, RTU_LAUNCH_SHADE, k, ad != nullptr, no_list, ad ? n_act : 0u);
+                    rc = launch(ctx, frame, ctx->sample_buf.get(), stream, false, i, nb, nullptr, RTU_LAUNCH_SHADE, k, ad != nullptr, no_list, ad ? n_act : 0u);
                     if (rc != RTU_OK) return rc;
                 }
                 if (ad && (rc = adaptive_step(i, nb)) != RTU_OK) return rc;
@@ -1585,21 +1511,21 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
         }
         if (ad) {
             cur ^= 1;
-            n_act = *ctx->ad_n_host;  // (read in the batch's synchronisation)
+            n_act = *ctx->ad_n_host.get();  // (read in the batch's synchronisation)
             if (n_act == 0) break;    // every pixel has stopped
             continue;
         }
         if (h_dump) {
-            RTU_HIP(ctx, hipMemcpyAsync(h_dump + (size_t)(i - i_begin) * pixels * 4u, ctx->sample_buf, (size_t)nb * pixels * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            RTU_HIP(ctx, hipMemcpyAsync(h_dump + (size_t)(i - i_begin) * pixels * 4u, ctx->sample_buf.get(), (size_t)nb * pixels * sizeof(float4), hipMemcpyDeviceToHost, stream));
             RTU_HIP(ctx, hipStreamSynchronize(stream));
             continue;
         }
-        hipError_t e = (hipError_t)rtu_launch_accumulate(ctx->sample_buf, (uint32_t)nb, ctx->acc, ctx->acc_hits, (uint32_t)pixels, i == 0, stream);
+        hipError_t e = (hipError_t)rtu_launch_accumulate(ctx->sample_buf.get(), (uint32_t)nb, ctx->acc.get(), ctx->acc_hits.get(), (uint32_t)pixels, i == 0, stream);
         if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     }
     if (h_dump) return RTU_OK;
-    hipError_t e = ad ? (hipError_t)rtu_launch_resolve_counts(ctx->acc, ctx->acc_hits, ctx->ad_counts, d_out, run->d_counts, (uint32_t)pixels, stream)
-                      : (hipError_t)rtu_launch_resolve(ctx->acc, ctx->acc_hits, d_out, (uint32_t)pixels, (uint32_t)frame->samples, stream);
+    hipError_t e = ad ? (hipError_t)rtu_launch_resolve_counts(ctx->acc.get(), ctx->acc_hits.get(), ctx->ad_counts.get(), d_out, run->d_counts, (uint32_t)pixels, stream)
+                      : (hipError_t)rtu_launch_resolve(ctx->acc.get(), ctx->acc_hits.get(), d_out, (uint32_t)pixels, (uint32_t)frame->samples, stream);
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     return RTU_OK;
 }
@@ -1671,12 +1597,12 @@ RtuContext* rtu_create_context(int device_id, int* err_out) {
     ctx->device = device_id;
     bool ok = hipSetDevice(device_id) == hipSuccess &&
               hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc((void**)&ctx->fcnt_side, sizeof(FrameCounters)) == hipSuccess && hipMemset(ctx->fcnt_side, 0, sizeof(FrameCounters)) == hipSuccess &&
+              ctx->fcnt_side.grow(1) == hipSuccess && hipMemset(ctx->fcnt_side.get(), 0, sizeof(FrameCounters)) == hipSuccess &&
               hipEventCreate(&ctx->ev0) == hipSuccess && hipEventCreate(&ctx->ev1) == hipSuccess &&
-              hipMalloc((void**)&ctx->counters, kCounterBytes) == hipSuccess &&
-              hipMalloc((void**)&ctx->fcnt, sizeof(FrameCounters)) == hipSuccess &&
-              hipMemset(ctx->fcnt, 0, sizeof(FrameCounters)) == hipSuccess &&
-              hipMemset(ctx->counters, 0, kCounterBytes) == hipSuccess;
+              ctx->counters.grow(kCounterBytes / sizeof(unsigned long long)) == hipSuccess &&
+              ctx->fcnt.grow(1) == hipSuccess &&
+              hipMemset(ctx->fcnt.get(), 0, sizeof(FrameCounters)) == hipSuccess &&
+              hipMemset(ctx->counters.get(), 0, kCounterBytes) == hipSuccess;
     if (!ok) {
         if (err_out) *err_out = RTU_ERR_HIP;
         rtu_destroy_context(ctx);
@@ -1690,40 +1616,18 @@ void rtu_destroy_context(RtuContext* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
-    if (ctx->aux_ev0) (void)hipEventDestroy(ctx->aux_ev0);
-    if (ctx->aux_ev1) (void)hipEventDestroy(ctx->aux_ev1);
-    if (ctx->fcnt_side) (void)hipFree(ctx->fcnt_side);
-    free_scene(ctx);
+    if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     ll_builder_destroy(ctx->llb);
-    free_levels(ctx);
-    if (ctx->fcnt) (void)hipFree(ctx->fcnt);
-    if (ctx->tl) (void)hipFree(ctx->tl);
-    if (ctx->cover) (void)hipFree(ctx->cover);
-    if (ctx->occ) (void)hipFree(ctx->occ);
-    if (ctx->d_cams) (void)hipFree(ctx->d_cams);
-    if (ctx->h_cams) (void)hipHostFree(ctx->h_cams);
-    for (hipEvent_t e : ctx->cam_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->fb) (void)hipFree(ctx->fb);
-    if (ctx->acc) (void)hipFree(ctx->acc);
-    if (ctx->acc_hits) (void)hipFree(ctx->acc_hits);
-    if (ctx->sample_buf) (void)hipFree(ctx->sample_buf);
-    if (ctx->ad_sq) (void)hipFree(ctx->ad_sq);
-    if (ctx->ad_counts) (void)hipFree(ctx->ad_counts);
-    for (uint4* l : ctx->ad_list)
-        if (l) (void)hipFree(l);
-    if (ctx->ad_n) (void)hipFree(ctx->ad_n);
-    if (ctx->ad_n_host) (void)hipHostFree(ctx->ad_n_host);
-    if (ctx->gi_h) (void)hipFree(ctx->gi_h);
-    if (ctx->gi_res) (void)hipFree(ctx->gi_res);
-    if (ctx->counters) (void)hipFree(ctx->counters);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    for (hipEvent_t e : ctx->probe_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    // the buffers go with the context (DevBuf); its events and streams after them
+    std::vector<hipEvent_t> events = {ctx->aux_ev0, ctx->aux_ev1, ctx->ev0, ctx->ev1};
+    events.insert(events.end(), std::begin(ctx->cam_ev), std::end(ctx->cam_ev));
+    events.insert(events.end(), std::begin(ctx->probe_ev), std::end(ctx->probe_ev));
+    const hipStream_t streams[] = {ctx->aux_stream, ctx->stream};
     delete ctx;
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamDestroy(s);
 }
 
 const char* rtu_last_error(const RtuContext* ctx) { return ctx ? ctx->error.c_str() : "context is NULL"; }
@@ -2089,12 +1993,8 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     ds.n_nodes = s->n_nodes;
     ds.walk_stack_limit = 0xFFFFu;
     ds.node_bounds = 1;
-    {   // screen rectangles of the node-level bounds, one set per frame in flight (written by k_node_rects on every launch)
-        void* d = nullptr;
-        RTU_HIP(ctx, hipMalloc(&d, sizeof(int4) * (size_t)RTU_MAX_FRAME_BATCH * s->n_nodes));
-        ctx->scene_allocs.push_back(d);
-        ctx->node_rects = static_cast<int4*>(d);
-    }
+    // screen rectangles of the node-level bounds, one set per frame in flight (written by k_node_rects on every launch)
+    if ((rc = alloc_owned(ctx, ctx->scene_allocs, sizeof(int4) * (size_t)RTU_MAX_FRAME_BATCH * s->n_nodes, &ctx->node_rects)) != RTU_OK) return rc;
     ctx->n_meshes = s->n_meshes;
     ctx->mesh_info = mesh_info;
     ctx->bvh_stack_needed = stack_needed;
@@ -2279,10 +2179,10 @@ int rtu_get_stats(RtuContext* ctx, RtuStats* stats) {
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     RTU_HIP(ctx, hipDeviceSynchronize());
     static_assert(sizeof(RtuStats) == 11 * sizeof(unsigned long long), "RtuStats layout");
-    RTU_HIP(ctx, hipMemcpy(stats, ctx->counters, sizeof(RtuStats), hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(stats, ctx->counters.get(), sizeof(RtuStats), hipMemcpyDeviceToHost));
     std::unique_ptr<FrameCounters> hp(new FrameCounters);  // a quarter of a megabyte: not on the stack
     FrameCounters& h = *hp;
-    RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt, sizeof h, hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt.get(), sizeof h, hipMemcpyDeviceToHost));
     if (!h.overflow) learn_tail(ctx, h, nullptr);  // (after a counting render: no side mode)
     return RTU_OK;
 }
@@ -2292,7 +2192,7 @@ int rtu_get_touched(RtuContext* ctx, RtuTouched* per_slot, int n_slots) {
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     RTU_HIP(ctx, hipDeviceSynchronize());
     std::vector<unsigned long long> h((size_t)RTU_TL_KERNELS * RTU_TOUCH_STRIDE);
-    RTU_HIP(ctx, hipMemcpy(h.data(), ctx->counters, kCounterBytes, hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(h.data(), ctx->counters.get(), kCounterBytes, hipMemcpyDeviceToHost));
     static_assert(sizeof(RtuTouched) == RTU_TOUCH_FIELDS * sizeof(unsigned long long), "RtuTouched layout");
     static_assert(RTU_KERNEL_SLOTS == RTU_TL_KERNELS, "slot count");
     const int n = n_slots < RTU_TL_KERNELS ? n_slots : RTU_TL_KERNELS;
@@ -2363,22 +2263,16 @@ int rtu_render_frame(RtuContext* ctx, const RtuFrameDesc* frame, float* h_rgbz, 
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     size_t rows = (size_t)rtu_shard_rows(frame);
     size_t bytes = rows * (size_t)frame->width * sizeof(float4);
-    if (bytes > ctx->fb_bytes) {
-        if (ctx->fb) (void)hipFree(ctx->fb);
-        ctx->fb = nullptr;
-        ctx->fb_bytes = 0;
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->fb, bytes));
-        ctx->fb_bytes = bytes;
-    }
+    RTU_HIP(ctx, ctx->fb.grow(rows * (size_t)frame->width));
     RtuFrameDesc f = *frame;
     if (stats) f.collect_stats = 1;
     for (int attempt = 0;; attempt++) {
         if (f.samples >= 1) {  // recipe S settles its capacities pass by pass
-            if ((rc = render_sampled(ctx, &f, ctx->fb, ctx->stream, true)) != RTU_OK) return rc;
+            if ((rc = render_sampled(ctx, &f, ctx->fb.get(), ctx->stream, true)) != RTU_OK) return rc;
             RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
             break;
         }
-        rc = launch(ctx, &f, ctx->fb, ctx->stream, true);
+        rc = launch(ctx, &f, ctx->fb.get(), ctx->stream, true);
         if (rc != RTU_OK) return rc;
         RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         bool overflow = false;
@@ -2388,7 +2282,7 @@ int rtu_render_frame(RtuContext* ctx, const RtuFrameDesc* frame, float* h_rgbz, 
         // (every round settles at least one more recursion level)
         if (attempt >= 2 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
     }
-    if (bytes) RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->fb, bytes, hipMemcpyDeviceToHost));
+    if (bytes) RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->fb.get(), bytes, hipMemcpyDeviceToHost));
     if (stats) return rtu_get_stats(ctx, stats);
     return RTU_OK;
 }
@@ -2401,19 +2295,6 @@ int rtu_adaptive_defaults(RtuAdaptiveDesc* out) {
     out->max_batch = 0;
     return RTU_OK;
 }
-
-namespace {
-int ensure_fb(RtuContext* ctx, size_t bytes) {
-    if (bytes > ctx->fb_bytes) {
-        if (ctx->fb) (void)hipFree(ctx->fb);
-        ctx->fb = nullptr;
-        ctx->fb_bytes = 0;
-        RTU_HIP(ctx, hipMalloc((void**)&ctx->fb, bytes));
-        ctx->fb_bytes = bytes;
-    }
-    return RTU_OK;
-}
-}  // namespace
 
 int rtu_render_frame_adaptive_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, void* d_rgbz, void* d_counts,
                                      void* hip_stream) {
@@ -2436,16 +2317,16 @@ int rtu_render_frame_adaptive(RtuContext* ctx, const RtuFrameDesc* frame, const 
     if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
-    if ((rc = ensure_fb(ctx, pixels * sizeof(float4))) != RTU_OK) return rc;
+    RTU_HIP(ctx, ctx->fb.grow(pixels));
     RtuFrameDesc f = *frame;
     if (stats) f.collect_stats = 1;
     SampledRun run;
     run.ad = adaptive;
-    if ((rc = render_sampled(ctx, &f, ctx->fb, ctx->stream, true, &run)) != RTU_OK) return rc;
+    if ((rc = render_sampled(ctx, &f, ctx->fb.get(), ctx->stream, true, &run)) != RTU_OK) return rc;
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (pixels) {
-        RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->fb, pixels * sizeof(float4), hipMemcpyDeviceToHost));
-        if (h_counts) RTU_HIP(ctx, hipMemcpy(h_counts, ctx->ad_counts, pixels, hipMemcpyDeviceToHost));
+        RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->fb.get(), pixels * sizeof(float4), hipMemcpyDeviceToHost));
+        if (h_counts) RTU_HIP(ctx, hipMemcpy(h_counts, ctx->ad_counts.get(), pixels, hipMemcpyDeviceToHost));
     }
     if (stats) return rtu_get_stats(ctx, stats);
     return RTU_OK;
@@ -2518,8 +2399,8 @@ int rtu_render_timeline(RtuContext* ctx, const RtuFrameDesc* frame, void* d_rgbz
     if (frame->samples != 0) return fail(ctx, RTU_ERR_ARG, "the timeline is of one launch sequence of recipe W (samples == 0)");
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)RTU_TL_KERNELS * RTU_TL_STRIDE;
-    if (!ctx->tl) RTU_HIP(ctx, hipMalloc((void**)&ctx->tl, n * sizeof(unsigned long long)));
-    RTU_HIP(ctx, hipMemsetAsync(ctx->tl, 0, n * sizeof(unsigned long long), ctx->stream));
+    RTU_HIP(ctx, ctx->tl.grow(n));
+    RTU_HIP(ctx, hipMemsetAsync(ctx->tl.get(), 0, n * sizeof(unsigned long long), ctx->stream));
     ctx->stamp_next = true;
     rc = launch(ctx, frame, (float4*)d_rgbz, ctx->stream, true);
     ctx->stamp_next = false;
@@ -2531,7 +2412,7 @@ int rtu_render_timeline(RtuContext* ctx, const RtuFrameDesc* frame, void* d_rgbz
         if (overflow) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames exceeded the provisioned capacity; render the frame again");
     }
     std::vector<unsigned long long> h(n);
-    RTU_HIP(ctx, hipMemcpy(h.data(), ctx->tl, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(h.data(), ctx->tl.get(), n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     int khz = 0;
     RTU_HIP(ctx, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device));
     if (khz <= 0) khz = 100000;
@@ -2556,10 +2437,10 @@ int rtu_render_timeline(RtuContext* ctx, const RtuFrameDesc* frame, void* d_rgbz
 
 int rtu_timeline_exits(RtuContext* ctx, int slot, int max_values, double* exit_us_out) {
     if (!ctx || !exit_us_out || slot < 0 || slot >= RTU_TL_KERNELS || max_values < 1) return RTU_ERR_ARG;
-    if (!ctx->tl) return fail(ctx, RTU_ERR_ARG, "no timeline recorded yet (rtu_render_timeline)");
+    if (!ctx->tl.get()) return fail(ctx, RTU_ERR_ARG, "no timeline recorded yet (rtu_render_timeline)");
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<unsigned long long> h(RTU_TL_STRIDE);
-    RTU_HIP(ctx, hipMemcpy(h.data(), ctx->tl + (size_t)slot * RTU_TL_STRIDE, RTU_TL_STRIDE * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(h.data(), ctx->tl.get() + (size_t)slot * RTU_TL_STRIDE, RTU_TL_STRIDE * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     int khz = 0;
     RTU_HIP(ctx, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device));
     if (khz <= 0) khz = 100000;
@@ -2723,7 +2604,7 @@ int rtu_frame_counts(RtuContext* ctx, uint32_t* frames_out, uint32_t* deferred_o
     RTU_HIP(ctx, hipDeviceSynchronize());
     std::unique_ptr<FrameCounters> hp(new FrameCounters);  // a quarter of a megabyte: not on the stack
     FrameCounters& h = *hp;
-    RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt, sizeof h, hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt.get(), sizeof h, hipMemcpyDeviceToHost));
     for (int L = 0; L < RTU_MAX_LEVELS; L++) {
         frames_out[L] = 0;
         for (int s = 0; s < RTU_SHARDS; s++) frames_out[L] += h.n_frames[L][(s) * RTU_CSTRIDE];
@@ -2733,7 +2614,7 @@ int rtu_frame_counts(RtuContext* ctx, uint32_t* frames_out, uint32_t* deferred_o
         for (int s = 0; s < RTU_SHARDS; s++) deferred_out[p] += h.n_defer[p][(s) * RTU_CSTRIDE];
     }
     if (ctx->last_side) {  // side mode: the primary phase's defer list and the frames its stage 2 made are counted apart (KernelArgs::fcnt0)
-        RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt_side, sizeof h, hipMemcpyDeviceToHost));
+        RTU_HIP(ctx, hipMemcpy(&h, ctx->fcnt_side.get(), sizeof h, hipMemcpyDeviceToHost));
         for (int L = 0; L < RTU_MAX_LEVELS; L++)
             for (int s = 0; s < RTU_SHARDS; s++) frames_out[L] += h.n_frames[L][(s) * RTU_CSTRIDE];
         for (int s = 0; s < RTU_SHARDS; s++) deferred_out[0] += h.n_defer[0][(s) * RTU_CSTRIDE];
@@ -2744,22 +2625,22 @@ int rtu_frame_counts(RtuContext* ctx, uint32_t* frames_out, uint32_t* deferred_o
 int rtu_selftest_division(RtuContext* ctx, unsigned long long n_pairs, unsigned long long seed, unsigned long long* mismatches_out) {
     if (!ctx || !mismatches_out) return RTU_ERR_ARG;
     RTU_HIP(ctx, hipSetDevice(ctx->device));
-    RTU_HIP(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));
-    hipError_t e = (hipError_t)rtu_launch_selftest_fdiv(n_pairs, seed, ctx->counters, ctx->stream);
+    RTU_HIP(ctx, hipMemsetAsync(ctx->counters.get(), 0, sizeof(unsigned long long), ctx->stream));
+    hipError_t e = (hipError_t)rtu_launch_selftest_fdiv(n_pairs, seed, ctx->counters.get(), ctx->stream);
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "selftest launch: %s", hipGetErrorString(e));
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RTU_HIP(ctx, hipMemcpy(mismatches_out, ctx->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(mismatches_out, ctx->counters.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RTU_OK;
 }
 
 int rtu_selftest_primitives(RtuContext* ctx, unsigned long long n_rays, unsigned long long seed, unsigned long long* mismatches_out) {
     if (!ctx || !mismatches_out) return RTU_ERR_ARG;
     RTU_HIP(ctx, hipSetDevice(ctx->device));
-    RTU_HIP(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));
-    hipError_t e = (hipError_t)rtu_launch_selftest_prims(n_rays, seed, ctx->counters, ctx->stream);
+    RTU_HIP(ctx, hipMemsetAsync(ctx->counters.get(), 0, sizeof(unsigned long long), ctx->stream));
+    hipError_t e = (hipError_t)rtu_launch_selftest_prims(n_rays, seed, ctx->counters.get(), ctx->stream);
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "selftest launch: %s", hipGetErrorString(e));
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RTU_HIP(ctx, hipMemcpy(mismatches_out, ctx->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(mismatches_out, ctx->counters.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RTU_OK;
 }
 
@@ -2786,25 +2667,24 @@ int rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, u
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     const unsigned long long chunk = 1ull << 22;
     const int nin = RTU_TEXOP_IN(op), nout = RTU_TEXOP_OUT(op);
-    float *d_in = nullptr, *d_out = nullptr;
-    RtuTexMap* d_map = nullptr;  // the kernel reads the map from device memory
-    hipError_t e = hipMalloc(&d_in, sizeof(float) * nin * chunk);
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * nout * chunk);
-    if (e == hipSuccess && op == RTU_TEXOP_MAP) e = hipMalloc(&d_map, sizeof map);
-    if (e == hipSuccess && op == RTU_TEXOP_MAP) e = hipMemcpy(d_map, &map, sizeof map, hipMemcpyHostToDevice);
+    DevBuf<float> d_in, d_out;
+    DevBuf<RtuTexMap> d_map;  // the kernel reads the map from device memory
+    hipError_t e = d_in.grow(nin * chunk);
+    if (e == hipSuccess) e = d_out.grow(nout * chunk);
+    if (e == hipSuccess && op == RTU_TEXOP_MAP) e = d_map.grow(1);
+    if (e == hipSuccess && op == RTU_TEXOP_MAP) e = hipMemcpy(d_map.get(), &map, sizeof map, hipMemcpyHostToDevice);
     for (unsigned long long done = 0; e == hipSuccess && done < n; done += chunk) {
         const unsigned long long m = n - done < chunk ? n - done : chunk;
-        e = hipMemcpyAsync(d_in, h_in + nin * done, sizeof(float) * nin * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = (hipError_t)rtu_launch_debug_texcoords(s, op, tex, d_map, d_in, d_out, m, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_out + nout * done, d_out, sizeof(float) * nout * m, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(d_in.get(), h_in + nin * done, sizeof(float) * nin * m, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = (hipError_t)rtu_launch_debug_texcoords(s, op, tex, d_map.get(), d_in.get(), d_out.get(), m, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_out + nout * done, d_out.get(), sizeof(float) * nout * m, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_map);
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "texcoords: %s", hipGetErrorString(e));
     return RTU_OK;
 }
+
+unsigned long long rtu_debug_device_allocations(void) { return g_devbuf_allocations.load(); }
 
 void* rtu_device_alloc(RtuContext* ctx, size_t bytes) {
     if (!ctx || bytes == 0) return nullptr;

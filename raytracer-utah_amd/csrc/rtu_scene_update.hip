@@ -12,6 +12,7 @@
 //   radix sort     stable, by key: per cell ascending zmin, ties in face order — std::stable_sort of the host's face-order cells
 //   k_cell_off     cell -> first entry (binary search), and the longest cell
 //   k_entries      {slot of the fast tree, zmin bits} per entry
+#include "rtu_devbuf.h"
 #include "rtu_lightlist.h"
 
 #include <hipcub/hipcub.hpp>
@@ -23,16 +24,11 @@ namespace {
 
 const int kBlock = 256;
 
+// at least n elements, with slack: a buffer that grows gets n + n / 4 + 64
 template <class T>
-hipError_t grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 4 + 64;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
+hipError_t grow(DevBuf<T>& b, size_t n) {
+    if (n <= b.size() && b.get()) return hipSuccess;
+    return b.grow(n + n / 4 + 64);
 }
 
 // a float's bits as an unsigned key in the order of float comparison: -0 and +0 are one key (they compare equal, so the face
@@ -210,29 +206,19 @@ uint32_t blocks_capped(unsigned long long n) { const unsigned long long b = (n +
 }  // namespace
 
 struct LlBuilder {
-    double* verts[RTU_MAX_COVER] = {};    // per cover node: 9 doubles per face (world-space vertices)
-    size_t  verts_cap[RTU_MAX_COVER] = {};
-    double* red = nullptr;                // reductions (6 doubles per cover node / pair)
-    size_t  red_cap = 0;
-    LlFrame* frames = nullptr;
-    size_t   frames_cap = 0;
-    int*     pair_cover = nullptr;
-    size_t   pair_cover_cap = 0;
-    LlFaceCells* cells = nullptr;         // of the list being built
-    size_t   cells_cap = 0;
-    unsigned long long* rows = nullptr;   // [nf + 1] rows per face, then its first (face, row) pair
-    unsigned long long* row_start = nullptr;
-    size_t   rows_cap = 0, row_start_cap = 0;
-    unsigned long long* cnt = nullptr;    // [R + 1] entries per (face, row), then where they go
-    unsigned long long* ent_start = nullptr;
-    size_t   cnt_cap = 0, ent_start_cap = 0;
-    unsigned long long* keys[2] = {};
-    uint32_t* vals[2] = {};
-    size_t   keys_cap[2] = {}, vals_cap[2] = {};
-    void*    tmp = nullptr;
-    size_t   tmp_cap = 0;
-    uint32_t* longest = nullptr;
-    size_t   longest_cap = 0;
+    DevBuf<double> verts[RTU_MAX_COVER];  // per cover node: 9 doubles per face (world-space vertices)
+    DevBuf<double> red;                   // reductions (6 doubles per cover node / pair)
+    DevBuf<LlFrame> frames;
+    DevBuf<int> pair_cover;
+    DevBuf<LlFaceCells> cells;            // of the list being built
+    DevBuf<unsigned long long> rows;      // [nf + 1] rows per face, then its first (face, row) pair
+    DevBuf<unsigned long long> row_start;
+    DevBuf<unsigned long long> cnt;       // [R + 1] entries per (face, row), then where they go
+    DevBuf<unsigned long long> ent_start;
+    DevBuf<unsigned long long> keys[2];
+    DevBuf<uint32_t> vals[2];
+    DevBuf<char> tmp;                     // hipcub's temporary storage
+    DevBuf<uint32_t> longest;
     // the list counted last
     uint32_t cur_nf = 0, cur_E = 0;
     int      cur_cover = -1;
@@ -256,23 +242,14 @@ hipError_t tock(LlBuilder* b, hipStream_t st, float* acc) {
     return hipSuccess;
 }
 
-hipError_t tmp_for(LlBuilder* b, size_t bytes) {
-    size_t cap = b->tmp_cap;
-    char* p = (char*)b->tmp;
-    hipError_t e = grow(p, cap, bytes);
-    b->tmp = p;
-    b->tmp_cap = cap;
-    return e;
-}
-
 // exclusive sum of n + 1 values (the last one 0): out[n] is the total
 hipError_t scan(LlBuilder* b, hipStream_t st, const unsigned long long* in, unsigned long long* out, size_t n1) {
     size_t bytes = 0;
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n1, st);
     if (e != hipSuccess) return e;
-    if ((e = tmp_for(b, bytes)) != hipSuccess) return e;
-    bytes = b->tmp_cap;
-    return hipcub::DeviceScan::ExclusiveSum(b->tmp, bytes, in, out, n1, st);
+    if ((e = grow(b->tmp, bytes)) != hipSuccess) return e;
+    bytes = b->tmp.size();
+    return hipcub::DeviceScan::ExclusiveSum(b->tmp.get(), bytes, in, out, n1, st);
 }
 
 CoverSet cover_set(const LlCover* covers, int n) {
@@ -290,9 +267,6 @@ LlBuilder* ll_builder_create() { return new LlBuilder; }
 
 void ll_builder_destroy(LlBuilder* b) {
     if (!b) return;
-    for (double* p : b->verts) if (p) (void)hipFree(p);
-    void* bufs[] = {b->red, b->frames, b->pair_cover, b->cells, b->rows, b->row_start, b->cnt, b->ent_start, b->keys[0], b->keys[1], b->vals[0], b->vals[1], b->tmp, b->longest};
-    for (void* p : bufs) if (p) (void)hipFree(p);
     for (hipEvent_t e : b->ev) if (e) (void)hipEventDestroy(e);
     delete b;
 }
@@ -314,14 +288,14 @@ hipError_t ll_build_covers(LlBuilder* b, hipStream_t st, const LlCover* covers, 
     LL_TRY(tick(b, st));
     for (int c = 0; c < n_cover; c++) {
         const LlCover& cv = covers[c];
-        LL_TRY(grow(b->verts[c], b->verts_cap[c], (size_t)cv.nf * 9));
-        k_cover_faces<<<blocks_for(cv.nf), kBlock, 0, st>>>(cv.f, cv.v, cv.nf, cv.chain, b->verts[c], cv.boxes);
+        LL_TRY(grow(b->verts[c], (size_t)cv.nf * 9));
+        k_cover_faces<<<blocks_for(cv.nf), kBlock, 0, st>>>(cv.f, cv.v, cv.nf, cv.chain, b->verts[c].get(), cv.boxes);
         LL_TRY(hipGetLastError());
     }
-    LL_TRY(grow(b->red, b->red_cap, (size_t)6 * RTU_LMASK_LIGHTS * RTU_MAX_COVER));
-    k_box_extent<<<n_cover, kBlock, 0, st>>>(cover_set(covers, n_cover), b->red);
+    LL_TRY(grow(b->red, (size_t)6 * RTU_LMASK_LIGHTS * RTU_MAX_COVER));
+    k_box_extent<<<n_cover, kBlock, 0, st>>>(cover_set(covers, n_cover), b->red.get());
     LL_TRY(hipGetLastError());
-    LL_TRY(hipMemcpyAsync(lohi_out, b->red, sizeof(double) * 6 * n_cover, hipMemcpyDeviceToHost, st));
+    LL_TRY(hipMemcpyAsync(lohi_out, b->red.get(), sizeof(double) * 6 * n_cover, hipMemcpyDeviceToHost, st));
     LL_TRY(hipStreamSynchronize(st));
     return tock(b, st, &b->t.cover_ms);
 }
@@ -332,14 +306,14 @@ hipError_t ll_build_extents(LlBuilder* b, hipStream_t st, const LlCover* covers,
     LL_TRY(tick(b, st));
     int n_cover = 0;
     for (int p = 0; p < n_pairs; p++) n_cover = pair_cover[p] + 1 > n_cover ? pair_cover[p] + 1 : n_cover;
-    LL_TRY(grow(b->frames, b->frames_cap, (size_t)n_pairs));
-    LL_TRY(grow(b->pair_cover, b->pair_cover_cap, (size_t)n_pairs));
-    LL_TRY(grow(b->red, b->red_cap, (size_t)6 * n_pairs));
-    LL_TRY(hipMemcpyAsync(b->frames, frames, sizeof(LlFrame) * n_pairs, hipMemcpyHostToDevice, st));
-    LL_TRY(hipMemcpyAsync(b->pair_cover, pair_cover, sizeof(int) * n_pairs, hipMemcpyHostToDevice, st));
-    k_corner_extent<<<n_pairs, kBlock, 0, st>>>(cover_set(covers, n_cover), b->pair_cover, b->frames, wscale, b->red);
+    LL_TRY(grow(b->frames, (size_t)n_pairs));
+    LL_TRY(grow(b->pair_cover, (size_t)n_pairs));
+    LL_TRY(grow(b->red, (size_t)6 * n_pairs));
+    LL_TRY(hipMemcpyAsync(b->frames.get(), frames, sizeof(LlFrame) * n_pairs, hipMemcpyHostToDevice, st));
+    LL_TRY(hipMemcpyAsync(b->pair_cover.get(), pair_cover, sizeof(int) * n_pairs, hipMemcpyHostToDevice, st));
+    k_corner_extent<<<n_pairs, kBlock, 0, st>>>(cover_set(covers, n_cover), b->pair_cover.get(), b->frames.get(), wscale, b->red.get());
     LL_TRY(hipGetLastError());
-    LL_TRY(hipMemcpyAsync(out6, b->red, sizeof(double) * 6 * n_pairs, hipMemcpyDeviceToHost, st));
+    LL_TRY(hipMemcpyAsync(out6, b->red.get(), sizeof(double) * 6 * n_pairs, hipMemcpyDeviceToHost, st));
     LL_TRY(hipStreamSynchronize(st));
     return tock(b, st, &b->t.extent_ms);
 }
@@ -347,22 +321,22 @@ hipError_t ll_build_extents(LlBuilder* b, hipStream_t st, const LlCover* covers,
 hipError_t ll_count(LlBuilder* b, hipStream_t st, const LlCover& cv, int cover_index, const LlFrame& F, const LlGrid& g, float wscale, size_t* entries_out) {
     LL_TRY(tick(b, st));
     const uint32_t nf = cv.nf;
-    LL_TRY(grow(b->cells, b->cells_cap, (size_t)nf));
-    LL_TRY(grow(b->rows, b->rows_cap, (size_t)nf + 1));
-    LL_TRY(grow(b->row_start, b->row_start_cap, (size_t)nf + 1));
-    k_face_setup<<<blocks_for(nf), kBlock, 0, st>>>(b->verts[cover_index], cv.boxes, nf, F, g, wscale, b->cells, b->rows);
+    LL_TRY(grow(b->cells, (size_t)nf));
+    LL_TRY(grow(b->rows, (size_t)nf + 1));
+    LL_TRY(grow(b->row_start, (size_t)nf + 1));
+    k_face_setup<<<blocks_for(nf), kBlock, 0, st>>>(b->verts[cover_index].get(), cv.boxes, nf, F, g, wscale, b->cells.get(), b->rows.get());
     LL_TRY(hipGetLastError());
-    LL_TRY(scan(b, st, b->rows, b->row_start, (size_t)nf + 1));
+    LL_TRY(scan(b, st, b->rows.get(), b->row_start.get(), (size_t)nf + 1));
     unsigned long long R = 0;
-    LL_TRY(hipMemcpyAsync(&R, b->row_start + nf, sizeof R, hipMemcpyDeviceToHost, st));
+    LL_TRY(hipMemcpyAsync(&R, b->row_start.get() + nf, sizeof R, hipMemcpyDeviceToHost, st));
     LL_TRY(hipStreamSynchronize(st));
-    LL_TRY(grow(b->cnt, b->cnt_cap, (size_t)R + 1));
-    LL_TRY(grow(b->ent_start, b->ent_start_cap, (size_t)R + 1));
-    k_row_count<<<blocks_capped(R), kBlock, 0, st>>>(b->row_start, nf, R, b->cells, b->cnt);
+    LL_TRY(grow(b->cnt, (size_t)R + 1));
+    LL_TRY(grow(b->ent_start, (size_t)R + 1));
+    k_row_count<<<blocks_capped(R), kBlock, 0, st>>>(b->row_start.get(), nf, R, b->cells.get(), b->cnt.get());
     LL_TRY(hipGetLastError());
-    LL_TRY(scan(b, st, b->cnt, b->ent_start, (size_t)R + 1));
+    LL_TRY(scan(b, st, b->cnt.get(), b->ent_start.get(), (size_t)R + 1));
     unsigned long long E = 0;
-    LL_TRY(hipMemcpyAsync(&E, b->ent_start + R, sizeof E, hipMemcpyDeviceToHost, st));
+    LL_TRY(hipMemcpyAsync(&E, b->ent_start.get() + R, sizeof E, hipMemcpyDeviceToHost, st));
     LL_TRY(hipStreamSynchronize(st));
     b->cur_nf = nf;
     b->cur_R = R;
@@ -377,34 +351,34 @@ hipError_t ll_fill(LlBuilder* b, hipStream_t st, const LlCover& cv, const LlGrid
     LL_TRY(tick(b, st));
     const uint32_t E = b->cur_E, cells = g.G * g.G;
     for (int k = 0; k < 2; k++) {
-        LL_TRY(grow(b->keys[k], b->keys_cap[k], (size_t)E + 1));
-        LL_TRY(grow(b->vals[k], b->vals_cap[k], (size_t)E + 1));
+        LL_TRY(grow(b->keys[k], (size_t)E + 1));
+        LL_TRY(grow(b->vals[k], (size_t)E + 1));
     }
-    LL_TRY(grow(b->longest, b->longest_cap, 1));
-    LL_TRY(hipMemsetAsync(b->longest, 0, sizeof(uint32_t), st));
+    LL_TRY(grow(b->longest, 1));
+    LL_TRY(hipMemsetAsync(b->longest.get(), 0, sizeof(uint32_t), st));
     if (b->cur_R)
-        k_row_fill<<<blocks_capped(b->cur_R), kBlock, 0, st>>>(b->row_start, b->cur_nf, b->cur_R, b->cells, g.G, b->ent_start, b->keys[0], b->vals[0]);
+        k_row_fill<<<blocks_capped(b->cur_R), kBlock, 0, st>>>(b->row_start.get(), b->cur_nf, b->cur_R, b->cells.get(), g.G, b->ent_start.get(), b->keys[0].get(), b->vals[0].get());
     LL_TRY(hipGetLastError());
     LL_TRY(tock(b, st, &b->t.fill_ms));
     LL_TRY(tick(b, st));
     int end_bit = 32;
     while ((1u << (end_bit - 32)) < cells) end_bit++;
-    hipcub::DoubleBuffer<unsigned long long> kb(b->keys[0], b->keys[1]);
-    hipcub::DoubleBuffer<uint32_t> vb(b->vals[0], b->vals[1]);
+    hipcub::DoubleBuffer<unsigned long long> kb(b->keys[0].get(), b->keys[1].get());
+    hipcub::DoubleBuffer<uint32_t> vb(b->vals[0].get(), b->vals[1].get());
     if (E > 1) {
         size_t bytes = 0;
         LL_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, kb, vb, (int)E, 0, end_bit, st));
-        LL_TRY(tmp_for(b, bytes));
-        bytes = b->tmp_cap;
-        LL_TRY(hipcub::DeviceRadixSort::SortPairs(b->tmp, bytes, kb, vb, (int)E, 0, end_bit, st));
+        LL_TRY(grow(b->tmp, bytes));
+        bytes = b->tmp.size();
+        LL_TRY(hipcub::DeviceRadixSort::SortPairs(b->tmp.get(), bytes, kb, vb, (int)E, 0, end_bit, st));
     }
     LL_TRY(tock(b, st, &b->t.sort_ms));
     LL_TRY(tick(b, st));
-    k_cell_off<<<blocks_for((size_t)cells + 1), kBlock, 0, st>>>(kb.Current(), E, cells, cell_off, b->longest);
+    k_cell_off<<<blocks_for((size_t)cells + 1), kBlock, 0, st>>>(kb.Current(), E, cells, cell_off, b->longest.get());
     LL_TRY(hipGetLastError());
-    if (E) k_entries<<<blocks_for(E), kBlock, 0, st>>>(vb.Current(), E, cv.slot_of, b->cells, cell_tri);
+    if (E) k_entries<<<blocks_for(E), kBlock, 0, st>>>(vb.Current(), E, cv.slot_of, b->cells.get(), cell_tri);
     LL_TRY(hipGetLastError());
-    LL_TRY(hipMemcpyAsync(longest_out, b->longest, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LL_TRY(hipMemcpyAsync(longest_out, b->longest.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     LL_TRY(hipStreamSynchronize(st));
     b->t.lists++;
     return tock(b, st, &b->t.fill_ms);

@@ -1336,7 +1336,8 @@ def test_alternating_launch_shapes_do_not_reallocate(pkg, ctx, golden):
     """A caller that alternates launch shapes — a run of batches whose last one is shorter — must not make the frame arrays swing between
     the shapes' wishes: the smaller batch (below the 16 M pixels from which deeper levels start at a quarter of level 0) wants MORE at the
     deep levels and less at level 0 than the larger one. The arrays only grow (ensure_levels); found as a 2.4 s stall per timed region of
-    `bench.py --frames-in-flight 24` (every launch freed and allocated 20 GB). Timed with two orders of magnitude to spare."""
+    `bench.py --frames-in-flight 24` (every launch freed and allocated 20 GB). Timed with two orders of magnitude to spare, and the
+    library's own device allocations counted (rtu_debug_device_allocations): none."""
     import time
     g = golden("teapot2_1080")
     scene = g.scene(pkg)
@@ -1360,12 +1361,15 @@ def test_alternating_launch_shapes_do_not_reallocate(pkg, ctx, golden):
         for _ in range(2):
             launch(big)
             launch(small)
+        allocs = pkg.hip.rtu_debug_device_allocations()
         t0 = time.perf_counter()
         for _ in range(6):
             launch(big)
             launch(small)
         el = time.perf_counter() - t0
         assert el < 0.6, "twelve launches took %.2f s: the frame arrays are being reallocated" % el
+        grown = pkg.hip.rtu_debug_device_allocations() - allocs
+        assert grown == 0, "twelve launches made %d device allocations" % grown
         got = np.empty((small, H, W, 4), np.float32)
         assert pkg.hip.rtu_copy_to_host(ctx._h, got.ctypes.data, d, got.nbytes) == 0
         assert np.array_equal(got[small - 1].view(np.uint32), single.view(np.uint32))
