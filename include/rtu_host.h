@@ -17,6 +17,8 @@
  *                           <- ComputeSampleCountImage / SaveSampleCountImage  scene.h:614-640
  *   rtu_begin_render / rtu_stop_render / rtu_render_wait
  *                           <- BeginRender()/StopRender()        main.cpp:66-72, viewport.cpp:36-37
+ *   rtu_begin_render_progressive
+ *                           <- the viewport showing renderImage fill in  viewport.cpp:390-449
  */
 #ifndef RTU_HOST_H_INCLUDED
 #define RTU_HOST_H_INCLUDED
@@ -125,7 +127,24 @@ RtuRenderJob* rtu_begin_render_paths(const RtuScene* scene, RtuImage* img,
 RtuRenderJob* rtu_begin_render_adaptive(const RtuScene* scene, RtuImage* img, const int* device_ids, int n_devices, int samples,
                                         int gather_bounces, const RtuAdaptiveDesc* adaptive, const char* result_png,
                                         const char* zbuffer_png, const char* samplecount_png);
-void      rtu_stop_render(RtuRenderJob* job);      /* cooperative cancel between bands */
+/* Progressive display (rtu_progressive_begin, rtu_render.h): the frame refined pass by pass behind BeginRender(), as the reference's
+ * viewport shows renderImage filling in (viewport.cpp:390-449). A recipe S (gather_bounces 0) or P (4) frame of `samples` per pixel
+ * (adaptive NULL), or adaptive with `samples` the maximum (1 .. 255). pass_samples[n_passes] are the samples of each pass: every
+ * one >= 1, adding up to `samples` (NULL: 1, 1, 2, 4, 8, ... — each pass doubles what is shown, the last one up to `samples`);
+ * anything else is refused (NULL, rtu_host_last_error) before any GPU is touched. One context and one session per listed device (ids
+ * may repeat), each rendering its shard; the passes advance in lockstep. After every pass the shards' snapshots are assembled into
+ * img — Color24 pixels, z-buffer, and sample counts when adaptive — and on_pass(user, samples_done, pass) is called from the job's
+ * thread (pass: 1 for the first); the next pass starts when it returns, so img does not change while it runs (copy img there); the rendered-pixel counter reaches W * H with the first pass and stays there. At the end:
+ * Result.png, ZBuffer.png and, adaptive only, SampleCount.png (any path may be NULL). rtu_stop_render ends the job after the current
+ * batch: img then holds the last complete pass, which is VALID — the mean of each pixel's first samples_done samples (its count, if
+ * adaptive) — and its PNGs are written; rtu_render_wait returns RTU_ERR_CANCELLED (no PNG if no pass had completed). */
+typedef void (*RtuPassDone)(void* user, int samples_done, int pass);
+RtuRenderJob* rtu_begin_render_progressive(const RtuScene* scene, RtuImage* img, const int* device_ids, int n_devices,
+                                           int samples, int gather_bounces, const RtuAdaptiveDesc* adaptive,
+                                           const int* pass_samples, int n_passes,
+                                           RtuPassDone on_pass, void* user,
+                                           const char* result_png, const char* zbuffer_png, const char* samplecount_png);
+void      rtu_stop_render(RtuRenderJob* job);      /* cooperative cancel between bands (a relaxed atomic store: any thread) */
 int       rtu_render_wait(RtuRenderJob* job);      /* join; 0 or negative error code */
 /* After the job (joins): how the shards reached the host — 1 one context; 2 several contexts, asynchronous copies into one
  * pinned buffer, all in flight together; 3 RCCL (grouped ncclSend / ncclRecv to the root GPU, then one copy). */

@@ -45,6 +45,7 @@ extern "C" {
 #define RTU_ERR_CAPACITY    (-7)  /* more Shade() frames than provisioned (see rtu_frame_status) */
 #define RTU_ERR_CANCELLED   (-8)  /* the caller's cancel flag was raised (rtu_set_cancel_flag, RtuProgress): StopRender(), main.cpp:70-72 */
 #define RTU_ERR_SCENE_SHAPE (-9)  /* rtu_update_scene: not the shape of the uploaded scene (rtu_last_error names the first difference) */
+#define RTU_ERR_STALE       (-10) /* a progressive session's context got a new scene (rtu_upload_scene / rtu_update_scene) */
 
 #define RTU_BAND_ROWS 8  /* image rows per band; one wavefront renders an 8x8 pixel tile */
 
@@ -254,9 +255,41 @@ int  rtu_render_frame_adaptive_device(RtuContext* ctx, const RtuFrameDesc* frame
  * adds, n x rtu_shard_rows x width float4 {r, g, b, z}, z = RTU_BIGFLOAT for a miss — to h_out. Synchronous. */
 int  rtu_debug_sample_images(RtuContext* ctx, const RtuFrameDesc* frame, int first, int n, float* h_out);
 
+/* ---- Progressive rendering: a recipe S / P frame refined call by call, shown at any time -------------------------------------------
+ * What the reference's viewport shows while Render() runs (viewport.cpp:390-449): the image fills in and can be stopped. A SESSION keeps
+ * the running sums of one frame between calls. frame is a recipe S or P frame (samples >= 1, gather_bounces 0 or 4, collect_stats 0);
+ * frame.samples is the TARGET count S — it fixes the pixel offsets index / S + Halton(index, 4|5) (RenderFunctions.cpp:80-85), so it is
+ * known from the start. Shards are honoured. adaptive (may be NULL: every pixel takes every sample) is checked as for
+ * rtu_render_frame_adaptive (then S <= 255). RTU_ERR_ARG for anything else; *err_out (may be NULL) gets the code.
+ *   rtu_progressive_advance   traces samples [done, done + n) in the batches of the one-shot render (RTU_MAX_BATCH, 2^25 pixels,
+ *                             max_batch), each checked for capacity and rendered again if need be before it is added; the cancel flag
+ *                             (rtu_set_cancel_flag) is polled before every batch: RTU_ERR_CANCELLED with done at the last batch added, the
+ *                             session still usable. n < 1 or done + n > S: RTU_ERR_ARG. An adaptive session whose pixels have all stopped
+ *                             traces nothing (done still advances). Synchronous: on return the sums are complete on `hip_stream`.
+ *                             RTU_ERR_STALE once the context got a new scene (rtu_upload_scene / rtu_update_scene).
+ *   rtu_progressive_status    samples done, and the 8x8 tiles that still sample: the length of an adaptive session's active-tile list
+ *                             (all tiles before the first batch), all tiles of a fixed one until done == S, then 0. Either pointer may be NULL.
+ *   rtu_progressive_snapshot  the image now, the session left as it is: pixel p with n samples so far (done; adaptive: its own count,
+ *                             min(done, its stop)) is rgb = s / n, z = (sum of z) / hits (RTU_BIGFLOAT without a hit) — the binary32
+ *                             operations of the one-shot resolve, so a session driven to S is the one-shot image bit for bit, and after
+ *                             any pass the mean of each pixel's first n samples. counts (may be NULL; only when S <= 255) receives n.
+ *                             done == 0: RTU_ERR_ARG. Still answers after RTU_ERR_STALE. The _device form writes d_rgbz (rtu_shard_rows
+ *                             * width float4) and d_counts asynchronously on hip_stream; the host form is synchronous.
+ * The session owns its sums (none of the context's own): a render on the same context between two calls neither disturbs it nor is
+ * disturbed by it, and several sessions may be open on one context. rtu_destroy_context frees the device memory of its open sessions;
+ * every call on such a handle but rtu_progressive_free then returns RTU_ERR_ARG. Messages: rtu_last_error of the context. */
+typedef struct RtuProgressive RtuProgressive;
+RtuProgressive* rtu_progressive_begin(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, int* err_out);
+int  rtu_progressive_advance(RtuProgressive* p, int n_samples, void* hip_stream);
+int  rtu_progressive_status(const RtuProgressive* p, int32_t* samples_done, uint32_t* live_tiles);
+int  rtu_progressive_snapshot_device(RtuProgressive* p, void* d_rgbz, void* d_counts, void* hip_stream);
+int  rtu_progressive_snapshot(RtuProgressive* p, float* h_rgbz, uint8_t* h_counts);
+void rtu_progressive_free(RtuProgressive* p);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
- * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. A single launch sequence (a frame of
+ * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer
+ * on another thread stores it with __atomic_store_n(flag, 1, __ATOMIC_RELAXED) (rtu_stop_render does). A single launch sequence (a frame of
  * recipe W, a batch of frames in flight) is a fraction of a millisecond and is never interrupted. */
 int  rtu_set_cancel_flag(RtuContext* ctx, const volatile int* flag);
 
@@ -463,6 +496,8 @@ int  rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, 
 /* Debug: device allocations the library has made for its own buffers so far (every context together, the whole process).
  * rtu_device_alloc is not counted. */
 unsigned long long rtu_debug_device_allocations(void);
+/* Debug: bytes of device memory the library's own buffers hold now (every context and progressive session together). */
+unsigned long long rtu_debug_device_bytes(void);
 
 /* Device memory helpers so a C/C++ host needs no HIP headers. */
 /* The context's own stream (a hipStream_t as void*) and device: a multi-GPU host (host/begin_render.cpp) renders every shard on

@@ -34,6 +34,7 @@ RTU_ERR_NO_DEVICE = -6
 RTU_ERR_CAPACITY = -7
 RTU_ERR_CANCELLED = -8
 RTU_ERR_SCENE_SHAPE = -9
+RTU_ERR_STALE = -10  # a progressive session's context got a new scene
 
 
 class RtuError(RuntimeError):
@@ -149,7 +150,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_device_free", "rtu_copy_to_host", "rtu_device_info", "rtu_set_cancel_flag", "rtu_create_context_multi", "rtu_destroy_context_multi",
                "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind",
                "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords",
-               "rtu_debug_device_allocations"]
+               "rtu_debug_device_allocations", "rtu_progressive_begin", "rtu_progressive_advance", "rtu_progressive_status",
+               "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -205,6 +207,13 @@ _sig(hip, "rtu_render_frame_adaptive_device", _I, _P, ctypes.POINTER(RtuFrameDes
 _sig(hip, "rtu_debug_sample_images", _I, _P, ctypes.POINTER(RtuFrameDesc), _I, _I, _P)
 _sig(hip, "rtu_debug_texcoords", _I, _P, _I, _I, _P, ctypes.c_ulonglong, _P)
 _sig(hip, "rtu_debug_device_allocations", ctypes.c_ulonglong)
+_sig(hip, "rtu_debug_device_bytes", ctypes.c_ulonglong)
+_sig(hip, "rtu_progressive_begin", _P, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuAdaptiveDesc), ctypes.POINTER(_I))
+_sig(hip, "rtu_progressive_advance", _I, _P, _I, _P)
+_sig(hip, "rtu_progressive_status", _I, _P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32))
+_sig(hip, "rtu_progressive_snapshot_device", _I, _P, _P, _P, _P)
+_sig(hip, "rtu_progressive_snapshot", _I, _P, _P, _P)
+_sig(hip, "rtu_progressive_free", None, _P)
 # rtu_debug_texcoords operations (include/rtu_render.h RTU_TEXOP_*) and the floats per input / output of each
 TEXOP_ATAN2F, TEXOP_ASINF, TEXOP_SPHERE_UV, TEXOP_ENV_UVW, TEXOP_TILE_CLAMP, TEXOP_TEXTURE, TEXOP_MAP = range(7)
 TEXOP_IN = (2, 1, 3, 3, 3, 3, 3)
@@ -323,7 +332,7 @@ HOST_SYMBOLS = ["rtu_scene_load_xml", "rtu_scene_clone", "rtu_scene_load_blob", 
                 "rtu_begin_render", "rtu_begin_render_sampled", "rtu_begin_render_paths", "rtu_stop_render", "rtu_render_wait", "rtu_render_gather_kind", "rtu_render_job_free",
                 "rtu_image_sample_count", "rtu_image_fill_sample_count", "rtu_image_compute_sample_count_img", "rtu_image_sample_count_image",
                 "rtu_image_save_sample_count_png", "rtu_begin_render_adaptive", "rtu_scene_node_scale", "rtu_scene_node_rotate",
-                "rtu_scene_node_translate", "rtu_scene_set_light"]
+                "rtu_scene_node_translate", "rtu_scene_set_light", "rtu_begin_render_progressive"]
 _sig(host, "rtu_scene_load_xml", _P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
 _sig(host, "rtu_scene_clone", _P, _P)
 _sig(host, "rtu_scene_load_blob", _P, _P, ctypes.c_size_t)
@@ -368,6 +377,46 @@ _sig(host, "rtu_image_sample_count_image", _P, _P)
 _sig(host, "rtu_image_save_sample_count_png", _I, _P, ctypes.c_char_p)
 _sig(host, "rtu_begin_render_adaptive", _P, _P, _P, ctypes.POINTER(_I), _I, _I, _I, ctypes.POINTER(RtuAdaptiveDesc), ctypes.c_char_p, ctypes.c_char_p,
      ctypes.c_char_p)
+PASS_DONE = ctypes.CFUNCTYPE(None, _P, _I, _I)  # RtuPassDone(user, samples_done, pass)
+_sig(host, "rtu_begin_render_progressive", _P, _P, _P, ctypes.POINTER(_I), _I, _I, _I, ctypes.POINTER(RtuAdaptiveDesc), ctypes.POINTER(_I), _I,
+     PASS_DONE, _P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
+
+
+class ProgressiveJob:
+    """rtu_begin_render_progressive: the frame refined pass by pass into `image` on a host thread. on_pass(samples_done, pass) is
+    called after every pass (from that thread). wait() returns the job's code (RTU_ERR_CANCELLED after stop(): the image then holds
+    the last complete pass)."""
+
+    def __init__(self, scene, image, device_ids, samples, gather_bounces=0, adaptive=None, passes=None, on_pass=None, result_png=None,
+                 zbuffer_png=None, samplecount_png=None):
+        devs = (_I * len(device_ids))(*device_ids)
+        sched = (_I * len(passes))(*passes) if passes is not None else None
+        self._cb = PASS_DONE(lambda user, done, k: on_pass(done, k)) if on_pass else PASS_DONE()
+        enc = lambda p: p.encode() if p else None
+        self._h = host.rtu_begin_render_progressive(scene._h, image._h, devs, len(device_ids), samples, gather_bounces,
+                                                    ctypes.byref(adaptive) if adaptive is not None else None, sched,
+                                                    len(passes) if passes is not None else 0, self._cb, None, enc(result_png), enc(zbuffer_png),
+                                                    enc(samplecount_png))
+        if not self._h:
+            raise RtuError(RTU_ERR_ARG, host.rtu_host_last_error().decode())
+        self._keep = (scene, image)
+
+    def stop(self):
+        host.rtu_stop_render(self._h)
+
+    def wait(self):
+        return host.rtu_render_wait(self._h)
+
+    def close(self):
+        if self._h:
+            host.rtu_render_job_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Scene:
@@ -515,6 +564,58 @@ class MultiContext:
             pass
 
 
+class Progressive:
+    """A progressive session (RtuProgressive*, include/rtu_render.h): a recipe S / P frame refined call by call. Made by
+    Context.progressive(); errors raise RtuError with the context's message."""
+
+    def __init__(self, ctx, frame, adaptive=None):
+        err = _I(0)
+        self._ctx = ctx
+        self.frame = frame
+        self.adaptive = adaptive
+        self._h = hip.rtu_progressive_begin(ctx._h, ctypes.byref(frame), ctypes.byref(adaptive) if adaptive is not None else None, ctypes.byref(err))
+        if not self._h:
+            ctx._check(err.value if err.value != RTU_OK else RTU_ERR_ARG)
+
+    def _check(self, rc):
+        if rc != RTU_OK:
+            msg = hip.rtu_last_error(self._ctx._h).decode() if self._ctx._h else "the context is closed"
+            raise RtuError(rc, msg)
+
+    def advance(self, n, stream=None):
+        """Trace the next n samples (synchronous)."""
+        self._check(hip.rtu_progressive_advance(self._h, n, stream))
+
+    def status(self):
+        """(samples done, 8x8 tiles still sampling)."""
+        done, live = ctypes.c_int32(0), ctypes.c_uint32(0)
+        self._check(hip.rtu_progressive_status(self._h, ctypes.byref(done), ctypes.byref(live)))
+        return done.value, live.value
+
+    def snapshot(self):
+        """The image now: (rgbz float32 [rows, W, 4], counts uint8 [rows, W] — the samples each pixel has — or None when frame.samples > 255)."""
+        import numpy as np
+        rows = hip.rtu_shard_rows(ctypes.byref(self.frame))
+        out = np.empty((rows, self.frame.width, 4), np.float32)
+        counts = np.empty((rows, self.frame.width), np.uint8) if self.frame.samples <= 255 else None
+        self._check(hip.rtu_progressive_snapshot(self._h, out.ctypes.data, counts.ctypes.data if counts is not None else None))
+        return out, counts
+
+    def snapshot_device(self, d_rgbz, d_counts=None, stream=None):
+        self._check(hip.rtu_progressive_snapshot_device(self._h, d_rgbz, d_counts, stream))
+
+    def close(self):
+        if self._h:
+            hip.rtu_progressive_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU (RtuContext*)."""
 
@@ -576,6 +677,16 @@ class Context:
         self._check(hip.rtu_render_frame_adaptive(self._h, ctypes.byref(frame), ctypes.byref(adaptive), out.ctypes.data, counts.ctypes.data,
                                                   ctypes.byref(st) if stats else None))
         return out, counts, (st.as_dict() if stats else None)
+
+    def progressive(self, frame, adaptive=None):
+        """A progressive session of `frame` (recipe S / P; adaptive: RtuAdaptiveDesc or None for a fixed count): advance(n), status(),
+        snapshot() -> (rgbz, counts), close()."""
+        return Progressive(self, frame, adaptive)
+
+    def set_cancel(self, flag):
+        """rtu_set_cancel_flag: a ctypes.c_int the library polls between sample batches (None: none)."""
+        self._cancel = flag
+        self._check(hip.rtu_set_cancel_flag(self._h, ctypes.byref(flag) if flag is not None else None))
 
     def sample_images(self, frame, first, n):
         """The images of samples [first, first + n) of the fixed recipe S / P frame: float32 [n, rows, W, 4], what the accumulator adds."""

@@ -98,6 +98,12 @@ __global__ void __launch_bounds__(256) k_gi_final(KernelArgs a) {
 
 // ---- recipe S: the sums of RenderFunctions.cpp:109-110,148 in sample order, and :152 -----------
 namespace {
+// the mean of a pixel's sums over n samples of which `hits` hit: rgb / n, z / hits (BIGFLOAT without a hit), each a binary32
+// division. k_resolve, k_resolve_counts and k_progressive_snapshot all call this, so a snapshot is their image by construction.
+__device__ __forceinline__ float4 resolve_mean(const float4& s, uint32_t hits, float n) {
+    return make_float4(s.x / n, s.y / n, s.z / n, hits ? s.w / (float)hits : RTU_BIGFLOAT);
+}
+
 __global__ void __launch_bounds__(256) k_accumulate(const float4* samples, uint32_t batch, float4* acc, uint32_t* hits, uint32_t pixels, int first) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= pixels) return;
@@ -117,8 +123,20 @@ __global__ void __launch_bounds__(256) k_resolve(const float4* acc, const uint32
     if (i >= pixels) return;
     const float4 s = acc[i];
     const uint32_t n = hits[i];
-    const float S = (float)samples;
-    out[i] = make_float4(s.x / S, s.y / S, s.z / S, n ? s.w / (float)n : RTU_BIGFLOAT);
+    out[i] = resolve_mean(s, n, (float)samples);
+}
+
+// rtu_progressive_snapshot: the image of a session's running sums, which it leaves as they are. counts == nullptr: every pixel has
+// `n` samples (a fixed session); else its own count (adaptive). counts_out (may be nullptr) receives that count.
+__global__ void __launch_bounds__(256) k_progressive_snapshot(const float4* acc, const uint32_t* hits, const uint8_t* counts, uint32_t n, float4* out,
+                                                              uint8_t* counts_out, uint32_t pixels) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= pixels) return;
+    const float4 s = acc[i];
+    const uint32_t h = hits[i];
+    const uint32_t c = counts ? (uint32_t)counts[i] : n;
+    out[i] = resolve_mean(s, h, (float)c);
+    if (counts_out) counts_out[i] = (uint8_t)c;
 }
 }  // namespace
 
@@ -189,8 +207,7 @@ __global__ void __launch_bounds__(256) k_resolve_counts(const float4* acc, const
     const float4 s = acc[i];
     const uint32_t h = hits[i];
     const uint8_t c = counts[i];
-    const float S = (float)c;
-    out[i] = make_float4(s.x / S, s.y / S, s.z / S, h ? s.w / (float)h : RTU_BIGFLOAT);
+    out[i] = resolve_mean(s, h, (float)c);
     if (counts_out) counts_out[i] = c;
 }
 }  // namespace
@@ -309,6 +326,13 @@ int rtu_launch_accumulate(const float4* samples, uint32_t batch, float4* acc, ui
 }
 int rtu_launch_resolve(const float4* acc, const uint32_t* hits, float4* out, uint32_t pixels, uint32_t samples, hipStream_t stream) {
     hipLaunchKernelGGL(k_resolve, dim3((pixels + 255u) / 256u), dim3(256), 0, stream, acc, hits, out, pixels, samples);
+    return (int)hipGetLastError();
+}
+
+int rtu_launch_progressive_snapshot(const float4* acc, const uint32_t* hits, const uint8_t* counts, uint32_t n, float4* out, uint8_t* counts_out,
+                                    uint32_t pixels, hipStream_t stream) {
+    if (pixels == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_progressive_snapshot, dim3((pixels + 255u) / 256u), dim3(256), 0, stream, acc, hits, counts, n, out, counts_out, pixels);
     return (int)hipGetLastError();
 }
 

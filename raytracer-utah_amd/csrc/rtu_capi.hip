@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+struct RtuProgressive;
+
 struct RtuContext {
     int         device = 0;
     hipStream_t stream = nullptr;
@@ -114,6 +116,8 @@ struct RtuContext {
     int cam_slot = 0;
     uint32_t dbg = 0;
     const volatile int* cancel = nullptr;    // rtu_set_cancel_flag: polled between the launch sequences of a sampled frame
+    uint64_t scene_gen = 0;                  // bumped by every upload and update: a progressive session of an older scene is stale
+    std::vector<RtuProgressive*> sessions;   // the open progressive sessions (rtu_destroy_context frees their device memory)
     DevBuf<uint32_t> cover;                  // coverage masks of primary rays (KernelArgs::cover), grown on demand
     uint32_t  cover_faces = 0;
     DevBuf<uint32_t> occ;                    // tile occupancy of primary rays (KernelArgs::occ), grown on demand
@@ -1384,6 +1388,20 @@ struct SampledRun {
     int      first = 0, end = 0;
 };
 
+// The running sums a run of batches adds to — the context's own (render_sampled) or a progressive session's (rtu_progressive_*) —
+// and, adaptive, where the run stands: the active-tile lists, the one the next batch walks (cur) and its length (n_act).
+struct SampleSums {
+    float4*   acc = nullptr;
+    uint32_t* hits = nullptr;
+    float4*   sq = nullptr;        // adaptive only, from here on
+    uint8_t*  counts = nullptr;
+    uint4*    list[2] = {nullptr, nullptr};
+    uint32_t* n_dev = nullptr;     // [2] on the device
+    uint32_t* n_host = nullptr;    // pinned
+    int       cur = 0;
+    uint32_t  n_act = 0;
+};
+
 int ensure_adaptive(RtuContext* ctx, size_t pixels, size_t tiles) {  // grow-only, like acc
     RTU_HIP(ctx, ctx->ad_sq.grow(pixels));
     RTU_HIP(ctx, ctx->ad_counts.grow(pixels));
@@ -1393,53 +1411,55 @@ int ensure_adaptive(RtuContext* ctx, size_t pixels, size_t tiles) {  // grow-onl
     return RTU_OK;
 }
 
-// Recipe S: one launch sequence per batch of samples (as many as fit 2^25 pixels, at most RTU_MAX_BATCH),
-// each checked for frame-capacity overflow before its images are added to the accumulators in sample
-// order; the mean goes to d_out. Synchronises per batch.
-// Adaptive (run->ad): the primary phase of a batch walks the list of tiles that still have a pixel sampling; k_adaptive_step,
-// queued behind the batch and ahead of the batch's synchronisation, adds the samples of those pixels up to their stop and writes
-// the next list, whose length the host reads in that same synchronisation. A batch that has to be rendered again (capacity) is
-// not added (the step kernel sees the overflow flags the host will see).
-int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, const SampledRun* run = nullptr) {
-    const size_t pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
-    if (pixels == 0) return RTU_OK;
-    const bool gi = frame->gather_bounces != 0;
-    const RtuAdaptiveDesc* ad = run ? run->ad : nullptr;
-    float* const h_dump = run ? run->h_dump : nullptr;
+// Samples per launch sequence of a recipe S / P frame: as many as fit 2^25 pixels, at most RTU_MAX_BATCH (and max_batch, adaptive).
+int sampled_batch(const RtuFrameDesc* frame, const RtuAdaptiveDesc* ad, size_t pixels) {
     static const int kGiLog2 = [] { const char* e = getenv("RTU_GI_BATCH_LOG2"); return e ? atoi(e) : 25; }();  // tuning knob (23 / 24 / 25: 138.2 / 131.9 / 130.6 ms for config 5 at 64 spp)
+    const bool gi = frame->gather_bounces != 0;
     int batch = (int)(((size_t)1 << (gi ? kGiLog2 : 25)) / pixels);  // recipe P keeps 22 float4 per chain and two roots per chain hit (a larger batch buys nothing: measured)
     if (batch > RTU_MAX_BATCH) batch = RTU_MAX_BATCH;
     if (ad && ad->max_batch > 0 && batch > ad->max_batch) batch = ad->max_batch;
     if (batch > frame->samples) batch = frame->samples;
     if (batch < 1) batch = 1;
-    RTU_HIP(ctx, ctx->acc.grow(pixels));
-    RTU_HIP(ctx, ctx->acc_hits.grow(pixels));
-    RTU_HIP(ctx, ctx->sample_buf.grow(pixels * (size_t)batch));
+    return batch;
+}
+
+bool cancel_raised(const RtuContext* ctx) { return ctx->cancel && __atomic_load_n(ctx->cancel, __ATOMIC_RELAXED) != 0; }
+
+// The batch loop of recipes S / P: samples [i_begin, i_end) in batches of `batch`, one launch sequence each, each checked for
+// frame-capacity overflow before its images are added to `sums` in sample order. Synchronises per batch. *reached: the end of the
+// last batch added (i_end once an adaptive run's list is empty). The cancel word is polled before every batch.
+// Adaptive (run->ad): the primary phase of a batch walks the list of tiles that still have a pixel sampling; k_adaptive_step,
+// queued behind the batch and ahead of the batch's synchronisation, adds the samples of those pixels up to their stop and writes
+// the next list, whose length the host reads in that same synchronisation. A batch that has to be rendered again (capacity) is
+// not added (the step kernel sees the overflow flags the host will see).
+int sample_batches(RtuContext* ctx, const RtuFrameDesc* frame, hipStream_t stream, bool zero_counters, const SampledRun* run, SampleSums& sums,
+                   int i_begin, int i_end, int batch, int* reached) {
+    const size_t pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
+    const bool gi = frame->gather_bounces != 0;
+    const RtuAdaptiveDesc* ad = run ? run->ad : nullptr;
+    float* const h_dump = run ? run->h_dump : nullptr;
     const uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
     const uint32_t tiles = tiles_x * (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
-    if (ad) {
-        int rc = ensure_adaptive(ctx, pixels, tiles);
-        if (rc != RTU_OK) return rc;
-    }
-    int cur = 0;          // adaptive: the list the next batch walks ...
-    uint32_t n_act = 0;   // ... and its length
+    int& cur = sums.cur;          // adaptive: the list the next batch walks ...
+    uint32_t& n_act = sums.n_act; // ... and its length
+    *reached = i_begin;
     auto adaptive_start = [&]() -> int {  // (again after the counting variant starts over)
         cur = 0;
         n_act = tiles;
-        hipError_t e = (hipError_t)rtu_launch_adaptive_init(ctx->ad_list[0].get(), tiles, tiles_x, frame->width, frame->height, frame->shard_rank, frame->shard_count, stream);
+        hipError_t e = (hipError_t)rtu_launch_adaptive_init(sums.list[0], tiles, tiles_x, frame->width, frame->height, frame->shard_rank, frame->shard_count, stream);
         return e == hipSuccess ? RTU_OK : fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     };
     auto adaptive_step = [&](int i, int nb) -> int {
-        RTU_HIP(ctx, hipMemsetAsync(ctx->ad_n.get() + (cur ^ 1), 0, sizeof(uint32_t), stream));
+        RTU_HIP(ctx, hipMemsetAsync(sums.n_dev + (cur ^ 1), 0, sizeof(uint32_t), stream));
         AdaptiveStep p;
         p.samples = ctx->sample_buf.get();
-        p.acc = ctx->acc.get();
-        p.sq = ctx->ad_sq.get();
-        p.hits = ctx->acc_hits.get();
-        p.counts = ctx->ad_counts.get();
-        p.list_in = ctx->ad_list[cur].get();
-        p.list_out = ctx->ad_list[cur ^ 1].get();
-        p.n_out = ctx->ad_n.get() + (cur ^ 1);
+        p.acc = sums.acc;
+        p.sq = sums.sq;
+        p.hits = sums.hits;
+        p.counts = sums.counts;
+        p.list_in = sums.list[cur];
+        p.list_out = sums.list[cur ^ 1];
+        p.n_out = sums.n_dev + (cur ^ 1);
         p.skip_if = &ctx->fcnt.get()->overflow;
         p.skip_if_side = &ctx->fcnt_side.get()->overflow;
         p.n_in = n_act;
@@ -1457,20 +1477,20 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
         p.target = ad->target_variance;
         hipError_t e = (hipError_t)rtu_launch_adaptive_step(p, stream);
         if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-        RTU_HIP(ctx, hipMemcpyAsync(ctx->ad_n_host.get(), ctx->ad_n.get() + (cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        RTU_HIP(ctx, hipMemcpyAsync(sums.n_host, sums.n_dev + (cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         return RTU_OK;
     };
     const uint4* no_list = nullptr;
-    const int i_begin = h_dump ? run->first : 0, i_end = h_dump ? run->end : frame->samples;
     int rounds = 0;
     for (int i = i_begin; i < i_end; i += batch) {
-        if (ctx->cancel && *ctx->cancel) return fail(ctx, RTU_ERR_CANCELLED, "cancelled after %d of %d samples", i, frame->samples);  // StopRender(), main.cpp:70-72
+        *reached = i;
+        if (cancel_raised(ctx)) return fail(ctx, RTU_ERR_CANCELLED, "cancelled after %d of %d samples", i, frame->samples);  // StopRender(), main.cpp:70-72
         int nb = i_end - i < batch ? i_end - i : batch;
         while (!gi) {
             nb = i_end - i < batch ? i_end - i : batch;  // (i may have been reset below)
             int rc;
             if (ad && i == 0 && (rc = adaptive_start()) != RTU_OK) return rc;
-            rc = launch(ctx, frame, ctx->sample_buf.get(), stream, zero_counters && i == 0, i, nb, nullptr, RTU_LAUNCH_ALL, 0, ad != nullptr, ad ? ctx->ad_list[cur].get() : no_list, n_act);
+            rc = launch(ctx, frame, ctx->sample_buf.get(), stream, zero_counters && i == 0, i, nb, nullptr, RTU_LAUNCH_ALL, 0, ad != nullptr, ad ? sums.list[cur] : no_list, n_act);
             if (rc != RTU_OK) return rc;
             if (ad && (rc = adaptive_step(i, nb)) != RTU_OK) return rc;
             RTU_HIP(ctx, hipStreamSynchronize(stream));
@@ -1488,7 +1508,7 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
             // (adaptive: depth 0 walks the active tiles; the deeper depths run over every chain, a stopped one ends at once)
             for (int k = 0; k <= RTU_GI_BOUNCES; k++) {
                 rc = launch(ctx, frame, ctx->sample_buf.get(), stream, zero_counters && i == 0 && k == 0, i, nb, nullptr, RTU_LAUNCH_CHAIN, k, ad != nullptr,
-                            ad && k == 0 ? ctx->ad_list[cur].get() : no_list, ad ? n_act : 0u);
+                            ad && k == 0 ? sums.list[cur] : no_list, ad ? n_act : 0u);
                 if (rc != RTU_OK) return rc;
             }
             // the five shading steps are queued back to back; ONE host synchronisation per batch reads the (sticky) overflow
@@ -1511,18 +1531,53 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
         }
         if (ad) {
             cur ^= 1;
-            n_act = *ctx->ad_n_host.get();  // (read in the batch's synchronisation)
+            n_act = *sums.n_host;  // (read in the batch's synchronisation)
+            *reached = i + nb;
             if (n_act == 0) break;    // every pixel has stopped
             continue;
         }
         if (h_dump) {
             RTU_HIP(ctx, hipMemcpyAsync(h_dump + (size_t)(i - i_begin) * pixels * 4u, ctx->sample_buf.get(), (size_t)nb * pixels * sizeof(float4), hipMemcpyDeviceToHost, stream));
             RTU_HIP(ctx, hipStreamSynchronize(stream));
+            *reached = i + nb;
             continue;
         }
-        hipError_t e = (hipError_t)rtu_launch_accumulate(ctx->sample_buf.get(), (uint32_t)nb, ctx->acc.get(), ctx->acc_hits.get(), (uint32_t)pixels, i == 0, stream);
+        hipError_t e = (hipError_t)rtu_launch_accumulate(ctx->sample_buf.get(), (uint32_t)nb, sums.acc, sums.hits, (uint32_t)pixels, i == 0, stream);
         if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+        *reached = i + nb;
     }
+    *reached = i_end;
+    return RTU_OK;
+}
+
+// Recipe S / P in one call: the batch loop on the context's own accumulators, then the mean to d_out.
+int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, const SampledRun* run = nullptr) {
+    const size_t pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
+    if (pixels == 0) return RTU_OK;
+    const RtuAdaptiveDesc* ad = run ? run->ad : nullptr;
+    float* const h_dump = run ? run->h_dump : nullptr;
+    const int batch = sampled_batch(frame, ad, pixels);
+    RTU_HIP(ctx, ctx->acc.grow(pixels));
+    RTU_HIP(ctx, ctx->acc_hits.grow(pixels));
+    RTU_HIP(ctx, ctx->sample_buf.grow(pixels * (size_t)batch));
+    const uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
+    const uint32_t tiles = tiles_x * (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
+    SampleSums sums;
+    sums.acc = ctx->acc.get();
+    sums.hits = ctx->acc_hits.get();
+    if (ad) {
+        int rc = ensure_adaptive(ctx, pixels, tiles);
+        if (rc != RTU_OK) return rc;
+        sums.sq = ctx->ad_sq.get();
+        sums.counts = ctx->ad_counts.get();
+        sums.list[0] = ctx->ad_list[0].get();
+        sums.list[1] = ctx->ad_list[1].get();
+        sums.n_dev = ctx->ad_n.get();
+        sums.n_host = ctx->ad_n_host.get();
+    }
+    int reached = 0;
+    int rc = sample_batches(ctx, frame, stream, zero_counters, run, sums, h_dump ? run->first : 0, h_dump ? run->end : frame->samples, batch, &reached);
+    if (rc != RTU_OK) return rc;
     if (h_dump) return RTU_OK;
     hipError_t e = ad ? (hipError_t)rtu_launch_resolve_counts(ctx->acc.get(), ctx->acc_hits.get(), ctx->ad_counts.get(), d_out, run->d_counts, (uint32_t)pixels, stream)
                       : (hipError_t)rtu_launch_resolve(ctx->acc.get(), ctx->acc_hits.get(), d_out, (uint32_t)pixels, (uint32_t)frame->samples, stream);
@@ -1546,6 +1601,39 @@ int check_adaptive(RtuContext* ctx, const RtuFrameDesc* f, const RtuAdaptiveDesc
 }
 
 }  // namespace
+
+// A progressive session (rtu_progressive_*): a recipe S / P frame whose running sums live from call to call. It owns them; the
+// frame-record arrays and sample_buf it traces through are the context's scratch within one call.
+struct RtuProgressive {
+    RtuContext*     ctx = nullptr;    // nullptr once the context is destroyed
+    RtuFrameDesc    frame{};
+    bool            adaptive = false;
+    RtuAdaptiveDesc ad{};
+    uint64_t        scene_gen = 0;    // the context's scene generation at begin
+    int32_t         done = 0;         // samples [0, done) are in the sums
+    int             batch = 1;
+    size_t          pixels = 0;
+    uint32_t        tiles = 0;
+    DevBuf<float4>   acc, sq;
+    DevBuf<uint32_t> hits;
+    DevBuf<uint8_t>  counts;
+    DevBuf<uint4>    list[2];
+    DevBuf<uint32_t> n_dev;
+    PinnedBuf<uint32_t> n_host;
+    SampleSums      sums;
+};
+
+static void progressive_release(RtuProgressive* p) {
+    p->acc.reset();
+    p->sq.reset();
+    p->hits.reset();
+    p->counts.reset();
+    for (DevBuf<uint4>& l : p->list) l.reset();
+    p->n_dev.reset();
+    p->n_host.reset();
+    p->sums = SampleSums();
+    p->ctx = nullptr;
+}
 
 extern "C" {
 
@@ -1583,6 +1671,7 @@ const char* rtu_error_string(int err) {
         case RTU_ERR_CAPACITY: return "recursion frame capacity exceeded";
         case RTU_ERR_CANCELLED: return "cancelled";
         case RTU_ERR_SCENE_SHAPE: return "scene shape differs from the uploaded scene";
+        case RTU_ERR_STALE: return "the session's context got a new scene";
     }
     return "unknown error";
 }
@@ -1618,6 +1707,7 @@ void rtu_destroy_context(RtuContext* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     ll_builder_destroy(ctx->llb);
+    for (RtuProgressive* p : ctx->sessions) progressive_release(p);  // the handles stay valid for rtu_progressive_free
     // the buffers go with the context (DevBuf); its events and streams after them
     std::vector<hipEvent_t> events = {ctx->aux_ev0, ctx->aux_ev1, ctx->ev0, ctx->ev1};
     events.insert(events.end(), std::begin(ctx->cam_ev), std::end(ctx->cam_ev));
@@ -1867,6 +1957,7 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) RTU_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
     free_scene(ctx);
+    ctx->scene_gen++;
     ctx->slot_of.clear();
 
     // meshes
@@ -2031,6 +2122,7 @@ int rtu_update_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers rewritten below
     if (ctx->aux_stream) RTU_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
     if (!ctx->llb) ctx->llb = ll_builder_create();
+    ctx->scene_gen++;
     if ((rc = place_scene(ctx, &placed, true)) != RTU_OK) {
         free_scene(ctx);  // half placed: nothing to render from
         return rc;
@@ -2348,6 +2440,132 @@ int rtu_debug_sample_images(RtuContext* ctx, const RtuFrameDesc* frame, int firs
     run.first = first;
     run.end = first + n;
     return render_sampled(ctx, &f, nullptr, ctx->stream, true, &run);
+}
+
+RtuProgressive* rtu_progressive_begin(RtuContext* ctx, const RtuFrameDesc* frame, const RtuAdaptiveDesc* adaptive, int* err_out) {
+    auto refuse = [&](int rc) -> RtuProgressive* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (!frame) return refuse(fail(ctx, RTU_ERR_ARG, "frame is NULL"));
+    if (frame->samples < 1) return refuse(fail(ctx, RTU_ERR_ARG, "a progressive frame is a recipe S / P frame (samples >= 1)"));
+    if (frame->collect_stats != 0)
+        return refuse(fail(ctx, RTU_ERR_ARG, "a progressive frame has no counters (collect_stats == 0): the counting variant restarts from sample 0"));
+    int rc = adaptive ? check_adaptive(ctx, frame, adaptive) : check_frame(ctx, frame);
+    if (rc != RTU_OK) return refuse(rc);
+    if (!ctx->has_scene) return refuse(fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded"));
+    if (hipSetDevice(ctx->device) != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "hipSetDevice failed"));
+    std::unique_ptr<RtuProgressive> p(new RtuProgressive);
+    p->frame = *frame;
+    p->adaptive = adaptive != nullptr;
+    if (adaptive) p->ad = *adaptive;
+    p->scene_gen = ctx->scene_gen;
+    p->pixels = (size_t)rtu_shard_rows(frame) * (size_t)frame->width;
+    p->tiles = (uint32_t)((frame->width + 7) / 8) * (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
+    p->batch = p->pixels ? sampled_batch(frame, adaptive, p->pixels) : 1;
+    hipError_t e = p->acc.grow(p->pixels);
+    if (e == hipSuccess) e = p->hits.grow(p->pixels);
+    if (e == hipSuccess && adaptive) {
+        e = p->sq.grow(p->pixels);
+        if (e == hipSuccess) e = p->counts.grow(p->pixels);
+        for (DevBuf<uint4>& l : p->list)
+            if (e == hipSuccess) e = l.grow(p->tiles);
+        if (e == hipSuccess) e = p->n_dev.grow(2);
+        if (e == hipSuccess) e = p->n_host.grow(1);
+    }
+    if (e != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e)));
+    p->sums.acc = p->acc.get();
+    p->sums.hits = p->hits.get();
+    p->sums.sq = p->sq.get();
+    p->sums.counts = p->counts.get();
+    p->sums.list[0] = p->list[0].get();
+    p->sums.list[1] = p->list[1].get();
+    p->sums.n_dev = p->n_dev.get();
+    p->sums.n_host = p->n_host.get();
+    p->sums.n_act = p->tiles;
+    p->ctx = ctx;
+    ctx->sessions.push_back(p.get());
+    if (err_out) *err_out = RTU_OK;
+    return p.release();
+}
+
+int rtu_progressive_advance(RtuProgressive* p, int n_samples, void* hip_stream) {
+    if (!p || !p->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = p->ctx;
+    const int S = p->frame.samples;
+    if (n_samples < 1 || n_samples > S - p->done) return fail(ctx, RTU_ERR_ARG, "samples [%d, %d + %d) do not lie in [0, %d)", p->done, p->done, n_samples, S);
+    if (p->scene_gen != ctx->scene_gen) return fail(ctx, RTU_ERR_STALE, "the context got a new scene after this session began");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const int end = p->done + n_samples;
+    if (p->pixels == 0 || (p->adaptive && p->done > 0 && p->sums.n_act == 0)) {  // nothing to trace: no rows, or every pixel has stopped
+        p->done = end;
+        return RTU_OK;
+    }
+    RTU_HIP(ctx, ctx->sample_buf.grow(p->pixels * (size_t)p->batch));
+    SampledRun run;
+    run.ad = p->adaptive ? &p->ad : nullptr;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    int reached = p->done;
+    const int rc = sample_batches(ctx, &p->frame, stream, p->done == 0, &run, p->sums, p->done, end, p->batch, &reached);
+    // the sums hold every batch added so far, whatever ended the call; the last one may still be queued
+    const hipError_t e = hipStreamSynchronize(stream);
+    p->done = reached;
+    if (rc != RTU_OK) return rc;
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_progressive_status(const RtuProgressive* p, int32_t* samples_done, uint32_t* live_tiles) {
+    if (!p || !p->ctx) return RTU_ERR_ARG;
+    if (samples_done) *samples_done = p->done;
+    if (live_tiles) {
+        if (p->adaptive) *live_tiles = p->done == 0 ? p->tiles : p->sums.n_act;
+        else *live_tiles = p->done < p->frame.samples ? p->tiles : 0u;
+    }
+    return RTU_OK;
+}
+
+int rtu_progressive_snapshot_device(RtuProgressive* p, void* d_rgbz, void* d_counts, void* hip_stream) {
+    if (!p || !p->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = p->ctx;
+    if (p->done == 0) return fail(ctx, RTU_ERR_ARG, "no samples yet: advance the session first");
+    if (d_counts && p->frame.samples > 255) return fail(ctx, RTU_ERR_ARG, "counts are bytes: a session with more than 255 samples has none");
+    if (p->pixels == 0) return RTU_OK;
+    if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    hipError_t e = (hipError_t)rtu_launch_progressive_snapshot(p->acc.get(), p->hits.get(), p->adaptive ? p->counts.get() : nullptr, (uint32_t)p->done,
+                                                               (float4*)d_rgbz, (uint8_t*)d_counts, (uint32_t)p->pixels, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_progressive_snapshot(RtuProgressive* p, float* h_rgbz, uint8_t* h_counts) {
+    if (!p || !p->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = p->ctx;
+    if (p->done == 0) return fail(ctx, RTU_ERR_ARG, "no samples yet: advance the session first");
+    if (h_counts && p->frame.samples > 255) return fail(ctx, RTU_ERR_ARG, "counts are bytes: a session with more than 255 samples has none");
+    if (p->pixels == 0) return RTU_OK;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->fb.grow(p->pixels));
+    int rc = rtu_progressive_snapshot_device(p, ctx->fb.get(), nullptr, ctx->stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), p->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_counts && p->adaptive) RTU_HIP(ctx, hipMemcpyAsync(h_counts, p->counts.get(), p->pixels, hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_counts && !p->adaptive) memset(h_counts, p->done, p->pixels);  // what k_progressive_snapshot writes for a fixed session
+    return RTU_OK;
+}
+
+void rtu_progressive_free(RtuProgressive* p) {
+    if (!p) return;
+    if (RtuContext* ctx = p->ctx) {
+        (void)hipSetDevice(ctx->device);
+        ctx->sessions.erase(std::remove(ctx->sessions.begin(), ctx->sessions.end(), p), ctx->sessions.end());
+    }
+    delete p;
 }
 
 int rtu_frame_status(RtuContext* ctx) {
@@ -2685,6 +2903,7 @@ int rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, u
 }
 
 unsigned long long rtu_debug_device_allocations(void) { return g_devbuf_allocations.load(); }
+unsigned long long rtu_debug_device_bytes(void) { return g_devbuf_bytes.load(); }
 
 void* rtu_device_alloc(RtuContext* ctx, size_t bytes) {
     if (!ctx || bytes == 0) return nullptr;

@@ -9,21 +9,29 @@
 #include <cstddef>
 #include <utility>
 
-// device allocations made through DevBuf so far, in the whole process (rtu_debug_device_allocations)
+// device allocations made through DevBuf so far, in the whole process (rtu_debug_device_allocations), and the bytes of those still
+// held (rtu_debug_device_bytes)
 inline std::atomic<unsigned long long> g_devbuf_allocations{0};
+inline std::atomic<unsigned long long> g_devbuf_bytes{0};
 
 struct DeviceMem {
     static hipError_t alloc(void** p, size_t bytes) {
         const hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) g_devbuf_allocations++;
+        if (e == hipSuccess) {
+            g_devbuf_allocations++;
+            g_devbuf_bytes += bytes;
+        }
         return e;
     }
-    static void release(void* p) { (void)hipFree(p); }
+    static void release(void* p, size_t bytes) {
+        (void)hipFree(p);
+        g_devbuf_bytes -= bytes;
+    }
 };
 
 struct PinnedMem {
     static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
-    static void release(void* p) { (void)hipHostFree(p); }
+    static void release(void* p, size_t) { (void)hipHostFree(p); }
 };
 
 template <class T, class Mem = DeviceMem>
@@ -56,7 +64,7 @@ public:
         return hipSuccess;
     }
     void reset() {
-        if (p_) Mem::release(p_);
+        if (p_) Mem::release(p_, n_ * sizeof(T));
         p_ = nullptr;
         n_ = 0;
     }

@@ -408,6 +408,10 @@ struct AdaptiveStep {
 int rtu_launch_adaptive_init(uint4* list, uint32_t tiles, uint32_t tiles_x, int width, int height, int shard_rank, int shard_count, hipStream_t stream);
 int rtu_launch_adaptive_step(const AdaptiveStep& p, hipStream_t stream);
 int rtu_launch_resolve_counts(const float4* acc, const uint32_t* hits, const uint8_t* counts, float4* out, uint8_t* counts_out, uint32_t pixels, hipStream_t stream);
+// a progressive session's image from its running sums, left as they are (k_resolve's / k_resolve_counts's arithmetic): counts nullptr =
+// n samples in every pixel, else each pixel's own count; counts_out (may be nullptr) receives the count
+int rtu_launch_progressive_snapshot(const float4* acc, const uint32_t* hits, const uint8_t* counts, uint32_t n, float4* out, uint8_t* counts_out,
+                                    uint32_t pixels, hipStream_t stream);
 
 // gamma + Color24 + z of a float4 image: the content of the reference's RenderImage
 int rtu_launch_pack_image(const float4* rgbz, unsigned long long pixels, float* z_out, unsigned char* rgb_out, hipStream_t stream);

@@ -80,7 +80,8 @@ int fail(RtuMultiContext* m, int code, const std::string& what) {
     return code;
 }
 
-bool cancelled(const RtuProgress* p) { return p && p->cancel && *p->cancel; }
+bool raised(const volatile int* w) { return w && __atomic_load_n(w, __ATOMIC_RELAXED) != 0; }  // a word another thread may store
+bool cancelled(const RtuProgress* p) { return p && raised(p->cancel); }
 
 }  // namespace
 
@@ -182,7 +183,7 @@ int rtu_multi_render_frame(RtuMultiContext* m, const RtuFrameDesc* frame, float*
                 s.rc = rtu_render_frame_device(c, &s.frame, s.d_rgbz, rtu_context_stream(c));
                 // more Shade() frames than provisioned: the context has grown its buffers, render the shard again
                 for (int round = 0; s.rc == RTU_OK && (s.rc = rtu_frame_status(c)) == RTU_ERR_CAPACITY && round < 16; round++) {
-                    if (*flag) { s.rc = RTU_ERR_CANCELLED; break; }
+                    if (raised(flag)) { s.rc = RTU_ERR_CANCELLED; break; }
                     s.rc = rtu_render_frame_device(c, &s.frame, s.d_rgbz, rtu_context_stream(c));
                 }
                 if (s.rc != RTU_OK) s.error = rtu_last_error(c);
@@ -192,7 +193,7 @@ int rtu_multi_render_frame(RtuMultiContext* m, const RtuFrameDesc* frame, float*
     }
     for (int g = 0; g < G && rc == RTU_OK; g++)
         if (sh[(size_t)g].rc != RTU_OK) rc = fail(m, sh[(size_t)g].rc, std::string("GPU ") + std::to_string(m->devices[(size_t)g]) + ": " + sh[(size_t)g].error);
-    if (rc == RTU_OK && (*flag || cancelled(progress))) rc = fail(m, RTU_ERR_CANCELLED, "cancelled");
+    if (rc == RTU_OK && (raised(flag) || cancelled(progress))) rc = fail(m, RTU_ERR_CANCELLED, "cancelled");
 
     // ---- collect
     float* host = nullptr;
@@ -253,7 +254,7 @@ int rtu_multi_render_frame(RtuMultiContext* m, const RtuFrameDesc* frame, float*
     }
     // ---- hand the bands over, a context at a time as its transfer completes
     for (int g = 0; g < G && rc == RTU_OK; g++) {
-        if (cancelled(progress) || *flag) { rc = fail(m, RTU_ERR_CANCELLED, "cancelled"); break; }
+        if (cancelled(progress) || raised(flag)) { rc = fail(m, RTU_ERR_CANCELLED, "cancelled"); break; }
         if (!gathered) {
             rc = rtu_context_sync(m->ctx[(size_t)g]);
             if (rc != RTU_OK) { fail(m, rc, rtu_last_error(m->ctx[(size_t)g])); break; }

@@ -10,6 +10,8 @@
 namespace rtu {
 
 void set_error(const std::string& msg);
+// rtu_image_from_rgbz; count == false leaves the rendered-pixel counter alone (a progressive pass over rows shown before)
+void image_rows(RtuImage* img, const float* rgbz, int row0, int nrows, bool count);
 
 struct MeshData {
     std::vector<float>      v, vn, vt;

@@ -107,7 +107,12 @@ int rtu_image_is_done(const RtuImage* img) { return img && img->num_rendered.loa
 
 // RenderFunctions.cpp:152-160: gamma pow(double(c), 1/2.2) -> float, Color24, store;
 // z straight into the z-buffer (recipe W).
-void rtu_image_from_rgbz(RtuImage* img, const float* rgbz, int row0, int nrows) {
+void rtu_image_from_rgbz(RtuImage* img, const float* rgbz, int row0, int nrows) { rtu::image_rows(img, rgbz, row0, nrows, true); }
+
+}  // extern "C"
+
+// rtu_image_from_rgbz, and a progressive pass that replaces rows already counted (count == false)
+void rtu::image_rows(RtuImage* img, const float* rgbz, int row0, int nrows, bool count) {
     if (!img || !rgbz || row0 < 0 || nrows <= 0 || row0 + nrows > img->height) return;
     const int W = img->width;
     for (int r = 0; r < nrows; r++) {
@@ -122,8 +127,10 @@ void rtu_image_from_rgbz(RtuImage* img, const float* rgbz, int row0, int nrows) 
             zdst[x] = src[4 * x + 3];
         }
     }
-    img->num_rendered.fetch_add(nrows * W);
+    if (count) img->num_rendered.fetch_add(nrows * W);
 }
+
+extern "C" {
 
 // RenderImage::ComputeZBufferImage (scene.h:590-612)
 void rtu_image_compute_zimg(RtuImage* img) {
