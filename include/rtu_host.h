@@ -67,6 +67,17 @@ int       rtu_scene_node_rotate(RtuScene* scene, uint32_t node, float ax, float 
 int       rtu_scene_node_translate(RtuScene* scene, uint32_t node, float x, float y, float z);
 int       rtu_scene_set_light(RtuScene* scene, uint32_t index, const RtuLight* light);
 
+/* Deform a mesh of a loaded scene (then rtu_update_meshes, rtu_render.h). set_mesh_vertices: v is nv * 3 floats replacing the
+ * mesh's positions; vn is nvn * 3 floats or NULL (the normals stay). Connectivity (f, fn, ft, vt) stays. Then exactly what
+ * TriObj::Load does after reading the file (objects.h:57-58): ComputeBoundingBox and the reference's BVH build — the scene is,
+ * byte for byte as a blob, the scene a load of an .obj with those vertices gives; n_bvh_nodes and bvh_depth may change.
+ * recompute_normals: ComputeNormals (area-weighted, cyTriMesh.h:248-261) from the current positions, only for a mesh whose normals
+ * have that form (nvn == nv and fn equal to f, what the loader makes for a file without vn lines); otherwise -1 and nothing
+ * changes. Pointers from an earlier rtu_scene_desc stay valid (the arrays keep their sizes; bvh may move: read the desc again).
+ * 0, or -1 for a bad index / NULL (rtu_host_last_error). */
+int       rtu_scene_set_mesh_vertices(RtuScene* scene, uint32_t mesh, const float* v, const float* vn);
+int       rtu_scene_recompute_normals(RtuScene* scene, uint32_t mesh);
+
 const char* rtu_host_last_error(void);
 
 /* ---- output side: RenderImage mirror ------------------------------------ */

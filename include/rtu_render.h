@@ -141,13 +141,35 @@ int  rtu_validate_scene(const RtuSceneDesc* scene, char* err_buf, size_t err_len
  * SHAPE must be the uploaded scene's: the same n_nodes and, per node, parent, obj_type, mesh_id, depth and subtree_end; the same
  * n_meshes and, per mesh, nv, nf, nvn, nvt and n_bvh_nodes; the same n_textures and, per texture, type, width and height; the
  * same n_materials; material_maps present in both or in neither. Otherwise RTU_ERR_SCENE_SHAPE. The mesh and texture arrays
- * of `scene` are not read beyond those headers: the copies uploaded before are used (vertex edits and new images need
+ * of `scene` are not read beyond those headers: the copies uploaded before are used (vertex edits: rtu_update_meshes; new images need
  * rtu_upload_scene). The acceleration structures of the meshes and the textures stay; node records, node-level bounds, cover
  * meshes and occluder lists of shadow rays (built on the GPU, equal to what rtu_upload_scene builds for the same scene),
  * materials, lights and launch hints are rebuilt. RTU_ERR_NO_SCENE before any upload; a scene rtu_upload_scene would refuse
  * gets the same code. A refused update leaves the context as it was. Synchronous: waits for every launch in flight on the
  * context's streams first, so a batch enqueued before the call renders the old scene. */
 int  rtu_update_scene(RtuContext* ctx, const RtuSceneDesc* scene);
+
+/* Deform uploaded meshes in place. It is rtu_update_scene(ctx, scene) and, before the placement is rebuilt, for every mesh i of
+ * mesh_ids[n_meshes] the arrays v, vn, bvh, elements and the header fields n_bvh_nodes, bvh_depth, bound_min, bound_max of
+ * scene->meshes[i] are read and replace the uploaded ones (a host scene edited with rtu_scene_set_mesh_vertices, rtu_host.h, has
+ * them ready). nv, nf, nvn, nvt and n_elements must be the uploaded mesh's (RTU_ERR_SCENE_SHAPE); n_bvh_nodes of a LISTED mesh may
+ * differ, of an unlisted one not. f, fn, ft, vt are not read: the uploaded connectivity is used. n_meshes == 0 is rtu_update_scene.
+ * Everything is validated before anything is written, and a refused call leaves the context as it was: ids in range and not
+ * repeated (RTU_ERR_ARG); for each listed mesh what rtu_upload_scene checks of bvh / elements (child indices, leaf ranges, element
+ * ids, bvh_depth not understated: RTU_ERR_ARG) and bvh_depth <= RTU_MAX_BVH_STACK (RTU_ERR_UNSUPPORTED).
+ * Replaced per listed mesh: v, vn (copied); the `ref` tree (renumbered as at upload), its element order and triangle records,
+ * any_empty_box, the mesh box and cull scale, n_bvh_nodes; the triangle records of the fast tree; the boxes of its collapsed
+ * forms bvh4 / bvh8 — REFITTED on the GPU: each child box is the exact min / max (comparisons only) of the vertex coordinates of
+ * the triangles in that child's range of element slots, the float VALUES a build of that topology would store (-0 and +0 are one
+ * value; a NaN coordinate drops out as it does in the builder); triangle records are the upload's arithmetic bit for bit. KEPT: the
+ * fast tree's topology — its element order, every ref word of bvh4 / bvh8, the LDS staging, rtu_mesh_info, the stack need of the
+ * 4-wide walk. The topology stays that of the last UPLOAD however many updates follow: images never depend on it (exact ties,
+ * stack overflows and the counting variant go through the `ref` tree), frame times may — after a large deformation a fresh
+ * rtu_upload_scene can render faster. The shape the context remembers takes the new n_bvh_nodes and bounds (a later
+ * rtu_update_scene / rtu_scene_shape_diff compares against the mesh as it is now); progressive sessions turn RTU_ERR_STALE; launch
+ * hints are cleared. The `ref` tree's device buffer only grows: a sequence of updates that needs no growth allocates nothing.
+ * Synchronous; waits for both of the context's streams first. RTU_ERR_NO_SCENE before any upload. */
+int  rtu_update_meshes(RtuContext* ctx, const RtuSceneDesc* scene, const uint32_t* mesh_ids, int n_meshes);
 
 /* The shape check of rtu_update_scene on its own: RTU_OK when `b` has the shape of `a`, else RTU_ERR_SCENE_SHAPE with the first
  * difference in err_buf (may be NULL); RTU_ERR_ARG for a missing array. Pure host code. */
@@ -320,6 +342,7 @@ RtuContext* rtu_multi_context(RtuMultiContext* m, int i);            /* the i-th
 const char* rtu_multi_last_error(const RtuMultiContext* m);
 int         rtu_multi_upload_scene(RtuMultiContext* m, const RtuSceneDesc* scene);
 int         rtu_multi_update_scene(RtuMultiContext* m, const RtuSceneDesc* scene);  /* rtu_update_scene on every context */
+int         rtu_multi_update_meshes(RtuMultiContext* m, const RtuSceneDesc* scene, const uint32_t* mesh_ids, int n_meshes);  /* rtu_update_meshes on every context */
 int         rtu_multi_render_frame(RtuMultiContext* m, const RtuFrameDesc* frame, float* h_rgbz, const RtuProgress* progress);
 /* How the shards of the last rtu_multi_render_frame reached the host: 1 one context; 2 several contexts, asynchronous copies into
  * one pinned buffer, all in flight together; 3 RCCL (grouped ncclSend / ncclRecv to the first GPU, then one copy). */
@@ -409,6 +432,34 @@ int  rtu_debug_context_light_list(RtuContext* ctx, uint32_t index, RtuLightListD
  * between phases); ms_out5 (may be NULL) gets the milliseconds spent since the previous call: {cover meshes and their extents,
  * corner pass, count passes, fill and offsets, radix sort}. */
 int  rtu_debug_update_timing(RtuContext* ctx, int on, float* ms_out5);
+/* Diagnostic: on != 0 times the phases of later rtu_update_meshes calls with HIP events on the context's stream. ms_out4 (may be
+ * NULL) receives the milliseconds summed since the previous call: copies to HBM, triangle records, refit of bvh4 / bvh8, placement
+ * (the rtu_update_scene part); they are reset. */
+int  rtu_debug_mesh_update_timing(RtuContext* ctx, int on, float* ms_out4);
+
+/* Test hooks of rtu_update_meshes: one array of what a mesh is on the device. */
+#define RTU_MESH_BVH4          0  /* float4 [8 nodes4]: the fast tree collapsed to 4 children per node */
+#define RTU_MESH_BVH8          1  /* float4 [16 nodes8]: ... to 8 */
+#define RTU_MESH_FAST_TRI      2  /* float4 [4 nf]: triangle records in the fast tree's element order */
+#define RTU_MESH_REF_TRI       3  /* float4 [4 nf]: ... in the `ref` tree's */
+#define RTU_MESH_REF_BVH       4  /* RtuBvhNode [n_bvh_nodes]: the `ref` tree, renumbered breadth-first */
+#define RTU_MESH_REF_ELEMENTS  5  /* uint32 [nf] */
+#define RTU_MESH_V             6  /* float [3 nv] */
+#define RTU_MESH_VN            7  /* float [3 nvn] */
+#define RTU_MESH_HEADER        8  /* RtuMeshHeaderDump */
+#define RTU_MESH_FAST_ELEMENTS 9  /* uint32 [nf]: element slot of the fast tree -> face */
+typedef struct RtuMeshHeaderDump {
+    float    bmin[3], bmax[3], scale;
+    uint32_t n_bvh_nodes, any_empty_box;
+} RtuMeshHeaderDump;
+/* What the context holds for mesh `mesh` now, copied back from the GPU (synchronous). *bytes_out (may be NULL) is the size of the
+ * array; RTU_ERR_ARG when capacity_bytes is smaller (nothing is copied: ask with capacity 0 first). */
+int  rtu_debug_context_mesh(RtuContext* ctx, uint32_t mesh, int which, void* out, size_t capacity_bytes, size_t* bytes_out);
+/* The same array as the HOST makes it — pure host code, no GPU and no context: the topology of the fast tree from the builders of
+ * rtu_upload_scene on the mesh `uploaded`; boxes, records, vertices and `ref` tree from `now` (same nv / nf / nvn; its f is not read),
+ * the boxes by the host restatement of the device refit. now == NULL: `uploaded` as rtu_upload_scene builds it, no refit — what
+ * a refit with the uploaded vertices must reproduce (boxes as float values). */
+int  rtu_debug_host_mesh(const RtuMesh* uploaded, const RtuMesh* now, int which, void* out, size_t capacity_bytes, size_t* bytes_out);
 
 /* Diagnostic: Shade() frames per recursion level (6 values) and rays deferred to stage 2 per phase
  * (7 values: primary, then levels 0..5) of the most recent frame (fast variant). Synchronises. */

@@ -151,7 +151,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_multi_size", "rtu_multi_context", "rtu_multi_last_error", "rtu_multi_upload_scene", "rtu_multi_render_frame", "rtu_multi_gather_kind",
                "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords",
                "rtu_debug_device_allocations", "rtu_progressive_begin", "rtu_progressive_advance", "rtu_progressive_status",
-               "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes"]
+               "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes",
+               "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -269,6 +270,45 @@ _sig(hip, "rtu_multi_update_scene", _I, _P, _P)
 _sig(hip, "rtu_scene_shape_diff", _I, _P, _P, ctypes.c_char_p, ctypes.c_size_t)
 _sig(hip, "rtu_debug_context_light_list", _I, _P, ctypes.c_uint32, ctypes.POINTER(RtuLightListDump))
 _sig(hip, "rtu_debug_update_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
+_sig(hip, "rtu_update_meshes", _I, _P, _P, ctypes.POINTER(ctypes.c_uint32), _I)
+_sig(hip, "rtu_multi_update_meshes", _I, _P, _P, ctypes.POINTER(ctypes.c_uint32), _I)
+_sig(hip, "rtu_debug_mesh_update_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
+_sig(hip, "rtu_debug_context_mesh", _I, _P, ctypes.c_uint32, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
+_sig(hip, "rtu_debug_host_mesh", _I, _P, _P, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
+
+# the arrays of a mesh dump (include/rtu_render.h RTU_MESH_*): name -> (which, numpy dtype, trailing shape)
+MESH_ARRAYS = {"bvh4": (0, "float32", (8, 4)), "bvh8": (1, "float32", (16, 4)), "fast_tri": (2, "float32", (4, 4)), "ref_tri": (3, "float32", (4, 4)),
+               "ref_bvh": (4, "uint32", (8,)), "ref_elements": (5, "uint32", ()), "v": (6, "float32", (3,)), "vn": (7, "float32", (3,)),
+               "header": (8, "uint32", ()), "fast_elements": (9, "uint32", ())}
+
+
+def _mesh_dump(call, what):
+    """Every array of MESH_ARRAYS through `call(which, out, capacity, bytes_out)` as a dict of numpy arrays. Nodes of bvh4 / bvh8 come as
+    [nodes, 8 or 16, 4] float32 (view as uint32 for the ref words), ref_bvh as [nodes, 8] uint32 words {bmin, index, bmax, count}; the
+    header is unpacked into bmin, bmax, scale (float32) and n_bvh_nodes, any_empty_box."""
+    import numpy as np
+    out = {}
+    for name, (which, dtype, tail) in MESH_ARRAYS.items():
+        n = ctypes.c_size_t(0)
+        call(which, None, 0, ctypes.byref(n))  # the size (the call itself answers RTU_ERR_ARG: nothing fits in no buffer)
+        buf = np.empty(n.value // 4, dtype)
+        rc = call(which, buf.ctypes.data, buf.nbytes, ctypes.byref(n))
+        if rc != RTU_OK:
+            raise RtuError(rc, "%s: %s" % (what, name))
+        out[name] = buf.reshape((-1,) + tail) if tail else buf
+    h = out.pop("header")
+    out["bmin"], out["bmax"], out["scale"] = h[0:3].view(np.float32), h[3:6].view(np.float32), h[6:7].view(np.float32)[0]
+    out["n_bvh_nodes"], out["any_empty_box"] = int(h[7]), int(h[8])
+    return out
+
+
+def host_mesh(uploaded, mesh, now=None):
+    """Pure host code (rtu_debug_host_mesh): what the device holds for mesh `mesh` after upload(uploaded) and update_meshes(now, [mesh]) —
+    the fast tree's topology from `uploaded`, boxes / records / `ref` tree from `now`; now None: as upload(uploaded) builds it."""
+    size = ctypes.sizeof(RtuMesh)
+    up = uploaded.desc.meshes + mesh * size
+    nw = now.desc.meshes + mesh * size if now is not None else None
+    return _mesh_dump(lambda which, out, cap, n: hip.rtu_debug_host_mesh(up, nw, which, out, cap, n), "rtu_debug_host_mesh")
 
 
 def scene_shape_diff(a, b):
@@ -332,7 +372,8 @@ HOST_SYMBOLS = ["rtu_scene_load_xml", "rtu_scene_clone", "rtu_scene_load_blob", 
                 "rtu_begin_render", "rtu_begin_render_sampled", "rtu_begin_render_paths", "rtu_stop_render", "rtu_render_wait", "rtu_render_gather_kind", "rtu_render_job_free",
                 "rtu_image_sample_count", "rtu_image_fill_sample_count", "rtu_image_compute_sample_count_img", "rtu_image_sample_count_image",
                 "rtu_image_save_sample_count_png", "rtu_begin_render_adaptive", "rtu_scene_node_scale", "rtu_scene_node_rotate",
-                "rtu_scene_node_translate", "rtu_scene_set_light", "rtu_begin_render_progressive"]
+                "rtu_scene_node_translate", "rtu_scene_set_light", "rtu_begin_render_progressive", "rtu_scene_set_mesh_vertices",
+                "rtu_scene_recompute_normals"]
 _sig(host, "rtu_scene_load_xml", _P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
 _sig(host, "rtu_scene_clone", _P, _P)
 _sig(host, "rtu_scene_load_blob", _P, _P, ctypes.c_size_t)
@@ -348,6 +389,8 @@ _sig(host, "rtu_scene_node_scale", _I, _P, ctypes.c_uint32, _F, _F, _F)
 _sig(host, "rtu_scene_node_rotate", _I, _P, ctypes.c_uint32, _F, _F, _F, _F)
 _sig(host, "rtu_scene_node_translate", _I, _P, ctypes.c_uint32, _F, _F, _F)
 _sig(host, "rtu_scene_set_light", _I, _P, ctypes.c_uint32, _P)
+_sig(host, "rtu_scene_set_mesh_vertices", _I, _P, ctypes.c_uint32, _P, _P)
+_sig(host, "rtu_scene_recompute_normals", _I, _P, ctypes.c_uint32)
 _sig(host, "rtu_host_last_error", ctypes.c_char_p)
 _sig(host, "rtu_image_create", _P, _I, _I)
 _sig(host, "rtu_image_free", None, _P)
@@ -486,6 +529,38 @@ class Scene:
         """Replace light `index` with an RtuLight-layout ctypes structure (a direct light's direction is normalised)."""
         self._ok(host.rtu_scene_set_light(self._h, index, ctypes.byref(light)), "set_light: bad index")
 
+    def mesh(self, mesh):
+        """The RtuMesh header of mesh `mesh` (a view: read it again after an edit)."""
+        if not 0 <= mesh < self.desc.n_meshes:
+            raise RtuError(RTU_ERR_ARG, "no mesh %d" % mesh)
+        return ctypes.cast(self.desc.meshes, ctypes.POINTER(RtuMesh))[mesh]
+
+    def mesh_vertices(self, mesh):
+        """A copy of the positions of mesh `mesh`: float32 [nv, 3]."""
+        import numpy as np
+        m = self.mesh(mesh)
+        return np.ctypeslib.as_array(ctypes.cast(m.v, ctypes.POINTER(ctypes.c_float)), (m.nv, 3)).copy()
+
+    def set_mesh_vertices(self, mesh, v, vn=None):
+        """New positions v [nv, 3] (and normals vn [nvn, 3], or None: they stay) on the loaded connectivity; bounding box and the
+        reference's BVH are rebuilt as the loader builds them (then Context.update_meshes)."""
+        import numpy as np
+        m = self.mesh(mesh)
+        v = np.ascontiguousarray(v, np.float32)
+        if v.size != m.nv * 3:
+            raise RtuError(RTU_ERR_ARG, "set_mesh_vertices: %d floats for %d vertices" % (v.size, m.nv))
+        if vn is not None:
+            vn = np.ascontiguousarray(vn, np.float32)
+            if vn.size != m.nvn * 3:
+                raise RtuError(RTU_ERR_ARG, "set_mesh_vertices: %d floats for %d normals" % (vn.size, m.nvn))
+        if host.rtu_scene_set_mesh_vertices(self._h, mesh, v.ctypes.data, vn.ctypes.data if vn is not None else None) != 0:
+            raise RtuError(RTU_ERR_ARG, host.rtu_host_last_error().decode())
+
+    def recompute_normals(self, mesh):
+        """ComputeNormals from the current positions; only for a mesh whose normals have that form (one per vertex, fn == f)."""
+        if host.rtu_scene_recompute_normals(self._h, mesh) != 0:
+            raise RtuError(RTU_ERR_ARG, host.rtu_host_last_error().decode())
+
     def close(self):
         if self._h:
             host.rtu_scene_free(self._h)
@@ -533,6 +608,11 @@ class MultiContext:
     def update(self, scene):
         """rtu_update_scene on every GPU's context: same shape, new placement / lights / materials / camera."""
         self._check(hip.rtu_multi_update_scene(self._h, scene.desc_ptr))
+
+    def update_meshes(self, scene, meshes):
+        """rtu_update_meshes on every GPU's context."""
+        ids = (ctypes.c_uint32 * len(meshes))(*meshes)
+        self._check(hip.rtu_multi_update_meshes(self._h, scene.desc_ptr, ids, len(meshes)))
 
     def context_handle(self, i):
         return hip.rtu_multi_context(self._h, i)
@@ -635,6 +715,22 @@ class Context:
     def update(self, scene):
         """rtu_update_scene: the uploaded scene moved, relit or re-coloured (same shape); waits for launches in flight."""
         self._check(hip.rtu_update_scene(self._h, scene.desc_ptr))
+
+    def update_meshes(self, scene, meshes):
+        """rtu_update_meshes: update(scene), and the listed meshes take the vertices, normals and reference BVH of `scene` (same
+        connectivity); the fast trees are refitted on the GPU."""
+        ids = (ctypes.c_uint32 * len(meshes))(*meshes)
+        self._check(hip.rtu_update_meshes(self._h, scene.desc_ptr, ids, len(meshes)))
+
+    def mesh_arrays(self, mesh):
+        """What the context holds for mesh `mesh` now, copied back from the GPU: the dict of host_mesh()."""
+        return _mesh_dump(lambda which, out, cap, n: hip.rtu_debug_context_mesh(self._h, mesh, which, out, cap, n), "rtu_debug_context_mesh")
+
+    def mesh_update_timing(self, on=True):
+        """Time the phases of later update_meshes calls; returns the ms spent per phase since the previous call."""
+        o = (ctypes.c_float * 4)()
+        self._check(hip.rtu_debug_mesh_update_timing(self._h, int(on), o))
+        return dict(zip(("copies", "records", "refit", "placement"), list(o)))
 
     def light_list(self, index):
         """The occluder list the context holds now (index as in light_lists()), copied back: the dict of light_list()."""

@@ -6,6 +6,7 @@
 #include "rtu_devbuf.h"
 #include "rtu_device.h"
 #include "rtu_lightlist.h"
+#include "rtu_meshrec.h"
 
 #include <algorithm>
 #include <array>
@@ -47,6 +48,13 @@ struct RtuContext {
     std::vector<const uint32_t*> slot_of;    // per mesh, device: face -> slot of the fast tree
     std::vector<DevLightMask> lmask_host;    // host copy of DevScene::lmask (rtu_debug_context_light_list)
     LlBuilder* llb = nullptr;                // the device builder of the occluder lists (rtu_scene_update.hip)
+    // what rtu_update_meshes needs of a mesh beyond its device record: the node ranges of the levels of its collapsed fast trees
+    // (root first, [levels + 1]) and which of scene_allocs holds its ref.bvh (the one per-mesh buffer whose size an update can change)
+    struct MeshRefit { std::vector<uint32_t> lvl4, lvl8; size_t ref_bvh_alloc = 0; };
+    std::vector<MeshRefit> refit;
+    bool  mu_timing = false;                 // rtu_debug_mesh_update_timing: HIP events around the phases of rtu_update_meshes
+    float mu_ms[4] = {};                     // copies, records, refit, placement: summed since the last read
+    hipEvent_t mu_ev[5] = {};
     DevScene dscene{};
     uint32_t bvh_stack_needed = 1;
 
@@ -477,28 +485,62 @@ void build_wide4(const SahTree& t, std::vector<float4>& out, uint32_t& stack_nee
 // the same float ops.
 void build_tri_records(const RtuMesh& m, const uint32_t* elements, uint32_t n, std::vector<float4>& tri) {
     tri.resize((size_t)n * 4);
-    for (uint32_t e = 0; e < n; e++) {
-        const uint32_t* fv = m.f + 3 * elements[e];
-        f3 A = ld3(m.v + 3 * fv[0]), B = ld3(m.v + 3 * fv[1]), C = ld3(m.v + 3 * fv[2]);
-        f3 N = norm3(cross3(B - A, C - A));                                        // :263
-        float anx = fabsf(N.x), any = fabsf(N.y), anz = fabsf(N.z);
-        float maxNormalAxis = smax(smax(anx, any), anz);                           // :274
-        uint32_t axis = (maxNormalAxis == anx) ? 0u : (maxNormalAxis == any) ? 1u : 2u;  // :278-296
-        float ax = axis == 0 ? A.y : A.x, ay = axis == 2 ? A.y : A.z;
-        float bx = axis == 0 ? B.y : B.x, by = axis == 2 ? B.y : B.z;
-        float cx = axis == 0 ? C.y : C.x, cy = axis == 2 ? C.y : C.z;
-        float e1x = cx - ax, e1y = cy - ay, e2x = bx - ax, e2y = by - ay;
-        float TriABCArea = (float)((double)((-e1y) * e2x + e1x * e2y) / 2.0);      // :298, Point2::Cross
-        double rcp = 1.0 / (double)TriABCArea;
-        uint64_t bits;
-        memcpy(&bits, &rcp, 8);
-        uint32_t lo = (uint32_t)bits, hi = (uint32_t)(bits >> 32);
-        float flo, fhi, faxis;
-        memcpy(&flo, &lo, 4); memcpy(&fhi, &hi, 4); memcpy(&faxis, &axis, 4);
-        tri[4 * e + 0] = make_float4(A.x, A.y, A.z, N.x);
-        tri[4 * e + 1] = make_float4(N.y, N.z, ax, ay);
-        tri[4 * e + 2] = make_float4(e1x, e1y, e2x, e2y);
-        tri[4 * e + 3] = make_float4(flo, fhi, faxis, 0.0f);
+    for (uint32_t e = 0; e < n; e++) mu_slot_record(m.f, m.v, elements, e, &tri[4 * (size_t)e]);  // (rtu_meshrec.h: shared with the device)
+}
+
+// The node ranges of the levels of a collapsed tree (build_wide4 / build_wide8 number breadth-first: a level is a range of nodes),
+// root first: level L = nodes [out[L], out[L + 1]). A function of the ref words only.
+template <int W>
+void wide_levels(const std::vector<float4>& tree, std::vector<uint32_t>& out) {
+    const float* t = reinterpret_cast<const float*>(tree.data());
+    const uint32_t n_nodes = (uint32_t)(tree.size() * 4 / MuWide<W>::kNodeFloats);
+    std::vector<uint32_t> level(n_nodes, 0u);
+    out.clear();
+    for (uint32_t i = 0; i < n_nodes; i++) {  // parents come before their children
+        if (i == 0 || level[i] != level[i - 1]) out.push_back(i);
+        for (uint32_t c = 0; c < (uint32_t)W; c++) {
+            const uint32_t ref = mu_ref<W>(t, i, c);
+            if (mu_is_inner(ref) && ref < n_nodes) level[ref] = level[i] + 1;
+        }
+    }
+    out.push_back(n_nodes);
+}
+
+// the boxes of a collapsed tree from the vertices of `m` through the fast tree's element order: what the device refit writes
+template <int W>
+void refit_host(std::vector<float4>& tree, const RtuMesh& m, const std::vector<uint32_t>& elements) {
+    float* t = reinterpret_cast<float*>(tree.data());
+    const uint32_t n_nodes = (uint32_t)(tree.size() * 4 / MuWide<W>::kNodeFloats);
+    for (uint32_t i = n_nodes; i-- > 0;)  // children have larger numbers than their parents
+        for (uint32_t c = 0; c < (uint32_t)W; c++) {
+            mu_leaf_slot<W>(t, i, c, m.f, m.v, elements.data(), (uint32_t)elements.size());
+            mu_inner_slot<W>(t, n_nodes, i, c);
+        }
+}
+
+// the reference's tree renumbered breadth-first (sibling pairs stay adjacent, the root stays node 1): same tree, same traversal
+// order. any_empty: some box has min > max (cannot come from triangles).
+void renumber_bfs(const RtuMesh& m, std::vector<RtuBvhNode>& bfs, uint32_t& any_empty) {
+    any_empty = 0;
+    for (uint32_t i = 1; i < m.n_bvh_nodes; i++) {
+        const RtuBvhNode& bn = m.bvh[i];
+        if (bn.bmin[0] > bn.bmax[0] || bn.bmin[1] > bn.bmax[1] || bn.bmin[2] > bn.bmax[2]) any_empty = 1;
+    }
+    bfs.resize(m.n_bvh_nodes);
+    memset(bfs.data(), 0, bfs.size() * sizeof(RtuBvhNode));
+    std::vector<std::pair<uint32_t, uint32_t>> queue;  // (old id, new id)
+    queue.push_back({1u, 1u});
+    uint32_t next_free = 2;
+    for (size_t qi = 0; qi < queue.size(); qi++) {
+        auto [oldId, newId] = queue[qi];
+        RtuBvhNode nn = m.bvh[oldId];
+        if (nn.count == 0) {
+            queue.push_back({nn.index, next_free});
+            queue.push_back({nn.index + 1, next_free + 1});
+            nn.index = next_free;
+            next_free += 2;
+        }
+        bfs[newId] = nn;
     }
 }
 
@@ -849,6 +891,32 @@ int build_light_lists_device(RtuContext* ctx, const RtuSceneDesc* s, const std::
     return place_upload(ctx, P_LMASK, masks.data(), masks.size(), &ds.lmask);
 }
 
+// The checks of a mesh's `ref` tree and element list (validate, and rtu_update_meshes for the trees it takes): element ids, and every
+// node reachable from the root well formed; children have larger ids than their parent (cyBVH.h:242-251), which also rules out
+// cycles.
+int validate_tree(RtuContext* ctx, const RtuMesh& m, uint32_t mi) {
+    for (uint32_t i = 0; i < m.n_elements; i++)
+        if (m.elements[i] >= m.nf) return fail(ctx, RTU_ERR_ARG, "mesh %u: element out of range", mi);
+    std::vector<std::pair<uint32_t, uint32_t>> st;  // node, level
+    st.push_back({1u, 1u});
+    uint32_t depth = 0;
+    while (!st.empty()) {
+        auto [id, lvl] = st.back();
+        st.pop_back();
+        if (lvl > depth) depth = lvl;
+        const RtuBvhNode& n = m.bvh[id];
+        if (n.count == 0) {
+            if (n.index <= id || n.index + 1 >= m.n_bvh_nodes) return fail(ctx, RTU_ERR_ARG, "mesh %u: bad child index at node %u", mi, id);
+            st.push_back({n.index, lvl + 1});
+            st.push_back({n.index + 1, lvl + 1});
+        } else {
+            if (n.count > 8 || n.index + n.count > m.n_elements) return fail(ctx, RTU_ERR_ARG, "mesh %u: bad leaf at node %u", mi, id);
+        }
+    }
+    if (depth > m.bvh_depth) return fail(ctx, RTU_ERR_ARG, "mesh %u: bvh_depth %u understates the tree (%u)", mi, m.bvh_depth, depth);
+    return RTU_OK;
+}
+
 // Reject anything the kernel's indexing does not expect, so that a malformed
 // scene is an error code and never an out-of-bounds access on the GPU. placement: the mesh and texture arrays are the uploaded
 // ones (rtu_update_scene): only what an update may change is checked.
@@ -913,27 +981,7 @@ int validate(RtuContext* ctx, const RtuSceneDesc* s, bool placement = false) {
         if (m.ft)
             for (uint32_t i = 0; i < m.nf * 3; i++)
                 if (m.ft[i] >= m.nvt) return fail(ctx, RTU_ERR_ARG, "mesh %u: texture-vertex index out of range", mi);
-        for (uint32_t i = 0; i < m.n_elements; i++)
-            if (m.elements[i] >= m.nf) return fail(ctx, RTU_ERR_ARG, "mesh %u: element out of range", mi);
-        // every node reachable from the root must be well formed; children have larger
-        // ids than their parent (cyBVH.h:242-251), which also rules out cycles
-        std::vector<std::pair<uint32_t, uint32_t>> st;  // node, level
-        st.push_back({1u, 1u});
-        uint32_t depth = 0;
-        while (!st.empty()) {
-            auto [id, lvl] = st.back();
-            st.pop_back();
-            if (lvl > depth) depth = lvl;
-            const RtuBvhNode& n = m.bvh[id];
-            if (n.count == 0) {
-                if (n.index <= id || n.index + 1 >= m.n_bvh_nodes) return fail(ctx, RTU_ERR_ARG, "mesh %u: bad child index at node %u", mi, id);
-                st.push_back({n.index, lvl + 1});
-                st.push_back({n.index + 1, lvl + 1});
-            } else {
-                if (n.count > 8 || n.index + n.count > m.n_elements) return fail(ctx, RTU_ERR_ARG, "mesh %u: bad leaf at node %u", mi, id);
-            }
-        }
-        if (depth > m.bvh_depth) return fail(ctx, RTU_ERR_ARG, "mesh %u: bvh_depth %u understates the tree (%u)", mi, m.bvh_depth, depth);
+        if (int rc = validate_tree(ctx, m, mi); rc != RTU_OK) return rc;
     }
     return RTU_OK;
 }
@@ -1712,6 +1760,7 @@ void rtu_destroy_context(RtuContext* ctx) {
     std::vector<hipEvent_t> events = {ctx->aux_ev0, ctx->aux_ev1, ctx->ev0, ctx->ev1};
     events.insert(events.end(), std::begin(ctx->cam_ev), std::end(ctx->cam_ev));
     events.insert(events.end(), std::begin(ctx->probe_ev), std::end(ctx->probe_ev));
+    events.insert(events.end(), std::begin(ctx->mu_ev), std::end(ctx->mu_ev));
     const hipStream_t streams[] = {ctx->aux_stream, ctx->stream};
     delete ctx;
     for (hipEvent_t e : events)
@@ -1945,6 +1994,68 @@ RtuSceneDesc shape_desc(const RtuContext* ctx) {
     return d;
 }
 
+
+// The writing half of rtu_update_meshes, after every check has passed: for each listed mesh the new vertices, normals and `ref` tree
+// go to HBM, and the kernels of rtu_mesh_update.hip rewrite what depends on the vertices — triangle records of both trees, the boxes
+// of bvh4 / bvh8. Everything is enqueued on the context's stream and waited for at the end. new_shape: the headers the context
+// remembers from now on.
+int write_meshes(RtuContext* ctx, const RtuSceneDesc* s, const uint32_t* mesh_ids, int n_meshes, const std::vector<RtuMesh>& new_shape) {
+    hipStream_t st = ctx->stream;
+    const bool timing = ctx->mu_timing;
+    if (timing && !ctx->mu_ev[0])
+        for (hipEvent_t& e : ctx->mu_ev) RTU_HIP(ctx, hipEventCreate(&e));
+    std::vector<std::vector<RtuBvhNode>> trees((size_t)n_meshes);  // host sources of asynchronous copies: alive until the wait below
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mu_ev[0], st));
+    for (int i = 0; i < n_meshes; i++) {
+        const uint32_t id = mesh_ids[i];
+        const RtuMesh& m = s->meshes[id];
+        DevMesh& d = ctx->dmeshes[id];
+        renumber_bfs(m, trees[(size_t)i], d.any_empty_box);
+        DevBuf<char>& tree_buf = ctx->scene_allocs[ctx->refit[id].ref_bvh_alloc];  // grow-only: a tree that fits makes no allocation
+        RTU_HIP(ctx, tree_buf.grow(sizeof(RtuBvhNode) * (size_t)m.n_bvh_nodes));
+        d.ref.bvh = reinterpret_cast<const float4*>(tree_buf.get());
+        RTU_HIP(ctx, hipMemcpyAsync(tree_buf.get(), trees[(size_t)i].data(), sizeof(RtuBvhNode) * (size_t)m.n_bvh_nodes, hipMemcpyHostToDevice, st));
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(d.ref.elements), m.elements, sizeof(uint32_t) * (size_t)m.n_elements, hipMemcpyHostToDevice, st));
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<float*>(d.v), m.v, sizeof(float) * 3 * (size_t)m.nv, hipMemcpyHostToDevice, st));
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<float*>(d.vn), m.vn, sizeof(float) * 3 * (size_t)m.nvn, hipMemcpyHostToDevice, st));
+        d.scale = 0.0f;
+        for (int k = 0; k < 3; k++) d.scale = fmaxf(d.scale, fmaxf(fabsf(m.bound_min[k]), fabsf(m.bound_max[k])));
+        memcpy(d.bmin, m.bound_min, sizeof d.bmin);
+        memcpy(d.bmax, m.bound_max, sizeof d.bmax);
+        d.n_bvh_nodes = m.n_bvh_nodes;
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<DevMesh*>(ctx->dscene.meshes) + id, &d, sizeof d, hipMemcpyHostToDevice, st));
+    }
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mu_ev[1], st));
+    for (int i = 0; i < n_meshes; i++) {
+        const DevMesh& d = ctx->dmeshes[mesh_ids[i]];
+        RTU_HIP(ctx, mu_tri_records(st, d.f, d.v, d.ref.elements, d.n_elements, const_cast<float4*>(d.ref.tri)));
+        RTU_HIP(ctx, mu_tri_records(st, d.f, d.v, d.fast.elements, d.n_elements, const_cast<float4*>(d.fast.tri)));
+    }
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mu_ev[2], st));
+    for (int i = 0; i < n_meshes; i++) {
+        const uint32_t id = mesh_ids[i];
+        const DevMesh& d = ctx->dmeshes[id];
+        const RtuContext::MeshRefit& r = ctx->refit[id];
+        RTU_HIP(ctx, mu_refit(st, 4, const_cast<float4*>(d.bvh4), ctx->mesh_info[id].nodes4, r.lvl4.data(), (uint32_t)r.lvl4.size() - 1u, d.f, d.v,
+                              d.fast.elements, d.n_elements));
+        RTU_HIP(ctx, mu_refit(st, 8, const_cast<float4*>(d.bvh8), ctx->mesh_info[id].nodes8, r.lvl8.data(), (uint32_t)r.lvl8.size() - 1u, d.f, d.v,
+                              d.fast.elements, d.n_elements));
+    }
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mu_ev[3], st));
+    RTU_HIP(ctx, hipStreamSynchronize(st));
+    // the `ref` trees' depths changed: the stack the walks need (what rtu_upload_scene computes, from the numbers it kept)
+    ctx->shape_meshes = new_shape;
+    uint32_t stack_needed = 1;
+    for (size_t mi = 0; mi < ctx->shape_meshes.size(); mi++) {
+        const RtuContext::MeshInfo& info = ctx->mesh_info[mi];
+        stack_needed = std::max(stack_needed, std::min<uint32_t>(info.stack4, RTU_MAX_BVH_STACK));
+        stack_needed = std::max(stack_needed, info.sah_depth);
+        stack_needed = std::max(stack_needed, ctx->shape_meshes[mi].bvh_depth);
+    }
+    ctx->bvh_stack_needed = stack_needed;
+    return RTU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1966,6 +2077,7 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     std::vector<uint32_t> fast_nodes(s->n_meshes, 0);
     std::vector<std::vector<uint32_t>> fast_elements(s->n_meshes);  // per mesh: slot of the fast tree's leaf order -> face
     std::vector<uint32_t> slot_of;
+    std::vector<RtuContext::MeshRefit> refit(s->n_meshes);
     uint32_t stack_needed = 1;
     for (uint32_t mi = 0; mi < s->n_meshes; mi++) {
         const RtuMesh& m = s->meshes[mi];
@@ -1973,31 +2085,11 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         memset(&d, 0, sizeof d);
         std::vector<float4> tri;
         build_tri_records(m, m.elements, m.n_elements, tri);
-        for (uint32_t i = 1; i < m.n_bvh_nodes; i++) {
-            const RtuBvhNode& bn = m.bvh[i];
-            if (bn.bmin[0] > bn.bmax[0] || bn.bmin[1] > bn.bmax[1] || bn.bmin[2] > bn.bmax[2]) d.any_empty_box = 1;
-        }
         static_assert(sizeof(RtuBvhNode) == 2 * sizeof(float4), "BVH node is two float4");
-        // `ref` tree: the reference's, renumbered breadth-first (sibling pairs stay adjacent, the
-        // root stays node 1): same tree, same traversal order.
-        std::vector<RtuBvhNode> bfs(m.n_bvh_nodes);
-        memset(bfs.data(), 0, bfs.size() * sizeof(RtuBvhNode));
-        {
-            std::vector<std::pair<uint32_t, uint32_t>> queue;  // (old id, new id)
-            queue.push_back({1u, 1u});
-            uint32_t next_free = 2;
-            for (size_t qi = 0; qi < queue.size(); qi++) {
-                auto [oldId, newId] = queue[qi];
-                RtuBvhNode nn = m.bvh[oldId];
-                if (nn.count == 0) {
-                    queue.push_back({nn.index, next_free});
-                    queue.push_back({nn.index + 1, next_free + 1});
-                    nn.index = next_free;
-                    next_free += 2;
-                }
-                bfs[newId] = nn;
-            }
-        }
+        // `ref` tree: the reference's, renumbered breadth-first
+        std::vector<RtuBvhNode> bfs;
+        renumber_bfs(m, bfs, d.any_empty_box);
+        refit[mi].ref_bvh_alloc = ctx->scene_allocs.size();  // the allocation the next line makes
         if ((rc = upload(ctx, reinterpret_cast<const float4*>(bfs.data()), (size_t)m.n_bvh_nodes * 2, &d.ref.bvh)) != RTU_OK) return rc;
         if ((rc = upload(ctx, tri.data(), tri.size(), &d.ref.tri)) != RTU_OK) return rc;
         if ((rc = upload(ctx, m.elements, (size_t)m.n_elements, &d.ref.elements)) != RTU_OK) return rc;
@@ -2021,9 +2113,11 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         build_wide8(sah, sub_first, sub_total, wide8);
         if ((rc = upload(ctx, wide8.data(), wide8.size(), &d.bvh8)) != RTU_OK) return rc;
         fast_nodes[mi] = (uint32_t)(wide8.size() / 16);
+        wide_levels<8>(wide8, refit[mi].lvl8);
         std::vector<float4> wide4;
         uint32_t need4 = 1;
         build_wide4(sah, wide4, need4);
+        wide_levels<4>(wide4, refit[mi].lvl4);
         if ((rc = upload(ctx, wide4.data(), wide4.size(), &d.bvh4)) != RTU_OK) return rc;
         mesh_info.push_back({m.nf, sah.depth, need4, (uint32_t)(wide4.size() / 8), (uint32_t)(wide8.size() / 16)});
         if (need4 > RTU_MAX_BVH_STACK) need4 = RTU_MAX_BVH_STACK;  // a walk that needs more finishes on the reference's tree
@@ -2098,6 +2192,7 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     ctx->shape_materials = s->n_materials;
     ctx->shape_maps = s->material_maps != nullptr;
     ctx->fast_elements = std::move(fast_elements);
+    ctx->refit = std::move(refit);
     ctx->dmeshes = meshes;
     ctx->dscene = ds;
     if ((rc = place_scene(ctx, s, false)) != RTU_OK) return rc;
@@ -2128,6 +2223,207 @@ int rtu_update_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         return rc;
     }
     return RTU_OK;
+}
+
+int rtu_update_meshes(RtuContext* ctx, const RtuSceneDesc* s, const uint32_t* mesh_ids, int n_meshes) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (n_meshes == 0) return rtu_update_scene(ctx, s);
+    if (n_meshes < 0 || !mesh_ids) return fail(ctx, RTU_ERR_ARG, "mesh_ids is NULL or n_meshes negative");
+    // everything is checked before anything is written: a refused update leaves the context as it was
+    int rc = shape_args(ctx, s);
+    if (rc != RTU_OK) return rc;
+    const size_t nm = ctx->shape_meshes.size();
+    std::vector<char> listed(nm, 0);
+    for (int i = 0; i < n_meshes; i++) {
+        const uint32_t id = mesh_ids[i];
+        if (id >= nm) return fail(ctx, RTU_ERR_ARG, "mesh id %u out of range (%zu meshes)", id, nm);
+        if (listed[id]) return fail(ctx, RTU_ERR_ARG, "mesh id %u listed twice", id);
+        listed[id] = 1;
+    }
+    // the shape rule of rtu_update_scene, except that a LISTED mesh may bring a `ref` tree of another size
+    std::vector<RtuMesh> want = ctx->shape_meshes;
+    if (s->n_meshes == nm)
+        for (size_t id = 0; id < nm; id++)
+            if (listed[id]) want[id].n_bvh_nodes = s->meshes[id].n_bvh_nodes;
+    RtuSceneDesc up = shape_desc(ctx);
+    up.meshes = want.data();
+    const std::string diff = shape_diff(&up, s);
+    if (!diff.empty()) return fail(ctx, RTU_ERR_SCENE_SHAPE, "not the uploaded scene's shape: %s", diff.c_str());
+    std::vector<RtuMesh> new_shape = ctx->shape_meshes;
+    for (size_t id = 0; id < nm; id++) {
+        if (!listed[id]) continue;
+        const RtuMesh& m = s->meshes[id];
+        const uint32_t mi = (uint32_t)id;
+        if (m.n_elements != ctx->shape_meshes[id].n_elements)
+            return fail(ctx, RTU_ERR_SCENE_SHAPE, "not the uploaded scene's shape: mesh %u: n_elements differs", mi);
+        // what validate() asks of a mesh's vertices, normals and `ref` tree at upload, with its codes (connectivity is the uploaded one)
+        if (!m.v || !m.vn || !m.bvh || !m.elements) return fail(ctx, RTU_ERR_ARG, "mesh %u: missing array (v, vn, bvh and elements are read)", mi);
+        if (m.n_bvh_nodes < 2 || m.n_elements != m.nf || m.nf == 0) return fail(ctx, RTU_ERR_ARG, "mesh %u: empty", mi);
+        if (m.n_bvh_nodes >= (1u << 28)) return fail(ctx, RTU_ERR_UNSUPPORTED, "mesh %u: more than 2^28 nodes/elements", mi);
+        if (m.bvh_depth > RTU_MAX_BVH_STACK) return fail(ctx, RTU_ERR_UNSUPPORTED, "mesh %u: BVH depth %u > %d", mi, m.bvh_depth, RTU_MAX_BVH_STACK);
+        if ((rc = validate_tree(ctx, m, mi)) != RTU_OK) return rc;
+        RtuMesh& h = new_shape[id];
+        h.n_bvh_nodes = m.n_bvh_nodes;
+        h.bvh_depth = m.bvh_depth;
+        memcpy(h.bound_min, m.bound_min, sizeof h.bound_min);
+        memcpy(h.bound_max, m.bound_max, sizeof h.bound_max);
+    }
+    RtuSceneDesc placed = *s;  // headers as the context will remember them; the arrays stay NULL
+    placed.meshes = new_shape.data();
+    placed.textures = ctx->shape_textures.data();
+    if ((rc = validate(ctx, &placed, true)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers rewritten below
+    if (ctx->aux_stream) RTU_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
+    if (!ctx->llb) ctx->llb = ll_builder_create();
+    ctx->scene_gen++;
+    // the meshes first (and the shape with them): the placement's node-level bounds read the mesh boxes from the remembered headers
+    if ((rc = write_meshes(ctx, s, mesh_ids, n_meshes, new_shape)) == RTU_OK) {
+        placed.meshes = ctx->shape_meshes.data();
+        rc = place_scene(ctx, &placed, true);
+    }
+    if (rc != RTU_OK) {
+        free_scene(ctx);  // half written: nothing to render from
+        return rc;
+    }
+    if (ctx->mu_timing) {
+        RTU_HIP(ctx, hipEventRecord(ctx->mu_ev[4], ctx->stream));
+        RTU_HIP(ctx, hipEventSynchronize(ctx->mu_ev[4]));
+        for (int k = 0; k < 4; k++) {
+            float ms = 0;
+            RTU_HIP(ctx, hipEventElapsedTime(&ms, ctx->mu_ev[k], ctx->mu_ev[k + 1]));
+            ctx->mu_ms[k] += ms;
+        }
+    }
+    return RTU_OK;
+}
+
+int rtu_debug_mesh_update_timing(RtuContext* ctx, int on, float* ms_out4) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (ms_out4) memcpy(ms_out4, ctx->mu_ms, sizeof ctx->mu_ms);
+    memset(ctx->mu_ms, 0, sizeof ctx->mu_ms);
+    ctx->mu_timing = on != 0;
+    return RTU_OK;
+}
+
+namespace {
+// one array of a mesh dump to the caller: *bytes_out is always set; RTU_ERR_ARG when `out` is too small for it
+int dump_out(RtuContext* ctx, size_t bytes, void* out, size_t capacity, size_t* bytes_out) {
+    if (bytes_out) *bytes_out = bytes;
+    if (bytes > capacity || (bytes && !out)) return fail(ctx, RTU_ERR_ARG, "the array has %zu bytes, the buffer %zu", bytes, capacity);
+    return RTU_OK;
+}
+}  // namespace
+
+int rtu_debug_context_mesh(RtuContext* ctx, uint32_t mesh, int which, void* out, size_t capacity_bytes, size_t* bytes_out) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (bytes_out) *bytes_out = 0;
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (mesh >= ctx->dmeshes.size()) return fail(ctx, RTU_ERR_ARG, "no mesh %u", mesh);
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DevMesh d;  // the record the kernels read, not the host's copy of it
+    RTU_HIP(ctx, hipMemcpy(&d, ctx->dscene.meshes + mesh, sizeof d, hipMemcpyDeviceToHost));
+    const RtuMesh& h = ctx->shape_meshes[mesh];
+    const RtuContext::MeshInfo& info = ctx->mesh_info[mesh];
+    const void* src = nullptr;
+    size_t bytes = 0;
+    RtuMeshHeaderDump hd;
+    switch (which) {
+        case RTU_MESH_BVH4: src = d.bvh4; bytes = sizeof(float4) * 8 * (size_t)info.nodes4; break;
+        case RTU_MESH_BVH8: src = d.bvh8; bytes = sizeof(float4) * 16 * (size_t)info.nodes8; break;
+        case RTU_MESH_FAST_TRI: src = d.fast.tri; bytes = sizeof(float4) * 4 * (size_t)d.n_elements; break;
+        case RTU_MESH_REF_TRI: src = d.ref.tri; bytes = sizeof(float4) * 4 * (size_t)d.n_elements; break;
+        case RTU_MESH_REF_BVH: src = d.ref.bvh; bytes = sizeof(RtuBvhNode) * (size_t)d.n_bvh_nodes; break;
+        case RTU_MESH_REF_ELEMENTS: src = d.ref.elements; bytes = sizeof(uint32_t) * (size_t)d.n_elements; break;
+        case RTU_MESH_FAST_ELEMENTS: src = d.fast.elements; bytes = sizeof(uint32_t) * (size_t)d.n_elements; break;
+        case RTU_MESH_V: src = d.v; bytes = sizeof(float) * 3 * (size_t)h.nv; break;
+        case RTU_MESH_VN: src = d.vn; bytes = sizeof(float) * 3 * (size_t)h.nvn; break;
+        case RTU_MESH_HEADER:
+            memcpy(hd.bmin, d.bmin, sizeof hd.bmin); memcpy(hd.bmax, d.bmax, sizeof hd.bmax);
+            hd.scale = d.scale; hd.n_bvh_nodes = d.n_bvh_nodes; hd.any_empty_box = d.any_empty_box;
+            bytes = sizeof hd;
+            break;
+        default: return fail(ctx, RTU_ERR_ARG, "no mesh array %d", which);
+    }
+    int rc = dump_out(ctx, bytes, out, capacity_bytes, bytes_out);
+    if (rc != RTU_OK) return rc;
+    if (which == RTU_MESH_HEADER) memcpy(out, &hd, sizeof hd);
+    else if (bytes) RTU_HIP(ctx, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return RTU_OK;
+}
+
+int rtu_debug_host_mesh(const RtuMesh* uploaded, const RtuMesh* now, int which, void* out, size_t capacity_bytes, size_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    RtuContext tmp;  // plain host state: nothing here touches a GPU
+    const RtuMesh* cur = now ? now : uploaded;
+    for (const RtuMesh* m : {uploaded, cur}) {
+        if (!m || !m->v || !m->f || !m->vn || !m->bvh || !m->elements || m->nf == 0 || m->n_elements != m->nf || m->n_bvh_nodes < 2) return RTU_ERR_ARG;
+        if (m->bvh_depth > RTU_MAX_BVH_STACK) return RTU_ERR_UNSUPPORTED;
+        for (uint32_t i = 0; i < m->nf * 3; i++)
+            if (m->f[i] >= m->nv) return RTU_ERR_ARG;
+        int rc = validate_tree(&tmp, *m, 0);
+        if (rc != RTU_OK) return rc;
+    }
+    if (cur->nv != uploaded->nv || cur->nf != uploaded->nf || cur->nvn != uploaded->nvn) return RTU_ERR_SCENE_SHAPE;
+    RtuMesh edited = *cur;  // the deformed vertices and `ref` tree on the UPLOADED connectivity
+    edited.f = uploaded->f;
+    std::vector<float4> f4;
+    std::vector<RtuBvhNode> bfs;
+    RtuMeshHeaderDump hd;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    SahTree sah;
+    const bool fast = which == RTU_MESH_BVH4 || which == RTU_MESH_BVH8 || which == RTU_MESH_FAST_TRI || which == RTU_MESH_FAST_ELEMENTS;
+    std::vector<uint32_t> sub_first, sub_total;
+    if (fast) {  // the topology of the fast tree is the uploaded mesh's
+        build_sah(*uploaded, sah);
+        if (sah.depth > RTU_MAX_BVH_STACK) return RTU_ERR_UNSUPPORTED;
+        dfs_order(sah, sub_first, sub_total);
+    }
+    switch (which) {
+        case RTU_MESH_BVH4: {
+            uint32_t need4 = 1;
+            build_wide4(sah, f4, need4);
+            if (now) refit_host<4>(f4, edited, sah.elements);
+            src = f4.data(); bytes = sizeof(float4) * f4.size();
+            break;
+        }
+        case RTU_MESH_BVH8:
+            build_wide8(sah, sub_first, sub_total, f4);
+            if (now) refit_host<8>(f4, edited, sah.elements);
+            src = f4.data(); bytes = sizeof(float4) * f4.size();
+            break;
+        case RTU_MESH_FAST_TRI:
+            build_tri_records(edited, sah.elements.data(), (uint32_t)sah.elements.size(), f4);
+            src = f4.data(); bytes = sizeof(float4) * f4.size();
+            break;
+        case RTU_MESH_FAST_ELEMENTS: src = sah.elements.data(); bytes = sizeof(uint32_t) * sah.elements.size(); break;
+        case RTU_MESH_REF_TRI:
+            build_tri_records(edited, cur->elements, cur->n_elements, f4);
+            src = f4.data(); bytes = sizeof(float4) * f4.size();
+            break;
+        case RTU_MESH_REF_BVH:
+            renumber_bfs(*cur, bfs, hd.any_empty_box);
+            src = bfs.data(); bytes = sizeof(RtuBvhNode) * bfs.size();
+            break;
+        case RTU_MESH_REF_ELEMENTS: src = cur->elements; bytes = sizeof(uint32_t) * (size_t)cur->n_elements; break;
+        case RTU_MESH_V: src = cur->v; bytes = sizeof(float) * 3 * (size_t)cur->nv; break;
+        case RTU_MESH_VN: src = cur->vn; bytes = sizeof(float) * 3 * (size_t)cur->nvn; break;
+        case RTU_MESH_HEADER:
+            renumber_bfs(*cur, bfs, hd.any_empty_box);
+            memcpy(hd.bmin, cur->bound_min, sizeof hd.bmin); memcpy(hd.bmax, cur->bound_max, sizeof hd.bmax);
+            hd.scale = 0.0f;
+            for (int k = 0; k < 3; k++) hd.scale = fmaxf(hd.scale, fmaxf(fabsf(cur->bound_min[k]), fabsf(cur->bound_max[k])));
+            hd.n_bvh_nodes = cur->n_bvh_nodes;
+            src = &hd; bytes = sizeof hd;
+            break;
+        default: return RTU_ERR_ARG;
+    }
+    int rc = dump_out(nullptr, bytes, out, capacity_bytes, bytes_out);
+    if (rc == RTU_OK && bytes) memcpy(out, src, bytes);
+    return rc;
 }
 
 int rtu_scene_shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b, char* err_buf, size_t err_len) {

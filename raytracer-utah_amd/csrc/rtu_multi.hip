@@ -149,6 +149,19 @@ int rtu_multi_update_scene(RtuMultiContext* m, const RtuSceneDesc* scene) {
     return RTU_OK;
 }
 
+int rtu_multi_update_meshes(RtuMultiContext* m, const RtuSceneDesc* scene, const uint32_t* mesh_ids, int n_meshes) {
+    if (!m) return RTU_ERR_ARG;
+    // as rtu_multi_update_scene: every context holds the same scene and answers alike; one thread per GPU
+    const int G = (int)m->ctx.size();
+    std::vector<int> rcs((size_t)G, RTU_OK);
+    std::vector<std::thread> th;
+    for (int g = 0; g < G; g++) th.emplace_back([&, g] { rcs[(size_t)g] = rtu_update_meshes(m->ctx[(size_t)g], scene, mesh_ids, n_meshes); });
+    for (std::thread& t : th) t.join();
+    for (int g = 0; g < G; g++)
+        if (rcs[(size_t)g] != RTU_OK) return fail(m, rcs[(size_t)g], std::string("GPU ") + std::to_string(m->devices[(size_t)g]) + ": " + rtu_last_error(m->ctx[(size_t)g]));
+    return RTU_OK;
+}
+
 int rtu_multi_render_frame(RtuMultiContext* m, const RtuFrameDesc* frame, float* h_rgbz, const RtuProgress* progress) {
     if (!m || !frame) return RTU_ERR_ARG;
     if (!h_rgbz && !(progress && progress->rows_done)) return fail(m, RTU_ERR_ARG, "neither a frame buffer nor a rows_done callback: nowhere to put the image");
