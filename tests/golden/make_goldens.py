@@ -20,6 +20,10 @@ tests/test_oracle.py) to tests/golden/SceneFiles/: every scene XML and the meshe
 for the PNG textures only the filter type of each row and which texture of a golden blob holds their pixels
 (textures.json), from which the tests write them back. They are the inputs of the fixtures above, so the loader is checked without the reference tree.
 
+An .obj that goes through the reference needs `vt` lines and `v/vt/vn` faces: TriObj::IntersectRay reads the texture
+coordinates of every accepted hit unconditionally (objFunctions.cpp:320) and crashes on a mesh without them. The oracle
+and the device render such a mesh (uvw = 0); the reference cannot, so the scenes under tests/scenes carry `vt`.
+
 No reference source text is copied; the fixtures are inputs and outputs.
 """
 import gzip, hashlib, json, os, shutil, subprocess, sys
@@ -66,6 +70,9 @@ CONFIGS = [
     # row f3: an .obj that brings its own materials (usemtl / .mtl -> MultiMtl, xmlload.cpp:199-243) — a scene written for
     # this repository (tests/scenes/multimtl, "@" = repository path), run through the compiled reference like the others
     ("mtl_160x120", "@tests/scenes/multimtl/scene.xml", 160, 120, True),
+    # exact ties by the thousand (tests/scenes/ties): a torus pressed flat, three coincident grids lying in a `plane` object under
+    # both node orders — which of the triangles (or the plane) with bitwise-equal t wins is the reference's test order
+    ("ties_160x120", "@tests/scenes/ties/scene.xml", 160, 120, True),
     # recipe P (config 5): recipe S plus the 4-bounce Monte-Carlo gather of Render(); 8th field "P"
     ("p11_p2_120x68", "Project11/scene.xml", 120, 68, True, 2, "P"),
     ("p13_p2_96x72", "Project13/scene.xml", 96, 72, True, 2, "P"),

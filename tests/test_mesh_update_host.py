@@ -20,7 +20,7 @@ from conftest import MAC_PREFIX, REPO
 RTU_MAX_BVH_STACK = int(re.search(r"#define RTU_MAX_BVH_STACK\s+(\d+)", open(os.path.join(REPO, "include", "rtu_scene.h")).read()).group(1))
 
 # name, argument. The last two make coplanar and zero-area triangles (exact ties, NaN normals) by the thousand: they test the
-# builders, and no image is rendered from them.
+# builders here; images of flat and welded meshes are rendered from tests/scenes/ties (test_gpu_ties.py).
 DEFORMATIONS = [("wobble", 0), ("wobble", 1), ("wobble", 2), ("twist", 30), ("twist", 60), ("twist", 120), ("bulge", None),
                 ("flatten", None), ("collapse", None)]
 RENDERED = [("wobble", 0), ("wobble", 1), ("wobble", 2), ("twist", 120), ("bulge", None)]
@@ -298,23 +298,55 @@ def test_host_refit(pkg, golden, tag):
         assert same_bits_nan(plain["fast_tri"].reshape(-1, 16), tri_records_numpy(f, v, plain["fast_elements"]))
         assert same_bits_nan(plain["ref_tri"].reshape(-1, 16), tri_records_numpy(f, v, plain["ref_elements"]))
         for d in DEFORMATIONS:
-            now = deformed_scene(pkg, scene, mesh, d)
-            w = "%s %s" % (what, deform_name(d))
-            got = pkg.host_mesh(scene, mesh, now)
-            f2, v2 = mesh_arrays(now, mesh)
-            assert np.array_equal(f2, f)
-            # the topology is the uploaded mesh's
-            for width, key in ((4, "bvh4"), (8, "bvh8")):
-                assert np.array_equal(wide_slots(got[key], width)[2], wide_slots(plain[key], width)[2]), "%s: ref words of %s moved" % (w, key)
-            assert np.array_equal(got["fast_elements"], plain["fast_elements"]), "%s: fast.elements moved" % w
-            # boxes, records, vertices and `ref` tree are the deformed mesh's
-            check_boxes_are_exact(got, f, v2, w)
-            assert same_bits_nan(got["fast_tri"].reshape(-1, 16), tri_records_numpy(f, v2, plain["fast_elements"])), "%s: fast.tri" % w
-            rebuilt = pkg.host_mesh(now, mesh)
-            for key in ("ref_bvh", "ref_elements", "v", "vn", "bmin", "bmax"):
-                assert np.array_equal(got[key].view(np.uint32), rebuilt[key].view(np.uint32)), "%s: %s is not the deformed mesh's" % (w, key)
-            assert same_bits_nan(got["ref_tri"].reshape(-1, 16), tri_records_numpy(f, v2, rebuilt["ref_elements"])), "%s: ref.tri" % w
-            assert got["n_bvh_nodes"] == now.mesh(mesh).n_bvh_nodes and got["any_empty_box"] == rebuilt["any_empty_box"]
+            check_refit(pkg, scene, mesh, deformed_scene(pkg, scene, mesh, d), plain, "%s %s" % (what, deform_name(d)))
+
+
+def check_refit(pkg, scene, mesh, now, plain, w):
+    """`plain`: host_mesh(scene, mesh). The refit of that upload to the vertices of `now` keeps the uploaded topology; boxes, records,
+    vertices and `ref` tree are those of `now`."""
+    f, _ = mesh_arrays(scene, mesh)
+    got = pkg.host_mesh(scene, mesh, now)
+    f2, v2 = mesh_arrays(now, mesh)
+    assert np.array_equal(f2, f)
+    # the topology is the uploaded mesh's
+    for width, key in ((4, "bvh4"), (8, "bvh8")):
+        assert np.array_equal(wide_slots(got[key], width)[2], wide_slots(plain[key], width)[2]), "%s: ref words of %s moved" % (w, key)
+    assert np.array_equal(got["fast_elements"], plain["fast_elements"]), "%s: fast.elements moved" % w
+    # boxes, records, vertices and `ref` tree are the deformed mesh's
+    check_boxes_are_exact(got, f, v2, w)
+    assert same_bits_nan(got["fast_tri"].reshape(-1, 16), tri_records_numpy(f, v2, plain["fast_elements"])), "%s: fast.tri" % w
+    rebuilt = pkg.host_mesh(now, mesh)
+    for key in ("ref_bvh", "ref_elements", "v", "vn", "bmin", "bmax"):
+        assert np.array_equal(got[key].view(np.uint32), rebuilt[key].view(np.uint32)), "%s: %s is not the deformed mesh's" % (w, key)
+    assert same_bits_nan(got["ref_tri"].reshape(-1, 16), tri_records_numpy(f, v2, rebuilt["ref_elements"])), "%s: ref.tri" % w
+    assert got["n_bvh_nodes"] == now.mesh(mesh).n_bvh_nodes and got["any_empty_box"] == rebuilt["any_empty_box"]
+
+
+def test_host_refit_of_a_flat_upload(pkg, tmp_path):
+    """The inverse direction: the scene uploaded FLAT (tests/scenes/ties: a torus with every z = 0, so build_wide4 / build_wide8 choose
+    their collapses by box area with every area zero) and refitted to the round torus, which inflates that topology — and to the
+    half-welded pancake (zero-area triangles, NaN records). Leaf and inner boxes are still the exact min / max, every ref word is kept."""
+    from test_ties_host import pancake, round_vertices, ties_scene, welded_vertices, with_vertices
+    flat = ties_scene(pkg, tmp_path)
+    mesh = pancake(flat)
+    f, v = mesh_arrays(flat, mesh)
+    assert np.all(v[:, 2] == 0) and list(flat.mesh(mesh).bound_min)[2] == 0 == list(flat.mesh(mesh).bound_max)[2]
+    plain = pkg.host_mesh(flat, mesh)
+    assert_same_structures(pkg.host_mesh(flat, mesh, flat), plain, "pancake refit in place")
+    check_boxes_are_exact(plain, f, v, "pancake")
+    for width, key in ((4, "bvh4"), (8, "bvh8")):  # every box of the flat upload has no thickness
+        lo, hi, ref = wide_slots(plain[key], width)
+        used = ref != EMPTY_REF
+        assert used.any() and np.all(lo[used][:, 2] == 0) and np.all(hi[used][:, 2] == 0)
+    assert same_bits_nan(plain["fast_tri"].reshape(-1, 16), tri_records_numpy(f, v, plain["fast_elements"]))
+    round_ = with_vertices(pkg, flat, mesh, round_vertices(v))
+    welded = with_vertices(pkg, flat, mesh, welded_vertices(v))
+    for now, name in ((round_, "round"), (welded, "welded")):
+        assert now.mesh(mesh).bvh_depth <= RTU_MAX_BVH_STACK, "%s: depth %d" % (name, now.mesh(mesh).bvh_depth)  # a property of these inputs
+        check_refit(pkg, flat, mesh, now, plain, "pancake -> " + name)
+    assert np.isnan(pkg.host_mesh(flat, mesh, welded)["fast_tri"]).any(), "the welded pancake has no degenerate triangle"
+    # ... and the direction the other tests take, on the same mesh: uploaded round, pressed flat
+    check_refit(pkg, round_, mesh, flat, pkg.host_mesh(round_, mesh), "round -> pancake")
 
 
 def test_host_mesh_refuses_another_shape(pkg, golden):
