@@ -152,7 +152,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_adaptive_defaults", "rtu_render_frame_adaptive", "rtu_render_frame_adaptive_device", "rtu_debug_sample_images", "rtu_debug_texcoords",
                "rtu_debug_device_allocations", "rtu_progressive_begin", "rtu_progressive_advance", "rtu_progressive_status",
                "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes",
-               "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing"]
+               "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing",
+               "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -275,6 +276,53 @@ _sig(hip, "rtu_multi_update_meshes", _I, _P, _P, ctypes.POINTER(ctypes.c_uint32)
 _sig(hip, "rtu_debug_mesh_update_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
 _sig(hip, "rtu_debug_context_mesh", _I, _P, ctypes.c_uint32, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
 _sig(hip, "rtu_debug_host_mesh", _I, _P, _P, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
+
+# ray queries (include/rtu_render.h RtuRay / RtuRayHit): numpy layouts are built where numpy is imported (ray_dtype / hit_dtype)
+RTU_RAY_HIT, RTU_RAY_FRONT, RTU_RAY_INVALID = 1, 2, 4
+RTU_QUERY_REFERENCE_WALK = 1
+_sig(hip, "rtu_trace_rays_device", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P)
+_sig(hip, "rtu_occluded_rays_device", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P)
+_sig(hip, "rtu_trace_rays", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P)
+_sig(hip, "rtu_occluded_rays", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P)
+_sig(hip, "rtu_camera_rays", _I, ctypes.POINTER(RtuFrameDesc), _I, _I, _P)
+
+
+def ray_dtype():
+    """numpy layout of RtuRay (32 bytes): org[3], tmax, dir[3], reserved."""
+    import numpy as np
+    return np.dtype([("org", np.float32, 3), ("tmax", np.float32), ("dir", np.float32, 3), ("reserved", np.uint32)])
+
+
+def hit_dtype():
+    """numpy layout of RtuRayHit (48 bytes): t, node, flags, material, p[3], pad0, N[3], pad1."""
+    import numpy as np
+    return np.dtype([("t", np.float32), ("node", np.int32), ("flags", np.uint32), ("material", np.int32),
+                     ("p", np.float32, 3), ("pad0", np.float32), ("N", np.float32, 3), ("pad1", np.float32)])
+
+
+def _as_rays(rays):
+    """A contiguous RtuRay array from a structured array of ray_dtype() or a float32 [n, 8] array {org, tmax, dir, reserved}."""
+    import numpy as np
+    rays = np.asarray(rays)
+    if rays.dtype == ray_dtype():
+        return np.ascontiguousarray(rays).reshape(-1)
+    if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+        raise RtuError(RTU_ERR_ARG, "rays: a float32 [n, 8] array or a structured array of ray_dtype()")
+    return np.ascontiguousarray(rays).view(ray_dtype()).reshape(-1)
+
+
+def camera_rays(frame, row0=0, nrows=None):
+    """rtu_camera_rays (pure host code): the pixel-centre rays of image rows [row0, row0 + nrows) of `frame` as a structured array
+    [nrows * width] of ray_dtype(), in image order, tmax = RTU_BIGFLOAT: the primary rays of a render of that frame, bit for bit."""
+    import numpy as np
+    if nrows is None:
+        nrows = frame.height - row0
+    out = np.zeros(max(nrows, 0) * max(frame.width, 0), ray_dtype())
+    rc = hip.rtu_camera_rays(ctypes.byref(frame), row0, nrows, out.ctypes.data if out.size else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_camera_rays: rows outside the image or an empty frame")
+    return out
+
 
 # the arrays of a mesh dump (include/rtu_render.h RTU_MESH_*): name -> (which, numpy dtype, trailing shape)
 MESH_ARRAYS = {"bvh4": (0, "float32", (8, 4)), "bvh8": (1, "float32", (16, 4)), "fast_tri": (2, "float32", (4, 4)), "ref_tri": (3, "float32", (4, 4)),
@@ -801,6 +849,36 @@ class Context:
         out = np.empty((n, TEXOP_OUT[op]) if TEXOP_OUT[op] > 1 else (n,), np.float32)
         self._check(hip.rtu_debug_texcoords(self._h, op, index, x.ctypes.data, n, out.ctypes.data))
         return out
+
+    def trace_rays(self, rays, reference_walk=False):
+        """Closest hits of caller-supplied rays (rtu_trace_rays): rays float32 [n, 8] {org, tmax, dir, -} or a structured array of
+        ray_dtype(); returns a structured array [n] of hit_dtype(). Directions must be of unit length (else RTU_RAY_INVALID)."""
+        import numpy as np
+        r = _as_rays(rays)
+        out = np.zeros(r.size, hit_dtype())
+        self._check(hip.rtu_trace_rays(self._h, r.ctypes.data if r.size else None, r.size, RTU_QUERY_REFERENCE_WALK if reference_walk else 0,
+                                       out.ctypes.data if r.size else None))
+        return out
+
+    def occluded(self, rays, reference_walk=False):
+        """Is anything in front of tmax along each ray (rtu_occluded_rays)? uint8 [n], 1 or 0."""
+        import numpy as np
+        r = _as_rays(rays)
+        out = np.zeros(r.size, np.uint8)
+        self._check(hip.rtu_occluded_rays(self._h, r.ctypes.data if r.size else None, r.size, RTU_QUERY_REFERENCE_WALK if reference_walk else 0,
+                                          out.ctypes.data if r.size else None))
+        return out
+
+    def trace_rays_device(self, d_rays_ptr, n, d_hits_ptr, stream=None, reference_walk=False, flags=None):
+        """rtu_trace_rays_device: n RtuRay at d_rays_ptr -> n RtuRayHit at d_hits_ptr (device memory, 16-byte aligned: a torch tensor's
+        data_ptr()), asynchronous on `stream`. flags (an integer) overrides reference_walk."""
+        f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
+        self._check(hip.rtu_trace_rays_device(self._h, d_rays_ptr, n, f, d_hits_ptr, stream))
+
+    def occluded_device(self, d_rays_ptr, n, d_occluded_ptr, stream=None, reference_walk=False, flags=None):
+        """rtu_occluded_rays_device: n RtuRay at d_rays_ptr -> n bytes (1 / 0) at d_occluded_ptr, asynchronous on `stream`."""
+        f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
+        self._check(hip.rtu_occluded_rays_device(self._h, d_rays_ptr, n, f, d_occluded_ptr, stream))
 
     def render_frames_device(self, frames, d_ptr, stream=None):
         """Frames in flight: len(frames) frames of recipe W in one launch sequence, images consecutive at d_ptr."""

@@ -7,6 +7,7 @@
 #include "rtu_device.h"
 #include "rtu_lightlist.h"
 #include "rtu_meshrec.h"
+#include "rtu_query.h"
 
 #include <algorithm>
 #include <array>
@@ -130,6 +131,8 @@ struct RtuContext {
     uint32_t  cover_faces = 0;
     DevBuf<uint32_t> occ;                    // tile occupancy of primary rays (KernelArgs::occ), grown on demand
     int4* node_rects = nullptr;              // [RTU_MAX_FRAME_BATCH][n_nodes] screen rectangles of the node-level bounds (k_node_rects); owned by the scene
+    DevBuf<float4>  q_rays, q_hits;          // ray queries, host forms (rtu_trace_rays / rtu_occluded_rays): one chunk of rays and of answers
+    DevBuf<uint8_t> q_occ;
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -3195,6 +3198,111 @@ int rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, u
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "texcoords: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+// ---- ray queries (rtu_query.hip) ----------------------------------------------------------------------------------------------
+namespace {
+const size_t kQueryChunk = (size_t)1 << 20;  // rays per launch of the host forms: 32 MB of rays, 48 MB of hits
+
+int query_args(RtuContext* ctx, const void* rays, const void* out, size_t n, uint32_t flags, bool device) {
+    if (flags & ~RTU_QUERY_REFERENCE_WALK) return fail(ctx, RTU_ERR_ARG, "unknown ray-query flag bits 0x%x", flags & ~RTU_QUERY_REFERENCE_WALK);
+    if (n && (!rays || !out)) return fail(ctx, RTU_ERR_ARG, "rays / result pointer is NULL");
+    if (device && n && (((uintptr_t)rays & 15u) || ((uintptr_t)out & 15u)))
+        return fail(ctx, RTU_ERR_ARG, "device ray / result buffers must be 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    return RTU_OK;
+}
+
+// the scene as the renders see it now, without the experiment switches of rtu_debug_flags (they exist to render wrong images)
+DevScene query_scene(const RtuContext* ctx) {
+    DevScene s = ctx->dscene;
+    s.dbg = 0;
+    return s;
+}
+
+int query_host(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, RtuRayHit* h_hits, uint8_t* h_occ) {
+    const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->q_rays.grow(2 * chunk));
+    if (h_hits) RTU_HIP(ctx, ctx->q_hits.grow(3 * chunk));
+    else RTU_HIP(ctx, ctx->q_occ.grow((chunk + 15u) & ~(size_t)15u));
+    const DevScene s = query_scene(ctx);
+    const bool ref = (flags & RTU_QUERY_REFERENCE_WALK) != 0;
+    for (size_t done = 0; done < n; done += chunk) {
+        const size_t m = n - done < chunk ? n - done : chunk;
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->q_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
+        hipError_t e;
+        if (h_hits) {
+            e = (hipError_t)rtu_launch_query_closest(s, ctx->q_rays.get(), ctx->q_hits.get(), m, ref, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(h_hits + done, ctx->q_hits.get(), sizeof(RtuRayHit) * m, hipMemcpyDeviceToHost, ctx->stream);
+        } else {
+            e = (hipError_t)rtu_launch_query_any(s, ctx->q_rays.get(), ctx->q_occ.get(), m, ref, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(h_occ + done, ctx->q_occ.get(), m, hipMemcpyDeviceToHost, ctx->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "ray query: %s", hipGetErrorString(e));
+    }
+    return RTU_OK;
+}
+}  // namespace
+
+static_assert(sizeof(RtuRay) == 32 && sizeof(RtuRayHit) == 48, "ray query records are two / three float4");
+
+int rtu_trace_rays_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    const int rc = query_args(ctx, d_rays, d_hits, n, flags, true);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_query_closest(query_scene(ctx), (const float4*)d_rays, (float4*)d_hits, n,
+                                                              (flags & RTU_QUERY_REFERENCE_WALK) != 0, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "ray query launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_occluded_rays_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_occluded, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (n && d_rays && ((uintptr_t)d_rays & 15u)) return fail(ctx, RTU_ERR_ARG, "device ray buffer must be 16-byte aligned");
+    const int rc = query_args(ctx, d_rays, d_occluded, n, flags, false);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_query_any(query_scene(ctx), (const float4*)d_rays, (uint8_t*)d_occluded, n,
+                                                          (flags & RTU_QUERY_REFERENCE_WALK) != 0, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "ray query launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_trace_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, RtuRayHit* h_hits) {
+    if (!ctx) return RTU_ERR_ARG;
+    const int rc = query_args(ctx, h_rays, h_hits, n, flags, false);
+    if (rc != RTU_OK || n == 0) return rc;
+    return query_host(ctx, h_rays, n, flags, h_hits, nullptr);
+}
+
+int rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, uint8_t* h_occluded) {
+    if (!ctx) return RTU_ERR_ARG;
+    const int rc = query_args(ctx, h_rays, h_occluded, n, flags, false);
+    if (rc != RTU_OK || n == 0) return rc;
+    return query_host(ctx, h_rays, n, flags, nullptr, h_occluded);
+}
+
+// the primary rays of primary_pixel (render_impl.h; RenderFunctions.cpp:258-268, :97) for the pixel centres of rows [row0, row0 + nrows):
+// the same binary32 expressions in the same order (rtu_vec.h, this file is compiled with -ffp-contract=off), so the same bits
+int rtu_camera_rays(const RtuFrameDesc* frame, int row0, int nrows, RtuRay* rays_out) {
+    if (!frame || frame->width <= 0 || frame->height <= 0 || row0 < 0 || nrows < 0 || row0 > frame->height || nrows > frame->height - row0)
+        return RTU_ERR_ARG;
+    if (nrows && !rays_out) return RTU_ERR_ARG;
+    const f3 cam_pos = ld3(frame->cam_pos), cam_origin = ld3(frame->origin), cam_u = ld3(frame->u), cam_v = ld3(frame->v);
+    for (int y = row0; y < row0 + nrows; y++)
+        for (int x = 0; x < frame->width; x++) {
+            const f3 cp = (cam_origin + cam_u * ((float)x + 0.5f)) + cam_v * ((float)y + 0.5f);
+            const f3 dir = norm3(cp - cam_pos);
+            RtuRay& r = rays_out[(size_t)(y - row0) * (size_t)frame->width + (size_t)x];
+            r.org[0] = cam_pos.x; r.org[1] = cam_pos.y; r.org[2] = cam_pos.z;
+            r.tmax = RTU_BIGFLOAT;
+            r.dir[0] = dir.x; r.dir[1] = dir.y; r.dir[2] = dir.z;
+            r.reserved = 0;
+        }
     return RTU_OK;
 }
 
