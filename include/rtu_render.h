@@ -57,7 +57,12 @@ typedef struct RtuContext RtuContext;
 typedef struct RtuFrameDesc {
     int32_t width, height;
     int32_t shard_rank, shard_count;  /* 0,1 for a single GPU */
-    int32_t max_bounce;               /* 5, RenderFunctions.cpp:134 */
+    int32_t max_bounce;               /* the bounceCount every root Shade() call of the frame receives (the reference passes 5,
+                                         RenderFunctions.cpp:134-135; rtu_frame_setup sets 5): Shade() recurses through that many
+                                         reflections / refractions and is its light loop alone at 0. Recipe P: both calls of the pixel
+                                         and both of every gather bounce (:569-570) receive it. 0 .. RTU_MAX_BOUNCE, else RTU_ERR_ARG;
+                                         the frames of one rtu_render_frames_device call must agree in it. A scene without a
+                                         reflective or refractive material renders at 0 whatever is asked (the image is the same) */
     int32_t collect_stats;            /* 1: fill the ray / traversal counters RtuStats (the counting variant: the reference's own
                                          tree, no culling — slower); 2: the FAST variant as it is timed, counting per kernel what it
                                          touches (RtuTouched) */

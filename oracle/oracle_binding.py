@@ -75,13 +75,40 @@ class OracleError(RuntimeError):
         super().__init__("oracle error %d" % code)
 
 
-def render(scene, width, height, threads=1, row0=0, nrows=None):
+MAX_BOUNCE = 5  # RTU_MAX_BOUNCE: what the reference passes, and what the oracle is at between calls
+lib.rtu_oracle_debug_max_bounce.restype = ctypes.c_int
+lib.rtu_oracle_debug_max_bounce.argtypes = [ctypes.c_int]
+
+
+class _bounces:
+    """Test hook: the root Shade() calls of the renders inside the block receive bounceCount `max_bounce` (RtuFrameDesc.max_bounce
+    of the device); the oracle is back at the reference's 5 afterwards, whatever happened."""
+
+    def __init__(self, max_bounce):
+        if not 0 <= int(max_bounce) <= MAX_BOUNCE:
+            raise ValueError("max_bounce %r outside 0..%d" % (max_bounce, MAX_BOUNCE))
+        self.k = int(max_bounce)
+
+    def __enter__(self):
+        lib.rtu_oracle_debug_max_bounce(self.k)
+
+    def __exit__(self, *exc):
+        lib.rtu_oracle_debug_max_bounce(MAX_BOUNCE)
+
+
+def max_bounce_now():
+    """The depth the oracle renders at (5 outside a call that was given another)."""
+    return lib.rtu_oracle_debug_max_bounce(-1)
+
+
+def render(scene, width, height, threads=1, row0=0, nrows=None, max_bounce=MAX_BOUNCE):
     """Recipe W. `scene` is a raytracer_utah_amd.Scene. Returns (rgbz [rows,W,4] float32, stats dict)."""
     if nrows is None:
         nrows = height - row0
     out = np.empty((nrows, width, 4), np.float32)
     st = OracleStats()
-    rc = lib.rtu_oracle_render_rows(scene.desc_ptr, width, height, row0, nrows, out.ctypes.data, ctypes.byref(st), threads)
+    with _bounces(max_bounce):
+        rc = lib.rtu_oracle_render_rows(scene.desc_ptr, width, height, row0, nrows, out.ctypes.data, ctypes.byref(st), threads)
     if rc != 0:
         raise OracleError(rc)
     return out, st.as_dict()
@@ -105,46 +132,52 @@ def render_scheduled(scene, width, height, threads, per_pixel):
     return out, st.as_dict()
 
 
-def render_samples(scene, width, height, spp, stream=STREAM_KEYED, trig=TRIG_PORTABLE, threads=1, row0=0, nrows=None):
+def render_samples(scene, width, height, spp, stream=STREAM_KEYED, trig=TRIG_PORTABLE, threads=1, row0=0, nrows=None,
+                   max_bounce=MAX_BOUNCE):
     """Recipe S (row f1): spp samples per pixel with soft shadows / glossy bounces / depth of field."""
     if nrows is None:
         nrows = height - row0
     out = np.empty((nrows, width, 4), np.float32)
     st = OracleStats()
-    rc = lib.rtu_oracle_render_samples(scene.desc_ptr, width, height, row0, nrows, spp, stream, trig, out.ctypes.data,
-                                       ctypes.byref(st), threads)
+    with _bounces(max_bounce):
+        rc = lib.rtu_oracle_render_samples(scene.desc_ptr, width, height, row0, nrows, spp, stream, trig, out.ctypes.data,
+                                           ctypes.byref(st), threads)
     if rc != 0:
         raise OracleError(rc)
     return out, st.as_dict()
 
 
-def render_paths(scene, width, height, spp, stream=STREAM_KEYED, trig=TRIG_PORTABLE, threads=1, row0=0, nrows=None):
+def render_paths(scene, width, height, spp, stream=STREAM_KEYED, trig=TRIG_PORTABLE, threads=1, row0=0, nrows=None,
+                 max_bounce=MAX_BOUNCE):
     """Recipe P (config 5): recipe S plus the 4-bounce Monte-Carlo gather."""
     if nrows is None:
         nrows = height - row0
     out = np.empty((nrows, width, 4), np.float32)
     st = OracleStats()
-    rc = lib.rtu_oracle_render_paths(scene.desc_ptr, width, height, row0, nrows, spp, stream, trig, out.ctypes.data,
-                                     ctypes.byref(st), threads)
+    with _bounces(max_bounce):
+        rc = lib.rtu_oracle_render_paths(scene.desc_ptr, width, height, row0, nrows, spp, stream, trig, out.ctypes.data,
+                                         ctypes.byref(st), threads)
     if rc != 0:
         raise OracleError(rc)
     return out, st.as_dict()
 
 
-def sample_images(scene, width, height, spp, first, n, gi=False, threads=1, row0=0, nrows=None):
+def sample_images(scene, width, height, spp, first, n, gi=False, threads=1, row0=0, nrows=None, max_bounce=MAX_BOUNCE):
     """Samples [first, first + n) of the fixed spp-sample frame of recipe S (gi False) or P (gi True), keyed stream, portable trig:
     float32 [n, rows, W, 4] {r, g, b, z}, z = RTU_BIGFLOAT for a miss (what rtu_debug_sample_images returns)."""
     if nrows is None:
         nrows = height - row0
     out = np.empty((n, nrows, width, 4), np.float32)
-    rc = lib.rtu_oracle_render_sample_images(scene.desc_ptr, width, height, row0, nrows, spp, 1 if gi else 0, first, n, out.ctypes.data, threads)
+    with _bounces(max_bounce):
+        rc = lib.rtu_oracle_render_sample_images(scene.desc_ptr, width, height, row0, nrows, spp, 1 if gi else 0, first, n, out.ctypes.data,
+                                                 threads)
     if rc != 0:
         raise OracleError(rc)
     return out
 
 
 def render_adaptive(scene, width, height, spp, min_samples, increment, target, gi=False, trace_batch=1, counts_in=None, threads=1,
-                    row0=0, nrows=None):
+                    row0=0, nrows=None, max_bounce=MAX_BOUNCE):
     """Adaptive recipe S / P as include/rtu_render.h states it (keyed stream, portable trig). Returns (rgbz float32 [rows, W, 4],
     counts uint8 [rows, W] — the rule's —, margin float32 [rows, W], stats dict). counts_in (uint8 [rows, W]): each pixel returns the
     mean of its first counts_in samples instead of the rule's. margin: the smallest |max var - target| over the checkpoints the
@@ -161,9 +194,10 @@ def render_adaptive(scene, width, height, spp, min_samples, increment, target, g
         if cin.shape != (nrows, width):
             raise ValueError("counts_in has shape %s, not %s" % (cin.shape, (nrows, width)))
     st = OracleStats()
-    rc = lib.rtu_oracle_render_adaptive(scene.desc_ptr, width, height, row0, nrows, spp, 1 if gi else 0, min_samples, increment, target,
-                                        trace_batch, cin.ctypes.data if cin is not None else None,
-                                        out.ctypes.data, counts.ctypes.data, margin.ctypes.data, ctypes.byref(st), threads)
+    with _bounces(max_bounce):
+        rc = lib.rtu_oracle_render_adaptive(scene.desc_ptr, width, height, row0, nrows, spp, 1 if gi else 0, min_samples, increment, target,
+                                            trace_batch, cin.ctypes.data if cin is not None else None,
+                                            out.ctypes.data, counts.ctypes.data, margin.ctypes.data, ctypes.byref(st), threads)
     if rc != 0:
         raise OracleError(rc)
     return out, counts, margin, st.as_dict()

@@ -327,6 +327,10 @@ static void Flatten(Flat& F, RtuSceneDesc& d) {
     if (d.environment_map.texture < 0) { memset(&d.environment_map, 0, sizeof(RtuTexMap)); d.environment_map.texture = -1; }
 }
 
+// --bounces N: the bounceCount this driver's own Shade() calls pass (Render() passes 5, RenderFunctions.cpp:134-135). The Shade()
+// calls inside the reference's MonteCarlo() (:569-570) are the reference's and keep their 5.
+static int g_bounces = 5;
+
 // ---- recipe W --------------------------------------------------------------
 static void RenderRows(int y0, int y1, Point3 org, float* z, float* rgb, std::atomic<long long>* hits) {
     const int W = camera.imgWidth, H = camera.imgHeight;
@@ -341,7 +345,7 @@ static void RenderRows(int y0, int y1, Point3 org, float* z, float* rgb, std::at
             if (hit) {
                 nh++;
                 const Material* mtl = h.node->GetMaterial();
-                c = mtl ? mtl->Shade(ray, h, lights, 5) : Color(1, 1, 1);
+                c = mtl ? mtl->Shade(ray, h, lights, g_bounces) : Color(1, 1, 1);
             } else {
                 c = background.Sample(Point3((float)x / camera.imgWidth, (float)y / camera.imgHeight, 0));
             }
@@ -414,10 +418,10 @@ static void RenderRowsSampled(int y0, int y1, int spp, bool gi, float* z, float*
                     if (gi && mtl) {
                         LightList monteCarloList;
                         MonteCarlo(monteCarloList, h, x, y, monteCarloBounces, monteCarloSampleSize);
-                        c = mtl->Shade(ray, h, monteCarloList, 5);
-                        c += mtl->Shade(ray, h, lights, 5);
+                        c = mtl->Shade(ray, h, monteCarloList, g_bounces);
+                        c += mtl->Shade(ray, h, lights, g_bounces);
                     } else {
-                        c = mtl ? mtl->Shade(ray, h, lights, 5) : Color(1, 1, 1);
+                        c = mtl ? mtl->Shade(ray, h, lights, g_bounces) : Color(1, 1, 1);
                     }
                 } else {
                     c = background.Sample(Point3((float)x / camera.imgWidth, (float)y / camera.imgHeight, 0));
@@ -450,8 +454,16 @@ static bool WriteFile(const std::string& path, const void* p, size_t n) {
 
 int main(int argc, char** argv) {
     if (argc < 5) {
-        fprintf(stderr, "usage: %s scene.xml width height outdir [threads] [--scene-only | --spp N | --paths N]\n", argv[0]);
+        fprintf(stderr, "usage: %s scene.xml width height outdir [threads] [--scene-only | --spp N | --paths N] [--bounces N]\n", argv[0]);
         return 1;
+    }
+    for (int i = 5; i + 1 < argc; i++) {  // --bounces N may stand anywhere after outdir; the other options keep their places
+        if (strcmp(argv[i], "--bounces") != 0) continue;
+        g_bounces = atoi(argv[i + 1]);
+        if (g_bounces < 0 || g_bounces > 5) { fprintf(stderr, "--bounces outside 0..5\n"); return 1; }
+        for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+        argc -= 2;
+        break;
     }
     const char* xml = argv[1];
     int W = atoi(argv[2]), H = atoi(argv[3]);
@@ -501,8 +513,8 @@ int main(int argc, char** argv) {
     FILE* fp = fopen((out + "/stats.json").c_str(), "w");
     fprintf(fp,
             "{\"width\": %d, \"height\": %d, \"spp\": %d, \"threads\": %d, \"seconds\": %.6f, \"primary\": %lld, "
-            "\"primary_hits\": %lld, \"secondary\": %lld, \"shadow\": %lld}\n",
-            W, H, spp, threads, sec, (long long)W * H * (spp > 0 ? spp : 1), hits.load(), g_secondary.load(), g_shadow.load());
+            "\"primary_hits\": %lld, \"secondary\": %lld, \"shadow\": %lld, \"bounces\": %d}\n",
+            W, H, spp, threads, sec, (long long)W * H * (spp > 0 ? spp : 1), hits.load(), g_secondary.load(), g_shadow.load(), g_bounces);
     fclose(fp);
     printf("recipe %s %dx%d: %.3f s, hits %lld, secondary %lld, shadow %lld\n", gi ? "P" : spp > 0 ? "S" : "W", W, H, sec, hits.load(),
            g_secondary.load(), g_shadow.load());

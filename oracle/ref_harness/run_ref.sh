@@ -3,6 +3,7 @@
 # Authoring container only. The reference's XMLs carry the author's absolute
 # macOS paths: a path-remapped COPY is written under oracle/_ref/.
 #   usage: run_ref.sh <scene path relative to SceneFiles> <W> <H> <tag> [threads] [spp] [paths]   (spp: recipe S; "paths": recipe P)
+#   BOUNCES=N in the environment: the bounceCount of the root Shade() calls (--bounces N of ref_render; 5 without it)
 set -e
 REF=${REF:-/root/reference}
 HERE=$(cd "$(dirname "$0")/../.." && pwd)
@@ -19,4 +20,4 @@ case "$1" in
 esac
 MODE=""
 if [ -n "$6" ]; then if [ -n "$7" ]; then MODE="--paths $6"; else MODE="--spp $6"; fi; fi
-"$HERE/oracle/_ref/ref_render" "$OUT/scene.xml" "$2" "$3" "$OUT" "${5:-8}" $MODE | tail -1
+"$HERE/oracle/_ref/ref_render" "$OUT/scene.xml" "$2" "$3" "$OUT" "${5:-8}" $MODE ${BOUNCES:+--bounces $BOUNCES} | tail -1

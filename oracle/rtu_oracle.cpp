@@ -376,6 +376,11 @@ bool tri_hit(Ctx& cx, const RtuMesh& mesh, const Ray& ray, Hit& h, uint32_t face
 // triangle test would accept (a ray clipping a box corner within rounding), so that tests can aim at them.
 static bool g_all_triangles = false;
 
+// Test hook (rtu_oracle_debug_max_bounce): the bounceCount every root Shade() call receives — the pixel's (RenderFunctions.cpp:134-135)
+// and, in recipe P, those of every gather bounce (:569-570). The reference passes 5; the device takes it per frame
+// (RtuFrameDesc.max_bounce). Set between renders only: the render threads read it.
+static int g_max_bounce = RTU_MAX_BOUNCE;
+
 // TriObj::IntersectRay (objFunctions.cpp:333-406)
 bool mesh_hit(Ctx& cx, const RtuMesh& mesh, const Ray& ray, Hit& h) {
     bool hitResult = false;
@@ -788,8 +793,8 @@ C3 monte_carlo(Ctx& cx, const Hit& hInfo, int bounces, uint32_t key, const Light
             C3 indirect = monte_carlo(cx, h, bounces - 1, hkey, scene_lights);  // :568
             RtuLight amb = ambient_light(indirect);
             LightSet mc = {&amb, 1};
-            c += shade_node(cx, h, sampleRay, RTU_MAX_BOUNCE, child_key(hkey, SLOT_AMBIENT_TREE), mc);  // :569
-            c += shade_node(cx, h, sampleRay, RTU_MAX_BOUNCE, hkey, scene_lights);                        // :570
+            c += shade_node(cx, h, sampleRay, g_max_bounce, child_key(hkey, SLOT_AMBIENT_TREE), mc);  // :569
+            c += shade_node(cx, h, sampleRay, g_max_bounce, hkey, scene_lights);                        // :570
         } else {
             c += env_sample(*cx.s, sampleRay.dir);  // :575
         }
@@ -897,7 +902,7 @@ void render_rows(const RtuSceneDesc* s, const CamFrame& cf, int W, int H, std::a
                     C3 c;
                     if (hit) {
                         cx.st.primary_hits++;
-                        c = shade_node(cx, h, ray, RTU_MAX_BOUNCE, 0, scene_lights);  // :134-135
+                        c = shade_node(cx, h, ray, g_max_bounce, 0, scene_lights);  // :134-135
                     } else {
                         c = background_sample(*s, x, y);  // RenderFunctions.cpp:145
                     }
@@ -950,10 +955,10 @@ void render_rows(const RtuSceneDesc* s, const CamFrame& cf, int W, int H, std::a
                             C3 indirect = monte_carlo(cx, h, RTU_GI_BOUNCES, key, scene_lights);
                             RtuLight amb = ambient_light(indirect);
                             LightSet mc = {&amb, 1};
-                            c = shade_node(cx, h, ray, RTU_MAX_BOUNCE, child_key(key, SLOT_AMBIENT_TREE), mc);  // :134
-                            c += shade_node(cx, h, ray, RTU_MAX_BOUNCE, key, scene_lights);                     // :135
+                            c = shade_node(cx, h, ray, g_max_bounce, child_key(key, SLOT_AMBIENT_TREE), mc);  // :134
+                            c += shade_node(cx, h, ray, g_max_bounce, key, scene_lights);                     // :135
                         } else {
-                            c = shade_node(cx, h, ray, RTU_MAX_BOUNCE, key, scene_lights);  // :135
+                            c = shade_node(cx, h, ray, g_max_bounce, key, scene_lights);  // :135
                         }
                     } else {
                         c = background_sample(*s, x, y);  // :145
@@ -1346,6 +1351,12 @@ uint32_t rtu_oracle_sample_key(uint32_t pixel, uint32_t sample) { return sample_
 uint32_t rtu_oracle_child_key(uint32_t key, uint32_t slot) { return child_key(key, slot); }
 
 void rtu_oracle_debug_all_triangles(int on) { g_all_triangles = on != 0; }
+
+int rtu_oracle_debug_max_bounce(int max_bounce) {
+    const int prev = g_max_bounce;
+    if (max_bounce >= 0 && max_bounce <= RTU_MAX_BOUNCE) g_max_bounce = max_bounce;
+    return prev;
+}
 
 int rtu_oracle_render_scheduled(const RtuSceneDesc* scene, int width, int height, float* rgbz_out, RtuOracleStats* stats, int threads,
                                 int per_pixel_schedule) {

@@ -70,6 +70,9 @@ int  rtu_oracle_render_adaptive(const RtuSceneDesc* scene, int width, int height
                                 uint8_t* counts_out, float* margin_out, RtuOracleStats* stats, int threads);
 /* Test hook: 1 = test every triangle of a mesh whatever its boxes say (NOT the reference's algorithm; see rtu_oracle.cpp). */
 void rtu_oracle_debug_all_triangles(int on);
+/* Test hook: the bounceCount the root Shade() calls of every later render receive (0..RTU_MAX_BOUNCE; the reference's 5 until set;
+ * a value outside the range changes nothing). Returns the previous value. Not to be called while a render runs. */
+int  rtu_oracle_debug_max_bounce(int max_bounce);
 void rtu_oracle_portable_sincos(const float* t, int n, float* sin_out, float* cos_out);
 void rtu_oracle_portable_acos(const float* x, int n, float* out);
 uint32_t rtu_oracle_rand31(uint32_t key, uint32_t idx);

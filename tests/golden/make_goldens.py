@@ -15,6 +15,10 @@ SURVEY.md §8c; "recipe S" for the scenes with stochastic effects) and stores DA
   meta.json       resolution, ray counters, sha256 of the full float z / rgb /
                   8-bit buffers
 
+`make_goldens.py bounces` (or `bounces:<tag>`) writes <tag>/bounce<k>.npz for the depths of BOUNCES: the same scene through
+the same binary with the root Shade() calls given bounceCount k instead of 5 (ref_render --bounces k). A fixture reuses the
+tag's scene.rtus.gz and holds z, rgb (float32), the two 8-bit images and the counters primary_hits, secondary, shadow.
+
 `make_goldens.py SceneFiles` copies the reference's scene files that the loader tests read (tests/test_host.py,
 tests/test_oracle.py) to tests/golden/SceneFiles/: every scene XML and the meshes they name, .obj files gzipped;
 for the PNG textures only the filter type of each row and which texture of a golden blob holds their pixels
@@ -34,15 +38,17 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 RUN = os.path.join(REPO, "oracle", "ref_harness", "run_ref.sh")
 
 CONFIGS = [
-    # tag, scene (relative to SceneFiles), W, H, keep full floats
+    # tag, scene (relative to SceneFiles), W, H, keep full floats[, spp (0: recipe W)[, "P" for recipe P[, depths]]]
+    # depths: recursion depths other than the reference's 5 (RtuFrameDesc.max_bounce) that get a bounce<k>.npz next to golden.npz.
+    # Between them every depth 0..4 has a recipe W fixture on a plain and on a textured scene, and recipe S has one.
     ("p1_256", "Project1Example.xml", 256, 256, True),
     ("p3s_800x600", "Project3Simple.xml", 800, 600, True),
     ("p4_1080", "Project4.xml", 1920, 1080, False),
     ("teapot2_1080", "Teapot/scene2.xml", 1920, 1080, False),
     ("p11_1080", "Project11/scene.xml", 1920, 1080, False),
     # small versions of the 1080p configs so CPU-only tests stay fast
-    ("p4_240x135", "Project4.xml", 240, 135, True),
-    ("teapot2_240x135", "Teapot/scene2.xml", 240, 135, True),
+    ("p4_240x135", "Project4.xml", 240, 135, True, 0, None, (0, 1, 2, 3, 4)),
+    ("teapot2_240x135", "Teapot/scene2.xml", 240, 135, True, 0, None, (1, 3)),
     ("p11_240x135", "Project11/scene.xml", 240, 135, True),
     # the reference's other deterministic, untextured scenes, as extra regression inputs
     ("p1test_200x150", "Project1Test.xml", 200, 150, True),
@@ -51,16 +57,16 @@ CONFIGS = [
     ("p5_200x150", "Project5/scene.xml", 200, 150, True),
     ("p5low_200x150", "Project5/scene-low.xml", 200, 150, True),
     ("p11simple_200x150", "Project11/scene_simple.xml", 200, 150, True),
-    ("p13_200x150", "Project13/scene.xml", 200, 150, True),
+    ("p13_200x150", "Project13/scene.xml", 200, 150, True, 0, None, (2, 4)),
     # a resolution no other fixture renders this scene at (tests/test_oracle.py test_oracle_vs_live_reference_build)
     ("p5_176x132", "Project5/scene.xml", 176, 132, True),
     # textures ("next" row f2): checkerboards, two 1024x1024 PNGs (mesh diffuse, background, environment)
-    ("p7_200x150", "Project7/scene.xml", 200, 150, True),
+    ("p7_200x150", "Project7/scene.xml", 200, 150, True, 0, None, (1, 3)),
     # stochastic effects ("next" row f1), recipe S: the 7th field is samples per pixel. The reference is built
     # with rand() wrapped to the sequential sample stream (oracle/ref_harness/Makefile), so these are
     # reproducible: glossy reflection + refraction + a size-5 light + textures; depth of field + textures;
     # glossy reflections + a size-5 light; twelve size-1 lights + glossy refraction; the teapot under a size-5 light
-    ("p10_s4_160x120", "Project10/scene.xml", 160, 120, True, 4),
+    ("p10_s4_160x120", "Project10/scene.xml", 160, 120, True, 4, None, (2,)),
     ("p9_s3_160x120", "Project9/scene.xml", 160, 120, True, 3),
     ("p11gs_s2_160x90", "Project11/scene_glossy_soft.xml", 160, 90, True, 2),
     ("p11x86_s1_120x90", "Project11/scene_86.xml", 120, 90, True, 1),
@@ -69,7 +75,7 @@ CONFIGS = [
     ("p11g_s2_160x90", "Project11/scene_glossy.xml", 160, 90, True, 2),
     # row f3: an .obj that brings its own materials (usemtl / .mtl -> MultiMtl, xmlload.cpp:199-243) — a scene written for
     # this repository (tests/scenes/multimtl, "@" = repository path), run through the compiled reference like the others
-    ("mtl_160x120", "@tests/scenes/multimtl/scene.xml", 160, 120, True),
+    ("mtl_160x120", "@tests/scenes/multimtl/scene.xml", 160, 120, True, 0, None, (0, 1, 2, 3, 4)),
     # exact ties by the thousand (tests/scenes/ties): a torus pressed flat, three coincident grids lying in a `plane` object under
     # both node orders — which of the triangles (or the plane) with bitwise-equal t wins is the reference's test order
     ("ties_160x120", "@tests/scenes/ties/scene.xml", 160, 120, True),
@@ -77,6 +83,9 @@ CONFIGS = [
     ("p11_p2_120x68", "Project11/scene.xml", 120, 68, True, 2, "P"),
     ("p13_p2_96x72", "Project13/scene.xml", 96, 72, True, 2, "P"),
 ]
+
+# tag -> the depths of its bounce<k>.npz fixtures (the 8th field of a config)
+BOUNCES = {c[0]: c[7] for c in CONFIGS if len(c) > 7}
 
 
 # the files the scene XMLs name (absolute macOS paths, remapped to the copy by the tests); Teapot/ink*.png do not exist
@@ -138,8 +147,62 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def save_npz(path, arrays):
+    """An .npz (numpy.load reads it like any other) whose members are LZMA-compressed instead of deflated: a bounce<k>.npz may
+    not be larger than its tag's golden.npz, and one whose image equals the depth-5 image carries three counters more."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w") as zf:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.save(buf, np.asarray(arrays[name], order="C"))
+            small = len(buf.getvalue()) < 1024
+            zf.writestr(zipfile.ZipInfo(name + ".npy", (1980, 1, 1, 0, 0, 0)), buf.getvalue(),
+                        zipfile.ZIP_STORED if small else zipfile.ZIP_LZMA)
+
+
+def make_bounces(only):
+    """<tag>/bounce<k>.npz for BOUNCES (only: the tags asked for, empty = all)."""
+    for cfg in CONFIGS:
+        tag, scene, W, H = cfg[:4]
+        spp = cfg[5] if len(cfg) > 5 else 0
+        if tag not in BOUNCES or (only and tag not in only):
+            continue
+        assert not (len(cfg) > 6 and cfg[6] == "P"), "MonteCarlo()'s own Shade calls keep their 5: no recipe P fixture at another depth"
+        scene_arg = os.path.join(REPO, scene[1:]) if scene.startswith("@") else scene
+        dst = os.path.join(HERE, tag)
+        blob = gzip.open(os.path.join(dst, "scene.rtus.gz")).read()
+        for k in BOUNCES[tag]:
+            run = "%s_bounce%d" % (tag, k)
+            subprocess.check_call([RUN, scene_arg, str(W), str(H), run, "8"] + ([str(spp)] if spp else []), env=dict(os.environ, BOUNCES=str(k)))
+            src = os.path.join(REPO, "oracle", "_ref", "out", run)
+            assert open(os.path.join(src, "scene.rtus"), "rb").read() == blob, "the fixture's scene is not the tag's scene.rtus.gz"
+            stats = json.load(open(os.path.join(src, "stats.json")))
+            assert stats["bounces"] == k and stats["spp"] == spp
+            arrays = {
+                "z": np.fromfile(os.path.join(src, "z.f32"), np.float32).reshape(H, W),
+                "rgb": np.fromfile(os.path.join(src, "rgb.f32"), np.float32).reshape(H, W, 3),
+                "result_u8": np.fromfile(os.path.join(src, "result.u8"), np.uint8).reshape(H, W, 3),
+                "zbuffer_u8": np.fromfile(os.path.join(src, "zbuffer.u8"), np.uint8).reshape(H, W),
+            }
+            for name in ("primary_hits", "secondary", "shadow"):
+                arrays[name] = np.int64(stats[name])
+            out = os.path.join(dst, "bounce%d.npz" % k)
+            save_npz(out, arrays)
+            size, limit = os.path.getsize(out), os.path.getsize(os.path.join(dst, "golden.npz"))
+            assert size <= limit, "%s: %d bytes, golden.npz has %d" % (out, size, limit)
+            print(run, stats["primary_hits"], stats["secondary"], stats["shadow"], size, "bytes")
+            shutil.rmtree(src)
+
+
 def main():
     only = set(sys.argv[1:])
+    bounce_tags = {a.split(":", 1)[1] for a in only if a.startswith("bounces:")}
+    if "bounces" in only or bounce_tags:
+        make_bounces(bounce_tags)
+        only = {a for a in only if a != "bounces" and not a.startswith("bounces:")}
+        if not only:
+            return
     if "SceneFiles" in only:
         copy_scene_files()
         only.discard("SceneFiles")
