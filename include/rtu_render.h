@@ -358,6 +358,44 @@ int  rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t
  * NULL frame, width or height < 1, rows outside the image, NULL rays_out with nrows > 0. */
 int  rtu_camera_rays(const RtuFrameDesc* frame, int row0, int nrows, RtuRay* rays_out);
 
+/* ---- Ray batches: radiance along caller-supplied rays (raytracer-utah_amd/csrc/render_rays_impl.h) -----------------------------------
+ * What a render gives a pinhole camera's pixels, for any ray: a panoramic, fisheye or orthographic sensor, an environment probe, a
+ * light-map bake, a re-shade of chosen pixels. Per ray one float4 {r, g, b, t}, linear, like a render's pixel:
+ *   hit      the ray is traced as by rtu_trace_rays — Trace(ray) with HitInfo::Init's z replaced by tmax, dir used exactly as given —;
+ *            rgb = Shade(ray, hInfo, lights, max_bounce) of the hit node's material (MtlBlinn::Shade, mtlFunctions.cpp:115-291: shadow
+ *            rays, refraction / Fresnel / mirror recursion, textures: the hit carries uvw), t = hInfo.z. A node without a material gives
+ *            white, as in a render. The stale-z sphere of rtu_trace_rays (t = tmax) is a hit and is shaded as the reference would.
+ *   miss     rgb = environment.SampleEnvironment(dir), t = tmax: what the reference does for every ray that is not a pixel (a reflected
+ *            or refracted ray that leaves the scene, mtlFunctions.cpp:250, :267, :289). The background is a function of the pixel, and
+ *            a ray has none.
+ *   invalid  (the rule of the ray queries above) {0, 0, 0, 0}, not traced. t == 0 means nothing else: a valid ray has tmax > 0.
+ * eye is the `camera.pos` of Shade()'s view vector (mtlFunctions.cpp:137) for the root call AND every bounce, as the reference's single
+ * camera is: the rays of rtu_camera_rays shaded with eye = cam_pos give rtu_render_frame's rgb at every hit pixel and its z at every
+ * pixel, bit for bit (a miss pixel of a render shows the background instead). One eye per call.
+ * flags: 0, or RTU_QUERY_REFERENCE_WALK for the counting variant (collect_stats = 1 of a frame: the reference's tree, every Shade() call
+ * a frame); the output is the same, bit for bit. max_bounce as RtuFrameDesc.max_bounce (0 where no material recurses).
+ * A scene with stochastic features is refused (RTU_ERR_STOCHASTIC) as a samples == 0 frame is: sampled recipes are not supported.
+ * Errors: RTU_ERR_ARG for a NULL pointer with n > 0 (or a NULL descriptor), a device pointer that is not 16-byte aligned, an unknown flag
+ * bit, non-zero reserved, max_bounce outside 0 .. RTU_MAX_BOUNCE, a non-finite eye, n > 2^26 in the device form; RTU_ERR_NO_SCENE before
+ * rtu_upload_scene. n == 0 is RTU_OK and launches nothing.
+ * THIS CALL IS A RENDER, unlike the ray queries: it uses the context's frame records, append counters and launch hints (under a key of
+ * its own), and the ONE STREAM PER CONTEXT rule of rtu_render_frame_device applies. The _device form reads n RtuRay from and writes n
+ * float4 to DEVICE memory and is asynchronous on hip_stream; rtu_frame_status afterwards as for a frame — RTU_ERR_CAPACITY: call it
+ * again —, rtu_get_stats after a RTU_QUERY_REFERENCE_WALK call as after a counting render. The host form copies through grow-only
+ * buffers of the context in chunks of at most 2^20 rays, checks capacity and repeats a chunk itself, and is synchronous; stats non-NULL
+ * selects the counting variant, the counters summed over the chunks (of camera rays: the RtuStats of the frame).
+ * rtu_debug_flags 64 and 2048, rtu_debug_node_bounds, rtu_debug_walk_stack_limit and rtu_debug_tail_from apply as to a render and change
+ * no bit. The touched-bytes mode (collect_stats == 2) does not exist for ray batches. */
+typedef struct RtuShadeDesc {      /* 32 B */
+    float    eye[3];      /* the `camera.pos` of MtlBlinn::Shade's view vector (mtlFunctions.cpp:137), for the root call and every bounce */
+    int32_t  max_bounce;  /* bounceCount of the root Shade() calls, 0 .. RTU_MAX_BOUNCE; as RtuFrameDesc.max_bounce */
+    uint32_t flags;       /* 0, or RTU_QUERY_REFERENCE_WALK: the counting variant (the reference's tree, every call a frame) */
+    uint32_t reserved[3]; /* must be 0 */
+} RtuShadeDesc;
+int  rtu_shade_defaults(RtuShadeDesc* out);   /* eye 0, max_bounce 5, flags 0; pure host code */
+int  rtu_shade_rays_device(RtuContext* ctx, const void* d_rays, size_t n, const RtuShadeDesc* desc, void* d_rgbt, void* hip_stream);
+int  rtu_shade_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

@@ -153,7 +153,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_debug_device_allocations", "rtu_progressive_begin", "rtu_progressive_advance", "rtu_progressive_status",
                "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes",
                "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing",
-               "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays"]
+               "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays",
+               "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -285,6 +286,26 @@ _sig(hip, "rtu_occluded_rays_device", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint
 _sig(hip, "rtu_trace_rays", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P)
 _sig(hip, "rtu_occluded_rays", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P)
 _sig(hip, "rtu_camera_rays", _I, ctypes.POINTER(RtuFrameDesc), _I, _I, _P)
+
+
+class RtuShadeDesc(ctypes.Structure):
+    """include/rtu_render.h RtuShadeDesc (32 bytes): how a ray batch is shaded."""
+    _fields_ = [("eye", ctypes.c_float * 3), ("max_bounce", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+_sig(hip, "rtu_shade_defaults", _I, ctypes.POINTER(RtuShadeDesc))
+_sig(hip, "rtu_shade_rays_device", _I, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
+_sig(hip, "rtu_shade_rays", _I, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
+
+
+def shade_desc(eye=(0.0, 0.0, 0.0), max_bounce=5, reference_walk=False):
+    """An RtuShadeDesc: rtu_shade_defaults, then the eye, the depth and the counting variant's flag."""
+    d = RtuShadeDesc()
+    hip.rtu_shade_defaults(ctypes.byref(d))
+    d.eye[:] = [float(x) for x in eye]
+    d.max_bounce = max_bounce
+    d.flags = RTU_QUERY_REFERENCE_WALK if reference_walk else 0
+    return d
 
 
 def ray_dtype():
@@ -874,6 +895,25 @@ class Context:
         data_ptr()), asynchronous on `stream`. flags (an integer) overrides reference_walk."""
         f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
         self._check(hip.rtu_trace_rays_device(self._h, d_rays_ptr, n, f, d_hits_ptr, stream))
+
+    def shade_rays(self, rays, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+        """Radiance along caller-supplied rays (rtu_shade_rays): rays as for trace_rays; eye is the camera position of Shade()'s view
+        vector. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None): a hit is shaded like a render's pixel, a miss is the
+        environment along the ray with t = tmax, an invalid ray is four zeros. desc (an RtuShadeDesc) overrides the other options."""
+        import numpy as np
+        r = _as_rays(rays)
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        out = np.zeros((r.size, 4), np.float32)
+        st = RtuStats() if stats else None
+        self._check(hip.rtu_shade_rays(self._h, r.ctypes.data if r.size else None, r.size, ctypes.byref(d), out.ctypes.data if r.size else None,
+                                       ctypes.byref(st) if stats else None))
+        return out, (st.as_dict() if stats else None)
+
+    def shade_rays_device(self, d_rays_ptr, n, eye, d_rgbt_ptr, stream=None, max_bounce=5, reference_walk=False, desc=None):
+        """rtu_shade_rays_device: n RtuRay at d_rays_ptr -> n float4 {r, g, b, t} at d_rgbt_ptr (device memory, 16-byte aligned),
+        asynchronous on `stream`; frame_status() afterwards as for render_device (RTU_ERR_CAPACITY: call it again)."""
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        self._check(hip.rtu_shade_rays_device(self._h, d_rays_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
 
     def occluded_device(self, d_rays_ptr, n, d_occluded_ptr, stream=None, reference_walk=False, flags=None):
         """rtu_occluded_rays_device: n RtuRay at d_rays_ptr -> n bytes (1 / 0) at d_occluded_ptr, asynchronous on `stream`."""

@@ -1851,7 +1851,9 @@ int launch_all(const KernelArgs& a, uint32_t n_tiles, bool stats, hipStream_t st
     const uint32_t pcap = a.pgrid ? a.pgrid : 32768u;
     const dim3 gridP(blocksP), gridPF(blocksP < pcap ? blocksP : pcap);
     if (CNTD) stats = false;  // the touched-bytes instantiations are the fast variant's (the reference-counting kernels are not built for them)
-    if (mode == RTU_LAUNCH_SHADE) {
+    if (mode == RTU_LAUNCH_LEVELS) {
+        // a ray batch: its roots are level-0 frames already queued on this stream (k_ray_roots, render_rays_impl.h)
+    } else if (mode == RTU_LAUNCH_SHADE) {
         RTU_LAUNCH(RTU_TL_GI_ROOTS, (k_gi_roots<TEX>), gridN, block, a, (stats || (a.dbg & 2048u)) ? 0 : 1);  // (rtu_debug_flags 2048: no inline shading — results must not change)
     } else if (stats) {
         if constexpr (!CNTD) hipLaunchKernelGGL((k_primary_counting<STACK, TEX>), gridP, dim3(256), 0, stream, a, n_tiles);

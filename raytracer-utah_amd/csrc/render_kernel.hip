@@ -421,6 +421,15 @@ int rtu_launch_frame(const KernelArgs& args, uint32_t n_tiles, uint32_t bvh_stac
     }
 }
 
+int rtu_launch_rays0(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream, const LaunchProbe* probe);
+int rtu_launch_rays1(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream, const LaunchProbe* probe);
+
+int rtu_launch_ray_batch(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream, const LaunchProbe* probe) {
+    if (args.sampling || args.frame_batch) return (int)hipErrorInvalidValue;  // feature sets 0 and 1 only
+    return args.scene.textured ? rtu_launch_rays1(args, rays, n, bvh_stack_needed, stats, stream, probe)
+                               : rtu_launch_rays0(args, rays, n, bvh_stack_needed, stats, stream, probe);
+}
+
 int rtu_launch_gi_final(const KernelArgs& args, hipStream_t stream) {
     hipLaunchKernelGGL(k_gi_final, dim3((args.gi_total + 255u) / 256u), dim3(256), 0, stream, args);
     return (int)hipGetLastError();

@@ -133,6 +133,7 @@ struct RtuContext {
     int4* node_rects = nullptr;              // [RTU_MAX_FRAME_BATCH][n_nodes] screen rectangles of the node-level bounds (k_node_rects); owned by the scene
     DevBuf<float4>  q_rays, q_hits;          // ray queries, host forms (rtu_trace_rays / rtu_occluded_rays): one chunk of rays and of answers
     DevBuf<uint8_t> q_occ;
+    DevBuf<float4>  sh_rays, sh_out;         // ray batches, host form (rtu_shade_rays): one chunk of rays and of {r, g, b, t}
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -1126,12 +1127,16 @@ float halton(int index, int base) {
 // gi_mode RTU_LAUNCH_CHAIN / RTU_LAUNCH_SHADE: one step of recipe P at chain depth gi_depth (render_sampled).
 // adaptive: a launch of an adaptive frame (hint keys of its own: its shape changes every batch); act_list / act_n: the active-tile list
 // its primary phase walks (KernelArgs::act_list), nullptr for every tile (act_n then only keys the hints).
+// d_rays / n_rays: a RAY BATCH (rtu_shade_rays): the roots are the Shade() calls of n_rays caller-supplied rays in device memory, d_out has
+// one float4 per ray; `frame` carries the eye (cam_pos), max_bounce and collect_stats (0 / 1) of a recipe-W frame and no camera. A
+// "tile" is a chunk of 64 rays (k_ray_roots): no screen rectangles, coverage masks or tile occupancy, no side mode, hint keys of its own.
 int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, int sample_index = 0, int batch = 1,
            const RtuFrameDesc* frames_batch = nullptr, int gi_mode = RTU_LAUNCH_ALL, int gi_depth = 0, bool adaptive = false,
-           const uint4* act_list = nullptr, uint32_t act_n = 0) {
+           const uint4* act_list = nullptr, uint32_t act_n = 0, const float4* d_rays = nullptr, uint32_t n_rays = 0) {
+    const bool rays = d_rays != nullptr;
     uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
     uint32_t bands = (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
-    uint32_t n_tiles = tiles_x * bands * (uint32_t)batch;
+    uint32_t n_tiles = rays ? (n_rays + 63u) / 64u : tiles_x * bands * (uint32_t)batch;
     uint32_t pixels = (uint32_t)rtu_shard_rows(frame) * (uint32_t)frame->width;
     const bool gi = gi_mode != RTU_LAUNCH_ALL;
     // recipe P: every chain hit is the root of two Shade() trees
@@ -1172,7 +1177,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     a.scene.dbg = ctx->dbg;
     a.counters = stats ? ctx->counters.get() : nullptr;
     a.host_launches = stats == 2 ? ctx->slot_launches : nullptr;
-    a.node_rects = (stats != 1 && frame->samples == 0 && ctx->dscene.node_bounds) ? ctx->node_rects : nullptr;
+    a.node_rects = (stats != 1 && frame->samples == 0 && ctx->dscene.node_bounds && !rays) ? ctx->node_rects : nullptr;  // (a ray has no pixel)
     if (a.node_rects && (ctx->dscene.n_cover + ctx->dscene.n_pcover) && !gi && ((size_t)((frame->width + 7) / 8) * (size_t)((frame->height + 7) / 8) + 31u) / 32u <= 12288u) {  // (the mask has to fit k_mesh_cover's LDS copy)
         a.tiles_xf = (uint32_t)((frame->width + 7) / 8);
         a.cover_words = (a.tiles_xf * (uint32_t)((frame->height + 7) / 8) + 31u) / 32u;
@@ -1204,7 +1209,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     // so that a batch learns from batches of about its size and the maps stay small)
     const uint32_t act_tiles = act_n ? act_n * (uint32_t)batch : n_tiles;
     const uint64_t tail_key = adaptive ? ((uint64_t)(32 - __builtin_clz(act_tiles | 1u)) << 8) | (uint64_t)(16 | 2 | (gi ? 8 : 0))
-                                       : ((uint64_t)n_tiles << 8) | (uint64_t)((frame->samples ? 2 : 0) | (frames_batch ? 4 : 0) | (gi ? 8 : 0));
+                                       : ((uint64_t)n_tiles << 8) | (uint64_t)((frame->samples ? 2 : 0) | (frames_batch ? 4 : 0) | (gi ? 8 : 0) | (rays ? 32 : 0));  // (32: a ray batch and a frame of as many tiles teach each other nothing)
     int hint = RTU_MAX_LEVELS;
     bool forced = false;
     if (ctx->tail_hint != 0) { hint = ctx->tail_hint; ctx->tail_hint = 0; forced = true; }
@@ -1268,7 +1273,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     // this shape deferred enough primary rays for the one-lane-per-ray stage 2 (a first launch, or a short list: the old order).
     ctx->last_side = false;
     const uint32_t thr0 = (uint32_t)(frame->coop_threshold > 0 ? frame->coop_threshold : 70000);
-    if (stats != 1 && !gi && frame->samples == 0 && ctx->n_meshes > 0 && ctx->mesh_hits_childless && !ctx->stamp_next && !(ctx->dbg & (8192u | 2048u | 64u)) &&
+    if (stats != 1 && !gi && !rays && frame->samples == 0 && ctx->n_meshes > 0 && ctx->mesh_hits_childless && !ctx->stamp_next && !(ctx->dbg & (8192u | 2048u | 64u)) &&
         ctx->dscene.node_bounds && ctx->dscene.lmask &&  // (the occluder lists are what settles a mesh hit's shadow rays inline)
         !ctx->side_off.count(tail_key) && ctx->list_hints.count(tail_key) && ctx->list_hints[tail_key][0] - 1u > thr0 &&
         ctx->side_frames.count(tail_key) && ctx->side_frames[tail_key] <= 256u) {
@@ -1318,7 +1323,8 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         if (e0 != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e0));
         return RTU_OK;
     }
-    hipError_t e = (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
+    hipError_t e = rays ? (hipError_t)rtu_launch_ray_batch(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr)
+                        : (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
     if (probing && probe_recorded) ctx->probe_used++;
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     return RTU_OK;
@@ -3284,6 +3290,86 @@ int rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t 
     const int rc = query_args(ctx, h_rays, h_occluded, n, flags, false);
     if (rc != RTU_OK || n == 0) return rc;
     return query_host(ctx, h_rays, n, flags, nullptr, h_occluded);
+}
+
+// ---- ray batches: Shade() along caller-supplied rays (render_rays_impl.h) -------------------------------------------------------
+namespace {
+// the checks both forms share, then the frame descriptor launch() takes for a ray batch: no camera, the eye in cam_pos
+int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, const RtuShadeDesc* d, bool device, RtuFrameDesc* f) {
+    if (!d) return fail(ctx, RTU_ERR_ARG, "shade descriptor is NULL");
+    if (d->flags & ~RTU_QUERY_REFERENCE_WALK) return fail(ctx, RTU_ERR_ARG, "unknown shade flag bits 0x%x", d->flags & ~RTU_QUERY_REFERENCE_WALK);
+    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(ctx, RTU_ERR_ARG, "RtuShadeDesc.reserved must be 0");
+    if (d->max_bounce < 0 || d->max_bounce > RTU_MAX_BOUNCE) return fail(ctx, RTU_ERR_ARG, "max_bounce out of range");
+    if (!std::isfinite(d->eye[0]) || !std::isfinite(d->eye[1]) || !std::isfinite(d->eye[2])) return fail(ctx, RTU_ERR_ARG, "eye is not finite");
+    if (n && (!rays || !out)) return fail(ctx, RTU_ERR_ARG, "rays / result pointer is NULL");
+    if (device && n && (((uintptr_t)rays & 15u) || ((uintptr_t)out & 15u)))
+        return fail(ctx, RTU_ERR_ARG, "device ray / result buffers must be 16-byte aligned");
+    if (device && n > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "more than 2^26 rays in one call");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (ctx->scene_stochastic)
+        return fail(ctx, RTU_ERR_STOCHASTIC, "the scene has %s: ray batches are recipe W (sampled recipes are not supported)", ctx->stochastic_what.c_str());
+    memset(f, 0, sizeof *f);
+    f->width = 64;  // (launch() sizes a ray batch from n; these only have to be a valid frame)
+    f->height = 1;
+    f->shard_count = 1;
+    f->max_bounce = d->max_bounce;
+    f->collect_stats = (d->flags & RTU_QUERY_REFERENCE_WALK) ? 1 : 0;
+    memcpy(f->cam_pos, d->eye, sizeof f->cam_pos);
+    return RTU_OK;
+}
+}  // namespace
+
+static_assert(sizeof(RtuShadeDesc) == 32, "RtuShadeDesc is 32 bytes");
+
+int rtu_shade_defaults(RtuShadeDesc* out) {
+    if (!out) return RTU_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    out->max_bounce = RTU_MAX_BOUNCE;
+    return RTU_OK;
+}
+
+int rtu_shade_rays_device(RtuContext* ctx, const void* d_rays, size_t n, const RtuShadeDesc* desc, void* d_rgbt, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    const int rc = shade_args(ctx, d_rays, d_rgbt, n, desc, true, &f);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    return launch(ctx, &f, (float4*)d_rgbt, (hipStream_t)hip_stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, (const float4*)d_rays, (uint32_t)n);
+}
+
+int rtu_shade_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f);
+    if (rc != RTU_OK) return rc;
+    if (stats) { memset(stats, 0, sizeof *stats); f.collect_stats = 1; }
+    if (n == 0) return RTU_OK;
+    const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->sh_rays.grow(2 * chunk));
+    RTU_HIP(ctx, ctx->sh_out.grow(chunk));
+    for (size_t done = 0; done < n; done += chunk) {
+        const size_t m = n - done < chunk ? n - done : chunk;
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
+        for (int attempt = 0;; attempt++) {  // as rtu_render_frame: a chunk that ran out of frame capacity is shaded again
+            rc = launch(ctx, &f, ctx->sh_out.get(), ctx->stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, ctx->sh_rays.get(), (uint32_t)m);
+            if (rc != RTU_OK) return rc;
+            RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            bool overflow = false;
+            if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
+            if (!overflow) break;
+            if (attempt >= 2 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+        }
+        RTU_HIP(ctx, hipMemcpy(h_rgbt + 4 * done, ctx->sh_out.get(), sizeof(float4) * m, hipMemcpyDeviceToHost));
+        if (stats) {  // the counters are zeroed per launch: the batch's are the sum over its chunks
+            RtuStats part;
+            if ((rc = rtu_get_stats(ctx, &part)) != RTU_OK) return rc;
+            unsigned long long* to = reinterpret_cast<unsigned long long*>(stats);
+            const unsigned long long* from = reinterpret_cast<const unsigned long long*>(&part);
+            for (size_t k = 0; k < sizeof(RtuStats) / sizeof(unsigned long long); k++) to[k] += from[k];
+        }
+    }
+    return RTU_OK;
 }
 
 // the primary rays of primary_pixel (render_impl.h; RenderFunctions.cpp:258-268, :97) for the pixel centres of rows [row0, row0 + nrows):

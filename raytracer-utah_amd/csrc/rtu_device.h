@@ -366,10 +366,12 @@ struct KernelArgs {
 // Enqueue one frame (primary pass, then per level: trace, consume; then combine
 // bottom-up) on `stream`. Returns hipError_t as int.
 // mode: RTU_LAUNCH_ALL; recipe P: RTU_LAUNCH_CHAIN (trace the chain's ray of depth gi_depth, no shading),
-// RTU_LAUNCH_SHADE (the two Shade() trees of every chain hit of depth gi_depth)
+// RTU_LAUNCH_SHADE (the two Shade() trees of every chain hit of depth gi_depth); a ray batch: RTU_LAUNCH_LEVELS (the level-0
+// frames are already queued on this stream — k_ray_roots, render_rays_impl.h —: the recursion levels only)
 #define RTU_LAUNCH_ALL   0
 #define RTU_LAUNCH_CHAIN 1
 #define RTU_LAUNCH_SHADE 2
+#define RTU_LAUNCH_LEVELS 3
 #define RTU_GI_BOUNCES   4   // monteCarloBounces, RenderFunctions.cpp:31
 // stats: 0 the fast variant, 1 the reference-counting variant (RtuStats), 2 the fast variant in touched-bytes mode (RtuTouched;
 // recipe W only). probe (may be NULL): bracket the launch in timeline slot `slot` with the two HIP events.
@@ -382,6 +384,10 @@ struct LaunchProbe {
 int rtu_launch_frame(const KernelArgs& args, uint32_t n_tiles, uint32_t bvh_stack_needed, int stats, hipStream_t stream, int mode = RTU_LAUNCH_ALL,
                      const LaunchProbe* probe = nullptr);
 int rtu_launch_gi_final(const KernelArgs& args, hipStream_t stream);
+// A ray batch (rtu_shade_rays): the root Shade() calls of n RtuRay (two float4 each, 16-byte aligned) into args.out[0 .. n), then the
+// recursion levels. args as for a frame of recipe W with frame.cam_pos = the eye; stats: the reference-counting variant.
+int rtu_launch_ray_batch(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream,
+                         const LaunchProbe* probe = nullptr);
 
 // recipe S: add one sample's image to the accumulators / write the mean
 int rtu_launch_accumulate(const float4* samples, uint32_t batch, float4* acc, uint32_t* hits, uint32_t pixels, bool first, hipStream_t stream);

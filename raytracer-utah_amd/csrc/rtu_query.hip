@@ -24,16 +24,7 @@ namespace {
 // three wavefronts per SIMD, as the stage-2 walks (RTU_OCC_WALK): the 12 KB LDS stack allows 13 workgroups per CU
 #define RTU_OCC_QUERY __attribute__((amdgpu_waves_per_eu(3, 3)))
 
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// rtu_render.h "Invalid rays": every component finite, tmax > 0, |dot(dir, dir) - 1| <= 2e-3 (binary32, dot3's order)
-__device__ __forceinline__ bool ray_valid(const float4& a, const float4& b) {
-    const bool fin = finite_bits(a.x) && finite_bits(a.y) && finite_bits(a.z) && finite_bits(a.w) && finite_bits(b.x) && finite_bits(b.y) &&
-                     finite_bits(b.z);
-    const float dd = dot3(mk3(b.x, b.y, b.z), mk3(b.x, b.y, b.z));
-    return fin && a.w > 0.0f && !(fabsf(dd - 1.0f) > 2e-3f);
-}
-
+// (ray_valid: rtu_query.h)
 template <bool REFWALK, bool SHADOW>
 __device__ __forceinline__ bool query_trace(const DevScene& s, const float4& a, const float4& b, Hit& h, uint32_t* stk) {
     Ray ray;

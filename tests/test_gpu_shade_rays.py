@@ -1,0 +1,514 @@
+"""Ray batches (rtu_shade_rays / rtu_shade_rays_device, include/rtu_render.h) against the renders and the oracle.
+
+The oracle has no ray-level entry, so it is reached through cameras, as for the ray queries: the pixel-centre rays of a camera
+(rtu_camera_rays) shaded with eye = that camera's position must give the render's rgb and z bit for bit, and meet the oracle's
+image of that camera within the project's bar (z bit-exact, linear RGB relative error <= 2e-5, 8-bit +-1: check_against). A miss
+is the environment along the ray where a render shows the background, so colours are compared at hit rays and misses are checked
+against the texture arithmetic on their own."""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from test_gpu_parity import check_against
+from test_gpu_ray_query import BIG, REGIONS, CAM_RES, bits, frame_of, lights, materials, random_cameras, set_camera
+from test_light_lists import RtuLight
+from test_mesh_update_host import clone, deformed_scene
+
+pytestmark = pytest.mark.gpu
+
+TAGS = ["p1_256", "p4_240x135", "teapot2_240x135", "p13_200x150", "ties_160x120", "mtl_160x120", "p7_200x150"]
+RTU_SHARDS = 64  # raytracer-utah_amd/csrc/rtu_device.h
+
+
+def same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def eye_of(frame):
+    return tuple(frame.cam_pos)
+
+
+def against_oracle(out, cpu, orc):
+    """t bit-exact at every ray; the hit set within the project's bar (the colours of the misses are taken from the oracle's
+    image, so check_against compares the hits alone). Returns the hit mask."""
+    cpu = cpu.reshape(-1, 4)
+    hit = cpu[:, 3] != BIG
+    img = cpu.copy()
+    img[:, 3] = out[:, 3]
+    img[hit, :3] = out[hit, :3]
+    check_against(img.reshape(1, -1, 4), cpu.reshape(1, -1, 4), orc)
+    return hit
+
+
+@pytest.fixture(scope="module")
+def ctx(pkg):
+    c = pkg.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def cam(pkg, orc, golden, ctx):
+    """Per golden tag, computed once and left unchanged: the scene, its camera's frame and rays, the fast variant's shade of them
+    (eye = the camera, max_bounce 5), the oracle's image and counters. The shared context holds some other scene afterwards."""
+    cache = {}
+
+    def get(tag):
+        if tag not in cache:
+            g = golden(tag)
+            scene = g.scene(pkg)
+            ctx.upload(scene)
+            frame = frame_of(pkg, scene, g.width, g.height)
+            rays = pkg.camera_rays(frame)
+            out = ctx.shade_rays(rays, eye_of(frame))[0]
+            cpu, cstats = orc.render(scene, g.width, g.height, threads=8)
+            for a in (rays, out, cpu):
+                a.setflags(write=False)
+            cache[tag] = SimpleNamespace(scene=scene, frame=frame, rays=rays, eye=eye_of(frame), out=out, cpu=cpu, cstats=cstats,
+                                         hit=cpu[..., 3].reshape(-1) != BIG)
+        return cache[tag]
+    return get
+
+
+# ---- 1. camera rays equal the render and the oracle ------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", TAGS)
+def test_camera_rays_equal_the_render_and_the_oracle(pkg, orc, ctx, cam, tag):
+    c = cam(tag)
+    ctx.upload(c.scene)
+    render = ctx.render(c.frame)[0].reshape(-1, 4)
+    cpu = c.cpu.reshape(-1, 4)
+    print("%s: %d rays, %d hit" % (tag, c.rays.size, int(c.hit.sum())))
+    assert c.hit.sum() > 1000
+
+    def check(out, what):
+        tbad = int((bits(out[:, 3]) != bits(cpu[:, 3])).sum())
+        rbad = int((bits(out[c.hit, :3]) != bits(render[c.hit, :3])).any(axis=1).sum())
+        print("%s %s: t differs from the oracle's z at %d rays, rgb from the render's at %d hit rays" % (tag, what, tbad, rbad))
+        assert tbad == 0 and rbad == 0
+        assert np.array_equal(bits(out[:, 3]), bits(render[:, 3]))
+        assert np.array_equal(against_oracle(out, cpu, orc), c.hit)
+
+    check(c.out, "fast")
+    ref = ctx.shade_rays(c.rays, c.eye, reference_walk=True)[0]
+    check(ref, "reference walk")
+    assert same_bytes(ref, c.out), "the counting variant's output differs from the fast variant's"
+    ref2, stats = ctx.shade_rays(c.rays, c.eye, reference_walk=True, stats=True)
+    assert same_bytes(ref2, c.out)
+    assert stats == c.cstats, "counters of the batch differ from the oracle's of the frame: %s vs %s" % (stats, c.cstats)
+
+
+# ---- 2. misses -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", ["p7_200x150", "teapot2_240x135"])
+def test_a_miss_is_the_environment_along_the_ray(pkg, ctx, cam, tag):
+    c = cam(tag)
+    ctx.upload(c.scene)
+    miss = ~c.hit
+    assert miss.sum() > 1000
+    d = c.scene.desc
+    colour = np.array(list(d.environment.color), np.float32)
+    dirs = np.ascontiguousarray(c.rays["dir"][miss])
+    if d.environment.has_map and not d.environment.map_is_null and d.environment_map.present:
+        uvw = ctx.texcoords(pkg.TEXOP_ENV_UVW, dirs)
+        want = colour[None, :] * ctx.texcoords(pkg.TEXOP_MAP, uvw, -2)       # TexturedColor::Sample: color * map->Sample(uvw)
+        assert len(np.unique(want, axis=0)) > 100                            # a picture, not a constant
+    elif d.environment.has_map:
+        want = np.broadcast_to(colour * np.float32(0), dirs.shape)           # TextureMap(NULL): colour * black
+    else:
+        want = np.broadcast_to(colour, dirs.shape)
+    assert (tag == "p7_200x150") == bool(d.environment.has_map and not d.environment.map_is_null)
+    assert same_bytes(c.out[miss, :3], np.ascontiguousarray(want, np.float32))
+    assert np.all(c.out[miss, 3] == BIG) and np.array_equal(bits(c.out[miss, 3]), bits(c.rays["tmax"][miss]))
+
+
+def test_a_miss_without_an_environment_map_is_the_environment_colour(pkg, ctx, cam):
+    c = cam("mtl_160x120")  # environment 0.2 without a map, background (0.1, 0.15, 0.3): the two cannot be confused
+    d = c.scene.desc
+    assert not d.environment.has_map and list(d.environment.color) != list(d.background.color)
+    miss = ~c.hit
+    assert miss.sum() > 1000
+    assert same_bytes(c.out[miss, :3], np.broadcast_to(np.array(list(d.environment.color), np.float32), (int(miss.sum()), 3)))
+    assert np.all(c.out[miss, 3] == BIG)
+
+
+# ---- 3. depth --------------------------------------------------------------------------------------------------------------------
+def test_every_max_bounce_equals_the_render_at_that_depth(pkg, ctx, cam):
+    c = cam("p4_240x135")
+    assert c.hit.all()  # a closed room: every ray is a hit, so the whole output is the render's
+    ctx.upload(c.scene)
+    images = []
+    for k in range(6):
+        f = pkg.frame_setup(c.scene.desc.camera, c.frame.width, c.frame.height, max_bounce=k)
+        render = ctx.render(f)[0].reshape(-1, 4)
+        out = ctx.shade_rays(c.rays, c.eye, max_bounce=k)[0]
+        bad = int((bits(out) != bits(render)).any(axis=1).sum())
+        print("max_bounce %d: %d of %d rays differ from the render" % (k, bad, len(out)))
+        assert bad == 0
+        images.append(out)
+    assert same_bytes(images[5], c.out)
+    assert all(not same_bytes(images[k], images[k + 1]) for k in range(3))  # the depth does reach the recursion
+
+
+# ---- 4. switches -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", ["teapot2_240x135", "ties_160x120", "p4_240x135"])
+def test_switches_change_no_bit(pkg, ctx, cam, tag):
+    c = cam(tag)
+    ctx.upload(c.scene)
+    hip, h = pkg.hip, ctx._h
+    try:
+        for flag in (64, 2048):
+            assert hip.rtu_debug_flags(h, flag) == pkg.RTU_OK
+            assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out), "rtu_debug_flags %d" % flag
+        assert hip.rtu_debug_flags(h, 0) == pkg.RTU_OK
+        for level in range(1, 7):
+            assert hip.rtu_debug_tail_from(h, level) == pkg.RTU_OK
+            assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out), "rtu_debug_tail_from %d" % level
+        assert hip.rtu_debug_node_bounds(h, 0) == pkg.RTU_OK
+        assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out), "rtu_debug_node_bounds(0)"
+        ctx.upload(c.scene)  # (the two scene hooks last until the next upload)
+        assert hip.rtu_debug_walk_stack_limit(h, 3) == pkg.RTU_OK
+        assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out), "rtu_debug_walk_stack_limit(3)"
+    finally:
+        hip.rtu_debug_flags(h, 0)
+        ctx.upload(c.scene)
+
+
+# ---- 5. a buffer no image has ----------------------------------------------------------------------------------------------------
+def scrambled(c):
+    """The camera rays permuted (fixed seed), every seventh repeated, an invalid ray of each kind in turn after every hundredth:
+    (rays, source pixel per ray or -1 for an invalid one)."""
+    rng = np.random.RandomState(20261018)
+    perm = rng.permutation(c.rays.size)
+    idx, kind = [], []
+    kinds = 0
+    for j, p in enumerate(perm):
+        idx.append(p)
+        kind.append(-1)
+        if j % 7 == 6:
+            idx.append(p)
+            kind.append(-1)
+        if j % 100 == 99:
+            idx.append(p)
+            kind.append(kinds % 8)
+            kinds += 1
+    idx, kind = np.array(idx, np.int64), np.array(kind, np.int64)
+    rays = c.rays[idx].copy()
+    nan, inf = np.float32("nan"), np.float32("inf")
+    rays["org"][kind % 4 == 0, 1] = nan                                    # NaN
+    rays["dir"][(kind >= 0) & (kind % 4 == 1), 0] = inf                    # infinite
+    rays["tmax"][kind == 2] = np.float32(0.0)                              # tmax <= 0
+    rays["tmax"][kind == 6] = np.float32(-3.0)
+    rays["dir"][(kind >= 0) & (kind % 4 == 3)] *= np.float32(1.5)          # dir not of unit length
+    return rays, np.where(kind < 0, idx, -1)
+
+
+@pytest.mark.parametrize("tag", ["p4_240x135", "mtl_160x120"])
+def test_a_scrambled_buffer_with_invalid_rays(pkg, ctx, cam, tag):
+    c = cam(tag)
+    ctx.upload(c.scene)
+    rays, src = scrambled(c)
+    valid = src >= 0
+    assert (~valid).sum() >= 4 * 40 and rays.size > c.rays.size * 8 // 7
+    want = np.zeros((rays.size, 4), np.float32)
+    want[valid] = c.out[src[valid]]
+    for ref in (False, True):
+        out = ctx.shade_rays(rays, c.eye, reference_walk=ref)[0]
+        assert not out[~valid].view(np.uint8).any(), "an invalid ray must give sixteen zero bytes"
+        bad = int((bits(out) != bits(want)).any(axis=1).sum())
+        print("%s ref=%s: %d rays (%d invalid), %d differ from their pixel's bytes" % (tag, ref, rays.size, int((~valid).sum()), bad))
+        assert bad == 0
+    for n in (1, 63, 64, 65, 4097, 64 * RTU_SHARDS + 1):
+        # (from an offset where the prefix holds repeated and invalid rays)
+        sub = rays[300:300 + n]
+        assert sub.size == n and (n < 200 or (src[300:300 + n] < 0).any())
+        assert same_bytes(ctx.shade_rays(sub, c.eye)[0], want[300:300 + n]), n
+        assert same_bytes(ctx.shade_rays(rays[:n], c.eye)[0], want[:n]), n
+
+
+# ---- 6. rays no camera of the call's eye fires -----------------------------------------------------------------------------------
+def without_specular(pkg, scene):
+    s = clone(pkg, scene)
+    for m in range(s.desc.n_materials):
+        mt = materials(s)[m]
+        mt.specular[0] = mt.specular[1] = mt.specular[2] = 0.0
+    return s
+
+
+@pytest.mark.parametrize("tag", sorted(REGIONS))
+def test_rays_from_elsewhere_than_the_eye(pkg, orc, ctx, cam, tag):
+    """24 cameras all over the scene. Without specular colours Shade()'s view vector cannot reach a colour, so the rays of camera k
+    shaded with the GOLDEN camera's eye must still be the oracle's image of camera k; with them, the same rays need their own eye
+    — and on p4 the golden's eye must then give another colour somewhere, or the eye is not plumbed."""
+    c = cam(tag)
+    dull = without_specular(pkg, c.scene)
+    cams = random_cameras(tag)
+    batches = []
+    for pos, target, fov in cams:
+        views = []
+        for scene in (dull, c.scene):
+            s = clone(pkg, scene)
+            set_camera(s, pos, target, fov=fov)
+            views.append((frame_of(pkg, s, CAM_RES, CAM_RES), orc.render(s, CAM_RES, CAM_RES, threads=4)[0]))
+        batches.append(views)
+    hits = 0
+    ctx.upload(dull)
+    for (frame, cpu), _ in batches:
+        out = ctx.shade_rays(pkg.camera_rays(frame), c.eye)[0]  # the golden's eye, not the rays' origin
+        hits += int(against_oracle(out, cpu, orc).sum())
+    print("%s without specular: %d hit rays of %d" % (tag, hits, len(cams) * CAM_RES * CAM_RES))
+    assert hits > 1000
+    ctx.upload(c.scene)
+    hits, eye_matters = 0, 0
+    for _, (frame, cpu) in batches:
+        rays = pkg.camera_rays(frame)
+        out = ctx.shade_rays(rays, eye_of(frame))[0]  # one call per camera: its own eye
+        hit = against_oracle(out, cpu, orc)
+        hits += int(hit.sum())
+        other = ctx.shade_rays(rays, c.eye)[0]
+        assert np.array_equal(bits(other[:, 3]), bits(out[:, 3]))
+        eye_matters += int((bits(other[hit, :3]) != bits(out[hit, :3])).any(axis=1).sum())
+    print("%s: %d hit rays, %d whose colour depends on the eye" % (tag, hits, eye_matters))
+    assert hits > 1000
+    if tag == "p4_240x135":
+        assert eye_matters > 0, "the eye does not reach Shade()'s view vector"
+
+
+# ---- 7. tmax ---------------------------------------------------------------------------------------------------------------------
+def test_tmax_cuts_the_ray(pkg, ctx, cam):
+    c = cam("p4_240x135")
+    ctx.upload(c.scene)
+    z = c.out[:, 3]
+    assert c.hit.all() and np.all(z > 0)
+    short, far = c.rays.copy(), c.rays.copy()
+    short["tmax"] = z * np.float32(0.5)
+    far["tmax"] = z * np.float32(2.0)
+    env = np.array(list(c.scene.desc.environment.color), np.float32)
+    assert not c.scene.desc.environment.has_map
+    for ref in (False, True):
+        s = ctx.shade_rays(short, c.eye, reference_walk=ref)[0]
+        assert np.array_equal(bits(s[:, 3]), bits(short["tmax"])), "a miss answers t = tmax"
+        assert same_bytes(s[:, :3], np.broadcast_to(env, (len(s), 3)))
+        assert same_bytes(ctx.shade_rays(far, c.eye, reference_walk=ref)[0], c.out)
+
+
+# ---- 8. capacity -----------------------------------------------------------------------------------------------------------------
+GLASSROOM = """<xml><scene>
+  <object type="sphere" name="room" material="wall"><scale value="60"/></object>
+  <object type="sphere" name="ball" material="glassmirror"><scale value="9"/><translate x="0" y="0" z="0"/></object>
+  <material type="blinn" name="wall"><diffuse r="0.7" g="0.6" b="0.5"/><specular value="0.2"/><glossiness value="10"/></material>
+  <material type="blinn" name="glassmirror"><diffuse r="0.1" g="0.1" b="0.1"/><specular value="0.8"/><glossiness value="60"/>
+    <reflection value="0.4"/><refraction index="1.4" value="0.7"/></material>
+  <light type="ambient" name="a"><intensity value="0.3"/></light>
+  <light type="point" name="p"><intensity value="0.8"/><position x="10" y="-20" z="25"/></light>
+</scene><camera><position x="0" y="-14" z="0"/><target x="0" y="0" z="0"/><up x="0" y="0" z="1"/><fov value="70"/>
+  <width value="128"/><height value="96"/></camera></xml>"""
+
+
+def test_capacity_overflow_is_reported_and_repaired(pkg, orc, tmp_path):
+    """The glass-and-mirror ball in a room: up to three child frames per ray, and a fresh context provisions one."""
+    import torch
+    xml = tmp_path / "glassroom.xml"
+    xml.write_text(GLASSROOM)
+    scene = pkg.Scene.from_xml(str(xml))
+    W, H = 128, 96
+    cpu = orc.render(scene, W, H, threads=4)[0]
+    frame = pkg.frame_setup(scene.desc.camera, W, H)
+    rays = pkg.camera_rays(frame)
+    c = pkg.Context(0)  # a fresh context: nothing learned, nothing grown
+    try:
+        c.upload(scene)
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays).view(np.uint8).copy()).to("cuda:0")
+        d_out = torch.zeros(rays.size * 4, dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        c.shade_rays_device(d_rays.data_ptr(), rays.size, eye_of(frame), d_out.data_ptr())
+        with pytest.raises(pkg.RtuError) as e:
+            c.frame_status()
+        assert e.value.code == pkg.RTU_ERR_CAPACITY  # it did overflow: otherwise nothing is tested
+        for attempt in range(8):  # every report grows the capacity of at least one more recursion level
+            c.shade_rays_device(d_rays.data_ptr(), rays.size, eye_of(frame), d_out.data_ptr())
+            try:
+                c.frame_status()
+                break
+            except pkg.RtuError as err:
+                assert err.code == pkg.RTU_ERR_CAPACITY
+        else:
+            raise AssertionError("capacity never sufficed")
+        print("the device form succeeded at repeat %d" % (attempt + 1))
+        dev = d_out.cpu().numpy().reshape(-1, 4)
+        assert against_oracle(dev, cpu, orc).sum() > 1000
+        frames, _ = c.frame_counts()
+        assert max(frames[1:]) > W * H, frames  # more child frames than rays in some level
+    finally:
+        c.close()
+    c2 = pkg.Context(0)  # the host form on another fresh context: repairs itself
+    try:
+        c2.upload(scene)
+        host = c2.shade_rays(rays, eye_of(frame))[0]
+        c2.frame_status()
+        against_oracle(host, cpu, orc)
+        assert same_bytes(host, dev)
+    finally:
+        c2.close()
+
+
+# ---- 9. neighbours ---------------------------------------------------------------------------------------------------------------
+def test_renders_and_shades_leave_each_other_alone(pkg, cam):
+    c = cam("teapot2_240x135")
+    small = pkg.frame_setup(c.scene.desc.camera, 96, 64)
+    ctx = pkg.Context(0)
+    try:
+        ctx.upload(c.scene)
+        before = ctx.render(c.frame)[0]
+        assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out)
+        assert same_bytes(ctx.render(c.frame)[0], before)
+        a0 = None
+        for k in range(5):
+            assert same_bytes(ctx.shade_rays(c.rays[:20001], c.eye)[0], c.out[:20001])
+            ctx.render(small)
+            if k == 0:
+                a0 = pkg.hip.rtu_debug_device_allocations()
+        assert pkg.hip.rtu_debug_device_allocations() == a0
+        assert same_bytes(ctx.render(c.frame)[0], before)
+    finally:
+        ctx.close()
+
+
+def test_shades_follow_scene_updates(pkg, cam):
+    c = cam("teapot2_240x135")
+
+    def fresh(scene):
+        f = pkg.Context(0)
+        try:
+            f.upload(scene)
+            return f.shade_rays(c.rays, c.eye)[0]
+        finally:
+            f.close()
+    ctx = pkg.Context(0)
+    try:
+        ctx.upload(c.scene)
+        assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out)
+        relit = clone(pkg, c.scene)
+        assert lights(relit)[1].type == 1  # the direct light: turned
+        l = RtuLight.from_buffer_copy(bytes(lights(relit)[1]))
+        l.vec[0], l.vec[1], l.vec[2] = l.vec[0] + 0.5, l.vec[1] - 0.25, l.vec[2]
+        relit.set_light(1, l)
+        ctx.update(relit)
+        out1 = ctx.shade_rays(c.rays, c.eye)[0]
+        assert not same_bytes(out1, c.out)
+        assert same_bytes(out1, fresh(relit))
+        twisted = deformed_scene(pkg, relit, 0, ("twist", 120))
+        ctx.update_meshes(twisted, [0])
+        out2 = ctx.shade_rays(c.rays, c.eye)[0]
+        assert not same_bytes(out2, out1)
+        assert same_bytes(out2, fresh(twisted))
+    finally:
+        ctx.close()
+
+
+def test_the_device_form_on_a_callers_stream_equals_the_host_form(pkg, ctx, cam):
+    import torch
+    c = cam("p4_240x135")
+    ctx.upload(c.scene)
+    stream = torch.cuda.Stream(device=0)
+    d_rays = torch.from_numpy(np.ascontiguousarray(c.rays).view(np.uint8).copy()).to("cuda:0")
+    d_out = torch.full((c.rays.size * 4,), 7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    for ref in (False, True):
+        for attempt in range(8):
+            ctx.shade_rays_device(d_rays.data_ptr(), c.rays.size, c.eye, d_out.data_ptr(), stream.cuda_stream, reference_walk=ref)
+            try:
+                ctx.frame_status()
+                break
+            except pkg.RtuError as err:
+                assert err.code == pkg.RTU_ERR_CAPACITY
+        else:
+            raise AssertionError("capacity never sufficed")
+        assert same_bytes(d_out.cpu().numpy().reshape(-1, 4), c.out)
+        if ref:  # rtu_get_stats works as after a counting render
+            st = pkg.RtuStats()
+            assert pkg.hip.rtu_get_stats(ctx._h, ctypes.byref(st)) == pkg.RTU_OK
+            assert st.as_dict() == c.cstats
+        d_out.fill_(7.0)
+        torch.cuda.synchronize()
+
+
+def test_an_open_progressive_session_is_not_disturbed(pkg, ctx, cam):
+    c = cam("p4_240x135")
+    ctx.upload(c.scene)
+    f = pkg.frame_setup(c.scene.desc.camera, 96, 54, samples=4)
+    p = ctx.progressive(f)
+    try:
+        p.advance(2)
+        snap0, _ = p.snapshot()
+        assert same_bytes(ctx.shade_rays(c.rays, c.eye)[0], c.out)
+        snap1, _ = p.snapshot()
+        assert same_bytes(snap0, snap1)
+        assert p.status()[0] == 2
+    finally:
+        p.close()
+
+
+# ---- 10. errors ------------------------------------------------------------------------------------------------------------------
+def test_errors(pkg, golden, cam):
+    c = cam("teapot2_240x135")
+    hip = pkg.hip
+    r = np.ascontiguousarray(c.rays[:8])
+    out = np.zeros((8, 4), np.float32)
+    ctx = pkg.Context(0)
+    try:
+        h = ctx._h
+        ok = pkg.shade_desc(c.eye)
+
+        def host(desc, rays=r.ctypes.data, o=out.ctypes.data, n=8):
+            rc = hip.rtu_shade_rays(h, rays, n, ctypes.byref(desc) if desc is not None else None, o, None)
+            ctx.frame_status()  # clean afterwards
+            return rc
+
+        def device(desc, rays=4096, o=8192, n=8):  # (every case below is refused before a pointer is read)
+            rc = hip.rtu_shade_rays_device(h, rays, n, ctypes.byref(desc) if desc is not None else None, o, None)
+            ctx.frame_status()
+            return rc
+        assert host(ok) == pkg.RTU_ERR_NO_SCENE and device(ok) == pkg.RTU_ERR_NO_SCENE
+        stochastic = golden("p10_s4_160x120").scene(pkg)
+        ctx.upload(stochastic)
+        assert host(ok) == pkg.RTU_ERR_STOCHASTIC and device(ok) == pkg.RTU_ERR_STOCHASTIC
+        ctx.upload(c.scene)
+        assert host(ok) == pkg.RTU_OK
+        assert same_bytes(out, c.out[:8])
+        # n == 0: fine, whatever the pointers, and nothing is launched
+        counts = ctx.frame_counts()
+        assert host(ok, None, None, 0) == pkg.RTU_OK and device(ok, None, None, 0) == pkg.RTU_OK
+        assert ctx.frame_counts() == counts
+        assert ctx.shade_rays(c.rays[:0], c.eye)[0].shape == (0, 4)
+        # NULL pointers with n > 0
+        assert host(ok, None) == pkg.RTU_ERR_ARG and host(ok, o=None) == pkg.RTU_ERR_ARG and host(None) == pkg.RTU_ERR_ARG
+        assert device(ok, None) == pkg.RTU_ERR_ARG and device(ok, o=None) == pkg.RTU_ERR_ARG and device(None) == pkg.RTU_ERR_ARG
+        # device pointers that are not 16-byte aligned
+        assert device(ok, rays=4096 + 8) == pkg.RTU_ERR_ARG and device(ok, o=8192 + 4) == pkg.RTU_ERR_ARG
+        # n > 2^26 in the device form
+        assert device(ok, n=(1 << 26) + 1) == pkg.RTU_ERR_ARG
+        for flags in (2, 4, 0x80000000, 3):
+            d = pkg.shade_desc(c.eye)
+            d.flags = flags
+            assert host(d) == pkg.RTU_ERR_ARG and device(d) == pkg.RTU_ERR_ARG
+        for k in range(3):
+            d = pkg.shade_desc(c.eye)
+            d.reserved[k] = 1
+            assert host(d) == pkg.RTU_ERR_ARG and device(d) == pkg.RTU_ERR_ARG
+        for mb in (-1, 6, 1 << 30):
+            d = pkg.shade_desc(c.eye)
+            d.max_bounce = mb
+            assert host(d) == pkg.RTU_ERR_ARG and device(d) == pkg.RTU_ERR_ARG
+        for k, v in ((0, float("nan")), (1, float("inf")), (2, float("-inf"))):
+            d = pkg.shade_desc(c.eye)
+            d.eye[k] = v
+            assert host(d) == pkg.RTU_ERR_ARG and device(d) == pkg.RTU_ERR_ARG
+        assert hip.rtu_shade_rays(None, r.ctypes.data, 8, ctypes.byref(ok), out.ctypes.data, None) == pkg.RTU_ERR_ARG
+        with pytest.raises(pkg.RtuError):
+            ctx.shade_rays_device(None, 8, c.eye, None)
+        # the context still works
+        assert host(ok) == pkg.RTU_OK and same_bytes(out, c.out[:8])
+    finally:
+        ctx.close()

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Time of a ray batch (rtu_shade_rays_device) against the render of the same camera, one JSON line: the 1920x1080 camera rays of
+teapot2_1080 and p4_1080, in image order and shuffled, shaded with eye = the camera; and rtu_render_frame_device of that camera as a
+single frame, in the same run. Each figure is the median over `reps` launches, every launch bracketed by HIP events on one stream,
+after `warmup` launches that are not counted (they also settle the frame capacities and launch hints: rtu_frame_status after each).
+The ray form has no tile occupancy, no screen rectangles and no two-stage walk: on the teapot, where most of the image is background,
+it is expected to be slower than the render. p4, where every ray has work and the recursion is real, is the honest comparison.
+
+usage: tools/shade_rays_bench.py [--reps 20] [--warmup 3] [--out profiles/r09_shade_rays.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+TAGS = ["teapot2_1080", "p4_1080"]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import __graft_entry__ as g
+    from conftest import Golden
+    pkg = g.load_package()
+    ctx = pkg.Context(0)
+    stream = torch.cuda.Stream(device=0)
+
+    def timed(launch):
+        """Median / min / max ms of `reps` launches after `warmup` launches; every launch must be complete (rtu_frame_status)."""
+        for _ in range(args.warmup + 8):  # (a capacity report repeats the launch: at most one per recursion level)
+            launch()
+            try:
+                ctx.frame_status()
+            except pkg.RtuError as err:
+                if err.code != pkg.RTU_ERR_CAPACITY:
+                    raise
+        ms = []
+        for _ in range(args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            launch()
+            e1.record(stream)
+            e1.synchronize()
+            ctx.frame_status()  # raises if a timed launch was incomplete
+            ms.append(e0.elapsed_time(e1))
+        return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
+
+    out = {"tool": "shade_rays_bench", "reps": args.reps, "warmup": args.warmup, "device": pkg.device_info(0)["name"], "scenes": []}
+    for tag in TAGS:
+        gd = Golden(tag)
+        scene = gd.scene(pkg)
+        W, H = gd.width, gd.height
+        ctx.upload(scene)
+        frame = pkg.frame_setup(scene.desc.camera, W, H)
+        eye = tuple(frame.cam_pos)
+        rays = pkg.camera_rays(frame)
+        n = rays.size
+        d_out = torch.zeros(n * 4, dtype=torch.float32, device="cuda:0")
+        row = {"scene": tag, "width": W, "height": H, "rays": int(n), "shade_rays": {}}
+        render = timed(lambda: ctx.render_device(frame, d_out.data_ptr(), stream.cuda_stream))
+        render["mrays_per_s"] = n / render["median_ms"] / 1e3
+        row["render_frame"] = render
+        image = d_out.cpu().numpy().reshape(-1, 4).copy()
+        hit = image[:, 3] != np.float32(1.0e30)
+        for oname, order in (("image", np.arange(n)), ("shuffled", np.random.RandomState(1).permutation(n))):
+            d_rays = torch.from_numpy(np.ascontiguousarray(rays[order]).view(np.uint8).copy()).to("cuda:0")
+            t = timed(lambda: ctx.shade_rays_device(d_rays.data_ptr(), n, eye, d_out.data_ptr(), stream.cuda_stream))
+            got = d_out.cpu().numpy().reshape(-1, 4)
+            want = image[order]
+            h = hit[order]
+            # what is timed is the render's answer: t at every ray, rgb at every hit ray, bit for bit
+            t["equals_render"] = bool(np.array_equal(got[:, 3].view(np.uint32), want[:, 3].view(np.uint32)) and
+                                      np.array_equal(got[h, :3].view(np.uint32), want[h, :3].view(np.uint32)))
+            t["mrays_per_s"] = n / t["median_ms"] / 1e3
+            t["ratio_to_render"] = t["median_ms"] / render["median_ms"]
+            row["shade_rays"][oname] = t
+            del d_rays
+        row["hit_rays"] = int(hit.sum())
+        out["scenes"].append(row)
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
