@@ -268,3 +268,57 @@ def check_portable(fn, first, count, seed=0, threads=8):
     fb = (ctypes.c_uint32 * 2)()
     n = lib.rtu_oracle_check_portable(fn, first, count, seed, threads, fb)
     return int(n), (int(fb[0]), int(fb[1]))
+
+
+# the ray-level entry (rtu_oracle_rays): layouts of RtuRay / RtuRayHit (include/rtu_render.h), as the package's ray_dtype() / hit_dtype()
+RAYS_CLOSEST, RAYS_OCCLUDED, RAYS_SHADE = 0, 1, 2
+RAY_HIT, RAY_FRONT = 1, 2
+RAY_DTYPE = np.dtype([("org", np.float32, 3), ("tmax", np.float32), ("dir", np.float32, 3), ("reserved", np.uint32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("node", np.int32), ("flags", np.uint32), ("material", np.int32),
+                      ("p", np.float32, 3), ("pad0", np.float32), ("N", np.float32, 3), ("pad1", np.float32)])
+lib.rtu_oracle_rays.restype = ctypes.c_int
+lib.rtu_oracle_rays.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                ctypes.POINTER(OracleStats), ctypes.c_int]
+
+
+def _rays(scene, rays, mode, out, eye=None, stats=None, threads=1):
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: a structured array of the package's ray_dtype() or float32 [n, 8]")
+    r = np.ascontiguousarray(rays).reshape(-1).view(RAY_DTYPE)
+    assert len(out) == r.size
+    e = np.ascontiguousarray(eye, np.float32) if eye is not None else None
+    if e is not None and e.shape != (3,):
+        raise ValueError("eye: three floats")
+    rc = lib.rtu_oracle_rays(scene.desc_ptr, r.ctypes.data if r.size else None, r.size, e.ctypes.data if e is not None else None, mode,
+                             out.ctypes.data if r.size else None, ctypes.byref(stats) if stats is not None else None, threads)
+    if rc != 0:
+        raise OracleError(rc)
+    return out
+
+
+def _n_rays(rays):
+    rays = np.asarray(rays)
+    return rays.size if rays.dtype == RAY_DTYPE else len(rays)
+
+
+def trace_rays(scene, rays, threads=1):
+    """Trace() along caller-supplied rays, HitInfo::Init's z replaced by tmax, dir as given, nothing filtered (valid rays only): a
+    structured array [n] with the fields of RtuRayHit — what the device's rtu_trace_rays answers."""
+    return _rays(scene, rays, RAYS_CLOSEST, np.zeros(_n_rays(rays), HIT_DTYPE), threads=threads)
+
+
+def occluded_rays(scene, rays, threads=1):
+    """ShadowTrace() along the rays, then `hit && hInfo.z > 0`: uint8 [n] — what rtu_occluded_rays answers."""
+    return _rays(scene, rays, RAYS_OCCLUDED, np.zeros(_n_rays(rays), np.uint8), threads=threads)
+
+
+def shade_rays(scene, rays, eye, threads=1, max_bounce=MAX_BOUNCE):
+    """Trace() and Shade(..., max_bounce) along the rays with `eye` as camera.pos; a miss is the environment along dir with t = tmax:
+    (float32 [n, 4] {r, g, b, t}, stats dict) — what rtu_shade_rays answers."""
+    st = OracleStats()
+    out = np.zeros((_n_rays(rays), 4), np.float32)
+    with _bounces(max_bounce):
+        _rays(scene, rays, RAYS_SHADE, out, eye=eye, stats=st, threads=threads)
+    return out, st.as_dict()

@@ -1369,6 +1369,85 @@ int rtu_oracle_render(const RtuSceneDesc* scene, int width, int height, float* r
 }
 
 // Camera set-up alone, for checking the product's rtu_frame_setup (a3).
+// Ray-level entry: the functions a render calls per pixel, on caller-supplied rays (the counterpart of the device's rtu_trace_rays,
+// rtu_occluded_rays and rtu_shade_rays). Per ray HitInfo::Init's z is replaced by tmax and dir is used as given; nothing is filtered.
+//   CLOSEST   Trace(ray): the fields of RtuRayHit (include/rtu_render.h); a miss is {tmax, -1, 0, -1, p = N = 0}.
+//   OCCLUDED  ShadowTrace(ray), then GenLight::Shadow's conclusion `hit && hInfo.z > 0` (lightFunctions.cpp:27-37): one byte.
+//   SHADE     what the recipe W pixel loop does after it has its ray (RenderFunctions.cpp:103-135), with `eye` in place of camera.pos
+//             (read by Shade() at mtlFunctions.cpp:137 only) and, on a miss, environment.SampleEnvironment(dir) as for a bounce
+//             that leaves the scene (mtlFunctions.cpp:250): float4 {r, g, b, hInfo.z} and the counters.
+// Threads take contiguous chunks of rays with their own Ctx; the counters are summed at the end, as render_impl does.
+int rtu_oracle_rays(const RtuSceneDesc* scene, const RtuOracleRay* rays, long long n, const float* eye, int mode, void* out,
+                    RtuOracleStats* stats, int threads) {
+    int err = check_scene(scene, false);
+    if (err) return err;
+    if (mode < RTU_ORACLE_RAYS_CLOSEST || mode > RTU_ORACLE_RAYS_SHADE || n < 0 || (n && (!rays || !out))) return RTU_ORACLE_ERR_ARG;
+    if (mode == RTU_ORACLE_RAYS_SHADE && !eye) return RTU_ORACLE_ERR_ARG;
+    RtuSceneDesc local = *scene;  // shallow: only camera.pos differs
+    if (mode == RTU_ORACLE_RAYS_SHADE)
+        for (int k = 0; k < 3; k++) local.camera.pos[k] = eye[k];
+    if (threads < 1) threads = 1;
+    std::vector<RtuOracleStats> st(threads);
+    auto work = [&](int t, long long b, long long e) {
+        Ctx cx;
+        cx.s = &local;
+        cx.sequential = cx.libm_trig = false;
+        cx.seq_key = cx.seq_counter = 0;
+        cx.gather_rays = 0;
+        memset(&cx.st, 0, sizeof cx.st);
+        const LightSet scene_lights = {local.lights, local.n_lights};
+        for (long long i = b; i < e; i++) {
+            Ray ray;
+            ray.p = ld3(rays[i].org);
+            ray.dir = ld3(rays[i].dir);
+            Hit h = new_hit();
+            h.z = rays[i].tmax;
+            if (mode == RTU_ORACLE_RAYS_OCCLUDED) {
+                const bool hit = shadow_trace(cx, ray, 0, h);
+                ((uint8_t*)out)[i] = hit && h.z > 0.0 ? 1 : 0;
+            } else if (mode == RTU_ORACLE_RAYS_CLOSEST) {
+                const bool hit = trace(cx, ray, 0, h);
+                RtuOracleRayHit r;
+                memset(&r, 0, sizeof r);
+                r.t = h.z;
+                r.node = r.material = -1;
+                if (hit) {
+                    r.node = h.node;
+                    r.flags = RTU_ORACLE_RAY_HIT | (h.front ? RTU_ORACLE_RAY_FRONT : 0u);
+                    r.material = local.nodes[h.node].material_id;
+                    r.p[0] = h.p.x; r.p[1] = h.p.y; r.p[2] = h.p.z;
+                    r.N[0] = h.N.x; r.N[1] = h.N.y; r.N[2] = h.N.z;
+                }
+                ((RtuOracleRayHit*)out)[i] = r;
+            } else {
+                cx.st.primary_rays++;
+                C3 c;
+                if (trace(cx, ray, 0, h)) {
+                    cx.st.primary_hits++;
+                    c = shade_node(cx, h, ray, g_max_bounce, 0, scene_lights);
+                } else {
+                    c = env_sample(local, ray.dir);
+                }
+                float* o = (float*)out + 4 * i;
+                o[0] = c.r; o[1] = c.g; o[2] = c.b; o[3] = h.z;
+            }
+        }
+        st[t] = cx.st;
+    };
+    if (threads == 1) {
+        work(0, 0, n);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < threads; t++) th.emplace_back(work, t, n * t / threads, n * (t + 1) / threads);
+        for (auto& t : th) t.join();
+    }
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        for (auto& s : st) add_stats(*stats, s);
+    }
+    return 0;
+}
+
 int rtu_oracle_camera_frame(const RtuCamera* cam, int width, int height, float out12[12]) {
     if (!cam || !out12 || width <= 0 || height <= 0) return RTU_ORACLE_ERR_ARG;
     CamFrame f = camera_frame(*cam, width, height);

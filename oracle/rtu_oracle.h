@@ -2,6 +2,7 @@
  * rtu_oracle.h — C interface of the CPU restatement (oracle/rtu_oracle.cpp).
  * TEST INFRASTRUCTURE: see the header of rtu_oracle.cpp. Loaded only by tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg.
+ * Besides the renders of whole images there is one ray-level entry, rtu_oracle_rays: closest hit, occlusion and radiance along caller-supplied rays.
  */
 #ifndef RTU_ORACLE_H_INCLUDED
 #define RTU_ORACLE_H_INCLUDED
@@ -101,6 +102,23 @@ void rtu_oracle_host_libm(int fn, const float* in, long long n, float* out);
  * count - 1, for ATAN2F the pairs first .. first + count - 1 of a seeded generator (rtu_oracle.cpp atan2f_pair). Counts
  * results that differ (NaN equals NaN); first_bad[2] gets the lowest failing input (bits of x, or of y and x). */
 long long rtu_oracle_check_portable(int fn, uint64_t first, uint64_t count, uint64_t seed, int threads, uint32_t* first_bad);
+/* The ray-level entry: Trace / ShadowTrace / Shade on n caller-supplied rays, the counterpart of the device's rtu_trace_rays,
+ * rtu_occluded_rays and rtu_shade_rays (include/rtu_render.h; RtuOracleRay and RtuOracleRayHit have the layouts of RtuRay and
+ * RtuRayHit). Per ray HitInfo::Init's z is replaced by tmax and dir is used as given; NO ray is filtered: pass valid rays only.
+ * out: CLOSEST n RtuOracleRayHit (a miss: t = tmax, flags 0, node = material = -1, p = N = 0); OCCLUDED n bytes (`hit && hInfo.z > 0`);
+ * SHADE n float4 {r, g, b, hInfo.z} — a hit is Shade() at the depth of rtu_oracle_debug_max_bounce with `eye` (three floats, SHADE
+ * only) as camera.pos, a miss is environment.SampleEnvironment(dir) with z = tmax — and the counters in `stats` (may be NULL).
+ * Stochastic scenes are refused as by rtu_oracle_render_rows. */
+typedef struct RtuOracleRay    { float org[3]; float tmax; float dir[3]; uint32_t reserved; } RtuOracleRay;       /* 32 B */
+typedef struct RtuOracleRayHit { float t; int32_t node; uint32_t flags; int32_t material;
+                                 float p[3]; float pad0; float N[3]; float pad1; } RtuOracleRayHit;                /* 48 B */
+#define RTU_ORACLE_RAY_HIT       1u
+#define RTU_ORACLE_RAY_FRONT     2u
+#define RTU_ORACLE_RAYS_CLOSEST  0
+#define RTU_ORACLE_RAYS_OCCLUDED 1
+#define RTU_ORACLE_RAYS_SHADE    2
+int  rtu_oracle_rays(const RtuSceneDesc* scene, const RtuOracleRay* rays, long long n, const float* eye, int mode, void* out,
+                     RtuOracleStats* stats, int threads);
 /* pos, origin, u, v of the image plane (RenderFunctions.cpp:243-269). */
 int  rtu_oracle_camera_frame(const RtuCamera* cam, int width, int height, float out12[12]);
 /* gamma + Color24 + z-image; any output pointer may be NULL. */

@@ -399,11 +399,19 @@ __device__ __forceinline__ bool plane_hit_t(const Ray& ray, Hit& h, bool tex = f
         float t = (-ray.p.z) / (ray.dir.z);
         if (gt_001<LITERAL>(t) && t < h.z) {
             f3 q = ray.p + ray.dir * t;
-            if (q.x > -1 && q.x < 1 && q.y > -1 && q.y < 1) {
-                if (!LITERAL) {
-                    const bool edge = !(fabsf(q.x) < 1.0f - 1e-5f * (1.0f + fabsf(ray.p.x))) || !(fabsf(q.y) < 1.0f - 1e-5f * (1.0f + fabsf(ray.p.y)));
-                    if (edge && !box_hit(ray, mk3(-1, -1, 0), mk3(1, 1, 0), RTU_BIGFLOAT)) return false;
+            bool inside = q.x > -1 && q.x < 1 && q.y > -1 && q.y < 1;
+            if (!LITERAL) {
+                // One wave-uniform branch around the rare box test, as in sphere_hit_t, and ONE place where the hit is stored. The
+                // earlier form — `if (edge && !box_hit(...)) return false;` per lane inside the block that stores the hit — was
+                // compiled wrongly in k_query_closest: lanes that took the box test and passed it kept h.p.x or h.p.y of the previous
+                // best hit (tests/test_gpu_rays_oracle.py family A1 found it).
+                const bool edge = inside && (!(fabsf(q.x) < 1.0f - 1e-5f * (1.0f + fabsf(ray.p.x))) || !(fabsf(q.y) < 1.0f - 1e-5f * (1.0f + fabsf(ray.p.y))));
+                if (__any(edge)) {
+                    const bool bh = box_hit(ray, mk3(-1, -1, 0), mk3(1, 1, 0), RTU_BIGFLOAT);
+                    inside = inside && (!edge || bh);
                 }
+            }
+            if (inside) {
                 h.front = ray.p.z > 0;
                 h.N = mk3(0, 0, h.front ? 1.0f : -1.0f);
                 h.z = t;

@@ -1,8 +1,10 @@
 """Ray queries (rtu_trace_rays / rtu_occluded_rays, include/rtu_render.h) against the oracle and the renders.
 
-The oracle has no ray-level entry, so it is reached through cameras: a batch of rays is the set of pixel-centre rays of some camera
-(rtu_camera_rays), and the oracle's z image of that camera is the expected t, bit for bit. Node identity and occlusion are read off
-the oracle's colours of scenes edited so that a colour says which node was hit, or whether a light arrives."""
+Here the oracle is reached through cameras: a batch of rays is the set of pixel-centre rays of some camera (rtu_camera_rays), and
+the oracle's z image of that camera is the expected t, bit for bit. Node identity and occlusion are read off the oracle's colours of
+scenes edited so that a colour says which node was hit, or whether a light arrives. Rays no camera fires (axis-parallel grids, probes
+from inside the scene, tmax at the hit, rays from surfaces, the unit-length band) are compared field by field with the oracle's
+ray-level entry (rtu_oracle_rays) in tests/test_gpu_rays_oracle.py."""
 import ctypes
 
 import numpy as np

@@ -1,10 +1,11 @@
 """Ray batches (rtu_shade_rays / rtu_shade_rays_device, include/rtu_render.h) against the renders and the oracle.
 
-The oracle has no ray-level entry, so it is reached through cameras, as for the ray queries: the pixel-centre rays of a camera
-(rtu_camera_rays) shaded with eye = that camera's position must give the render's rgb and z bit for bit, and meet the oracle's
-image of that camera within the project's bar (z bit-exact, linear RGB relative error <= 2e-5, 8-bit +-1: check_against). A miss
-is the environment along the ray where a render shows the background, so colours are compared at hit rays and misses are checked
-against the texture arithmetic on their own."""
+Here the oracle is reached through cameras, as for the ray queries: the pixel-centre rays of a camera (rtu_camera_rays) shaded with
+eye = that camera's position must give the render's rgb and z bit for bit, and meet the oracle's image of that camera within the
+project's bar (z bit-exact, linear RGB relative error <= 2e-5, 8-bit +-1: check_against). A miss is the environment along the ray
+where a render shows the background, so colours are compared at hit rays and misses are checked against the texture arithmetic on
+their own. Batches no camera fires are compared with the oracle's ray-level entry (rtu_oracle_rays), misses included, in
+tests/test_gpu_rays_oracle.py."""
 import ctypes
 from types import SimpleNamespace
 
