@@ -374,7 +374,8 @@ int  rtu_camera_rays(const RtuFrameDesc* frame, int row0, int nrows, RtuRay* ray
  * pixel, bit for bit (a miss pixel of a render shows the background instead). One eye per call.
  * flags: 0, or RTU_QUERY_REFERENCE_WALK for the counting variant (collect_stats = 1 of a frame: the reference's tree, every Shade() call
  * a frame); the output is the same, bit for bit. max_bounce as RtuFrameDesc.max_bounce (0 where no material recurses).
- * A scene with stochastic features is refused (RTU_ERR_STOCHASTIC) as a samples == 0 frame is: sampled recipes are not supported.
+ * A scene with stochastic features is refused (RTU_ERR_STOCHASTIC) as a samples == 0 frame is: these two calls are recipe W.
+ * rtu_shade_rays_sampled / rtu_shade_rays_sampled_device below shade rays by recipe S, each ray on the sample stream of its own key.
  * Errors: RTU_ERR_ARG for a NULL pointer with n > 0 (or a NULL descriptor), a device pointer that is not 16-byte aligned, an unknown flag
  * bit, non-zero reserved, max_bounce outside 0 .. RTU_MAX_BOUNCE, a non-finite eye, n > 2^26 in the device form; RTU_ERR_NO_SCENE before
  * rtu_upload_scene. n == 0 is RTU_OK and launches nothing.
@@ -395,6 +396,42 @@ typedef struct RtuShadeDesc {      /* 32 B */
 int  rtu_shade_defaults(RtuShadeDesc* out);   /* eye 0, max_bounce 5, flags 0; pure host code */
 int  rtu_shade_rays_device(RtuContext* ctx, const void* d_rays, size_t n, const RtuShadeDesc* desc, void* d_rgbt, void* hip_stream);
 int  rtu_shade_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats);
+
+/* ---- Sampled ray batches: recipe S along caller-supplied rays (render_rays2.hip / render_rays3.hip) ---------------------------------
+ * rtu_shade_rays with ONE Shade() call of RECIPE S per ray (direct lighting only: gather_bounces 0): soft shadows and glossy bounces on
+ * the sample streams stated above ("Sample streams of recipe S"). keys[i] is the `key` of ray i's root Shade() call — what
+ * sample_key(p, i) is to a sample of a pixel: the disk sample of light l draws from rand31(key, 16 + 2 l ...), the glossy normals of the
+ * root call from 0x10000 / 0x20000 / 0x30000 ..., and the Shade() of the hit of secondary ray `slot` continues with
+ * child_key(key, slot), exactly as behind a render's primary hit. The answer to a ray depends on the scene, the eye, max_bounce, that
+ * ray and that key — not on its index, the batch size or the order. Whatever the caller needs for the ray itself (a lens point, an
+ * offset inside a pixel) it draws itself; purposes 0 and 1 are free for that, and rtu_camera_sample_rays uses them as the renders
+ * do. One sample per ray: averaging is the caller's (several keys per direction, e.g. rtu_sample_key(direction index, k)).
+ * hit / miss / invalid / a node without material, eye, max_bounce, flags (RTU_QUERY_REFERENCE_WALK), stats, RtuRay.reserved (ignored)
+ * and every error are as for rtu_shade_rays; RtuShadeDesc is the same structure under the same rules. A scene WITHOUT stochastic
+ * features is accepted: its arithmetic is recipe S's on that scene, which draws nothing. d_keys / h_keys: n uint32, 4-byte aligned
+ * (RTU_ERR_ARG otherwise, and for NULL with n > 0).
+ * The calls are renders, as rtu_shade_rays: frame records, append counters, launch hints (under a key of their own — neither a sampled
+ * frame's nor an unsampled batch's), the ONE STREAM PER CONTEXT rule, rtu_frame_status after the _device form (RTU_ERR_CAPACITY: call
+ * it again), n <= 2^26 in the _device form; the host form copies rays and keys through grow-only buffers of the context in chunks of at
+ * most 2^20 rays, repeats a chunk that ran out of capacity itself, and is synchronous. rtu_debug_flags 64 and 2048,
+ * rtu_debug_node_bounds, rtu_debug_walk_stack_limit and rtu_debug_tail_from apply and change no bit.
+ * Against a render: the rays and keys of rtu_camera_sample_rays(frame, k) shaded with eye = cam_pos are sample k of the recipe S frame
+ * — rtu_debug_sample_images(frame, k, 1) — bit for bit in t at every ray and in rgb at every hit ray (a miss shows the environment
+ * where a render shows the background). */
+int  rtu_shade_rays_sampled_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_rgbt,
+                                   void* hip_stream);
+int  rtu_shade_rays_sampled(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_rgbt,
+                            RtuStats* stats);
+/* The primary rays and keys of sample `sample` (0 <= sample < frame->samples) of the recipe S frame `frame`, image rows
+ * [row0, row0 + nrows), width * nrows of each in image order; shards are ignored. key = sample_key(x + width * y, sample); the pixel
+ * offset is sample / S + Halton(sample, 4 | 5) in x | y (RenderFunctions.cpp:80-85, :96); the origin is the lens point
+ * (cam_pos + lens_up * (rad * sin)) + lens_right * (rad * cos) with rad = sqrt((sampleX * dof) * dof), sampleX = rand31(key, 0) / 2^31,
+ * the angle rand31(key, 1) / float(RAND_MAX / 2 pi) through portable_sincos (:88-93); dir = normalize(cp - origin), tmax = RTU_BIGFLOAT.
+ * The binary32 expressions are the kernels' own in the same order. Pure host code, needs no GPU and no context. RTU_ERR_ARG: NULL
+ * frame, width or height < 1, samples < 1, sample outside [0, samples), rows outside the image, a NULL output with nrows > 0. */
+int  rtu_camera_sample_rays(const RtuFrameDesc* frame, int sample, int row0, int nrows, RtuRay* rays_out, uint32_t* keys_out);
+uint32_t rtu_sample_key(uint32_t pixel, uint32_t sample);   /* sample_key(p, i) as stated above; pure host code */
+uint32_t rtu_child_key(uint32_t key, uint32_t slot);        /* child_key(key, slot) as stated above; pure host code */
 
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds

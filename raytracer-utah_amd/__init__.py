@@ -154,7 +154,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes",
                "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing",
                "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays",
-               "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays"]
+               "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays",
+               "rtu_shade_rays_sampled_device", "rtu_shade_rays_sampled", "rtu_camera_sample_rays", "rtu_sample_key", "rtu_child_key"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -296,6 +297,11 @@ class RtuShadeDesc(ctypes.Structure):
 _sig(hip, "rtu_shade_defaults", _I, ctypes.POINTER(RtuShadeDesc))
 _sig(hip, "rtu_shade_rays_device", _I, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
 _sig(hip, "rtu_shade_rays", _I, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
+_sig(hip, "rtu_shade_rays_sampled_device", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
+_sig(hip, "rtu_shade_rays_sampled", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
+_sig(hip, "rtu_camera_sample_rays", _I, ctypes.POINTER(RtuFrameDesc), _I, _I, _I, _P, _P)
+_sig(hip, "rtu_sample_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
+_sig(hip, "rtu_child_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
 
 
 def shade_desc(eye=(0.0, 0.0, 0.0), max_bounce=5, reference_walk=False):
@@ -343,6 +349,39 @@ def camera_rays(frame, row0=0, nrows=None):
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_camera_rays: rows outside the image or an empty frame")
     return out
+
+
+def camera_sample_rays(frame, sample, row0=0, nrows=None):
+    """rtu_camera_sample_rays (pure host code): the primary rays and keys of sample `sample` of the recipe S frame `frame`, image rows
+    [row0, row0 + nrows): (rays [nrows * width] of ray_dtype(), keys uint32 [nrows * width]) in image order — Halton pixel offset,
+    lens point and sample_key(pixel, sample) as the renders draw them, bit for bit."""
+    import numpy as np
+    if nrows is None:
+        nrows = frame.height - row0
+    n = max(nrows, 0) * max(frame.width, 0)
+    rays, keys = np.zeros(n, ray_dtype()), np.zeros(n, np.uint32)
+    rc = hip.rtu_camera_sample_rays(ctypes.byref(frame), sample, row0, nrows, rays.ctypes.data if n else None, keys.ctypes.data if n else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_camera_sample_rays: not a recipe S frame, sample outside [0, samples) or rows outside the image")
+    return rays, keys
+
+
+def sample_key(pixel, sample):
+    """rtu_sample_key: the key of the root Shade() call of sample `sample` of pixel `pixel` (include/rtu_render.h, sample streams)."""
+    return int(hip.rtu_sample_key(int(pixel) & 0xFFFFFFFF, int(sample) & 0xFFFFFFFF))
+
+
+def child_key(key, slot):
+    """rtu_child_key: the key of the Shade() call behind secondary ray `slot` of the call with key `key`."""
+    return int(hip.rtu_child_key(int(key) & 0xFFFFFFFF, int(slot) & 0xFFFFFFFF))
+
+
+def _as_keys(keys, n):
+    import numpy as np
+    k = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+    if k.size != n:
+        raise RtuError(RTU_ERR_ARG, "keys: one uint32 per ray")
+    return k
 
 
 # the arrays of a mesh dump (include/rtu_render.h RTU_MESH_*): name -> (which, numpy dtype, trailing shape)
@@ -914,6 +953,26 @@ class Context:
         asynchronous on `stream`; frame_status() afterwards as for render_device (RTU_ERR_CAPACITY: call it again)."""
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         self._check(hip.rtu_shade_rays_device(self._h, d_rays_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
+
+    def shade_rays_sampled(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+        """Recipe S along caller-supplied rays (rtu_shade_rays_sampled): as shade_rays, with one uint32 key per ray — the key of the
+        sample streams of that ray's root Shade() call (soft shadows, glossy bounces). One sample per ray; scenes with stochastic
+        features are accepted. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None)."""
+        import numpy as np
+        r = _as_rays(rays)
+        k = _as_keys(keys, r.size)
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        out = np.zeros((r.size, 4), np.float32)
+        st = RtuStats() if stats else None
+        self._check(hip.rtu_shade_rays_sampled(self._h, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None, r.size, ctypes.byref(d),
+                                               out.ctypes.data if r.size else None, ctypes.byref(st) if stats else None))
+        return out, (st.as_dict() if stats else None)
+
+    def shade_rays_sampled_device(self, d_rays_ptr, d_keys_ptr, n, eye, d_rgbt_ptr, stream=None, max_bounce=5, reference_walk=False, desc=None):
+        """rtu_shade_rays_sampled_device: n RtuRay at d_rays_ptr and n uint32 keys at d_keys_ptr -> n float4 {r, g, b, t} at d_rgbt_ptr
+        (device memory), asynchronous on `stream`; frame_status() afterwards as for render_device."""
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        self._check(hip.rtu_shade_rays_sampled_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
 
     def occluded_device(self, d_rays_ptr, n, d_occluded_ptr, stream=None, reference_walk=False, flags=None):
         """rtu_occluded_rays_device: n RtuRay at d_rays_ptr -> n bytes (1 / 0) at d_occluded_ptr, asynchronous on `stream`."""

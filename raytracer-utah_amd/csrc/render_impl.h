@@ -56,6 +56,10 @@ namespace {
 // same images — counting per kernel launch what they read and write (Counters::t_*, RtuTouched in rtu_render.h). The
 // roofline of bench.py is computed from these counters, i.e. from the work the timed kernels themselves do.
 #define CNTD ((TEX & 16) != 0)
+// bit 5 (with bit 1): a RAY BATCH of recipe S (rtu_shade_rays_sampled, render_rays2.hip / render_rays3.hip): a level-0 frame carries the
+// index of its ray, and the key of its sample streams comes from the caller's key buffer (ray_keys) instead of a pixel and a sample
+// index. Compile-time only: no instantiation without the bit changes.
+#define RAYD ((TEX & 32) != 0)
 // occupancy hints per kernel family (amdgpu_waves_per_eu), see DESIGN.md 5 for what was measured
 #ifndef RTU_OCC_PRIMARY
 // k_primary: six wavefronts per SIMD (<= 85 VGPRs) — the tile loop left alone takes 97 and fits five: 335 us per 16 frames against 304;
@@ -303,8 +307,13 @@ __device__ __forceinline__ void pixel_of(const KernelArgs& a, uint32_t pix, int&
     y = (int)(((ly / RTU_BAND_ROWS) * a.frame.shard_count + a.frame.shard_rank) * RTU_BAND_ROWS + ly % RTU_BAND_ROWS);
 }
 
+// The keys of a sampled ray batch (RAYD), one per ray. KernelArgs has no room for another pointer (the hot kernels are at their
+// scalar-register ceiling) and a ray batch has no cameras: `cam`, which only a batch of recipe-W frames (BATD) reads,
+// carries them.
+__device__ __forceinline__ const uint32_t* ray_keys(const KernelArgs& a) { return reinterpret_cast<const uint32_t*>(a.cam); }
+
 // The key of the sample streams of the Shade() call a frame stands for (recipe S): level 0 frames
-// carry their pixel in fb.w, deeper frames their key.
+// carry their pixel in fb.w (a ray batch: their ray), deeper frames their key.
 template <int TEX>
 __device__ __forceinline__ Smp frame_smp(const KernelArgs& a, int L, float fbw) {
     Smp smp;
@@ -312,7 +321,9 @@ __device__ __forceinline__ Smp frame_smp(const KernelArgs& a, int L, float fbw) 
     smp.key = 0;
     if (smp.on) {
         const uint32_t w = __float_as_uint(fbw);
-        if (L == 0 && !GID) {
+        if (L == 0 && RAYD) {
+            smp.key = ray_keys(a)[w];  // (no pixel_of: a ray batch has no image, and a.batch_pixels is a divisor there)
+        } else if (L == 0 && !GID) {
             int x, y;
             uint32_t sidx;
             pixel_of<TEX>(a, w, x, y, sidx);
@@ -1851,7 +1862,9 @@ int launch_all(const KernelArgs& a, uint32_t n_tiles, bool stats, hipStream_t st
     const uint32_t pcap = a.pgrid ? a.pgrid : 32768u;
     const dim3 gridP(blocksP), gridPF(blocksP < pcap ? blocksP : pcap);
     if (CNTD) stats = false;  // the touched-bytes instantiations are the fast variant's (the reference-counting kernels are not built for them)
-    if (mode == RTU_LAUNCH_LEVELS) {
+    if constexpr (RAYD) {
+        // a sampled ray batch: always RTU_LAUNCH_LEVELS, and no kernel of a camera's primary phase is instantiated for it
+    } else if (mode == RTU_LAUNCH_LEVELS) {
         // a ray batch: its roots are level-0 frames already queued on this stream (k_ray_roots, render_rays_impl.h)
     } else if (mode == RTU_LAUNCH_SHADE) {
         RTU_LAUNCH(RTU_TL_GI_ROOTS, (k_gi_roots<TEX>), gridN, block, a, (stats || (a.dbg & 2048u)) ? 0 : 1);  // (rtu_debug_flags 2048: no inline shading — results must not change)

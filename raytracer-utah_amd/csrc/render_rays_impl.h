@@ -14,7 +14,11 @@
 // coverage masks or tile occupancy, and no ray is deferred. STATS walks the reference's tree and counts primary_rays /
 // primary_hits as k_primary_counting does. Chunk c appends to shard c % RTU_SHARDS, so ensure_levels(ceil(n / 64)) sizes level 0
 // for every root, exactly as for tiles.
-// Included by render_rays0.hip / render_rays1.hip only: the kernels of the render_feat*.hip units are not compiled again.
+// Included by render_rays0.hip .. render_rays3.hip only: the kernels of the render_feat*.hip units are not compiled again.
+// RECIPE S (rtu_shade_rays_sampled; render_rays2.hip / render_rays3.hip, feature sets 2|32 and 3|32, RAYD of render_impl.h): the root
+// call of ray i has the key keys[i] (ray_keys) where a render's has sample_key(pixel, sample); the ray is given, so the lens and
+// pixel-offset draws of primary_pixel are the caller's (rtu_camera_sample_rays). Those two units instantiate the level kernels
+// themselves — frame_smp of a level-0 frame reads the key buffer there, which the kernels of render_feat2/3.hip cannot.
 #ifndef RTU_RENDER_RAYS_IMPL_H_INCLUDED
 #define RTU_RENDER_RAYS_IMPL_H_INCLUDED
 // (render_impl.h defines the prelude kernels of a camera's launch sequence, which nothing here launches)
@@ -33,13 +37,14 @@ __global__ void __launch_bounds__(64) RTU_OCC_WALK k_ray_roots(KernelArgs a, con
     const uint32_t chunks = (n + 63u) / 64u;
     Counters cnt = {};
     Smp smp;
-    smp.on = false;
+    smp.on = SMPD;  // (recipe S: the sampled feature sets, render_rays2.hip / render_rays3.hip)
     smp.key = 0;
     for (uint32_t c = blockIdx.x; c < chunks; c += gridDim.x) {  // whole wavefronts: the tail below votes and appends wave by wave
         const uint32_t i = c * 64u + lane;
         const uint32_t shard = c % RTU_SHARDS;
         float4 ra = make_float4(0, 0, 0, 0), rb = ra;
         if (i < n) { ra = rays[2 * (size_t)i]; rb = rays[2 * (size_t)i + 1]; }
+        if (SMPD && i < n) smp.key = ray_keys(a)[i];  // the key of the ray's root Shade() call: the caller's (make_info draws the first refraction normal from it)
         const bool valid = i < n && ray_valid(ra, rb);
         if (i < n && !valid) a.out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // not traced; t == 0 means nothing else (a valid ray has tmax > 0)
         Ray ray;
@@ -67,7 +72,8 @@ __global__ void __launch_bounds__(64) RTU_OCC_WALK k_ray_roots(KernelArgs a, con
         uint32_t info = 0;
         if (want) info = make_info<TEX>(a, mid, a.frame.max_bounce, h.front, ray.dir, h.p, h.N, h.uvw, smp);
         // A childless Shade() call is settled by the lane that found the hit, as in primary_pixel (rtu_debug_flags 2048 switches
-        // this off: results must not change). a.frame.cam_pos is the call's eye.
+        // this off: results must not change). a.frame.cam_pos is the call's eye. Recipe S, as k_primary_sampled: shadows_inline refuses
+        // a call that a soft light reaches — its shadow ray aims at a sample of the light's disk (frame_ray) —, which becomes a frame.
         if (!STATS && !(a.dbg & 2048u) && __any(want && !(info & (RTU_FI_MAIN | RTU_FI_C)))) {
             const bool tryI = want && !(info & (RTU_FI_MAIN | RTU_FI_C));
             uint32_t lit = ~0u;

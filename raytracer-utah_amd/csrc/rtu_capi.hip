@@ -134,6 +134,7 @@ struct RtuContext {
     DevBuf<float4>  q_rays, q_hits;          // ray queries, host forms (rtu_trace_rays / rtu_occluded_rays): one chunk of rays and of answers
     DevBuf<uint8_t> q_occ;
     DevBuf<float4>  sh_rays, sh_out;         // ray batches, host form (rtu_shade_rays): one chunk of rays and of {r, g, b, t}
+    DevBuf<uint32_t> sh_keys;                // ... and of keys (rtu_shade_rays_sampled)
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -1130,9 +1131,11 @@ float halton(int index, int base) {
 // d_rays / n_rays: a RAY BATCH (rtu_shade_rays): the roots are the Shade() calls of n_rays caller-supplied rays in device memory, d_out has
 // one float4 per ray; `frame` carries the eye (cam_pos), max_bounce and collect_stats (0 / 1) of a recipe-W frame and no camera. A
 // "tile" is a chunk of 64 rays (k_ray_roots): no screen rectangles, coverage masks or tile occupancy, no side mode, hint keys of its own.
+// d_keys: the ray batch is SAMPLED (rtu_shade_rays_sampled): `frame` is a recipe-S frame with samples = 1, d_keys[i] the key of ray i's root
+// Shade() call; the pointer travels in KernelArgs::cam (ray_keys, render_impl.h), which a ray batch leaves idle.
 int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, int sample_index = 0, int batch = 1,
            const RtuFrameDesc* frames_batch = nullptr, int gi_mode = RTU_LAUNCH_ALL, int gi_depth = 0, bool adaptive = false,
-           const uint4* act_list = nullptr, uint32_t act_n = 0, const float4* d_rays = nullptr, uint32_t n_rays = 0) {
+           const uint4* act_list = nullptr, uint32_t act_n = 0, const float4* d_rays = nullptr, uint32_t n_rays = 0, const uint32_t* d_keys = nullptr) {
     const bool rays = d_rays != nullptr;
     uint32_t tiles_x = (uint32_t)((frame->width + 7) / 8);
     uint32_t bands = (uint32_t)shard_bands(frame->height, frame->shard_rank, frame->shard_count);
@@ -1209,7 +1212,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     // so that a batch learns from batches of about its size and the maps stay small)
     const uint32_t act_tiles = act_n ? act_n * (uint32_t)batch : n_tiles;
     const uint64_t tail_key = adaptive ? ((uint64_t)(32 - __builtin_clz(act_tiles | 1u)) << 8) | (uint64_t)(16 | 2 | (gi ? 8 : 0))
-                                       : ((uint64_t)n_tiles << 8) | (uint64_t)((frame->samples ? 2 : 0) | (frames_batch ? 4 : 0) | (gi ? 8 : 0) | (rays ? 32 : 0));  // (32: a ray batch and a frame of as many tiles teach each other nothing)
+                                       : ((uint64_t)n_tiles << 8) | (uint64_t)((frame->samples ? 2 : 0) | (frames_batch ? 4 : 0) | (gi ? 8 : 0) | (rays ? 32 : 0));  // (32: a ray batch and a frame of as many tiles teach each other nothing; a sampled ray batch has 2 | 32: neither a sampled frame's hints nor an unsampled batch's)
     int hint = RTU_MAX_LEVELS;
     bool forced = false;
     if (ctx->tail_hint != 0) { hint = ctx->tail_hint; ctx->tail_hint = 0; forced = true; }
@@ -1257,6 +1260,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         RTU_HIP(ctx, hipEventRecord(ctx->cam_ev[slot], stream));
         a.cam = ctx->d_cams.get();
     }
+    if (d_keys) a.cam = reinterpret_cast<const BatchCam*>(d_keys);  // (ray_keys: no batch of frames here — frames_batch is NULL —, so nothing reads it as cameras)
     if (gi) {
         a.gi_h = ctx->gi_h.get();
         a.gi_res = ctx->gi_res.get();
@@ -1323,7 +1327,8 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         if (e0 != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e0));
         return RTU_OK;
     }
-    hipError_t e = rays ? (hipError_t)rtu_launch_ray_batch(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr)
+    hipError_t e = rays ? (d_keys ? (hipError_t)rtu_launch_ray_batch_sampled(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr)
+                                  : (hipError_t)rtu_launch_ray_batch(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr))
                         : (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
     if (probing && probe_recorded) ctx->probe_used++;
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
@@ -3295,7 +3300,9 @@ int rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t 
 // ---- ray batches: Shade() along caller-supplied rays (render_rays_impl.h) -------------------------------------------------------
 namespace {
 // the checks both forms share, then the frame descriptor launch() takes for a ray batch: no camera, the eye in cam_pos
-int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, const RtuShadeDesc* d, bool device, RtuFrameDesc* f) {
+// keys: the sampled forms (rtu_shade_rays_sampled*) — n uint32, one per ray; the frame is then a recipe-S frame of one sample
+int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, const RtuShadeDesc* d, bool device, RtuFrameDesc* f, bool sampled = false,
+               const void* keys = nullptr) {
     if (!d) return fail(ctx, RTU_ERR_ARG, "shade descriptor is NULL");
     if (d->flags & ~RTU_QUERY_REFERENCE_WALK) return fail(ctx, RTU_ERR_ARG, "unknown shade flag bits 0x%x", d->flags & ~RTU_QUERY_REFERENCE_WALK);
     if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(ctx, RTU_ERR_ARG, "RtuShadeDesc.reserved must be 0");
@@ -3305,17 +3312,82 @@ int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, con
     if (device && n && (((uintptr_t)rays & 15u) || ((uintptr_t)out & 15u)))
         return fail(ctx, RTU_ERR_ARG, "device ray / result buffers must be 16-byte aligned");
     if (device && n > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "more than 2^26 rays in one call");
+    if (sampled && n && !keys) return fail(ctx, RTU_ERR_ARG, "key pointer is NULL");
+    if (sampled && n && ((uintptr_t)keys & 3u)) return fail(ctx, RTU_ERR_ARG, "the key buffer must be 4-byte aligned");
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
-    if (ctx->scene_stochastic)
-        return fail(ctx, RTU_ERR_STOCHASTIC, "the scene has %s: ray batches are recipe W (sampled recipes are not supported)", ctx->stochastic_what.c_str());
+    if (ctx->scene_stochastic && !sampled)
+        return fail(ctx, RTU_ERR_STOCHASTIC, "the scene has %s: rtu_shade_rays is recipe W (rtu_shade_rays_sampled shades rays by recipe S)", ctx->stochastic_what.c_str());
     memset(f, 0, sizeof *f);
     f->width = 64;  // (launch() sizes a ray batch from n; these only have to be a valid frame)
     f->height = 1;
     f->shard_count = 1;
     f->max_bounce = d->max_bounce;
     f->collect_stats = (d->flags & RTU_QUERY_REFERENCE_WALK) ? 1 : 0;
+    f->samples = sampled ? 1 : 0;  // one Shade() call of recipe S per ray: launch() sets the sampled feature set from it
     memcpy(f->cam_pos, d->eye, sizeof f->cam_pos);
     return RTU_OK;
+}
+
+// the host forms of both recipes: chunks of at most kQueryChunk rays (and keys) through the context's buffers, each checked for
+// capacity and shaded again if need be
+int shade_host(RtuContext* ctx, RtuFrameDesc& f, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, float* h_rgbt, RtuStats* stats) {
+    int rc = RTU_OK;
+    if (stats) { memset(stats, 0, sizeof *stats); f.collect_stats = 1; }
+    if (n == 0) return RTU_OK;
+    const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->sh_rays.grow(2 * chunk));
+    RTU_HIP(ctx, ctx->sh_out.grow(chunk));
+    if (h_keys) RTU_HIP(ctx, ctx->sh_keys.grow(chunk));
+    for (size_t done = 0; done < n; done += chunk) {
+        const size_t m = n - done < chunk ? n - done : chunk;
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
+        if (h_keys) RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_keys.get(), h_keys + done, sizeof(uint32_t) * m, hipMemcpyHostToDevice, ctx->stream));
+        for (int attempt = 0;; attempt++) {  // as rtu_render_frame: a chunk that ran out of frame capacity is shaded again
+            rc = launch(ctx, &f, ctx->sh_out.get(), ctx->stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, ctx->sh_rays.get(), (uint32_t)m,
+                        h_keys ? ctx->sh_keys.get() : nullptr);
+            if (rc != RTU_OK) return rc;
+            RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            bool overflow = false;
+            if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
+            if (!overflow) break;
+            if (attempt >= 2 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+        }
+        RTU_HIP(ctx, hipMemcpy(h_rgbt + 4 * done, ctx->sh_out.get(), sizeof(float4) * m, hipMemcpyDeviceToHost));
+        if (stats) {  // the counters are zeroed per launch: the batch's are the sum over its chunks
+            RtuStats part;
+            if ((rc = rtu_get_stats(ctx, &part)) != RTU_OK) return rc;
+            unsigned long long* to = reinterpret_cast<unsigned long long*>(stats);
+            const unsigned long long* from = reinterpret_cast<const unsigned long long*>(&part);
+            for (size_t k = 0; k < sizeof(RtuStats) / sizeof(unsigned long long); k++) to[k] += from[k];
+        }
+    }
+    return RTU_OK;
+}
+
+// ---- the sample streams on the host (include/rtu_render.h "Sample streams of recipe S"; rtu_intersect.h states them for the device) ----
+uint32_t h_mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+uint32_t h_rand31(uint32_t key, uint32_t purpose) { return h_mix32(key ^ h_mix32(purpose * 0x9e3779b9U + 0x85ebca6bU)) >> 1; }
+// portable_sincos of rtu_intersect.h restated for the host: binary64, IEEE operations only (this file is compiled with -ffp-contract=off),
+// the same sequence, so the same floats
+void h_portable_sincos(float t, float& sn, float& cs) {
+    const double x = (double)t;
+    const double kd = floor(x * 6.36619772367581382433e-01 + 0.5);
+    const int k = (int)kd;
+    const double y = (x - kd * 1.57079632673412561417e+00) - kd * 6.07710050650619224932e-11;
+    const double y2 = y * y;
+    const double ps = -1.66666666666666324348e-01 + y2 * (8.33333333332248946124e-03 + y2 * (-1.98412698298579493134e-04 +
+                      y2 * (2.75573137070700676789e-06 + y2 * (-2.50507602534068634195e-08 + y2 * 1.58969099521155010221e-10))));
+    const double pc = 4.16666666666666019037e-02 + y2 * (-1.38888888888741095749e-03 + y2 * (2.48015872894767294178e-05 +
+                      y2 * (-2.75573143513906633035e-07 + y2 * (2.08757232129817482790e-09 + y2 * -1.13596475577881948265e-11))));
+    const double s = y + (y * y2) * ps;
+    const double c = 1.0 - (0.5 * y2 - (y2 * y2) * pc);
+    const double so = (k & 1) ? c : s, co = (k & 1) ? s : c;
+    sn = (float)((k & 2) ? -so : so);
+    cs = (float)((((k + 1) & 2) != 0) ? -co : co);
 }
 }  // namespace
 
@@ -3340,35 +3412,64 @@ int rtu_shade_rays_device(RtuContext* ctx, const void* d_rays, size_t n, const R
 int rtu_shade_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats) {
     if (!ctx) return RTU_ERR_ARG;
     RtuFrameDesc f;
-    int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f);
+    const int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f);
     if (rc != RTU_OK) return rc;
-    if (stats) { memset(stats, 0, sizeof *stats); f.collect_stats = 1; }
-    if (n == 0) return RTU_OK;
-    const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    return shade_host(ctx, f, h_rays, nullptr, n, h_rgbt, stats);
+}
+
+// ---- sampled ray batches: one Shade() call of recipe S per ray, its sample streams keyed by the caller (render_rays2.hip / render_rays3.hip) ----
+int rtu_shade_rays_sampled_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_rgbt, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    const int rc = shade_args(ctx, d_rays, d_rgbt, n, desc, true, &f, true, d_keys);
+    if (rc != RTU_OK || n == 0) return rc;
     RTU_HIP(ctx, hipSetDevice(ctx->device));
-    RTU_HIP(ctx, ctx->sh_rays.grow(2 * chunk));
-    RTU_HIP(ctx, ctx->sh_out.grow(chunk));
-    for (size_t done = 0; done < n; done += chunk) {
-        const size_t m = n - done < chunk ? n - done : chunk;
-        RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
-        for (int attempt = 0;; attempt++) {  // as rtu_render_frame: a chunk that ran out of frame capacity is shaded again
-            rc = launch(ctx, &f, ctx->sh_out.get(), ctx->stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, ctx->sh_rays.get(), (uint32_t)m);
-            if (rc != RTU_OK) return rc;
-            RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            bool overflow = false;
-            if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
-            if (!overflow) break;
-            if (attempt >= 2 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+    return launch(ctx, &f, (float4*)d_rgbt, (hipStream_t)hip_stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, (const float4*)d_rays, (uint32_t)n,
+                  (const uint32_t*)d_keys);
+}
+
+int rtu_shade_rays_sampled(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    const int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f, true, h_keys);
+    if (rc != RTU_OK) return rc;
+    return shade_host(ctx, f, h_rays, h_keys, n, h_rgbt, stats);
+}
+
+uint32_t rtu_sample_key(uint32_t pixel, uint32_t sample) { return h_mix32(h_mix32(pixel + 0x68bc21ebU) ^ (sample * 0x9e3779b9U + 1U)); }
+uint32_t rtu_child_key(uint32_t key, uint32_t slot) { return h_mix32(key + (slot + 1U) * 0x632be5abU); }
+
+// the rays and keys of sample `sample` of a recipe-S frame: primary_pixel's recipe-S branch (render_impl.h; RenderFunctions.cpp:80-97,
+// :258-268) and launch()'s pixel offsets, the same binary32 expressions in the same order, so the same bits
+int rtu_camera_sample_rays(const RtuFrameDesc* frame, int sample, int row0, int nrows, RtuRay* rays_out, uint32_t* keys_out) {
+    if (!frame || frame->width <= 0 || frame->height <= 0 || row0 < 0 || nrows < 0 || row0 > frame->height || nrows > frame->height - row0)
+        return RTU_ERR_ARG;
+    if (frame->samples < 1 || sample < 0 || sample >= frame->samples) return RTU_ERR_ARG;
+    if (nrows && (!rays_out || !keys_out)) return RTU_ERR_ARG;
+    const f3 cam_pos = ld3(frame->cam_pos), cam_origin = ld3(frame->origin), cam_u = ld3(frame->u), cam_v = ld3(frame->v);
+    const float pixelIncrement = (float)(1.0 / frame->samples);  // RenderFunctions.cpp:68 (launch())
+    const float currentOffset = (float)sample * pixelIncrement;  // :80
+    const float ox = currentOffset + halton(sample, 4), oy = currentOffset + halton(sample, 5);  // :84, :85, :96
+    for (int y = row0; y < row0 + nrows; y++)
+        for (int x = 0; x < frame->width; x++) {
+            const uint32_t key = rtu_sample_key((uint32_t)x + (uint32_t)frame->width * (uint32_t)y, (uint32_t)sample);
+            const float sampleX = (float)h_rand31(key, 0u) / 2147483648.0f;                                              // :88 (RTU_RAND_MAX_F)
+            const float sampleTheta = (float)h_rand31(key, 1u) / ((float)(2147483647 / (2 * 3.14159265358979323846)));  // :89 (RTU_THETA_DIV)
+            float sn, cs;
+            h_portable_sincos(sampleTheta, sn, cs);
+            const float rad = sqrtf((sampleX * frame->dof) * frame->dof);
+            const float camOffsetX = rad * cs, camOffsetY = rad * sn;                                                    // :90-91
+            const f3 org = (cam_pos + ld3(frame->lens_up) * camOffsetY) + ld3(frame->lens_right) * camOffsetX;           // :93
+            const f3 cp = (cam_origin + cam_u * ((float)x + ox)) + cam_v * ((float)y + oy);
+            const f3 dir = norm3(cp - org);
+            const size_t i = (size_t)(y - row0) * (size_t)frame->width + (size_t)x;
+            RtuRay& r = rays_out[i];
+            r.org[0] = org.x; r.org[1] = org.y; r.org[2] = org.z;
+            r.tmax = RTU_BIGFLOAT;
+            r.dir[0] = dir.x; r.dir[1] = dir.y; r.dir[2] = dir.z;
+            r.reserved = 0;
+            keys_out[i] = key;
         }
-        RTU_HIP(ctx, hipMemcpy(h_rgbt + 4 * done, ctx->sh_out.get(), sizeof(float4) * m, hipMemcpyDeviceToHost));
-        if (stats) {  // the counters are zeroed per launch: the batch's are the sum over its chunks
-            RtuStats part;
-            if ((rc = rtu_get_stats(ctx, &part)) != RTU_OK) return rc;
-            unsigned long long* to = reinterpret_cast<unsigned long long*>(stats);
-            const unsigned long long* from = reinterpret_cast<const unsigned long long*>(&part);
-            for (size_t k = 0; k < sizeof(RtuStats) / sizeof(unsigned long long); k++) to[k] += from[k];
-        }
-    }
     return RTU_OK;
 }
 

@@ -356,6 +356,7 @@ struct KernelArgs {
     // a batch of FRAMES of recipe W (rtu_render_frames_device): the same index space, one camera per frame
     uint32_t     frame_batch;       // 0: no
     const BatchCam* cam;            // [batch] in device memory (copied there on the launch stream, ahead of the kernels)
+                                    // A SAMPLED RAY BATCH (frame_batch == 0; RAYD kernels only): the n uint32 keys of its rays, read through ray_keys() of render_impl.h
     // ADAPTIVE sampling (rtu_render_frame_adaptive, recipes S / P): the tiles that still have a pixel sampling, {tile of the shard, 0,
     // lane mask low, high} (k_adaptive_step); the primary phase walks batch x act_n entries instead of batch x tiles_per_image and
     // treats a lane outside the mask as outside the image. nullptr: every tile, every pixel (the fixed-count path)
@@ -388,6 +389,11 @@ int rtu_launch_gi_final(const KernelArgs& args, hipStream_t stream);
 // recursion levels. args as for a frame of recipe W with frame.cam_pos = the eye; stats: the reference-counting variant.
 int rtu_launch_ray_batch(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream,
                          const LaunchProbe* probe = nullptr);
+// A SAMPLED ray batch (rtu_shade_rays_sampled; render_rays2.hip / render_rays3.hip): one Shade() call of recipe S per ray. args as for a
+// recipe-S frame of one sample with frame.cam_pos = the eye, and args.cam = the n uint32 keys of the rays' root calls (ray_keys,
+// render_impl.h: a ray batch has no cameras, and KernelArgs no room for another pointer).
+int rtu_launch_ray_batch_sampled(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream,
+                                 const LaunchProbe* probe = nullptr);
 
 // recipe S: add one sample's image to the accumulators / write the mean
 int rtu_launch_accumulate(const float4* samples, uint32_t batch, float4* acc, uint32_t* hits, uint32_t pixels, bool first, hipStream_t stream);

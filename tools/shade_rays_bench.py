@@ -6,7 +6,11 @@ after `warmup` launches that are not counted (they also settle the frame capacit
 The ray form has no tile occupancy, no screen rectangles and no two-stage walk: on the teapot, where most of the image is background,
 it is expected to be slower than the render. p4, where every ray has work and the recursion is real, is the honest comparison.
 
-usage: tools/shade_rays_bench.py [--reps 20] [--warmup 3] [--out profiles/r09_shade_rays.json]"""
+--sampled: the same for recipe S (rtu_shade_rays_sampled_device): the camera-sample rays and keys (rtu_camera_sample_rays, sample 0 of a
+one-sample frame) of Project10/scene.xml and Project11/scene_glossy_soft.xml at 1920x1080 against rtu_render_frame_device of that frame
+with samples = 1 — one sample image, the accumulation and the resolve.
+
+usage: tools/shade_rays_bench.py [--sampled] [--reps 20] [--warmup 3] [--out profiles/r09_shade_rays.json]"""
 import argparse
 import json
 import os
@@ -18,6 +22,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 TAGS = ["teapot2_1080", "p4_1080"]
+SAMPLED = [("p10_s4_160x120", "Project10/scene.xml"), ("p11gs_s2_160x90", "Project11/scene_glossy_soft.xml")]  # (golden holding the scene, its file)
 
 
 def main():
@@ -25,6 +30,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--sampled", action="store_true", help="recipe S: rtu_shade_rays_sampled_device against a one-sample frame")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -54,18 +60,18 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
 
-    out = {"tool": "shade_rays_bench", "reps": args.reps, "warmup": args.warmup, "device": pkg.device_info(0)["name"], "scenes": []}
-    for tag in TAGS:
+    out = {"tool": "shade_rays_bench", "recipe": "S" if args.sampled else "W", "reps": args.reps, "warmup": args.warmup, "device": pkg.device_info(0)["name"], "scenes": []}
+    for tag, name in (SAMPLED if args.sampled else [(t, t) for t in TAGS]):
         gd = Golden(tag)
         scene = gd.scene(pkg)
-        W, H = gd.width, gd.height
+        W, H = (1920, 1080) if args.sampled else (gd.width, gd.height)
         ctx.upload(scene)
-        frame = pkg.frame_setup(scene.desc.camera, W, H)
+        frame = pkg.frame_setup(scene.desc.camera, W, H, samples=1 if args.sampled else 0)
         eye = tuple(frame.cam_pos)
-        rays = pkg.camera_rays(frame)
+        rays, keys = pkg.camera_sample_rays(frame, 0) if args.sampled else (pkg.camera_rays(frame), None)
         n = rays.size
         d_out = torch.zeros(n * 4, dtype=torch.float32, device="cuda:0")
-        row = {"scene": tag, "width": W, "height": H, "rays": int(n), "shade_rays": {}}
+        row = {"scene": name, "width": W, "height": H, "rays": int(n), "shade_rays": {}}
         render = timed(lambda: ctx.render_device(frame, d_out.data_ptr(), stream.cuda_stream))
         render["mrays_per_s"] = n / render["median_ms"] / 1e3
         row["render_frame"] = render
@@ -73,7 +79,11 @@ def main():
         hit = image[:, 3] != np.float32(1.0e30)
         for oname, order in (("image", np.arange(n)), ("shuffled", np.random.RandomState(1).permutation(n))):
             d_rays = torch.from_numpy(np.ascontiguousarray(rays[order]).view(np.uint8).copy()).to("cuda:0")
-            t = timed(lambda: ctx.shade_rays_device(d_rays.data_ptr(), n, eye, d_out.data_ptr(), stream.cuda_stream))
+            if args.sampled:
+                d_keys = torch.from_numpy(keys[order].view(np.int32).copy()).to("cuda:0")
+                t = timed(lambda: ctx.shade_rays_sampled_device(d_rays.data_ptr(), d_keys.data_ptr(), n, eye, d_out.data_ptr(), stream.cuda_stream))
+            else:
+                t = timed(lambda: ctx.shade_rays_device(d_rays.data_ptr(), n, eye, d_out.data_ptr(), stream.cuda_stream))
             got = d_out.cpu().numpy().reshape(-1, 4)
             want = image[order]
             h = hit[order]
