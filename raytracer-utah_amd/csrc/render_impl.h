@@ -427,7 +427,8 @@ __device__ __forceinline__ void primary_pixel(const KernelArgs& a, bool valid, i
     // (k_node_rects). A wavefront whose pixels lie outside every rectangle has nothing to trace: background, done.
     unsigned long long skip = 0;
     // (stage 1 only: a deferred pixel has passed its rectangles and masks already; stage 2, where every lane has its own camera
-    // entry and the lookups would be a dozen per-lane loads, bounds its ray in world space like any other ray — trace())
+    // entry and the lookups would be a dozen per-lane loads, bounds its ray in world space — trace() — and so do the primary rays
+    // of recipes S / P, which have no rectangle: both start at the camera, which may be anywhere, and take trace's FAR margin)
     const bool rects = !STATS && !SMPD && DEFER && a.node_rects != nullptr;
     if (rects) {
         const RTU_CONST int* rc = as_const(reinterpret_cast<const int*>(a.node_rects)) + 4u * (size_t)sidx * s.n_nodes;  // scalar loads where sidx is wave-uniform
@@ -511,7 +512,7 @@ __device__ __forceinline__ void primary_pixel(const KernelArgs& a, bool valid, i
         RTU_CNT(prim);
         bool hit = false;
         const unsigned units0 = CNTD ? cnt.t_inner4 * 2u + cnt.t_tri : 0u;
-        if (!(a.dbg & 4u)) hit = trace<STACK, STATS, !STATS, DEFER, COOP, TEXD, CNTD>(s, ray, false, h, stk, cnt, deferred, stride, lds_nodes, skip, rects);
+        if (!(a.dbg & 4u)) hit = trace<STACK, STATS, !STATS, DEFER, COOP, TEXD, CNTD, DEFER, false, !DEFER || SMPD>(s, ray, false, h, stk, cnt, deferred, stride, lds_nodes, skip, rects);
         if (CNTD) walk_units = cnt.t_inner4 * 2u + cnt.t_tri - units0;
         if (!deferred && leader) {
             if (!hit) {
@@ -1530,7 +1531,7 @@ __global__ void __launch_bounds__(64) RTU_OCC_GI_ROOTS k_gi_roots(KernelArgs a, 
 
 // NODE-LEVEL BOUNDS of primary rays (recipe W): per camera of the launch and per node, the rectangle of pixels whose
 // primary ray can come within the cull margin of the node's world-space bound — the eight corners of the bound, widened by
-// delta = 1e-4 * max(scene scale, |camera|), projected through the camera in binary64, two pixels of slack on every side.
+// delta = cull_margin(|camera|) (rtu_intersect.h), projected through the camera in binary64, two pixels of slack on every side.
 // A corner at or behind the camera plane makes the rectangle the whole image. One lane per (camera, node).
 __device__ __forceinline__ void node_rects_body(const KernelArgs& a, uint32_t entries) {
     const uint32_t n_nodes = a.scene.n_nodes;
@@ -1549,7 +1550,7 @@ __device__ __forceinline__ void node_rects_body(const KernelArgs& a, uint32_t en
             // w = c * (O + a U + b V): Cramer's rule on [U V O]
             const double det = U[0] * (V[1] * O[2] - V[2] * O[1]) - V[0] * (U[1] * O[2] - U[2] * O[1]) + O[0] * (U[1] * V[2] - U[2] * V[1]);
             const double pm = fmax(fabs(P[0]), fmax(fabs(P[1]), fabs(P[2])));
-            const double delta = 1e-4 * fmax((double)a.scene.wscale, pm);
+            const double delta = cull_margin_d(a.scene, pm);
             double amin = 1e300, amax = -1e300, bmin = 1e300, bmax = -1e300;
             bool all_front = det != 0.0;
             for (int c = 0; c < 8 && all_front; c++) {
@@ -1606,7 +1607,7 @@ __device__ __forceinline__ void mesh_cover_body(const KernelArgs& a, uint32_t en
     const f3 lo = mk3(blo.x, blo.y, blo.z), hi = mk3(bhi.x, bhi.y, bhi.z);
     const float pm = fmaxf(fabsf(P.x), fmaxf(fabsf(P.y), fabsf(P.z)));
     const float big = fmaxf(fmaxf(fabsf(lo.x), fabsf(hi.x)), fmaxf(fmaxf(fabsf(lo.y), fabsf(hi.y)), fmaxf(fabsf(lo.z), fabsf(hi.z))));
-    const float wid = 1e-4f * fmaxf(a.scene.wscale, pm) + 1e-5f * big;  // the cull margin for this camera + the rounding of the chain
+    const float wid = cull_margin(a.scene, pm) + 1e-5f * big;  // the cull margin for this camera + the rounding of the chain
     float amin = 3e38f, amax = -3e38f, bmin = 3e38f, bmax = -3e38f;
     bool ok = det != 0.0f && wid == wid;
     const float rdet = 1.0f / det;
@@ -1649,8 +1650,8 @@ __device__ __forceinline__ void mesh_cover_body(const KernelArgs& a, uint32_t en
 // the launch and masked plane. A Plane is the unit square of its node (objFunctions.cpp:107-140: the hit must lie strictly
 // inside (-1,1)^2 of the node's z = 0); the screen RECTANGLE of a square seen at an angle is mostly air (the headline's ground
 // is a diamond: half of its rectangle). So the square itself is projected: its four world-space corners (upload, binary64), each
-// pushed outwards along both of its edges by the cull margin for this camera (delta = 1e-4 max(scene scale, |camera|): a hundred
-// times the rounding of the reference's own ray / square arithmetic, as for the node bounds) divided by the sine of the corner's
+// pushed outwards along both of its edges by the cull margin for this camera (delta = cull_margin(|camera|), rtu_intersect.h: a hundred
+// times the rounding of the reference's own ray / square arithmetic plus what Node::ToNodeCoords moves the ray, as for the node bounds) divided by the sine of the corner's
 // angle, through the camera in binary64 like the node bound's corners; a tile — widened by two pixels on every side — is marked
 // unless a separating line is found: the quadrilateral's bounding box, or one of its four edges with the whole tile beyond it.
 // A corner at or behind the camera plane, a sliver of a corner (sine < 0.05) or a NaN makes the mask unusable (word 0 = 1).
@@ -1674,7 +1675,7 @@ __device__ __forceinline__ void plane_cover_body(const KernelArgs& a, uint32_t e
         const double O[3] = {co[0] - P[0], co[1] - P[1], co[2] - P[2]};
         const double det = U[0] * (V[1] * O[2] - V[2] * O[1]) - V[0] * (U[1] * O[2] - U[2] * O[1]) + O[0] * (U[1] * V[2] - U[2] * V[1]);
         const double pm = fmax(fabs(P[0]), fmax(fabs(P[1]), fabs(P[2])));
-        const double delta = 1e-4 * fmax((double)s.wscale, pm);
+        const double delta = cull_margin_d(s, pm);
         const float (*q)[3] = s.pcover_quad[c];
         const uint32_t ip = (i + 3u) & 3u, in = (i + 1u) & 3u;
         double w[3], ua[3], ub[3], la = 0, lb = 0, big = 0;

@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(64) RTU_OCC_WALK k_ray_roots(KernelArgs a, con
         if (valid) {
             RTU_CNT(prim);
             bool deferred;
-            const bool hit = trace<STACK, STATS, !STATS, false, false, TEXD, false>(s, ray, false, h, s_stack + lane, cnt, deferred);
+            const bool hit = trace<STACK, STATS, !STATS, false, false, TEXD, false, false, false, true>(s, ray, false, h, s_stack + lane, cnt, deferred);  // FAR: any origin
             if (!hit) {
                 const f3 env = (TEXD && s.env.has_map) ? env_sample(s, ray.dir) : ld3(s.environment);
                 a.out[i] = make_float4(env.x, env.y, env.z, h.z);  // h.z: still tmax

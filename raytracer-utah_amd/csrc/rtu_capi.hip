@@ -549,6 +549,60 @@ void renumber_bfs(const RtuMesh& m, std::vector<RtuBvhNode>& bfs, uint32_t& any_
     }
 }
 
+// The constants of the part of the cull margin that grows with the distance of a ray's origin, and of a sphere's slack along the
+// ray (derived at cull_margin and sphere_slack, rtu_intersect.h): per node the condition numbers along its chain, root first.
+struct WorldFar {
+    float wnoise, wreach, sph_k, sph_r;
+};
+namespace {
+double abs_row_norm(const double* m) {  // || |M| ||_inf of a row-major 3 x 3 matrix
+    double r = 0;
+    for (int i = 0; i < 3; i++) r = std::max(r, std::fabs(m[3 * i]) + std::fabs(m[3 * i + 1]) + std::fabs(m[3 * i + 2]));
+    return r;
+}
+void mul33(const double* a, const double* b, double* out) {
+    double t[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) t[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+    memcpy(out, t, sizeof t);
+}
+}  // namespace
+void world_far(const RtuSceneDesc* s, double wscale, WorldFar& out) {
+    const double u = 0x1p-24;
+    double K = 0, omega = 0, sph_cond = 0, sph_T = 0;
+    for (uint32_t i = 0; i < s->n_nodes; i++) {
+        const int type = s->nodes[i].obj_type;
+        if (type != RTU_OBJ_SPHERE && type != RTU_OBJ_PLANE && type != RTU_OBJ_TRIMESH) continue;
+        std::vector<int> chain;
+        for (int j = (int)i; j >= 0; j = s->nodes[j].parent) chain.push_back(j);
+        // root first: T = tm_0 ... tm_(j-1) takes space j to the world, Ti is its inverse, o the world position of the origin of space j
+        double T[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Ti[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
+        double k_node = 0, om = 0;
+        for (size_t c = chain.size(); c-- > 0;) {
+            const RtuNode& a = s->nodes[chain[c]];
+            double tm[9], itm[9], prod[9];
+            for (int r = 0; r < 3; r++)
+                for (int q = 0; q < 3; q++) { tm[3 * r + q] = a.tm[3 * q + r]; itm[3 * r + q] = a.itm[3 * q + r]; }  // (RtuNode: column-major)
+            for (int r = 0; r < 3; r++)
+                for (int q = 0; q < 3; q++)
+                    prod[3 * r + q] = std::fabs(tm[3 * r]) * std::fabs(itm[q]) + std::fabs(tm[3 * r + 1]) * std::fabs(itm[3 + q]) + std::fabs(tm[3 * r + 2]) * std::fabs(itm[6 + q]);
+            k_node += abs_row_norm(T) * abs_row_norm(Ti) * (3.0 + 6.0 * abs_row_norm(prod));
+            for (int r = 0; r < 3; r++) o[r] += T[3 * r] * a.pos[0] + T[3 * r + 1] * a.pos[1] + T[3 * r + 2] * a.pos[2];
+            om = std::max(om, std::max(std::fabs(o[0]), std::max(std::fabs(o[1]), std::fabs(o[2]))));
+            mul33(T, tm, T);
+            mul33(itm, Ti, Ti);
+        }
+        const double cond = abs_row_norm(T) * abs_row_norm(Ti);
+        if (!std::isfinite(k_node) || !std::isfinite(om) || !std::isfinite(cond)) continue;  // such a node has no bound at all (world_bounds)
+        K = std::max(K, k_node);
+        omega = std::max(omega, om);
+        if (type == RTU_OBJ_SPHERE) { sph_cond = std::max(sph_cond, cond); sph_T = std::max(sph_T, abs_row_norm(T)); }
+    }
+    out.wnoise = (float)(1.74 * u * K * (1 + 1e-6));
+    out.wreach = (float)(std::max(wscale, omega + 1.0) * (1 + 1e-6));
+    out.sph_k = (float)(5.2e-3 * sph_cond * (1 + 1e-6));
+    out.sph_r = (float)(1.74 * sph_T * (1 + 1e-6));
+}
 // NODE-LEVEL BOUNDS (DevNode::wmin / wmax; the argument is in rtu_intersect.h, trace): the object's own bounding box —
 // the unit cube of a sphere, the unit square of a plane (objects.h:25,37), the mesh's box — taken corner by corner through
 // the node's chain of transformations (p -> tm p + pos, scene.h:508-512) in binary64, then widened by
@@ -558,6 +612,8 @@ void renumber_bfs(const RtuMesh& m, std::vector<RtuBvhNode>& bfs, uint32_t& any_
 //     grazing root is off by up to ~5e-4 * D in t; with D bounded by the scene's diameter S both stay below
 //     4e-6 * S^2 / R + 1e-3 * S ... the latter only matters when R < 1e-3 * S, where the former is already larger. R is the
 //     smallest half-extent of the sphere's world box.
+//     (That D is the distance inside the scene. A ray from further away is covered per ray: rtu_intersect.h, cull_margin and
+//     sphere_slack.)
 // Returns the largest |coordinate| of all bounds (the scale of the per-ray margin).
 float world_bounds(const RtuSceneDesc* s, std::vector<DevNode>& nodes) {
     const uint32_t n = s->n_nodes;
@@ -1842,6 +1898,12 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
     ds.img_w = s->camera.img_width;
     ds.img_h = s->camera.img_height;
     ds.wscale = wscale;
+    WorldFar far;
+    world_far(s, wscale, far);
+    ds.wnoise = far.wnoise;
+    ds.wreach = far.wreach;
+    ds.wsphere_k = far.sph_k;
+    ds.wsphere_r = far.sph_r;
     ds.nol_ok = 1;
     for (uint32_t i = 0; i < s->n_lights; i++)
         for (int k = 0; k < 3; k++)

@@ -158,7 +158,8 @@ struct DevScene {
     RtuTexMap bg_map, env_map;      // present only with a real texture
     RtuEnvColor bg, env;
     int32_t  img_w, img_h;          // camera.imgWidth / imgHeight: the background is sampled at (x/imgWidth, y/imgHeight)
-    uint32_t textured, pad_tex;
+    uint32_t textured;
+    float    wnoise;            // factor of the cull margin's term in the square of the origin's distance (rtu_intersect.h: cull_margin)
     uint32_t n_nodes, n_lights;
     uint32_t walk_stack_limit;  // test hook (rtu_debug_walk_stack_limit): stack entries the walks of the fast trees may use
     float    wscale;            // largest |coordinate| of any node-level bound: the scale of the cull margin in world space
@@ -170,10 +171,12 @@ struct DevScene {
     uint32_t cover_nf[8];       //   binary64, rounded outwards), and the triangle count   // every non-ambient light's intensity is finite and below 1e15 (make_info: lights behind the surface)
     // PLANE nodes get a coverage mask too (slots n_cover .. n_cover + n_pcover - 1 of KernelArgs::cover): a Plane is the unit square of
     // its node, and the screen rectangle of a square seen at an angle is mostly air (k_plane_cover projects the square itself)
-    uint32_t n_pcover, pad_pc;
+    uint32_t n_pcover;
+    float    wreach;            // max(wscale, 1 + largest |coordinate| of the origin of any node's space): what cull_margin adds to |origin|
     int32_t  pcover_node[RTU_MAX_PCOVER];
     float    pcover_quad[RTU_MAX_PCOVER][4][3];  // the square's corners (-1,-1) (1,-1) (1,1) (-1,1) through the node's chain of transformations (binary64, rounded)
     uint32_t dbg;               // experiment switches (rtu_debug_flags), as KernelArgs::dbg
+    float    wsphere_k, wsphere_r;  // what a sphere's root can lie outside its box along the ray (rtu_intersect.h: sphere_slack)
     uint32_t node_bounds;       // 0: node-level bounds off (test hook rtu_debug_node_bounds; results must not change)
     float    background[3];     // background.Sample(...) for an untextured / NULL-map background
     float    environment[3];    // environment.SampleEnvironment(...) likewise

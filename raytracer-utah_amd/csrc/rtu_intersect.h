@@ -671,13 +671,66 @@ __device__ __forceinline__ bool fast_box(const FastRay& f, float4 lo, float4 hi,
     const float tf = fminf(fminf(fmaf(fx, f.r.x, f.cf.x), fmaf(fy, f.r.y, f.cf.y)), fmaf(fz, f.r.z, f.cf.z));
     return tn <= tf && tn <= hz && tf >= 0.0f;
 }
+// ... for the node-level bounds: `slack` widens the segment [0, hz] at both ends (0 but for a sphere: sphere_slack below)
+__device__ __forceinline__ bool fast_box_node(const FastRay& f, f3 lo, f3 hi, float hz, float slack) {
+    const float nx = f.px ? lo.x : hi.x, fx = f.px ? hi.x : lo.x;
+    const float ny = f.py ? lo.y : hi.y, fy = f.py ? hi.y : lo.y;
+    const float nz = f.pz ? lo.z : hi.z, fz = f.pz ? hi.z : lo.z;
+    const float tn = fmaxf(fmaxf(fmaf(nx, f.r.x, f.cn.x), fmaf(ny, f.r.y, f.cn.y)), fmaf(nz, f.r.z, f.cn.z));
+    const float tf = fminf(fminf(fmaf(fx, f.r.x, f.cf.x), fmaf(fy, f.r.y, f.cf.y)), fmaf(fz, f.r.z, f.cf.z));
+    return tn <= tf && tn <= hz + slack && tf >= -slack;
+}
 
+// THE CULL MARGIN IN WORLD SPACE of a ray that starts at a point whose largest |coordinate| is pm:
+//     delta = 1e-4 * max(wscale, pm) + wnoise * (min(pm, 2^25) + wreach)^2
+// The first term is the margin of "Culling" above: a hundred times the rounding of a slab bound or a hit point. The second is what
+// the reference's own transformation of the ray moves the line that its objects are tested against. Node::ToNodeCoords
+// (scene.h:501-507, to_node above) takes the direction as itm ((p + dir) - pos) - itm (p - pos) in binary32: with u = 2^-24 and
+// m the largest |coordinate| of p, p - pos and dir in that node's parent space, the roundings of p + dir, of the two differences
+// with pos (each <= u m per component) and of the two products with itm (each <= 3 u |itm| m, 6 u kappa m once taken back through
+// tm, kappa = || |tm| |itm| ||_inf) change the direction by up to (3 + 6 kappa) u m per unit of t. m is at most || |T^-1| ||_inf
+// times the distance from the ray's origin to the origin of that space, T being the product of the tm above the node, and the change
+// returns to world space through T. Summed along the chain of a node, root first,
+//     K = sum_j || |T_j| ||_inf || |T_j^-1| ||_inf (3 + 6 kappa_j)            (18 for an unrotated node under an identity root)
+// and the line the node's object is tested against leaves the caller's line by at most K u (pm + Omega + 1) per unit of t, Omega
+// being the largest |coordinate| of the origin of any space. Every point of every node's bound is within sqrt(3) (pm + wscale) of the
+// ray's origin and |dir| >= 0.999, so at the bound the two lines are at most
+//     1.74 K u (pm + Omega + 1) (pm + wscale)  <=  wnoise (pm + wreach)^2,   wnoise = 1.74 u max K,  wreach = max(wscale, Omega + 1)
+// apart on every axis (world_far, rtu_capi.hip, computes both). A hit the reference reports at t lies on ITS line inside the
+// object's box (within rounding), so the caller's line at the same t lies inside the box inflated by that much: tn <= t, and a
+// node whose inflated box begins beyond the best hit so far cannot beat it. 100 units from a scene 50 units across the second term
+// is 0.04 units, four times the first; 5000 units away it is 50 units, where the reference's line is in fact some 2.5 units off
+// (tests/test_oracle_far.py). Beyond |p| = 2^25 the sum p + dir is p: the reference's direction is zero, nothing grows any more.
+// THE SPHERE needs more along the ray, and only there. Sphere::IntersectRay (objFunctions.cpp:17-100) accepts whatever roots the
+// binary32 b*b - 4*a*c gives once the ray passes the unit cube. With P = |p| |dir| in the sphere's space, b*b carries an error of up
+// to 28 u P^2 (the dot product: 3 u P, doubled, squared and rounded), 4*a*c up to 32 u P^2: the discriminant is off by up to
+// 60 u P^2, its square root by up to sqrt(60 u) P = 1.9e-3 P, a root by up to 9.5e-4 |p| / |dir| in t — noise as soon as the true
+// chord is shorter, i.e. from |p| ~ 600 radii on (at 1000 radii the reference's sphere has hits with an impact parameter of 1.12, at
+// 5000 of 1.29, tests/test_oracle_far.py). The reported hit is the point of the reference's line at that root, so sideways it is
+// covered by cull_margin; along the ray it can lie in front of the box or behind it. The true roots, or with a negative true
+// discriminant the point of closest approach -b / 2a that the noisy roots surround, are within sqrt(3) of the sphere's centre
+// (the line passes the unit cube), i.e. within sqrt(3) / |dir| of the cube's own interval in t. Taken to world units through the
+// node's chain T (|p| / |dir| <= 3 cond(T) times the world distance, itself <= sqrt(3) (pm + Omega) / 0.999; 1 / |dir| <= ||T||):
+//     slack = 5.2e-3 max cond(T) (pm + wreach) + 1.74 max || |T| ||_inf       (maxima over the sphere nodes; world_far, rtu_capi.hip)
+// and a sphere node is skipped only if its inflated box begins more than `slack` beyond the best hit so far, or ends more than
+// `slack` behind the origin. Planes and meshes accept a hit only at a point inside the square or a triangle: no slack.
+__device__ __forceinline__ float sphere_slack(const DevScene& s, float pm) { return s.wsphere_k * (fminf(pm, 0x1p25f) + s.wreach) + s.wsphere_r; }
+__device__ __forceinline__ float cull_margin(const DevScene& s, float pm) {
+    const float q = fminf(pm, 0x1p25f) + s.wreach;
+    return 1e-4f * (s.wscale > pm ? s.wscale : pm) + s.wnoise * q * q;
+}
+__device__ __forceinline__ double cull_margin_d(const DevScene& s, double pm) {
+    const double q = fmin(pm, 0x1p25) + (double)s.wreach;
+    return 1e-4 * fmax((double)s.wscale, pm) + (double)s.wnoise * q * q;
+}
 // fast_ray for the node-level bounds: the reciprocals need not be correctly rounded (v_rcp_f32 is within 1 ulp, five
-// orders of magnitude inside the margin), and the scale of the margin is the scene's.
-__device__ __forceinline__ FastRay fast_ray_world(const Ray& ray, float sceneScale) {
+// orders of magnitude inside the margin). FAR: the margin of a ray that may start anywhere (cull_margin); else that of a ray
+// that starts in or around the scene.
+template <bool FAR>
+__device__ __forceinline__ FastRay fast_ray_world(const Ray& ray, const DevScene& s) {
     const float tiny = 0x1p-100f;
     const float pm = fmaxf(fabsf(ray.p.x), fmaxf(fabsf(ray.p.y), fabsf(ray.p.z)));
-    const float delta = 1e-4f * (sceneScale > pm ? sceneScale : pm);
+    const float delta = FAR ? cull_margin(s, pm) : 1e-4f * (s.wscale > pm ? s.wscale : pm);
     const float dx = fabsf(ray.dir.x) < tiny ? copysignf(tiny, ray.dir.x) : ray.dir.x;
     const float dy = fabsf(ray.dir.y) < tiny ? copysignf(tiny, ray.dir.y) : ray.dir.y;
     const float dz = fabsf(ray.dir.z) < tiny ? copysignf(tiny, ray.dir.z) : ray.dir.z;
@@ -1138,18 +1191,27 @@ __device__ __forceinline__ int mesh_shadow_cells(const uint32_t* cell_tri, uint3
 // again with DEFER=false. Rays that never touch a mesh complete in stage 1.
 //
 // NODE-LEVEL BOUNDS (CULL only, i.e. the fast variant; DevNode::wmin / wmax). Every hit the reference can report lies, within
-// rounding, inside the object's own bounding box: Box::IntersectRay on that box is the first thing Sphere / Plane /
-// TriObj::IntersectRay do (objFunctions.cpp:17, :109, :335), its slab arithmetic is good to a few ulp of the ray's
-// coordinates, and where its exactly-zero-direction branches ignore an axis (:154-216) the accepted hit point itself is on
-// the sphere, inside the square or inside a triangle. So a ray whose line, between its origin and the best hit so far, stays
-// clear of the box by delta = 1e-4 * max(scene scale, |origin|) on some axis — the geometric form of "Culling" above, on
-// the world-space box of the node — cannot produce a result there, and the node is skipped before its transformation
-// and exact test. (The margin is 100 x the slab rounding; the bound of a sphere is widened further at upload by what the
-// cancellation in its discriminant can move a grazing root, rtu_capi.hip world_bounds.) `skip` marks nodes the caller
+// rounding, inside the object's own bounding box ON THE LINE THE REFERENCE TESTS: Box::IntersectRay on that box is the first
+// thing Sphere / Plane / TriObj::IntersectRay do (objFunctions.cpp:17, :109, :335), its slab arithmetic is good to a few ulp of
+// the ray's coordinates, and where its exactly-zero-direction branches ignore an axis (:154-216) the accepted hit point is
+// inside the square or inside a triangle — or, for a sphere, anywhere on that line within sphere_slack of the cube. That line
+// is the caller's ray as Node::ToNodeCoords restates it, which leaves the caller's line by up to the second term of cull_margin.
+// FAR takes both into account. It is set by every walk whose ray can start anywhere: caller-supplied rays (rtu_query.hip,
+// render_rays_impl.h) and the render kernels' primary rays wherever they are bounded per ray — stage 2 of recipe W (a deferred
+// pixel is traced again without its rectangles) and both stages of recipes S / P, which have no rectangles (render_impl.h,
+// primary_pixel). Stage 1 of recipe W goes by the node rectangles and coverage masks, which carry cull_margin. Secondary and
+// shadow rays, and the gather rays of recipe P, start at hit points, i.e. on the scene's surfaces, and keep
+// delta = 1e-4 * max(scene scale, |origin|) and no slack: in k_trace the two terms cost scalar registers it does not have
+// (NOTEBOOK.md section 14).
+// So a ray whose line, between its origin and the best hit so far (for a sphere: sphere_slack further at both ends), stays
+// clear of the box by delta = cull_margin(|origin|) on some axis — the geometric form of "Culling" above, on the world-space
+// box of the node — cannot produce a result there, and the node is skipped before its transformation and exact test.
+// (The bound of a sphere is also widened at upload by what the cancellation in its discriminant can move a grazing root for
+// origins inside the scene, rtu_capi.hip world_bounds.) `skip` marks nodes the caller
 // has already excluded in the same sense: for primary rays, pixels outside the node's screen rectangle (k_node_rects).
 // INL (with DEFER): the occluder lists are walked HERE, in stage 1 (the inline shading of childless Shade() calls, render_impl.h
 // shadows_inline): `deferred` then means "this ray cannot be settled without a BVH walk".
-template <int STACK, bool STATS, bool CULL, bool DEFER, bool COOP = false, bool TEX = false, bool FC = false, bool ULS = DEFER, bool INL = false>
+template <int STACK, bool STATS, bool CULL, bool DEFER, bool COOP = false, bool TEX = false, bool FC = false, bool ULS = DEFER, bool INL = false, bool FAR = false>
 __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool shadow, Hit& h, uint32_t* stk, Counters& cnt, bool& deferred,
                                       const uint32_t stride = 64, const float4* lds_nodes = nullptr, const unsigned long long skip = 0,
                                       const bool rays_bounded = false, const int lslot = -1) {
@@ -1157,7 +1219,7 @@ __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool sha
     RTU_TOUCH(t_rays, 1);
     const bool bounds = CULL && s.node_bounds != 0 && !rays_bounded;  // wave-uniform
     FastRay wf = {};
-    if (bounds) wf = fast_ray_world(wr, s.wscale);
+    if (bounds) wf = fast_ray_world<FAR>(wr, s);
     const RTU_CONST DevNode* nodes = as_const(s.nodes);
     const RTU_CONST DevMesh* meshes = as_const(s.meshes);
     bool any = false;
@@ -1227,9 +1289,14 @@ __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool sha
             }
         }
         if (bounds) {
-            float tn;
             RTU_TOUCH_WAVE(t_bounds, 1);
-            if (!fast_box(wf, make_float4(n.wmin[0], n.wmin[1], n.wmin[2], 0.0f), make_float4(n.wmax[0], n.wmax[1], n.wmax[2], 0.0f), h.z, tn)) continue;
+            if (FAR) {
+                const float slack = n.obj_type == RTU_OBJ_SPHERE ? sphere_slack(s, fmaxf(fabsf(wr.p.x), fmaxf(fabsf(wr.p.y), fabsf(wr.p.z)))) : 0.0f;
+                if (!fast_box_node(wf, mk3(n.wmin[0], n.wmin[1], n.wmin[2]), mk3(n.wmax[0], n.wmax[1], n.wmax[2]), h.z, slack)) continue;
+            } else {
+                float tn;
+                if (!fast_box(wf, make_float4(n.wmin[0], n.wmin[1], n.wmin[2], 0.0f), make_float4(n.wmax[0], n.wmax[1], n.wmax[2], 0.0f), h.z, tn)) continue;
+            }
         }
         int parent = n.parent;
         Ray pr;

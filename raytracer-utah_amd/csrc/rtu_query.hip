@@ -34,7 +34,7 @@ __device__ __forceinline__ bool query_trace(const DevScene& s, const float4& a, 
     Counters cnt = {};
     bool deferred;
     if (REFWALK) return trace<RTU_MAX_BVH_STACK, true, false, false>(s, ray, SHADOW, h, stk, cnt, deferred);
-    return trace<RTU_MAX_BVH_STACK, false, true, false>(s, ray, SHADOW, h, stk, cnt, deferred);
+    return trace<RTU_MAX_BVH_STACK, false, true, false, false, false, false, false, false, true>(s, ray, SHADOW, h, stk, cnt, deferred);  // FAR: any origin
 }
 
 template <bool REFWALK>
