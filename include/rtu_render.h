@@ -398,7 +398,8 @@ int  rtu_shade_rays_device(RtuContext* ctx, const void* d_rays, size_t n, const 
 int  rtu_shade_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats);
 
 /* ---- Sampled ray batches: recipe S along caller-supplied rays (render_rays2.hip / render_rays3.hip) ---------------------------------
- * rtu_shade_rays with ONE Shade() call of RECIPE S per ray (direct lighting only: gather_bounces 0): soft shadows and glossy bounces on
+ * rtu_shade_rays with ONE Shade() call of RECIPE S per ray (direct lighting only: gather_bounces 0; rtu_shade_rays_paths / _device below
+ * add the Monte-Carlo gather of recipe P per ray): soft shadows and glossy bounces on
  * the sample streams stated above ("Sample streams of recipe S"). keys[i] is the `key` of ray i's root Shade() call — what
  * sample_key(p, i) is to a sample of a pixel: the disk sample of light l draws from rand31(key, 16 + 2 l ...), the glossy normals of the
  * root call from 0x10000 / 0x20000 / 0x30000 ..., and the Shade() of the hit of secondary ray `slot` continues with
@@ -422,6 +423,39 @@ int  rtu_shade_rays_sampled_device(RtuContext* ctx, const void* d_rays, const vo
                                    void* hip_stream);
 int  rtu_shade_rays_sampled(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_rgbt,
                             RtuStats* stats);
+/* ---- Path-traced ray batches: recipe P along caller-supplied rays (render_rays4.hip / render_rays5.hip, render_paths_impl.h) ---------
+ * rtu_shade_rays_sampled with the 4-bounce Monte-Carlo gather of recipe P behind every hit (RenderFunctions.cpp:129-135, :549-590,
+ * :320-337): indirect light for a light-map bake, an environment probe, a fisheye or panoramic sensor. Per ray one float4 {r, g, b, t}
+ * under the rules of rtu_shade_rays_sampled, except:
+ *   hit      rgb = Shade(h0, lights + MonteCarlo's AmbientLight) + Shade(h0, lights), exactly what a recipe-P sample of a pixel gets
+ *            (:134-135); t = hInfo.z. A node without material gives white, t = hInfo.z, and gathers nothing.
+ *   miss     environment.SampleEnvironment(dir), t = tmax. An invalid ray: sixteen zero bytes, not traced, no chain.
+ *   keys     keys[i] is the key of ray i's root call. The hemisphere sample at a chain hit draws from that hit's key with purposes
+ *            0x40000 / 0x40001, the gather ray's hit continues with child_key(key, 3), the AmbientLight tree with child_key(key, 4):
+ *            all as stated for RtuFrameDesc.gather_bounces. The gather depth is the reference's 4 (monteCarloBounces); it is not a
+ *            parameter. eye and max_bounce apply to every Shade() tree of the chain, as cam_pos and max_bounce of a recipe-P frame do.
+ * Against a render: the rays and keys of rtu_camera_sample_rays(frame, k) shaded with eye = cam_pos equal
+ * rtu_debug_sample_images(frame with gather_bounces = 4, k, 1) bit for bit — t at every ray, rgb at every hit ray.
+ * flags, stats, RtuRay.reserved and every error are as for the sampled pair (NULL and misaligned pointers, unknown flag bits, reserved,
+ * max_bounce, a non-finite eye, RTU_ERR_NO_SCENE; n == 0 is RTU_OK and launches nothing); a scene without stochastic features is
+ * accepted. LIMIT: a chain costs 352 bytes of chain records and results (5 depths x 4 float4 + 2 float4), so the _device form takes
+ * the recipe-P frame path's own cap on chains per launch sequence: n <= 2^25 (the 2^25 pixels a batch of samples of a recipe S / P
+ * frame may have by default; the frame path's tuning knob RTU_GI_BATCH_LOG2 does not move this limit), RTU_ERR_ARG beyond. The host form works in chunks of at most 2^20 rays.
+ * THE CALL IS A RENDER: it uses the context's frame records, append counters, chain records and results (grow-only, shared with
+ * recipe-P frames) and launch hints under a key of its own; the ONE STREAM PER CONTEXT rule applies. The _device form queues the whole
+ * sequence asynchronously on hip_stream — the roots, four chain steps, five shading steps from the deepest depth up, the final sum —;
+ * rtu_frame_status afterwards reports completeness, and on RTU_ERR_CAPACITY the caller calls the _device form again. The host form
+ * repeats the shading steps of a chunk itself with the grown capacities (chain records do not depend on them) and is synchronous.
+ * The counting variant (RTU_QUERY_REFERENCE_WALK, or stats non-NULL in the host form) gives the same bytes; its counters are summed
+ * over the chunks; gather rays are in no ray counter, as in a recipe-P frame (their traversal counters are). As a recipe-P frame with
+ * counters, the host form does not repeat a counting chunk that ran out of frame records: it returns RTU_ERR_CAPACITY — shade the
+ * batch once without counters first. rtu_debug_flags 64 and 2048, rtu_debug_node_bounds, rtu_debug_walk_stack_limit and
+ * rtu_debug_tail_from apply and change no bit; a cut level forced by rtu_debug_tail_from skips the chain steps, which have no recursion
+ * levels, and applies to all five shading steps of the next call (in the host form: of its first chunk's first attempt). */
+int  rtu_shade_rays_paths_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_rgbt,
+                                 void* hip_stream);
+int  rtu_shade_rays_paths(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_rgbt,
+                          RtuStats* stats);
 /* The primary rays and keys of sample `sample` (0 <= sample < frame->samples) of the recipe S frame `frame`, image rows
  * [row0, row0 + nrows), width * nrows of each in image order; shards are ignored. key = sample_key(x + width * y, sample); the pixel
  * offset is sample / S + Halton(sample, 4 | 5) in x | y (RenderFunctions.cpp:80-85, :96); the origin is the lens point
@@ -496,6 +530,9 @@ int  rtu_timeline_exits(RtuContext* ctx, int slot, int max_values, double* exit_
  * incomplete like a capacity overflow (rtu_frame_status) and rendered again level by level.
  * This sets the cut level for the NEXT launch only (taken as it is, never refused): 1..5, or 6 for "no tail". */
 int  rtu_debug_tail_from(RtuContext* ctx, int level);
+/* Test hook: the cut level the most recent launch of the recursion levels was made with — 1..5, or 6 for "no tail" (also what the
+ * counting variant always uses) —, whether forced by rtu_debug_tail_from or learned. RTU_ERR_ARG for a NULL context. */
+int  rtu_debug_last_tail_from(RtuContext* ctx);
 
 /* Test hook: switch the node-level bounds of the fast variant off (0) or on (1, the default after an upload) until the next
  * upload: the world-space box per scene node and, for primary rays, its screen rectangle per camera, by which a ray skips

@@ -155,7 +155,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing",
                "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays",
                "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays",
-               "rtu_shade_rays_sampled_device", "rtu_shade_rays_sampled", "rtu_camera_sample_rays", "rtu_sample_key", "rtu_child_key"]
+               "rtu_shade_rays_sampled_device", "rtu_shade_rays_sampled", "rtu_camera_sample_rays", "rtu_sample_key", "rtu_child_key",
+               "rtu_shade_rays_paths_device", "rtu_shade_rays_paths", "rtu_debug_last_tail_from"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -185,6 +186,7 @@ _sig(hip, "rtu_debug_node_bounds", _I, _P, _I)
 _sig(hip, "rtu_debug_flags", _I, _P, ctypes.c_uint32)
 _sig(hip, "rtu_set_sequences_in_flight", _I, _P, _I)
 _sig(hip, "rtu_debug_tail_from", _I, _P, _I)
+_sig(hip, "rtu_debug_last_tail_from", _I, _P)
 _sig(hip, "rtu_timeline_exits", _I, _P, _I, _I, ctypes.POINTER(ctypes.c_double))
 _sig(hip, "rtu_mesh_info", _I, _P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32))
 _sig(hip, "rtu_light_list_info", _I, _P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32))
@@ -299,6 +301,8 @@ _sig(hip, "rtu_shade_rays_device", _I, _P, _P, ctypes.c_size_t, ctypes.POINTER(R
 _sig(hip, "rtu_shade_rays", _I, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
 _sig(hip, "rtu_shade_rays_sampled_device", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
 _sig(hip, "rtu_shade_rays_sampled", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
+_sig(hip, "rtu_shade_rays_paths_device", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
+_sig(hip, "rtu_shade_rays_paths", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
 _sig(hip, "rtu_camera_sample_rays", _I, ctypes.POINTER(RtuFrameDesc), _I, _I, _I, _P, _P)
 _sig(hip, "rtu_sample_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
 _sig(hip, "rtu_child_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
@@ -973,6 +977,27 @@ class Context:
         (device memory), asynchronous on `stream`; frame_status() afterwards as for render_device."""
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         self._check(hip.rtu_shade_rays_sampled_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
+
+    def shade_rays_paths(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+        """Recipe P along caller-supplied rays (rtu_shade_rays_paths): as shade_rays_sampled, with the 4-bounce Monte-Carlo gather
+        behind every hit — rgb = Shade(hit, lights + the gathered AmbientLight) + Shade(hit, lights). keys[i] is the key of ray i's
+        root call; the gather draws from it as a recipe-P frame does. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None)."""
+        import numpy as np
+        r = _as_rays(rays)
+        k = _as_keys(keys, r.size)
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        out = np.zeros((r.size, 4), np.float32)
+        st = RtuStats() if stats else None
+        self._check(hip.rtu_shade_rays_paths(self._h, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None, r.size, ctypes.byref(d),
+                                             out.ctypes.data if r.size else None, ctypes.byref(st) if stats else None))
+        return out, (st.as_dict() if stats else None)
+
+    def shade_rays_paths_device(self, d_rays_ptr, d_keys_ptr, n, eye, d_rgbt_ptr, stream=None, max_bounce=5, reference_walk=False, desc=None):
+        """rtu_shade_rays_paths_device: n RtuRay at d_rays_ptr and n uint32 keys at d_keys_ptr -> n float4 {r, g, b, t} at d_rgbt_ptr
+        (device memory, n <= 2^25), the whole sequence asynchronous on `stream`; frame_status() afterwards as for render_device
+        (RTU_ERR_CAPACITY: call this again)."""
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        self._check(hip.rtu_shade_rays_paths_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
 
     def occluded_device(self, d_rays_ptr, n, d_occluded_ptr, stream=None, reference_walk=False, flags=None):
         """rtu_occluded_rays_device: n RtuRay at d_rays_ptr -> n bytes (1 / 0) at d_occluded_ptr, asynchronous on `stream`."""

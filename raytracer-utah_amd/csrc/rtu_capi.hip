@@ -1189,6 +1189,9 @@ float halton(int index, int base) {
 // "tile" is a chunk of 64 rays (k_ray_roots): no screen rectangles, coverage masks or tile occupancy, no side mode, hint keys of its own.
 // d_keys: the ray batch is SAMPLED (rtu_shade_rays_sampled): `frame` is a recipe-S frame with samples = 1, d_keys[i] the key of ray i's root
 // Shade() call; the pointer travels in KernelArgs::cam (ray_keys, render_impl.h), which a ray batch leaves idle.
+// d_rays with d_keys and a gi_mode: one step of a PATH-TRACED ray batch (rtu_shade_rays_paths): chain i is ray i, gi_total = n_rays.
+// RTU_LAUNCH_CHAIN at depth 0 traces the roots (render_rays4.hip / render_rays5.hip), at depth 1 .. 4 the gather rays; RTU_LAUNCH_SHADE
+// is the frame path's own (k_gi_roots, the levels, k_gi_final), which knows chains and no pixels.
 int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_t stream, bool zero_counters, int sample_index = 0, int batch = 1,
            const RtuFrameDesc* frames_batch = nullptr, int gi_mode = RTU_LAUNCH_ALL, int gi_depth = 0, bool adaptive = false,
            const uint4* act_list = nullptr, uint32_t act_n = 0, const float4* d_rays = nullptr, uint32_t n_rays = 0, const uint32_t* d_keys = nullptr) {
@@ -1202,7 +1205,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
     int rc = ensure_levels(ctx, gi ? 2u * (n_tiles + RTU_SHARDS) : n_tiles, gi);
     if (rc != RTU_OK) return rc;
     if (gi) {
-        const size_t chains = (size_t)pixels * (size_t)batch;
+        const size_t chains = rays ? (size_t)n_rays : (size_t)pixels * (size_t)batch;
         RTU_HIP(ctx, ctx->gi_h.grow(chains * (RTU_GI_BOUNCES + 1) * 4));
         RTU_HIP(ctx, ctx->gi_res.grow(chains * 2));
         // adaptive: the chains of stopped pixels are not traced; a zero depth-0 record is "no hit" to every later depth, k_gi_roots
@@ -1321,7 +1324,7 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         a.gi_h = ctx->gi_h.get();
         a.gi_res = ctx->gi_res.get();
         a.gi_depth = (uint32_t)gi_depth;
-        a.gi_total = pixels * (uint32_t)batch;
+        a.gi_total = rays ? n_rays : pixels * (uint32_t)batch;
     }
     const uint32_t launch_tiles = act_list ? act_n * (uint32_t)batch : n_tiles;
     a.act_list = act_list;
@@ -1383,9 +1386,10 @@ int launch(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hipStream_
         if (e0 != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e0));
         return RTU_OK;
     }
-    hipError_t e = rays ? (d_keys ? (hipError_t)rtu_launch_ray_batch_sampled(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr)
-                                  : (hipError_t)rtu_launch_ray_batch(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr))
-                        : (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
+    hipError_t e = (rays && gi_mode == RTU_LAUNCH_CHAIN) ? (hipError_t)rtu_launch_ray_batch_chain(a, d_rays, ctx->bvh_stack_needed, stats == 1, stream)
+                 : (rays && !gi) ? (d_keys ? (hipError_t)rtu_launch_ray_batch_sampled(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr)
+                                           : (hipError_t)rtu_launch_ray_batch(a, d_rays, n_rays, ctx->bvh_stack_needed, stats == 1, stream, probing ? &probe : nullptr))
+                                 : (hipError_t)rtu_launch_frame(a, launch_tiles, ctx->bvh_stack_needed, stats, stream, gi_mode, probing ? &probe : nullptr);
     if (probing && probe_recorded) ctx->probe_used++;
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     return RTU_OK;
@@ -3055,6 +3059,11 @@ int rtu_debug_tail_from(RtuContext* ctx, int level) {
     return RTU_OK;
 }
 
+int rtu_debug_last_tail_from(RtuContext* ctx) {
+    if (!ctx) return RTU_ERR_ARG;
+    return ctx->last_tail_from;
+}
+
 int rtu_set_sequences_in_flight(RtuContext* ctx, int n) {
     if (!ctx || n < 1) return RTU_ERR_ARG;
     ctx->sequences_in_flight = n;
@@ -3361,10 +3370,14 @@ int rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t 
 
 // ---- ray batches: Shade() along caller-supplied rays (render_rays_impl.h) -------------------------------------------------------
 namespace {
+// chains per launch sequence of recipe P: what sampled_batch allows a frame's batch of samples by default (2^25 pixels; its tuning
+// knob RTU_GI_BATCH_LOG2 moves the frame path's figure, not this one), and so a path-traced ray batch's _device form
+const size_t kPathChains = (size_t)1 << 25;
 // the checks both forms share, then the frame descriptor launch() takes for a ray batch: no camera, the eye in cam_pos
 // keys: the sampled forms (rtu_shade_rays_sampled*) — n uint32, one per ray; the frame is then a recipe-S frame of one sample
+// paths: rtu_shade_rays_paths* — sampled, and every ray is a chain of recipe P (352 bytes of chain records and results each)
 int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, const RtuShadeDesc* d, bool device, RtuFrameDesc* f, bool sampled = false,
-               const void* keys = nullptr) {
+               const void* keys = nullptr, bool paths = false) {
     if (!d) return fail(ctx, RTU_ERR_ARG, "shade descriptor is NULL");
     if (d->flags & ~RTU_QUERY_REFERENCE_WALK) return fail(ctx, RTU_ERR_ARG, "unknown shade flag bits 0x%x", d->flags & ~RTU_QUERY_REFERENCE_WALK);
     if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(ctx, RTU_ERR_ARG, "RtuShadeDesc.reserved must be 0");
@@ -3374,6 +3387,7 @@ int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, con
     if (device && n && (((uintptr_t)rays & 15u) || ((uintptr_t)out & 15u)))
         return fail(ctx, RTU_ERR_ARG, "device ray / result buffers must be 16-byte aligned");
     if (device && n > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "more than 2^26 rays in one call");
+    if (device && paths && n > kPathChains) return fail(ctx, RTU_ERR_ARG, "more than 2^25 rays (chains of recipe P) in one call");
     if (sampled && n && !keys) return fail(ctx, RTU_ERR_ARG, "key pointer is NULL");
     if (sampled && n && ((uintptr_t)keys & 3u)) return fail(ctx, RTU_ERR_ARG, "the key buffer must be 4-byte aligned");
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
@@ -3386,13 +3400,41 @@ int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, con
     f->max_bounce = d->max_bounce;
     f->collect_stats = (d->flags & RTU_QUERY_REFERENCE_WALK) ? 1 : 0;
     f->samples = sampled ? 1 : 0;  // one Shade() call of recipe S per ray: launch() sets the sampled feature set from it
+    f->gather_bounces = paths ? RTU_GI_BOUNCES : 0;
     memcpy(f->cam_pos, d->eye, sizeof f->cam_pos);
     return RTU_OK;
 }
 
-// the host forms of both recipes: chunks of at most kQueryChunk rays (and keys) through the context's buffers, each checked for
-// capacity and shaded again if need be
-int shade_host(RtuContext* ctx, RtuFrameDesc& f, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, float* h_rgbt, RtuStats* stats) {
+// ---- a path-traced ray batch (rtu_shade_rays_paths): the launch sequence of recipe P with chain i = ray i ----
+// the chain of a batch: the roots, then the four gather rays; chain records do not depend on the frame capacities.
+// A cut level set by rtu_debug_tail_from is for the "next launch", which launch() takes to be its own next call: a chain step has no
+// recursion levels, so the level is kept from it and handed on to the shading steps.
+int paths_chain(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n) {
+    const int forced = ctx->tail_hint;
+    int rc = RTU_OK;
+    for (int k = 0; k <= RTU_GI_BOUNCES && rc == RTU_OK; k++) {
+        ctx->tail_hint = 0;
+        rc = launch(ctx, &f, d_out, stream, k == 0, 0, 1, nullptr, RTU_LAUNCH_CHAIN, k, false, nullptr, 0, d_rays, n, d_keys);
+    }
+    ctx->tail_hint = forced;
+    return rc;
+}
+// the five shading steps from the deepest depth up (k_gi_roots needs the results of the depth below); depth 0 ends with k_gi_final.
+// Each of them is a whole launch of the recursion levels: a forced cut level applies to all five, then it is spent.
+int paths_shade(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n) {
+    const int forced = ctx->tail_hint;
+    int rc = RTU_OK;
+    for (int k = RTU_GI_BOUNCES; k >= 0 && rc == RTU_OK; k--) {
+        ctx->tail_hint = forced;
+        rc = launch(ctx, &f, d_out, stream, false, 0, 1, nullptr, RTU_LAUNCH_SHADE, k, false, nullptr, 0, d_rays, n, d_keys);
+    }
+    ctx->tail_hint = 0;
+    return rc;
+}
+
+// the host forms of all three recipes: chunks of at most kQueryChunk rays (and keys) through the context's buffers, each checked for
+// capacity and shaded again if need be. paths: the chain of a chunk is traced once, its shading steps are what is repeated
+int shade_host(RtuContext* ctx, RtuFrameDesc& f, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, float* h_rgbt, RtuStats* stats, bool paths = false) {
     int rc = RTU_OK;
     if (stats) { memset(stats, 0, sizeof *stats); f.collect_stats = 1; }
     if (n == 0) return RTU_OK;
@@ -3405,15 +3447,19 @@ int shade_host(RtuContext* ctx, RtuFrameDesc& f, const RtuRay* h_rays, const uin
         const size_t m = n - done < chunk ? n - done : chunk;
         RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
         if (h_keys) RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_keys.get(), h_keys + done, sizeof(uint32_t) * m, hipMemcpyHostToDevice, ctx->stream));
+        if (paths && (rc = paths_chain(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), ctx->sh_keys.get(), (uint32_t)m)) != RTU_OK) return rc;
         for (int attempt = 0;; attempt++) {  // as rtu_render_frame: a chunk that ran out of frame capacity is shaded again
-            rc = launch(ctx, &f, ctx->sh_out.get(), ctx->stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, ctx->sh_rays.get(), (uint32_t)m,
-                        h_keys ? ctx->sh_keys.get() : nullptr);
+            rc = paths ? paths_shade(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), ctx->sh_keys.get(), (uint32_t)m)
+                       : launch(ctx, &f, ctx->sh_out.get(), ctx->stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, ctx->sh_rays.get(), (uint32_t)m,
+                                h_keys ? ctx->sh_keys.get() : nullptr);
             if (rc != RTU_OK) return rc;
             RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
             bool overflow = false;
             if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
             if (!overflow) break;
-            if (attempt >= 2 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+            // (as sample_batches: the counters of the dropped shading steps are already in the totals)
+            if (paths && f.collect_stats) return fail(ctx, RTU_ERR_CAPACITY, "recipe P with counters: frame records ran out; shade the batch once without counters first");
+            if (attempt >= (paths ? 8 : 2) * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
         }
         RTU_HIP(ctx, hipMemcpy(h_rgbt + 4 * done, ctx->sh_out.get(), sizeof(float4) * m, hipMemcpyDeviceToHost));
         if (stats) {  // the counters are zeroed per launch: the batch's are the sum over its chunks
@@ -3496,6 +3542,25 @@ int rtu_shade_rays_sampled(RtuContext* ctx, const RtuRay* h_rays, const uint32_t
     const int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f, true, h_keys);
     if (rc != RTU_OK) return rc;
     return shade_host(ctx, f, h_rays, h_keys, n, h_rgbt, stats);
+}
+
+// ---- path-traced ray batches: recipe P per ray (render_rays4.hip / render_rays5.hip for the chain, render_feat10/11.hip behind it) ----
+int rtu_shade_rays_paths_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_rgbt, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    int rc = shade_args(ctx, d_rays, d_rgbt, n, desc, true, &f, true, d_keys, true);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = paths_chain(ctx, f, (float4*)d_rgbt, (hipStream_t)hip_stream, (const float4*)d_rays, (const uint32_t*)d_keys, (uint32_t)n)) != RTU_OK) return rc;
+    return paths_shade(ctx, f, (float4*)d_rgbt, (hipStream_t)hip_stream, (const float4*)d_rays, (const uint32_t*)d_keys, (uint32_t)n);
+}
+
+int rtu_shade_rays_paths(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_rgbt, RtuStats* stats) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    const int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f, true, h_keys, true);
+    if (rc != RTU_OK) return rc;
+    return shade_host(ctx, f, h_rays, h_keys, n, h_rgbt, stats, true);
 }
 
 uint32_t rtu_sample_key(uint32_t pixel, uint32_t sample) { return h_mix32(h_mix32(pixel + 0x68bc21ebU) ^ (sample * 0x9e3779b9U + 1U)); }

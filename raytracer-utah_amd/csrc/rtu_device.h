@@ -397,6 +397,11 @@ int rtu_launch_ray_batch(const KernelArgs& args, const float4* rays, uint32_t n,
 // render_impl.h: a ray batch has no cameras, and KernelArgs no room for another pointer).
 int rtu_launch_ray_batch_sampled(const KernelArgs& args, const float4* rays, uint32_t n, uint32_t bvh_stack_needed, bool stats, hipStream_t stream,
                                  const LaunchProbe* probe = nullptr);
+// A PATH-TRACED ray batch (rtu_shade_rays_paths; render_rays4.hip / render_rays5.hip): one step of the chains of recipe P, chain i
+// being ray i of args.gi_total rays. args.gi_depth 0: the roots — Trace() of the n RtuRay at `rays`, misses / invalid rays / null
+// materials to args.out, the depth-0 records to args.gi_h, args.cam = the n uint32 keys (ray_keys) —; 1 .. RTU_GI_BOUNCES: the gather
+// ray of that depth (rays is not read). The Shade() trees are rtu_launch_frame's (RTU_LAUNCH_SHADE), as for a frame of recipe P.
+int rtu_launch_ray_batch_chain(const KernelArgs& args, const float4* rays, uint32_t bvh_stack_needed, bool stats, hipStream_t stream);
 
 // recipe S: add one sample's image to the accumulators / write the mean
 int rtu_launch_accumulate(const float4* samples, uint32_t batch, float4* acc, uint32_t* hits, uint32_t pixels, bool first, hipStream_t stream);
