@@ -467,6 +467,60 @@ int  rtu_camera_sample_rays(const RtuFrameDesc* frame, int sample, int row0, int
 uint32_t rtu_sample_key(uint32_t pixel, uint32_t sample);   /* sample_key(p, i) as stated above; pure host code */
 uint32_t rtu_child_key(uint32_t key, uint32_t slot);        /* child_key(key, slot) as stated above; pure host code */
 
+/* ---- Ray sorting: a coherent order for caller-supplied rays (raytracer-utah_amd/csrc/rtu_raysort.hip, rtu_raysort.h) ----------------------
+ * The five ray entries above answer rays in whatever order they come, and pay for an incoherent one: neighbouring lanes walk different
+ * parts of the scene (a shuffled batch costs 1.2 to 2.3 times the same rays in image order). These calls bring a batch into
+ * a coherent order on the GPU, so that a caller can sort, call any entry UNCHANGED on the sorted buffers, and put the answers back:
+ *     rtu_ray_order_device(ctx, d_rays, n, d_order, s);
+ *     rtu_permute_device(ctx, d_rays, d_sorted, d_order, n, 32, 0, s);      (and the keys of a sampled batch: elem_bytes 4)
+ *     rtu_trace_rays_device(ctx, d_sorted, n, 0, d_hits_sorted, s);
+ *     rtu_permute_device(ctx, d_hits_sorted, d_hits, d_order, n, 48, 1, s);
+ * Every entry answers a ray whatever its index (a sampled ray: whatever its index, given its key), so d_hits holds the bytes the
+ * unsorted call writes.
+ *   THE BOX  rtu_ray_sort_box: lo[3], hi[3] — the union of the finite node-level bounds of the uploaded scene as it is now (kept at
+ *            rtu_upload_scene, refreshed by rtu_update_scene / rtu_update_meshes); [-w, w]^3 with w the largest |coordinate| of the scene
+ *            when no node has a finite bound. RTU_ERR_NO_SCENE before an upload. A box is DEGENERATE when a bound is not finite, when
+ *            hi < lo on an axis or when hi - lo is not finite: every spatial cell is then 0, and no ray misses.
+ *   THE KEY  rtu_ray_sort_keys (pure host code, needs no GPU and no context; RTU_ERR_ARG: NULL box, a NULL array with n > 0) and the
+ *            kernel evaluate, in binary32 with one rounding per operation, in this order (min / max are comparisons):
+ *              an INVALID ray (the rule of the ray queries above)                                           0xFFFFFFFF
+ *              inside = lo <= org <= hi on every axis; if not inside (and the box is not degenerate):
+ *                t0 = 0, t1 = tmax; per axis k = x, y, z: dir[k] == 0: a miss if org[k] < lo[k] or org[k] > hi[k], else nothing;
+ *                otherwise ta = (lo[k] - org[k]) / dir[k], tb = (hi[k] - org[k]) / dir[k], t0 = max(t0, min(ta, tb)),
+ *                t1 = min(t1, max(ta, tb)); t0 > t1: a miss. A valid ray that MISSES the box has key 0x40000000 | directional (below):
+ *                behind every ray that enters the box, and still ordered by direction — such rays are shaded too (the environment)
+ *              p = org if inside, else org + t0 * dir, clamped to [lo, hi] per axis
+ *              cell[k] = min(15, (int)floorf((p[k] - lo[k]) / (hi[k] - lo[k]) * 16.0f)), 0 where hi[k] - lo[k] is 0;
+ *              spatial = the 12-bit Morton code of the cells: bit i of cell x, y, z at bit 3 i, 3 i + 1, 3 i + 2
+ *              s = (|dx| + |dy|) + |dz|, px = dx / s, py = dy / s; dz < 0: (px, py) = ((1 - |py|) * sgn(px), (1 - |px|) * sgn(py)) with
+ *              sgn(a) = a >= 0 ? 1 : -1 (the octahedral map); u = px * 0.5f + 0.5f, v = py * 0.5f + 0.5f,
+ *              qu = clamp((int)floorf(u * 512.0f), 0, 511), qv likewise; directional = the 18-bit Morton code: bit i of qu, qv at bit
+ *              2 i, 2 i + 1
+ *              key = spatial << 18 | directional                                                             (30 bits; a miss: bit 30)
+ *            No libm function is involved, so host and device agree bit for bit.
+ *   THE ORDER rtu_ray_order_device writes order[0 .. n) (uint32, DEVICE memory), the permutation that sorts the keys of the n rays at
+ *            d_rays in the context's box STABLY — equal keys keep their index order: order = argsort(keys, stable), a pure function of
+ *            the rays and the scene. Ray order[i] of the batch is ray i of the sorted batch. Asynchronous on hip_stream. The scratch
+ *            (keys and indices double-buffered, digit histograms: 16 bytes per ray) is grow-only storage of the context, so the ONE STREAM
+ *            PER CONTEXT rule of rtu_render_frame_device applies to this call: two orderings, or an ordering and a render, in flight
+ *            on two streams need two contexts. It is no render: it touches no frame record, counter, launch hint or rtu_frame_status
+ *            report. rtu_ray_order is the synchronous host form (rays and order copied through grow-only buffers of the context).
+ *            RTU_ERR_ARG: n > 2^26, a NULL pointer with n > 0, d_rays not 16-byte or d_order not 4-byte aligned, a NULL context;
+ *            RTU_ERR_NO_SCENE before rtu_upload_scene; n == 0 is RTU_OK and launches nothing. An order stays a valid permutation
+ *            after the scene changes; it is then the order of the scene it was computed for.
+ *   PERMUTE  rtu_permute_device: scatter == 0: dst[i] = src[order[i]] (rays and keys going in); scatter == 1: dst[order[i]] = src[i]
+ *            (answers coming out), for n elements of elem_bytes = 1 (occlusion bytes), 4 (keys), 16 (float4), 32 (RtuRay) or 48
+ *            (RtuRayHit). Stateless: any stream, no scene needed. RTU_ERR_ARG: another elem_bytes, scatter not 0 / 1, n > 2^26, a NULL
+ *            pointer with n > 0, src == dst, src or dst not aligned to min(elem_bytes, 16) or order not to 4 bytes. The kernel does NOT
+ *            validate order: an index >= n is the caller's error (an out-of-bounds access), and the buffers must not overlap. */
+int  rtu_ray_sort_box(const RtuContext* ctx, float box_out[6]);
+int  rtu_scene_sort_box(const RtuSceneDesc* scene, float box_out[6]);   /* the box rtu_upload_scene(scene) would keep: pure host code (validates the scene first) */
+int  rtu_ray_sort_keys(const float box[6], const RtuRay* rays, size_t n, uint32_t* keys_out);
+int  rtu_ray_order_device(RtuContext* ctx, const void* d_rays, size_t n, void* d_order, void* hip_stream);
+int  rtu_ray_order(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t* h_order);
+int  rtu_permute_device(RtuContext* ctx, const void* d_src, void* d_dst, const void* d_order, size_t n, uint32_t elem_bytes, int scatter,
+                        void* hip_stream);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer
@@ -725,6 +779,7 @@ int   rtu_copy_to_host_async(RtuContext* ctx, void* h_dst, const void* d_src, si
 void* rtu_device_alloc(RtuContext* ctx, size_t bytes);
 void  rtu_device_free(RtuContext* ctx, void* d_ptr);
 int   rtu_copy_to_host(RtuContext* ctx, void* h_dst, const void* d_src, size_t bytes);
+int   rtu_copy_to_device(RtuContext* ctx, void* d_dst, const void* h_src, size_t bytes);   /* synchronous */
 
 #ifdef __cplusplus
 }

@@ -156,7 +156,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays",
                "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays",
                "rtu_shade_rays_sampled_device", "rtu_shade_rays_sampled", "rtu_camera_sample_rays", "rtu_sample_key", "rtu_child_key",
-               "rtu_shade_rays_paths_device", "rtu_shade_rays_paths", "rtu_debug_last_tail_from"]
+               "rtu_shade_rays_paths_device", "rtu_shade_rays_paths", "rtu_debug_last_tail_from",
+               "rtu_ray_sort_box", "rtu_scene_sort_box", "rtu_ray_sort_keys", "rtu_ray_order_device", "rtu_ray_order", "rtu_permute_device", "rtu_copy_to_device"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -306,6 +307,17 @@ _sig(hip, "rtu_shade_rays_paths", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTE
 _sig(hip, "rtu_camera_sample_rays", _I, ctypes.POINTER(RtuFrameDesc), _I, _I, _I, _P, _P)
 _sig(hip, "rtu_sample_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
 _sig(hip, "rtu_child_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
+# ray sorting (include/rtu_render.h, "Ray sorting")
+RTU_SORTKEY_INVALID, RTU_SORTKEY_MISS = 0xFFFFFFFF, 0x40000000  # MISS: a bit, beside the 18 direction bits
+_sig(hip, "rtu_ray_sort_box", _I, _P, ctypes.POINTER(ctypes.c_float))
+_sig(hip, "rtu_scene_sort_box", _I, _P, ctypes.POINTER(ctypes.c_float))
+_sig(hip, "rtu_ray_sort_keys", _I, ctypes.POINTER(ctypes.c_float), _P, ctypes.c_size_t, _P)
+_sig(hip, "rtu_ray_order_device", _I, _P, _P, ctypes.c_size_t, _P, _P)
+_sig(hip, "rtu_ray_order", _I, _P, _P, ctypes.c_size_t, _P)
+_sig(hip, "rtu_permute_device", _I, _P, _P, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _I, _P)
+_sig(hip, "rtu_copy_to_device", _I, _P, _P, _P, ctypes.c_size_t)
+_sig(hip, "rtu_context_stream", _P, _P)
+_sig(hip, "rtu_context_sync", _I, _P)
 
 
 def shade_desc(eye=(0.0, 0.0, 0.0), max_bounce=5, reference_walk=False):
@@ -378,6 +390,31 @@ def sample_key(pixel, sample):
 def child_key(key, slot):
     """rtu_child_key: the key of the Shade() call behind secondary ray `slot` of the call with key `key`."""
     return int(hip.rtu_child_key(int(key) & 0xFFFFFFFF, int(slot) & 0xFFFFFFFF))
+
+
+def scene_sort_box(scene):
+    """rtu_scene_sort_box (pure host code): the box Context.ray_sort_box() reports once `scene` is uploaded, float32 [6]."""
+    import numpy as np
+    b = (ctypes.c_float * 6)()
+    rc = hip.rtu_scene_sort_box(scene.desc_ptr, b)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_scene_sort_box: the scene does not validate")
+    return np.array(list(b), np.float32)
+
+
+def ray_sort_keys(box, rays):
+    """rtu_ray_sort_keys (pure host code): the sort keys of `rays` (as for trace_rays) in `box` = (lo x, y, z, hi x, y, z) — what
+    Context.ray_sort_box() returns for an uploaded scene — as uint32 [n]: 12 bits of Morton-coded cell of the point where the ray
+    enters the box, 18 bits of Morton-coded octahedral direction; RTU_SORTKEY_MISS | the direction bits for a ray that misses the box, RTU_SORTKEY_INVALID
+    for one the queries do not trace. The kernel's binary32 expressions in the same order: the same bits."""
+    import numpy as np
+    r = _as_rays(rays)
+    b = (ctypes.c_float * 6)(*[float(x) for x in np.asarray(box, np.float32).reshape(6)])
+    out = np.zeros(r.size, np.uint32)
+    rc = hip.rtu_ray_sort_keys(b, r.ctypes.data if r.size else None, r.size, out.ctypes.data if r.size else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_ray_sort_keys")
+    return out
 
 
 def _as_keys(keys, n):
@@ -914,24 +951,105 @@ class Context:
         self._check(hip.rtu_debug_texcoords(self._h, op, index, x.ctypes.data, n, out.ctypes.data))
         return out
 
-    def trace_rays(self, rays, reference_walk=False):
+    def ray_sort_box(self):
+        """rtu_ray_sort_box: the box the sort keys of this context's scene are quantised in, float32 [6] = lo x, y, z, hi x, y, z."""
+        import numpy as np
+        b = (ctypes.c_float * 6)()
+        self._check(hip.rtu_ray_sort_box(self._h, b))
+        return np.array(list(b), np.float32)
+
+    def ray_order(self, rays):
+        """rtu_ray_order: the permutation (uint32 [n]) that sorts `rays` by their sort key in this scene's box, stably — equal to
+        np.argsort(ray_sort_keys(self.ray_sort_box(), rays), kind="stable"), computed on the GPU. rays[order] is the coherent batch."""
+        import numpy as np
+        r = _as_rays(rays)
+        out = np.zeros(r.size, np.uint32)
+        self._check(hip.rtu_ray_order(self._h, r.ctypes.data if r.size else None, r.size, out.ctypes.data if r.size else None))
+        return out
+
+    def ray_order_device(self, d_rays_ptr, n, d_order_ptr, stream=None):
+        """rtu_ray_order_device: n RtuRay at d_rays_ptr -> the sorting permutation, n uint32 at d_order_ptr (device memory),
+        asynchronous on `stream`. Uses scratch of the context: one stream per context."""
+        self._check(hip.rtu_ray_order_device(self._h, d_rays_ptr, n, d_order_ptr, stream))
+
+    def permute_device(self, d_src_ptr, d_dst_ptr, d_order_ptr, n, elem_bytes, scatter=False, stream=None):
+        """rtu_permute_device: dst[i] = src[order[i]] (scatter False) or dst[order[i]] = src[i] (scatter True) for n elements of
+        elem_bytes = 1, 4, 16, 32 or 48 in device memory, asynchronous on `stream`."""
+        self._check(hip.rtu_permute_device(self._h, d_src_ptr, d_dst_ptr, d_order_ptr, n, elem_bytes, 1 if scatter else 0, stream))
+
+    def _sorted(self, r, keys, out, call, shading):
+        """sort=True of the five ray entries: upload the rays (and keys) once, order them on the GPU, gather them, run
+        call(d_rays, d_keys, d_out, stream) — an existing _device entry, unchanged — on the sorted buffers, scatter the answers back to
+        the callers' places and download them into `out`. A shading entry is repeated while rtu_frame_status reports
+        RTU_ERR_CAPACITY, as its host form does, up to 8 times."""
+        n = r.size
+        if n == 0:
+            return
+        stream = hip.rtu_context_stream(self._h)
+        ob = out.nbytes // n
+        sizes = {"rays": 32 * n, "srays": 32 * n, "order": 4 * n, "sout": ob * n, "out": ob * n}
+        if keys is not None:
+            sizes.update(keys=4 * n, skeys=4 * n)
+        d = {}
+        try:
+            for name, size in sizes.items():
+                d[name] = hip.rtu_device_alloc(self._h, size)
+                if not d[name]:
+                    raise RtuError(RTU_ERR_HIP, "device allocation of %d bytes failed" % size)
+            self._check(hip.rtu_copy_to_device(self._h, d["rays"], r.ctypes.data, 32 * n))
+            if keys is not None:
+                self._check(hip.rtu_copy_to_device(self._h, d["keys"], keys.ctypes.data, 4 * n))
+            self._check(hip.rtu_ray_order_device(self._h, d["rays"], n, d["order"], stream))
+            self._check(hip.rtu_permute_device(self._h, d["rays"], d["srays"], d["order"], n, 32, 0, stream))
+            if keys is not None:
+                self._check(hip.rtu_permute_device(self._h, d["keys"], d["skeys"], d["order"], n, 4, 0, stream))
+            for attempt in range(8):
+                call(d["srays"], d.get("skeys"), d["sout"], stream)
+                if not shading:
+                    break
+                rc = hip.rtu_frame_status(self._h)
+                if rc != RTU_ERR_CAPACITY:
+                    self._check(rc)
+                    break
+            else:
+                self._check(RTU_ERR_CAPACITY)
+            self._check(hip.rtu_permute_device(self._h, d["sout"], d["out"], d["order"], n, ob, 1, stream))
+            self._check(hip.rtu_context_sync(self._h))
+            self._check(hip.rtu_copy_to_host(self._h, out.ctypes.data, d["out"], ob * n))
+        finally:
+            for ptr in d.values():
+                if ptr:
+                    hip.rtu_device_free(self._h, ptr)
+
+    def trace_rays(self, rays, reference_walk=False, sort=False):
         """Closest hits of caller-supplied rays (rtu_trace_rays): rays float32 [n, 8] {org, tmax, dir, -} or a structured array of
-        ray_dtype(); returns a structured array [n] of hit_dtype(). Directions must be of unit length (else RTU_RAY_INVALID)."""
+        ray_dtype(); returns a structured array [n] of hit_dtype(). Directions must be of unit length (else RTU_RAY_INVALID).
+        sort=True: the batch is brought into a coherent order on the GPU first (ray_order), traced by rtu_trace_rays_device, and the
+        hits are put back in the callers' order: the same bytes. For the bare queries the sort costs more than it saves (DESIGN.md 20);
+        it pays on the sampled and path-traced shading entries."""
         import numpy as np
         r = _as_rays(rays)
         out = np.zeros(r.size, hit_dtype())
+        if sort:
+            self._sorted(r, None, out, lambda dr, dk, do, st: self.trace_rays_device(dr, r.size, do, st, reference_walk=reference_walk), False)
+            return out
         self._check(hip.rtu_trace_rays(self._h, r.ctypes.data if r.size else None, r.size, RTU_QUERY_REFERENCE_WALK if reference_walk else 0,
                                        out.ctypes.data if r.size else None))
         return out
 
-    def occluded(self, rays, reference_walk=False):
-        """Is anything in front of tmax along each ray (rtu_occluded_rays)? uint8 [n], 1 or 0."""
+    def occluded(self, rays, reference_walk=False, sort=False):
+        """Is anything in front of tmax along each ray (rtu_occluded_rays)? uint8 [n], 1 or 0. sort=True: as for trace_rays."""
         import numpy as np
         r = _as_rays(rays)
         out = np.zeros(r.size, np.uint8)
+        if sort:
+            self._sorted(r, None, out, lambda dr, dk, do, st: self.occluded_device(dr, r.size, do, st, reference_walk=reference_walk), False)
+            return out
         self._check(hip.rtu_occluded_rays(self._h, r.ctypes.data if r.size else None, r.size, RTU_QUERY_REFERENCE_WALK if reference_walk else 0,
                                           out.ctypes.data if r.size else None))
         return out
+
+    occluded_rays = occluded  # the name of the C entry
 
     def trace_rays_device(self, d_rays_ptr, n, d_hits_ptr, stream=None, reference_walk=False, flags=None):
         """rtu_trace_rays_device: n RtuRay at d_rays_ptr -> n RtuRayHit at d_hits_ptr (device memory, 16-byte aligned: a torch tensor's
@@ -939,15 +1057,21 @@ class Context:
         f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
         self._check(hip.rtu_trace_rays_device(self._h, d_rays_ptr, n, f, d_hits_ptr, stream))
 
-    def shade_rays(self, rays, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+    def shade_rays(self, rays, eye, max_bounce=5, reference_walk=False, stats=False, desc=None, sort=False):
         """Radiance along caller-supplied rays (rtu_shade_rays): rays as for trace_rays; eye is the camera position of Shade()'s view
         vector. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None): a hit is shaded like a render's pixel, a miss is the
-        environment along the ray with t = tmax, an invalid ray is four zeros. desc (an RtuShadeDesc) overrides the other options."""
+        environment along the ray with t = tmax, an invalid ray is four zeros. desc (an RtuShadeDesc) overrides the other options.
+        sort=True: ordered on the GPU first (ray_order), shaded by the _device entry on the sorted batch, answers put back: the same bytes."""
         import numpy as np
         r = _as_rays(rays)
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         out = np.zeros((r.size, 4), np.float32)
         st = RtuStats() if stats else None
+        if sort:
+            if stats:
+                raise RtuError(RTU_ERR_ARG, "sort=True goes through the _device entry, which returns no counters: stats=False")
+            self._sorted(r, None, out, lambda dr, dk, do, st_: self.shade_rays_device(dr, r.size, eye, do, st_, desc=d), True)
+            return out, None
         self._check(hip.rtu_shade_rays(self._h, r.ctypes.data if r.size else None, r.size, ctypes.byref(d), out.ctypes.data if r.size else None,
                                        ctypes.byref(st) if stats else None))
         return out, (st.as_dict() if stats else None)
@@ -958,16 +1082,22 @@ class Context:
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         self._check(hip.rtu_shade_rays_device(self._h, d_rays_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
 
-    def shade_rays_sampled(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+    def shade_rays_sampled(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None, sort=False):
         """Recipe S along caller-supplied rays (rtu_shade_rays_sampled): as shade_rays, with one uint32 key per ray — the key of the
         sample streams of that ray's root Shade() call (soft shadows, glossy bounces). One sample per ray; scenes with stochastic
-        features are accepted. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None)."""
+        features are accepted. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None).
+        sort=True: ordered on the GPU first (ray_order), shaded by the _device entry on the sorted batch, answers put back: the same bytes."""
         import numpy as np
         r = _as_rays(rays)
         k = _as_keys(keys, r.size)
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         out = np.zeros((r.size, 4), np.float32)
         st = RtuStats() if stats else None
+        if sort:
+            if stats:
+                raise RtuError(RTU_ERR_ARG, "sort=True goes through the _device entry, which returns no counters: stats=False")
+            self._sorted(r, k, out, lambda dr, dk, do, st_: self.shade_rays_sampled_device(dr, dk, r.size, eye, do, st_, desc=d), True)
+            return out, None
         self._check(hip.rtu_shade_rays_sampled(self._h, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None, r.size, ctypes.byref(d),
                                                out.ctypes.data if r.size else None, ctypes.byref(st) if stats else None))
         return out, (st.as_dict() if stats else None)
@@ -978,16 +1108,22 @@ class Context:
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         self._check(hip.rtu_shade_rays_sampled_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
 
-    def shade_rays_paths(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+    def shade_rays_paths(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None, sort=False):
         """Recipe P along caller-supplied rays (rtu_shade_rays_paths): as shade_rays_sampled, with the 4-bounce Monte-Carlo gather
         behind every hit — rgb = Shade(hit, lights + the gathered AmbientLight) + Shade(hit, lights). keys[i] is the key of ray i's
-        root call; the gather draws from it as a recipe-P frame does. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None)."""
+        root call; the gather draws from it as a recipe-P frame does. Returns (float32 [n, 4] {r, g, b, t}, stats dict or None).
+        sort=True: ordered on the GPU first (ray_order), shaded by the _device entry on the sorted batch, answers put back: the same bytes."""
         import numpy as np
         r = _as_rays(rays)
         k = _as_keys(keys, r.size)
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         out = np.zeros((r.size, 4), np.float32)
         st = RtuStats() if stats else None
+        if sort:
+            if stats:
+                raise RtuError(RTU_ERR_ARG, "sort=True goes through the _device entry, which returns no counters: stats=False")
+            self._sorted(r, k, out, lambda dr, dk, do, st_: self.shade_rays_paths_device(dr, dk, r.size, eye, do, st_, desc=d), True)
+            return out, None
         self._check(hip.rtu_shade_rays_paths(self._h, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None, r.size, ctypes.byref(d),
                                              out.ctypes.data if r.size else None, ctypes.byref(st) if stats else None))
         return out, (st.as_dict() if stats else None)

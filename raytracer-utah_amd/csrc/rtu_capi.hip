@@ -8,6 +8,7 @@
 #include "rtu_lightlist.h"
 #include "rtu_meshrec.h"
 #include "rtu_query.h"
+#include "rtu_raysort.h"
 
 #include <algorithm>
 #include <array>
@@ -135,6 +136,10 @@ struct RtuContext {
     DevBuf<uint8_t> q_occ;
     DevBuf<float4>  sh_rays, sh_out;         // ray batches, host form (rtu_shade_rays): one chunk of rays and of {r, g, b, t}
     DevBuf<uint32_t> sh_keys;                // ... and of keys (rtu_shade_rays_sampled)
+    float sort_box[6] = {};                  // ray sorting (rtu_raysort.h): the box the keys are quantised in, kept by place_scene
+    DevBuf<uint32_t> so_scratch;             // ... keys and indices double-buffered, digit histograms (rtu_ray_order_device)
+    DevBuf<float4>   so_rays;                // ... the host form's rays and order (rtu_ray_order)
+    DevBuf<uint32_t> so_order;
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -671,6 +676,24 @@ float world_bounds(const RtuSceneDesc* s, std::vector<DevNode>& nodes) {
         }
     }
     return (float)scale;
+}
+
+// the box of the ray-sort keys (rtu_ray_sort_box): the union of the finite node-level bounds world_bounds left, else [-wscale, wscale]^3
+void sort_box_of(const std::vector<DevNode>& nodes, float wscale, float out[6]) {
+    for (int k = 0; k < 3; k++) { out[k] = INFINITY; out[3 + k] = -INFINITY; }
+    bool any_bound = false;
+    for (const DevNode& d : nodes) {
+        bool finite = true;
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(d.wmin[k]) && std::isfinite(d.wmax[k]);
+        if (!finite) continue;
+        any_bound = true;
+        for (int k = 0; k < 3; k++) {
+            out[k] = std::min(out[k], d.wmin[k]);
+            out[3 + k] = std::max(out[3 + k], d.wmax[k]);
+        }
+    }
+    if (!any_bound)
+        for (int k = 0; k < 3; k++) { out[k] = -wscale; out[3 + k] = wscale; }
 }
 
 // OCCLUDER LISTS OF SHADOW RAYS (DevLightMask): for each of the first RTU_LMASK_LIGHTS non-ambient lights and each masked mesh
@@ -1887,6 +1910,8 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
 
 
     const float wscale = world_bounds(s, nodes);
+    float sort_box[6];
+    sort_box_of(nodes, wscale, sort_box);
     DevScene ds = ctx->dscene;
     if ((rc = place_upload(ctx, P_NODES, nodes.data(), nodes.size(), &ds.nodes)) != RTU_OK) return rc;
     if ((rc = place_upload(ctx, P_MATERIALS, s->materials, (size_t)s->n_materials, &ds.materials)) != RTU_OK) return rc;
@@ -1978,6 +2003,7 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
     env_value(s->background, ds.background);
     env_value(s->environment, ds.environment);
     ctx->dscene = ds;
+    memcpy(ctx->sort_box, sort_box, sizeof sort_box);
     ctx->nsl = 0;
     for (uint32_t i = 0; i < s->n_lights; i++)
         if (s->lights[i].type != RTU_LIGHT_AMBIENT) {
@@ -3617,6 +3643,91 @@ int rtu_camera_rays(const RtuFrameDesc* frame, int row0, int nrows, RtuRay* rays
             r.dir[0] = dir.x; r.dir[1] = dir.y; r.dir[2] = dir.z;
             r.reserved = 0;
         }
+    return RTU_OK;
+}
+
+// ---- ray sorting (rtu_raysort.hip): the order, and the kernels that apply it ----------------------------------------------------
+int rtu_ray_sort_box(const RtuContext* ctx, float box_out[6]) {
+    if (!ctx || !box_out) return RTU_ERR_ARG;
+    if (!ctx->has_scene) return RTU_ERR_NO_SCENE;
+    memcpy(box_out, ctx->sort_box, sizeof ctx->sort_box);
+    return RTU_OK;
+}
+
+// what rtu_ray_sort_box answers after rtu_upload_scene(scene), without a GPU
+int rtu_scene_sort_box(const RtuSceneDesc* s, float box_out[6]) {
+    if (!box_out) return RTU_ERR_ARG;
+    RtuContext tmp;  // plain host state: nothing here touches a GPU
+    const int rc = validate(&tmp, s);
+    if (rc != RTU_OK) return rc;
+    std::vector<DevNode> nodes(s->n_nodes);
+    const float wscale = world_bounds(s, nodes);
+    sort_box_of(nodes, wscale, box_out);
+    return RTU_OK;
+}
+
+namespace {
+const size_t kSortMaxRays = (size_t)1 << 26;
+
+int order_args(RtuContext* ctx, const void* rays, const void* order, size_t n, bool device) {
+    if (n > kSortMaxRays) return fail(ctx, RTU_ERR_ARG, "more than 2^26 rays in one call");
+    if (n && (!rays || !order)) return fail(ctx, RTU_ERR_ARG, "rays / order pointer is NULL");
+    if (device && n && ((uintptr_t)rays & 15u)) return fail(ctx, RTU_ERR_ARG, "the device ray buffer must be 16-byte aligned");
+    if (device && n && ((uintptr_t)order & 3u)) return fail(ctx, RTU_ERR_ARG, "the order buffer must be 4-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    return RTU_OK;
+}
+}  // namespace
+
+int rtu_ray_order_device(RtuContext* ctx, const void* d_rays, size_t n, void* d_order, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    const int rc = order_args(ctx, d_rays, d_order, n, true);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->so_scratch.grow(rtu_ray_order_scratch_words(n)));
+    const hipError_t e = (hipError_t)rtu_launch_ray_order(make_sortbox(ctx->sort_box), (const float4*)d_rays, n, (uint32_t*)d_order,
+                                                          ctx->so_scratch.get(), (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "ray sort launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_ray_order(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t* h_order) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = order_args(ctx, h_rays, h_order, n, false);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->so_rays.grow(2 * n));
+    RTU_HIP(ctx, ctx->so_order.grow(n));
+    RTU_HIP(ctx, hipMemcpyAsync(ctx->so_rays.get(), h_rays, sizeof(RtuRay) * n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = rtu_ray_order_device(ctx, ctx->so_rays.get(), n, ctx->so_order.get(), ctx->stream)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(h_order, ctx->so_order.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RTU_OK;
+}
+
+int rtu_permute_device(RtuContext* ctx, const void* d_src, void* d_dst, const void* d_order, size_t n, uint32_t elem_bytes, int scatter,
+                       void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 16 && elem_bytes != 32 && elem_bytes != 48)
+        return fail(ctx, RTU_ERR_ARG, "elem_bytes must be 1, 4, 16, 32 or 48");
+    if (scatter != 0 && scatter != 1) return fail(ctx, RTU_ERR_ARG, "scatter must be 0 or 1");
+    if (n > kSortMaxRays) return fail(ctx, RTU_ERR_ARG, "more than 2^26 elements in one call");
+    if (n == 0) return RTU_OK;
+    if (!d_src || !d_dst || !d_order) return fail(ctx, RTU_ERR_ARG, "source / destination / order pointer is NULL");
+    if (d_src == d_dst) return fail(ctx, RTU_ERR_ARG, "a permutation cannot be applied in place");
+    const uintptr_t align = elem_bytes >= 16 ? 15u : elem_bytes - 1;
+    if (((uintptr_t)d_src & align) || ((uintptr_t)d_dst & align) || ((uintptr_t)d_order & 3u))
+        return fail(ctx, RTU_ERR_ARG, "source and destination must be aligned to min(elem_bytes, 16), the order to 4 bytes");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_permute(d_src, d_dst, (const uint32_t*)d_order, n, elem_bytes, scatter, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "permute launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_copy_to_device(RtuContext* ctx, void* d_dst, const void* h_src, size_t bytes) {
+    if (!ctx || !d_dst || !h_src) return RTU_ERR_ARG;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipMemcpy(d_dst, h_src, bytes, hipMemcpyHostToDevice));
     return RTU_OK;
 }
 

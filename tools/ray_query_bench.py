@@ -5,7 +5,12 @@ entry points and both walks. Each figure is the median over `reps` launches, eve
 after `warmup` launches that are not counted. For comparison the primary phase of a recipe-W frame of the same camera on the same
 build: the launches of k_primary, k_primary2c and k_primary2, bracketed by rtu_probe_kernel (that phase also shades its hits).
 
-usage: tools/ray_query_bench.py [--reps 20] [--warmup 3] [--out profiles/r08_ray_queries.json]"""
+--sorted: instead, what sorting a shuffled batch on the GPU buys (tools/sorted_legs.py): per scene and entry point (fast walk) the
+shuffled camera rays (a) as they are, (b) rtu_ray_order_device + gather + the query + scatter as one region, (c) those parts one by
+one, and the image-order batch beside them; every timed sorted launch is compared byte for byte with the unsorted answers.
+--scale k fires the camera at k times the resolution (k * k times the rays): where the sort breaks even depends on the batch size.
+
+usage: tools/ray_query_bench.py [--sorted [--scale 1]] [--reps 20] [--warmup 3] [--out profiles/r08_ray_queries.json]"""
 import argparse
 import json
 import os
@@ -15,6 +20,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.insert(0, os.path.join(REPO, "tools"))
 
 TAGS = ["teapot2_1080", "p4_1080"]
 
@@ -33,6 +39,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--sorted", action="store_true", help="time a shuffled batch as it is against order + gather + query + scatter")
+    ap.add_argument("--scale", type=int, default=1, help="with --sorted: the camera at this multiple of the fixture's resolution")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -42,6 +50,31 @@ def main():
     ctx = pkg.Context(0)
     stream = torch.cuda.Stream(device=0)
     out = {"tool": "ray_query_bench", "reps": args.reps, "warmup": args.warmup, "device": pkg.device_info(0)["name"], "scenes": []}
+    if args.sorted:
+        from sorted_legs import sorted_legs
+        out["mode"] = "sorted"
+        for tag in TAGS:
+            gd = Golden(tag)
+            scene = gd.scene(pkg)
+            W, H = gd.width * args.scale, gd.height * args.scale
+            ctx.upload(scene)
+            rays = pkg.camera_rays(pkg.frame_setup(scene.desc.camera, W, H))
+            n = rays.size
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to("cuda:0")
+            d_image, d_shuffled = dev(rays), dev(rays[np.random.RandomState(1).permutation(n)])
+            row = {"scene": tag, "width": W, "height": H, "queries": {}}
+            for entry, nbytes in (("closest", 48), ("occluded", 1)):
+                query = ctx.trace_rays_device if entry == "closest" else ctx.occluded_device
+                row["queries"][entry] = sorted_legs(pkg, ctx, torch, stream, n, d_image, d_shuffled, None, None, nbytes,
+                                                    lambda r, k, o: query(r, n, o, stream.cuda_stream), args.reps, args.warmup, False)
+            out["scenes"].append(row)
+        line = json.dumps(out)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        ctx.close()
+        return
     for tag in TAGS:
         gd = Golden(tag)
         scene = gd.scene(pkg)

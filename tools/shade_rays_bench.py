@@ -15,8 +15,14 @@ with samples = 1 — one sample image, the accumulation and the resolve.
 --paths: the same for recipe P (rtu_shade_rays_paths_device): the camera-sample rays and keys of Project11/scene.xml and
 Project10/scene.xml at 1920x1080 against rtu_render_frame_device of that frame with samples = 1, gather_bounces = 4.
 
-usage: tools/shade_rays_bench.py [--sampled | --paths] [--reps 20] [--warmup 3] [--out FILE]
-(profiles/r09_shade_rays.json, r10_shade_rays_sampled.json with --sampled, r12_shade_rays_paths.json with --paths)"""
+--sorted (alone, or with --sampled / --paths): instead of the comparison with the render, what sorting a shuffled batch on the GPU
+buys (tools/sorted_legs.py): the shuffled rays (and keys) (a) as they are, (b) rtu_ray_order_device + gather of rays and keys + the
+batch + scatter as one region, (c) those parts one by one, and the image-order batch beside them; every timed launch is complete
+(rtu_frame_status) and every sorted one is compared byte for byte with the unsorted answers.
+
+usage: tools/shade_rays_bench.py [--sampled | --paths] [--sorted] [--reps 20] [--warmup 3] [--out FILE]
+(profiles/r09_shade_rays.json, r10_shade_rays_sampled.json with --sampled, r12_shade_rays_paths.json with --paths;
+profiles/r13_ray_sorting.json collects the --sorted runs of this tool and of tools/ray_query_bench.py)"""
 import argparse
 import json
 import os
@@ -26,6 +32,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.insert(0, os.path.join(REPO, "tools"))
 
 TAGS = ["teapot2_1080", "p4_1080"]
 PATHS = [("p11_p2_120x68", "Project11/scene.xml"), ("p10_s4_160x120", "Project10/scene.xml")]
@@ -39,6 +46,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--sampled", action="store_true", help="recipe S: rtu_shade_rays_sampled_device against a one-sample frame")
     ap.add_argument("--paths", action="store_true", help="recipe P: rtu_shade_rays_paths_device against a one-sample frame with gather_bounces = 4")
+    ap.add_argument("--sorted", action="store_true", help="time a shuffled batch as it is against order + gather + batch + scatter")
     args = ap.parse_args()
     if args.paths:
         args.sampled = True  # keys, a one-sample frame, 1920x1080: as recipe S
@@ -81,6 +89,20 @@ def main():
         eye = tuple(frame.cam_pos)
         rays, keys = pkg.camera_sample_rays(frame, 0) if args.sampled else (pkg.camera_rays(frame), None)
         n = rays.size
+        if args.sorted:
+            from sorted_legs import sorted_legs
+            perm = np.random.RandomState(1).permutation(n)
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to("cuda:0")
+            if args.sampled:
+                shade = ctx.shade_rays_paths_device if args.paths else ctx.shade_rays_sampled_device
+                call = lambda r, k, o: shade(r, k, n, eye, o, stream.cuda_stream)
+            else:
+                call = lambda r, k, o: ctx.shade_rays_device(r, n, eye, o, stream.cuda_stream)
+            row = sorted_legs(pkg, ctx, torch, stream, n, dev(rays), dev(rays[perm]), dev(keys) if args.sampled else None,
+                              dev(keys[perm]) if args.sampled else None, 16, call, args.reps, args.warmup, True)
+            out["mode"] = "sorted"
+            out["scenes"].append(dict(row, scene=name, width=W, height=H))
+            continue
         d_out = torch.zeros(n * 4, dtype=torch.float32, device="cuda:0")
         row = {"scene": name, "width": W, "height": H, "rays": int(n), "shade_rays": {}}
         render = timed(lambda o: ctx.render_device(frame, o.data_ptr(), stream.cuda_stream), [d_out])
