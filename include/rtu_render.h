@@ -521,6 +521,80 @@ int  rtu_ray_order(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t* h_
 int  rtu_permute_device(RtuContext* ctx, const void* d_src, void* d_dst, const void* d_order, size_t n, uint32_t elem_bytes, int scatter,
                         void* hip_stream);
 
+/* ---- Sensors: images for cameras that are no pinhole (raytracer-utah_amd/csrc/rtu_sensor.hip, rtu_sensor.h) ---------------------------
+ * The ray entries above answer rays; a SENSOR is what fires them and averages the answers: the renderer's outer loop — rays and keys
+ * written on the GPU where the shading kernels read them, the batch loop with its capacity check, the sums in sample order, the exact
+ * mean — for a panoramic (equirectangular), a fisheye (equidistant) and an orthographic sensor. The shading behind the rays is
+ * rtu_shade_rays_device / _sampled_device / _paths_device unchanged, so an image is tied to them bit for bit.
+ *   samples == 0, gather_bounces 0   recipe W: one ray per pixel at offset (0.5, 0.5); a stochastic scene: RTU_ERR_STOCHASTIC
+ *   samples S >= 1, gather_bounces 0 recipe S: sample k at ox = (float)k * (float)(1.0 / S) + halton(k, 4), oy likewise with base 5 —
+ *                                    the offsets of rtu_camera_sample_rays —, key = rtu_sample_key(x + width * y, k). Purposes 0 and
+ *                                    1 of the key stay undrawn: a sensor has no lens.
+ *   samples S >= 1, gather_bounces 4 recipe P, offsets and keys as recipe S
+ * THE RAY of pixel (x, y) with offsets (ox, oy): binary32, one rounding per operation, in the order written; sincos is the
+ * portable_sincos of the sample streams; tmax = RTU_BIGFLOAT. u = ((float)x + ox) / (float)width, v = ((float)y + oy) / (float)height.
+ *   RTU_SENSOR_EQUIRECT  u >= 1: u -= 1; v > 1: v = 1 (the offsets reach into [0, 2)). lon = u * 6.2831855f, pol = v * 3.1415927f,
+ *                        (sl, cl) = sincos(lon), (sp, cp) = sincos(pol), h = forward * (-cl) + right * (-sl),
+ *                        dir = norm3(up * cp + h * sp), org = pos: the centre column looks along forward, the top row along up.
+ *   RTU_SENSOR_FISHEYE   (equidistant) R = 0.5f * (float)min(width, height), dx = (((float)x + ox) - 0.5f * (float)width) / R, dy likewise
+ *                        with y and height, r = sqrtf(dx * dx + dy * dy). r > 1: outside the image circle: org = pos, dir = 0 — an
+ *                        INVALID ray by the rule of the ray queries: never traced, sixteen zero bytes. r == 0: dir = forward. Otherwise
+ *                        a = r * (fov_deg * 0.008726646f) (within [0, pi] for fov_deg <= 360), (sa, ca) = sincos(a),
+ *                        dir = norm3(forward * ca + (right * (dx / r) + up * (-(dy / r))) * sa), org = pos.
+ *   RTU_SENSOR_ORTHO     org = (pos + right * ((u - 0.5f) * extent[0])) + up * ((0.5f - v) * extent[1]), dir = forward.
+ * rtu_sensor_rays (pure host code, needs no GPU and no context) is the specification of these expressions: the rays and keys of
+ * sample `sample` for image rows [row0, row0 + nrows), width * nrows of each in image order, under the row and argument rules of
+ * rtu_camera_sample_rays. samples == 0: sample must be 0, keys are rtu_sample_key(pixel, 0) (no entry reads them for recipe W).
+ * rtu_sensor_rays_device writes the same bits for samples [sample0, sample0 + nsamples) into DEVICE memory, sample-major: ray
+ * (k - sample0) * pixels + pixel (pixels = width * height), d_rays 16-byte aligned (32 bytes per ray), d_keys 4-byte aligned or NULL.
+ * Asynchronous on hip_stream, allocates nothing, needs no scene and touches nothing of the context but its device id: any stream.
+ * The buffers go as they are to rtu_trace_rays_device / rtu_occluded_rays_device (depth, visibility) or to the shading entries.
+ * THE IMAGE  rtu_render_sensor / rtu_render_sensor_device: per pixel one float4 {r, g, b, z}; with n = max(samples, 1):
+ *   rgb = (the sum of the samples' rgb in sample order, binary32) / n; z = (the sum of t over the samples that hit) / their number, or
+ *   RTU_BIGFLOAT when none hit — the resolve of a recipe S frame. A miss adds the environment colour (as for every ray batch) and is
+ *   no hit; a sample outside the fisheye circle adds zeros and is no hit (t == 0 identifies it); a hit adds its colour, and t to z.
+ * pos is the eye of every Shade() call (one eye per call, as RtuShadeDesc.eye), flags (0 or RTU_QUERY_REFERENCE_WALK) and max_bounce go
+ * to the shading entry; the image is the same with and without the flag, byte for byte. Both calls are RENDERS as the ray batches
+ * are (frame records, counters, launch hints; ONE STREAM PER CONTEXT) but leave the frame accumulators and every progressive session
+ * alone: rays, keys, samples and sums live in grow-only buffers of their own, so a second call of the same shape allocates nothing.
+ * They run batches of at most min(RTU_MAX_BATCH, 2^25 / pixels) samples; a batch that ran out of frame records is shaded again with
+ * the grown capacities (the counting variant of recipe P returns RTU_ERR_CAPACITY, as rtu_shade_rays_paths does); the cancel flag is
+ * polled before every batch (RTU_ERR_CANCELLED). Both forms return when the image is complete — the _device form has then waited
+ * for hip_stream —, and rtu_frame_status is clean afterwards.
+ * RTU_ERR_ARG: a NULL descriptor or output, an unknown model, width or height < 1, width * height > 2^25, a non-finite pos, frame
+ * vector, fov_deg or extent, a frame vector with |dot(a, a) - 1| > 2e-3 or a pair with |dot(a, b)| > 2e-3 (the band of the ray rule;
+ * the vectors are used as given), fov_deg outside (0, 360] (fisheye), an extent <= 0 (orthographic), samples < 0 or > 65536,
+ * gather_bounces not 0 / 4 or 4 with samples == 0, max_bounce outside 0 .. RTU_MAX_BOUNCE, an unknown flag bit, non-zero reserved, a
+ * misaligned device pointer; rtu_sensor_rays_device: sample0 / nsamples outside the samples, more than 2^26 rays. RTU_ERR_NO_SCENE
+ * (the render entries) before rtu_upload_scene. */
+#define RTU_SENSOR_EQUIRECT 0
+#define RTU_SENSOR_FISHEYE  1
+#define RTU_SENSOR_ORTHO    2
+typedef struct RtuSensorDesc {     /* 128 B */
+    int32_t  model;                /* RTU_SENSOR_* */
+    int32_t  width, height;
+    int32_t  samples;              /* as RtuFrameDesc.samples: 0 recipe W, S >= 1 recipes S / P */
+    int32_t  gather_bounces;       /* as RtuFrameDesc.gather_bounces: 0, or 4 for recipe P */
+    int32_t  max_bounce;           /* as RtuFrameDesc.max_bounce */
+    uint32_t flags;                /* 0, or RTU_QUERY_REFERENCE_WALK */
+    float    pos[3];               /* ray origin (equirectangular, fisheye), window centre (orthographic); the eye of every Shade() call */
+    float    right[3], up[3], forward[3];  /* an orthonormal frame, used as given */
+    float    fov_deg;              /* fisheye: the full angle, in (0, 360] */
+    float    extent[2];            /* orthographic: width and height of the window in world units, > 0 */
+    uint32_t reserved[10];         /* must be 0 */
+} RtuSensorDesc;
+/* Writes exactly sizeof(RtuSensorDesc) bytes: an equirectangular 1 x 1 sensor at the origin, right +x, up +y, forward -z, samples 0,
+ * gather_bounces 0, max_bounce 5, flags 0, fov_deg 180, extent 1 x 1. Pure host code. */
+int  rtu_sensor_defaults(RtuSensorDesc* out);
+int  rtu_sensor_rays(const RtuSensorDesc* sensor, int sample, int row0, int nrows, RtuRay* rays_out, uint32_t* keys_out);
+int  rtu_sensor_rays_device(RtuContext* ctx, const RtuSensorDesc* sensor, int sample0, int nsamples, void* d_rays, void* d_keys, void* hip_stream);
+int  rtu_render_sensor(RtuContext* ctx, const RtuSensorDesc* sensor, float* h_rgbz);
+int  rtu_render_sensor_device(RtuContext* ctx, const RtuSensorDesc* sensor, void* d_rgbz, void* hip_stream);
+/* Diagnostic: on != 0 brackets the two kernels of later sensor renders (k_sensor_rays, k_sensor_accumulate) and each whole render with
+ * HIP events on the render's stream (it then waits for every batch's accumulation); ms_out3 (may be NULL) gets the milliseconds summed
+ * since the previous call: {k_sensor_rays, k_sensor_accumulate, the renders}; they are reset. The images do not change. */
+int  rtu_debug_sensor_timing(RtuContext* ctx, int on, float* ms_out3);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

@@ -157,7 +157,9 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays",
                "rtu_shade_rays_sampled_device", "rtu_shade_rays_sampled", "rtu_camera_sample_rays", "rtu_sample_key", "rtu_child_key",
                "rtu_shade_rays_paths_device", "rtu_shade_rays_paths", "rtu_debug_last_tail_from",
-               "rtu_ray_sort_box", "rtu_scene_sort_box", "rtu_ray_sort_keys", "rtu_ray_order_device", "rtu_ray_order", "rtu_permute_device", "rtu_copy_to_device"]
+               "rtu_ray_sort_box", "rtu_scene_sort_box", "rtu_ray_sort_keys", "rtu_ray_order_device", "rtu_ray_order", "rtu_permute_device", "rtu_copy_to_device",
+               "rtu_sensor_defaults", "rtu_sensor_rays", "rtu_sensor_rays_device", "rtu_render_sensor", "rtu_render_sensor_device",
+               "rtu_debug_sensor_timing"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -318,6 +320,61 @@ _sig(hip, "rtu_permute_device", _I, _P, _P, _P, _P, ctypes.c_size_t, ctypes.c_ui
 _sig(hip, "rtu_copy_to_device", _I, _P, _P, _P, ctypes.c_size_t)
 _sig(hip, "rtu_context_stream", _P, _P)
 _sig(hip, "rtu_context_sync", _I, _P)
+
+
+# sensors (include/rtu_render.h, "Sensors")
+RTU_SENSOR_EQUIRECT, RTU_SENSOR_FISHEYE, RTU_SENSOR_ORTHO = 0, 1, 2
+SENSOR_MODELS = {"equirect": RTU_SENSOR_EQUIRECT, "fisheye": RTU_SENSOR_FISHEYE, "ortho": RTU_SENSOR_ORTHO}
+
+
+class RtuSensorDesc(ctypes.Structure):
+    """include/rtu_render.h RtuSensorDesc (128 bytes): a panoramic, fisheye or orthographic sensor and how it is sampled."""
+    _fields_ = [("model", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("samples", ctypes.c_int32),
+                ("gather_bounces", ctypes.c_int32), ("max_bounce", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("pos", ctypes.c_float * 3), ("right", ctypes.c_float * 3), ("up", ctypes.c_float * 3), ("forward", ctypes.c_float * 3),
+                ("fov_deg", ctypes.c_float), ("extent", ctypes.c_float * 2), ("reserved", ctypes.c_uint32 * 10)]
+
+
+_sig(hip, "rtu_sensor_defaults", _I, ctypes.POINTER(RtuSensorDesc))
+_sig(hip, "rtu_sensor_rays", _I, ctypes.POINTER(RtuSensorDesc), _I, _I, _I, _P, _P)
+_sig(hip, "rtu_sensor_rays_device", _I, _P, ctypes.POINTER(RtuSensorDesc), _I, _I, _P, _P, _P)
+_sig(hip, "rtu_render_sensor", _I, _P, ctypes.POINTER(RtuSensorDesc), _P)
+_sig(hip, "rtu_render_sensor_device", _I, _P, ctypes.POINTER(RtuSensorDesc), _P, _P)
+_sig(hip, "rtu_debug_sensor_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
+
+
+def sensor_desc(model, width, height, pos, right, up, forward, samples=0, gather_bounces=0, max_bounce=5, fov_deg=180.0, extent=(1, 1),
+                reference_walk=False):
+    """An RtuSensorDesc: rtu_sensor_defaults, then the fields. model: RTU_SENSOR_* or "equirect" / "fisheye" / "ortho"; right, up and
+    forward are an orthonormal frame, used as given; samples / gather_bounces select the recipe as for frame_setup."""
+    d = RtuSensorDesc()
+    hip.rtu_sensor_defaults(ctypes.byref(d))
+    d.model = SENSOR_MODELS[model] if isinstance(model, str) else int(model)
+    d.width, d.height = int(width), int(height)
+    d.samples, d.gather_bounces, d.max_bounce = int(samples), int(gather_bounces), int(max_bounce)
+    d.flags = RTU_QUERY_REFERENCE_WALK if reference_walk else 0
+    d.pos[:] = [float(x) for x in pos]
+    d.right[:] = [float(x) for x in right]
+    d.up[:] = [float(x) for x in up]
+    d.forward[:] = [float(x) for x in forward]
+    d.fov_deg = float(fov_deg)
+    d.extent[:] = [float(x) for x in extent]
+    return d
+
+
+def sensor_rays(desc, sample=0, row0=0, nrows=None):
+    """rtu_sensor_rays (pure host code, the specification of a sensor's rays): the rays and keys of sample `sample` of the sensor, image
+    rows [row0, row0 + nrows): (rays [nrows * width] of ray_dtype(), keys uint32 [nrows * width]) in image order. A fisheye sample
+    outside the image circle has dir = 0: an invalid ray, which no entry traces."""
+    import numpy as np
+    if nrows is None:
+        nrows = desc.height - row0
+    n = max(nrows, 0) * max(desc.width, 0)
+    rays, keys = np.zeros(n, ray_dtype()), np.zeros(n, np.uint32)
+    rc = hip.rtu_sensor_rays(ctypes.byref(desc), sample, row0, nrows, rays.ctypes.data if n else None, keys.ctypes.data if n else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_sensor_rays: a sensor descriptor out of its rules, sample outside the samples or rows outside the image")
+    return rays, keys
 
 
 def shade_desc(eye=(0.0, 0.0, 0.0), max_bounce=5, reference_walk=False):
@@ -1134,6 +1191,32 @@ class Context:
         (RTU_ERR_CAPACITY: call this again)."""
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         self._check(hip.rtu_shade_rays_paths_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
+
+    def sensor_rays_device(self, desc, d_rays_ptr, d_keys_ptr=None, sample0=0, nsamples=1, stream=None):
+        """rtu_sensor_rays_device: the rays (and keys, unless d_keys_ptr is None) of samples [sample0, sample0 + nsamples) of the
+        sensor into device memory, sample-major — ray (k - sample0) * width * height + pixel —, the bits of sensor_rays, asynchronous
+        on `stream`. Needs no scene."""
+        self._check(hip.rtu_sensor_rays_device(self._h, ctypes.byref(desc), sample0, nsamples, d_rays_ptr, d_keys_ptr, stream))
+
+    def render_sensor(self, desc):
+        """rtu_render_sensor: the image of the sensor, float32 [height, width, 4] {r, g, b, z} (what Image.fill accepts): per pixel
+        the mean of its samples in sample order, z the mean t of the samples that hit (RTU_BIGFLOAT when none did)."""
+        import numpy as np
+        out = np.empty((max(desc.height, 0), max(desc.width, 0), 4), np.float32)
+        self._check(hip.rtu_render_sensor(self._h, ctypes.byref(desc), out.ctypes.data if out.size else None))
+        return out
+
+    def render_sensor_device(self, desc, d_ptr, stream=None):
+        """rtu_render_sensor_device: the same image into device memory (height * width float4 at d_ptr, 16-byte aligned), the
+        launches on `stream`; returns when the image is complete."""
+        self._check(hip.rtu_render_sensor_device(self._h, ctypes.byref(desc), d_ptr, stream))
+
+    def sensor_timing(self, on=True):
+        """Time the kernels of later sensor renders; returns the ms spent since the previous call in k_sensor_rays, in
+        k_sensor_accumulate and in the renders as a whole."""
+        o = (ctypes.c_float * 3)()
+        self._check(hip.rtu_debug_sensor_timing(self._h, int(on), o))
+        return dict(zip(("rays", "accumulate", "render"), list(o)))
 
     def occluded_device(self, d_rays_ptr, n, d_occluded_ptr, stream=None, reference_walk=False, flags=None):
         """rtu_occluded_rays_device: n RtuRay at d_rays_ptr -> n bytes (1 / 0) at d_occluded_ptr, asynchronous on `stream`."""
