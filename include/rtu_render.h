@@ -329,7 +329,7 @@ void rtu_progressive_free(RtuProgressive* p);
  * unit length: the conservative bounds of the fast walk were argued, and are tested, for the renderer's own rays. A ray is INVALID
  * and is not traced when a component of org, dir or tmax is NaN or infinite, when tmax <= 0, or when |dot(dir, dir) - 1| > 2e-3
  * (binary32, (x x + y y) + z z): it gets RTU_RAY_INVALID with the values of a miss, or 0 from the occlusion form.
- * Textures are not evaluated; uvw, face index and barycentrics are not reported.
+ * Textures are not evaluated; uvw, face index and barycentrics are not reported (rtu_ray_features adds the textured albedo of the hit).
  * flags: 0, or RTU_QUERY_REFERENCE_WALK for the walk of the counting variant (the reference's own tree, no culling, no node-level
  * bounds): every field of every answer is the same, bit for bit; it is slower. rtu_debug_walk_stack_limit and rtu_debug_node_bounds
  * apply as to a render; rtu_debug_flags does not.
@@ -594,6 +594,71 @@ int  rtu_render_sensor_device(RtuContext* ctx, const RtuSensorDesc* sensor, void
  * HIP events on the render's stream (it then waits for every batch's accumulation); ms_out3 (may be NULL) gets the milliseconds summed
  * since the previous call: {k_sensor_rays, k_sensor_accumulate, the renders}; they are reset. The images do not change. */
 int  rtu_debug_sensor_timing(RtuContext* ctx, int on, float* ms_out3);
+
+/* ---- First-hit features: the guides of a feature-guided filter (raytracer-utah_amd/csrc/rtu_features.hip) ---------------------------
+ * Per ray one RtuRayHit — every byte as rtu_trace_rays_device writes it, the invalid-ray rule and RTU_QUERY_REFERENCE_WALK included —
+ * and one float4 ALBEDO {r, g, b, 0}: what MtlBlinn::Shade returns for that hit under one AmbientLight of intensity (1, 1, 1) with
+ * bounceCount 0 (mtlFunctions.cpp:125-133). On a front face that is diffuse.Sample(hInfo.uvw) — texture maps evaluated at the hit's
+ * texture coordinates, the sub-material a MultiMtl node was given, white for a node without a material, as in a render; on a back
+ * face {0, 0, 0}. A miss or an invalid ray: {0, 0, 0, 0}. These are the bits rtu_shade_rays gives with max_bounce 0 for the scene with
+ * that one light.
+ *   rtu_ray_features     n caller-supplied rays, as rtu_trace_rays takes them.
+ *   rtu_frame_features   the pixel-centre ray of every pixel of `frame` (the rays of rtu_camera_rays, generated in the kernel: no ray
+ *                        buffer, no upload), width * height answers in image order. frame.shard_count must be 1 (RTU_ERR_ARG);
+ *                        samples, gather_bounces, dof and max_bounce are ignored: the guide of a depth-of-field or multi-sample frame
+ *                        is its pixel-centre pinhole ray.
+ * Errors as for rtu_trace_rays_device: RTU_ERR_ARG for an unknown flag bit, a NULL pointer with n > 0, a device pointer that is not
+ * 16-byte aligned, a NULL frame or a resolution outside 1 .. 65536; RTU_ERR_NO_SCENE. n == 0 is RTU_OK and launches nothing.
+ * The _device forms allocate nothing, read the scene's buffers only, touch no frame state and are asynchronous on hip_stream. The host
+ * forms copy through grow-only buffers of the context (at most 2^20 rays / pixels at a time) on its stream and are synchronous. */
+int  rtu_ray_features_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* d_albedo, void* hip_stream);
+int  rtu_ray_features(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo);
+int  rtu_frame_features_device(RtuContext* ctx, const RtuFrameDesc* frame, void* d_hits, void* d_albedo, void* hip_stream);
+int  rtu_frame_features(RtuContext* ctx, const RtuFrameDesc* frame, RtuRayHit* h_hits, float* h_albedo);
+
+/* ---- Denoising: an edge-avoiding filter for sampled previews (raytracer-utah_amd/csrc/rtu_denoise.h, rtu_denoise.hip) ---------------
+ * A five-pass (n_passes) 5 x 5 a-trous wavelet filter on albedo-demodulated colour, guided by the features above. It has no
+ * transcendental function; all arithmetic is binary32, one rounding per operation, no contraction, in this order — the host form and
+ * the device form give the same bits:
+ *   per pixel p   c = rgb of the float4 {r, g, b, z} image, H = its RtuRayHit, a = its albedo; p is VALID iff H.flags & RTU_RAY_HIT.
+ *   demodulate    per channel d = a > 0.01f ? a : 1.0f, e = c / d.
+ *   pass i        (i = 0 .. n_passes - 1) step s = 1 << i, sc = sigma_color * 2^-i (exact), sc2 = sc * sc. For a valid p, the taps
+ *                 q = p + s * (dx, dy), dy outer, dx inner, both -2 .. 2, skipping q outside the image and q not valid:
+ *                   h = k[dy + 2] * k[dx + 2], k = {1/16, 1/4, 3/8, 1/4, 1/16} (exact products)
+ *                   dot = (Np.x Nq.x + Np.y Nq.y) + Np.z Nq.z;  t = dot > 0 ? dot : 0 (a NaN gives 0), then t = t * t repeated
+ *                   normal_log2_power times
+ *                   D = Pq - Pp;  dd = (Np.x D.x + Np.y D.y) + Np.z D.z;  x = dd / (sigma_plane * Hp.t);  wp = 1 / (1 + x * x)
+ *                   delta = e_q - e_p;  dc = (dr dr + dg dg) + db db;  wc = 1 / (1 + dc / sc2)
+ *                   w = ((h * t) * wp) * wc;  per channel acc = acc + e_q * w;  wsum = wsum + w
+ *                 then e_p = wsum > 0 ? acc / wsum : e_p. Every tap reads the PREVIOUS pass's e.
+ *   output        rgb = e * d for a valid pixel, the input rgb bit for bit for any other; z is always the input z bit for bit.
+ * RTU_ERR_ARG: a NULL pointer, width or height outside 1 .. 65536, n_passes outside 1 .. 8, normal_log2_power outside 0 .. 7, a sigma
+ * that is not > 0, a non-zero reserved word, a device pointer that is not 16-byte aligned.
+ *   rtu_denoise          pure host code, no GPU and no context: the executable statement of the rules above. h_rgbz_out may be h_rgbz_in.
+ *   rtu_denoise_device   the same bits from device memory, asynchronous on hip_stream. d_out == d_in is allowed. Its four planes
+ *                        (64 B per pixel) are grow-only buffers of the context: one stream per context at a time, and no allocation
+ *                        once a frame of that size has been filtered. Needs no scene.
+ * The filter is for previews of recipes S and P at low sample counts; measured error ratios are in DESIGN.md section 22. */
+typedef struct RtuDenoiseDesc {    /* 32 B */
+    int32_t  width, height;
+    int32_t  n_passes;             /* 1 .. 8 */
+    float    sigma_color;          /* > 0 */
+    float    sigma_plane;          /* > 0 */
+    int32_t  normal_log2_power;    /* 0 .. 7: the cosine of the normals is raised to 2^this */
+    uint32_t reserved[2];          /* must be 0 */
+} RtuDenoiseDesc;
+int  rtu_denoise_defaults(RtuDenoiseDesc* out);   /* width, height 0; n_passes 5, sigma_color 1, sigma_plane 0.05, normal_log2_power 5 */
+int  rtu_denoise(const RtuDenoiseDesc* desc, const float* h_rgbz_in, const RtuRayHit* h_hits, const float* h_albedo, float* h_rgbz_out);
+int  rtu_denoise_device(RtuContext* ctx, const RtuDenoiseDesc* desc, const void* d_in, const void* d_hits, const void* d_albedo, void* d_out,
+                        void* hip_stream);
+/* The snapshot of rtu_progressive_snapshot, filtered: rtu_denoise of it with rtu_frame_features of the session's frame. desc_or_NULL:
+ * NULL selects rtu_denoise_defaults; width and height are the session's frame's, those of desc are ignored. The session computes its
+ * frame's features once, at the first such call, and keeps them (its camera and scene are fixed): from the second call on nothing is
+ * allocated. The session's sums are not touched. RTU_ERR_ARG: a sharded session (shard_count != 1), done == 0, a desc outside its
+ * rules. After RTU_ERR_STALE it still answers from the features it holds, as rtu_progressive_snapshot does; a session that holds none
+ * returns RTU_ERR_STALE. The _device form writes width * height float4 asynchronously on hip_stream; the host form is synchronous. */
+int  rtu_progressive_snapshot_denoised_device(RtuProgressive* p, const RtuDenoiseDesc* desc_or_NULL, void* d_rgbz, void* hip_stream);
+int  rtu_progressive_snapshot_denoised(RtuProgressive* p, const RtuDenoiseDesc* desc_or_NULL, float* h_rgbz);
 
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds

@@ -159,7 +159,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_shade_rays_paths_device", "rtu_shade_rays_paths", "rtu_debug_last_tail_from",
                "rtu_ray_sort_box", "rtu_scene_sort_box", "rtu_ray_sort_keys", "rtu_ray_order_device", "rtu_ray_order", "rtu_permute_device", "rtu_copy_to_device",
                "rtu_sensor_defaults", "rtu_sensor_rays", "rtu_sensor_rays_device", "rtu_render_sensor", "rtu_render_sensor_device",
-               "rtu_debug_sensor_timing"]
+               "rtu_debug_sensor_timing",
+               "rtu_ray_features_device", "rtu_ray_features", "rtu_frame_features_device", "rtu_frame_features",
+               "rtu_denoise_defaults", "rtu_denoise", "rtu_denoise_device",
+               "rtu_progressive_snapshot_denoised_device", "rtu_progressive_snapshot_denoised"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -341,6 +344,58 @@ _sig(hip, "rtu_sensor_rays_device", _I, _P, ctypes.POINTER(RtuSensorDesc), _I, _
 _sig(hip, "rtu_render_sensor", _I, _P, ctypes.POINTER(RtuSensorDesc), _P)
 _sig(hip, "rtu_render_sensor_device", _I, _P, ctypes.POINTER(RtuSensorDesc), _P, _P)
 _sig(hip, "rtu_debug_sensor_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
+
+
+# first-hit features and the denoising filter (include/rtu_render.h, "First-hit features", "Denoising")
+class RtuDenoiseDesc(ctypes.Structure):
+    """include/rtu_render.h RtuDenoiseDesc (32 bytes): the size of the image and the four constants of the filter."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_passes", ctypes.c_int32), ("sigma_color", ctypes.c_float),
+                ("sigma_plane", ctypes.c_float), ("normal_log2_power", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+_sig(hip, "rtu_ray_features_device", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P, _P)
+_sig(hip, "rtu_ray_features", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P)
+_sig(hip, "rtu_frame_features_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P, _P)
+_sig(hip, "rtu_frame_features", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P)
+_sig(hip, "rtu_denoise_defaults", _I, ctypes.POINTER(RtuDenoiseDesc))
+_sig(hip, "rtu_denoise", _I, ctypes.POINTER(RtuDenoiseDesc), _P, _P, _P, _P)
+_sig(hip, "rtu_denoise_device", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P, _P, _P, _P, _P)
+_sig(hip, "rtu_progressive_snapshot_denoised_device", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P, _P)
+_sig(hip, "rtu_progressive_snapshot_denoised", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P)
+
+
+def denoise_desc(width=0, height=0, **overrides):
+    """An RtuDenoiseDesc: rtu_denoise_defaults (n_passes 5, sigma_color 1, sigma_plane 0.05, normal_log2_power 5), the size, then `overrides`."""
+    d = RtuDenoiseDesc()
+    hip.rtu_denoise_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def denoise(rgbz, hits, albedo, desc=None):
+    """rtu_denoise (pure host code, the specification of the filter): rgbz float32 [H, W, 4], hits [H * W] of hit_dtype() and albedo
+    float32 [H * W, 4] as frame_features / ray_features return them -> the filtered float32 [H, W, 4]. desc: an RtuDenoiseDesc whose
+    width and height are taken from rgbz (None: the defaults)."""
+    import numpy as np
+    rgbz = np.ascontiguousarray(rgbz, np.float32)
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
+    d = RtuDenoiseDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else denoise_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    out = np.empty_like(rgbz)
+    rc = hip.rtu_denoise(ctypes.byref(d), rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data, out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_denoise: an empty image or a descriptor outside its rules (n_passes 1..8, sigmas > 0, "
+                           "normal_log2_power 0..7, reserved words 0)")
+    return out
 
 
 def sensor_desc(model, width, height, pos, right, up, forward, samples=0, gather_bounces=0, max_bounce=5, fov_deg=180.0, extent=(1, 1),
@@ -890,6 +945,17 @@ class Progressive:
     def snapshot_device(self, d_rgbz, d_counts=None, stream=None):
         self._check(hip.rtu_progressive_snapshot_device(self._h, d_rgbz, d_counts, stream))
 
+    def snapshot_denoised(self, desc=None):
+        """The image now, filtered (rtu_progressive_snapshot_denoised): denoise(snapshot, frame_features of the session's frame) as
+        float32 [H, W, 4]. desc: an RtuDenoiseDesc (None: the defaults). The features are made at the first call and kept."""
+        import numpy as np
+        out = np.empty((self.frame.height, self.frame.width, 4), np.float32)
+        self._check(hip.rtu_progressive_snapshot_denoised(self._h, ctypes.byref(desc) if desc is not None else None, out.ctypes.data))
+        return out
+
+    def snapshot_denoised_device(self, d_rgbz, desc=None, stream=None):
+        self._check(hip.rtu_progressive_snapshot_denoised_device(self._h, ctypes.byref(desc) if desc is not None else None, d_rgbz, stream))
+
     def close(self):
         if self._h:
             hip.rtu_progressive_free(self._h)
@@ -1113,6 +1179,40 @@ class Context:
         data_ptr()), asynchronous on `stream`. flags (an integer) overrides reference_walk."""
         f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
         self._check(hip.rtu_trace_rays_device(self._h, d_rays_ptr, n, f, d_hits_ptr, stream))
+
+    def ray_features(self, rays, reference_walk=False):
+        """First-hit features of caller-supplied rays (rtu_ray_features): rays as for trace_rays; returns (hits [n] of hit_dtype() — the
+        bytes of trace_rays —, albedo float32 [n, 4] {r, g, b, 0}: the textured diffuse colour at a front-face hit, white for a node
+        without a material, zero on a back face, at a miss and for an invalid ray)."""
+        import numpy as np
+        r = _as_rays(rays)
+        hits, albedo = np.zeros(r.size, hit_dtype()), np.zeros((r.size, 4), np.float32)
+        self._check(hip.rtu_ray_features(self._h, r.ctypes.data if r.size else None, r.size, RTU_QUERY_REFERENCE_WALK if reference_walk else 0,
+                                         hits.ctypes.data if r.size else None, albedo.ctypes.data if r.size else None))
+        return hits, albedo
+
+    def ray_features_device(self, d_rays_ptr, n, d_hits_ptr, d_albedo_ptr, stream=None, reference_walk=False, flags=None):
+        """rtu_ray_features_device: n RtuRay -> n RtuRayHit and n float4 albedo in device memory (16-byte aligned), asynchronous on `stream`."""
+        f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
+        self._check(hip.rtu_ray_features_device(self._h, d_rays_ptr, n, f, d_hits_ptr, d_albedo_ptr, stream))
+
+    def frame_features(self, frame):
+        """rtu_frame_features: ray_features of the pixel-centre rays of `frame` (camera_rays(frame)), generated on the GPU:
+        (hits [H * W], albedo float32 [H * W, 4]) in image order. frame.shard_count must be 1."""
+        import numpy as np
+        n = max(frame.width, 0) * max(frame.height, 0)
+        hits, albedo = np.zeros(n, hit_dtype()), np.zeros((n, 4), np.float32)
+        self._check(hip.rtu_frame_features(self._h, ctypes.byref(frame), hits.ctypes.data if n else None, albedo.ctypes.data if n else None))
+        return hits, albedo
+
+    def frame_features_device(self, frame, d_hits_ptr, d_albedo_ptr, stream=None):
+        """rtu_frame_features_device: width * height RtuRayHit and float4 albedo into device memory, asynchronous on `stream`."""
+        self._check(hip.rtu_frame_features_device(self._h, ctypes.byref(frame), d_hits_ptr, d_albedo_ptr, stream))
+
+    def denoise_device(self, desc, d_in_ptr, d_hits_ptr, d_albedo_ptr, d_out_ptr, stream=None):
+        """rtu_denoise_device: the filter of denoise() on device memory (desc.width * desc.height float4 / RtuRayHit / float4), the same
+        bits, asynchronous on `stream`; d_out_ptr may be d_in_ptr. Its planes are grow-only buffers of the context."""
+        self._check(hip.rtu_denoise_device(self._h, ctypes.byref(desc), d_in_ptr, d_hits_ptr, d_albedo_ptr, d_out_ptr, stream))
 
     def shade_rays(self, rays, eye, max_bounce=5, reference_walk=False, stats=False, desc=None, sort=False):
         """Radiance along caller-supplied rays (rtu_shade_rays): rays as for trace_rays; eye is the camera position of Shade()'s view

@@ -3,8 +3,10 @@
 // kernel launch. Compiled by hipcc with -ffp-contract=off so the few host-side
 // float computations (triangle normals, camera frame) round exactly like the
 // reference's CPU code.
+#include "rtu_denoise.h"
 #include "rtu_devbuf.h"
 #include "rtu_device.h"
+#include "rtu_features.h"
 #include "rtu_lightlist.h"
 #include "rtu_meshrec.h"
 #include "rtu_query.h"
@@ -135,6 +137,8 @@ struct RtuContext {
     int4* node_rects = nullptr;              // [RTU_MAX_FRAME_BATCH][n_nodes] screen rectangles of the node-level bounds (k_node_rects); owned by the scene
     DevBuf<float4>  q_rays, q_hits;          // ray queries, host forms (rtu_trace_rays / rtu_occluded_rays): one chunk of rays and of answers
     DevBuf<uint8_t> q_occ;
+    DevBuf<float4>  ft_albedo;               // first-hit features, host forms (rtu_ray_features / rtu_frame_features): one chunk of albedo (rays and hits: q_rays, q_hits)
+    DevBuf<float4>  dn_planes;               // the denoising filter (rtu_denoise_device): its four planes gN, gP, e0, e1 of one frame
     DevBuf<float4>  sh_rays, sh_out;         // ray batches, host form (rtu_shade_rays): one chunk of rays and of {r, g, b, t}
     DevBuf<uint32_t> sh_keys;                // ... and of keys (rtu_shade_rays_sampled)
     float sort_box[6] = {};                  // ray sorting (rtu_raysort.h): the box the keys are quantised in, kept by place_scene
@@ -1773,6 +1777,8 @@ struct RtuProgressive {
     DevBuf<uint32_t> n_dev;
     PinnedBuf<uint32_t> n_host;
     SampleSums      sums;
+    DevBuf<float4>   ft_hits, ft_albedo;  // rtu_progressive_snapshot_denoised: the first-hit features of the frame, made at the first such call
+    bool            has_features = false;
 };
 
 static void progressive_release(RtuProgressive* p) {
@@ -1783,6 +1789,9 @@ static void progressive_release(RtuProgressive* p) {
     for (DevBuf<uint4>& l : p->list) l.reset();
     p->n_dev.reset();
     p->n_host.reset();
+    p->ft_hits.reset();
+    p->ft_albedo.reset();
+    p->has_features = false;
     p->sums = SampleSums();
     p->ctx = nullptr;
 }
@@ -3400,6 +3409,155 @@ int rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t 
     const int rc = query_args(ctx, h_rays, h_occluded, n, flags, false);
     if (rc != RTU_OK || n == 0) return rc;
     return query_host(ctx, h_rays, n, flags, nullptr, h_occluded);
+}
+
+// ---- first-hit features (rtu_features.hip) and the denoising filter (rtu_denoise.hip) -----------------------------------------------
+namespace {
+static int feature_cam(RtuContext* ctx, const RtuFrameDesc* f, FeatureCam& cam) {
+    if (!f) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
+    if (f->width <= 0 || f->height <= 0 || f->width > 65536 || f->height > 65536) return fail(ctx, RTU_ERR_ARG, "bad resolution");
+    if (f->shard_count != 1 || f->shard_rank != 0) return fail(ctx, RTU_ERR_ARG, "the features of a frame are those of the whole image: shard_count must be 1");
+    for (int k = 0; k < 3; k++) { cam.pos[k] = f->cam_pos[k]; cam.origin[k] = f->origin[k]; cam.u[k] = f->u[k]; cam.v[k] = f->v[k]; }
+    cam.width = f->width;
+    cam.height = f->height;
+    return RTU_OK;
+}
+
+static bool misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+
+// chunks of rays (h_rays) or of a frame's pixels in image order (cam) through q_rays / q_hits / ft_albedo
+static int features_host(RtuContext* ctx, const RtuRay* h_rays, const FeatureCam* cam, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo) {
+    const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    if (h_rays) RTU_HIP(ctx, ctx->q_rays.grow(2 * chunk));
+    RTU_HIP(ctx, ctx->q_hits.grow(3 * chunk));
+    RTU_HIP(ctx, ctx->ft_albedo.grow(chunk));
+    const DevScene s = query_scene(ctx);
+    for (size_t done = 0; done < n; done += chunk) {
+        const size_t m = n - done < chunk ? n - done : chunk;
+        hipError_t e = hipSuccess;
+        if (h_rays) {
+            e = hipMemcpyAsync(ctx->q_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess) e = (hipError_t)rtu_launch_ray_features(s, ctx->q_rays.get(), ctx->q_hits.get(), ctx->ft_albedo.get(), m,
+                                                                         (flags & RTU_QUERY_REFERENCE_WALK) != 0, ctx->stream);
+        } else {
+            e = (hipError_t)rtu_launch_frame_features(s, *cam, done, m, ctx->q_hits.get(), ctx->ft_albedo.get(), ctx->stream);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(h_hits + done, ctx->q_hits.get(), sizeof(RtuRayHit) * m, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_albedo + 4 * done, ctx->ft_albedo.get(), sizeof(float4) * m, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "first-hit features: %s", hipGetErrorString(e));
+    }
+    return RTU_OK;
+}
+}  // namespace
+
+int rtu_ray_features_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* d_albedo, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (n && !d_albedo) return fail(ctx, RTU_ERR_ARG, "albedo pointer is NULL");
+    if (n && misaligned(d_albedo)) return fail(ctx, RTU_ERR_ARG, "device albedo buffer must be 16-byte aligned");
+    const int rc = query_args(ctx, d_rays, d_hits, n, flags, true);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_ray_features(query_scene(ctx), (const float4*)d_rays, (float4*)d_hits, (float4*)d_albedo, n,
+                                                             (flags & RTU_QUERY_REFERENCE_WALK) != 0, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "first-hit features launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_ray_features(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (n && !h_albedo) return fail(ctx, RTU_ERR_ARG, "albedo pointer is NULL");
+    const int rc = query_args(ctx, h_rays, h_hits, n, flags, false);
+    if (rc != RTU_OK || n == 0) return rc;
+    return features_host(ctx, h_rays, nullptr, n, flags, h_hits, h_albedo);
+}
+
+int rtu_frame_features_device(RtuContext* ctx, const RtuFrameDesc* frame, void* d_hits, void* d_albedo, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    FeatureCam cam;
+    const int rc = feature_cam(ctx, frame, cam);
+    if (rc != RTU_OK) return rc;
+    if (!d_hits || !d_albedo) return fail(ctx, RTU_ERR_ARG, "hits / albedo pointer is NULL");
+    if (misaligned(d_hits) || misaligned(d_albedo)) return fail(ctx, RTU_ERR_ARG, "device hits / albedo buffers must be 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_frame_features(query_scene(ctx), cam, 0, (unsigned long long)cam.width * (unsigned long long)cam.height,
+                                                               (float4*)d_hits, (float4*)d_albedo, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "first-hit features launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_frame_features(RtuContext* ctx, const RtuFrameDesc* frame, RtuRayHit* h_hits, float* h_albedo) {
+    if (!ctx) return RTU_ERR_ARG;
+    FeatureCam cam;
+    const int rc = feature_cam(ctx, frame, cam);
+    if (rc != RTU_OK) return rc;
+    if (!h_hits || !h_albedo) return fail(ctx, RTU_ERR_ARG, "hits / albedo pointer is NULL");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    return features_host(ctx, nullptr, &cam, (size_t)cam.width * (size_t)cam.height, 0, h_hits, h_albedo);
+}
+
+int rtu_denoise_device(RtuContext* ctx, const RtuDenoiseDesc* desc, const void* d_in, const void* d_hits, const void* d_albedo, void* d_out,
+                       void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_denoise_check_desc(desc) != RTU_OK)
+        return fail(ctx, RTU_ERR_ARG, "denoise: width, height 1 .. 65536, n_passes 1 .. 8, normal_log2_power 0 .. 7, sigmas > 0, reserved words 0");
+    if (!d_in || !d_hits || !d_albedo || !d_out) return fail(ctx, RTU_ERR_ARG, "denoise: a device pointer is NULL");
+    if (misaligned(d_in) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_out))
+        return fail(ctx, RTU_ERR_ARG, "denoise: device buffers must be 16-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->dn_planes.grow(4 * (size_t)desc->width * (size_t)desc->height));
+    const hipError_t e = (hipError_t)rtu_launch_denoise(*desc, (const float4*)d_in, (const float4*)d_hits, (const float4*)d_albedo, (float4*)d_out,
+                                                        ctx->dn_planes.get(), (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "denoise launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_progressive_snapshot_denoised_device(RtuProgressive* p, const RtuDenoiseDesc* desc_or_NULL, void* d_rgbz, void* hip_stream) {
+    if (!p || !p->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = p->ctx;
+    FeatureCam cam;
+    int rc = feature_cam(ctx, &p->frame, cam);  // refuses a sharded session
+    if (rc != RTU_OK) return rc;
+    RtuDenoiseDesc d;
+    if (desc_or_NULL) d = *desc_or_NULL;
+    else rtu_denoise_defaults(&d);
+    d.width = cam.width;
+    d.height = cam.height;
+    if (rtu_denoise_check_desc(&d) != RTU_OK)
+        return fail(ctx, RTU_ERR_ARG, "denoise: n_passes 1 .. 8, normal_log2_power 0 .. 7, sigmas > 0, reserved words 0");
+    if (p->done == 0) return fail(ctx, RTU_ERR_ARG, "no samples yet: advance the session first");
+    if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
+    if (misaligned(d_rgbz)) return fail(ctx, RTU_ERR_ARG, "d_rgbz must be 16-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    if (!p->has_features) {
+        // the session's frame as its scene was when it began: a newer scene would guide the filter with surfaces the sums never saw
+        if (p->scene_gen != ctx->scene_gen) return fail(ctx, RTU_ERR_STALE, "the context got a new scene before this session made its features");
+        if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+        RTU_HIP(ctx, p->ft_hits.grow(3 * p->pixels));
+        RTU_HIP(ctx, p->ft_albedo.grow(p->pixels));
+        const hipError_t e = (hipError_t)rtu_launch_frame_features(query_scene(ctx), cam, 0, p->pixels, p->ft_hits.get(), p->ft_albedo.get(),
+                                                                   (hipStream_t)hip_stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "first-hit features launch: %s", hipGetErrorString(e));
+        p->has_features = true;
+    }
+    rc = rtu_progressive_snapshot_device(p, d_rgbz, nullptr, hip_stream);
+    if (rc != RTU_OK) return rc;
+    return rtu_denoise_device(ctx, &d, d_rgbz, p->ft_hits.get(), p->ft_albedo.get(), d_rgbz, hip_stream);  // in place
+}
+
+int rtu_progressive_snapshot_denoised(RtuProgressive* p, const RtuDenoiseDesc* desc_or_NULL, float* h_rgbz) {
+    if (!p || !p->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = p->ctx;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->fb.grow(p->pixels ? p->pixels : 1));
+    const int rc = rtu_progressive_snapshot_denoised_device(p, desc_or_NULL, ctx->fb.get(), ctx->stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), p->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RTU_OK;
 }
 
 // ---- ray batches: Shade() along caller-supplied rays (render_rays_impl.h) -------------------------------------------------------
