@@ -464,6 +464,11 @@ int  rtu_shade_rays_paths(RtuContext* ctx, const RtuRay* h_rays, const uint32_t*
  * The binary32 expressions are the kernels' own in the same order. Pure host code, needs no GPU and no context. RTU_ERR_ARG: NULL
  * frame, width or height < 1, samples < 1, sample outside [0, samples), rows outside the image, a NULL output with nrows > 0. */
 int  rtu_camera_sample_rays(const RtuFrameDesc* frame, int sample, int row0, int nrows, RtuRay* rays_out, uint32_t* keys_out);
+/* The same on the device (k_camera_sample_rays, raytracer-utah_amd/csrc/rtu_camrays.hip, one lane per pixel): width * height RtuRay to
+ * d_rays and as many keys to d_keys, image order, the bits of rtu_camera_sample_rays(frame, sample, 0, height, ...) — a new sample of a
+ * frame costs no upload. Needs no scene, allocates nothing, asynchronous on hip_stream. RTU_ERR_ARG as the host form, and for a NULL
+ * context, a NULL d_rays or d_keys, d_rays not 16-byte or d_keys not 4-byte aligned, more than 2^26 pixels. */
+int  rtu_camera_sample_rays_device(RtuContext* ctx, const RtuFrameDesc* frame, int sample, void* d_rays, void* d_keys, void* hip_stream);
 uint32_t rtu_sample_key(uint32_t pixel, uint32_t sample);   /* sample_key(p, i) as stated above; pure host code */
 uint32_t rtu_child_key(uint32_t key, uint32_t slot);        /* child_key(key, slot) as stated above; pure host code */
 
@@ -659,6 +664,88 @@ int  rtu_denoise_device(RtuContext* ctx, const RtuDenoiseDesc* desc, const void*
  * returns RTU_ERR_STALE. The _device form writes width * height float4 asynchronously on hip_stream; the host form is synchronous. */
 int  rtu_progressive_snapshot_denoised_device(RtuProgressive* p, const RtuDenoiseDesc* desc_or_NULL, void* d_rgbz, void* hip_stream);
 int  rtu_progressive_snapshot_denoised(RtuProgressive* p, const RtuDenoiseDesc* desc_or_NULL, float* h_rgbz);
+
+/* ---- Temporal accumulation: sampled previews that follow a moving camera (raytracer-utah_amd/csrc/rtu_temporal.h, rtu_temporal.hip) ----
+ * One new sample per pixel is blended into what earlier frames accumulated for the same surface point, found by projecting the
+ * pixel's first-hit point into the PREVIOUS camera. The guides are the features above (pinhole pixel-centre rays). A HISTORY is three
+ * planes of width * height float4 each, E then P then N, 48 B per pixel, owned by the caller:
+ *   E = {e.r, e.g, e.b, n}   accumulated albedo-demodulated colour and the history length n
+ *   P = {p.x, p.y, p.z, t}   first-hit point and its distance
+ *   N = {N.x, N.y, N.z, node as bits}
+ * It has no transcendental function; all arithmetic is binary32, one rounding per operation, no contraction, IEEE divisions, in this
+ * order — the host form and the device form give the same bits. dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ * a x b = {a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x}; vector operations are per component.
+ *   per pixel     c = rgb of the float4 {r, g, b, z} image, H = its RtuRayHit, a = its albedo; the pixel is VALID iff
+ *                 H.flags & RTU_RAY_HIT. d = a > 0.01f ? a : 1.0f per channel and e_cur = c / d, as in "Denoising".
+ *   not valid     rgbz_out is the input bit for bit; history out E = 0, P = 0, N = {0, 0, 0, node -1}.
+ *   lookup        hist_prev == NULL: none. The fields cam_pos, origin, u, v, width, height of prev_cam and cur_cam equal bit for bit
+ *                 (the STATIC path): the one tap is the pixel itself with weight 1. Otherwise, with prev = prev_cam:
+ *                   D = H.p - prev.cam_pos;  nrm = prev.u x prev.v;  s = dot(prev.origin - prev.cam_pos, nrm) / dot(D, nrm)
+ *                   none unless s is finite and s > 0
+ *                   Q = (prev.cam_pos + D * s) - prev.origin
+ *                   fx = dot(Q, prev.u) / dot(prev.u, prev.u) - 0.5f;  fy = dot(Q, prev.v) / dot(prev.v, prev.v) - 0.5f
+ *                   none unless -1 <= fx < width and -1 <= fy < height (a NaN fails; tested before any conversion to an integer)
+ *                   x0 = floor(fx), wx = fx - x0, ux = 1 - wx; y0, wy, uy likewise
+ *                   four taps in the order (x0, y0) weight ux * uy, (x0 + 1, y0) wx * uy, (x0, y0 + 1) ux * wy, (x0 + 1, y0 + 1) wx * wy
+ *   a tap q       is ACCEPTED iff it lies inside the image, E_q.n > 0, the bits of its node equal those of H.node,
+ *                 dot(H.N, N_q) >= normal_min and |dot(H.N, P_q.xyz - H.p)| <= sigma_plane * H.t (a NaN fails either).
+ *                 For the accepted taps in their order: acc = acc + E_q.rgb * w;  nacc = nacc + E_q.n * w;  wsum = wsum + w.
+ *                 wsum > 0.01f: e_prev = acc / wsum, n_prev = nacc / wsum; otherwise n_prev = 0.
+ *   blend         c has a channel that is not finite (the sample is not accumulated): with n_prev == 0 rgbz_out is the input bit for
+ *                 bit and E = 0; otherwise e = e_prev, n = n_prev.
+ *                 else n_prev == 0: e = e_cur, n = 1.
+ *                 else n = min(n_prev + 1, max_history), A = 1 / n, e = e_prev + (e_cur - e_prev) * A.
+ *   output        rgb = e * d; z is the input z bit for bit. History out E = {e, n}, P = {H.p, H.t}, N = {H.N, H.node}.
+ * Only cam_pos, origin, u, v, width and height of the two cameras are read; both sizes must be the desc's. With hist_prev == NULL
+ * prev_cam may be NULL. hist_out must not overlap hist_prev (taps read anywhere in it); rgbz_out may be rgbz.
+ * RTU_ERR_ARG: a NULL pointer, width or height outside 1 .. 65536 or more than 2^26 pixels, max_history outside 1 .. 65535, sigma_plane
+ * not > 0, normal_min outside -1 .. 1, an unknown flag bit, a non-zero reserved word, a camera of another size, overlapping histories,
+ * a device pointer that is not 16-byte aligned. flags are read by sessions only.
+ *   rtu_temporal_accumulate          pure host code, no GPU and no context: the executable statement of the rules above.
+ *   rtu_temporal_accumulate_device   the same bits from device memory (k_temporal, one lane per pixel), asynchronous on hip_stream.
+ *                                    Allocates nothing, needs no scene, touches no state of the context. */
+#define RTU_TEMPORAL_DENOISE 1u     /* a session filters the accumulated image with rtu_denoise_device and its defaults */
+typedef struct RtuTemporalDesc {   /* 32 B */
+    int32_t  width, height;
+    int32_t  max_history;          /* 1 .. 65535: the blend weight never falls below 1 / max_history */
+    float    sigma_plane;          /* > 0: a tap further than sigma_plane * t from the pixel's tangent plane is another surface */
+    float    normal_min;           /* -1 .. 1: smallest Ncur . Ntap of an accepted tap */
+    uint32_t flags;                /* session only: RTU_TEMPORAL_DENOISE */
+    uint32_t reserved[2];          /* must be 0 */
+} RtuTemporalDesc;
+int  rtu_temporal_defaults(RtuTemporalDesc* out);   /* width, height 0; max_history 32, sigma_plane 0.05, normal_min 0.9, flags 0 */
+int  rtu_temporal_accumulate(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                             const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out);
+int  rtu_temporal_accumulate_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                    const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                    void* d_rgbz_out, void* hip_stream);
+/* A session that drives it. Frame k of the session, counted from 0 since rtu_temporal_begin or the last rtu_temporal_reset, of the
+ * recipe S / P frame `frame` (samples = S >= 1, gather_bounces 0 or 4, shard_count 1, collect_stats 0, the desc's size; its camera may
+ * differ from call to call):
+ *   1. the rays and keys of sample k mod S (rtu_camera_sample_rays_device),
+ *   2. shaded by rtu_shade_rays_sampled_device (gather_bounces 0) or rtu_shade_rays_paths_device (4) with eye = cam_pos and the frame's
+ *      max_bounce; the capacity of the frame records is checked and the batch shaded again until it is complete, as
+ *      rtu_progressive_advance does — THIS PART IS SYNCHRONOUS on hip_stream,
+ *   3. rtu_frame_features_device of the frame, and rtu_temporal_accumulate_device against the previous frame's camera and history
+ *      (frame 0: none) into d_rgbz,
+ *   4. with RTU_TEMPORAL_DENOISE: rtu_denoise_device with rtu_denoise_defaults on d_rgbz, in place. The history stays unfiltered.
+ * Steps 3 and 4 are asynchronous on hip_stream. The image is that of a ray batch: a pixel whose ray misses shows the environment, not
+ * the background image, and z = RTU_BIGFLOAT. All buffers — rays, keys, the current sample, guides, two histories (212 B per pixel) —
+ * belong to the session and are allocated by rtu_temporal_begin (which needs no scene); a frame allocates nothing once the context's
+ * frame records have grown to what the scene needs. ONE STREAM PER CONTEXT as for every launch. A session does not go stale: once the
+ * context got a new scene (rtu_upload_scene, rtu_update_scene, rtu_update_meshes) the next frame starts over with no history and k = 0.
+ * RTU_ERR_ARG: a desc outside its rules, a frame of another size, sharded, with counters or of recipe W, a NULL or misaligned d_rgbz;
+ * RTU_ERR_NO_SCENE before an upload. rtu_temporal_frame is the host form, synchronous on the context's stream.
+ * rtu_temporal_history_device writes width * height floats: the history length n of every pixel after the last frame (0 before the
+ * first). Ownership as for progressive sessions: rtu_destroy_context releases the device memory of open sessions, the handle stays
+ * valid for rtu_temporal_free alone. */
+typedef struct RtuTemporal RtuTemporal;
+RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, int* err_out);
+int  rtu_temporal_frame_device(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgbz, void* hip_stream);
+int  rtu_temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz);
+int  rtu_temporal_history_device(RtuTemporal* t, void* d_n, void* hip_stream);
+int  rtu_temporal_reset(RtuTemporal* t);
+void rtu_temporal_free(RtuTemporal* t);
 
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds

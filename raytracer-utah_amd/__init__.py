@@ -162,7 +162,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_debug_sensor_timing",
                "rtu_ray_features_device", "rtu_ray_features", "rtu_frame_features_device", "rtu_frame_features",
                "rtu_denoise_defaults", "rtu_denoise", "rtu_denoise_device",
-               "rtu_progressive_snapshot_denoised_device", "rtu_progressive_snapshot_denoised"]
+               "rtu_progressive_snapshot_denoised_device", "rtu_progressive_snapshot_denoised",
+               "rtu_camera_sample_rays_device", "rtu_temporal_defaults", "rtu_temporal_accumulate", "rtu_temporal_accumulate_device",
+               "rtu_temporal_begin", "rtu_temporal_frame_device", "rtu_temporal_frame", "rtu_temporal_history_device", "rtu_temporal_reset",
+               "rtu_temporal_free"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -362,6 +365,72 @@ _sig(hip, "rtu_denoise", _I, ctypes.POINTER(RtuDenoiseDesc), _P, _P, _P, _P)
 _sig(hip, "rtu_denoise_device", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P, _P, _P, _P, _P)
 _sig(hip, "rtu_progressive_snapshot_denoised_device", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P, _P)
 _sig(hip, "rtu_progressive_snapshot_denoised", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P)
+
+
+# temporal accumulation (include/rtu_render.h, "Temporal accumulation")
+RTU_TEMPORAL_DENOISE = 1
+
+
+class RtuTemporalDesc(ctypes.Structure):
+    """include/rtu_render.h RtuTemporalDesc (32 bytes): the size of the image, the three constants of the accumulator, the session's flags."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_history", ctypes.c_int32), ("sigma_plane", ctypes.c_float),
+                ("normal_min", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+_sig(hip, "rtu_camera_sample_rays_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _I, _P, _P, _P)
+_sig(hip, "rtu_temporal_defaults", _I, ctypes.POINTER(RtuTemporalDesc))
+_sig(hip, "rtu_temporal_accumulate", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+     _P, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_begin", _P, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(_I))
+_sig(hip, "rtu_temporal_frame_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P)
+_sig(hip, "rtu_temporal_frame", _I, _P, ctypes.POINTER(RtuFrameDesc), _P)
+_sig(hip, "rtu_temporal_history_device", _I, _P, _P, _P)
+_sig(hip, "rtu_temporal_reset", _I, _P)
+_sig(hip, "rtu_temporal_free", None, _P)
+
+
+def temporal_desc(width=0, height=0, denoise=False, **overrides):
+    """An RtuTemporalDesc: rtu_temporal_defaults (max_history 32, sigma_plane 0.05, normal_min 0.9), the size, RTU_TEMPORAL_DENOISE
+    for denoise=True (read by sessions only), then `overrides`."""
+    d = RtuTemporalDesc()
+    hip.rtu_temporal_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    d.flags = RTU_TEMPORAL_DENOISE if denoise else 0
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def temporal_accumulate(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev=None, desc=None):
+    """rtu_temporal_accumulate (pure host code, the specification of the accumulator): one new sample rgbz float32 [H, W, 4] with the
+    guides hits [H * W] of hit_dtype() and albedo float32 [H * W, 4] of cur_cam (an RtuFrameDesc) blended into hist_prev — float32
+    [3, H, W, 4], the planes E, P, N of the frame before, whose camera was prev_cam; None: no history — -> (accumulated rgbz
+    [H, W, 4], the new history [3, H, W, 4]). desc: an RtuTemporalDesc whose width and height are taken from rgbz (None: the defaults)."""
+    import numpy as np
+    rgbz = np.ascontiguousarray(rgbz, np.float32)
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
+    if hist_prev is not None:
+        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
+        if hist_prev.size != 12 * H * W:
+            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [3, H, W, 4]")
+    d = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    out, hist = np.empty_like(rgbz), np.empty((3, H, W, 4), np.float32)
+    rc = hip.rtu_temporal_accumulate(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
+                                     rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
+                                     hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate: a descriptor outside its rules (max_history 1..65535, sigma_plane > 0, normal_min "
+                           "-1..1, known flags, reserved words 0) or a camera of another size")
+    return out, hist
 
 
 def denoise_desc(width=0, height=0, **overrides):
@@ -968,6 +1037,68 @@ class Progressive:
             pass
 
 
+class Temporal:
+    """A temporal session (RtuTemporal*, include/rtu_render.h "Temporal accumulation"): one new sample per frame of a recipe S / P
+    frame whose camera may move, accumulated by reprojection. Made by Context.temporal(); errors raise RtuError with the context's message."""
+
+    def __init__(self, ctx, desc):
+        err = _I(0)
+        self._ctx = ctx
+        self.desc = desc
+        self._h = hip.rtu_temporal_begin(ctx._h, ctypes.byref(desc), ctypes.byref(err))
+        if not self._h:
+            ctx._check(err.value if err.value != RTU_OK else RTU_ERR_ARG)
+
+    def _check(self, rc):
+        if rc != RTU_OK:
+            msg = hip.rtu_last_error(self._ctx._h).decode() if self._ctx._h else "the context is closed"
+            raise RtuError(rc, msg)
+
+    def frame(self, frame):
+        """The next frame of the session through the camera of `frame`: rgbz float32 [H, W, 4] (synchronous)."""
+        import numpy as np
+        out = np.empty((self.desc.height, self.desc.width, 4), np.float32)
+        self._check(hip.rtu_temporal_frame(self._h, ctypes.byref(frame), out.ctypes.data))
+        return out
+
+    def frame_device(self, frame, d_rgbz, stream=None):
+        self._check(hip.rtu_temporal_frame_device(self._h, ctypes.byref(frame), d_rgbz, stream))
+
+    def history(self):
+        """The history length of every pixel after the last frame, float32 [H, W] (0 before the first)."""
+        import numpy as np
+        n = self.desc.width * self.desc.height
+        out = np.empty((self.desc.height, self.desc.width), np.float32)
+        d = hip.rtu_device_alloc(self._ctx._h, 4 * n)
+        if not d:
+            self._check(RTU_ERR_HIP)
+        try:
+            self.history_device(d, hip.rtu_context_stream(self._ctx._h))
+            self._check(hip.rtu_context_sync(self._ctx._h))
+            self._check(hip.rtu_copy_to_host(self._ctx._h, out.ctypes.data, d, 4 * n))
+        finally:
+            hip.rtu_device_free(self._ctx._h, d)
+        return out
+
+    def history_device(self, d_n, stream=None):
+        self._check(hip.rtu_temporal_history_device(self._h, d_n, stream))
+
+    def reset(self):
+        """Start over: the next frame is frame 0 and has no history."""
+        self._check(hip.rtu_temporal_reset(self._h))
+
+    def close(self):
+        if self._h:
+            hip.rtu_temporal_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU (RtuContext*)."""
 
@@ -1050,6 +1181,22 @@ class Context:
         """A progressive session of `frame` (recipe S / P; adaptive: RtuAdaptiveDesc or None for a fixed count): advance(n), status(),
         snapshot() -> (rgbz, counts), close()."""
         return Progressive(self, frame, adaptive)
+
+    def temporal(self, desc):
+        """A temporal session (desc: an RtuTemporalDesc with the size of its frames, see temporal_desc()): frame(frame) -> rgbz,
+        frame_device(), history(), reset(), close()."""
+        return Temporal(self, desc)
+
+    def camera_sample_rays_device(self, frame, sample, d_rays_ptr, d_keys_ptr, stream=None):
+        """rtu_camera_sample_rays_device: the rays and keys of camera_sample_rays(frame, sample) written to device memory by a kernel."""
+        self._check(hip.rtu_camera_sample_rays_device(self._h, ctypes.byref(frame), sample, d_rays_ptr, d_keys_ptr, stream))
+
+    def temporal_accumulate_device(self, desc, prev_cam, cur_cam, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr, d_rgbz_out_ptr,
+                                   stream=None):
+        """rtu_temporal_accumulate_device: temporal_accumulate() on device memory; d_hist_prev_ptr (and then prev_cam) may be None."""
+        self._check(hip.rtu_temporal_accumulate_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                                       ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                                       d_rgbz_out_ptr, stream))
 
     def set_cancel(self, flag):
         """rtu_set_cancel_flag: a ctypes.c_int the library polls between sample batches (None: none)."""

@@ -3,6 +3,7 @@
 // kernel launch. Compiled by hipcc with -ffp-contract=off so the few host-side
 // float computations (triangle normals, camera frame) round exactly like the
 // reference's CPU code.
+#include "rtu_camrays.h"
 #include "rtu_denoise.h"
 #include "rtu_devbuf.h"
 #include "rtu_device.h"
@@ -12,6 +13,7 @@
 #include "rtu_query.h"
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
+#include "rtu_temporal.h"
 
 #include <algorithm>
 #include <array>
@@ -26,6 +28,7 @@
 #include <vector>
 
 struct RtuProgressive;
+struct RtuTemporal;
 
 struct RtuContext {
     int         device = 0;
@@ -131,6 +134,7 @@ struct RtuContext {
     const volatile int* cancel = nullptr;    // rtu_set_cancel_flag: polled between the launch sequences of a sampled frame
     uint64_t scene_gen = 0;                  // bumped by every upload and update: a progressive session of an older scene is stale
     std::vector<RtuProgressive*> sessions;   // the open progressive sessions (rtu_destroy_context frees their device memory)
+    std::vector<RtuTemporal*> temporals;     // ... and the open temporal sessions (rtu_temporal_begin), likewise
     DevBuf<uint32_t> cover;                  // coverage masks of primary rays (KernelArgs::cover), grown on demand
     uint32_t  cover_faces = 0;
     DevBuf<uint32_t> occ;                    // tile occupancy of primary rays (KernelArgs::occ), grown on demand
@@ -1796,6 +1800,32 @@ static void progressive_release(RtuProgressive* p) {
     p->ctx = nullptr;
 }
 
+// A temporal session (rtu_temporal_*): one new sample per frame, accumulated over a moving camera. It owns every buffer a frame
+// writes; the frame-record arrays it shades through are the context's scratch within one call.
+struct RtuTemporal {
+    RtuContext*     ctx = nullptr;    // nullptr once the context is destroyed
+    RtuTemporalDesc desc{};
+    size_t          pixels = 0;
+    uint64_t        scene_gen = 0;    // the context's scene generation at the last frame: another one starts the history over
+    int             k = 0;            // frames since begin / reset
+    bool            has_hist = false; // hist[cur] and prev_cam are those of the previous frame
+    int             cur = 0;
+    RtuFrameDesc    prev_cam{};
+    DevBuf<float4>   rays, img, hits, albedo, hist[2];
+    DevBuf<uint32_t> keys;
+};
+
+static void temporal_release(RtuTemporal* t) {
+    t->rays.reset();
+    t->img.reset();
+    t->hits.reset();
+    t->albedo.reset();
+    for (DevBuf<float4>& h : t->hist) h.reset();
+    t->keys.reset();
+    t->has_hist = false;
+    t->ctx = nullptr;
+}
+
 extern "C" {
 
 int rtu_device_info(int device_id, RtuDeviceInfo* out) {
@@ -1869,6 +1899,7 @@ void rtu_destroy_context(RtuContext* ctx) {
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     ll_builder_destroy(ctx->llb);
     for (RtuProgressive* p : ctx->sessions) progressive_release(p);  // the handles stay valid for rtu_progressive_free
+    for (RtuTemporal* t : ctx->temporals) temporal_release(t);       // ... and for rtu_temporal_free
     // the buffers go with the context (DevBuf); its events and streams after them
     std::vector<hipEvent_t> events = {ctx->aux_ev0, ctx->aux_ev1, ctx->ev0, ctx->ev1};
     events.insert(events.end(), std::begin(ctx->cam_ev), std::end(ctx->cam_ev));
@@ -3670,7 +3701,6 @@ uint32_t h_mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
-uint32_t h_rand31(uint32_t key, uint32_t purpose) { return h_mix32(key ^ h_mix32(purpose * 0x9e3779b9U + 0x85ebca6bU)) >> 1; }
 // portable_sincos of rtu_intersect.h restated for the host: binary64, IEEE operations only (this file is compiled with -ffp-contract=off),
 // the same sequence, so the same floats
 void h_portable_sincos(float t, float& sn, float& cs) {
@@ -3688,6 +3718,28 @@ void h_portable_sincos(float t, float& sn, float& cs) {
     const double so = (k & 1) ? c : s, co = (k & 1) ? s : c;
     sn = (float)((k & 2) ? -so : so);
     cs = (float)((((k + 1) & 2) != 0) ? -co : co);
+}
+struct HostSinCos {
+    void operator()(float t, float& sn, float& cs) const { h_portable_sincos(t, sn, cs); }
+};
+
+// what camera_sample_ray (rtu_camrays.h) takes of sample `sample` of `frame`: the camera, and the pixel offsets by launch()'s expressions
+CamSample cam_sample(const RtuFrameDesc* frame, int sample) {
+    CamSample c;
+    memset(&c, 0, sizeof c);
+    for (int k = 0; k < 3; k++) {
+        c.cam_pos[k] = frame->cam_pos[k]; c.origin[k] = frame->origin[k]; c.u[k] = frame->u[k]; c.v[k] = frame->v[k];
+        c.lens_up[k] = frame->lens_up[k]; c.lens_right[k] = frame->lens_right[k];
+    }
+    c.dof = frame->dof;
+    const float pixelIncrement = (float)(1.0 / frame->samples);  // RenderFunctions.cpp:68 (launch())
+    const float currentOffset = (float)sample * pixelIncrement;  // :80
+    c.ox = currentOffset + halton(sample, 4);                    // :84, :85, :96
+    c.oy = currentOffset + halton(sample, 5);
+    c.width = frame->width;
+    c.height = frame->height;
+    c.sample = (uint32_t)sample;
+    return c;
 }
 }  // namespace
 
@@ -3765,22 +3817,12 @@ int rtu_camera_sample_rays(const RtuFrameDesc* frame, int sample, int row0, int 
         return RTU_ERR_ARG;
     if (frame->samples < 1 || sample < 0 || sample >= frame->samples) return RTU_ERR_ARG;
     if (nrows && (!rays_out || !keys_out)) return RTU_ERR_ARG;
-    const f3 cam_pos = ld3(frame->cam_pos), cam_origin = ld3(frame->origin), cam_u = ld3(frame->u), cam_v = ld3(frame->v);
-    const float pixelIncrement = (float)(1.0 / frame->samples);  // RenderFunctions.cpp:68 (launch())
-    const float currentOffset = (float)sample * pixelIncrement;  // :80
-    const float ox = currentOffset + halton(sample, 4), oy = currentOffset + halton(sample, 5);  // :84, :85, :96
+    const CamSample c = cam_sample(frame, sample);
     for (int y = row0; y < row0 + nrows; y++)
         for (int x = 0; x < frame->width; x++) {
-            const uint32_t key = rtu_sample_key((uint32_t)x + (uint32_t)frame->width * (uint32_t)y, (uint32_t)sample);
-            const float sampleX = (float)h_rand31(key, 0u) / 2147483648.0f;                                              // :88 (RTU_RAND_MAX_F)
-            const float sampleTheta = (float)h_rand31(key, 1u) / ((float)(2147483647 / (2 * 3.14159265358979323846)));  // :89 (RTU_THETA_DIV)
-            float sn, cs;
-            h_portable_sincos(sampleTheta, sn, cs);
-            const float rad = sqrtf((sampleX * frame->dof) * frame->dof);
-            const float camOffsetX = rad * cs, camOffsetY = rad * sn;                                                    // :90-91
-            const f3 org = (cam_pos + ld3(frame->lens_up) * camOffsetY) + ld3(frame->lens_right) * camOffsetX;           // :93
-            const f3 cp = (cam_origin + cam_u * ((float)x + ox)) + cam_v * ((float)y + oy);
-            const f3 dir = norm3(cp - org);
+            f3 org, dir;
+            uint32_t key;
+            camera_sample_ray(c, x, y, HostSinCos(), org, dir, key);
             const size_t i = (size_t)(y - row0) * (size_t)frame->width + (size_t)x;
             RtuRay& r = rays_out[i];
             r.org[0] = org.x; r.org[1] = org.y; r.org[2] = org.z;
@@ -3789,6 +3831,20 @@ int rtu_camera_sample_rays(const RtuFrameDesc* frame, int sample, int row0, int 
             r.reserved = 0;
             keys_out[i] = key;
         }
+    return RTU_OK;
+}
+
+// the same on the device (rtu_camrays.hip): camera_sample_ray per lane, so the same bits
+int rtu_camera_sample_rays_device(RtuContext* ctx, const RtuFrameDesc* frame, int sample, void* d_rays, void* d_keys, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!frame || frame->width <= 0 || frame->height <= 0) return fail(ctx, RTU_ERR_ARG, "frame is NULL or empty");
+    if (frame->samples < 1 || sample < 0 || sample >= frame->samples) return fail(ctx, RTU_ERR_ARG, "not a recipe S frame, or sample outside [0, samples)");
+    if ((size_t)frame->width * (size_t)frame->height > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "more than 2^26 pixels in one call");
+    if (!d_rays || !d_keys) return fail(ctx, RTU_ERR_ARG, "ray / key pointer is NULL");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_keys & 3u)) return fail(ctx, RTU_ERR_ARG, "the ray buffer must be 16-byte, the key buffer 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_camera_sample_rays(cam_sample(frame, sample), (float4*)d_rays, (uint32_t*)d_keys, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "camera ray launch: %s", hipGetErrorString(e));
     return RTU_OK;
 }
 
@@ -3812,12 +3868,166 @@ int rtu_camera_rays(const RtuFrameDesc* frame, int row0, int nrows, RtuRay* rays
     return RTU_OK;
 }
 
+// ---- temporal accumulation (rtu_temporal.h, rtu_temporal.hip): the accumulator on device memory, and the session that drives it ----
+static_assert(sizeof(RtuTemporalDesc) == 32, "RtuTemporalDesc is 32 bytes");
+
+int rtu_temporal_accumulate_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                   const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                   void* d_rgbz_out, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK)
+        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
+    if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "temporal: a camera is NULL");
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return fail(ctx, RTU_ERR_ARG, "temporal: the cameras must have the desc's width and height");
+    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
+    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out))
+        return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
+    if (d_hist_prev) {
+        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)48 * (uintptr_t)desc->width * (uintptr_t)desc->height;
+        if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
+    }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_temporal(tp_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr), (const float4*)d_rgbz, (const float4*)d_hits,
+                                                         (const float4*)d_albedo, (const float4*)d_hist_prev, (float4*)d_hist_out, (float4*)d_rgbz_out,
+                                                         (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, int* err_out) {
+    auto refuse = [&](int rc) -> RtuTemporal* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (rtu_temporal_check_desc(desc) != RTU_OK)
+        return refuse(fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0"));
+    if (hipSetDevice(ctx->device) != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "hipSetDevice failed"));
+    std::unique_ptr<RtuTemporal> t(new RtuTemporal);
+    t->desc = *desc;
+    t->pixels = (size_t)desc->width * (size_t)desc->height;
+    t->scene_gen = ctx->scene_gen;
+    const size_t n = t->pixels;
+    hipError_t e = t->rays.grow(2 * n);
+    if (e == hipSuccess) e = t->keys.grow(n);
+    if (e == hipSuccess) e = t->img.grow(n);
+    if (e == hipSuccess) e = t->hits.grow(3 * n);
+    if (e == hipSuccess) e = t->albedo.grow(n);
+    for (DevBuf<float4>& h : t->hist)
+        if (e == hipSuccess) e = h.grow(3 * n);
+    if (e == hipSuccess && (desc->flags & RTU_TEMPORAL_DENOISE)) e = ctx->dn_planes.grow(4 * n);  // the filter's planes are the context's
+    if (e != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e)));
+    t->ctx = ctx;
+    ctx->temporals.push_back(t.get());
+    if (err_out) *err_out = RTU_OK;
+    return t.release();
+}
+
+int rtu_temporal_frame_device(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgbz, void* hip_stream) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!frame) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
+    if (frame->width != t->desc.width || frame->height != t->desc.height) return fail(ctx, RTU_ERR_ARG, "the frame has not the session's width and height");
+    if (frame->shard_count != 1 || frame->shard_rank != 0) return fail(ctx, RTU_ERR_ARG, "a temporal session renders the whole image: shard_count must be 1");
+    if (frame->samples < 1) return fail(ctx, RTU_ERR_ARG, "a temporal frame is a recipe S / P frame (samples >= 1)");
+    if (frame->gather_bounces != 0 && frame->gather_bounces != RTU_GI_BOUNCES) return fail(ctx, RTU_ERR_ARG, "gather_bounces is 0 or %d", RTU_GI_BOUNCES);
+    if (frame->collect_stats != 0) return fail(ctx, RTU_ERR_ARG, "a temporal frame has no counters (collect_stats == 0)");
+    if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
+    if (misaligned(d_rgbz)) return fail(ctx, RTU_ERR_ARG, "d_rgbz must be 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const bool paths = frame->gather_bounces != 0;
+    const size_t n = t->pixels;
+    if (t->scene_gen != ctx->scene_gen) {  // moved geometry or lights: what was accumulated shows another scene
+        t->scene_gen = ctx->scene_gen;
+        t->has_hist = false;
+        t->k = 0;
+    }
+    int rc = rtu_camera_sample_rays_device(ctx, frame, t->k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
+    if (rc != RTU_OK) return rc;
+    RtuShadeDesc sd;
+    rtu_shade_defaults(&sd);
+    memcpy(sd.eye, frame->cam_pos, sizeof sd.eye);
+    sd.max_bounce = frame->max_bounce;
+    RtuFrameDesc f;
+    if ((rc = shade_args(ctx, t->rays.get(), t->img.get(), n, &sd, true, &f, true, t->keys.get(), paths)) != RTU_OK) return rc;
+    // as shade_host: the chain of recipe P is traced once, the shading is what is repeated when the frame records ran out
+    if (paths && (rc = paths_chain(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n)) != RTU_OK) return rc;
+    for (int attempt = 0;; attempt++) {
+        rc = paths ? paths_shade(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n)
+                   : launch(ctx, &f, t->img.get(), stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, t->rays.get(), (uint32_t)n, t->keys.get());
+        if (rc != RTU_OK) return rc;
+        RTU_HIP(ctx, hipStreamSynchronize(stream));
+        bool overflow = false;
+        if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
+        if (!overflow) break;
+        if (attempt >= (paths ? 8 : 2) * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+    }
+    if ((rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
+    RtuTemporalDesc td = t->desc;
+    td.flags = 0;
+    rc = rtu_temporal_accumulate_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                        t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
+    if (rc != RTU_OK) return rc;
+    t->cur ^= 1;
+    t->has_hist = true;
+    t->prev_cam = *frame;
+    t->k++;
+    if (t->desc.flags & RTU_TEMPORAL_DENOISE) {
+        RtuDenoiseDesc dd;
+        rtu_denoise_defaults(&dd);
+        dd.width = t->desc.width;
+        dd.height = t->desc.height;
+        return rtu_denoise_device(ctx, &dd, d_rgbz, t->hits.get(), t->albedo.get(), d_rgbz, hip_stream);  // in place; the history stays unfiltered
+    }
+    return RTU_OK;
+}
+
+int rtu_temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->fb.grow(t->pixels));
+    const int rc = rtu_temporal_frame_device(t, frame, ctx->fb.get(), ctx->stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), t->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RTU_OK;
+}
+
+int rtu_temporal_history_device(RtuTemporal* t, void* d_n, void* hip_stream) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!d_n) return fail(ctx, RTU_ERR_ARG, "d_n is NULL");
+    if ((uintptr_t)d_n & 3u) return fail(ctx, RTU_ERR_ARG, "d_n must be 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const bool live = t->has_hist && t->scene_gen == ctx->scene_gen;
+    const hipError_t e = (hipError_t)rtu_launch_temporal_history(live ? t->hist[t->cur].get() : nullptr, (float*)d_n, t->pixels, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal history launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_reset(RtuTemporal* t) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    t->has_hist = false;
+    t->k = 0;
+    return RTU_OK;
+}
+
+void rtu_temporal_free(RtuTemporal* t) {
+    if (!t) return;
+    if (RtuContext* ctx = t->ctx) {
+        (void)hipSetDevice(ctx->device);
+        ctx->temporals.erase(std::remove(ctx->temporals.begin(), ctx->temporals.end(), t), ctx->temporals.end());
+    }
+    delete t;
+}
+
 // ---- sensors (rtu_sensor.h, rtu_sensor.hip): the rays of a panoramic, fisheye or orthographic sensor, and its image --------------
 namespace {
-struct HostSinCos {
-    void operator()(float t, float& sn, float& cs) const { h_portable_sincos(t, sn, cs); }
-};
-
 const size_t kSensorPixels = (size_t)1 << 25;  // pixels of a sensor, and rays of one batch of its samples, at most
 
 bool fin3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }

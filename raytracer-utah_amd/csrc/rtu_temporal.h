@@ -1,0 +1,147 @@
+// rtu_temporal.h — the arithmetic of the temporal accumulator (rtu_temporal_accumulate / rtu_temporal_accumulate_device,
+// include/rtu_render.h "Temporal accumulation"), host + device, and the launch interface of its kernels (rtu_temporal.hip), called by
+// rtu_capi.hip.
+//
+// A pixel's first-hit point is projected into the previous camera, the history is fetched there with four bilinear taps, each tested
+// for being the same surface, and the new sample is blended in. No transcendental function: the translation units that include this
+// header are compiled with -ffp-contract=off and IEEE divides, every operation below rounds once, so the host form and the kernel give
+// the same bits.
+//
+// A HISTORY is three planes of one float4 per pixel:  E = {e.rgb, n}   P = {p.xyz, t}   N = {N.xyz, node as bits}
+#ifndef RTU_TEMPORAL_H_INCLUDED
+#define RTU_TEMPORAL_H_INCLUDED
+
+#include "rtu_denoise.h"
+
+#define TP_LOOKUP_NONE      0  // no previous history
+#define TP_LOOKUP_STATIC    1  // the cameras are equal bit for bit: the pixel itself with weight 1
+#define TP_LOOKUP_REPROJECT 2
+
+// what a pixel needs of the desc and of the PREVIOUS camera; made once per call by tp_setup on the host, for both forms
+struct TpParams {
+    int32_t width, height, lookup;
+    float   max_history, sigma_plane, normal_min;
+    float   pos[3], origin[3], u[3], v[3];
+    float   nrm[3];      // u x v
+    float   num;         // dot(origin - pos, nrm)
+    float   uu, vv;      // dot(u, u), dot(v, v)
+};
+
+inline bool tp_same_camera(const RtuFrameDesc& a, const RtuFrameDesc& b) {
+    union { float f; uint32_t u; } x, y;
+    if (a.width != b.width || a.height != b.height) return false;
+    for (int k = 0; k < 3; k++) {
+        const float fa[4] = {a.cam_pos[k], a.origin[k], a.u[k], a.v[k]}, fb[4] = {b.cam_pos[k], b.origin[k], b.u[k], b.v[k]};
+        for (int j = 0; j < 4; j++) {
+            x.f = fa[j]; y.f = fb[j];
+            if (x.u != y.u) return false;
+        }
+    }
+    return true;
+}
+
+inline TpParams tp_setup(const RtuTemporalDesc& d, const RtuFrameDesc& prev, const RtuFrameDesc& cur, bool has_prev) {
+    TpParams p{};
+    p.width = d.width;
+    p.height = d.height;
+    p.lookup = !has_prev ? TP_LOOKUP_NONE : (tp_same_camera(prev, cur) ? TP_LOOKUP_STATIC : TP_LOOKUP_REPROJECT);
+    p.max_history = (float)d.max_history;
+    p.sigma_plane = d.sigma_plane;
+    p.normal_min = d.normal_min;
+    const f3 pos = ld3(prev.cam_pos), origin = ld3(prev.origin), u = ld3(prev.u), v = ld3(prev.v);
+    const f3 nrm = cross3(u, v);
+    for (int k = 0; k < 3; k++) { p.pos[k] = prev.cam_pos[k]; p.origin[k] = prev.origin[k]; p.u[k] = prev.u[k]; p.v[k] = prev.v[k]; }
+    p.nrm[0] = nrm.x; p.nrm[1] = nrm.y; p.nrm[2] = nrm.z;
+    p.num = dot3(origin - pos, nrm);
+    p.uu = dot3(u, u);
+    p.vv = dot3(v, v);
+    return p;
+}
+
+RTU_HD bool tp_finite(float x) { return (x - x) == 0.0f; }  // false for an infinity and for a NaN
+
+// One tap of pixel p's lookup at pixel (qx, qy) of the previous history with weight w: where it is ACCEPTED, E_q.rgb w is added to acc,
+// E_q.n w to nacc and w to wsum.
+RTU_HD void tp_tap(const TpParams& P, const float4* hE, const float4* hP, const float4* hN, int qx, int qy, float w, const f3& Np, const f3& Pp,
+                   uint32_t node, float plane_max, f3& acc, float& nacc, float& wsum) {
+    if (qx < 0 || qy < 0 || qx >= P.width || qy >= P.height) return;
+    const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
+    const float4 Eq = hE[q], Pq = hP[q], Nq = hN[q];
+    union { float f; uint32_t u; } nb;
+    nb.f = Nq.w;
+    if (!(Eq.w > 0.0f) || nb.u != node) return;
+    if (!(dot3(Np, mk3(Nq.x, Nq.y, Nq.z)) >= P.normal_min)) return;
+    if (!(fabsf(dot3(Np, mk3(Pq.x, Pq.y, Pq.z) - Pp)) <= plane_max)) return;
+    acc = acc + mk3(Eq.x, Eq.y, Eq.z) * w;
+    nacc = nacc + Eq.w * w;
+    wsum = wsum + w;
+}
+
+// Pixel (x, y): hE / hP / hN the planes of the previous history (not read with TP_LOOKUP_NONE), hit the three float4 of its RtuRayHit.
+// out: its pixel of the accumulated image; oE, oP, oN: its pixel of the new history.
+RTU_HD void tp_pixel(const TpParams& P, const float4* hE, const float4* hP, const float4* hN, int x, int y, const float4& rgbz, const float4* hit,
+                     const float4& albedo, float4& out, float4& oE, float4& oP, float4& oN) {
+    union { float f; uint32_t u; } flags, node;
+    flags.f = hit[0].z;
+    node.f = hit[0].y;
+    const bool valid = (flags.u & RTU_RAY_HIT) != 0;
+    const f3 d = dn_demod(albedo);
+    const f3 e_cur = mk3(rgbz.x / d.x, rgbz.y / d.y, rgbz.z / d.z);
+    const f3 Pp = mk3(hit[1].x, hit[1].y, hit[1].z), Np = mk3(hit[2].x, hit[2].y, hit[2].z);
+    const float plane_max = P.sigma_plane * hit[0].x;
+
+    f3 acc = mk3(0.0f, 0.0f, 0.0f), e_prev = mk3(0.0f, 0.0f, 0.0f);
+    float nacc = 0.0f, wsum = 0.0f, n_prev = 0.0f;
+    if (valid && P.lookup == TP_LOOKUP_STATIC) {
+        tp_tap(P, hE, hP, hN, x, y, 1.0f, Np, Pp, node.u, plane_max, acc, nacc, wsum);
+    } else if (valid && P.lookup == TP_LOOKUP_REPROJECT) {
+        const f3 pos = ld3(P.pos), nrm = ld3(P.nrm);
+        const f3 D = Pp - pos;
+        const float s = P.num / dot3(D, nrm);
+        if (tp_finite(s) && s > 0.0f) {
+            const f3 Q = (pos + D * s) - ld3(P.origin);
+            const float fx = dot3(Q, ld3(P.u)) / P.uu - 0.5f, fy = dot3(Q, ld3(P.v)) / P.vv - 0.5f;
+            if (fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {  // (a NaN fails; tested before any conversion)
+                const float flx = floorf(fx), fly = floorf(fy);
+                const int x0 = (int)flx, y0 = (int)fly;
+                const float wx = fx - flx, wy = fy - fly;
+                const float ux = 1.0f - wx, uy = 1.0f - wy;
+                tp_tap(P, hE, hP, hN, x0, y0, ux * uy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
+                tp_tap(P, hE, hP, hN, x0 + 1, y0, wx * uy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
+                tp_tap(P, hE, hP, hN, x0, y0 + 1, ux * wy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
+                tp_tap(P, hE, hP, hN, x0 + 1, y0 + 1, wx * wy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
+            }
+        }
+    }
+    if (wsum > 0.01f) {
+        e_prev = mk3(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+        n_prev = nacc / wsum;
+    }
+
+    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);  // else the sample is not accumulated
+    const bool fresh = n_prev == 0.0f;
+    const float n_blend = smin(n_prev + 1.0f, P.max_history);
+    const float a = 1.0f / n_blend;
+    const f3 e_blend = e_prev + (e_cur - e_prev) * a;
+    const f3 e = !finite ? e_prev : (fresh ? e_cur : e_blend);
+    const float n = !finite ? n_prev : (fresh ? 1.0f : n_blend);
+    const bool keep = valid && (finite || !fresh);  // the pixel has an accumulated colour; else its input passes through
+    if (!valid) node.u = 0xFFFFFFFFu;               // node -1
+    out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, rgbz.w) : rgbz;
+    oE = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    oP = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    oN = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
+}
+
+// RTU_OK or RTU_ERR_ARG: the rules of RtuTemporalDesc (include/rtu_render.h)
+int rtu_temporal_check_desc(const RtuTemporalDesc* d);
+
+// The accumulator on the device: rgbz, albedo, rgbz_out [width * height] float4, hits [width * height] RtuRayHit, hist_prev (nullptr
+// with TP_LOOKUP_NONE) and hist_out three planes of width * height float4 each. rgbz_out == rgbz is allowed; hist_out does not overlap
+// hist_prev. Pointers 16-byte aligned and desc checked by the caller. Returns a hipError_t as int. Asynchronous on `stream`.
+int rtu_launch_temporal(const TpParams& p, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+                        float4* rgbz_out, hipStream_t stream);
+// n_out[i] = the history length of pixel i (E.w of `hist`), or 0 everywhere with hist == nullptr
+int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream);
+
+#endif

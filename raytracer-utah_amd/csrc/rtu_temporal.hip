@@ -1,0 +1,117 @@
+// rtu_temporal.hip — the temporal accumulator of include/rtu_render.h ("Temporal accumulation"): its host form
+// rtu_temporal_accumulate, which is the executable statement of the rules, and the kernel of rtu_temporal_accumulate_device. Both call
+// tp_pixel of rtu_temporal.h, pixel by pixel.
+//
+//   k_temporal          one lane per pixel, 32 x 8 pixel workgroups as k_dn_pass (a wavefront is two rows of 32). A lane reads its
+//                       pixel's {rgbz, RtuRayHit, albedo} (80 B), up to four taps of the previous history — three 16-byte loads each,
+//                       neighbouring lanes' taps are neighbouring pixels while the surface is smooth, so the lines are shared through
+//                       the vector L1 —, and writes its pixel of the image and of the three planes of the new history (64 B). No
+//                       LDS, no atomics. The lookup mode is wave-uniform (a kernel argument).
+//   k_temporal_history  one lane per pixel: the history length out of the E plane.
+// Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
+// anywhere in hist_prev: hist_out must not overlap it.
+#include "rtu_temporal.h"
+
+#include <vector>
+
+namespace {
+
+__global__ void __launch_bounds__(256) k_temporal(TpParams P, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
+                                                  const float4* __restrict__ hist_prev, float4* __restrict__ hist_out, float4* rgbz_out) {
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= P.width || y >= P.height) return;
+    const size_t n = (size_t)P.width * (size_t)P.height;
+    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
+    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
+    float4 out, oE, oP, oN;
+    const float4* hP = hist_prev ? hist_prev + n : nullptr;
+    const float4* hN = hist_prev ? hist_prev + 2 * n : nullptr;
+    tp_pixel(P, hist_prev, hP, hN, x, y, rgbz[p], hit, albedo[p], out, oE, oP, oN);
+    rgbz_out[p] = out;
+    hist_out[p] = oE;
+    hist_out[n + p] = oP;
+    hist_out[2 * n + p] = oN;
+}
+
+__global__ void __launch_bounds__(256) k_temporal_history(const float4* __restrict__ hist, float* __restrict__ n_out, unsigned long long pixels) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    if (i >= pixels) return;
+    n_out[i] = hist ? hist[i].w : 0.0f;
+}
+
+}  // namespace
+
+int rtu_launch_temporal(const TpParams& p, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+                        float4* rgbz_out, hipStream_t stream) {
+    const dim3 grid((uint32_t)((p.width + 31) / 32), (uint32_t)((p.height + 7) / 8));
+    hipLaunchKernelGGL(k_temporal, grid, dim3(256), 0, stream, p, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out);
+    return (int)hipGetLastError();
+}
+
+int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream) {
+    if (pixels == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_temporal_history, dim3((uint32_t)((pixels + 255) / 256)), dim3(256), 0, stream, hist, n_out, (unsigned long long)pixels);
+    return (int)hipGetLastError();
+}
+
+int rtu_temporal_check_desc(const RtuTemporalDesc* d) {
+    if (!d || d->width < 1 || d->height < 1 || d->width > 65536 || d->height > 65536) return RTU_ERR_ARG;
+    if ((unsigned long long)d->width * (unsigned long long)d->height > (1ull << 26)) return RTU_ERR_ARG;
+    if (d->max_history < 1 || d->max_history > 65535) return RTU_ERR_ARG;
+    if (!(d->sigma_plane > 0.0f) || !(d->normal_min >= -1.0f && d->normal_min <= 1.0f)) return RTU_ERR_ARG;  // a NaN is refused too
+    if (d->flags & ~RTU_TEMPORAL_DENOISE) return RTU_ERR_ARG;
+    if (d->reserved[0] || d->reserved[1]) return RTU_ERR_ARG;
+    return RTU_OK;
+}
+
+extern "C" {
+
+int rtu_temporal_defaults(RtuTemporalDesc* out) {
+    if (!out) return RTU_ERR_ARG;
+    *out = RtuTemporalDesc{};
+    out->max_history = 32;
+    out->sigma_plane = 0.05f;
+    out->normal_min = 0.9f;
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                            const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out) {
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
+    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return RTU_ERR_ARG;
+    const int W = desc->width, H = desc->height;
+    const size_t n = (size_t)W * (size_t)H;
+    if (h_hist_prev) {  // taps read anywhere in the previous history
+        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 48 * n;
+        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
+    }
+    const TpParams P = tp_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr);
+    std::vector<float4> prev;  // (the planes as float4: the caller's floats need not be 16-byte aligned)
+    if (h_hist_prev) {
+        prev.resize(3 * n);
+        for (size_t i = 0; i < 3 * n; i++) prev[i] = make_float4(h_hist_prev[4 * i], h_hist_prev[4 * i + 1], h_hist_prev[4 * i + 2], h_hist_prev[4 * i + 3]);
+    }
+    const float4* hE = h_hist_prev ? prev.data() : nullptr;
+    const float4* hP = h_hist_prev ? prev.data() + n : nullptr;
+    const float4* hN = h_hist_prev ? prev.data() + 2 * n : nullptr;
+    auto f4 = [](const float* p, size_t i) { return make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); };
+    auto st = [](float* p, size_t i, const float4& v) { p[4 * i] = v.x; p[4 * i + 1] = v.y; p[4 * i + 2] = v.z; p[4 * i + 3] = v.w; };
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t p = (size_t)y * (size_t)W + (size_t)x;
+            const float* h = reinterpret_cast<const float*>(h_hits + p);
+            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
+            float4 out, oE, oP, oN;
+            tp_pixel(P, hE, hP, hN, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, oE, oP, oN);
+            st(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
+            st(h_hist_out, p, oE);
+            st(h_hist_out, n + p, oP);
+            st(h_hist_out, 2 * n + p, oN);
+        }
+    return RTU_OK;
+}
+
+}  // extern "C"
