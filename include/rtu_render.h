@@ -747,6 +747,77 @@ int  rtu_temporal_history_device(RtuTemporal* t, void* d_n, void* hip_stream);
 int  rtu_temporal_reset(RtuTemporal* t);
 void rtu_temporal_free(RtuTemporal* t);
 
+/* ---- Temporal accumulation across scene updates: moving nodes (rtu_temporal.h tp_pixel_motion, rtu_temporal.hip k_temporal_motion) ----
+ * rtu_temporal_frame starts over once the scene changed. The entries below keep the history instead: a pixel's hit point is first
+ * carried to where that point of its NODE was in the previous frame's scene, by an affine map per node, and the lookup of "Temporal
+ * accumulation" is made from there.
+ *
+ * THE TABLE  rtu_scene_motion (pure host code, no GPU and no context) makes one RtuNodeMotion per node of `cur` (the pre-order index
+ *   of RtuSceneDesc.nodes, which is RtuRayHit.node). With W(x) = FromNodeCoords from the node up to the root (tm x + pos per level)
+ *   and W^-1(p) = ToNodeCoords from the root down (itm (p - pos) per level, the scene's own itm):
+ *     m = W_prev o W_cur^-1 as three rows {a, b, c, d}: p_prev.k = dot(row_k.abc, p) + row_k.d
+ *     g = the transpose of the linear part of W_cur o W_prev^-1 (the inverse-transpose of m's linear part): N_prev = g N, normalised
+ *   both composed in binary64 and rounded to binary32 once at the end. A node whose whole chain (tm and pos of itself and of every
+ *   ancestor) is bit-identical in both scenes gets RTU_MOTION_STATIC and the identity in m and g; a node whose mesh_id is one of
+ *   reset_mesh_ids — the list given to rtu_update_meshes: a deformed surface has no rigid map — gets RTU_MOTION_RESET (besides).
+ *   RTU_ERR_SCENE_SHAPE: `cur` has not the shape of `prev` (rtu_scene_shape_diff; n_bvh_nodes of a mesh in reset_mesh_ids may
+ *   differ, as rtu_update_meshes allows). RTU_ERR_ARG: a NULL pointer (reset_mesh_ids may be
+ *   NULL with n_reset == 0), n_reset < 0, a mesh id >= n_meshes.
+ *
+ * THE RULE  rtu_temporal_accumulate_motion is rtu_temporal_accumulate with, for a VALID pixel, k = H.node and T = motion[k]:
+ *   no lookup     k < 0, k >= n_nodes, or T.flags & RTU_MOTION_RESET.
+ *   T is STATIC   Pm = H.p, Nm = H.N bit for bit. If hist_prev is given and the two cameras are equal bit for bit, the one tap is the
+ *                 pixel itself with weight 1 (the STATIC path of "Temporal accumulation").
+ *   otherwise     Pm.k = dot(row_k.abc, H.p) + row_k.d;  q = {dot(g_0, H.N), dot(g_1, H.N), dot(g_2, H.N)};  l = dot(q, q);
+ *                 Nm = q / sqrtf(l) per component (correctly rounded); no lookup if a component of Pm or of Nm is not finite.
+ *   Every pixel that does not take the one-tap path is reprojected into the previous camera by the expressions of "Temporal
+ *   accumulation" with Pm in place of H.p — also when the cameras are equal. A tap is ACCEPTED iff it lies inside the image,
+ *   E_q.n > 0, the bits of its node equal those of H.node, dot(Nm, N_q) >= normal_min and |dot(Nm, P_q.xyz - Pm)| <= sigma_plane * H.t.
+ *   history_cap   0: none. 1 .. 65535: where n_prev > 0, n_prev = min(n_prev, (float)history_cap) before the blend, for EVERY pixel —
+ *                 a moving object changes shadows and bounce light on surfaces that did not move; the caller's control over lag.
+ *   The history written is that of "Temporal accumulation": the current H.p, H.t, H.N, H.node.
+ * So an all-STATIC table with history_cap 0 gives the bits of rtu_temporal_accumulate. RTU_ERR_ARG: what rtu_temporal_accumulate
+ * refuses; a NULL table; history_cap outside 0 .. 65535; in the host form a table entry with a non-zero reserved word or an unknown
+ * flag bit. THE DEVICE FORM TRUSTS THE TABLE (it is device memory, 16-byte aligned, n_nodes entries, never written): it allocates
+ * nothing, needs no scene and is asynchronous on hip_stream.
+ *
+ * MOTION VECTORS  rtu_motion_vectors / _device write one float4 {fx, fy, 1, 0} per pixel: the continuous coordinates in the previous
+ *   image the four taps are taken around (an integer is a pixel centre), for a VALID pixel whose node is inside the table and not
+ *   RESET, with Pm and s finite and s > 0; {0, 0, 0, 0} otherwise. It always projects: no one-tap path, no bounds test. Only
+ *   width and height of `desc` are read (the other fields must still be valid). Host and device form give the same bits.
+ *
+ * THE SESSION  rtu_temporal_frame_moved[_device] is rtu_temporal_frame[_device] except that (a) another scene generation does not
+ *   clear the history nor the sample counter — the session adopts it — and (b) step 3 uses the motion form with h_motion, a HOST
+ *   table of n_nodes entries (== the uploaded scene's node count, else RTU_ERR_ARG; checked as the host form checks it) that
+ *   describes the scene of the PREVIOUS FRAME of this session against the scene now: after two updates between frames, call
+ *   rtu_scene_motion on the two scenes that were rendered. The table is copied through staging memory of the session into a grow-only
+ *   device buffer of the session before the call returns; after the first frame that needs them a frame allocates nothing. On frame 0
+ *   the table is not used. Plain and moved frames may be mixed; a plain frame after an update starts over as before. */
+#define RTU_MOTION_STATIC 1u   /* the node's whole chain (tm, pos of itself and every ancestor) is bit-identical in both scenes */
+#define RTU_MOTION_RESET  2u   /* no lookup for pixels that show this node */
+typedef struct RtuNodeMotion {   /* 96 B */
+    float    m[12];      /* prev_from_cur, three rows {a, b, c, d}: p_prev.k = dot(row_k.abc, p) + row_k.d */
+    float    g[9];       /* three rows: N_prev is g N, normalised */
+    uint32_t flags;
+    uint32_t reserved[2];  /* 0 */
+} RtuNodeMotion;
+int  rtu_scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* reset_mesh_ids, int n_reset,
+                      RtuNodeMotion* out /* cur->n_nodes */);
+int  rtu_temporal_accumulate_motion(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                    const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
+                                    const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap);
+int  rtu_temporal_accumulate_motion_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                           const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                           void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream);
+int  rtu_motion_vectors(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuNodeMotion* motion,
+                        uint32_t n_nodes, float* h_mv);
+int  rtu_motion_vectors_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const void* d_hits,
+                               const RtuNodeMotion* d_motion, uint32_t n_nodes, void* d_mv, void* hip_stream);
+int  rtu_temporal_frame_moved_device(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                                     void* d_rgbz, void* hip_stream);
+int  rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                              float* h_rgbz);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

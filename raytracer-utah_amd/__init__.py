@@ -165,7 +165,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_progressive_snapshot_denoised_device", "rtu_progressive_snapshot_denoised",
                "rtu_camera_sample_rays_device", "rtu_temporal_defaults", "rtu_temporal_accumulate", "rtu_temporal_accumulate_device",
                "rtu_temporal_begin", "rtu_temporal_frame_device", "rtu_temporal_frame", "rtu_temporal_history_device", "rtu_temporal_reset",
-               "rtu_temporal_free"]
+               "rtu_temporal_free", "rtu_scene_motion", "rtu_temporal_accumulate_motion", "rtu_temporal_accumulate_motion_device",
+               "rtu_motion_vectors", "rtu_motion_vectors_device", "rtu_temporal_frame_moved_device", "rtu_temporal_frame_moved"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -431,6 +432,96 @@ def temporal_accumulate(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev=None, d
         raise RtuError(rc, "rtu_temporal_accumulate: a descriptor outside its rules (max_history 1..65535, sigma_plane > 0, normal_min "
                            "-1..1, known flags, reserved words 0) or a camera of another size")
     return out, hist
+
+
+# temporal accumulation across scene updates (include/rtu_render.h): the per-node motion table
+RTU_MOTION_STATIC, RTU_MOTION_RESET = 1, 2
+_U32 = ctypes.c_uint32
+_sig(hip, "rtu_scene_motion", _I, _P, _P, _P, _I, _P)
+_sig(hip, "rtu_temporal_accumulate_motion", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+     _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32)
+_sig(hip, "rtu_temporal_accumulate_motion_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+     _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32, _P)
+_sig(hip, "rtu_motion_vectors", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, _U32, _P)
+_sig(hip, "rtu_motion_vectors_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, _U32, _P, _P)
+_sig(hip, "rtu_temporal_frame_moved_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _U32, ctypes.c_int32, _P, _P)
+_sig(hip, "rtu_temporal_frame_moved", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _U32, ctypes.c_int32, _P)
+
+
+def motion_dtype():
+    """RtuNodeMotion (96 bytes) as a numpy structured dtype: m [3, 4] (prev_from_cur, rows {a, b, c, d}), g [3, 3], flags, reserved."""
+    import numpy as np
+    return np.dtype([("m", np.float32, (3, 4)), ("g", np.float32, (3, 3)), ("flags", np.uint32), ("reserved", np.uint32, (2,))])
+
+
+def _as_motion(motion):
+    import numpy as np
+    motion = np.ascontiguousarray(motion)
+    if motion.dtype != motion_dtype() or motion.ndim != 1:
+        raise RtuError(RTU_ERR_ARG, "motion: a 1-d array of motion_dtype()")
+    return motion
+
+
+def scene_motion(prev, cur, reset_meshes=()):
+    """rtu_scene_motion (pure host code): for every node of the Scene `cur` the affine map that carries a point of that node's surface
+    to where it was in the Scene `prev` (same shape), as an array of motion_dtype(). Nodes whose chain did not change are
+    RTU_MOTION_STATIC; nodes of the meshes in reset_meshes (those given to update_meshes) are RTU_MOTION_RESET."""
+    import numpy as np
+    out = np.zeros(cur.desc.n_nodes, motion_dtype())
+    ids = (ctypes.c_uint32 * max(1, len(reset_meshes)))(*reset_meshes)
+    rc = hip.rtu_scene_motion(prev.desc_ptr, cur.desc_ptr, ids, len(reset_meshes), out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_scene_motion: " + ("a mesh id outside the scene's meshes" if rc == RTU_ERR_ARG else scene_shape_diff(prev, cur) or ""))
+    return out
+
+
+def temporal_accumulate_motion(prev_cam, cur_cam, rgbz, hits, albedo, motion, hist_prev=None, desc=None, history_cap=0):
+    """rtu_temporal_accumulate_motion (pure host code): temporal_accumulate() across a scene update — `motion` (motion_dtype(), see
+    scene_motion()) carries every pixel's hit point to the previous frame's scene before the lookup; history_cap 0 (none) .. 65535
+    bounds the history length a pixel takes over. -> (accumulated rgbz [H, W, 4], the new history [3, H, W, 4])."""
+    import numpy as np
+    rgbz = np.ascontiguousarray(rgbz, np.float32)
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
+    if hist_prev is not None:
+        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
+        if hist_prev.size != 12 * H * W:
+            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [3, H, W, 4]")
+    motion = _as_motion(motion)
+    d = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    out, hist = np.empty_like(rgbz), np.empty((3, H, W, 4), np.float32)
+    rc = hip.rtu_temporal_accumulate_motion(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
+                                            rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
+                                            hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data,
+                                            motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), int(history_cap))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate_motion: a descriptor outside its rules, a camera of another size, history_cap outside "
+                           "0..65535, or a table entry with an unknown flag or a non-zero reserved word")
+    return out, hist
+
+
+def motion_vectors(prev_cam, hits, motion, width, height):
+    """rtu_motion_vectors (pure host code): float32 [H, W, 4] — per pixel {fx, fy, 1, 0}, the continuous coordinates in the image of
+    prev_cam (an integer is a pixel centre) where the pixel's surface point was before the update described by `motion`, or zeros."""
+    import numpy as np
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != hit_dtype() or hits.size != width * height:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype()")
+    motion = _as_motion(motion)
+    d = temporal_desc(width, height)
+    out = np.empty((height, width, 4), np.float32)
+    rc = hip.rtu_motion_vectors(ctypes.byref(d), ctypes.byref(prev_cam), hits.ctypes.data,
+                                motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_motion_vectors: a camera of another size or a table entry with an unknown flag or a non-zero reserved word")
+    return out
 
 
 def denoise_desc(width=0, height=0, **overrides):
@@ -1064,6 +1155,19 @@ class Temporal:
     def frame_device(self, frame, d_rgbz, stream=None):
         self._check(hip.rtu_temporal_frame_device(self._h, ctypes.byref(frame), d_rgbz, stream))
 
+    def frame_moved(self, frame, motion, history_cap=0):
+        """The next frame after the scene was updated (Context.update / update_meshes): the history is kept and looked up through
+        `motion`, scene_motion(scene of the previous frame, scene now). rgbz float32 [H, W, 4] (synchronous)."""
+        import numpy as np
+        motion = _as_motion(motion)
+        out = np.empty((self.desc.height, self.desc.width, 4), np.float32)
+        self._check(hip.rtu_temporal_frame_moved(self._h, ctypes.byref(frame), motion.ctypes.data, len(motion), int(history_cap), out.ctypes.data))
+        return out
+
+    def frame_moved_device(self, frame, motion, d_rgbz, history_cap=0, stream=None):
+        motion = _as_motion(motion)
+        self._check(hip.rtu_temporal_frame_moved_device(self._h, ctypes.byref(frame), motion.ctypes.data, len(motion), int(history_cap), d_rgbz, stream))
+
     def history(self):
         """The history length of every pixel after the last frame, float32 [H, W] (0 before the first)."""
         import numpy as np
@@ -1197,6 +1301,18 @@ class Context:
         self._check(hip.rtu_temporal_accumulate_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
                                                        ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
                                                        d_rgbz_out_ptr, stream))
+
+    def temporal_accumulate_motion_device(self, desc, prev_cam, cur_cam, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                          d_rgbz_out_ptr, d_motion_ptr, n_nodes, history_cap=0, stream=None):
+        """rtu_temporal_accumulate_motion_device: temporal_accumulate_motion() on device memory; d_motion_ptr: n_nodes RtuNodeMotion,
+        16-byte aligned, trusted as it is."""
+        self._check(hip.rtu_temporal_accumulate_motion_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                                              ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                                              d_rgbz_out_ptr, d_motion_ptr, n_nodes, int(history_cap), stream))
+
+    def motion_vectors_device(self, desc, prev_cam, d_hits_ptr, d_motion_ptr, n_nodes, d_mv_ptr, stream=None):
+        """rtu_motion_vectors_device: motion_vectors() on device memory, width * height float4 to d_mv_ptr."""
+        self._check(hip.rtu_motion_vectors_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam), d_hits_ptr, d_motion_ptr, n_nodes, d_mv_ptr, stream))
 
     def set_cancel(self, flag):
         """rtu_set_cancel_flag: a ctypes.c_int the library polls between sample batches (None: none)."""

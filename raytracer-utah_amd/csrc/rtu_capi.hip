@@ -1813,6 +1813,8 @@ struct RtuTemporal {
     RtuFrameDesc    prev_cam{};
     DevBuf<float4>   rays, img, hits, albedo, hist[2];
     DevBuf<uint32_t> keys;
+    DevBuf<RtuNodeMotion>    motion;      // rtu_temporal_frame_moved: the table of the frame, grown at the first frame that needs it ...
+    PinnedBuf<RtuNodeMotion> motion_host; // ... and the staging memory it is copied through
 };
 
 static void temporal_release(RtuTemporal* t) {
@@ -1822,6 +1824,8 @@ static void temporal_release(RtuTemporal* t) {
     t->albedo.reset();
     for (DevBuf<float4>& h : t->hist) h.reset();
     t->keys.reset();
+    t->motion.reset();
+    t->motion_host.reset();
     t->has_hist = false;
     t->ctx = nullptr;
 }
@@ -2590,6 +2594,105 @@ int rtu_scene_shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b, char* err
     }
     if (err_buf && err_len) snprintf(err_buf, err_len, "%s", tmp.error.c_str());
     return rc;
+}
+
+// The per-node maps of rtu_render.h "Temporal accumulation across scene updates", composed in binary64. Affine maps as {A row-major, b}.
+namespace {
+struct Affine64 { double A[9], b[3]; };
+
+Affine64 affine_identity() { return Affine64{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}}; }
+
+// x -> M (A x + b) + t with M column-major binary32 as RtuNode.tm: one level of FromNodeCoords
+Affine64 affine_from_level(const Affine64& a, const float* M, const float* t) {
+    Affine64 r;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) r.A[3 * i + j] = ((double)M[i] * a.A[j] + (double)M[i + 3] * a.A[3 + j]) + (double)M[i + 6] * a.A[6 + j];
+        r.b[i] = (((double)M[i] * a.b[0] + (double)M[i + 3] * a.b[1]) + (double)M[i + 6] * a.b[2]) + (double)t[i];
+    }
+    return r;
+}
+
+// x -> M ((A x + b) - t): one level of ToNodeCoords with M = itm
+Affine64 affine_to_level(const Affine64& a, const float* M, const float* t) {
+    Affine64 r;
+    const double c[3] = {a.b[0] - (double)t[0], a.b[1] - (double)t[1], a.b[2] - (double)t[2]};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) r.A[3 * i + j] = ((double)M[i] * a.A[j] + (double)M[i + 3] * a.A[3 + j]) + (double)M[i + 6] * a.A[6 + j];
+        r.b[i] = ((double)M[i] * c[0] + (double)M[i + 3] * c[1]) + (double)M[i + 6] * c[2];
+    }
+    return r;
+}
+
+// a o b
+Affine64 affine_compose(const Affine64& a, const Affine64& b) {
+    Affine64 r;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) r.A[3 * i + j] = (a.A[3 * i] * b.A[j] + a.A[3 * i + 1] * b.A[3 + j]) + a.A[3 * i + 2] * b.A[6 + j];
+        r.b[i] = ((a.A[3 * i] * b.b[0] + a.A[3 * i + 1] * b.b[1]) + a.A[3 * i + 2] * b.b[2]) + a.b[i];
+    }
+    return r;
+}
+
+// W (node -> world) and W^-1 of node i of scene s; false for a parent chain that does not lead to the root in RTU_MAX_NODE_DEPTH + 1 levels
+bool node_chain(const RtuSceneDesc* s, uint32_t i, Affine64& W, Affine64& Winv) {
+    uint32_t chain[RTU_MAX_NODE_DEPTH + 1];
+    int n = 0;
+    for (int32_t k = (int32_t)i; k >= 0; k = s->nodes[k].parent) {
+        if (n > RTU_MAX_NODE_DEPTH || (uint32_t)k >= s->n_nodes) return false;
+        chain[n++] = (uint32_t)k;
+    }
+    W = affine_identity();
+    Winv = affine_identity();
+    for (int l = 0; l < n; l++) W = affine_from_level(W, s->nodes[chain[l]].tm, s->nodes[chain[l]].pos);              // the node first
+    for (int l = n - 1; l >= 0; l--) Winv = affine_to_level(Winv, s->nodes[chain[l]].itm, s->nodes[chain[l]].pos);   // the root first
+    return true;
+}
+}  // namespace
+
+int rtu_scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* reset_mesh_ids, int n_reset, RtuNodeMotion* out) {
+    if (!prev || !cur || !out || n_reset < 0 || (n_reset > 0 && !reset_mesh_ids)) return RTU_ERR_ARG;
+    if ((prev->n_meshes && !prev->meshes) || (cur->n_meshes && !cur->meshes)) return RTU_ERR_ARG;
+    for (int k = 0; k < n_reset; k++)
+        if (reset_mesh_ids[k] >= cur->n_meshes) return RTU_ERR_ARG;
+    // the shape rule of rtu_update_scene, except that a RESET mesh may have a reference tree of another size, as rtu_update_meshes allows
+    RtuSceneDesc before = *prev;
+    std::vector<RtuMesh> want;
+    if (n_reset > 0 && prev->n_meshes == cur->n_meshes) {
+        want.assign(prev->meshes, prev->meshes + prev->n_meshes);
+        for (int k = 0; k < n_reset; k++) want[reset_mesh_ids[k]].n_bvh_nodes = cur->meshes[reset_mesh_ids[k]].n_bvh_nodes;
+        before.meshes = want.data();
+    }
+    const int rc = rtu_scene_shape_diff(&before, cur, nullptr, 0);
+    if (rc != RTU_OK) return rc;
+    std::vector<uint8_t> same(cur->n_nodes);  // the node's own tm and pos are bit-identical, and so are its ancestors' (pre-order: a parent comes first)
+    for (uint32_t i = 0; i < cur->n_nodes; i++) {
+        const RtuNode &a = prev->nodes[i], &b = cur->nodes[i];
+        if (a.parent >= (int32_t)i) return RTU_ERR_ARG;
+        same[i] = memcmp(a.tm, b.tm, sizeof a.tm) == 0 && memcmp(a.pos, b.pos, sizeof a.pos) == 0 && (a.parent < 0 || same[a.parent]);
+    }
+    for (uint32_t i = 0; i < cur->n_nodes; i++) {
+        RtuNodeMotion& o = out[i];
+        memset(&o, 0, sizeof o);
+        if (same[i]) {
+            o.m[0] = o.m[5] = o.m[10] = 1.0f;
+            o.g[0] = o.g[4] = o.g[8] = 1.0f;
+            o.flags = RTU_MOTION_STATIC;
+        } else {
+            Affine64 Wp, Wpi, Wc, Wci;
+            if (!node_chain(prev, i, Wp, Wpi) || !node_chain(cur, i, Wc, Wci)) return RTU_ERR_ARG;
+            const Affine64 m = affine_compose(Wp, Wci), back = affine_compose(Wc, Wpi);
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) {
+                    o.m[4 * r + c] = (float)m.A[3 * r + c];
+                    o.g[3 * r + c] = (float)back.A[3 * c + r];
+                }
+                o.m[4 * r + 3] = (float)m.b[r];
+            }
+        }
+        for (int k = 0; k < n_reset; k++)
+            if (cur->nodes[i].mesh_id >= 0 && (uint32_t)cur->nodes[i].mesh_id == reset_mesh_ids[k]) o.flags |= RTU_MOTION_RESET;
+    }
+    return RTU_OK;
 }
 
 // CalculateImageOrigin + the u,v of CalculateCurrentPoint (RenderFunctions.cpp:243-269)
@@ -3925,7 +4028,71 @@ RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, in
     return t.release();
 }
 
+static_assert(sizeof(RtuNodeMotion) == 96, "RtuNodeMotion is 96 bytes");
+
+int rtu_temporal_accumulate_motion_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                          const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                          void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK)
+        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
+    if (rtu_temporal_check_motion(nullptr, n_nodes, history_cap) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "temporal: history_cap is 0 .. 65535");
+    if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "temporal: a camera is NULL");
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return fail(ctx, RTU_ERR_ARG, "temporal: the cameras must have the desc's width and height");
+    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out || !d_motion) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
+    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out) ||
+        misaligned(d_motion))
+        return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
+    if (d_hist_prev) {
+        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)48 * (uintptr_t)desc->width * (uintptr_t)desc->height;
+        if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
+    }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_temporal_motion(tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap),
+                                                                (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo, (const float4*)d_hist_prev,
+                                                                (float4*)d_hist_out, (float4*)d_rgbz_out, d_motion, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_motion_vectors_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const void* d_hits, const RtuNodeMotion* d_motion,
+                              uint32_t n_nodes, void* d_mv, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK)
+        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
+    if (!prev_cam || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return fail(ctx, RTU_ERR_ARG, "motion vectors: the previous camera must have the desc's width and height");
+    if (!d_hits || !d_motion || !d_mv) return fail(ctx, RTU_ERR_ARG, "motion vectors: a device pointer is NULL");
+    if (misaligned(d_hits) || misaligned(d_motion) || misaligned(d_mv)) return fail(ctx, RTU_ERR_ARG, "motion vectors: device buffers must be 16-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_motion_vectors(tp_setup(*desc, *prev_cam, *prev_cam, true), n_nodes, (const float4*)d_hits, d_motion, (float4*)d_mv,
+                                                               (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "motion vector launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+// what a moved frame has beyond a plain one (rtu_temporal_frame_moved_device)
+struct TemporalMoved {
+    const RtuNodeMotion* h_motion;
+    uint32_t n_nodes;
+    int32_t  history_cap;
+};
+
+static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgbz, void* hip_stream, const TemporalMoved* moved);
+
 int rtu_temporal_frame_device(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgbz, void* hip_stream) {
+    return temporal_frame(t, frame, d_rgbz, hip_stream, nullptr);
+}
+
+int rtu_temporal_frame_moved_device(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                                    void* d_rgbz, void* hip_stream) {
+    const TemporalMoved moved{h_motion, n_nodes, history_cap};
+    return temporal_frame(t, frame, d_rgbz, hip_stream, &moved);
+}
+
+static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgbz, void* hip_stream, const TemporalMoved* moved) {
     if (!t || !t->ctx) return RTU_ERR_ARG;
     RtuContext* ctx = t->ctx;
     if (!frame) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
@@ -3940,10 +4107,22 @@ int rtu_temporal_frame_device(RtuTemporal* t, const RtuFrameDesc* frame, void* d
     const hipStream_t stream = (hipStream_t)hip_stream;
     const bool paths = frame->gather_bounces != 0;
     const size_t n = t->pixels;
-    if (t->scene_gen != ctx->scene_gen) {  // moved geometry or lights: what was accumulated shows another scene
+    if (moved) {
+        if (moved->n_nodes != (uint32_t)ctx->shape_nodes.size())
+            return fail(ctx, RTU_ERR_ARG, "the motion table has %u entries, the uploaded scene %u nodes", moved->n_nodes, (uint32_t)ctx->shape_nodes.size());
+        if (!moved->h_motion && t->has_hist) return fail(ctx, RTU_ERR_ARG, "the motion table is NULL");
+        if (rtu_temporal_check_motion(moved->h_motion, moved->n_nodes, moved->history_cap) != RTU_OK)
+            return fail(ctx, RTU_ERR_ARG, "motion: history_cap 0 .. 65535, known flags and reserved words 0 in every table entry");
+        RTU_HIP(ctx, hipSetDevice(ctx->device));  // (also on frame 0, which does not use them: the next moved frame allocates nothing)
+        RTU_HIP(ctx, t->motion.grow(moved->n_nodes));
+        RTU_HIP(ctx, t->motion_host.grow(moved->n_nodes));
+    }
+    if (t->scene_gen != ctx->scene_gen) {
         t->scene_gen = ctx->scene_gen;
-        t->has_hist = false;
-        t->k = 0;
+        if (!moved) {  // moved geometry or lights: what was accumulated shows another scene
+            t->has_hist = false;
+            t->k = 0;
+        }
     }
     int rc = rtu_camera_sample_rays_device(ctx, frame, t->k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
     if (rc != RTU_OK) return rc;
@@ -3968,8 +4147,16 @@ int rtu_temporal_frame_device(RtuTemporal* t, const RtuFrameDesc* frame, void* d
     if ((rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
     RtuTemporalDesc td = t->desc;
     td.flags = 0;
-    rc = rtu_temporal_accumulate_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
-                                        t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
+    if (moved && t->has_hist) {
+        // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
+        memcpy(t->motion_host.get(), moved->h_motion, moved->n_nodes * sizeof(RtuNodeMotion));
+        RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), moved->n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
+        rc = rtu_temporal_accumulate_motion_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(), t->hist[t->cur].get(),
+                                                   t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), moved->n_nodes, moved->history_cap, hip_stream);
+    } else {  // (frame 0 of a moved session has nothing to look up: the plain form gives its bits)
+        rc = rtu_temporal_accumulate_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                            t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
+    }
     if (rc != RTU_OK) return rc;
     t->cur ^= 1;
     t->has_hist = true;
@@ -3992,6 +4179,19 @@ int rtu_temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz)
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     RTU_HIP(ctx, ctx->fb.grow(t->pixels));
     const int rc = rtu_temporal_frame_device(t, frame, ctx->fb.get(), ctx->stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), t->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RTU_OK;
+}
+
+int rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap, float* h_rgbz) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->fb.grow(t->pixels));
+    const int rc = rtu_temporal_frame_moved_device(t, frame, h_motion, n_nodes, history_cap, ctx->fb.get(), ctx->stream);
     if (rc != RTU_OK) return rc;
     RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), t->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -133,8 +133,150 @@ RTU_HD void tp_pixel(const TpParams& P, const float4* hE, const float4* hP, cons
     oN = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
 }
 
+// ---- moving nodes (include/rtu_render.h "Temporal accumulation across scene updates") ------------------------------------------------
+// What the motion form needs beyond TpParams; made once per call by tp_motion_setup. P.lookup is TP_LOOKUP_NONE or TP_LOOKUP_REPROJECT
+// here: whether a pixel takes the one tap is decided per pixel (same_cam and its node's RTU_MOTION_STATIC).
+struct TpMotionParams {
+    TpParams P;
+    int32_t  same_cam;  // the two cameras are equal bit for bit
+    uint32_t n_nodes;
+    float    cap;       // (float)history_cap, 0: none
+};
+
+inline TpMotionParams tp_motion_setup(const RtuTemporalDesc& d, const RtuFrameDesc& prev, const RtuFrameDesc& cur, bool has_prev, uint32_t n_nodes,
+                                      int32_t history_cap) {
+    TpMotionParams M{};
+    M.P = tp_setup(d, prev, cur, has_prev);
+    M.same_cam = M.P.lookup == TP_LOOKUP_STATIC;
+    if (has_prev) M.P.lookup = TP_LOOKUP_REPROJECT;
+    M.n_nodes = n_nodes;
+    M.cap = (float)history_cap;
+    return M;
+}
+
+// the words of an RtuNodeMotion that are read, in registers: the caller loads them (the kernel with 16-byte loads, the host form from
+// a table of any alignment)
+struct TpMotion {
+    float    m[12], g[9];
+    uint32_t flags;
+};
+
+RTU_HD TpMotion tp_motion_identity() {
+    TpMotion T;
+    for (int i = 0; i < 12; i++) T.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    for (int i = 0; i < 9; i++) T.g[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+    T.flags = RTU_MOTION_STATIC;
+    return T;
+}
+
+// the index of a hit's node in a table of n_nodes entries, or -1: not a hit, node < 0, node >= n_nodes
+RTU_HD int32_t tp_motion_index(const float4& hit0, uint32_t n_nodes) {
+    union { float f; uint32_t u; } flags, node;
+    flags.f = hit0.z;
+    node.f = hit0.y;
+    return ((flags.u & RTU_RAY_HIT) != 0 && node.u < n_nodes && node.u < 0x80000000u) ? (int32_t)node.u : -1;
+}
+
+// Where the surface point of a pixel was in the previous scene: Pm, Nm by the pixel's table entry T (tp_motion_identity() when in_table
+// is false). Returns whether the pixel may look its history up at all.
+RTU_HD bool tp_moved_point(bool in_table, const TpMotion& T, const f3& Pp, const f3& Np, f3& Pm, f3& Nm) {
+    const bool is_static = (T.flags & RTU_MOTION_STATIC) != 0;
+    const f3 pm = mk3(dot3(mk3(T.m[0], T.m[1], T.m[2]), Pp) + T.m[3], dot3(mk3(T.m[4], T.m[5], T.m[6]), Pp) + T.m[7],
+                      dot3(mk3(T.m[8], T.m[9], T.m[10]), Pp) + T.m[11]);
+    const f3 q = mk3(dot3(mk3(T.g[0], T.g[1], T.g[2]), Np), dot3(mk3(T.g[3], T.g[4], T.g[5]), Np), dot3(mk3(T.g[6], T.g[7], T.g[8]), Np));
+    const float len = sqrtf(dot3(q, q));
+    const f3 nm = mk3(q.x / len, q.y / len, q.z / len);
+    const bool fin = tp_finite(pm.x) && tp_finite(pm.y) && tp_finite(pm.z) && tp_finite(nm.x) && tp_finite(nm.y) && tp_finite(nm.z);
+    Pm = is_static ? Pp : pm;
+    Nm = is_static ? Np : nm;
+    return in_table && (T.flags & RTU_MOTION_RESET) == 0 && (is_static || fin);
+}
+
+// The previous-image coordinates of world point Pm (the expressions of tp_pixel): false unless s is finite and > 0.
+RTU_HD bool tp_project(const TpParams& P, const f3& Pm, float& fx, float& fy) {
+    const f3 pos = ld3(P.pos), nrm = ld3(P.nrm);
+    const f3 D = Pm - pos;
+    const float s = P.num / dot3(D, nrm);
+    const f3 Q = (pos + D * s) - ld3(P.origin);
+    fx = dot3(Q, ld3(P.u)) / P.uu - 0.5f;
+    fy = dot3(Q, ld3(P.v)) / P.vv - 0.5f;
+    return tp_finite(s) && s > 0.0f;
+}
+
+// tp_pixel with a moving scene: in_table / T as for tp_moved_point.
+RTU_HD void tp_pixel_motion(const TpMotionParams& M, bool in_table, const TpMotion& T, const float4* hE, const float4* hP, const float4* hN, int x, int y,
+                            const float4& rgbz, const float4* hit, const float4& albedo, float4& out, float4& oE, float4& oP, float4& oN) {
+    const TpParams& P = M.P;
+    union { float f; uint32_t u; } flags, node;
+    flags.f = hit[0].z;
+    node.f = hit[0].y;
+    const bool valid = (flags.u & RTU_RAY_HIT) != 0;
+    const f3 d = dn_demod(albedo);
+    const f3 e_cur = mk3(rgbz.x / d.x, rgbz.y / d.y, rgbz.z / d.z);
+    const f3 Pp = mk3(hit[1].x, hit[1].y, hit[1].z), Np = mk3(hit[2].x, hit[2].y, hit[2].z);
+    const float plane_max = P.sigma_plane * hit[0].x;
+
+    f3 Pm, Nm;
+    const bool look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && valid && P.lookup != TP_LOOKUP_NONE;
+    const bool one_tap = look && M.same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
+
+    f3 acc = mk3(0.0f, 0.0f, 0.0f), e_prev = mk3(0.0f, 0.0f, 0.0f);
+    float nacc = 0.0f, wsum = 0.0f, n_prev = 0.0f;
+    if (one_tap) {
+        tp_tap(P, hE, hP, hN, x, y, 1.0f, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+    } else if (look) {
+        float fx, fy;
+        if (tp_project(P, Pm, fx, fy) && fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {
+            const float flx = floorf(fx), fly = floorf(fy);
+            const int x0 = (int)flx, y0 = (int)fly;
+            const float wx = fx - flx, wy = fy - fly;
+            const float ux = 1.0f - wx, uy = 1.0f - wy;
+            tp_tap(P, hE, hP, hN, x0, y0, ux * uy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+            tp_tap(P, hE, hP, hN, x0 + 1, y0, wx * uy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+            tp_tap(P, hE, hP, hN, x0, y0 + 1, ux * wy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+            tp_tap(P, hE, hP, hN, x0 + 1, y0 + 1, wx * wy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+        }
+    }
+    if (wsum > 0.01f) {
+        e_prev = mk3(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+        n_prev = nacc / wsum;
+    }
+    if (M.cap > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, M.cap);
+
+    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);
+    const bool fresh = n_prev == 0.0f;
+    const float n_blend = smin(n_prev + 1.0f, P.max_history);
+    const float a = 1.0f / n_blend;
+    const f3 e_blend = e_prev + (e_cur - e_prev) * a;
+    const f3 e = !finite ? e_prev : (fresh ? e_cur : e_blend);
+    const float n = !finite ? n_prev : (fresh ? 1.0f : n_blend);
+    const bool keep = valid && (finite || !fresh);
+    if (!valid) node.u = 0xFFFFFFFFu;
+    out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, rgbz.w) : rgbz;
+    oE = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    oP = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    oN = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
+}
+
+// the motion vector of a pixel: {fx, fy, 1, 0} or zeros
+RTU_HD float4 tp_motion_vector(const TpParams& P, bool in_table, const TpMotion& T, const float4* hit) {
+    f3 Pm, Nm;
+    const f3 Pp = mk3(hit[1].x, hit[1].y, hit[1].z), Np = mk3(hit[2].x, hit[2].y, hit[2].z);
+    (void)tp_moved_point(in_table, T, Pp, Np, Pm, Nm);
+    float fx, fy;
+    const bool ok = tp_project(P, Pm, fx, fy) && in_table && (T.flags & RTU_MOTION_RESET) == 0 && tp_finite(Pm.x) && tp_finite(Pm.y) && tp_finite(Pm.z);
+    return ok ? make_float4(fx, fy, 1.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 // RTU_OK or RTU_ERR_ARG: the rules of RtuTemporalDesc (include/rtu_render.h)
 int rtu_temporal_check_desc(const RtuTemporalDesc* d);
+// RTU_OK or RTU_ERR_ARG: history_cap 0 .. 65535; with a host table, its reserved words 0 and its flags known
+int rtu_temporal_check_motion(const RtuNodeMotion* h_motion_or_null, uint32_t n_nodes, int32_t history_cap);
+// The motion form on the device: as rtu_launch_temporal, d_motion n_nodes entries, 16-byte aligned (nullptr allowed with n_nodes == 0).
+int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
+// mv[i] = the motion vector of pixel i
+int rtu_launch_motion_vectors(const TpParams& p, uint32_t n_nodes, const float4* hits, const RtuNodeMotion* d_motion, float4* mv, hipStream_t stream);
 
 // The accumulator on the device: rgbz, albedo, rgbz_out [width * height] float4, hits [width * height] RtuRayHit, hist_prev (nullptr
 // with TP_LOOKUP_NONE) and hist_out three planes of width * height float4 each. rgbz_out == rgbz is allowed; hist_out does not overlap

@@ -8,10 +8,17 @@
 //                       the vector L1 —, and writes its pixel of the image and of the three planes of the new history (64 B). No
 //                       LDS, no atomics. The lookup mode is wave-uniform (a kernel argument).
 //   k_temporal_history  one lane per pixel: the history length out of the E plane.
+//   k_temporal_motion   k_temporal for a moving scene (tp_pixel_motion): the same lanes, workgroups, loads and stores; besides, a lane
+//                       reads the table entry of its pixel's node, 96 B as six 16-byte loads STRAIGHT FROM GLOBAL MEMORY: the table
+//                       has no bound that LDS could hold, the lanes of a wavefront mostly show one or two nodes — lanes with one
+//                       address are served by one request — and the few entries a frame touches stay in the vector L1. The lookup
+//                       mode (none, one tap, four taps) is per lane; single exit, select on values.
+//   k_motion_vectors    one lane per pixel: its RtuRayHit and its node's entry in, one float4 out.
 // Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
 // anywhere in hist_prev: hist_out must not overlap it.
 #include "rtu_temporal.h"
 
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -33,6 +40,52 @@ __global__ void __launch_bounds__(256) k_temporal(TpParams P, const float4* rgbz
     hist_out[2 * n + p] = oN;
 }
 
+// the table entry of a pixel (in_table) or the identity; 16-byte loads: the table is 16-byte aligned and an entry is 96 B
+__device__ TpMotion load_motion(const RtuNodeMotion* __restrict__ motion, int32_t k) {
+    TpMotion T = tp_motion_identity();
+    if (k >= 0) {
+        const float4* e = reinterpret_cast<const float4*>(motion + k);
+        const float4 a = e[0], b = e[1], c = e[2], d = e[3], f = e[4], g = e[5];
+        union { float f; uint32_t u; } fl;
+        fl.f = g.y;
+        T.m[0] = a.x; T.m[1] = a.y; T.m[2] = a.z; T.m[3] = a.w; T.m[4] = b.x; T.m[5] = b.y; T.m[6] = b.z; T.m[7] = b.w;
+        T.m[8] = c.x; T.m[9] = c.y; T.m[10] = c.z; T.m[11] = c.w;
+        T.g[0] = d.x; T.g[1] = d.y; T.g[2] = d.z; T.g[3] = d.w; T.g[4] = f.x; T.g[5] = f.y; T.g[6] = f.z; T.g[7] = f.w; T.g[8] = g.x;
+        T.flags = fl.u;
+    }
+    return T;
+}
+
+__global__ void __launch_bounds__(256) k_temporal_motion(TpMotionParams M, const float4* rgbz, const float4* __restrict__ hits,
+                                                         const float4* __restrict__ albedo, const float4* __restrict__ hist_prev,
+                                                         float4* __restrict__ hist_out, float4* rgbz_out, const RtuNodeMotion* __restrict__ motion) {
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= M.P.width || y >= M.P.height) return;
+    const size_t n = (size_t)M.P.width * (size_t)M.P.height;
+    const size_t p = (size_t)y * (size_t)M.P.width + (size_t)x;
+    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
+    const int32_t k = tp_motion_index(hit[0], M.n_nodes);
+    const TpMotion T = load_motion(motion, k);
+    float4 out, oE, oP, oN;
+    const float4* hP = hist_prev ? hist_prev + n : nullptr;
+    const float4* hN = hist_prev ? hist_prev + 2 * n : nullptr;
+    tp_pixel_motion(M, k >= 0, T, hist_prev, hP, hN, x, y, rgbz[p], hit, albedo[p], out, oE, oP, oN);
+    rgbz_out[p] = out;
+    hist_out[p] = oE;
+    hist_out[n + p] = oP;
+    hist_out[2 * n + p] = oN;
+}
+
+__global__ void __launch_bounds__(256) k_motion_vectors(TpParams P, uint32_t n_nodes, const float4* __restrict__ hits,
+                                                        const RtuNodeMotion* __restrict__ motion, float4* __restrict__ mv) {
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= P.width || y >= P.height) return;
+    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
+    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
+    const int32_t k = tp_motion_index(hit[0], n_nodes);
+    mv[p] = tp_motion_vector(P, k >= 0, load_motion(motion, k), hit);
+}
+
 __global__ void __launch_bounds__(256) k_temporal_history(const float4* __restrict__ hist, float* __restrict__ n_out, unsigned long long pixels) {
     const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
     if (i >= pixels) return;
@@ -52,6 +105,37 @@ int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels,
     if (pixels == 0) return (int)hipSuccess;
     hipLaunchKernelGGL(k_temporal_history, dim3((uint32_t)((pixels + 255) / 256)), dim3(256), 0, stream, hist, n_out, (unsigned long long)pixels);
     return (int)hipGetLastError();
+}
+
+int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
+    const dim3 grid((uint32_t)((m.P.width + 31) / 32), (uint32_t)((m.P.height + 7) / 8));
+    hipLaunchKernelGGL(k_temporal_motion, grid, dim3(256), 0, stream, m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
+    return (int)hipGetLastError();
+}
+
+int rtu_launch_motion_vectors(const TpParams& p, uint32_t n_nodes, const float4* hits, const RtuNodeMotion* d_motion, float4* mv, hipStream_t stream) {
+    const dim3 grid((uint32_t)((p.width + 31) / 32), (uint32_t)((p.height + 7) / 8));
+    hipLaunchKernelGGL(k_motion_vectors, grid, dim3(256), 0, stream, p, n_nodes, hits, d_motion, mv);
+    return (int)hipGetLastError();
+}
+
+int rtu_temporal_check_motion(const RtuNodeMotion* h, uint32_t n_nodes, int32_t history_cap) {
+    if (history_cap < 0 || history_cap > 65535) return RTU_ERR_ARG;
+    if (h)
+        for (uint32_t i = 0; i < n_nodes; i++)
+            if ((h[i].flags & ~(RTU_MOTION_STATIC | RTU_MOTION_RESET)) || h[i].reserved[0] || h[i].reserved[1]) return RTU_ERR_ARG;
+    return RTU_OK;
+}
+
+static TpMotion host_motion(const RtuNodeMotion* motion, int32_t k) {
+    TpMotion T = tp_motion_identity();
+    if (k >= 0) {
+        memcpy(T.m, motion[k].m, sizeof T.m);
+        memcpy(T.g, motion[k].g, sizeof T.g);
+        T.flags = motion[k].flags;
+    }
+    return T;
 }
 
 int rtu_temporal_check_desc(const RtuTemporalDesc* d) {
@@ -111,6 +195,65 @@ int rtu_temporal_accumulate(const RtuTemporalDesc* desc, const RtuFrameDesc* pre
             st(h_hist_out, n + p, oP);
             st(h_hist_out, 2 * n + p, oN);
         }
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate_motion(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                   const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
+                                   const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap) {
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out || !motion) return RTU_ERR_ARG;
+    if (rtu_temporal_check_motion(motion, n_nodes, history_cap) != RTU_OK) return RTU_ERR_ARG;
+    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return RTU_ERR_ARG;
+    const int W = desc->width, H = desc->height;
+    const size_t n = (size_t)W * (size_t)H;
+    if (h_hist_prev) {  // taps read anywhere in the previous history
+        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 48 * n;
+        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
+    }
+    const TpMotionParams M = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
+    std::vector<float4> prev;
+    if (h_hist_prev) {
+        prev.resize(3 * n);
+        for (size_t i = 0; i < 3 * n; i++) prev[i] = make_float4(h_hist_prev[4 * i], h_hist_prev[4 * i + 1], h_hist_prev[4 * i + 2], h_hist_prev[4 * i + 3]);
+    }
+    const float4* hE = h_hist_prev ? prev.data() : nullptr;
+    const float4* hP = h_hist_prev ? prev.data() + n : nullptr;
+    const float4* hN = h_hist_prev ? prev.data() + 2 * n : nullptr;
+    auto f4 = [](const float* p, size_t i) { return make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); };
+    auto st = [](float* p, size_t i, const float4& v) { p[4 * i] = v.x; p[4 * i + 1] = v.y; p[4 * i + 2] = v.z; p[4 * i + 3] = v.w; };
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t p = (size_t)y * (size_t)W + (size_t)x;
+            const float* h = reinterpret_cast<const float*>(h_hits + p);
+            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
+            const int32_t k = tp_motion_index(hit[0], n_nodes);
+            float4 out, oE, oP, oN;
+            tp_pixel_motion(M, k >= 0, host_motion(motion, k), hE, hP, hN, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, oE, oP, oN);
+            st(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
+            st(h_hist_out, p, oE);
+            st(h_hist_out, n + p, oP);
+            st(h_hist_out, 2 * n + p, oN);
+        }
+    return RTU_OK;
+}
+
+int rtu_motion_vectors(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuNodeMotion* motion, uint32_t n_nodes,
+                       float* h_mv) {
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !prev_cam || !h_hits || !motion || !h_mv) return RTU_ERR_ARG;
+    if (rtu_temporal_check_motion(motion, n_nodes, 0) != RTU_OK) return RTU_ERR_ARG;
+    if (prev_cam->width != desc->width || prev_cam->height != desc->height) return RTU_ERR_ARG;
+    const TpParams P = tp_setup(*desc, *prev_cam, *prev_cam, true);
+    const size_t n = (size_t)desc->width * (size_t)desc->height;
+    for (size_t p = 0; p < n; p++) {
+        const float* h = reinterpret_cast<const float*>(h_hits + p);
+        const float4 hit[3] = {make_float4(h[0], h[1], h[2], h[3]), make_float4(h[4], h[5], h[6], h[7]), make_float4(h[8], h[9], h[10], h[11])};
+        const int32_t k = tp_motion_index(hit[0], n_nodes);
+        const float4 v = tp_motion_vector(P, k >= 0, host_motion(motion, k), hit);
+        h_mv[4 * p] = v.x; h_mv[4 * p + 1] = v.y; h_mv[4 * p + 2] = v.z; h_mv[4 * p + 3] = v.w;
+    }
     return RTU_OK;
 }
 

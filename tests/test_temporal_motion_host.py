@@ -1,0 +1,529 @@
+"""Temporal accumulation across scene updates (include/rtu_render.h "Temporal accumulation across scene updates"), no GPU: the motion
+table of rtu_scene_motion against a numpy binary64 composition of the same node fields; the host form of the accumulator
+(rtu_temporal_accumulate_motion) and of the motion vectors against an independent numpy restatement, bit for bit, over chains of
+five frames; and its effect on the oracle's own path-traced samples of a scene whose teapot moves.
+
+The restatement extends np_temporal of tests/test_temporal_host.py: whole float32 arrays, one operation at a time in the order of the
+rules, so every pixel sees the binary32 operations of tp_pixel_motion (raytracer-utah_amd/csrc/rtu_temporal.h) in their order."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+from test_denoise_host import SIZES, bits, dot3, oracle_guides
+from test_light_lists import RtuNode
+from test_mesh_update_host import clone, deformed_scene
+from test_temporal_host import FRAMES, chain_cameras, chain_inputs, cross3, make_camera, np_temporal, same_camera, v3
+
+F = np.float32
+RTU_RAY_HIT = 1
+STATIC, RESET = 1, 2
+
+
+def nodes(scene):
+    return ctypes.cast(scene.desc.nodes, ctypes.POINTER(RtuNode))
+
+
+# ---- 1. rtu_scene_motion --------------------------------------------------------------------------------------------------------------
+def np_chain(scene, i):
+    """(A, b) of W and of W^-1 of node i in binary64 from the scene's own tm, itm and pos."""
+    A, b = np.eye(3), np.zeros(3)
+    chain, j = [], i
+    while j >= 0:
+        chain.append(j)
+        j = nodes(scene)[j].parent
+    for j in chain:  # FromNodeCoords, the node first
+        t = nodes(scene)[j]
+        tm = np.array(list(t.tm), np.float64).reshape(3, 3).T  # column-major
+        A, b = tm @ A, tm @ b + np.array(list(t.pos), np.float64)
+    Ai, bi = np.eye(3), np.zeros(3)
+    for j in reversed(chain):  # ToNodeCoords, the root first
+        t = nodes(scene)[j]
+        itm = np.array(list(t.itm), np.float64).reshape(3, 3).T
+        Ai, bi = itm @ Ai, itm @ (bi - np.array(list(t.pos), np.float64))
+    return (A, b), (Ai, bi)
+
+
+def chain_same(prev, cur, i):
+    j = i
+    while j >= 0:
+        a, b = nodes(prev)[j], nodes(cur)[j]
+        if bytes(a.tm) != bytes(b.tm) or bytes(a.pos) != bytes(b.pos):
+            return False
+        j = a.parent
+    return True
+
+
+def replace_nodes(scene, rng, which):
+    """Random re-placements through the Scene mutators, which keep tm and itm consistent."""
+    for i in which:
+        axis = rng.normal(size=3)
+        scene.node_rotate(i, tuple(float(x) for x in axis / np.linalg.norm(axis)), float(rng.uniform(-60, 60)))
+        scene.node_scale(i, *(float(x) for x in rng.uniform(0.6, 1.6, 3)))
+        scene.node_translate(i, tuple(float(x) for x in rng.uniform(-2, 2, 3)))
+
+
+def check_motion(pkg, prev, cur, table, rng):
+    ulp = 2.0 ** -23
+    n = cur.desc.n_nodes
+    assert table.shape == (n,) and not table["reserved"].any()
+    for i in range(n):
+        T = table[i]
+        same = chain_same(prev, cur, i)
+        assert bool(T["flags"] & STATIC) == same, "node %d: STATIC %s, chain unchanged %s" % (i, bool(T["flags"] & STATIC), same)
+        if same:
+            assert np.array_equal(bits(T["m"]), bits(np.eye(3, 4, dtype=F))) and np.array_equal(bits(T["g"]), bits(np.eye(3, dtype=F)))
+            continue
+        (Ap, bp), (Api, bpi) = np_chain(prev, i)
+        (Ac, bc), (Aci, bci) = np_chain(cur, i)
+        m = np.concatenate([Ap @ Aci, (Ap @ bci + bp)[:, None]], axis=1)
+        g = (Ac @ Api).T
+        # one final rounding of a value at most the row's largest (half an ulp of it), and a binary64 association that differs from
+        # numpy's moves the binary64 value by parts in 2^-52, which can flip that rounding: one ulp of the row's largest magnitude
+        for what, got, want in (("m", T["m"], m), ("g", T["g"], g)):
+            tol = ulp * np.abs(want).max(axis=1, keepdims=True)
+            assert (np.abs(got.astype(np.float64) - want) <= tol).all(), "node %d %s:\n%s\n%s" % (i, what, got, want)
+        x = rng.uniform(-3, 3, (50, 3))
+        pc, pp = x @ Ac.T + bc, x @ Ap.T + bp
+        back = pc @ T["m"][:, :3].astype(np.float64).T + T["m"][:, 3].astype(np.float64)
+        scale = np.abs(T["m"][:, :3].astype(np.float64)).max() * np.abs(pc).max(axis=1) + np.abs(T["m"][:, 3]).max()
+        # m is off by an ulp of its row's largest entry per entry (four entries per row); W_cur^-1 o W_cur is the identity only as
+        # far as the scene's own itm inverts tm, which its binary32 entries do to a few ulp per level (RTU_MAX_NODE_DEPTH + 1 levels)
+        print("node %d: m W_cur(x) - W_prev(x), worst in ulp of the scale: %.2f" % (i, (np.abs(back - pp).max(axis=1) / (ulp * scale)).max()))
+        assert (np.abs(back - pp).max(axis=1) <= (4 + 8 * 9) * ulp * scale).all(), "node %d: m W_cur(x) != W_prev(x)" % i
+
+
+def moved_cases(pkg, scene, rng):
+    """(what, edited scene) for several re-placements of `scene`: a single leaf, a group (its children move with it), everything."""
+    n = scene.desc.n_nodes
+    leaves = [i for i in range(1, n) if nodes(scene)[i].subtree_end == i + 1]
+    groups = [i for i in range(1, n) if nodes(scene)[i].subtree_end > i + 1]
+    cases = []
+    for which in ([leaves[0]], [leaves[-1], leaves[len(leaves) // 2]], groups[:1] or leaves[1:2], list(range(1, n))):
+        s = clone(pkg, scene)
+        replace_nodes(s, rng, which)
+        cases.append((which, s))
+    return cases
+
+
+@pytest.mark.parametrize("which", ["torus", "p11_p2_120x68"])
+def test_scene_motion(pkg, golden, tmp_path, which):
+    from test_gpu_scene_update import torus_scene
+    scene = torus_scene(pkg, tmp_path) if which == "torus" else golden(which).scene(pkg)
+    rng = np.random.default_rng(77)
+    n = scene.desc.n_nodes
+    # two equal scenes: all STATIC with identity bits
+    t = pkg.scene_motion(scene, clone(pkg, scene))
+    assert (t["flags"] == STATIC).all()
+    check_motion(pkg, scene, scene, t, rng)
+    prev = scene
+    seen_static = seen_moved = 0
+    for moved, cur in moved_cases(pkg, scene, rng):
+        t = pkg.scene_motion(prev, cur)
+        check_motion(pkg, prev, cur, t, rng)
+        assert not (t["flags"] & RESET).any()
+        seen_static += int((t["flags"] & STATIC != 0).sum())
+        seen_moved += int((t["flags"] & STATIC == 0).sum())
+        prev = cur  # the next case is measured against this one: both scenes away from the loader's
+    assert seen_static > 0 and seen_moved > 0
+    if which == "torus":  # node 1 is the group, node 2 its child, node 3 the other instance of the mesh, node 4 the floor
+        nd = nodes(scene)
+        assert nd[2].parent == 1 and nd[3].parent == nd[1].parent and nd[2].mesh_id == nd[3].mesh_id >= 0
+        cur = clone(pkg, scene)
+        cur.node_translate(1, (0.5, 0.0, 0.0))
+        t = pkg.scene_motion(scene, cur)
+        assert not t["flags"][1] & STATIC and not t["flags"][2] & STATIC, "a child of a moved group is not static"
+        assert t["flags"][3] == STATIC and t["flags"][4] == STATIC and t["flags"][0] == STATIC, "the untouched siblings are static"
+        assert np.allclose(t["m"][2][:, 3], [-0.5, 0, 0], atol=1e-5) and np.allclose(t["m"][2][:, :3], np.eye(3), atol=1e-6)
+        t = pkg.scene_motion(scene, cur, reset_meshes=[nd[2].mesh_id])
+        assert [int(f) for f in t["flags"]] == [STATIC, 0, RESET, STATIC | RESET, STATIC], "RESET on both instances of the mesh, and only there"
+    else:
+        mesh_of = [nodes(scene)[i].mesh_id for i in range(n)]
+        used = sorted({m for m in mesh_of if m >= 0})
+        t = pkg.scene_motion(scene, prev, reset_meshes=used[:1])
+        assert [(int(f) & RESET) != 0 for f in t["flags"]] == [m == used[0] for m in mesh_of]
+        # a deformed mesh (its reference tree rebuilt, of another size perhaps) is what RESET is for: taken as rtu_update_meshes takes it
+        now = deformed_scene(pkg, scene, used[0], ("wobble", 1))
+        t = pkg.scene_motion(scene, now, reset_meshes=used[:1])
+        assert [int(f) for f in t["flags"]] == [STATIC | RESET if m == used[0] else STATIC for m in mesh_of]
+    # the refusals
+    out = np.zeros(n, pkg.motion_dtype())
+    ids = (ctypes.c_uint32 * 2)(0, scene.desc.n_meshes)
+    call = pkg.hip.rtu_scene_motion
+    assert call(scene.desc_ptr, prev.desc_ptr, None, 0, out.ctypes.data) == pkg.RTU_OK
+    assert call(None, prev.desc_ptr, None, 0, out.ctypes.data) == pkg.RTU_ERR_ARG
+    assert call(scene.desc_ptr, None, None, 0, out.ctypes.data) == pkg.RTU_ERR_ARG
+    assert call(scene.desc_ptr, prev.desc_ptr, None, 0, None) == pkg.RTU_ERR_ARG
+    assert call(scene.desc_ptr, prev.desc_ptr, None, 1, out.ctypes.data) == pkg.RTU_ERR_ARG
+    assert call(scene.desc_ptr, prev.desc_ptr, ids, -1, out.ctypes.data) == pkg.RTU_ERR_ARG
+    assert call(scene.desc_ptr, prev.desc_ptr, ids, 2, out.ctypes.data) == pkg.RTU_ERR_ARG, "mesh id n_meshes is out of range"
+    assert call(scene.desc_ptr, prev.desc_ptr, ids, 1, out.ctypes.data) == pkg.RTU_OK
+    other = golden("p10_s4_160x120").scene(pkg)
+    assert call(scene.desc_ptr, other.desc_ptr, None, 0, out.ctypes.data) == pkg.RTU_ERR_SCENE_SHAPE
+    with pytest.raises(pkg.RtuError) as e:
+        pkg.scene_motion(scene, other)
+    assert e.value.code == pkg.RTU_ERR_SCENE_SHAPE
+
+
+# ---- 2. the accumulator against a numpy restatement -----------------------------------------------------------------------------------
+def np_moved(hits, motion, H, W):
+    """Per pixel: in_table, static, reset, Pm, Nm, fin (the non-static map's results are all finite) — the rules' binary32 operations."""
+    valid = (hits["flags"].reshape(H, W) & RTU_RAY_HIT) != 0
+    node = hits["node"].reshape(H, W)
+    Pp, Np = hits["p"].reshape(H, W, 3), hits["N"].reshape(H, W, 3)
+    n = len(motion)
+    in_table = valid & (node >= 0) & (node < n)
+    ident = np.zeros(1, motion.dtype)
+    ident["m"][0], ident["g"][0], ident["flags"][0] = np.eye(3, 4, dtype=F), np.eye(3, dtype=F), STATIC
+    tab = np.concatenate([motion, ident])
+    T = tab[np.where(in_table, node, n)]
+    static, reset = (T["flags"] & STATIC) != 0, (T["flags"] & RESET) != 0
+    with np.errstate(all="ignore"):
+        pm = np.stack([dot3(T["m"][..., r, :3], Pp) + T["m"][..., r, 3] for r in range(3)], axis=-1)
+        q = np.stack([dot3(T["g"][..., r, :], Np) for r in range(3)], axis=-1)
+        l = dot3(q, q)
+        nm = q / np.sqrt(l)[..., None]
+    assert pm.dtype == F and nm.dtype == F
+    fin = np.isfinite(pm).all(-1) & np.isfinite(nm).all(-1)
+    Pm = np.where(static[..., None], Pp, pm)
+    Nm = np.where(static[..., None], Np, nm)
+    return valid, in_table, static, reset, Pm, Nm, fin, np.isfinite(nm).all(-1)
+
+
+def np_project(prev_cam, Pm):
+    pos, origin, u, v = (v3(getattr(prev_cam, k)) for k in ("cam_pos", "origin", "u", "v"))
+    nrm = cross3(u, v)
+    num = dot3(origin - pos, nrm)
+    with np.errstate(all="ignore"):
+        D = Pm - pos
+        s = num / dot3(D, nrm)
+        Q = (pos + D * s[..., None]) - origin
+        fx = dot3(Q, u) / dot3(u, u) - F(0.5)
+        fy = dot3(Q, v) / dot3(v, v) - F(0.5)
+    assert fx.dtype == F and s.dtype == F
+    return np.isfinite(s) & (s > 0), fx, fy
+
+
+def np_temporal_motion(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc, motion, cap):
+    """The rules restated: (rgbz_out [H, W, 4], history [3, H, W, 4], counts of the branches taken)."""
+    H, W = rgbz.shape[:2]
+    c = rgbz[..., :3]
+    a = albedo.reshape(H, W, 4)[..., :3]
+    d = np.where(a > F(0.01), a, F(1.0))
+    Np, Pp = hits["N"].reshape(H, W, 3), hits["p"].reshape(H, W, 3)
+    t, node = hits["t"].reshape(H, W), hits["node"].reshape(H, W)
+    valid, in_table, static, reset, Pm, Nm, fin_m, fin_nm = np_moved(hits, motion, H, W)
+    normal_min, maxh = F(desc.normal_min), F(desc.max_history)
+    acc, nacc, wsum = np.zeros((H, W, 3), F), np.zeros((H, W), F), np.zeros((H, W), F)
+    ntaps = np.zeros((H, W), int)
+    yg, xg = np.mgrid[0:H, 0:W]
+    has_prev = hist_prev is not None
+    look = valid & in_table & ~reset & (static | fin_m) & has_prev
+    same = has_prev and same_camera(prev_cam, cur_cam)
+    one_tap = look & static & same
+    reproj = look & ~one_tap
+    with np.errstate(all="ignore"):
+        e_cur = c / d
+        plane_max = F(desc.sigma_plane) * t
+
+        def tap(qx, qy, w, mask):
+            nonlocal acc, nacc, wsum, ntaps
+            inside = mask & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+            cx, cy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+            Eq, Pq, Nq = hist_prev[0][cy, cx], hist_prev[1][cy, cx], hist_prev[2][cy, cx]
+            ok = inside & (Eq[..., 3] > 0) & (np.ascontiguousarray(Nq[..., 3]).view(np.int32) == node)
+            ok &= dot3(Nm, Nq[..., :3]) >= normal_min
+            ok &= np.abs(dot3(Nm, Pq[..., :3] - Pm)) <= plane_max
+            acc = np.where(ok[..., None], acc + Eq[..., :3] * w[..., None], acc)
+            nacc = np.where(ok, nacc + Eq[..., 3] * w, nacc)
+            wsum = np.where(ok, wsum + w, wsum)
+            ntaps += ok
+        looked = one_tap.copy()
+        if has_prev:
+            tap(xg, yg, np.ones((H, W), F), one_tap)
+            front, fx, fy = np_project(prev_cam, Pm)
+            looked4 = reproj & front & (fx >= F(-1.0)) & (fx < F(W)) & (fy >= F(-1.0)) & (fy < F(H))
+            flx, fly = np.floor(np.where(looked4, fx, F(0))), np.floor(np.where(looked4, fy, F(0)))
+            x0, y0 = flx.astype(int), fly.astype(int)
+            wx, wy = fx - flx, fy - fly
+            ux, uy = F(1.0) - wx, F(1.0) - wy
+            tap(x0, y0, ux * uy, looked4)
+            tap(x0 + 1, y0, wx * uy, looked4)
+            tap(x0, y0 + 1, ux * wy, looked4)
+            tap(x0 + 1, y0 + 1, wx * wy, looked4)
+            looked |= looked4
+        has = valid & (wsum > F(0.01))
+        e_prev = np.where(has[..., None], acc / wsum[..., None], F(0.0))
+        n_prev = np.where(has, nacc / wsum, F(0.0))
+        capf = F(cap)
+        capped = (capf > 0) & (n_prev > 0) & (capf < n_prev)
+        uncapped = (capf > 0) & (n_prev > 0) & ~capped
+        n_prev = np.where(capped, capf, n_prev)
+        fin = np.isfinite(c).all(axis=-1)
+        n_b = np.where(maxh < n_prev + F(1.0), maxh, n_prev + F(1.0))
+        e_b = e_prev + (e_cur - e_prev) * (F(1.0) / n_b)[..., None]
+        fresh = n_prev == 0
+        e = np.where(~fin[..., None], e_prev, np.where(fresh[..., None], e_cur, e_b))
+        n = np.where(~fin, n_prev, np.where(fresh, F(1.0), n_b))
+        passthrough = ~valid | (~fin & fresh)
+        out = rgbz.copy()
+        out[..., :3] = np.where(passthrough[..., None], c, e * d)
+    hist = np.zeros((3, H, W, 4), F)
+    keep = valid & ~(~fin & fresh)
+    hist[0][..., :3] = np.where(keep[..., None], e, F(0.0))
+    hist[0][..., 3] = np.where(keep, n, F(0.0))
+    hist[1][..., :3] = np.where(valid[..., None], Pp, F(0.0))
+    hist[1][..., 3] = np.where(valid, t, F(0.0))
+    hist[2][..., :3] = np.where(valid[..., None], Np, F(0.0))
+    hist[2][..., 3] = np.where(valid, node, -1).astype(np.int32).view(F)
+    assert out.dtype == F and e.dtype == F and n.dtype == F
+    mv = looked & ~static
+    counts = {"one_tap_same_cam": int(one_tap.sum()) if same else 0, "reproject_same_cam": int((looked & ~one_tap).sum()) if same else 0,
+              "moved_taps0": int((mv & (ntaps == 0)).sum()), "moved_taps1to3": int((mv & (ntaps >= 1) & (ntaps <= 3)).sum()),
+              "moved_taps4": int((mv & (ntaps == 4)).sum()), "reset": int((valid & in_table & reset).sum()) if has_prev else 0,
+              "out_of_table": int((valid & ~in_table).sum()) if has_prev else 0,
+              "nonfinite_Nm": int((valid & in_table & ~reset & ~static & ~fin_nm).sum()) if has_prev else 0,
+              "cap_applied": int((valid & capped).sum()), "cap_not_binding": int((valid & uncapped).sum())}
+    return out, hist, counts
+
+
+def table(kind, n=3):
+    """A table for the synthetic chains (node ids 1 and 2; 2 lies on both planes, whose common in-plane direction is y)."""
+    t = np.zeros(n, np.dtype([("m", F, (3, 4)), ("g", F, (3, 3)), ("flags", np.uint32), ("reserved", np.uint32, (2,))]))
+    t["m"], t["g"], t["flags"] = np.eye(3, 4, dtype=F), np.eye(3, dtype=F), STATIC
+    if kind == "static":
+        pass
+    elif kind == "slide":      # within its own planes: the taps land on the same surface at shifted pixels
+        t["flags"][2], t["m"][2][1, 3] = 0, 0.23
+    elif kind == "push":       # out of the plane: every tap is another surface
+        t["flags"][2], t["m"][2][2, 3] = 0, 1.0
+    elif kind == "rotscale":   # a rotation about the left plane's normal and a non-uniform scale: g is no rotation, Nm is normalised
+        c, s = math.cos(0.02), math.sin(0.02)
+        A = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]) @ np.diag([1.02, 0.97, 1.0])
+        t["flags"][2], t["m"][2][:, :3], t["g"][2] = 0, A, np.linalg.inv(A).T * 3.0  # (any positive multiple of g is the same map)
+    elif kind == "reset1":
+        t["flags"][1] = STATIC | RESET
+    elif kind == "zero_g":
+        t["flags"][2], t["g"][2] = 0, 0.0
+        t["flags"][1], t["m"][1][0, 3] = 0, np.nan
+    else:
+        raise ValueError(kind)
+    return t
+
+
+EQUAL = "equal cameras"
+# (table, entries, cameras, history_cap, desc overrides)
+CASES = [("static", 3, "X", 0, {"max_history": 3}), ("static", 3, "Y", 0, {}), ("slide", 3, "X", 0, {}), ("slide", 3, EQUAL, 3, {}),
+         ("push", 3, "X", 0, {}), ("rotscale", 3, "Y", 1, {}), ("rotscale", 3, EQUAL, 0, {"normal_min": 0.5}), ("reset1", 3, "X", 0, {}),
+         ("static", 2, "X", 3, {}), ("static", 0, EQUAL, 0, {}), ("zero_g", 3, "X", 0, {}), ("slide", 3, "X", 1, {"sigma_plane": 0.4, "normal_min": -1.0})]
+
+
+def case_cameras(pkg, W, H, name):
+    return [make_camera(pkg, W, H) for _ in range(FRAMES)] if name == EQUAL else chain_cameras(pkg, W, H)[name]
+
+
+def run_motion_chain(cams, frames, desc, motion, cap, form):
+    res, hist = [], None
+    for k in range(FRAMES):
+        r = form(cams[k - 1] if k else None, cams[k], *frames[k], hist, desc, motion, cap)
+        hist = r[1]
+        res.append(r)
+    return res
+
+
+def host_motion_form(pkg):
+    return lambda prev, cur, rgbz, hits, albedo, hist, desc, motion, cap: pkg.temporal_accumulate_motion(prev, cur, rgbz, hits, albedo, motion, hist, desc, cap)
+
+
+def assert_same(got, want, what):
+    for k in range(FRAMES):
+        for name, g, w in (("image", got[k][0], want[k][0]), ("history", got[k][1], want[k][1])):
+            diff = bits(g) != bits(w)
+            assert not diff.any(), "%s frame %d %s: %d words differ, first at %s" % (what, k, name, diff.sum(), np.argwhere(diff)[0])
+
+
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+def test_host_form_equals_the_numpy_restatement(pkg, size):
+    W, H = size
+    total = {}
+    for ci, (kind, n, camname, cap, over) in enumerate(CASES):
+        cams = case_cameras(pkg, W, H, camname)
+        frames = chain_inputs(pkg, W, H, 1234 + ci)
+        desc = pkg.temporal_desc(W, H, **over)
+        motion = table(kind)[:n]
+        got = run_motion_chain(cams, frames, desc, motion, cap, host_motion_form(pkg))
+        want = run_motion_chain(cams, frames, desc, motion, cap, np_temporal_motion)
+        what = "table %s[%d] cameras %s cap %d %s" % (kind, n, camname, cap, over)
+        assert_same(got, want, what)
+        for k in range(FRAMES):
+            rgbz, hits = frames[k][0], frames[k][1]
+            invalid = ((hits["flags"] & RTU_RAY_HIT) == 0).reshape(H, W)
+            assert np.array_equal(bits(got[k][0])[invalid], bits(rgbz)[invalid]), "an invalid pixel was changed"
+            assert np.array_equal(bits(got[k][0][..., 3]), bits(rgbz[..., 3])), "z was changed"
+            for key, v in want[k][2].items():
+                total[key] = total.get(key, 0) + v
+        if kind == "static" and n == 3 and cap == 0:  # the consequence: the bits of the plain accumulator (and of its restatement)
+            for form in (lambda p, c, r, h, a, hi, d, m, cp: pkg.temporal_accumulate(p, c, r, h, a, hi, d),
+                         lambda p, c, r, h, a, hi, d, m, cp: np_temporal(p, c, r, h, a, hi, d)):
+                assert_same(got, run_motion_chain(cams, frames, desc, motion, cap, form), what + " against the plain form")
+        node = frames[-1][1]["node"].reshape(H, W)
+        nlast = got[-1][1][0][..., 3]
+        if kind == "push" and size == (67, 35):
+            assert (nlast[node == 2] <= 1).all() and (nlast[node == 1] > 1).any(), "a pushed node found history, or nothing else did"
+        if kind == "reset1":
+            assert (nlast[node == 1] <= 1).all() and (size != (67, 35) or (nlast[node == 2] > 1).any())
+        if n == 0:
+            assert (nlast <= 1).all()
+        if cap == 1 and size == (67, 35):
+            assert nlast.max() == 2, "history_cap 1: a pixel never has more than two samples"
+    print(size, total)
+    if size == (67, 35):  # every branch of the rules occurs
+        for key in ("one_tap_same_cam", "reproject_same_cam", "moved_taps0", "moved_taps1to3", "moved_taps4", "reset", "out_of_table", "nonfinite_Nm",
+                    "cap_applied", "cap_not_binding"):
+            assert total[key] > 0, "no pixel took the branch %r: %s" % (key, total)
+
+
+def test_in_place_and_refusals(pkg):
+    W, H = 67, 35
+    cams = chain_cameras(pkg, W, H)["X"]
+    frames = chain_inputs(pkg, W, H, 5)
+    d = pkg.temporal_desc(W, H)
+    motion = table("slide")
+    res = run_motion_chain(cams, frames, d, motion, 3, host_motion_form(pkg))
+    rgbz, hits, albedo = frames[3]
+    prev_hist = np.ascontiguousarray(res[2][1])
+    buf, hist = rgbz.copy(), np.empty((3, H, W, 4), F)
+
+    def call(desc=d, prev=cams[2], cur=cams[3], hp=prev_hist.ctypes.data, ho=None, m=motion, n=3, cap=3):
+        return pkg.hip.rtu_temporal_accumulate_motion(ctypes.byref(desc), ctypes.byref(prev) if prev is not None else None, ctypes.byref(cur),
+                                                      buf.ctypes.data, hits.ctypes.data, albedo.ctypes.data, hp, ho if ho is not None else hist.ctypes.data,
+                                                      buf.ctypes.data, m.ctypes.data if m is not None else None, n, cap)
+    assert call() == pkg.RTU_OK                       # rgbz_out == rgbz
+    assert np.array_equal(bits(buf), bits(res[3][0])) and np.array_equal(bits(hist), bits(res[3][1]))
+    buf[:] = rgbz
+    assert call(ho=prev_hist.ctypes.data) == pkg.RTU_ERR_ARG, "aliased histories"
+    assert call(m=None) == pkg.RTU_ERR_ARG
+    for cap in (-1, 65536, 1 << 20):
+        assert call(cap=cap) == pkg.RTU_ERR_ARG
+    assert call(cap=65535) == pkg.RTU_OK and call(cap=0) == pkg.RTU_OK
+    buf[:] = rgbz
+    for field, value in (("flags", 4), ("flags", STATIC | 8), ("reserved", (1, 0)), ("reserved", (0, 7))):
+        bad = motion.copy()
+        bad[field][2] = value
+        assert call(m=bad) == pkg.RTU_ERR_ARG, (field, value)
+        assert call(m=bad, n=2) == pkg.RTU_OK, "an entry beyond n_nodes is not read"
+        buf[:] = rgbz
+    bd = pkg.temporal_desc(W, H, max_history=0)
+    assert call(desc=bd) == pkg.RTU_ERR_ARG
+    assert call(prev=None) == pkg.RTU_ERR_ARG and call(prev=None, hp=None) == pkg.RTU_OK
+    assert call(prev=make_camera(pkg, W + 1, H)) == pkg.RTU_ERR_ARG
+    with pytest.raises(pkg.RtuError):
+        pkg.temporal_accumulate_motion(cams[2], cams[3], rgbz, hits, albedo, motion, prev_hist, d, history_cap=-2)
+    mvc = lambda m, n, prev=cams[2], out=buf: pkg.hip.rtu_motion_vectors(ctypes.byref(d), ctypes.byref(prev) if prev is not None else None, hits.ctypes.data,
+                                                                        m.ctypes.data if m is not None else None, n, out.ctypes.data if out is not None else None)
+    assert mvc(motion, 3) == pkg.RTU_OK and mvc(None, 3) == pkg.RTU_ERR_ARG and mvc(motion, 3, prev=None) == pkg.RTU_ERR_ARG
+    assert mvc(motion, 3, out=None) == pkg.RTU_ERR_ARG and mvc(motion, 3, prev=make_camera(pkg, W, H + 1)) == pkg.RTU_ERR_ARG
+    bad = motion.copy()
+    bad["flags"][0] = 16
+    assert mvc(bad, 3) == pkg.RTU_ERR_ARG
+
+
+# ---- 3. motion vectors ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+def test_motion_vectors_equal_the_restatement(pkg, size):
+    W, H = size
+    given = 0
+    for ci, (kind, n, camname, cap, over) in enumerate(CASES):
+        cams = case_cameras(pkg, W, H, camname)
+        frames = chain_inputs(pkg, W, H, 1234 + ci)
+        motion = table(kind)[:n]
+        for k in range(1, FRAMES):
+            hits = frames[k][1]
+            got = pkg.motion_vectors(cams[k - 1], hits, motion, W, H)
+            valid, in_table, static, reset, Pm, Nm, fin_m, fin_nm = np_moved(hits, motion, H, W)
+            front, fx, fy = np_project(cams[k - 1], Pm)
+            ok = in_table & ~reset & np.isfinite(Pm).all(-1) & front
+            want = np.zeros((H, W, 4), F)
+            want[..., 0], want[..., 1], want[..., 2] = np.where(ok, fx, F(0)), np.where(ok, fy, F(0)), np.where(ok, F(1), F(0))
+            diff = bits(got) != bits(want)
+            assert not diff.any(), "table %s[%d] cameras %s frame %d: %d words differ, first at %s" % (kind, n, camname, k, diff.sum(), np.argwhere(diff)[0])
+            given += int(ok.sum())
+            if camname == EQUAL and kind == "static" and n == 3:  # nothing moved: a pixel's own coordinates, to the rounding of the projection
+                yg, xg = np.mgrid[0:H, 0:W]
+                m1 = ok & (hits["p"].reshape(H, W, 3)[..., 2] == F(-5.0))  # (the points on the image plane of make_camera)
+                assert np.abs(got[..., 0] - xg)[m1].max() < 1e-3 and np.abs(got[..., 1] - yg)[m1].max() < 1e-3
+            if camname == EQUAL and kind == "slide":
+                yg, xg = np.mgrid[0:H, 0:W]
+                m2 = ok & (hits["node"].reshape(H, W) == 2) & (hits["p"].reshape(H, W, 3)[..., 2] == F(-5.0))
+                if m2.any():  # 0.23 in y at 0.1 per pixel
+                    assert np.abs(got[..., 1] - yg - 2.3)[m2].max() < 1e-3 and np.abs(got[..., 0] - xg)[m2].max() < 1e-3
+    assert given > 0
+
+
+# ---- 4. quality, on the oracle alone ------------------------------------------------------------------------------------------------
+MOVE_FRAMES = 8
+MOVE_STEP = 0.3
+TEAPOT = 7
+
+# RMSE in linear rgb of the last of eight frames against 256 spp of the last scene, p11_p2_120x68, the camera at rest, node 7 (the
+# teapot) translated 0.3 in x per frame, the defaults. Ratios to the raw last sample — what a plain session shows after every update:
+#                                  node 7's pixels    the whole image
+#   raw last sample (RMSE)         0.01743            0.02398
+#   accumulated, history_cap 0     0.386              0.363
+#   accumulated, history_cap 4     0.407              0.375
+#   cap 0, then rtu_denoise        0.303              0.218
+#   cap 4, then rtu_denoise        0.304              0.218
+# 97.8 % of the 584 pixels that show node 7 in the last frame end with n >= 2 (mean n 7.74 of 8; the whole image 7.91, 4.97 with cap 4).
+# Every ratio on the moved node is below 1. The mean of eight independent samples would give 8^-1/2 = 0.354: the whole image is at
+# 0.363 with the camera at rest (one tap, no resampling blur, which is what takes the orbit of test_temporal_host.py to 0.287).
+# The bounds are those ratios times 1.25, rounded up to two digits; the margin covers nothing but a changed sample stream.
+BOUNDS = {("acc", 0, "node"): 0.49, ("acc", 0, "all"): 0.46, ("acc", 4, "node"): 0.51, ("acc", 4, "all"): 0.47,
+          ("dn", 0, "node"): 0.38, ("dn", 0, "all"): 0.28, ("dn", 4, "node"): 0.38, ("dn", 4, "all"): 0.28}
+
+
+def test_quality_on_the_oracle(pkg, orc, golden):
+    g = golden("p11_p2_120x68")
+    scene = g.scene(pkg)
+    W, H = g.width, g.height
+    assert nodes(scene)[TEAPOT].mesh_id >= 0
+    desc = pkg.temporal_desc(W, H)
+    frame = pkg.frame_setup(scene.desc.camera, W, H, samples=16, gather_bounces=4)
+    state = {0: [None, None], 4: [None, None]}  # history_cap -> [image, history]
+    prev_scene = None
+    for k in range(MOVE_FRAMES):
+        s = clone(pkg, scene)
+        s.node_translate(TEAPOT, (MOVE_STEP * k, 0.0, 0.0))
+        sample = orc.sample_images(s, W, H, 16, k, 1, gi=True, threads=8)[0]
+        hits, albedo = oracle_guides(pkg, orc, s, W, H)
+        motion = pkg.scene_motion(prev_scene if k else s, s)
+        assert [int(f) for f in motion["flags"]] == [0 if (k and i == TEAPOT) else STATIC for i in range(s.desc.n_nodes)]
+        for cap, st in state.items():
+            st[0], st[1] = pkg.temporal_accumulate_motion(frame if k else None, frame, sample, hits, albedo, motion, st[1], desc, cap)
+        prev_scene = s
+    on_node = ((hits["flags"] & RTU_RAY_HIT) != 0).reshape(H, W) & (hits["node"].reshape(H, W) == TEAPOT)
+    n = state[0][1][0][..., 3]
+    share = float((n[on_node] >= 2).mean())
+    print("node %d moved %d x %.2f: %d pixels show it, %.1f %% of them have n >= 2 (mean n %.2f); whole image mean n %.2f, with cap 4 %.2f"
+          % (TEAPOT, MOVE_FRAMES, MOVE_STEP, on_node.sum(), 100 * share, n[on_node].mean(), n.mean(), state[4][1][0][..., 3].mean()))
+    assert on_node.sum() > 300
+    assert share >= 0.8, "the step is too large for this test: a condition on its input"
+    assert state[4][1][0][..., 3].max() <= 5
+    ref = orc.render_paths(s, W, H, 256, threads=8)[0]
+
+    def rmse(img, mask):
+        d2 = (img[..., :3].astype(np.float64) - ref[..., :3].astype(np.float64)) ** 2
+        return float(np.sqrt(np.mean(d2[mask])))
+    masks = {"node": on_node, "all": np.ones((H, W), bool)}
+    raw = {w: rmse(sample, m) for w, m in masks.items()}
+    print("RMSE of the raw last sample: node %.5f, all %.5f" % (raw["node"], raw["all"]))
+    ratios = {}
+    for cap, st in state.items():
+        dn = pkg.denoise(st[0], hits, albedo)
+        for w, m in masks.items():
+            ratios[("acc", cap, w)] = rmse(st[0], m) / raw[w]
+            ratios[("dn", cap, w)] = rmse(dn, m) / raw[w]
+    for key in sorted(ratios):
+        print("ratio %s: %.4f" % (key, ratios[key]))
+    for key, r in ratios.items():
+        assert r < BOUNDS[key], "%s: RMSE ratio %.3f, bound %.2f" % (key, r, BOUNDS[key])
