@@ -892,10 +892,12 @@ int  rtu_debug_node_bounds(RtuContext* ctx, int on);
 
 /* Experiment switches for performance work (which part of a kernel costs what): bits are defined next to their use in
  * render_impl.h; bits 0..7 render WRONG images: never set them in production paths or tests of results. Five bits only switch an
- * optimisation off and leave every result bit alone (tests compare the images with and without): 256 = no tile occupancy
+ * optimisation off and leave every result bit alone (tests compare the images with and without; 4096 below is a sixth): 256 = no tile occupancy
  * (k_primary tests every tile against the node rectangles and coverage masks itself), 512 = no stage-2 grid hints (both
  * stage-2 kernels of every tracing phase are launched at full size), 64 = the occluder lists of shadow rays only say "empty cell or
  * not" (every listed ray walks the BVH), 2048 = no Shade() call is settled without a frame record (every hit becomes a frame),
+ * 4096 = a plane hit's normal through every transformation of its chain, as the reference writes it, instead of from the node's
+ * table (csrc/rtu_device.h DevNode::plane_n),
  * 8192 = no side mode (stage 2 of the primary phase in the launch stream, before the recursion levels, instead of beside them),
  * 16384 = both stage-2 kernels of every phase are launched whatever the last launch's list lengths said (outside side mode).
  * 131072 (a wrong image; frames with collect_stats == 2 only) = stage 2 of the primary phase writes the work of each ray's BVH walk — two

@@ -336,6 +336,30 @@ int rtu_launch_progressive_snapshot(const float4* acc, const uint32_t* hits, con
     return (int)hipGetLastError();
 }
 
+// DevNode::plane_n: one thread per node. The expressions are the pixels' own — from_node for the node and each ancestor in trace()'s
+// order — in this translation unit's binary32 arithmetic, which is every render kernel's (the Makefile's flags): IEEE operations in a
+// fixed order have one result. The plane's own normal (0, 0, +-1) arrives as kernel arguments (zero = 0, one = 1), as a value the
+// compiler does not know: every operation is then executed by the instruction a pixel would execute it with, whatever a folded
+// constant would make of a NaN's payload.
+__global__ void __launch_bounds__(64) k_plane_normals(DevNode* nodes, uint32_t n_nodes, float zero, float one) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n_nodes || nodes[i].obj_type != RTU_OBJ_PLANE) return;
+    for (int side = 0; side < 2; side++) {
+        Hit h;
+        fresh_hit(h, RTU_BIGFLOAT);
+        h.N = mk3(zero, zero, side == 0 ? one : -one);  // plane_hit: front, back
+        for (int j = (int)i; j >= 0; j = nodes[j].parent) from_node(nodes[j], h);
+        nodes[i].plane_n[side][0] = h.N.x;
+        nodes[i].plane_n[side][1] = h.N.y;
+        nodes[i].plane_n[side][2] = h.N.z;
+    }
+}
+int rtu_launch_plane_normals(DevNode* nodes, uint32_t n_nodes, hipStream_t stream) {
+    if (n_nodes == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_plane_normals, dim3((n_nodes + 63u) / 64u), dim3(64), 0, stream, nodes, n_nodes, 0.0f, 1.0f);
+    return (int)hipGetLastError();
+}
+
 int rtu_launch_selftest_fdiv(unsigned long long n_pairs, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t stream) {
     hipLaunchKernelGGL(k_selftest_fdiv, dim3(4096), dim3(256), 0, stream, n_pairs, seed, d_mismatches);
     return (int)hipGetLastError();

@@ -1968,6 +1968,10 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
     if ((rc = place_upload(ctx, P_NODES, nodes.data(), nodes.size(), &ds.nodes)) != RTU_OK) return rc;
     if ((rc = place_upload(ctx, P_MATERIALS, s->materials, (size_t)s->n_materials, &ds.materials)) != RTU_OK) return rc;
     if ((rc = place_upload(ctx, P_LIGHTS, s->lights, (size_t)s->n_lights, &ds.lights)) != RTU_OK) return rc;
+    // the world normals of the plane nodes (DevNode::plane_n), by the kernels' own code on the nodes just placed; a caller's stream
+    // may read them next (ray queries)
+    RTU_HIP(ctx, (hipError_t)rtu_launch_plane_normals(const_cast<DevNode*>(ds.nodes), s->n_nodes, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ds.textured) {
         if (s->material_maps)
             if ((rc = place_upload(ctx, P_MATMAPS, s->material_maps, (size_t)s->n_materials * 4, &ds.mat_maps)) != RTU_OK) return rc;

@@ -111,6 +111,9 @@ struct DevMesh {
     float    scale;             // largest |coordinate| of the mesh's bounding box (cull margin, rtu_intersect.h)
 };
 
+// rtu_debug_flags 4096: a plane hit's normal through every transformation of its chain, as the reference writes it, instead of
+// DevNode::plane_n (rtu_render.h). Results must not change.
+#define RTU_DBG_LITERAL_NORMALS 4096u
 #define RTU_MAX_PCOVER 8      // plane nodes that get a coverage mask for primary rays
 struct DevNode {                // one scene-graph node (wave-uniform data)
     float   tm[9], itm[9], pos[3];
@@ -122,6 +125,11 @@ struct DevNode {                // one scene-graph node (wave-uniform data)
     // the margin of rtu_intersect.h "Culling" cannot pass the reference's own box test of this object, so the node is
     // skipped before its transformation and exact test — which still decide every result bit of the rays that remain.
     float   wmin[3], wmax[3];
+    // PLANE NORMALS (fast variant only; RTU_OBJ_PLANE nodes): the world-space normal of a hit on the front ([0]) and on the back ([1]) of
+    // the unit square — the epilogue of trace() (rtu_intersect.h) applied to (0, 0, 1) and (0, 0, -1): it depends on the node's chain and
+    // on the side alone. Written on the device by the epilogue's own code (k_plane_normals), so the bits are the per-hit ones,
+    // non-finite chains included.
+    float   plane_n[2][3];
 };
 
 // OCCLUDER LISTS of one (non-ambient light, mesh node) pair, made at upload (rtu_capi.hip: build_light_lists): the mesh seen from the
@@ -440,6 +448,8 @@ int rtu_launch_pack_image(const float4* rgbz, unsigned long long pixels, float* 
 int rtu_launch_minmax_z(const float4* rgbz, uint32_t pixels_per_frame, uint32_t frames, long long* minmax, hipStream_t stream);
 int rtu_launch_pack_output(const float4* rgbz, uint32_t pixels_per_frame, uint32_t frames, const long long* minmax, unsigned char* out, hipStream_t stream);
 
+// DevNode::plane_n of every plane node, after every placement of the nodes.
+int rtu_launch_plane_normals(DevNode* nodes, uint32_t n_nodes, hipStream_t stream);
 int rtu_launch_selftest_prims(unsigned long long n_rays, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t stream);
 int rtu_launch_selftest_fdiv(unsigned long long n_pairs, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t stream);
 int rtu_launch_debug_texcoords(const DevScene& s, int op, const DevTexture* tex, const RtuTexMap* map, const float* in, float* out,

@@ -67,6 +67,11 @@ __device__ __forceinline__ void from_node(const NodeT& n, Hit& h) {
     h.p = mat_mul(n.tm, h.p) + ld3(n.pos);
     h.N = norm3(mat_tmul(n.itm, h.N));
 }
+// ... the point alone (the normal of a plane hit comes from DevNode::plane_n, see trace)
+template <class NodeT>
+__device__ __forceinline__ void from_node_p(const NodeT& n, Hit& h) {
+    h.p = mat_mul(n.tm, h.p) + ld3(n.pos);
+}
 
 // ---------------------------------------------------------------------------
 // Slab interval of Box::IntersectRay / BVHBoxIntersection (objFunctions.cpp:143-254,
@@ -1358,10 +1363,17 @@ __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool sha
         h.p = lp;
         h.N = lN;
         const DevNode* gn = s.nodes;  // per-lane node index: ordinary loads
+        // A PLANE's normal is (0, 0, +-1) by the side hit (plane_hit), so what the loop below makes of it is a constant of the node
+        // and the side: DevNode::plane_n, computed at upload by this loop's own code (k_plane_normals) — the same operations on
+        // the same operands, the same bits. The fast variant reads it and transforms h.p alone; the counting variant keeps the
+        // literal loop, and every test that compares the two checks the table.
+        const bool tabled = CULL && !(s.dbg & RTU_DBG_LITERAL_NORMALS) && gn[best].obj_type == RTU_OBJ_PLANE;
         for (int j = best; j >= 0; j = gn[j].parent) {
             RTU_TOUCH(t_xform, 1);
-            from_node(gn[j], h);
+            if (tabled) from_node_p(gn[j], h);
+            else from_node(gn[j], h);
         }
+        if (tabled) h.N = ld3(gn[best].plane_n[h.front ? 0 : 1]);
     }
     return any;
 }

@@ -10,7 +10,7 @@ feat = sys.argv[1] if len(sys.argv) > 1 else "4"
 stack = sys.argv[2] if len(sys.argv) > 2 else "32"
 repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pkg = os.path.join(repo, "raytracer-utah_amd")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-ffp-contract=off", "-fPIC",
+cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC",
        "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero", "-I" + os.path.join(repo, "include"),
        "-I" + os.path.join(pkg, "csrc"), "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null",
        os.path.join(pkg, "csrc", ("render_feat%s.hip" if feat.isdigit() else "%s.hip") % feat)] + os.environ.get("RTU_EXTRA", "").split()
