@@ -818,6 +818,94 @@ int  rtu_temporal_frame_moved_device(RtuTemporal* t, const RtuFrameDesc* frame, 
 int  rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
                               float* h_rgbz);
 
+/* ---- Variance-guided filtering: the filter steered by per-pixel variance from temporal moments (rtu_variance.h, rtu_variance.hip) ----
+ * The history gets a fourth plane with the first and second moment of the sample's luminance; out of it comes the variance of the
+ * accumulated mean per pixel, and that variance sets the colour edge-stop of every a-trous pass: a pixel with a long history is left
+ * nearly alone, a disoccluded one is filtered hard. Binary32, one rounding per operation, no contraction, IEEE divisions, in this
+ * order — host and device forms give the same bits. dot, d, e, VALID, k as in "Denoising" and "Temporal accumulation";
+ * l(e) = (0.2126f e.r + 0.7152f e.g) + 0.0722f e.b.
+ *
+ * 1. MOMENTS  rtu_temporal_accumulate_moments is rtu_temporal_accumulate_motion on a MOMENTS HISTORY: four planes E, P, N, M of
+ *   width * height float4 each, 64 B per pixel, M = {m1, m2, 0, 0}. rgbz_out and the planes E, P, N are the motion form's bit for
+ *   bit. With l = l(e_cur) and l2 = l * l:
+ *     an ACCEPTED tap adds M_q.x * w to m1acc and M_q.y * w to m2acc, in the taps' order; wsum > 0.01f: m1_prev = m1acc / wsum,
+ *     m2_prev = m2acc / wsum; otherwise both 0.
+ *     the sample is not accumulated (c not finite), or l2 is not finite (l or l * l overflowed: THE MOMENTS SKIP THIS SAMPLE, while E
+ *     and n take it): m = m_prev — zeros for a fresh pixel.
+ *     else n_prev == 0: m1 = l, m2 = l2.
+ *     else m1 = m1_prev + (l - m1_prev) * A, m2 = m2_prev + (l2 - m2_prev) * A with the A of the blend.
+ *     M = {m1, m2, 0, 0} where E is written (the pixel is valid and has an accumulated colour), zeros elsewhere.
+ *   So M.xy are the bits that E.xy of rtu_temporal_accumulate_motion has when it is fed the image {l, l2, 0, z} with albedo {1, 1, 1, 0},
+ *   wherever both images are finite in the same pixels. hist_out (64 B per pixel) must not overlap hist_prev. Errors as for the
+ *   motion form.
+ *
+ * 2. VARIANCE  rtu_variance: one float per pixel out of a moments history and the RtuRayHit of its frame. With n = E_p.n:
+ *     v = 0 unless p is valid and n > 0.
+ *     x = m2 - m1 * m1;  vt = x > 0 ? x : 0 (a NaN gives 0).
+ *     n >= min_history: var = vt.
+ *     n <  min_history: rp = 1 / (sigma_plane * H_p.t). Over the taps q = p + (dx, dy), dy outer, dx inner, both -3 .. 3, that lie in
+ *       the image, are valid and have E_q.n > 0 (p is one of them):
+ *         dot = dot(Np, Nq);  t = dot > 0 ? dot : 0, then t = t * t repeated normal_log2_power times
+ *         x = dot(Np, Pq - Pp) * rp;  wp = 1 / (1 + x * x);  w = t * wp
+ *         s1 = s1 + M_q.x * w;  s2 = s2 + M_q.y * w;  ws = ws + w
+ *       ws > 0: a1 = s1 / ws, a2 = s2 / ws, x = a2 - a1 * a1, vs = x > 0 ? x : 0; otherwise vs = 0 (no usable tap: a zero or NaN
+ *       normal). var = (vs > vt ? vs : vt) * ((float)min_history / n).
+ *     v = var / n.
+ *
+ * 3. THE FILTER  rtu_denoise_variance: n_passes passes at steps 1, 2, 4, ... on e = c / d as in "Denoising", each pixel carrying its
+ *   variance v (the caller's, for every pixel) with it. Per valid pixel p and pass, sl2 = sigma_lum * sigma_lum:
+ *     g = sum of v_q * k3 / sum of k3 over q = p + (dx, dy), dy outer, dx inner, both -1 .. 1 (distance 1 whatever the step), q in
+ *       the image and valid; k3 = {1/4, 1/2, 1/4}[dy + 1] * {1/4, 1/2, 1/4}[dx + 1]; both sums in that order, then one division.
+ *     r = 1 / (sl2 * g + 1e-8f);  lp = l(e_p);  rp = 1 / (sigma_plane * H_p.t) (made once, before the first pass)
+ *     the 25 taps of "Denoising", in its order and with its skips:
+ *       t as above;  x = dot(Np, Pq - Pp) * rp;  wp = 1 / (1 + x * x);  dl = l(e_q) - lp;  wc = 1 / (1 + (dl * dl) * r)
+ *       w = (h * (t * wp)) * wc;  per channel acc = acc + e_q * w;  vacc = vacc + v_q * (w * w);  wsum = wsum + w
+ *     wsum > 0: e_p = acc / wsum and, with ws2 = wsum * wsum, v_p = ws2 > 0 ? vacc / ws2 : v_p; otherwise both stay.
+ *   Every tap reads the PREVIOUS pass's e and v. There is no halving of a sigma: the variance that shrinks from pass to pass tightens
+ *   the later passes. Two divisions per tap. Output as in "Denoising": rgb = e * d for a valid pixel, the input rgb bit for bit for
+ *   any other, z always the input z bit for bit.
+ *
+ * RTU_ERR_ARG: a NULL pointer, width or height outside 1 .. 65536 or more than 2^26 pixels, n_passes outside 1 .. 8, normal_log2_power
+ * outside 0 .. 7, a sigma that is not > 0, min_history outside 1 .. 65535, a non-zero reserved word, a device pointer that is not
+ * 16-byte aligned (d_v: 4-byte). The host forms are pure host code, no GPU and no context: the executable statement of the rules. The
+ * _device forms give the same bits from device memory, asynchronous on hip_stream: rtu_temporal_accumulate_moments_device
+ * (k_temporal_moments) and rtu_variance_device (k_variance) allocate nothing, need no scene and touch no state of the context;
+ * rtu_denoise_variance_device uses the four grow-only planes of rtu_denoise_device (64 B per pixel, one stream per context, no
+ * allocation once a frame of that size has been filtered by either), d_out == d_in is allowed.
+ *
+ * THE SESSION  rtu_temporal_begin_variance opens an RtuTemporal whose frames, plain and moved, are those of "Temporal accumulation"
+ * except that step 3 uses the moments form — a plain frame with an all-STATIC table of the uploaded scene's nodes and history_cap 0,
+ * which gives the plain form's E, P, N — and step 4 is rtu_variance_device of the new history, then rtu_denoise_variance_device on
+ * d_rgbz, in place. The history stays unfiltered. variance_desc: its width and height are ignored, the session's are used.
+ * RTU_TEMPORAL_DENOISE in temporal_desc is RTU_ERR_ARG here. Two moments histories, the variance and the table belong to the session
+ * (248 B per pixel in all); everything else — rtu_temporal_history_device, rtu_temporal_reset, rtu_temporal_free, ownership, one
+ * stream per context, no allocation after the first frame (the first moved frame, for the staging memory) — as for any session.
+ * Not done here: filtered colour is not fed back into the history, fireflies are not clamped, progressive sessions hold no second
+ * moment, sharded frames are refused. Measured error ratios are in DESIGN.md section 25. */
+typedef struct RtuVarianceDesc {   /* 40 B */
+    int32_t  width, height;
+    int32_t  n_passes;             /* 1 .. 8 */
+    float    sigma_lum;            /* > 0: the colour edge-stop in standard deviations of the pixel's luminance */
+    float    sigma_plane;          /* > 0 */
+    int32_t  normal_log2_power;    /* 0 .. 7 */
+    int32_t  min_history;          /* 1 .. 65535: below it the variance is estimated over the 7 x 7 neighbourhood */
+    uint32_t reserved[3];          /* must be 0 */
+} RtuVarianceDesc;
+int  rtu_variance_defaults(RtuVarianceDesc* out);   /* width, height 0; n_passes 3, sigma_lum 2, sigma_plane 0.05, normal_log2_power 5, min_history 4 */
+int  rtu_temporal_accumulate_moments(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                     const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
+                                     const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap);
+int  rtu_temporal_accumulate_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                            const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                            void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream);
+int  rtu_variance(const RtuVarianceDesc* desc, const float* h_hist, const RtuRayHit* h_hits, float* h_v);
+int  rtu_variance_device(RtuContext* ctx, const RtuVarianceDesc* desc, const void* d_hist, const void* d_hits, void* d_v, void* hip_stream);
+int  rtu_denoise_variance(const RtuVarianceDesc* desc, const float* h_rgbz_in, const RtuRayHit* h_hits, const float* h_albedo, const float* h_v,
+                          float* h_rgbz_out);
+int  rtu_denoise_variance_device(RtuContext* ctx, const RtuVarianceDesc* desc, const void* d_in, const void* d_hits, const void* d_albedo,
+                                 const void* d_v, void* d_out, void* hip_stream);
+RtuTemporal* rtu_temporal_begin_variance(RtuContext* ctx, const RtuTemporalDesc* temporal_desc, const RtuVarianceDesc* variance_desc, int* err_out);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

@@ -166,7 +166,9 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_camera_sample_rays_device", "rtu_temporal_defaults", "rtu_temporal_accumulate", "rtu_temporal_accumulate_device",
                "rtu_temporal_begin", "rtu_temporal_frame_device", "rtu_temporal_frame", "rtu_temporal_history_device", "rtu_temporal_reset",
                "rtu_temporal_free", "rtu_scene_motion", "rtu_temporal_accumulate_motion", "rtu_temporal_accumulate_motion_device",
-               "rtu_motion_vectors", "rtu_motion_vectors_device", "rtu_temporal_frame_moved_device", "rtu_temporal_frame_moved"]
+               "rtu_motion_vectors", "rtu_motion_vectors_device", "rtu_temporal_frame_moved_device", "rtu_temporal_frame_moved",
+               "rtu_variance_defaults", "rtu_temporal_accumulate_moments", "rtu_temporal_accumulate_moments_device", "rtu_variance",
+               "rtu_variance_device", "rtu_denoise_variance", "rtu_denoise_variance_device", "rtu_temporal_begin_variance"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -555,6 +557,119 @@ def denoise(rgbz, hits, albedo, desc=None):
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_denoise: an empty image or a descriptor outside its rules (n_passes 1..8, sigmas > 0, "
                            "normal_log2_power 0..7, reserved words 0)")
+    return out
+
+
+# variance-guided filtering (include/rtu_render.h, "Variance-guided filtering")
+class RtuVarianceDesc(ctypes.Structure):
+    """include/rtu_render.h RtuVarianceDesc (40 bytes): the size of the image, the constants of the variance and of its filter."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_passes", ctypes.c_int32), ("sigma_lum", ctypes.c_float),
+                ("sigma_plane", ctypes.c_float), ("normal_log2_power", ctypes.c_int32), ("min_history", ctypes.c_int32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
+_sig(hip, "rtu_variance_defaults", _I, ctypes.POINTER(RtuVarianceDesc))
+_sig(hip, "rtu_temporal_accumulate_moments", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+     _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32)
+_sig(hip, "rtu_temporal_accumulate_moments_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+     _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32, _P)
+_sig(hip, "rtu_variance", _I, ctypes.POINTER(RtuVarianceDesc), _P, _P, _P)
+_sig(hip, "rtu_variance_device", _I, _P, ctypes.POINTER(RtuVarianceDesc), _P, _P, _P, _P)
+_sig(hip, "rtu_denoise_variance", _I, ctypes.POINTER(RtuVarianceDesc), _P, _P, _P, _P, _P)
+_sig(hip, "rtu_denoise_variance_device", _I, _P, ctypes.POINTER(RtuVarianceDesc), _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_begin_variance", _P, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuVarianceDesc), ctypes.POINTER(_I))
+
+
+def variance_desc(width=0, height=0, **overrides):
+    """An RtuVarianceDesc: rtu_variance_defaults (n_passes 3, sigma_lum 2, sigma_plane 0.05, normal_log2_power 5, min_history 4), the
+    size, then `overrides`."""
+    d = RtuVarianceDesc()
+    hip.rtu_variance_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def _sized_variance_desc(desc, W, H):
+    d = RtuVarianceDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else variance_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    return d
+
+
+def temporal_accumulate_moments(prev_cam, cur_cam, rgbz, hits, albedo, motion, hist_prev=None, desc=None, history_cap=0):
+    """rtu_temporal_accumulate_moments (pure host code): temporal_accumulate_motion() on a moments history, float32 [4, H, W, 4] — the
+    planes E, P, N and M = {m1, m2, 0, 0}, the running moments of the sample's luminance. -> (accumulated rgbz [H, W, 4], the new
+    history [4, H, W, 4]); the image and the first three planes are temporal_accumulate_motion()'s bits."""
+    import numpy as np
+    rgbz = np.ascontiguousarray(rgbz, np.float32)
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
+    if hist_prev is not None:
+        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
+        if hist_prev.size != 16 * H * W:
+            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [4, H, W, 4]")
+    motion = _as_motion(motion)
+    d = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    out, hist = np.empty_like(rgbz), np.empty((4, H, W, 4), np.float32)
+    rc = hip.rtu_temporal_accumulate_moments(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
+                                             rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
+                                             hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data,
+                                             motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), int(history_cap))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate_moments: a descriptor outside its rules, a camera of another size, history_cap outside "
+                           "0..65535, or a table entry with an unknown flag or a non-zero reserved word")
+    return out, hist
+
+
+def variance(hist, hits, desc=None):
+    """rtu_variance (pure host code): the variance of the accumulated mean's luminance per pixel, float32 [H, W], out of a moments
+    history float32 [4, H, W, 4] and the hits [H * W] of its frame; 0 for a pixel without history. desc: an RtuVarianceDesc whose
+    width and height are taken from hist (None: the defaults)."""
+    import numpy as np
+    hist = np.ascontiguousarray(hist, np.float32)
+    if hist.ndim != 4 or hist.shape[0] != 4 or hist.shape[3] != 4:
+        raise RtuError(RTU_ERR_ARG, "hist: a float32 [4, H, W, 4] array")
+    H, W = hist.shape[1:3]
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != hit_dtype() or hits.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype()")
+    d = _sized_variance_desc(desc, W, H)
+    out = np.empty((H, W), np.float32)
+    rc = hip.rtu_variance(ctypes.byref(d), hist.ctypes.data, hits.ctypes.data, out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_variance: an empty image or a descriptor outside its rules (n_passes 1..8, sigmas > 0, normal_log2_power "
+                           "0..7, min_history 1..65535, reserved words 0)")
+    return out
+
+
+def denoise_variance(rgbz, hits, albedo, v, desc=None):
+    """rtu_denoise_variance (pure host code, the specification of the filter): denoise() with a colour edge-stop per pixel, set by the
+    variance v float32 [H, W] (see variance()) -> the filtered float32 [H, W, 4]."""
+    import numpy as np
+    rgbz = np.ascontiguousarray(rgbz, np.float32)
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W or v.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]; v: float32 [H, W]")
+    d = _sized_variance_desc(desc, W, H)
+    out = np.empty_like(rgbz)
+    rc = hip.rtu_denoise_variance(ctypes.byref(d), rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data, v.ctypes.data, out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_denoise_variance: an empty image or a descriptor outside its rules (n_passes 1..8, sigmas > 0, "
+                           "normal_log2_power 0..7, min_history 1..65535, reserved words 0)")
     return out
 
 
@@ -1130,13 +1245,18 @@ class Progressive:
 
 class Temporal:
     """A temporal session (RtuTemporal*, include/rtu_render.h "Temporal accumulation"): one new sample per frame of a recipe S / P
-    frame whose camera may move, accumulated by reprojection. Made by Context.temporal(); errors raise RtuError with the context's message."""
+    frame whose camera may move, accumulated by reprojection. Made by Context.temporal(); errors raise RtuError with the context's message.
+    variance: an RtuVarianceDesc (see variance_desc()) makes it a variance session (rtu_temporal_begin_variance): its history holds the
+    moments, and every frame is filtered by denoise_variance() with the variance() of that history."""
 
-    def __init__(self, ctx, desc):
+    def __init__(self, ctx, desc, variance=None):
         err = _I(0)
         self._ctx = ctx
         self.desc = desc
-        self._h = hip.rtu_temporal_begin(ctx._h, ctypes.byref(desc), ctypes.byref(err))
+        if variance is not None:
+            self._h = hip.rtu_temporal_begin_variance(ctx._h, ctypes.byref(desc), ctypes.byref(variance), ctypes.byref(err))
+        else:
+            self._h = hip.rtu_temporal_begin(ctx._h, ctypes.byref(desc), ctypes.byref(err))
         if not self._h:
             ctx._check(err.value if err.value != RTU_OK else RTU_ERR_ARG)
 
@@ -1286,10 +1406,10 @@ class Context:
         snapshot() -> (rgbz, counts), close()."""
         return Progressive(self, frame, adaptive)
 
-    def temporal(self, desc):
+    def temporal(self, desc, variance=None):
         """A temporal session (desc: an RtuTemporalDesc with the size of its frames, see temporal_desc()): frame(frame) -> rgbz,
         frame_device(), history(), reset(), close()."""
-        return Temporal(self, desc)
+        return Temporal(self, desc, variance)
 
     def camera_sample_rays_device(self, frame, sample, d_rays_ptr, d_keys_ptr, stream=None):
         """rtu_camera_sample_rays_device: the rays and keys of camera_sample_rays(frame, sample) written to device memory by a kernel."""
@@ -1309,6 +1429,21 @@ class Context:
         self._check(hip.rtu_temporal_accumulate_motion_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
                                                               ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
                                                               d_rgbz_out_ptr, d_motion_ptr, n_nodes, int(history_cap), stream))
+
+    def temporal_accumulate_moments_device(self, desc, prev_cam, cur_cam, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                           d_rgbz_out_ptr, d_motion_ptr, n_nodes, history_cap=0, stream=None):
+        """rtu_temporal_accumulate_moments_device: temporal_accumulate_moments() on device memory; the histories are four planes."""
+        self._check(hip.rtu_temporal_accumulate_moments_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                                               ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                                               d_rgbz_out_ptr, d_motion_ptr, n_nodes, int(history_cap), stream))
+
+    def variance_device(self, desc, d_hist_ptr, d_hits_ptr, d_v_ptr, stream=None):
+        """rtu_variance_device: variance() on device memory, desc.width * desc.height floats to d_v_ptr."""
+        self._check(hip.rtu_variance_device(self._h, ctypes.byref(desc), d_hist_ptr, d_hits_ptr, d_v_ptr, stream))
+
+    def denoise_variance_device(self, desc, d_in_ptr, d_hits_ptr, d_albedo_ptr, d_v_ptr, d_out_ptr, stream=None):
+        """rtu_denoise_variance_device: denoise_variance() on device memory, the same bits; d_out_ptr may be d_in_ptr."""
+        self._check(hip.rtu_denoise_variance_device(self._h, ctypes.byref(desc), d_in_ptr, d_hits_ptr, d_albedo_ptr, d_v_ptr, d_out_ptr, stream))
 
     def motion_vectors_device(self, desc, prev_cam, d_hits_ptr, d_motion_ptr, n_nodes, d_mv_ptr, stream=None):
         """rtu_motion_vectors_device: motion_vectors() on device memory, width * height float4 to d_mv_ptr."""

@@ -14,6 +14,7 @@
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
 #include "rtu_temporal.h"
+#include "rtu_variance.h"
 
 #include <algorithm>
 #include <array>
@@ -1815,6 +1816,9 @@ struct RtuTemporal {
     DevBuf<uint32_t> keys;
     DevBuf<RtuNodeMotion>    motion;      // rtu_temporal_frame_moved: the table of the frame, grown at the first frame that needs it ...
     PinnedBuf<RtuNodeMotion> motion_host; // ... and the staging memory it is copied through
+    bool             variance = false;    // rtu_temporal_begin_variance: hist[] have four planes, a frame ends with k_variance and the filter
+    RtuVarianceDesc  vdesc{};
+    DevBuf<float>    var;                 // ... the variance of the frame
 };
 
 static void temporal_release(RtuTemporal* t) {
@@ -1826,6 +1830,7 @@ static void temporal_release(RtuTemporal* t) {
     t->keys.reset();
     t->motion.reset();
     t->motion_host.reset();
+    t->var.reset();
     t->has_hist = false;
     t->ctx = nullptr;
 }
@@ -4003,7 +4008,7 @@ int rtu_temporal_accumulate_device(RtuContext* ctx, const RtuTemporalDesc* desc,
     return RTU_OK;
 }
 
-RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, int* err_out) {
+static RtuTemporal* temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuVarianceDesc* vdesc, int* err_out) {
     auto refuse = [&](int rc) -> RtuTemporal* {
         if (err_out) *err_out = rc;
         return nullptr;
@@ -4011,9 +4016,15 @@ RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, in
     if (!ctx) return refuse(RTU_ERR_ARG);
     if (rtu_temporal_check_desc(desc) != RTU_OK)
         return refuse(fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0"));
+    if (vdesc && (desc->flags & RTU_TEMPORAL_DENOISE))
+        return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a variance session has its own filter (RTU_TEMPORAL_DENOISE must not be set)"));
     if (hipSetDevice(ctx->device) != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "hipSetDevice failed"));
     std::unique_ptr<RtuTemporal> t(new RtuTemporal);
     t->desc = *desc;
+    if (vdesc) {
+        t->variance = true;
+        t->vdesc = *vdesc;
+    }
     t->pixels = (size_t)desc->width * (size_t)desc->height;
     t->scene_gen = ctx->scene_gen;
     const size_t n = t->pixels;
@@ -4023,8 +4034,9 @@ RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, in
     if (e == hipSuccess) e = t->hits.grow(3 * n);
     if (e == hipSuccess) e = t->albedo.grow(n);
     for (DevBuf<float4>& h : t->hist)
-        if (e == hipSuccess) e = h.grow(3 * n);
-    if (e == hipSuccess && (desc->flags & RTU_TEMPORAL_DENOISE)) e = ctx->dn_planes.grow(4 * n);  // the filter's planes are the context's
+        if (e == hipSuccess) e = h.grow((vdesc ? 4 : 3) * n);
+    if (e == hipSuccess && vdesc) e = t->var.grow(n);
+    if (e == hipSuccess && (vdesc || (desc->flags & RTU_TEMPORAL_DENOISE))) e = ctx->dn_planes.grow(4 * n);  // the filter's planes are the context's
     if (e != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e)));
     t->ctx = ctx;
     ctx->temporals.push_back(t.get());
@@ -4032,7 +4044,81 @@ RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, in
     return t.release();
 }
 
+RtuTemporal* rtu_temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc, int* err_out) { return temporal_begin(ctx, desc, nullptr, err_out); }
+
+static const char* const kVarianceDescRules =
+    "variance: width, height 1 .. 65536 (2^26 pixels), n_passes 1 .. 8, normal_log2_power 0 .. 7, sigmas > 0, min_history 1 .. 65535, reserved words 0";
+
+RtuTemporal* rtu_temporal_begin_variance(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuVarianceDesc* vdesc, int* err_out) {
+    auto refuse = [&](int rc) -> RtuTemporal* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (!vdesc || !desc) return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a descriptor is NULL"));
+    RtuVarianceDesc vd = *vdesc;  // (its size is the session's)
+    vd.width = desc->width;
+    vd.height = desc->height;
+    if (rtu_temporal_check_desc(desc) == RTU_OK && rtu_variance_check_desc(&vd) != RTU_OK) return refuse(fail(ctx, RTU_ERR_ARG, "%s", kVarianceDescRules));
+    return temporal_begin(ctx, desc, &vd, err_out);
+}
+
 static_assert(sizeof(RtuNodeMotion) == 96, "RtuNodeMotion is 96 bytes");
+static_assert(sizeof(RtuVarianceDesc) == 40, "RtuVarianceDesc is 40 bytes");
+
+int rtu_temporal_accumulate_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                           const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                           void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK)
+        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
+    if (rtu_temporal_check_motion(nullptr, n_nodes, history_cap) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "temporal: history_cap is 0 .. 65535");
+    if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "temporal: a camera is NULL");
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return fail(ctx, RTU_ERR_ARG, "temporal: the cameras must have the desc's width and height");
+    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out || !d_motion) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
+    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out) ||
+        misaligned(d_motion))
+        return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
+    if (d_hist_prev) {
+        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)64 * (uintptr_t)desc->width * (uintptr_t)desc->height;
+        if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
+    }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_temporal_moments(tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap),
+                                                                 (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo, (const float4*)d_hist_prev,
+                                                                 (float4*)d_hist_out, (float4*)d_rgbz_out, d_motion, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_variance_device(RtuContext* ctx, const RtuVarianceDesc* desc, const void* d_hist, const void* d_hits, void* d_v, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_variance_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kVarianceDescRules);
+    if (!d_hist || !d_hits || !d_v) return fail(ctx, RTU_ERR_ARG, "variance: a device pointer is NULL");
+    if (misaligned(d_hist) || misaligned(d_hits) || ((uintptr_t)d_v & 3u))
+        return fail(ctx, RTU_ERR_ARG, "variance: device buffers must be 16-byte aligned (d_v: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_variance(vr_setup(*desc), (const float4*)d_hist, (const float4*)d_hits, (float*)d_v, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "variance launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_denoise_variance_device(RtuContext* ctx, const RtuVarianceDesc* desc, const void* d_in, const void* d_hits, const void* d_albedo, const void* d_v,
+                                void* d_out, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_variance_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kVarianceDescRules);
+    if (!d_in || !d_hits || !d_albedo || !d_v || !d_out) return fail(ctx, RTU_ERR_ARG, "variance: a device pointer is NULL");
+    if (misaligned(d_in) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_out) || ((uintptr_t)d_v & 3u))
+        return fail(ctx, RTU_ERR_ARG, "variance: device buffers must be 16-byte aligned (d_v: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->dn_planes.grow(4 * (size_t)desc->width * (size_t)desc->height));
+    const hipError_t e = (hipError_t)rtu_launch_denoise_variance(*desc, (const float4*)d_in, (const float4*)d_hits, (const float4*)d_albedo, (const float*)d_v,
+                                                                 (float4*)d_out, ctx->dn_planes.get(), (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "variance filter launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
 
 int rtu_temporal_accumulate_motion_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
                                           const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
@@ -4117,9 +4203,15 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         if (!moved->h_motion && t->has_hist) return fail(ctx, RTU_ERR_ARG, "the motion table is NULL");
         if (rtu_temporal_check_motion(moved->h_motion, moved->n_nodes, moved->history_cap) != RTU_OK)
             return fail(ctx, RTU_ERR_ARG, "motion: history_cap 0 .. 65535, known flags and reserved words 0 in every table entry");
-        RTU_HIP(ctx, hipSetDevice(ctx->device));  // (also on frame 0, which does not use them: the next moved frame allocates nothing)
-        RTU_HIP(ctx, t->motion.grow(moved->n_nodes));
-        RTU_HIP(ctx, t->motion_host.grow(moved->n_nodes));
+    }
+    // the table of the frame: a moved frame's (== the scene's node count), or a variance session's all-STATIC one for a plain frame —
+    // at least one entry there, the moments form refuses a NULL table. Also on frame 0, which does not use it: a later frame allocates nothing.
+    const uint32_t n_static = (uint32_t)ctx->shape_nodes.size();
+    if (moved || t->variance) {
+        const size_t entries = (t->variance && n_static == 0) ? 1 : n_static;
+        RTU_HIP(ctx, hipSetDevice(ctx->device));
+        RTU_HIP(ctx, t->motion.grow(entries));
+        RTU_HIP(ctx, t->motion_host.grow(entries));
     }
     if (t->scene_gen != ctx->scene_gen) {
         t->scene_gen = ctx->scene_gen;
@@ -4151,7 +4243,25 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     if ((rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
     RtuTemporalDesc td = t->desc;
     td.flags = 0;
-    if (moved && t->has_hist) {
+    if (t->variance) {
+        // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
+        const uint32_t n_nodes = moved ? moved->n_nodes : n_static;
+        if (moved && t->has_hist) {
+            memcpy(t->motion_host.get(), moved->h_motion, n_nodes * sizeof(RtuNodeMotion));
+        } else {
+            RtuNodeMotion id{};
+            const TpMotion T = tp_motion_identity();
+            memcpy(id.m, T.m, sizeof id.m);
+            memcpy(id.g, T.g, sizeof id.g);
+            id.flags = RTU_MOTION_STATIC;
+            for (uint32_t i = 0; i < n_nodes; i++) t->motion_host.get()[i] = id;
+        }
+        if (n_nodes > 0)
+            RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
+        rc = rtu_temporal_accumulate_moments_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                                    t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(),
+                                                    n_nodes, moved ? moved->history_cap : 0, hip_stream);
+    } else if (moved && t->has_hist) {
         // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
         memcpy(t->motion_host.get(), moved->h_motion, moved->n_nodes * sizeof(RtuNodeMotion));
         RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), moved->n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
@@ -4166,6 +4276,10 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     t->has_hist = true;
     t->prev_cam = *frame;
     t->k++;
+    if (t->variance) {
+        if ((rc = rtu_variance_device(ctx, &t->vdesc, t->hist[t->cur].get(), t->hits.get(), t->var.get(), hip_stream)) != RTU_OK) return rc;
+        return rtu_denoise_variance_device(ctx, &t->vdesc, d_rgbz, t->hits.get(), t->albedo.get(), t->var.get(), d_rgbz, hip_stream);  // in place
+    }
     if (t->desc.flags & RTU_TEMPORAL_DENOISE) {
         RtuDenoiseDesc dd;
         rtu_denoise_defaults(&dd);

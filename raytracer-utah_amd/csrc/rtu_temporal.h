@@ -204,6 +204,9 @@ RTU_HD bool tp_project(const TpParams& P, const f3& Pm, float& fx, float& fy) {
 }
 
 // tp_pixel with a moving scene: in_table / T as for tp_moved_point.
+// NOTE: vr_pixel_moments and vr_tap of rtu_variance.h repeat this function and tp_tap expression by expression (and vr_load_motion of
+// rtu_variance.hip repeats load_motion of rtu_temporal.hip), with the moments beside them: a change here is made there as well —
+// tests/test_variance_host.py holds the two to the same bits.
 RTU_HD void tp_pixel_motion(const TpMotionParams& M, bool in_table, const TpMotion& T, const float4* hE, const float4* hP, const float4* hN, int x, int y,
                             const float4& rgbz, const float4* hit, const float4& albedo, float4& out, float4& oE, float4& oP, float4& oN) {
     const TpParams& P = M.P;
