@@ -747,7 +747,7 @@ int  rtu_temporal_history_device(RtuTemporal* t, void* d_n, void* hip_stream);
 int  rtu_temporal_reset(RtuTemporal* t);
 void rtu_temporal_free(RtuTemporal* t);
 
-/* ---- Temporal accumulation across scene updates: moving nodes (rtu_temporal.h tp_pixel_motion, rtu_temporal.hip k_temporal_motion) ----
+/* ---- Temporal accumulation across scene updates: moving nodes (rtu_temporal.h tp_pixel with MOVING, rtu_temporal.hip k_temporal<true, false>) ----
  * rtu_temporal_frame starts over once the scene changed. The entries below keep the history instead: a pixel's hit point is first
  * carried to where that point of its NODE was in the previous frame's scene, by an affine map per node, and the lookup of "Temporal
  * accumulation" is made from there.
@@ -869,7 +869,7 @@ int  rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const R
  * outside 0 .. 7, a sigma that is not > 0, min_history outside 1 .. 65535, a non-zero reserved word, a device pointer that is not
  * 16-byte aligned (d_v: 4-byte). The host forms are pure host code, no GPU and no context: the executable statement of the rules. The
  * _device forms give the same bits from device memory, asynchronous on hip_stream: rtu_temporal_accumulate_moments_device
- * (k_temporal_moments) and rtu_variance_device (k_variance) allocate nothing, need no scene and touch no state of the context;
+ * (k_temporal<true, true>) and rtu_variance_device (k_variance) allocate nothing, need no scene and touch no state of the context;
  * rtu_denoise_variance_device uses the four grow-only planes of rtu_denoise_device (64 B per pixel, one stream per context, no
  * allocation once a frame of that size has been filtered by either), d_out == d_in is allowed.
  *

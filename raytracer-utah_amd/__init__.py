@@ -405,11 +405,9 @@ def temporal_desc(width=0, height=0, denoise=False, **overrides):
     return d
 
 
-def temporal_accumulate(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev=None, desc=None):
-    """rtu_temporal_accumulate (pure host code, the specification of the accumulator): one new sample rgbz float32 [H, W, 4] with the
-    guides hits [H * W] of hit_dtype() and albedo float32 [H * W, 4] of cur_cam (an RtuFrameDesc) blended into hist_prev — float32
-    [3, H, W, 4], the planes E, P, N of the frame before, whose camera was prev_cam; None: no history — -> (accumulated rgbz
-    [H, W, 4], the new history [3, H, W, 4]). desc: an RtuTemporalDesc whose width and height are taken from rgbz (None: the defaults)."""
+def _temporal_accumulate(planes, call, prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc, motion=None, history_cap=0):
+    """What the three temporal_accumulate*() share: the arrays validated, desc copied and sized from rgbz, `call` (the host form of
+    librtu_hip, with a history of `planes` planes; motion None: the form that takes no table) -> (rc, accumulated rgbz, new history)."""
     import numpy as np
     rgbz = np.ascontiguousarray(rgbz, np.float32)
     if rgbz.ndim != 3 or rgbz.shape[2] != 4:
@@ -421,15 +419,27 @@ def temporal_accumulate(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev=None, d
         raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
     if hist_prev is not None:
         hist_prev = np.ascontiguousarray(hist_prev, np.float32)
-        if hist_prev.size != 12 * H * W:
-            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [3, H, W, 4]")
+        if hist_prev.size != 4 * planes * H * W:
+            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [%d, H, W, 4]" % planes)
+    table = ()
+    if motion is not None:
+        motion = _as_motion(motion)
+        table = (motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), int(history_cap))
     d = RtuTemporalDesc()
     ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
     d.width, d.height = W, H
-    out, hist = np.empty_like(rgbz), np.empty((3, H, W, 4), np.float32)
-    rc = hip.rtu_temporal_accumulate(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
-                                     rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
-                                     hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data)
+    out, hist = np.empty_like(rgbz), np.empty((planes, H, W, 4), np.float32)
+    rc = call(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam), rgbz.ctypes.data, hits.ctypes.data,
+              albedo.ctypes.data, hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data, *table)
+    return rc, out, hist
+
+
+def temporal_accumulate(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev=None, desc=None):
+    """rtu_temporal_accumulate (pure host code, the specification of the accumulator): one new sample rgbz float32 [H, W, 4] with the
+    guides hits [H * W] of hit_dtype() and albedo float32 [H * W, 4] of cur_cam (an RtuFrameDesc) blended into hist_prev — float32
+    [3, H, W, 4], the planes E, P, N of the frame before, whose camera was prev_cam; None: no history — -> (accumulated rgbz
+    [H, W, 4], the new history [3, H, W, 4]). desc: an RtuTemporalDesc whose width and height are taken from rgbz (None: the defaults)."""
+    rc, out, hist = _temporal_accumulate(3, hip.rtu_temporal_accumulate, prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc)
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_temporal_accumulate: a descriptor outside its rules (max_history 1..65535, sigma_plane > 0, normal_min "
                            "-1..1, known flags, reserved words 0) or a camera of another size")
@@ -481,28 +491,7 @@ def temporal_accumulate_motion(prev_cam, cur_cam, rgbz, hits, albedo, motion, hi
     """rtu_temporal_accumulate_motion (pure host code): temporal_accumulate() across a scene update — `motion` (motion_dtype(), see
     scene_motion()) carries every pixel's hit point to the previous frame's scene before the lookup; history_cap 0 (none) .. 65535
     bounds the history length a pixel takes over. -> (accumulated rgbz [H, W, 4], the new history [3, H, W, 4])."""
-    import numpy as np
-    rgbz = np.ascontiguousarray(rgbz, np.float32)
-    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
-        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
-    H, W = rgbz.shape[:2]
-    hits = np.ascontiguousarray(hits)
-    albedo = np.ascontiguousarray(albedo, np.float32)
-    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
-        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
-    if hist_prev is not None:
-        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
-        if hist_prev.size != 12 * H * W:
-            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [3, H, W, 4]")
-    motion = _as_motion(motion)
-    d = RtuTemporalDesc()
-    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
-    d.width, d.height = W, H
-    out, hist = np.empty_like(rgbz), np.empty((3, H, W, 4), np.float32)
-    rc = hip.rtu_temporal_accumulate_motion(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
-                                            rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
-                                            hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data,
-                                            motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), int(history_cap))
+    rc, out, hist = _temporal_accumulate(3, hip.rtu_temporal_accumulate_motion, prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc, motion, history_cap)
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_temporal_accumulate_motion: a descriptor outside its rules, a camera of another size, history_cap outside "
                            "0..65535, or a table entry with an unknown flag or a non-zero reserved word")
@@ -602,28 +591,7 @@ def temporal_accumulate_moments(prev_cam, cur_cam, rgbz, hits, albedo, motion, h
     """rtu_temporal_accumulate_moments (pure host code): temporal_accumulate_motion() on a moments history, float32 [4, H, W, 4] — the
     planes E, P, N and M = {m1, m2, 0, 0}, the running moments of the sample's luminance. -> (accumulated rgbz [H, W, 4], the new
     history [4, H, W, 4]); the image and the first three planes are temporal_accumulate_motion()'s bits."""
-    import numpy as np
-    rgbz = np.ascontiguousarray(rgbz, np.float32)
-    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
-        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
-    H, W = rgbz.shape[:2]
-    hits = np.ascontiguousarray(hits)
-    albedo = np.ascontiguousarray(albedo, np.float32)
-    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
-        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
-    if hist_prev is not None:
-        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
-        if hist_prev.size != 16 * H * W:
-            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [4, H, W, 4]")
-    motion = _as_motion(motion)
-    d = RtuTemporalDesc()
-    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
-    d.width, d.height = W, H
-    out, hist = np.empty_like(rgbz), np.empty((4, H, W, 4), np.float32)
-    rc = hip.rtu_temporal_accumulate_moments(ctypes.byref(d), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
-                                             rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
-                                             hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data,
-                                             motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), int(history_cap))
+    rc, out, hist = _temporal_accumulate(4, hip.rtu_temporal_accumulate_moments, prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc, motion, history_cap)
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_temporal_accumulate_moments: a descriptor outside its rules, a camera of another size, history_cap outside "
                            "0..65535, or a table entry with an unknown flag or a non-zero reserved word")

@@ -3767,6 +3767,25 @@ int paths_shade(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream
     return rc;
 }
 
+// Shade a ray batch whose rays (and keys) are in device memory until its frame records suffice: launch() — with paths the five steps
+// of paths_shade, the chain having been traced by the caller —, wait, check_overflow, and again with the capacities that raised.
+// counters_refusal: what to say where a path-traced batch with counters would have to be shaded again (its counters of the dropped
+// steps are already in the totals), or nullptr where the caller has no counters.
+int shade_until_fits(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n,
+                     bool paths, const char* counters_refusal) {
+    for (int attempt = 0;; attempt++) {
+        int rc = paths ? paths_shade(ctx, f, d_out, stream, d_rays, d_keys, n)
+                       : launch(ctx, &f, d_out, stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, d_rays, n, d_keys);
+        if (rc != RTU_OK) return rc;
+        RTU_HIP(ctx, hipStreamSynchronize(stream));
+        bool overflow = false;
+        if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
+        if (!overflow) return RTU_OK;
+        if (paths && f.collect_stats && counters_refusal) return fail(ctx, RTU_ERR_CAPACITY, "%s", counters_refusal);
+        if (attempt >= (paths ? 8 : 2) * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+    }
+}
+
 // the host forms of all three recipes: chunks of at most kQueryChunk rays (and keys) through the context's buffers, each checked for
 // capacity and shaded again if need be. paths: the chain of a chunk is traced once, its shading steps are what is repeated
 int shade_host(RtuContext* ctx, RtuFrameDesc& f, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, float* h_rgbt, RtuStats* stats, bool paths = false) {
@@ -3783,19 +3802,10 @@ int shade_host(RtuContext* ctx, RtuFrameDesc& f, const RtuRay* h_rays, const uin
         RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
         if (h_keys) RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_keys.get(), h_keys + done, sizeof(uint32_t) * m, hipMemcpyHostToDevice, ctx->stream));
         if (paths && (rc = paths_chain(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), ctx->sh_keys.get(), (uint32_t)m)) != RTU_OK) return rc;
-        for (int attempt = 0;; attempt++) {  // as rtu_render_frame: a chunk that ran out of frame capacity is shaded again
-            rc = paths ? paths_shade(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), ctx->sh_keys.get(), (uint32_t)m)
-                       : launch(ctx, &f, ctx->sh_out.get(), ctx->stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, ctx->sh_rays.get(), (uint32_t)m,
-                                h_keys ? ctx->sh_keys.get() : nullptr);
-            if (rc != RTU_OK) return rc;
-            RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            bool overflow = false;
-            if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
-            if (!overflow) break;
-            // (as sample_batches: the counters of the dropped shading steps are already in the totals)
-            if (paths && f.collect_stats) return fail(ctx, RTU_ERR_CAPACITY, "recipe P with counters: frame records ran out; shade the batch once without counters first");
-            if (attempt >= (paths ? 8 : 2) * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
-        }
+        // as rtu_render_frame: a chunk that ran out of frame capacity is shaded again
+        if ((rc = shade_until_fits(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), h_keys ? ctx->sh_keys.get() : nullptr, (uint32_t)m, paths,
+                                   "recipe P with counters: frame records ran out; shade the batch once without counters first")) != RTU_OK)
+            return rc;
         RTU_HIP(ctx, hipMemcpy(h_rgbt + 4 * done, ctx->sh_out.get(), sizeof(float4) * m, hipMemcpyDeviceToHost));
         if (stats) {  // the counters are zeroed per launch: the batch's are the sum over its chunks
             RtuStats part;
@@ -3983,24 +3993,38 @@ int rtu_camera_rays(const RtuFrameDesc* frame, int row0, int nrows, RtuRay* rays
 // ---- temporal accumulation (rtu_temporal.h, rtu_temporal.hip): the accumulator on device memory, and the session that drives it ----
 static_assert(sizeof(RtuTemporalDesc) == 32, "RtuTemporalDesc is 32 bytes");
 
-int rtu_temporal_accumulate_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
-                                   const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
-                                   void* d_rgbz_out, void* hip_stream) {
+static const char* const kTemporalDescRules =
+    "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0";
+
+// The checks the three rtu_temporal_accumulate*_device entries share, in their order of precedence: `planes` 3 or 4 float4 per pixel
+// of a history; has_motion: the entry takes a table and a history_cap. prev_cam: NULL becomes cur_cam. RTU_OK: the device is set.
+static int temporal_device_args(RtuContext* ctx, int planes, bool has_motion, const RtuTemporalDesc* desc, const RtuFrameDesc*& prev_cam,
+                                const RtuFrameDesc* cur_cam, const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev,
+                                const void* d_hist_out, const void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap) {
     if (!ctx) return RTU_ERR_ARG;
-    if (rtu_temporal_check_desc(desc) != RTU_OK)
-        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
+    if (rtu_temporal_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
+    if (has_motion && rtu_temporal_check_motion(nullptr, n_nodes, history_cap) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "temporal: history_cap is 0 .. 65535");
     if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "temporal: a camera is NULL");
     if (!prev_cam) prev_cam = cur_cam;
     if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
         return fail(ctx, RTU_ERR_ARG, "temporal: the cameras must have the desc's width and height");
-    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
-    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out))
+    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out || (has_motion && !d_motion)) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
+    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out) ||
+        misaligned(d_motion))
         return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
     if (d_hist_prev) {
-        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)48 * (uintptr_t)desc->width * (uintptr_t)desc->height;
+        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)(16 * planes) * (uintptr_t)desc->width * (uintptr_t)desc->height;
         if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
     }
     RTU_HIP(ctx, hipSetDevice(ctx->device));
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                   const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                   void* d_rgbz_out, void* hip_stream) {
+    const int rc = temporal_device_args(ctx, 3, false, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, nullptr, 0, 0);
+    if (rc != RTU_OK) return rc;
     const hipError_t e = (hipError_t)rtu_launch_temporal(tp_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr), (const float4*)d_rgbz, (const float4*)d_hits,
                                                          (const float4*)d_albedo, (const float4*)d_hist_prev, (float4*)d_hist_out, (float4*)d_rgbz_out,
                                                          (hipStream_t)hip_stream);
@@ -4015,7 +4039,7 @@ static RtuTemporal* temporal_begin(RtuContext* ctx, const RtuTemporalDesc* desc,
     };
     if (!ctx) return refuse(RTU_ERR_ARG);
     if (rtu_temporal_check_desc(desc) != RTU_OK)
-        return refuse(fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0"));
+        return refuse(fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules));
     if (vdesc && (desc->flags & RTU_TEMPORAL_DENOISE))
         return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a variance session has its own filter (RTU_TEMPORAL_DENOISE must not be set)"));
     if (hipSetDevice(ctx->device) != hipSuccess) return refuse(fail(ctx, RTU_ERR_HIP, "hipSetDevice failed"));
@@ -4069,23 +4093,9 @@ static_assert(sizeof(RtuVarianceDesc) == 40, "RtuVarianceDesc is 40 bytes");
 int rtu_temporal_accumulate_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
                                            const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
                                            void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
-    if (!ctx) return RTU_ERR_ARG;
-    if (rtu_temporal_check_desc(desc) != RTU_OK)
-        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
-    if (rtu_temporal_check_motion(nullptr, n_nodes, history_cap) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "temporal: history_cap is 0 .. 65535");
-    if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "temporal: a camera is NULL");
-    if (!prev_cam) prev_cam = cur_cam;
-    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
-        return fail(ctx, RTU_ERR_ARG, "temporal: the cameras must have the desc's width and height");
-    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out || !d_motion) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
-    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out) ||
-        misaligned(d_motion))
-        return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
-    if (d_hist_prev) {
-        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)64 * (uintptr_t)desc->width * (uintptr_t)desc->height;
-        if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
-    }
-    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const int rc = temporal_device_args(ctx, 4, true, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, d_motion, n_nodes,
+                                        history_cap);
+    if (rc != RTU_OK) return rc;
     const hipError_t e = (hipError_t)rtu_launch_temporal_moments(tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap),
                                                                  (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo, (const float4*)d_hist_prev,
                                                                  (float4*)d_hist_out, (float4*)d_rgbz_out, d_motion, (hipStream_t)hip_stream);
@@ -4123,23 +4133,9 @@ int rtu_denoise_variance_device(RtuContext* ctx, const RtuVarianceDesc* desc, co
 int rtu_temporal_accumulate_motion_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
                                           const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
                                           void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
-    if (!ctx) return RTU_ERR_ARG;
-    if (rtu_temporal_check_desc(desc) != RTU_OK)
-        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
-    if (rtu_temporal_check_motion(nullptr, n_nodes, history_cap) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "temporal: history_cap is 0 .. 65535");
-    if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "temporal: a camera is NULL");
-    if (!prev_cam) prev_cam = cur_cam;
-    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
-        return fail(ctx, RTU_ERR_ARG, "temporal: the cameras must have the desc's width and height");
-    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out || !d_motion) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
-    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out) ||
-        misaligned(d_motion))
-        return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
-    if (d_hist_prev) {
-        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out, bytes = (uintptr_t)48 * (uintptr_t)desc->width * (uintptr_t)desc->height;
-        if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
-    }
-    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const int rc = temporal_device_args(ctx, 3, true, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, d_motion, n_nodes,
+                                        history_cap);
+    if (rc != RTU_OK) return rc;
     const hipError_t e = (hipError_t)rtu_launch_temporal_motion(tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap),
                                                                 (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo, (const float4*)d_hist_prev,
                                                                 (float4*)d_hist_out, (float4*)d_rgbz_out, d_motion, (hipStream_t)hip_stream);
@@ -4151,7 +4147,7 @@ int rtu_motion_vectors_device(RtuContext* ctx, const RtuTemporalDesc* desc, cons
                               uint32_t n_nodes, void* d_mv, void* hip_stream) {
     if (!ctx) return RTU_ERR_ARG;
     if (rtu_temporal_check_desc(desc) != RTU_OK)
-        return fail(ctx, RTU_ERR_ARG, "temporal: width, height 1 .. 65536 (2^26 pixels), max_history 1 .. 65535, sigma_plane > 0, normal_min -1 .. 1, known flags, reserved words 0");
+        return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
     if (!prev_cam || prev_cam->width != desc->width || prev_cam->height != desc->height)
         return fail(ctx, RTU_ERR_ARG, "motion vectors: the previous camera must have the desc's width and height");
     if (!d_hits || !d_motion || !d_mv) return fail(ctx, RTU_ERR_ARG, "motion vectors: a device pointer is NULL");
@@ -4230,16 +4226,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     if ((rc = shade_args(ctx, t->rays.get(), t->img.get(), n, &sd, true, &f, true, t->keys.get(), paths)) != RTU_OK) return rc;
     // as shade_host: the chain of recipe P is traced once, the shading is what is repeated when the frame records ran out
     if (paths && (rc = paths_chain(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n)) != RTU_OK) return rc;
-    for (int attempt = 0;; attempt++) {
-        rc = paths ? paths_shade(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n)
-                   : launch(ctx, &f, t->img.get(), stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, t->rays.get(), (uint32_t)n, t->keys.get());
-        if (rc != RTU_OK) return rc;
-        RTU_HIP(ctx, hipStreamSynchronize(stream));
-        bool overflow = false;
-        if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
-        if (!overflow) break;
-        if (attempt >= (paths ? 8 : 2) * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
-    }
+    if ((rc = shade_until_fits(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n, paths, nullptr)) != RTU_OK) return rc;
     if ((rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
     RtuTemporalDesc td = t->desc;
     td.flags = 0;
@@ -4290,30 +4277,25 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     return RTU_OK;
 }
 
-int rtu_temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz) {
+// the host forms: the frame into the context's frame buffer, then its copy to h_rgbz
+static int temporal_frame_host(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz, const TemporalMoved* moved) {
     if (!t || !t->ctx) return RTU_ERR_ARG;
     RtuContext* ctx = t->ctx;
     if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     RTU_HIP(ctx, ctx->fb.grow(t->pixels));
-    const int rc = rtu_temporal_frame_device(t, frame, ctx->fb.get(), ctx->stream);
+    const int rc = temporal_frame(t, frame, ctx->fb.get(), ctx->stream, moved);
     if (rc != RTU_OK) return rc;
     RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), t->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RTU_OK;
 }
 
+int rtu_temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz) { return temporal_frame_host(t, frame, h_rgbz, nullptr); }
+
 int rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap, float* h_rgbz) {
-    if (!t || !t->ctx) return RTU_ERR_ARG;
-    RtuContext* ctx = t->ctx;
-    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
-    RTU_HIP(ctx, hipSetDevice(ctx->device));
-    RTU_HIP(ctx, ctx->fb.grow(t->pixels));
-    const int rc = rtu_temporal_frame_moved_device(t, frame, h_motion, n_nodes, history_cap, ctx->fb.get(), ctx->stream);
-    if (rc != RTU_OK) return rc;
-    RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), t->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RTU_OK;
+    const TemporalMoved moved{h_motion, n_nodes, history_cap};
+    return temporal_frame_host(t, frame, h_rgbz, &moved);
 }
 
 int rtu_temporal_history_device(RtuTemporal* t, void* d_n, void* hip_stream) {
@@ -4511,17 +4493,9 @@ int rtu_render_sensor_device(RtuContext* ctx, const RtuSensorDesc* d, void* d_rg
         if ((rc = sensor_generate(ctx, d, i, nb, rays, ctx->sn_keys.get(), stream)) != RTU_OK) return rc;
         if (timing) RTU_HIP(ctx, hipEventRecord(ctx->sn_ev[1], stream));
         if (paths && (rc = paths_chain(ctx, f, out, stream, rays, keys, m)) != RTU_OK) return rc;
-        for (int attempt = 0;; attempt++) {
-            rc = paths ? paths_shade(ctx, f, out, stream, rays, keys, m)
-                       : launch(ctx, &f, out, stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, rays, m, keys);
-            if (rc != RTU_OK) return rc;
-            RTU_HIP(ctx, hipStreamSynchronize(stream));
-            bool overflow = false;
-            if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
-            if (!overflow) break;
-            if (paths && f.collect_stats) return fail(ctx, RTU_ERR_CAPACITY, "recipe P with counters: frame records ran out; render the sensor once without RTU_QUERY_REFERENCE_WALK first");
-            if (attempt >= (paths ? 8 : 2) * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
-        }
+        if ((rc = shade_until_fits(ctx, f, out, stream, rays, keys, m, paths,
+                                   "recipe P with counters: frame records ran out; render the sensor once without RTU_QUERY_REFERENCE_WALK first")) != RTU_OK)
+            return rc;
         const bool last = i + nb >= n;
         if (timing) RTU_HIP(ctx, hipEventRecord(ctx->sn_ev[2], stream));
         const hipError_t e = (hipError_t)rtu_launch_sensor_accumulate(out, (uint32_t)nb, ctx->sn_acc.get(), ctx->sn_hits.get(), (uint32_t)pixels, i == 0,

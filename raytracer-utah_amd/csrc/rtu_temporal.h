@@ -1,17 +1,21 @@
-// rtu_temporal.h — the arithmetic of the temporal accumulator (rtu_temporal_accumulate / rtu_temporal_accumulate_device,
-// include/rtu_render.h "Temporal accumulation"), host + device, and the launch interface of its kernels (rtu_temporal.hip), called by
-// rtu_capi.hip.
+// rtu_temporal.h — the arithmetic of the temporal accumulator (include/rtu_render.h "Temporal accumulation", "... across scene
+// updates" and the moments of "Variance-guided filtering"), host + device, and the launch interface of its kernels (rtu_temporal.hip),
+// called by rtu_capi.hip. The three forms — rtu_temporal_accumulate, _motion and _moments, each with its _device form — are the
+// instantiations of one function, tp_pixel<MOVING, MOMENTS>.
 //
 // A pixel's first-hit point is projected into the previous camera, the history is fetched there with four bilinear taps, each tested
 // for being the same surface, and the new sample is blended in. No transcendental function: the translation units that include this
-// header are compiled with -ffp-contract=off and IEEE divides, every operation below rounds once, so the host form and the kernel give
-// the same bits.
+// header are compiled with -ffp-contract=off and IEEE divides and square roots, every operation below rounds once, so the host forms
+// and the kernels give the same bits.
 //
 // A HISTORY is three planes of one float4 per pixel:  E = {e.rgb, n}   P = {p.xyz, t}   N = {N.xyz, node as bits}
+// A MOMENTS HISTORY has a fourth:  M = {m1, m2, 0, 0}, the running first and second moment of the luminance of the demodulated sample.
 #ifndef RTU_TEMPORAL_H_INCLUDED
 #define RTU_TEMPORAL_H_INCLUDED
 
 #include "rtu_denoise.h"
+
+#include <type_traits>
 
 #define TP_LOOKUP_NONE      0  // no previous history
 #define TP_LOOKUP_STATIC    1  // the cameras are equal bit for bit: the pixel itself with weight 1
@@ -58,80 +62,11 @@ inline TpParams tp_setup(const RtuTemporalDesc& d, const RtuFrameDesc& prev, con
     return p;
 }
 
+// float4 i of a caller's floats, which need not be 16-byte aligned (the host forms)
+inline float4 f4(const float* p, size_t i) { return make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); }
+inline void st4(float* p, size_t i, const float4& v) { p[4 * i] = v.x; p[4 * i + 1] = v.y; p[4 * i + 2] = v.z; p[4 * i + 3] = v.w; }
+
 RTU_HD bool tp_finite(float x) { return (x - x) == 0.0f; }  // false for an infinity and for a NaN
-
-// One tap of pixel p's lookup at pixel (qx, qy) of the previous history with weight w: where it is ACCEPTED, E_q.rgb w is added to acc,
-// E_q.n w to nacc and w to wsum.
-RTU_HD void tp_tap(const TpParams& P, const float4* hE, const float4* hP, const float4* hN, int qx, int qy, float w, const f3& Np, const f3& Pp,
-                   uint32_t node, float plane_max, f3& acc, float& nacc, float& wsum) {
-    if (qx < 0 || qy < 0 || qx >= P.width || qy >= P.height) return;
-    const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-    const float4 Eq = hE[q], Pq = hP[q], Nq = hN[q];
-    union { float f; uint32_t u; } nb;
-    nb.f = Nq.w;
-    if (!(Eq.w > 0.0f) || nb.u != node) return;
-    if (!(dot3(Np, mk3(Nq.x, Nq.y, Nq.z)) >= P.normal_min)) return;
-    if (!(fabsf(dot3(Np, mk3(Pq.x, Pq.y, Pq.z) - Pp)) <= plane_max)) return;
-    acc = acc + mk3(Eq.x, Eq.y, Eq.z) * w;
-    nacc = nacc + Eq.w * w;
-    wsum = wsum + w;
-}
-
-// Pixel (x, y): hE / hP / hN the planes of the previous history (not read with TP_LOOKUP_NONE), hit the three float4 of its RtuRayHit.
-// out: its pixel of the accumulated image; oE, oP, oN: its pixel of the new history.
-RTU_HD void tp_pixel(const TpParams& P, const float4* hE, const float4* hP, const float4* hN, int x, int y, const float4& rgbz, const float4* hit,
-                     const float4& albedo, float4& out, float4& oE, float4& oP, float4& oN) {
-    union { float f; uint32_t u; } flags, node;
-    flags.f = hit[0].z;
-    node.f = hit[0].y;
-    const bool valid = (flags.u & RTU_RAY_HIT) != 0;
-    const f3 d = dn_demod(albedo);
-    const f3 e_cur = mk3(rgbz.x / d.x, rgbz.y / d.y, rgbz.z / d.z);
-    const f3 Pp = mk3(hit[1].x, hit[1].y, hit[1].z), Np = mk3(hit[2].x, hit[2].y, hit[2].z);
-    const float plane_max = P.sigma_plane * hit[0].x;
-
-    f3 acc = mk3(0.0f, 0.0f, 0.0f), e_prev = mk3(0.0f, 0.0f, 0.0f);
-    float nacc = 0.0f, wsum = 0.0f, n_prev = 0.0f;
-    if (valid && P.lookup == TP_LOOKUP_STATIC) {
-        tp_tap(P, hE, hP, hN, x, y, 1.0f, Np, Pp, node.u, plane_max, acc, nacc, wsum);
-    } else if (valid && P.lookup == TP_LOOKUP_REPROJECT) {
-        const f3 pos = ld3(P.pos), nrm = ld3(P.nrm);
-        const f3 D = Pp - pos;
-        const float s = P.num / dot3(D, nrm);
-        if (tp_finite(s) && s > 0.0f) {
-            const f3 Q = (pos + D * s) - ld3(P.origin);
-            const float fx = dot3(Q, ld3(P.u)) / P.uu - 0.5f, fy = dot3(Q, ld3(P.v)) / P.vv - 0.5f;
-            if (fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {  // (a NaN fails; tested before any conversion)
-                const float flx = floorf(fx), fly = floorf(fy);
-                const int x0 = (int)flx, y0 = (int)fly;
-                const float wx = fx - flx, wy = fy - fly;
-                const float ux = 1.0f - wx, uy = 1.0f - wy;
-                tp_tap(P, hE, hP, hN, x0, y0, ux * uy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
-                tp_tap(P, hE, hP, hN, x0 + 1, y0, wx * uy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
-                tp_tap(P, hE, hP, hN, x0, y0 + 1, ux * wy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
-                tp_tap(P, hE, hP, hN, x0 + 1, y0 + 1, wx * wy, Np, Pp, node.u, plane_max, acc, nacc, wsum);
-            }
-        }
-    }
-    if (wsum > 0.01f) {
-        e_prev = mk3(acc.x / wsum, acc.y / wsum, acc.z / wsum);
-        n_prev = nacc / wsum;
-    }
-
-    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);  // else the sample is not accumulated
-    const bool fresh = n_prev == 0.0f;
-    const float n_blend = smin(n_prev + 1.0f, P.max_history);
-    const float a = 1.0f / n_blend;
-    const f3 e_blend = e_prev + (e_cur - e_prev) * a;
-    const f3 e = !finite ? e_prev : (fresh ? e_cur : e_blend);
-    const float n = !finite ? n_prev : (fresh ? 1.0f : n_blend);
-    const bool keep = valid && (finite || !fresh);  // the pixel has an accumulated colour; else its input passes through
-    if (!valid) node.u = 0xFFFFFFFFu;               // node -1
-    out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, rgbz.w) : rgbz;
-    oE = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    oP = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    oN = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
-}
 
 // ---- moving nodes (include/rtu_render.h "Temporal accumulation across scene updates") ------------------------------------------------
 // What the motion form needs beyond TpParams; made once per call by tp_motion_setup. P.lookup is TP_LOOKUP_NONE or TP_LOOKUP_REPROJECT
@@ -192,7 +127,7 @@ RTU_HD bool tp_moved_point(bool in_table, const TpMotion& T, const f3& Pp, const
     return in_table && (T.flags & RTU_MOTION_RESET) == 0 && (is_static || fin);
 }
 
-// The previous-image coordinates of world point Pm (the expressions of tp_pixel): false unless s is finite and > 0.
+// The previous-image coordinates of world point Pm: false unless s is finite and > 0.
 RTU_HD bool tp_project(const TpParams& P, const f3& Pm, float& fx, float& fy) {
     const f3 pos = ld3(P.pos), nrm = ld3(P.nrm);
     const f3 D = Pm - pos;
@@ -203,13 +138,53 @@ RTU_HD bool tp_project(const TpParams& P, const f3& Pm, float& fx, float& fy) {
     return tp_finite(s) && s > 0.0f;
 }
 
-// tp_pixel with a moving scene: in_table / T as for tp_moved_point.
-// NOTE: vr_pixel_moments and vr_tap of rtu_variance.h repeat this function and tp_tap expression by expression (and vr_load_motion of
-// rtu_variance.hip repeats load_motion of rtu_temporal.hip), with the moments beside them: a change here is made there as well —
-// tests/test_variance_host.py holds the two to the same bits.
-RTU_HD void tp_pixel_motion(const TpMotionParams& M, bool in_table, const TpMotion& T, const float4* hE, const float4* hP, const float4* hN, int x, int y,
-                            const float4& rgbz, const float4* hit, const float4& albedo, float4& out, float4& oE, float4& oP, float4& oN) {
-    const TpParams& P = M.P;
+// l(e) of a demodulated colour: what the moments are taken of
+RTU_HD float vr_lum(const f3& e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z; }
+
+// ---- the accumulator: one function for the three forms ---------------------------------------------------------------------------
+// MOVING: the hit point is carried through its node's table entry before the lookup, and the history taken over is capped
+// (TpMotionParams); else the scene is at rest (TpParams). MOMENTS: the history has the fourth plane M.
+template <bool MOVING> using TpArgs = typename std::conditional<MOVING, TpMotionParams, TpParams>::type;
+RTU_HD const TpParams& tp_base(const TpParams& p) { return p; }
+RTU_HD const TpParams& tp_base(const TpMotionParams& m) { return m.P; }
+
+// the weighted sums over the accepted taps of a lookup: E.rgb, E.n, the weights, and with MOMENTS M.xy
+struct TpSums {
+    f3    acc;
+    float n, w, m1, m2;
+};
+
+// One tap of pixel p's lookup at pixel (qx, qy) of the previous history h (its planes) with weight w: where it is ACCEPTED, it is added
+// to S. Pp, Np: p's point and normal as they were in the previous scene.
+template <bool MOMENTS>
+RTU_HD void tp_tap(const TpParams& P, const float4* const* h, int qx, int qy, float w, const f3& Np, const f3& Pp, uint32_t node, float plane_max,
+                   TpSums& S) {
+    if (qx < 0 || qy < 0 || qx >= P.width || qy >= P.height) return;
+    const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
+    const float4 Eq = h[0][q], Pq = h[1][q], Nq = h[2][q];
+    union { float f; uint32_t u; } nb;
+    nb.f = Nq.w;
+    if (!(Eq.w > 0.0f) || nb.u != node) return;
+    if (!(dot3(Np, mk3(Nq.x, Nq.y, Nq.z)) >= P.normal_min)) return;
+    if (!(fabsf(dot3(Np, mk3(Pq.x, Pq.y, Pq.z) - Pp)) <= plane_max)) return;
+    S.acc = S.acc + mk3(Eq.x, Eq.y, Eq.z) * w;
+    S.n = S.n + Eq.w * w;
+    S.w = S.w + w;
+    if (MOMENTS) {
+        const float4 Mq = h[3][q];
+        S.m1 = S.m1 + Mq.x * w;
+        S.m2 = S.m2 + Mq.y * w;
+    }
+}
+
+// Pixel (x, y): h the three (MOMENTS: four) planes of the previous history (not read with TP_LOOKUP_NONE), hit the three float4 of its
+// RtuRayHit; MOVING: in_table / T as for tp_moved_point (else neither is read). out: its pixel of the accumulated image; o: its pixel
+// of the planes of the new history, all written after every read. A.lookup is wave-uniform without MOVING; with it, whether a pixel
+// takes no, one or four taps is its own matter.
+template <bool MOVING, bool MOMENTS>
+RTU_HD void tp_pixel(const TpArgs<MOVING>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
+                     const float4* hit, const float4& albedo, float4& out, float4* o) {
+    const TpParams& P = tp_base(A);
     union { float f; uint32_t u; } flags, node;
     flags.f = hit[0].z;
     node.f = hit[0].y;
@@ -219,48 +194,65 @@ RTU_HD void tp_pixel_motion(const TpMotionParams& M, bool in_table, const TpMoti
     const f3 Pp = mk3(hit[1].x, hit[1].y, hit[1].z), Np = mk3(hit[2].x, hit[2].y, hit[2].z);
     const float plane_max = P.sigma_plane * hit[0].x;
 
-    f3 Pm, Nm;
-    const bool look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && valid && P.lookup != TP_LOOKUP_NONE;
-    const bool one_tap = look && M.same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
+    f3 Pm = Pp, Nm = Np;
+    bool look = valid && P.lookup != TP_LOOKUP_NONE, one_tap = valid && P.lookup == TP_LOOKUP_STATIC;
+    if constexpr (MOVING) {
+        look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && look;
+        one_tap = look && A.same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
+    }
 
-    f3 acc = mk3(0.0f, 0.0f, 0.0f), e_prev = mk3(0.0f, 0.0f, 0.0f);
-    float nacc = 0.0f, wsum = 0.0f, n_prev = 0.0f;
+    TpSums S = {mk3(0.0f, 0.0f, 0.0f), 0.0f, 0.0f, 0.0f, 0.0f};
+    f3 e_prev = mk3(0.0f, 0.0f, 0.0f);
+    float n_prev = 0.0f, m1_prev = 0.0f, m2_prev = 0.0f;
     if (one_tap) {
-        tp_tap(P, hE, hP, hN, x, y, 1.0f, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+        tp_tap<MOMENTS>(P, h, x, y, 1.0f, Nm, Pm, node.u, plane_max, S);
     } else if (look) {
         float fx, fy;
+        // (a NaN fails; tested before any conversion)
         if (tp_project(P, Pm, fx, fy) && fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {
             const float flx = floorf(fx), fly = floorf(fy);
             const int x0 = (int)flx, y0 = (int)fly;
             const float wx = fx - flx, wy = fy - fly;
             const float ux = 1.0f - wx, uy = 1.0f - wy;
-            tp_tap(P, hE, hP, hN, x0, y0, ux * uy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
-            tp_tap(P, hE, hP, hN, x0 + 1, y0, wx * uy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
-            tp_tap(P, hE, hP, hN, x0, y0 + 1, ux * wy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
-            tp_tap(P, hE, hP, hN, x0 + 1, y0 + 1, wx * wy, Nm, Pm, node.u, plane_max, acc, nacc, wsum);
+            tp_tap<MOMENTS>(P, h, x0, y0, ux * uy, Nm, Pm, node.u, plane_max, S);
+            tp_tap<MOMENTS>(P, h, x0 + 1, y0, wx * uy, Nm, Pm, node.u, plane_max, S);
+            tp_tap<MOMENTS>(P, h, x0, y0 + 1, ux * wy, Nm, Pm, node.u, plane_max, S);
+            tp_tap<MOMENTS>(P, h, x0 + 1, y0 + 1, wx * wy, Nm, Pm, node.u, plane_max, S);
         }
     }
-    if (wsum > 0.01f) {
-        e_prev = mk3(acc.x / wsum, acc.y / wsum, acc.z / wsum);
-        n_prev = nacc / wsum;
+    if (S.w > 0.01f) {
+        e_prev = mk3(S.acc.x / S.w, S.acc.y / S.w, S.acc.z / S.w);
+        n_prev = S.n / S.w;
+        if (MOMENTS) {
+            m1_prev = S.m1 / S.w;
+            m2_prev = S.m2 / S.w;
+        }
     }
-    if (M.cap > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, M.cap);
+    if constexpr (MOVING)
+        if (A.cap > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, A.cap);
 
-    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);
+    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);  // else the sample is not accumulated
     const bool fresh = n_prev == 0.0f;
     const float n_blend = smin(n_prev + 1.0f, P.max_history);
     const float a = 1.0f / n_blend;
     const f3 e_blend = e_prev + (e_cur - e_prev) * a;
     const f3 e = !finite ? e_prev : (fresh ? e_cur : e_blend);
     const float n = !finite ? n_prev : (fresh ? 1.0f : n_blend);
-    const bool keep = valid && (finite || !fresh);
-    if (!valid) node.u = 0xFFFFFFFFu;
+    const bool keep = valid && (finite || !fresh);  // the pixel has an accumulated colour; else its input passes through
+    if (MOMENTS) {  // l l finite (so l is) or the sample leaves the moments as they were — zeros for a fresh pixel
+        const float l = vr_lum(e_cur), l2 = l * l;
+        const bool usable = finite && tp_finite(l2);
+        const float m1_blend = m1_prev + (l - m1_prev) * a, m2_blend = m2_prev + (l2 - m2_prev) * a;
+        const float m1 = !usable ? m1_prev : (fresh ? l : m1_blend);
+        const float m2 = !usable ? m2_prev : (fresh ? l2 : m2_blend);
+        o[3] = keep ? make_float4(m1, m2, 0.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if (!valid) node.u = 0xFFFFFFFFu;  // node -1
     out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, rgbz.w) : rgbz;
-    oE = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    oP = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    oN = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
+    o[0] = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    o[1] = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    o[2] = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
 }
-
 // the motion vector of a pixel: {fx, fy, 1, 0} or zeros
 RTU_HD float4 tp_motion_vector(const TpParams& P, bool in_table, const TpMotion& T, const float4* hit) {
     f3 Pm, Nm;
@@ -275,9 +267,6 @@ RTU_HD float4 tp_motion_vector(const TpParams& P, bool in_table, const TpMotion&
 int rtu_temporal_check_desc(const RtuTemporalDesc* d);
 // RTU_OK or RTU_ERR_ARG: history_cap 0 .. 65535; with a host table, its reserved words 0 and its flags known
 int rtu_temporal_check_motion(const RtuNodeMotion* h_motion_or_null, uint32_t n_nodes, int32_t history_cap);
-// The motion form on the device: as rtu_launch_temporal, d_motion n_nodes entries, 16-byte aligned (nullptr allowed with n_nodes == 0).
-int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
-                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 // mv[i] = the motion vector of pixel i
 int rtu_launch_motion_vectors(const TpParams& p, uint32_t n_nodes, const float4* hits, const RtuNodeMotion* d_motion, float4* mv, hipStream_t stream);
 
@@ -286,6 +275,12 @@ int rtu_launch_motion_vectors(const TpParams& p, uint32_t n_nodes, const float4*
 // hist_prev. Pointers 16-byte aligned and desc checked by the caller. Returns a hipError_t as int. Asynchronous on `stream`.
 int rtu_launch_temporal(const TpParams& p, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
                         float4* rgbz_out, hipStream_t stream);
+// The motion form: d_motion n_nodes entries, 16-byte aligned (nullptr allowed with n_nodes == 0). The moments form: that with histories
+// of four planes.
+int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
+int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 // n_out[i] = the history length of pixel i (E.w of `hist`), or 0 everywhere with hist == nullptr
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream);
 

@@ -1,18 +1,20 @@
-// rtu_temporal.hip — the temporal accumulator of include/rtu_render.h ("Temporal accumulation"): its host form
-// rtu_temporal_accumulate, which is the executable statement of the rules, and the kernel of rtu_temporal_accumulate_device. Both call
-// tp_pixel of rtu_temporal.h, pixel by pixel.
+// rtu_temporal.hip — the temporal accumulator of include/rtu_render.h ("Temporal accumulation", "... across scene updates", and the
+// moments of "Variance-guided filtering"): its host forms rtu_temporal_accumulate, _motion and _moments, which are the executable
+// statement of the rules, and the kernels of their _device forms. Both call tp_pixel<MOVING, MOMENTS> of rtu_temporal.h, pixel by
+// pixel; the three forms are the instantiations <false, false>, <true, false> and <true, true> of one kernel and of one host loop.
 //
 //   k_temporal          one lane per pixel, 32 x 8 pixel workgroups as k_dn_pass (a wavefront is two rows of 32). A lane reads its
 //                       pixel's {rgbz, RtuRayHit, albedo} (80 B), up to four taps of the previous history — three 16-byte loads each,
 //                       neighbouring lanes' taps are neighbouring pixels while the surface is smooth, so the lines are shared through
 //                       the vector L1 —, and writes its pixel of the image and of the three planes of the new history (64 B). No
-//                       LDS, no atomics. The lookup mode is wave-uniform (a kernel argument).
+//                       LDS, no atomics. Without MOVING the lookup mode is wave-uniform (a kernel argument, TpParams).
+//     MOVING            a moving scene (TpMotionParams): besides, a lane reads the table entry of its pixel's node, 96 B as six
+//                       16-byte loads STRAIGHT FROM GLOBAL MEMORY: the table has no bound that LDS could hold, the lanes of a
+//                       wavefront mostly show one or two nodes — lanes with one address are served by one request — and the few
+//                       entries a frame touches stay in the vector L1. The lookup mode (none, one tap, four taps) is per lane;
+//                       single exit, select on values.
+//     MOMENTS           a four-plane history: besides, one 16-byte load of M per ACCEPTED tap and one 16-byte store.
 //   k_temporal_history  one lane per pixel: the history length out of the E plane.
-//   k_temporal_motion   k_temporal for a moving scene (tp_pixel_motion): the same lanes, workgroups, loads and stores; besides, a lane
-//                       reads the table entry of its pixel's node, 96 B as six 16-byte loads STRAIGHT FROM GLOBAL MEMORY: the table
-//                       has no bound that LDS could hold, the lanes of a wavefront mostly show one or two nodes — lanes with one
-//                       address are served by one request — and the few entries a frame touches stay in the vector L1. The lookup
-//                       mode (none, one tap, four taps) is per lane; single exit, select on values.
 //   k_motion_vectors    one lane per pixel: its RtuRayHit and its node's entry in, one float4 out.
 // Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
 // anywhere in hist_prev: hist_out must not overlap it.
@@ -23,24 +25,7 @@
 
 namespace {
 
-__global__ void __launch_bounds__(256) k_temporal(TpParams P, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
-                                                  const float4* __restrict__ hist_prev, float4* __restrict__ hist_out, float4* rgbz_out) {
-    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
-    if (x >= P.width || y >= P.height) return;
-    const size_t n = (size_t)P.width * (size_t)P.height;
-    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
-    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
-    float4 out, oE, oP, oN;
-    const float4* hP = hist_prev ? hist_prev + n : nullptr;
-    const float4* hN = hist_prev ? hist_prev + 2 * n : nullptr;
-    tp_pixel(P, hist_prev, hP, hN, x, y, rgbz[p], hit, albedo[p], out, oE, oP, oN);
-    rgbz_out[p] = out;
-    hist_out[p] = oE;
-    hist_out[n + p] = oP;
-    hist_out[2 * n + p] = oN;
-}
-
-// the table entry of a pixel (in_table) or the identity; 16-byte loads: the table is 16-byte aligned and an entry is 96 B
+// the table entry of a pixel (k >= 0) or the identity; 16-byte loads: the table is 16-byte aligned and an entry is 96 B
 __device__ TpMotion load_motion(const RtuNodeMotion* __restrict__ motion, int32_t k) {
     TpMotion T = tp_motion_identity();
     if (k >= 0) {
@@ -56,24 +41,35 @@ __device__ TpMotion load_motion(const RtuNodeMotion* __restrict__ motion, int32_
     return T;
 }
 
-__global__ void __launch_bounds__(256) k_temporal_motion(TpMotionParams M, const float4* rgbz, const float4* __restrict__ hits,
-                                                         const float4* __restrict__ albedo, const float4* __restrict__ hist_prev,
-                                                         float4* __restrict__ hist_out, float4* rgbz_out, const RtuNodeMotion* __restrict__ motion) {
+// `motion` is read with MOVING only; hist_prev and hist_out have three planes, with MOMENTS four
+template <bool MOVING, bool MOMENTS>
+__global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING> A, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
+                                                  const float4* __restrict__ hist_prev, float4* __restrict__ hist_out, float4* rgbz_out,
+                                                  const RtuNodeMotion* __restrict__ motion) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    const TpParams& P = tp_base(A);
     const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
-    if (x >= M.P.width || y >= M.P.height) return;
-    const size_t n = (size_t)M.P.width * (size_t)M.P.height;
-    const size_t p = (size_t)y * (size_t)M.P.width + (size_t)x;
+    if (x >= P.width || y >= P.height) return;
+    const size_t n = (size_t)P.width * (size_t)P.height;
+    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
     const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
-    const int32_t k = tp_motion_index(hit[0], M.n_nodes);
+    int32_t k = -1;
+    if constexpr (MOVING) k = tp_motion_index(hit[0], A.n_nodes);
     const TpMotion T = load_motion(motion, k);
-    float4 out, oE, oP, oN;
-    const float4* hP = hist_prev ? hist_prev + n : nullptr;
-    const float4* hN = hist_prev ? hist_prev + 2 * n : nullptr;
-    tp_pixel_motion(M, k >= 0, T, hist_prev, hP, hN, x, y, rgbz[p], hit, albedo[p], out, oE, oP, oN);
+    const float4* h[PLANES];
+    for (int i = 0; i < PLANES; i++) h[i] = hist_prev ? hist_prev + i * n : nullptr;
+    float4 out, o[PLANES];
+    tp_pixel<MOVING, MOMENTS>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o);
     rgbz_out[p] = out;
-    hist_out[p] = oE;
-    hist_out[n + p] = oP;
-    hist_out[2 * n + p] = oN;
+    for (int i = 0; i < PLANES; i++) hist_out[i * n + p] = o[i];
+}
+
+template <bool MOVING, bool MOMENTS>
+int launch_temporal(const TpArgs<MOVING>& a, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+                    float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
+    const dim3 grid((uint32_t)((tp_base(a).width + 31) / 32), (uint32_t)((tp_base(a).height + 7) / 8));
+    hipLaunchKernelGGL((k_temporal<MOVING, MOMENTS>), grid, dim3(256), 0, stream, a, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
+    return (int)hipGetLastError();
 }
 
 __global__ void __launch_bounds__(256) k_motion_vectors(TpParams P, uint32_t n_nodes, const float4* __restrict__ hits,
@@ -96,21 +92,22 @@ __global__ void __launch_bounds__(256) k_temporal_history(const float4* __restri
 
 int rtu_launch_temporal(const TpParams& p, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
                         float4* rgbz_out, hipStream_t stream) {
-    const dim3 grid((uint32_t)((p.width + 31) / 32), (uint32_t)((p.height + 7) / 8));
-    hipLaunchKernelGGL(k_temporal, grid, dim3(256), 0, stream, p, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out);
-    return (int)hipGetLastError();
+    return launch_temporal<false, false>(p, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, nullptr, stream);
+}
+
+int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
+    return launch_temporal<true, false>(m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
+}
+
+int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
+    return launch_temporal<true, true>(m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
 }
 
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream) {
     if (pixels == 0) return (int)hipSuccess;
     hipLaunchKernelGGL(k_temporal_history, dim3((uint32_t)((pixels + 255) / 256)), dim3(256), 0, stream, hist, n_out, (unsigned long long)pixels);
-    return (int)hipGetLastError();
-}
-
-int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
-                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
-    const dim3 grid((uint32_t)((m.P.width + 31) / 32), (uint32_t)((m.P.height + 7) / 8));
-    hipLaunchKernelGGL(k_temporal_motion, grid, dim3(256), 0, stream, m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
     return (int)hipGetLastError();
 }
 
@@ -148,6 +145,48 @@ int rtu_temporal_check_desc(const RtuTemporalDesc* d) {
     return RTU_OK;
 }
 
+// the three host forms: motion, n_nodes and history_cap are read with MOVING only; the histories have three planes, with MOMENTS four
+template <bool MOVING, bool MOMENTS>
+static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz, const RtuRayHit* h_hits,
+                           const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion,
+                           uint32_t n_nodes, int32_t history_cap) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
+    if (MOVING && (!motion || rtu_temporal_check_motion(motion, n_nodes, history_cap) != RTU_OK)) return RTU_ERR_ARG;
+    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return RTU_ERR_ARG;
+    const int W = desc->width, H = desc->height;
+    const size_t n = (size_t)W * (size_t)H;
+    if (h_hist_prev) {  // taps read anywhere in the previous history
+        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 16 * PLANES * n;
+        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
+    }
+    TpArgs<MOVING> A;
+    if constexpr (MOVING) A = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
+    else A = tp_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr);
+    std::vector<float4> prev;  // (the planes as float4: the caller's floats need not be 16-byte aligned)
+    const float4* hp[PLANES] = {};
+    if (h_hist_prev) {
+        prev.resize(PLANES * n);
+        for (size_t i = 0; i < PLANES * n; i++) prev[i] = f4(h_hist_prev, i);
+        for (int i = 0; i < PLANES; i++) hp[i] = prev.data() + i * n;
+    }
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t p = (size_t)y * (size_t)W + (size_t)x;
+            const float* h = reinterpret_cast<const float*>(h_hits + p);
+            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
+            const int32_t k = MOVING ? tp_motion_index(hit[0], n_nodes) : -1;
+            float4 out, o[PLANES];
+            tp_pixel<MOVING, MOMENTS>(A, k >= 0, host_motion(motion, k), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o);
+            st4(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
+            for (int i = 0; i < PLANES; i++) st4(h_hist_out, i * n + p, o[i]);
+        }
+    return RTU_OK;
+}
+
 extern "C" {
 
 int rtu_temporal_defaults(RtuTemporalDesc* out) {
@@ -161,83 +200,19 @@ int rtu_temporal_defaults(RtuTemporalDesc* out) {
 
 int rtu_temporal_accumulate(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
                             const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out) {
-    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
-    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
-    if (!prev_cam) prev_cam = cur_cam;
-    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
-        return RTU_ERR_ARG;
-    const int W = desc->width, H = desc->height;
-    const size_t n = (size_t)W * (size_t)H;
-    if (h_hist_prev) {  // taps read anywhere in the previous history
-        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 48 * n;
-        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
-    }
-    const TpParams P = tp_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr);
-    std::vector<float4> prev;  // (the planes as float4: the caller's floats need not be 16-byte aligned)
-    if (h_hist_prev) {
-        prev.resize(3 * n);
-        for (size_t i = 0; i < 3 * n; i++) prev[i] = make_float4(h_hist_prev[4 * i], h_hist_prev[4 * i + 1], h_hist_prev[4 * i + 2], h_hist_prev[4 * i + 3]);
-    }
-    const float4* hE = h_hist_prev ? prev.data() : nullptr;
-    const float4* hP = h_hist_prev ? prev.data() + n : nullptr;
-    const float4* hN = h_hist_prev ? prev.data() + 2 * n : nullptr;
-    auto f4 = [](const float* p, size_t i) { return make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); };
-    auto st = [](float* p, size_t i, const float4& v) { p[4 * i] = v.x; p[4 * i + 1] = v.y; p[4 * i + 2] = v.z; p[4 * i + 3] = v.w; };
-    for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) {
-            const size_t p = (size_t)y * (size_t)W + (size_t)x;
-            const float* h = reinterpret_cast<const float*>(h_hits + p);
-            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
-            float4 out, oE, oP, oN;
-            tp_pixel(P, hE, hP, hN, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, oE, oP, oN);
-            st(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
-            st(h_hist_out, p, oE);
-            st(h_hist_out, n + p, oP);
-            st(h_hist_out, 2 * n + p, oN);
-        }
-    return RTU_OK;
+    return accumulate_host<false, false>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, nullptr, 0, 0);
 }
 
 int rtu_temporal_accumulate_motion(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
                                    const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
                                    const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap) {
-    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out || !motion) return RTU_ERR_ARG;
-    if (rtu_temporal_check_motion(motion, n_nodes, history_cap) != RTU_OK) return RTU_ERR_ARG;
-    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
-    if (!prev_cam) prev_cam = cur_cam;
-    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
-        return RTU_ERR_ARG;
-    const int W = desc->width, H = desc->height;
-    const size_t n = (size_t)W * (size_t)H;
-    if (h_hist_prev) {  // taps read anywhere in the previous history
-        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 48 * n;
-        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
-    }
-    const TpMotionParams M = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
-    std::vector<float4> prev;
-    if (h_hist_prev) {
-        prev.resize(3 * n);
-        for (size_t i = 0; i < 3 * n; i++) prev[i] = make_float4(h_hist_prev[4 * i], h_hist_prev[4 * i + 1], h_hist_prev[4 * i + 2], h_hist_prev[4 * i + 3]);
-    }
-    const float4* hE = h_hist_prev ? prev.data() : nullptr;
-    const float4* hP = h_hist_prev ? prev.data() + n : nullptr;
-    const float4* hN = h_hist_prev ? prev.data() + 2 * n : nullptr;
-    auto f4 = [](const float* p, size_t i) { return make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); };
-    auto st = [](float* p, size_t i, const float4& v) { p[4 * i] = v.x; p[4 * i + 1] = v.y; p[4 * i + 2] = v.z; p[4 * i + 3] = v.w; };
-    for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) {
-            const size_t p = (size_t)y * (size_t)W + (size_t)x;
-            const float* h = reinterpret_cast<const float*>(h_hits + p);
-            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
-            const int32_t k = tp_motion_index(hit[0], n_nodes);
-            float4 out, oE, oP, oN;
-            tp_pixel_motion(M, k >= 0, host_motion(motion, k), hE, hP, hN, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, oE, oP, oN);
-            st(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
-            st(h_hist_out, p, oE);
-            st(h_hist_out, n + p, oP);
-            st(h_hist_out, 2 * n + p, oN);
-        }
-    return RTU_OK;
+    return accumulate_host<true, false>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes, history_cap);
+}
+
+int rtu_temporal_accumulate_moments(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                    const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
+                                    const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap) {
+    return accumulate_host<true, true>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes, history_cap);
 }
 
 int rtu_motion_vectors(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuNodeMotion* motion, uint32_t n_nodes,

@@ -1,13 +1,10 @@
 // rtu_variance.h — the arithmetic of the variance-guided preview filter (include/rtu_render.h "Variance-guided filtering"), host +
 // device, and the launch interface of its kernels (rtu_variance.hip), called by rtu_capi.hip:
-//   vr_pixel_moments    rtu_temporal_accumulate_moments: tp_pixel_motion of rtu_temporal.h on a history with a fourth plane M
 //   vr_variance_pixel   rtu_variance: the variance of the accumulated mean out of E.n and M
 //   vd_*                rtu_denoise_variance: the a-trous passes of rtu_denoise.h with a per-pixel colour edge-stop
+// The moments themselves are accumulated by tp_pixel<true, true> of rtu_temporal.h (a MOMENTS HISTORY, vr_lum).
 // No transcendental function: the translation units that include this header are compiled with -ffp-contract=off and IEEE divides
 // and square roots, every operation below rounds once, so the host forms and the kernels give the same bits.
-//
-// A MOMENTS HISTORY is the three planes of rtu_temporal.h and a fourth:  M = {m1, m2, 0, 0}, the running first and second moment of
-// the luminance of the demodulated sample.
 #ifndef RTU_VARIANCE_H_INCLUDED
 #define RTU_VARIANCE_H_INCLUDED
 
@@ -15,96 +12,7 @@
 
 #define VR_EPS 1e-8f  // added to sigma_lum^2 g3(v): a pixel without variance still accepts taps of its own luminance
 
-// l(e) of a demodulated colour
-RTU_HD float vr_lum(const f3& e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z; }
-
-// ---- 1. moments in the history ---------------------------------------------------------------------------------------------------
-// tp_tap with the moments: an ACCEPTED tap also adds M_q.xy w to macc.
-RTU_HD void vr_tap(const TpParams& P, const float4* hE, const float4* hP, const float4* hN, const float4* hM, int qx, int qy, float w, const f3& Np,
-                   const f3& Pp, uint32_t node, float plane_max, f3& acc, float& nacc, float& wsum, float& m1acc, float& m2acc) {
-    if (qx < 0 || qy < 0 || qx >= P.width || qy >= P.height) return;
-    const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-    const float4 Eq = hE[q], Pq = hP[q], Nq = hN[q];
-    union { float f; uint32_t u; } nb;
-    nb.f = Nq.w;
-    if (!(Eq.w > 0.0f) || nb.u != node) return;
-    if (!(dot3(Np, mk3(Nq.x, Nq.y, Nq.z)) >= P.normal_min)) return;
-    if (!(fabsf(dot3(Np, mk3(Pq.x, Pq.y, Pq.z) - Pp)) <= plane_max)) return;
-    const float4 Mq = hM[q];
-    acc = acc + mk3(Eq.x, Eq.y, Eq.z) * w;
-    nacc = nacc + Eq.w * w;
-    wsum = wsum + w;
-    m1acc = m1acc + Mq.x * w;
-    m2acc = m2acc + Mq.y * w;
-}
-
-// tp_pixel_motion with the moments: every expression that makes out, oE, oP, oN is that of tp_pixel_motion, in its order. oM: the
-// pixel of the fourth plane.
-RTU_HD void vr_pixel_moments(const TpMotionParams& M, bool in_table, const TpMotion& T, const float4* hE, const float4* hP, const float4* hN,
-                             const float4* hM, int x, int y, const float4& rgbz, const float4* hit, const float4& albedo, float4& out, float4& oE,
-                             float4& oP, float4& oN, float4& oM) {
-    const TpParams& P = M.P;
-    union { float f; uint32_t u; } flags, node;
-    flags.f = hit[0].z;
-    node.f = hit[0].y;
-    const bool valid = (flags.u & RTU_RAY_HIT) != 0;
-    const f3 d = dn_demod(albedo);
-    const f3 e_cur = mk3(rgbz.x / d.x, rgbz.y / d.y, rgbz.z / d.z);
-    const f3 Pp = mk3(hit[1].x, hit[1].y, hit[1].z), Np = mk3(hit[2].x, hit[2].y, hit[2].z);
-    const float plane_max = P.sigma_plane * hit[0].x;
-
-    f3 Pm, Nm;
-    const bool look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && valid && P.lookup != TP_LOOKUP_NONE;
-    const bool one_tap = look && M.same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
-
-    f3 acc = mk3(0.0f, 0.0f, 0.0f), e_prev = mk3(0.0f, 0.0f, 0.0f);
-    float nacc = 0.0f, wsum = 0.0f, n_prev = 0.0f, m1acc = 0.0f, m2acc = 0.0f, m1_prev = 0.0f, m2_prev = 0.0f;
-    if (one_tap) {
-        vr_tap(P, hE, hP, hN, hM, x, y, 1.0f, Nm, Pm, node.u, plane_max, acc, nacc, wsum, m1acc, m2acc);
-    } else if (look) {
-        float fx, fy;
-        if (tp_project(P, Pm, fx, fy) && fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {
-            const float flx = floorf(fx), fly = floorf(fy);
-            const int x0 = (int)flx, y0 = (int)fly;
-            const float wx = fx - flx, wy = fy - fly;
-            const float ux = 1.0f - wx, uy = 1.0f - wy;
-            vr_tap(P, hE, hP, hN, hM, x0, y0, ux * uy, Nm, Pm, node.u, plane_max, acc, nacc, wsum, m1acc, m2acc);
-            vr_tap(P, hE, hP, hN, hM, x0 + 1, y0, wx * uy, Nm, Pm, node.u, plane_max, acc, nacc, wsum, m1acc, m2acc);
-            vr_tap(P, hE, hP, hN, hM, x0, y0 + 1, ux * wy, Nm, Pm, node.u, plane_max, acc, nacc, wsum, m1acc, m2acc);
-            vr_tap(P, hE, hP, hN, hM, x0 + 1, y0 + 1, wx * wy, Nm, Pm, node.u, plane_max, acc, nacc, wsum, m1acc, m2acc);
-        }
-    }
-    if (wsum > 0.01f) {
-        e_prev = mk3(acc.x / wsum, acc.y / wsum, acc.z / wsum);
-        n_prev = nacc / wsum;
-        m1_prev = m1acc / wsum;
-        m2_prev = m2acc / wsum;
-    }
-    if (M.cap > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, M.cap);
-
-    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);
-    const bool fresh = n_prev == 0.0f;
-    const float n_blend = smin(n_prev + 1.0f, P.max_history);
-    const float a = 1.0f / n_blend;
-    const f3 e_blend = e_prev + (e_cur - e_prev) * a;
-    const f3 e = !finite ? e_prev : (fresh ? e_cur : e_blend);
-    const float n = !finite ? n_prev : (fresh ? 1.0f : n_blend);
-    const bool keep = valid && (finite || !fresh);
-    // the moments: l l finite (so l is) or the sample leaves them as they were — zeros for a fresh pixel
-    const float l = vr_lum(e_cur), l2 = l * l;
-    const bool usable = finite && tp_finite(l2);
-    const float m1_blend = m1_prev + (l - m1_prev) * a, m2_blend = m2_prev + (l2 - m2_prev) * a;
-    const float m1 = !usable ? m1_prev : (fresh ? l : m1_blend);
-    const float m2 = !usable ? m2_prev : (fresh ? l2 : m2_blend);
-    if (!valid) node.u = 0xFFFFFFFFu;
-    out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, rgbz.w) : rgbz;
-    oE = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    oP = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    oN = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
-    oM = keep ? make_float4(m1, m2, 0.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// ---- 2. the variance of the accumulated mean -------------------------------------------------------------------------------------
+// ---- 1. the variance of the accumulated mean -------------------------------------------------------------------------------------
 struct VrParams {
     int32_t width, height, nlog2;
     float   min_history, sigma_plane;
@@ -174,7 +82,7 @@ RTU_HD float vr_variance_pixel(const VrParams& V, const float4* hE, const float4
     return live ? var / n : 0.0f;
 }
 
-// ---- 3. the filter ---------------------------------------------------------------------------------------------------------------
+// ---- 2. the filter ---------------------------------------------------------------------------------------------------------------
 // Four planes of one float4 per pixel, as rtu_denoise.h:
 //   gN = {N.xyz, valid ? 1 : 0}      gP = {p.xyz, 1 / (sigma_plane * t)}      e = {demodulated rgb, v}, two of them, ping-pong
 RTU_HD void vd_prepare(const float4& rgbz, const float4* hit, const float4& albedo, float v, float sigma_plane, float4& gN, float4& gP, float4& e) {
@@ -251,9 +159,6 @@ RTU_HD float4 vd_pass_pixel(const float4* gN, const float4* gP, const float4* e,
 // RTU_OK or RTU_ERR_ARG: the rules of RtuVarianceDesc (include/rtu_render.h)
 int rtu_variance_check_desc(const RtuVarianceDesc* d);
 
-// The moments form on the device: as rtu_launch_temporal_motion with histories of four planes.
-int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
-                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 // v[i] = the variance of pixel i: hist four planes of width * height float4, hits width * height RtuRayHit
 int rtu_launch_variance(const VrParams& V, const float4* hist, const float4* hits, float* v, hipStream_t stream);
 // The filter on the device: as rtu_launch_denoise, v width * height floats; planes four arrays of width * height float4.

@@ -1,10 +1,7 @@
-// rtu_variance.hip — the variance-guided preview filter of include/rtu_render.h ("Variance-guided filtering"): its three host forms
-// rtu_temporal_accumulate_moments, rtu_variance and rtu_denoise_variance, which are the executable statement of the rules, and the
-// kernels of their _device forms. Both call the same functions of rtu_variance.h, pixel by pixel.
+// rtu_variance.hip — the variance-guided preview filter of include/rtu_render.h ("Variance-guided filtering"): its host forms
+// rtu_variance and rtu_denoise_variance, which are the executable statement of the rules, and the kernels of their _device forms.
+// Both call the same functions of rtu_variance.h, pixel by pixel. (The moments they read are accumulated by rtu_temporal.hip.)
 //
-//   k_temporal_moments  k_temporal_motion of rtu_temporal.hip on a four-plane history: the same lanes (one per pixel), 32 x 8 pixel
-//                       workgroups, loads and stores, and besides one 16-byte load of M per ACCEPTED tap and one 16-byte store. The
-//                       lookup mode is per lane; single exit, select on values.
 //   k_variance          one lane per pixel: its E, M and the first float4 of its RtuRayHit in, one float out. Only a lane whose history is
 //                       shorter than min_history walks the 7 x 7 window (five 16-byte loads per usable tap); the other lanes of its
 //                       wavefront wait for it and do nothing else.
@@ -19,52 +16,12 @@
 //                       flight together, 0.169 ms per pass. LAST: the pass writes the output image instead
 //                       of a plane.
 // A pass reads plane e[i & 1] and writes e[(i + 1) & 1]; only the last touches rgbz_out, each lane its own pixel after reading that
-// pixel of rgbz_in — so rgbz_out == rgbz_in is allowed. Taps of k_temporal_moments read anywhere in hist_prev: hist_out must not
-// overlap it.
+// pixel of rgbz_in — so rgbz_out == rgbz_in is allowed.
 #include "rtu_variance.h"
 
-#include <cstring>
 #include <vector>
 
 namespace {
-
-// the table entry of a pixel or the identity (rtu_temporal.hip load_motion)
-__device__ TpMotion vr_load_motion(const RtuNodeMotion* __restrict__ motion, int32_t k) {
-    TpMotion T = tp_motion_identity();
-    if (k >= 0) {
-        const float4* e = reinterpret_cast<const float4*>(motion + k);
-        const float4 a = e[0], b = e[1], c = e[2], d = e[3], f = e[4], g = e[5];
-        union { float f; uint32_t u; } fl;
-        fl.f = g.y;
-        T.m[0] = a.x; T.m[1] = a.y; T.m[2] = a.z; T.m[3] = a.w; T.m[4] = b.x; T.m[5] = b.y; T.m[6] = b.z; T.m[7] = b.w;
-        T.m[8] = c.x; T.m[9] = c.y; T.m[10] = c.z; T.m[11] = c.w;
-        T.g[0] = d.x; T.g[1] = d.y; T.g[2] = d.z; T.g[3] = d.w; T.g[4] = f.x; T.g[5] = f.y; T.g[6] = f.z; T.g[7] = f.w; T.g[8] = g.x;
-        T.flags = fl.u;
-    }
-    return T;
-}
-
-__global__ void __launch_bounds__(256) k_temporal_moments(TpMotionParams M, const float4* rgbz, const float4* __restrict__ hits,
-                                                          const float4* __restrict__ albedo, const float4* __restrict__ hist_prev,
-                                                          float4* __restrict__ hist_out, float4* rgbz_out, const RtuNodeMotion* __restrict__ motion) {
-    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
-    if (x >= M.P.width || y >= M.P.height) return;
-    const size_t n = (size_t)M.P.width * (size_t)M.P.height;
-    const size_t p = (size_t)y * (size_t)M.P.width + (size_t)x;
-    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
-    const int32_t k = tp_motion_index(hit[0], M.n_nodes);
-    const TpMotion T = vr_load_motion(motion, k);
-    float4 out, oE, oP, oN, oM;
-    const float4* hP = hist_prev ? hist_prev + n : nullptr;
-    const float4* hN = hist_prev ? hist_prev + 2 * n : nullptr;
-    const float4* hM = hist_prev ? hist_prev + 3 * n : nullptr;
-    vr_pixel_moments(M, k >= 0, T, hist_prev, hP, hN, hM, x, y, rgbz[p], hit, albedo[p], out, oE, oP, oN, oM);
-    rgbz_out[p] = out;
-    hist_out[p] = oE;
-    hist_out[n + p] = oP;
-    hist_out[2 * n + p] = oN;
-    hist_out[3 * n + p] = oM;
-}
 
 __global__ void __launch_bounds__(256) k_variance(VrParams V, const float4* __restrict__ hist, const float4* __restrict__ hits, float* __restrict__ v) {
     const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
@@ -100,27 +57,7 @@ __global__ void __launch_bounds__(256) k_vd_pass(const float4* __restrict__ gN, 
     else e_out[p] = e;
 }
 
-TpMotion host_motion(const RtuNodeMotion* motion, int32_t k) {
-    TpMotion T = tp_motion_identity();
-    if (k >= 0) {
-        memcpy(T.m, motion[k].m, sizeof T.m);
-        memcpy(T.g, motion[k].g, sizeof T.g);
-        T.flags = motion[k].flags;
-    }
-    return T;
-}
-
-float4 f4(const float* p, size_t i) { return make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); }
-void st4(float* p, size_t i, const float4& v) { p[4 * i] = v.x; p[4 * i + 1] = v.y; p[4 * i + 2] = v.z; p[4 * i + 3] = v.w; }
-
 }  // namespace
-
-int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
-                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
-    const dim3 grid((uint32_t)((m.P.width + 31) / 32), (uint32_t)((m.P.height + 7) / 8));
-    hipLaunchKernelGGL(k_temporal_moments, grid, dim3(256), 0, stream, m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
-    return (int)hipGetLastError();
-}
 
 int rtu_launch_variance(const VrParams& V, const float4* hist, const float4* hits, float* v, hipStream_t stream) {
     const dim3 grid((uint32_t)((V.width + 31) / 32), (uint32_t)((V.height + 7) / 8));
@@ -168,48 +105,6 @@ int rtu_variance_defaults(RtuVarianceDesc* out) {
     out->sigma_plane = 0.05f;
     out->normal_log2_power = 5;
     out->min_history = 4;
-    return RTU_OK;
-}
-
-int rtu_temporal_accumulate_moments(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
-                                    const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
-                                    const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap) {
-    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out || !motion) return RTU_ERR_ARG;
-    if (rtu_temporal_check_motion(motion, n_nodes, history_cap) != RTU_OK) return RTU_ERR_ARG;
-    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
-    if (!prev_cam) prev_cam = cur_cam;
-    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
-        return RTU_ERR_ARG;
-    const int W = desc->width, H = desc->height;
-    const size_t n = (size_t)W * (size_t)H;
-    if (h_hist_prev) {  // taps read anywhere in the previous history
-        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 64 * n;
-        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
-    }
-    const TpMotionParams M = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
-    std::vector<float4> prev;  // (the planes as float4: the caller's floats need not be 16-byte aligned)
-    if (h_hist_prev) {
-        prev.resize(4 * n);
-        for (size_t i = 0; i < 4 * n; i++) prev[i] = f4(h_hist_prev, i);
-    }
-    const float4* hE = h_hist_prev ? prev.data() : nullptr;
-    const float4* hP = h_hist_prev ? prev.data() + n : nullptr;
-    const float4* hN = h_hist_prev ? prev.data() + 2 * n : nullptr;
-    const float4* hM = h_hist_prev ? prev.data() + 3 * n : nullptr;
-    for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) {
-            const size_t p = (size_t)y * (size_t)W + (size_t)x;
-            const float* h = reinterpret_cast<const float*>(h_hits + p);
-            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
-            const int32_t k = tp_motion_index(hit[0], n_nodes);
-            float4 out, oE, oP, oN, oM;
-            vr_pixel_moments(M, k >= 0, host_motion(motion, k), hE, hP, hN, hM, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, oE, oP, oN, oM);
-            st4(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
-            st4(h_hist_out, p, oE);
-            st4(h_hist_out, n + p, oP);
-            st4(h_hist_out, 2 * n + p, oN);
-            st4(h_hist_out, 3 * n + p, oM);
-        }
     return RTU_OK;
 }
 

@@ -1,5 +1,5 @@
 """GPU: temporal accumulation across scene updates (include/rtu_render.h "Temporal accumulation across scene updates"). The device
-accumulator (rtu_temporal_accumulate_motion_device, k_temporal_motion) and the device motion vectors against their host forms (which
+accumulator (rtu_temporal_accumulate_motion_device, k_temporal<true, false>) and the device motion vectors against their host forms (which
 tests/test_temporal_motion_host.py holds to the rules), bit for bit; a session's moved frames against the same thing assembled by hand
 from existing entries on the updated context; the session's contract."""
 import ctypes

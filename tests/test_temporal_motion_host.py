@@ -4,7 +4,7 @@ table of rtu_scene_motion against a numpy binary64 composition of the same node 
 five frames; and its effect on the oracle's own path-traced samples of a scene whose teapot moves.
 
 The restatement extends np_temporal of tests/test_temporal_host.py: whole float32 arrays, one operation at a time in the order of the
-rules, so every pixel sees the binary32 operations of tp_pixel_motion (raytracer-utah_amd/csrc/rtu_temporal.h) in their order."""
+rules, so every pixel sees the binary32 operations of tp_pixel with MOVING (raytracer-utah_amd/csrc/rtu_temporal.h) in their order."""
 import ctypes
 import math
 
