@@ -906,6 +906,89 @@ int  rtu_denoise_variance_device(RtuContext* ctx, const RtuVarianceDesc* desc, c
                                  const void* d_v, void* d_out, void* hip_stream);
 RtuTemporal* rtu_temporal_begin_variance(RtuContext* ctx, const RtuTemporalDesc* temporal_desc, const RtuVarianceDesc* variance_desc, int* err_out);
 
+/* ---- Steered sampling: a budget of extra rays per frame, spent where the variance is highest (rtu_steer.h, rtu_steer.hip) ----
+ * A variance session fires one new sample per pixel whatever the pixel's history. The entries below spend `budget` further rays of a
+ * frame on the pixels whose accumulated mean is least certain, and fold what they bring into the history before it is filtered. All
+ * weights are integers and their sum is exact: the allocation does not depend on the order in which anything is added, and host and
+ * device forms give the same words. The floating-point expressions are binary32, one rounding per operation, no contraction, IEEE
+ * divisions, in this order. VALID, d, e, l(e) as in "Temporal accumulation" and "Variance-guided filtering"; p is the pixel's index
+ * x + width * y; mix32 is that of "Sample streams of recipe S".
+ *
+ * 1. ALLOCATION  rtu_sample_allocation: out of a moments history, the RtuRayHit of its frame and the variance v of rtu_variance,
+ *   uint32 counts[pixels], uint32 offsets[pixels] and the total.
+ *     w = 0 unless p is VALID and E_p.n > 0.
+ *     x = (v_p / (M_p.x * M_p.x + 1.0f)) * 16777216.0f: the variance of the mean — absolute where the mean luminance is small
+ *       against 1, relative to its square where it is large.
+ *     w = 0 if x is a NaN or not > 0; otherwise w = x >= 1048576.0f ? 1048576 : (uint32_t)x.
+ *     Wsum = the sum of w over all pixels, in 64 bits. Wsum == 0: every count is 0.
+ *     h = mix32(p + 0x9e3779b9u * (frame_index + 1u)) >> 16                          (a dither of 16 bits per pixel and frame)
+ *     c = (budget * w + ((h * Wsum) >> 16)) / Wsum in 64-bit unsigned arithmetic, then c = min(c, max_extra).
+ *     o = the exclusive scan of c in pixel order; THE CUT: offsets_p = min(o_p, budget), counts_p = min(c_p, budget - offsets_p),
+ *     total = min(sum of c, budget). So offsets is the exclusive scan of counts, and total <= budget.
+ *   Without the dither a budget below one ray per pixel would floor to nothing; with it the expected count of a pixel is its share.
+ *
+ * 2. THE EXTRA RAYS  rtu_extra_sample_rays: with S = frame->samples >= 1, E = max_extra, k = frame_index and F = `frame` with
+ *   samples = S * (1 + E): ray offsets_p + j (j < counts_p) and its key are those of pixel p in
+ *   rtu_camera_sample_rays(F, S + (k mod S) * E + j), bit for bit, and owner[offsets_p + j] = p. The sample indices are disjoint
+ *   from 0 .. S - 1 and distinct over (k mod S, j): every extra sample is a sample image of a recipe S / P frame of S * (1 + E)
+ *   samples. `capacity` is the number of rays, keys and owners the output arrays hold.
+ *
+ * 3. THE FOLD  rtu_temporal_refine: the shaded {r, g, b, t} of the extra rays folded into the planes E and M of a moments history and
+ *   into rgbz, all in place. For a VALID pixel with E.n > 0 and counts_p > 0, for j = 0 .. counts_p - 1 in order, with c the rgb of
+ *   rgbt[offsets_p + j]:
+ *     a channel of c is not finite: the sample is skipped.
+ *     otherwise e_cur = c / d;  n = min(n + 1, max_history);  A = 1 / n;  e = e + (e_cur - e) * A;
+ *     l = l(e_cur), l2 = l * l; if l2 is finite m1 = m1 + (l - m1) * A and m2 = m2 + (l2 - m2) * A (the skip rule of the moments).
+ *   Then E = {e, n}, M.xy = {m1, m2}, rgb = e * d. The planes P and N, z and every other pixel pass bit for bit. So a pixel with one
+ *   extra sample gets the bits a second rtu_temporal_accumulate_moments on the STATIC one-tap path would give it (where no component
+ *   of E is a negative zero). Of desc only width, height and max_history are used (the others must still be valid).
+ *
+ * RTU_ERR_ARG: a NULL pointer; width or height outside 1 .. 65536 or more than 2^26 pixels; budget above 2^26; max_extra outside
+ * 1 .. 15; a non-zero reserved word; a frame of another size than the desc, with samples < 1 or S * (1 + E) > 65536; capacity or
+ * n_rays above 2^26; a device pointer that is not 16-byte aligned (counts, offsets, keys, owner, total: 4-byte). The host forms — pure
+ * host code, no GPU and no context — also refuse a count above max_extra (rays) and a pixel whose offsets_p + counts_p exceeds
+ * capacity / n_rays. THE DEVICE FORMS TRUST counts AND offsets but never leave the arrays: a count is taken as min(count, max_extra),
+ * a ray or sample at or beyond capacity / n_rays is not written / not read. They are asynchronous on hip_stream and need no scene.
+ * rtu_sample_allocation_device (k_steer_weight: a reduction per workgroup and one 64-bit atomic add each; k_steer_counts,
+ * k_steer_sums, k_steer_finish: a three-step scan) keeps 4 B per pixel and per 1024 pixels in a grow-only buffer of the context: one
+ * stream per context, nothing allocated from the second call at a size. rtu_extra_sample_rays_device (k_steer_rays) and
+ * rtu_temporal_refine_device (k_refine), one lane per pixel, allocate nothing and touch no state of the context.
+ *
+ * THE SESSION  rtu_temporal_begin_steered opens a variance session whose frames, plain and moved, continue after step 3 and
+ * rtu_variance_device with: the allocation, frame_index = the session's frame counter k of this frame; the extra rays; their shading
+ * by the unchanged rtu_shade_rays_sampled_device / rtu_shade_rays_paths_device path of step 2 with n = the total, which is read back
+ * (4 bytes; this part of a frame is synchronous already); the fold into the new history and d_rgbz; rtu_variance_device again on the
+ * folded history; then the filter. steer_desc: width, height and frame_index are ignored. budget == 0 gives a variance session's
+ * bits and launches nothing more. A frame needs S * (1 + max_extra) <= 65536. rtu_temporal_extra_counts_device writes width * height
+ * uint32: the counts of the last frame (zeros before the first, after a reset and with budget 0); rtu_temporal_steer_total returns
+ * their sum. Counts, offsets, and min(budget, pixels * max_extra) rays, keys, owners and results (68 B each) belong to the session; a
+ * frame allocates nothing after the first. Everything else as for a variance session. Measured error ratios and times are in
+ * DESIGN.md section 26. */
+typedef struct RtuSteerDesc {      /* 32 B */
+    int32_t  width, height;
+    uint32_t budget;               /* 0 .. 2^26: extra rays per frame, at most */
+    int32_t  max_extra;            /* 1 .. 15: extra rays per pixel, at most */
+    uint32_t frame_index;          /* varies the dither from frame to frame, and selects the extra samples */
+    uint32_t reserved[3];          /* must be 0 */
+} RtuSteerDesc;
+int  rtu_steer_defaults(RtuSteerDesc* out);   /* width, height 0; budget 0, max_extra 3, frame_index 0 */
+int  rtu_sample_allocation(const RtuSteerDesc* desc, const float* h_hist, const RtuRayHit* h_hits, const float* h_v, uint32_t* counts,
+                           uint32_t* offsets, uint32_t* total);
+int  rtu_sample_allocation_device(RtuContext* ctx, const RtuSteerDesc* desc, const void* d_hist, const void* d_hits, const void* d_v,
+                                  void* d_counts, void* d_offsets, void* d_total, void* hip_stream);
+int  rtu_extra_sample_rays(const RtuSteerDesc* desc, const RtuFrameDesc* frame, const uint32_t* counts, const uint32_t* offsets, size_t capacity,
+                           RtuRay* rays_out, uint32_t* keys_out, uint32_t* owner_out);
+int  rtu_extra_sample_rays_device(RtuContext* ctx, const RtuSteerDesc* desc, const RtuFrameDesc* frame, const void* d_counts, const void* d_offsets,
+                                  size_t capacity, void* d_rays, void* d_keys, void* d_owner, void* hip_stream);
+int  rtu_temporal_refine(const RtuTemporalDesc* desc, float* h_hist, const RtuRayHit* h_hits, const float* h_albedo, const uint32_t* counts,
+                         const uint32_t* offsets, const float* h_rgbt, size_t n_rays, float* h_rgbz);
+int  rtu_temporal_refine_device(RtuContext* ctx, const RtuTemporalDesc* desc, void* d_hist, const void* d_hits, const void* d_albedo,
+                                const void* d_counts, const void* d_offsets, const void* d_rgbt, size_t n_rays, void* d_rgbz, void* hip_stream);
+RtuTemporal* rtu_temporal_begin_steered(RtuContext* ctx, const RtuTemporalDesc* temporal_desc, const RtuVarianceDesc* variance_desc,
+                                        const RtuSteerDesc* steer_desc, int* err_out);
+int  rtu_temporal_extra_counts_device(RtuTemporal* t, void* d_counts, void* hip_stream);
+int  rtu_temporal_steer_total(RtuTemporal* t, uint32_t* total_out);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

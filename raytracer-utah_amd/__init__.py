@@ -168,7 +168,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_temporal_free", "rtu_scene_motion", "rtu_temporal_accumulate_motion", "rtu_temporal_accumulate_motion_device",
                "rtu_motion_vectors", "rtu_motion_vectors_device", "rtu_temporal_frame_moved_device", "rtu_temporal_frame_moved",
                "rtu_variance_defaults", "rtu_temporal_accumulate_moments", "rtu_temporal_accumulate_moments_device", "rtu_variance",
-               "rtu_variance_device", "rtu_denoise_variance", "rtu_denoise_variance_device", "rtu_temporal_begin_variance"]
+               "rtu_variance_device", "rtu_denoise_variance", "rtu_denoise_variance_device", "rtu_temporal_begin_variance",
+               "rtu_steer_defaults", "rtu_sample_allocation", "rtu_sample_allocation_device", "rtu_extra_sample_rays",
+               "rtu_extra_sample_rays_device", "rtu_temporal_refine", "rtu_temporal_refine_device", "rtu_temporal_begin_steered",
+               "rtu_temporal_extra_counts_device", "rtu_temporal_steer_total"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -639,6 +642,116 @@ def denoise_variance(rgbz, hits, albedo, v, desc=None):
         raise RtuError(rc, "rtu_denoise_variance: an empty image or a descriptor outside its rules (n_passes 1..8, sigmas > 0, "
                            "normal_log2_power 0..7, min_history 1..65535, reserved words 0)")
     return out
+
+
+# steered sampling (include/rtu_render.h, "Steered sampling")
+class RtuSteerDesc(ctypes.Structure):
+    """include/rtu_render.h RtuSteerDesc (32 bytes): the size of the image, the budget of extra rays of a frame, the most a pixel gets,
+    and the frame's index."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("budget", ctypes.c_uint32), ("max_extra", ctypes.c_int32),
+                ("frame_index", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+_sig(hip, "rtu_steer_defaults", _I, ctypes.POINTER(RtuSteerDesc))
+_sig(hip, "rtu_sample_allocation", _I, ctypes.POINTER(RtuSteerDesc), _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_sample_allocation_device", _I, _P, ctypes.POINTER(RtuSteerDesc), _P, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_extra_sample_rays", _I, ctypes.POINTER(RtuSteerDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, ctypes.c_size_t, _P, _P, _P)
+_sig(hip, "rtu_extra_sample_rays_device", _I, _P, ctypes.POINTER(RtuSteerDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, ctypes.c_size_t, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_refine", _I, ctypes.POINTER(RtuTemporalDesc), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P)
+_sig(hip, "rtu_temporal_refine_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P)
+_sig(hip, "rtu_temporal_begin_steered", _P, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuVarianceDesc), ctypes.POINTER(RtuSteerDesc),
+     ctypes.POINTER(_I))
+_sig(hip, "rtu_temporal_extra_counts_device", _I, _P, _P, _P)
+_sig(hip, "rtu_temporal_steer_total", _I, _P, ctypes.POINTER(_U32))
+
+
+def steer_desc(width=0, height=0, **overrides):
+    """An RtuSteerDesc: rtu_steer_defaults (budget 0, max_extra 3, frame_index 0), the size, then `overrides`."""
+    d = RtuSteerDesc()
+    hip.rtu_steer_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def _sized_steer_desc(desc, W, H):
+    d = RtuSteerDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else steer_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    return d
+
+
+def sample_allocation(hist, hits, v, desc):
+    """rtu_sample_allocation (pure host code): desc.budget extra rays spread over the pixels by the variance v float32 [H, W] of the
+    moments history float32 [4, H, W, 4] (see variance()), at most desc.max_extra each -> (counts uint32 [H, W], offsets uint32
+    [H, W], total). The width and height of desc are taken from hist."""
+    import numpy as np
+    hist = np.ascontiguousarray(hist, np.float32)
+    if hist.ndim != 4 or hist.shape[0] != 4 or hist.shape[3] != 4:
+        raise RtuError(RTU_ERR_ARG, "hist: a float32 [4, H, W, 4] array")
+    H, W = hist.shape[1:3]
+    hits = np.ascontiguousarray(hits)
+    v = np.ascontiguousarray(v, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or v.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); v: float32 [H, W]")
+    d = _sized_steer_desc(desc, W, H)
+    counts, offsets, total = np.empty((H, W), np.uint32), np.empty((H, W), np.uint32), _U32(0)
+    rc = hip.rtu_sample_allocation(ctypes.byref(d), hist.ctypes.data, hits.ctypes.data, v.ctypes.data, counts.ctypes.data, offsets.ctypes.data,
+                                   ctypes.byref(total))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_sample_allocation: an empty image or a descriptor outside its rules (budget 0..2^26, max_extra 1..15, "
+                           "reserved words 0)")
+    return counts, offsets, int(total.value)
+
+
+def extra_sample_rays(frame, counts, offsets, desc, capacity=None):
+    """rtu_extra_sample_rays (pure host code): the extra rays of frame desc.frame_index of the recipe S / P frame `frame` for the
+    counts and offsets of sample_allocation() -> (rays [capacity] of ray_dtype(), keys uint32, owner uint32). capacity: None is the
+    number of rays the counts and offsets name."""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, np.uint32)
+    offsets = np.ascontiguousarray(offsets, np.uint32)
+    if counts.size != frame.width * frame.height or offsets.size != counts.size:
+        raise RtuError(RTU_ERR_ARG, "counts, offsets: uint32 [H, W] of the frame")
+    if capacity is None:
+        capacity = int((offsets.astype(np.uint64) + counts).max()) if counts.size and counts.any() else 0
+    d = _sized_steer_desc(desc, frame.width, frame.height)
+    rays, keys, owner = np.zeros(capacity, ray_dtype()), np.zeros(capacity, np.uint32), np.zeros(capacity, np.uint32)
+    rc = hip.rtu_extra_sample_rays(ctypes.byref(d), ctypes.byref(frame), counts.ctypes.data, offsets.ctypes.data, capacity,
+                                   rays.ctypes.data if capacity else None, keys.ctypes.data if capacity else None,
+                                   owner.ctypes.data if capacity else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_extra_sample_rays: a descriptor outside its rules, not a recipe S frame, samples * (1 + max_extra) > 65536, "
+                           "a count above max_extra or a ray beyond the capacity")
+    return rays, keys, owner
+
+
+def temporal_refine(hist, rgbz, hits, albedo, counts, offsets, rgbt, desc=None):
+    """rtu_temporal_refine (pure host code): the shaded extra samples rgbt float32 [n, 4] folded into the moments history float32
+    [4, H, W, 4] and the image rgbz [H, W, 4] -> (rgbz, hist), new arrays (the C entry works in place). Of desc (an RtuTemporalDesc,
+    None: the defaults) max_history is used."""
+    import numpy as np
+    hist = np.array(hist, np.float32, order="C")
+    rgbz = np.array(rgbz, np.float32, order="C")
+    if hist.ndim != 4 or hist.shape[0] != 4 or hist.shape[3] != 4 or rgbz.shape != hist.shape[1:]:
+        raise RtuError(RTU_ERR_ARG, "hist: a float32 [4, H, W, 4] array; rgbz: float32 [H, W, 4]")
+    H, W = hist.shape[1:3]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    counts = np.ascontiguousarray(counts, np.uint32)
+    offsets = np.ascontiguousarray(offsets, np.uint32)
+    rgbt = np.ascontiguousarray(rgbt, np.float32).reshape(-1, 4)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W or counts.size != H * W or offsets.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]; counts, offsets: uint32 [H, W]")
+    d = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    rc = hip.rtu_temporal_refine(ctypes.byref(d), hist.ctypes.data, hits.ctypes.data, albedo.ctypes.data, counts.ctypes.data, offsets.ctypes.data,
+                                 rgbt.ctypes.data if len(rgbt) else None, len(rgbt), rgbz.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_refine: a descriptor outside its rules, or a pixel whose samples lie beyond rgbt")
+    return rgbz, hist
 
 
 def sensor_desc(model, width, height, pos, right, up, forward, samples=0, gather_bounces=0, max_bounce=5, fov_deg=180.0, extent=(1, 1),
@@ -1215,13 +1328,18 @@ class Temporal:
     """A temporal session (RtuTemporal*, include/rtu_render.h "Temporal accumulation"): one new sample per frame of a recipe S / P
     frame whose camera may move, accumulated by reprojection. Made by Context.temporal(); errors raise RtuError with the context's message.
     variance: an RtuVarianceDesc (see variance_desc()) makes it a variance session (rtu_temporal_begin_variance): its history holds the
-    moments, and every frame is filtered by denoise_variance() with the variance() of that history."""
+    moments, and every frame is filtered by denoise_variance() with the variance() of that history. steer: an RtuSteerDesc (see
+    steer_desc(); with variance) makes it a steered session (rtu_temporal_begin_steered): every frame spends steer.budget extra rays
+    where that variance is highest and folds them into the history before it is filtered."""
 
-    def __init__(self, ctx, desc, variance=None):
+    def __init__(self, ctx, desc, variance=None, steer=None):
         err = _I(0)
         self._ctx = ctx
         self.desc = desc
-        if variance is not None:
+        if steer is not None:
+            self._h = hip.rtu_temporal_begin_steered(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
+                                                     ctypes.byref(steer), ctypes.byref(err))
+        elif variance is not None:
             self._h = hip.rtu_temporal_begin_variance(ctx._h, ctypes.byref(desc), ctypes.byref(variance), ctypes.byref(err))
         else:
             self._h = hip.rtu_temporal_begin(ctx._h, ctypes.byref(desc), ctypes.byref(err))
@@ -1274,6 +1392,31 @@ class Temporal:
 
     def history_device(self, d_n, stream=None):
         self._check(hip.rtu_temporal_history_device(self._h, d_n, stream))
+
+    def extra_counts(self):
+        """A steered session: the extra rays every pixel got in the last frame, uint32 [H, W] (zeros before the first)."""
+        import numpy as np
+        n = self.desc.width * self.desc.height
+        out = np.empty((self.desc.height, self.desc.width), np.uint32)
+        d = hip.rtu_device_alloc(self._ctx._h, 4 * n)
+        if not d:
+            self._check(RTU_ERR_HIP)
+        try:
+            self.extra_counts_device(d, hip.rtu_context_stream(self._ctx._h))
+            self._check(hip.rtu_context_sync(self._ctx._h))
+            self._check(hip.rtu_copy_to_host(self._ctx._h, out.ctypes.data, d, 4 * n))
+        finally:
+            hip.rtu_device_free(self._ctx._h, d)
+        return out
+
+    def extra_counts_device(self, d_counts, stream=None):
+        self._check(hip.rtu_temporal_extra_counts_device(self._h, d_counts, stream))
+
+    def steer_total(self):
+        """A steered session: the number of extra rays of the last frame."""
+        n = _U32(0)
+        self._check(hip.rtu_temporal_steer_total(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def reset(self):
         """Start over: the next frame is frame 0 and has no history."""
@@ -1374,10 +1517,25 @@ class Context:
         snapshot() -> (rgbz, counts), close()."""
         return Progressive(self, frame, adaptive)
 
-    def temporal(self, desc, variance=None):
+    def temporal(self, desc, variance=None, steer=None):
         """A temporal session (desc: an RtuTemporalDesc with the size of its frames, see temporal_desc()): frame(frame) -> rgbz,
-        frame_device(), history(), reset(), close()."""
-        return Temporal(self, desc, variance)
+        frame_device(), history(), reset(), close(). variance, steer: see Temporal."""
+        return Temporal(self, desc, variance, steer)
+
+    def sample_allocation_device(self, desc, d_hist_ptr, d_hits_ptr, d_v_ptr, d_counts_ptr, d_offsets_ptr, d_total_ptr, stream=None):
+        """rtu_sample_allocation_device: sample_allocation() on device memory, the same words; the total is one uint32 at d_total_ptr."""
+        self._check(hip.rtu_sample_allocation_device(self._h, ctypes.byref(desc), d_hist_ptr, d_hits_ptr, d_v_ptr, d_counts_ptr, d_offsets_ptr,
+                                                     d_total_ptr, stream))
+
+    def extra_sample_rays_device(self, desc, frame, d_counts_ptr, d_offsets_ptr, capacity, d_rays_ptr, d_keys_ptr, d_owner_ptr, stream=None):
+        """rtu_extra_sample_rays_device: extra_sample_rays() written to device memory by a kernel; nothing at or beyond `capacity`."""
+        self._check(hip.rtu_extra_sample_rays_device(self._h, ctypes.byref(desc), ctypes.byref(frame), d_counts_ptr, d_offsets_ptr, int(capacity),
+                                                     d_rays_ptr, d_keys_ptr, d_owner_ptr, stream))
+
+    def temporal_refine_device(self, desc, d_hist_ptr, d_hits_ptr, d_albedo_ptr, d_counts_ptr, d_offsets_ptr, d_rgbt_ptr, n_rays, d_rgbz_ptr, stream=None):
+        """rtu_temporal_refine_device: temporal_refine() on device memory, in place in d_hist_ptr (four planes) and d_rgbz_ptr."""
+        self._check(hip.rtu_temporal_refine_device(self._h, ctypes.byref(desc), d_hist_ptr, d_hits_ptr, d_albedo_ptr, d_counts_ptr, d_offsets_ptr,
+                                                   d_rgbt_ptr, int(n_rays), d_rgbz_ptr, stream))
 
     def camera_sample_rays_device(self, frame, sample, d_rays_ptr, d_keys_ptr, stream=None):
         """rtu_camera_sample_rays_device: the rays and keys of camera_sample_rays(frame, sample) written to device memory by a kernel."""

@@ -13,6 +13,7 @@
 #include "rtu_query.h"
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
+#include "rtu_steer.h"
 #include "rtu_temporal.h"
 #include "rtu_variance.h"
 
@@ -156,6 +157,7 @@ struct RtuContext {
     bool  sn_timing = false;                 // rtu_debug_sensor_timing: HIP events around the two kernels of rtu_sensor.hip and the whole render
     float sn_ms[3] = {};                     // k_sensor_rays, k_sensor_accumulate, the render: summed since the last read
     hipEvent_t sn_ev[6] = {};
+    DevBuf<uint32_t> st_scratch;             // steered sampling (rtu_sample_allocation_device): the weights, the tile sums, Wsum
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -1819,6 +1821,13 @@ struct RtuTemporal {
     bool             variance = false;    // rtu_temporal_begin_variance: hist[] have four planes, a frame ends with k_variance and the filter
     RtuVarianceDesc  vdesc{};
     DevBuf<float>    var;                 // ... the variance of the frame
+    bool             steered = false;     // rtu_temporal_begin_steered: a frame goes on with the allocation, the extra rays and the fold
+    RtuSteerDesc     sdesc{};
+    size_t           st_cap = 0;          // ... rays of a frame at most: min(budget, pixels * max_extra)
+    uint32_t         st_total = 0;        // ... of the last frame
+    DevBuf<uint32_t> st_counts, st_offsets, st_total_dev, st_keys, st_owner;
+    DevBuf<float4>   st_rays, st_img;
+    PinnedBuf<uint32_t> st_total_host;
 };
 
 static void temporal_release(RtuTemporal* t) {
@@ -1831,6 +1840,15 @@ static void temporal_release(RtuTemporal* t) {
     t->motion.reset();
     t->motion_host.reset();
     t->var.reset();
+    t->st_counts.reset();
+    t->st_offsets.reset();
+    t->st_total_dev.reset();
+    t->st_keys.reset();
+    t->st_owner.reset();
+    t->st_rays.reset();
+    t->st_img.reset();
+    t->st_total_host.reset();
+    t->st_total = 0;
     t->has_hist = false;
     t->ctx = nullptr;
 }
@@ -4159,6 +4177,206 @@ int rtu_motion_vectors_device(RtuContext* ctx, const RtuTemporalDesc* desc, cons
     return RTU_OK;
 }
 
+// ---- steered sampling (rtu_steer.h, rtu_steer.hip): the allocation, the extra rays and the fold on device memory ----
+static_assert(sizeof(RtuSteerDesc) == 32, "RtuSteerDesc is 32 bytes");
+
+static const char* const kSteerDescRules =
+    "steer: width, height 1 .. 65536 (2^26 pixels), budget 0 .. 2^26, max_extra 1 .. 15, reserved words 0";
+static bool misaligned4(const void* p) { return ((uintptr_t)p & 3u) != 0; }
+
+// What st_extra_ray takes of `frame` for the extra samples of frame `d.frame_index`: the camera, and the pixel offsets of the samples
+// S + (k mod S) * E + j of the frame with S * (1 + E) samples, by launch()'s expressions (cam_sample). false: the frame is refused.
+static bool steer_rays_setup(const RtuSteerDesc& d, const RtuFrameDesc* frame, StRays* r) {
+    if (!frame || frame->width != d.width || frame->height != d.height || frame->samples < 1) return false;
+    const long long S = frame->samples, E = d.max_extra;
+    if (S * (1 + E) > 65536) return false;
+    RtuFrameDesc f = *frame;
+    f.samples = (int32_t)(S * (1 + E));
+    const uint32_t sample0 = (uint32_t)(S + (long long)(d.frame_index % (uint32_t)S) * E);
+    memset(r, 0, sizeof *r);
+    r->c = cam_sample(&f, (int)sample0);
+    for (int j = 0; j < d.max_extra; j++) {
+        const CamSample cj = cam_sample(&f, (int)sample0 + j);
+        r->ox[j] = cj.ox;
+        r->oy[j] = cj.oy;
+    }
+    r->sample0 = sample0;
+    return true;
+}
+
+int rtu_extra_sample_rays(const RtuSteerDesc* desc, const RtuFrameDesc* frame, const uint32_t* counts, const uint32_t* offsets, size_t capacity,
+                          RtuRay* rays_out, uint32_t* keys_out, uint32_t* owner_out) {
+    StRays r;
+    if (rtu_steer_check_desc(desc) != RTU_OK || !steer_rays_setup(*desc, frame, &r) || !counts || !offsets || capacity > ((size_t)1 << 26))
+        return RTU_ERR_ARG;
+    if (capacity && (!rays_out || !keys_out || !owner_out)) return RTU_ERR_ARG;
+    const size_t n = (size_t)desc->width * (size_t)desc->height;
+    for (size_t p = 0; p < n; p++)
+        if (counts[p] > (uint32_t)desc->max_extra || (unsigned long long)offsets[p] + counts[p] > capacity) return RTU_ERR_ARG;
+    for (size_t p = 0; p < n; p++) {
+        const int y = (int)(p / (size_t)desc->width), x = (int)(p - (size_t)y * (size_t)desc->width);
+        for (uint32_t j = 0; j < counts[p]; j++) {
+            f3 org, dir;
+            uint32_t key;
+            st_extra_ray(r.c, r.ox[j], r.oy[j], r.sample0 + j, x, y, HostSinCos(), org, dir, key);
+            const size_t i = (size_t)offsets[p] + j;
+            RtuRay& ray = rays_out[i];
+            ray.org[0] = org.x; ray.org[1] = org.y; ray.org[2] = org.z;
+            ray.tmax = RTU_BIGFLOAT;
+            ray.dir[0] = dir.x; ray.dir[1] = dir.y; ray.dir[2] = dir.z;
+            ray.reserved = 0;
+            keys_out[i] = key;
+            owner_out[i] = (uint32_t)p;
+        }
+    }
+    return RTU_OK;
+}
+
+int rtu_sample_allocation_device(RtuContext* ctx, const RtuSteerDesc* desc, const void* d_hist, const void* d_hits, const void* d_v, void* d_counts,
+                                 void* d_offsets, void* d_total, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_steer_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kSteerDescRules);
+    if (!d_hist || !d_hits || !d_v || !d_counts || !d_offsets || !d_total) return fail(ctx, RTU_ERR_ARG, "steer: a device pointer is NULL");
+    if (misaligned(d_hist) || misaligned(d_hits) || misaligned4(d_v) || misaligned4(d_counts) || misaligned4(d_offsets) || misaligned4(d_total))
+        return fail(ctx, RTU_ERR_ARG, "steer: device buffers must be 16-byte aligned (d_v, d_counts, d_offsets, d_total: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->st_scratch.grow(rtu_steer_scratch_words((size_t)desc->width * (size_t)desc->height)));
+    const hipError_t e = (hipError_t)rtu_launch_sample_allocation(*desc, (const float4*)d_hist, (const float4*)d_hits, (const float*)d_v, (uint32_t*)d_counts,
+                                                                  (uint32_t*)d_offsets, (uint32_t*)d_total, ctx->st_scratch.get(), (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "allocation launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_extra_sample_rays_device(RtuContext* ctx, const RtuSteerDesc* desc, const RtuFrameDesc* frame, const void* d_counts, const void* d_offsets,
+                                 size_t capacity, void* d_rays, void* d_keys, void* d_owner, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_steer_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kSteerDescRules);
+    StRays r;
+    if (!steer_rays_setup(*desc, frame, &r))
+        return fail(ctx, RTU_ERR_ARG, "steer: the frame must have the desc's size, samples >= 1 and samples * (1 + max_extra) <= 65536");
+    if (capacity > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "steer: more than 2^26 rays");
+    if (!d_counts || !d_offsets || (capacity && (!d_rays || !d_keys || !d_owner))) return fail(ctx, RTU_ERR_ARG, "steer: a device pointer is NULL");
+    if (misaligned(d_rays) || misaligned4(d_keys) || misaligned4(d_owner) || misaligned4(d_counts) || misaligned4(d_offsets))
+        return fail(ctx, RTU_ERR_ARG, "steer: the ray buffer must be 16-byte, the other buffers 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_extra_sample_rays(r, (uint32_t)desc->max_extra, (const uint32_t*)d_counts, (const uint32_t*)d_offsets,
+                                                                  (float4*)d_rays, (uint32_t*)d_keys, (uint32_t*)d_owner, (uint32_t)capacity, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "extra ray launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_refine_device(RtuContext* ctx, const RtuTemporalDesc* desc, void* d_hist, const void* d_hits, const void* d_albedo, const void* d_counts,
+                               const void* d_offsets, const void* d_rgbt, size_t n_rays, void* d_rgbz, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
+    if (n_rays > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "refine: more than 2^26 samples");
+    if (!d_hist || !d_hits || !d_albedo || !d_counts || !d_offsets || !d_rgbz || (n_rays && !d_rgbt)) return fail(ctx, RTU_ERR_ARG, "refine: a device pointer is NULL");
+    if (misaligned(d_hist) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_rgbt) || misaligned(d_rgbz) || misaligned4(d_counts) ||
+        misaligned4(d_offsets))
+        return fail(ctx, RTU_ERR_ARG, "refine: device buffers must be 16-byte aligned (d_counts, d_offsets: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_temporal_refine((size_t)desc->width * (size_t)desc->height, (float)desc->max_history, (float4*)d_hist,
+                                                                (const float4*)d_hits, (const float4*)d_albedo, (const uint32_t*)d_counts,
+                                                                (const uint32_t*)d_offsets, (const float4*)d_rgbt, (uint32_t)n_rays, (float4*)d_rgbz,
+                                                                (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "refine launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+RtuTemporal* rtu_temporal_begin_steered(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuVarianceDesc* vdesc, const RtuSteerDesc* sdesc, int* err_out) {
+    auto refuse = [&](int rc) -> RtuTemporal* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (!sdesc || !desc || !vdesc) return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a descriptor is NULL"));
+    RtuSteerDesc sd = *sdesc;  // (its size is the session's, its frame_index the frame's)
+    sd.width = desc->width;
+    sd.height = desc->height;
+    sd.frame_index = 0;
+    if (rtu_temporal_check_desc(desc) == RTU_OK && rtu_steer_check_desc(&sd) != RTU_OK) return refuse(fail(ctx, RTU_ERR_ARG, "%s", kSteerDescRules));
+    RtuTemporal* t = rtu_temporal_begin_variance(ctx, desc, vdesc, err_out);
+    if (!t) return nullptr;
+    t->steered = true;
+    t->sdesc = sd;
+    const size_t n = t->pixels, most = n * (size_t)sd.max_extra;
+    t->st_cap = sd.budget < most ? sd.budget : most;
+    hipError_t e = t->st_counts.grow(n);
+    if (e == hipSuccess) e = hipMemset(t->st_counts.get(), 0, n * sizeof(uint32_t));  // (before the first frame: zeros)
+    if (e == hipSuccess && t->st_cap) {
+        e = t->st_offsets.grow(n);
+        if (e == hipSuccess) e = t->st_total_dev.grow(1);
+        if (e == hipSuccess) e = t->st_total_host.grow(1);
+        if (e == hipSuccess) e = t->st_rays.grow(2 * t->st_cap);
+        if (e == hipSuccess) e = t->st_keys.grow(t->st_cap);
+        if (e == hipSuccess) e = t->st_owner.grow(t->st_cap);
+        if (e == hipSuccess) e = t->st_img.grow(t->st_cap);
+        if (e == hipSuccess) e = ctx->st_scratch.grow(rtu_steer_scratch_words(n));
+    }
+    if (e != hipSuccess) {
+        const int rc = fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e));
+        rtu_temporal_free(t);
+        return refuse(rc);
+    }
+    return t;
+}
+
+// a steered session's frame after the accumulator and the first rtu_variance_device: the extra rays of the frame, folded into the new
+// history and d_rgbz, and the variance of the folded history
+static int temporal_steer(RtuTemporal* t, const RtuFrameDesc* frame, uint32_t k, void* d_rgbz, void* hip_stream) {
+    RtuContext* ctx = t->ctx;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const bool paths = frame->gather_bounces != 0;
+    RtuSteerDesc sd = t->sdesc;
+    sd.frame_index = k;
+    float4* hist = t->hist[t->cur].get();
+    int rc = rtu_sample_allocation_device(ctx, &sd, hist, t->hits.get(), t->var.get(), t->st_counts.get(), t->st_offsets.get(), t->st_total_dev.get(), hip_stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(t->st_total_host.get(), t->st_total_dev.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    RTU_HIP(ctx, hipStreamSynchronize(stream));
+    const uint32_t total = *t->st_total_host.get();
+    if ((size_t)total > t->st_cap) return fail(ctx, RTU_ERR_HIP, "steer: %u rays allocated, the session holds %zu", total, t->st_cap);
+    t->st_total = total;
+    if (total == 0) return RTU_OK;
+    if ((rc = rtu_extra_sample_rays_device(ctx, &sd, frame, t->st_counts.get(), t->st_offsets.get(), total, t->st_rays.get(), t->st_keys.get(),
+                                           t->st_owner.get(), hip_stream)) != RTU_OK)
+        return rc;
+    RtuShadeDesc shd;
+    rtu_shade_defaults(&shd);
+    memcpy(shd.eye, frame->cam_pos, sizeof shd.eye);
+    shd.max_bounce = frame->max_bounce;
+    RtuFrameDesc f;
+    if ((rc = shade_args(ctx, t->st_rays.get(), t->st_img.get(), total, &shd, true, &f, true, t->st_keys.get(), paths)) != RTU_OK) return rc;
+    if (paths && (rc = paths_chain(ctx, f, t->st_img.get(), stream, t->st_rays.get(), t->st_keys.get(), total)) != RTU_OK) return rc;
+    if ((rc = shade_until_fits(ctx, f, t->st_img.get(), stream, t->st_rays.get(), t->st_keys.get(), total, paths, nullptr)) != RTU_OK) return rc;
+    if ((rc = rtu_temporal_refine_device(ctx, &t->desc, hist, t->hits.get(), t->albedo.get(), t->st_counts.get(), t->st_offsets.get(), t->st_img.get(),
+                                         total, d_rgbz, hip_stream)) != RTU_OK)
+        return rc;
+    return rtu_variance_device(ctx, &t->vdesc, hist, t->hits.get(), t->var.get(), hip_stream);
+}
+
+int rtu_temporal_extra_counts_device(RtuTemporal* t, void* d_counts, void* hip_stream) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!t->steered) return fail(ctx, RTU_ERR_ARG, "not a steered session");
+    if (!d_counts) return fail(ctx, RTU_ERR_ARG, "d_counts is NULL");
+    if (misaligned4(d_counts)) return fail(ctx, RTU_ERR_ARG, "d_counts must be 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    if (t->has_hist)
+        RTU_HIP(ctx, hipMemcpyAsync(d_counts, t->st_counts.get(), t->pixels * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    else
+        RTU_HIP(ctx, hipMemsetAsync(d_counts, 0, t->pixels * sizeof(uint32_t), (hipStream_t)hip_stream));
+    return RTU_OK;
+}
+
+int rtu_temporal_steer_total(RtuTemporal* t, uint32_t* total_out) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    if (!t->steered) return fail(t->ctx, RTU_ERR_ARG, "not a steered session");
+    if (!total_out) return fail(t->ctx, RTU_ERR_ARG, "total_out is NULL");
+    *total_out = t->st_total;
+    return RTU_OK;
+}
+
 // what a moved frame has beyond a plain one (rtu_temporal_frame_moved_device)
 struct TemporalMoved {
     const RtuNodeMotion* h_motion;
@@ -4265,6 +4483,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     t->k++;
     if (t->variance) {
         if ((rc = rtu_variance_device(ctx, &t->vdesc, t->hist[t->cur].get(), t->hits.get(), t->var.get(), hip_stream)) != RTU_OK) return rc;
+        if (t->steered && t->st_cap && (rc = temporal_steer(t, frame, (uint32_t)(t->k - 1), d_rgbz, hip_stream)) != RTU_OK) return rc;
         return rtu_denoise_variance_device(ctx, &t->vdesc, d_rgbz, t->hits.get(), t->albedo.get(), t->var.get(), d_rgbz, hip_stream);  // in place
     }
     if (t->desc.flags & RTU_TEMPORAL_DENOISE) {
@@ -4314,6 +4533,7 @@ int rtu_temporal_reset(RtuTemporal* t) {
     if (!t || !t->ctx) return RTU_ERR_ARG;
     t->has_hist = false;
     t->k = 0;
+    t->st_total = 0;
     return RTU_OK;
 }
 
