@@ -989,6 +989,110 @@ RtuTemporal* rtu_temporal_begin_steered(RtuContext* ctx, const RtuTemporalDesc* 
 int  rtu_temporal_extra_counts_device(RtuTemporal* t, void* d_counts, void* hip_stream);
 int  rtu_temporal_steer_total(RtuTemporal* t, uint32_t* total_out);
 
+/* ---- Temporal gradients: a pixel's history is shortened where its shading changed (rtu_gradient.h, rtu_gradient.hip) ----
+ * Neither a variance nor a steered session notices that the LIGHT arriving at a surface point changed: after rtu_update_scene moved or
+ * dimmed a light every node is RTU_MOTION_STATIC, the whole history is kept and the old lighting fades over max_history frames. The
+ * entries below re-shade one pixel of every 3 x 3 STRATUM with the random numbers of the previous frame, compare it with what the
+ * previous frame saw there, and cap the history where the two differ. With the camera at rest and the node static the re-shaded
+ * sample is the previous frame's ray with the previous frame's key: the difference is exactly zero unless the scene changed.
+ * Binary32, one rounding per operation, no contraction, IEEE divisions and square roots, in this order; host and device forms give the
+ * same bits. VALID, d, l(e), mix32, the table, Pm, Nm, the projection {s, fx, fy} and a tap's ACCEPTED are those of the sections above.
+ *
+ * 1. STRATA AND GRADIENT RAYS  SW = ceil(width / 3), SH = ceil(height / 3); stratum (sx, sy) has index s = sx + SW * sy and OWNS one
+ *   pixel per frame: h = mix32(s + 0x9e3779b9u * (frame_index + 1u)), x = 3 sx + (h >> 16) % min(3, width - 3 sx),
+ *   y = 3 sy + (h >> 24) % min(3, height - 3 sy), owner_s = x + width * y. rtu_gradient_rays writes, per stratum, owner_s and the ray
+ *   and key of that pixel in rtu_camera_sample_rays(frame, sample), bit for bit: `sample` is the caller's — a session passes
+ *   (k - 1) mod S, the sample the previous frame used. The frame must have the desc's size and samples > sample >= 0.
+ *
+ * 2. THE SAMPLE'S LUMINANCE  rtu_sample_luminance: one float per pixel of a frame's raw sample image, L_p = l(c / d); 0 for a pixel
+ *   that is not VALID or whose c has a channel that is not finite.
+ *
+ * 3. GRADIENTS AND LAMBDA  rtu_temporal_gradient: out of the two cameras, the current frame's RtuRayHit and albedo, the table, the
+ *   previous moments history and luminance plane, the owners and the shaded {r, g, b, t} of the gradient rays (one per stratum),
+ *   one float4 diff_s and one float lambda_s per stratum. With p = owner_s and c the rgb of rgbt_s:
+ *     no gradient, diff_s = {0, 0, 0, 0}: p is not VALID; a channel of c is not finite; rtu_temporal_accumulate_moments would make no
+ *       lookup for p (hist_prev == NULL, node outside the table, RESET, a component of Pm or Nm of a node that is not STATIC not
+ *       finite, s not finite or not > 0); q (below) outside the image; the tap q is not ACCEPTED for p.
+ *     q = p on the one-tap path (the cameras equal bit for bit and p's node STATIC); otherwise q = (floor(fx + 0.5f), floor(fy + 0.5f))
+ *       from the accumulator's fx, fy (compared with 0 and the size as floats: a NaN fails, before any conversion to an integer).
+ *     lc = l(c / d_p);  lp = L_prev[q];  num = lc - lp;  den = lc > lp ? lc : lp
+ *     noise = 0 on the one-tap path (the comparand is the same ray with the same key); otherwise x = M_q.y - M_q.x * M_q.x and
+ *       noise = 2 * (x > 0 ? x : 0): the comparand is another ray, this is its per-sample variance, twice.
+ *     diff_s = {num, den, noise, 0}
+ *   Then per stratum, over the strata (sx + dx, sy + dy), dy outer, dx inner, both -radius .. radius, that lie in the strata grid:
+ *     Nsum, Dsum, Zsum = the sums of diff.x, diff.y, diff.z in that order
+ *     x = |Nsum| - kappa * sqrtf(Zsum);  a = x > 0 ? x : 0 (a NaN gives 0);  r = a / Dsum
+ *     lambda_s = 0 unless Dsum > 0 and r is not a NaN; otherwise r < 1 ? r : 1.
+ *
+ * 4. THE CAPPED ACCUMULATOR  rtu_temporal_accumulate_gradient is rtu_temporal_accumulate_moments with one more input, `lambda`: one
+ *   float per stratum (SW * SH floats), or NULL. For pixel (x, y), L = lambda[(x / 3) + SW * (y / 3)]. Where L > 0 and n_prev > 0 —
+ *   after history_cap, which keeps its meaning, and before the blend —: n_prev = min(n_prev, L < 1 ? 1 / L - 1 : 0). So the weight of
+ *   the new sample is not below L (roughly), and L >= 1 starts the pixel over: n_prev = 0, e_prev, m1_prev and m2_prev zeros, as for
+ *   a pixel that found no history — so n = 1, e = e_cur and the moments are those of a fresh pixel.
+ *   A NaN caps nothing. The moments are blended with the same A: where history was dropped the variance rises, the filter smooths
+ *   harder and a steered session sends its extra rays there. With lambda NULL or all zero the output is the moments form's bit for bit.
+ *
+ * RTU_ERR_ARG: what the moments form refuses; a NULL pointer (hist_prev, and with it prev_cam and L_prev, may be NULL: no gradient
+ * anywhere); a gradient desc of another size than the temporal desc or outside its rules: width, height 1 .. 65536 and 2^26 pixels,
+ * radius 0 .. 3, kappa >= 0 and finite, enabled 0 or 1, reserved words 0; a device pointer that is not 16-byte aligned (keys, owners,
+ * luminance planes, lambda: 4-byte). The host forms — pure host code, no GPU and no context — also refuse an owner outside the image.
+ * THE DEVICE FORMS TRUST THE TABLE AND THE OWNERS but never leave the arrays: an owner outside the image gives no gradient. They
+ * allocate nothing, need no scene, touch no state of the context and are asynchronous on hip_stream: rtu_gradient_rays_device
+ * (k_gradient_rays, a lane per stratum), rtu_sample_luminance_device (k_sample_luminance), rtu_temporal_gradient_device
+ * (k_gradient_diff, then k_gradient_lambda: one 16-byte load per tap) and rtu_temporal_accumulate_gradient_device
+ * (k_temporal<true, true, true>). rgbz_out == rgbz is allowed as for every accumulator; no other output may overlap an input.
+ *
+ * THE SESSION  rtu_temporal_begin_gradient opens a variance session, or with steer_desc a steered session, whose frames, plain and
+ * moved, change in four ways when the session has a previous frame (not frame 0, not the frame after rtu_temporal_reset, not a plain
+ * frame after a scene change: those start over as before and take no gradient): (a) behind the rays and keys of sample k mod S the
+ * gradient rays of sample (k - 1) mod S with frame_index = k are written into the same buffers; (b) the unchanged shading path of step
+ * 2 shades width * height + SW * SH rays in its one launch sequence; (c) after the guides come rtu_temporal_gradient_device and
+ * rtu_temporal_accumulate_gradient_device in place of the moments form; (d) rtu_sample_luminance_device of the new sample is kept for
+ * the next frame (this on every frame). gradient_desc: width and height are ignored, the session's are used; enabled == 0 gives the
+ * parent session's bits and launches nothing more. rtu_temporal_lambda_device writes width * height floats, the lambda of every
+ * pixel's stratum in the last frame; zeros where no gradient was taken (before the first frame, after a frame that started over, with
+ * enabled == 0). Two luminance planes (8 B per pixel) and 76 B per stratum — ray, key, result, owner, diff, lambda — belong to the
+ * session besides the parent's, about 16.5 B per pixel in all, allocated at begin; a frame allocates nothing after the first: a
+ * frame that starts over also shades SW * SH gradient rays (those of sample (k + S - 1) mod S) and uses none of their results, so
+ * that every frame's batch has one size and the context's frame records grow once.
+ * Everything else as for the parent session. Not done here: the previous pixel's key is not forwarded under reprojection (the noise
+ * floor stands in for the cancellation that would bring), the gradient samples are not folded into the history, lambda is one value
+ * per stratum, progressive sessions take no gradients. Measured error ratios and times are in DESIGN.md section 27. */
+typedef struct RtuGradientDesc {   /* 32 B */
+    int32_t  width, height;
+    int32_t  radius;               /* 0 .. 3: strata on each side that lambda is summed over */
+    float    kappa;                /* >= 0: the noise floor in standard deviations of the summed difference */
+    uint32_t enabled;              /* session only: 0 gives the parent session */
+    uint32_t frame_index;          /* selects the owners (rtu_gradient_rays); a session sets it */
+    uint32_t reserved[2];          /* must be 0 */
+} RtuGradientDesc;
+int  rtu_gradient_defaults(RtuGradientDesc* out);   /* width, height 0; radius 1, kappa 2, enabled 1, frame_index 0 */
+int  rtu_gradient_rays(const RtuGradientDesc* desc, const RtuFrameDesc* frame, int sample, RtuRay* rays_out, uint32_t* keys_out,
+                       uint32_t* owner_out);
+int  rtu_gradient_rays_device(RtuContext* ctx, const RtuGradientDesc* desc, const RtuFrameDesc* frame, int sample, void* d_rays, void* d_keys,
+                              void* d_owner, void* hip_stream);
+int  rtu_sample_luminance(const RtuGradientDesc* desc, const float* h_rgbz, const RtuRayHit* h_hits, const float* h_albedo, float* h_lum);
+int  rtu_sample_luminance_device(RtuContext* ctx, const RtuGradientDesc* desc, const void* d_rgbz, const void* d_hits, const void* d_albedo,
+                                 void* d_lum, void* hip_stream);
+int  rtu_temporal_gradient(const RtuTemporalDesc* desc, const RtuGradientDesc* gradient_desc, const RtuFrameDesc* prev_cam,
+                           const RtuFrameDesc* cur_cam, const RtuRayHit* h_hits, const float* h_albedo, const RtuNodeMotion* motion,
+                           uint32_t n_nodes, const float* h_hist_prev, const float* h_lum_prev, const uint32_t* owner, const float* h_rgbt,
+                           float* h_diff_out, float* h_lambda_out);
+int  rtu_temporal_gradient_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuGradientDesc* gradient_desc, const RtuFrameDesc* prev_cam,
+                                  const RtuFrameDesc* cur_cam, const void* d_hits, const void* d_albedo, const RtuNodeMotion* d_motion,
+                                  uint32_t n_nodes, const void* d_hist_prev, const void* d_lum_prev, const void* d_owner, const void* d_rgbt,
+                                  void* d_diff_out, void* d_lambda_out, void* hip_stream);
+int  rtu_temporal_accumulate_gradient(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                      const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
+                                      const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap, const float* h_lambda);
+int  rtu_temporal_accumulate_gradient_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                             const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                             void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap,
+                                             const void* d_lambda, void* hip_stream);
+RtuTemporal* rtu_temporal_begin_gradient(RtuContext* ctx, const RtuTemporalDesc* temporal_desc, const RtuVarianceDesc* variance_desc,
+                                         const RtuSteerDesc* steer_desc_or_null, const RtuGradientDesc* gradient_desc, int* err_out);
+int  rtu_temporal_lambda_device(RtuTemporal* t, void* d_lambda, void* hip_stream);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

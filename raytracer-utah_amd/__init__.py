@@ -171,7 +171,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_variance_device", "rtu_denoise_variance", "rtu_denoise_variance_device", "rtu_temporal_begin_variance",
                "rtu_steer_defaults", "rtu_sample_allocation", "rtu_sample_allocation_device", "rtu_extra_sample_rays",
                "rtu_extra_sample_rays_device", "rtu_temporal_refine", "rtu_temporal_refine_device", "rtu_temporal_begin_steered",
-               "rtu_temporal_extra_counts_device", "rtu_temporal_steer_total"]
+               "rtu_temporal_extra_counts_device", "rtu_temporal_steer_total",
+               "rtu_gradient_defaults", "rtu_gradient_rays", "rtu_gradient_rays_device", "rtu_sample_luminance", "rtu_sample_luminance_device",
+               "rtu_temporal_gradient", "rtu_temporal_gradient_device", "rtu_temporal_accumulate_gradient",
+               "rtu_temporal_accumulate_gradient_device", "rtu_temporal_begin_gradient", "rtu_temporal_lambda_device"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -754,6 +757,137 @@ def temporal_refine(hist, rgbz, hits, albedo, counts, offsets, rgbt, desc=None):
     return rgbz, hist
 
 
+# temporal gradients (include/rtu_render.h, "Temporal gradients")
+class RtuGradientDesc(ctypes.Structure):
+    """include/rtu_render.h RtuGradientDesc (32 bytes): the size of the image, the radius (in strata) lambda is summed over, the noise
+    floor kappa, the session's switch and the frame's index."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("radius", ctypes.c_int32), ("kappa", ctypes.c_float),
+                ("enabled", ctypes.c_uint32), ("frame_index", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+_TD, _GD, _FD = ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuGradientDesc), ctypes.POINTER(RtuFrameDesc)
+_sig(hip, "rtu_gradient_defaults", _I, _GD)
+_sig(hip, "rtu_gradient_rays", _I, _GD, _FD, _I, _P, _P, _P)
+_sig(hip, "rtu_gradient_rays_device", _I, _P, _GD, _FD, _I, _P, _P, _P, _P)
+_sig(hip, "rtu_sample_luminance", _I, _GD, _P, _P, _P, _P)
+_sig(hip, "rtu_sample_luminance_device", _I, _P, _GD, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_gradient", _I, _TD, _GD, _FD, _FD, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_gradient_device", _I, _P, _TD, _GD, _FD, _FD, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_gradient", _I, _TD, _FD, _FD, _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32, _P)
+_sig(hip, "rtu_temporal_accumulate_gradient_device", _I, _P, _TD, _FD, _FD, _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32, _P, _P)
+_sig(hip, "rtu_temporal_begin_gradient", _P, _P, _TD, ctypes.POINTER(RtuVarianceDesc), ctypes.POINTER(RtuSteerDesc), _GD, ctypes.POINTER(_I))
+_sig(hip, "rtu_temporal_lambda_device", _I, _P, _P, _P)
+
+
+def gradient_desc(width=0, height=0, **overrides):
+    """An RtuGradientDesc: rtu_gradient_defaults (radius 1, kappa 2, enabled 1, frame_index 0), the size, then `overrides`."""
+    d = RtuGradientDesc()
+    hip.rtu_gradient_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def _sized_gradient_desc(desc, W, H):
+    d = RtuGradientDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else gradient_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    return d
+
+
+def strata(width, height):
+    """(SW, SH): the 3 x 3 strata of a width x height image."""
+    return (width + 2) // 3, (height + 2) // 3
+
+
+def gradient_rays(frame, sample, desc=None):
+    """rtu_gradient_rays (pure host code): per stratum the pixel it owns in frame desc.frame_index and that pixel's ray and key of
+    camera_sample_rays(frame, sample) -> (rays [SW * SH] of ray_dtype(), keys uint32, owner uint32)."""
+    import numpy as np
+    d = _sized_gradient_desc(desc, frame.width, frame.height)
+    sw, sh = strata(frame.width, frame.height)
+    rays, keys, owner = np.zeros(sw * sh, ray_dtype()), np.zeros(sw * sh, np.uint32), np.zeros(sw * sh, np.uint32)
+    rc = hip.rtu_gradient_rays(ctypes.byref(d), ctypes.byref(frame), int(sample), rays.ctypes.data, keys.ctypes.data, owner.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_gradient_rays: a descriptor outside its rules (radius 0..3, kappa >= 0, enabled 0 or 1, reserved words 0), "
+                           "not a recipe S frame or a sample outside [0, samples)")
+    return rays, keys, owner
+
+
+def sample_luminance(rgbz, hits, albedo):
+    """rtu_sample_luminance (pure host code): float32 [H, W], the luminance of the demodulated raw sample rgbz float32 [H, W, 4]; 0 for
+    a pixel that is not valid or not finite."""
+    import numpy as np
+    rgbz = np.ascontiguousarray(rgbz, np.float32)
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
+    d = gradient_desc(W, H)
+    out = np.empty((H, W), np.float32)
+    rc = hip.rtu_sample_luminance(ctypes.byref(d), rgbz.ctypes.data, hits.ctypes.data, albedo.ctypes.data, out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_sample_luminance: an empty image")
+    return out
+
+
+def temporal_gradient(prev_cam, cur_cam, hits, albedo, motion, hist_prev, lum_prev, owner, rgbt, desc=None, gradient=None):
+    """rtu_temporal_gradient (pure host code): the gradient rays' shaded samples rgbt float32 [SW * SH, 4] of the owners `owner`
+    (see gradient_rays()) against lum_prev float32 [H, W] (sample_luminance() of the previous frame) where the accumulator looks the
+    owner's history up in hist_prev float32 [4, H, W, 4] -> (diff float32 [SH, SW, 4] = {num, den, noise, 0}, lambda float32 [SH, SW]).
+    hist_prev None: no gradient anywhere. desc: an RtuTemporalDesc, gradient: an RtuGradientDesc, both sized from cur_cam."""
+    import numpy as np
+    W, H = cur_cam.width, cur_cam.height
+    sw, sh = strata(W, H)
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    owner = np.ascontiguousarray(owner, np.uint32)
+    rgbt = np.ascontiguousarray(rgbt, np.float32)
+    motion = _as_motion(motion)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W or owner.size != sw * sh or rgbt.size != 4 * sw * sh:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]; owner: uint32 [SW * SH]; rgbt: float32 [SW * SH, 4]")
+    if hist_prev is not None:
+        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
+        lum_prev = np.ascontiguousarray(lum_prev, np.float32)
+        if hist_prev.size != 16 * H * W or lum_prev.size != H * W:
+            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [4, H, W, 4]; lum_prev: float32 [H, W]")
+    td = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(td), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(td))
+    td.width, td.height = W, H
+    gd = _sized_gradient_desc(gradient, W, H)
+    diff, lam = np.empty((sh, sw, 4), np.float32), np.empty((sh, sw), np.float32)
+    rc = hip.rtu_temporal_gradient(ctypes.byref(td), ctypes.byref(gd), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam),
+                                   hits.ctypes.data, albedo.ctypes.data, motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()),
+                                   len(motion), hist_prev.ctypes.data if hist_prev is not None else None,
+                                   lum_prev.ctypes.data if hist_prev is not None else None, owner.ctypes.data, rgbt.ctypes.data, diff.ctypes.data,
+                                   lam.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_gradient: a descriptor outside its rules, a camera of another size, an owner outside the image, or a "
+                           "table entry with an unknown flag or a non-zero reserved word")
+    return diff, lam
+
+
+def temporal_accumulate_gradient(prev_cam, cur_cam, rgbz, hits, albedo, motion, hist_prev=None, desc=None, history_cap=0, lam=None):
+    """rtu_temporal_accumulate_gradient (pure host code): temporal_accumulate_moments() whose history taken over is capped once more,
+    per pixel, by lam float32 [SH, SW] (see temporal_gradient(); None: the moments form's bits) -> (accumulated rgbz, new history)."""
+    import numpy as np
+    if lam is not None:
+        H, W = np.shape(rgbz)[:2]
+        lam = np.ascontiguousarray(lam, np.float32)
+        if lam.size != strata(W, H)[0] * strata(W, H)[1]:
+            raise RtuError(RTU_ERR_ARG, "lam: float32 [SH, SW]")
+    call = lambda *a: hip.rtu_temporal_accumulate_gradient(*a, lam.ctypes.data if lam is not None else None)
+    rc, out, hist = _temporal_accumulate(4, call, prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc, motion, history_cap)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate_gradient: a descriptor outside its rules, a camera of another size, history_cap outside "
+                           "0..65535, or a table entry with an unknown flag or a non-zero reserved word")
+    return out, hist
+
+
 def sensor_desc(model, width, height, pos, right, up, forward, samples=0, gather_bounces=0, max_bounce=5, fov_deg=180.0, extent=(1, 1),
                 reference_walk=False):
     """An RtuSensorDesc: rtu_sensor_defaults, then the fields. model: RTU_SENSOR_* or "equirect" / "fisheye" / "ortho"; right, up and
@@ -1330,13 +1464,18 @@ class Temporal:
     variance: an RtuVarianceDesc (see variance_desc()) makes it a variance session (rtu_temporal_begin_variance): its history holds the
     moments, and every frame is filtered by denoise_variance() with the variance() of that history. steer: an RtuSteerDesc (see
     steer_desc(); with variance) makes it a steered session (rtu_temporal_begin_steered): every frame spends steer.budget extra rays
-    where that variance is highest and folds them into the history before it is filtered."""
+    where that variance is highest and folds them into the history before it is filtered. gradient: an RtuGradientDesc (see
+    gradient_desc(); with variance, steer or not) makes it a gradient session (rtu_temporal_begin_gradient): every frame re-shades one
+    pixel per 3 x 3 stratum with the previous frame's random numbers and shortens the history where the shading changed."""
 
-    def __init__(self, ctx, desc, variance=None, steer=None):
+    def __init__(self, ctx, desc, variance=None, steer=None, gradient=None):
         err = _I(0)
         self._ctx = ctx
         self.desc = desc
-        if steer is not None:
+        if gradient is not None:
+            self._h = hip.rtu_temporal_begin_gradient(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
+                                                      ctypes.byref(steer) if steer is not None else None, ctypes.byref(gradient), ctypes.byref(err))
+        elif steer is not None:
             self._h = hip.rtu_temporal_begin_steered(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
                                                      ctypes.byref(steer), ctypes.byref(err))
         elif variance is not None:
@@ -1392,6 +1531,25 @@ class Temporal:
 
     def history_device(self, d_n, stream=None):
         self._check(hip.rtu_temporal_history_device(self._h, d_n, stream))
+
+    def lambda_image(self):
+        """A gradient session: the lambda of every pixel's stratum in the last frame, float32 [H, W] (zeros where no gradient was taken)."""
+        import numpy as np
+        n = self.desc.width * self.desc.height
+        out = np.empty((self.desc.height, self.desc.width), np.float32)
+        d = hip.rtu_device_alloc(self._ctx._h, 4 * n)
+        if not d:
+            self._check(RTU_ERR_HIP)
+        try:
+            self.lambda_device(d, hip.rtu_context_stream(self._ctx._h))
+            self._check(hip.rtu_context_sync(self._ctx._h))
+            self._check(hip.rtu_copy_to_host(self._ctx._h, out.ctypes.data, d, 4 * n))
+        finally:
+            hip.rtu_device_free(self._ctx._h, d)
+        return out
+
+    def lambda_device(self, d_lambda, stream=None):
+        self._check(hip.rtu_temporal_lambda_device(self._h, d_lambda, stream))
 
     def extra_counts(self):
         """A steered session: the extra rays every pixel got in the last frame, uint32 [H, W] (zeros before the first)."""
@@ -1517,10 +1675,32 @@ class Context:
         snapshot() -> (rgbz, counts), close()."""
         return Progressive(self, frame, adaptive)
 
-    def temporal(self, desc, variance=None, steer=None):
+    def temporal(self, desc, variance=None, steer=None, gradient=None):
         """A temporal session (desc: an RtuTemporalDesc with the size of its frames, see temporal_desc()): frame(frame) -> rgbz,
-        frame_device(), history(), reset(), close(). variance, steer: see Temporal."""
-        return Temporal(self, desc, variance, steer)
+        frame_device(), history(), reset(), close(). variance, steer, gradient: see Temporal."""
+        return Temporal(self, desc, variance, steer, gradient)
+
+    def gradient_rays_device(self, desc, frame, sample, d_rays_ptr, d_keys_ptr, d_owner_ptr, stream=None):
+        """rtu_gradient_rays_device: gradient_rays() written to device memory by a kernel, one ray, key and owner per stratum."""
+        self._check(hip.rtu_gradient_rays_device(self._h, ctypes.byref(desc), ctypes.byref(frame), int(sample), d_rays_ptr, d_keys_ptr, d_owner_ptr, stream))
+
+    def sample_luminance_device(self, desc, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_lum_ptr, stream=None):
+        """rtu_sample_luminance_device: sample_luminance() on device memory, desc.width * desc.height floats to d_lum_ptr."""
+        self._check(hip.rtu_sample_luminance_device(self._h, ctypes.byref(desc), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_lum_ptr, stream))
+
+    def temporal_gradient_device(self, desc, gradient, prev_cam, cur_cam, d_hits_ptr, d_albedo_ptr, d_motion_ptr, n_nodes, d_hist_prev_ptr, d_lum_prev_ptr,
+                                 d_owner_ptr, d_rgbt_ptr, d_diff_ptr, d_lambda_ptr, stream=None):
+        """rtu_temporal_gradient_device: temporal_gradient() on device memory: one float4 and one float per stratum."""
+        self._check(hip.rtu_temporal_gradient_device(self._h, ctypes.byref(desc), ctypes.byref(gradient), ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                                     ctypes.byref(cur_cam), d_hits_ptr, d_albedo_ptr, d_motion_ptr, n_nodes, d_hist_prev_ptr, d_lum_prev_ptr,
+                                                     d_owner_ptr, d_rgbt_ptr, d_diff_ptr, d_lambda_ptr, stream))
+
+    def temporal_accumulate_gradient_device(self, desc, prev_cam, cur_cam, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                            d_rgbz_out_ptr, d_motion_ptr, n_nodes, history_cap=0, d_lambda_ptr=None, stream=None):
+        """rtu_temporal_accumulate_gradient_device: temporal_accumulate_gradient() on device memory; d_lambda_ptr: one float per stratum or None."""
+        self._check(hip.rtu_temporal_accumulate_gradient_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                                                ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
+                                                                d_rgbz_out_ptr, d_motion_ptr, n_nodes, int(history_cap), d_lambda_ptr, stream))
 
     def sample_allocation_device(self, desc, d_hist_ptr, d_hits_ptr, d_v_ptr, d_counts_ptr, d_offsets_ptr, d_total_ptr, stream=None):
         """rtu_sample_allocation_device: sample_allocation() on device memory, the same words; the total is one uint32 at d_total_ptr."""

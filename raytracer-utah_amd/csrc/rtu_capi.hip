@@ -13,6 +13,7 @@
 #include "rtu_query.h"
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
+#include "rtu_gradient.h"
 #include "rtu_steer.h"
 #include "rtu_temporal.h"
 #include "rtu_variance.h"
@@ -1828,6 +1829,14 @@ struct RtuTemporal {
     DevBuf<uint32_t> st_counts, st_offsets, st_total_dev, st_keys, st_owner;
     DevBuf<float4>   st_rays, st_img;
     PinnedBuf<uint32_t> st_total_host;
+    bool             gradient = false;    // rtu_temporal_begin_gradient with enabled != 0: a frame with a previous frame shades the gradient rays
+    RtuGradientDesc  gdesc{};             // ... behind its own (rays, keys and img hold pixels + strata) and caps the history by their lambda
+    size_t           strata = 0;
+    bool             has_lambda = false;  // ... gr_lambda is that of the last frame
+    int              lcur = 0;            // ... lum[lcur] is the luminance plane of the last frame's sample
+    DevBuf<float>    lum[2], gr_lambda;
+    DevBuf<uint32_t> gr_owner;
+    DevBuf<float4>   gr_diff;
 };
 
 static void temporal_release(RtuTemporal* t) {
@@ -1849,6 +1858,11 @@ static void temporal_release(RtuTemporal* t) {
     t->st_img.reset();
     t->st_total_host.reset();
     t->st_total = 0;
+    for (DevBuf<float>& l : t->lum) l.reset();
+    t->gr_lambda.reset();
+    t->gr_owner.reset();
+    t->gr_diff.reset();
+    t->has_lambda = false;
     t->has_hist = false;
     t->ctx = nullptr;
 }
@@ -4377,6 +4391,163 @@ int rtu_temporal_steer_total(RtuTemporal* t, uint32_t* total_out) {
     return RTU_OK;
 }
 
+// ---- temporal gradients (rtu_gradient.h, rtu_gradient.hip): the gradient rays, the luminance plane, lambda and the capped accumulator ----
+static_assert(sizeof(RtuGradientDesc) == 32, "RtuGradientDesc is 32 bytes");
+
+static const char* const kGradientDescRules =
+    "gradient: width, height 1 .. 65536 (2^26 pixels), radius 0 .. 3, kappa >= 0 and finite, enabled 0 or 1, reserved words 0";
+
+static bool gradient_rays_args(const RtuGradientDesc* desc, const RtuFrameDesc* frame, int sample) {
+    return rtu_gradient_check_desc(desc) == RTU_OK && frame && frame->width == desc->width && frame->height == desc->height && frame->samples >= 1 &&
+           sample >= 0 && sample < frame->samples;
+}
+
+int rtu_gradient_rays(const RtuGradientDesc* desc, const RtuFrameDesc* frame, int sample, RtuRay* rays_out, uint32_t* keys_out, uint32_t* owner_out) {
+    if (!gradient_rays_args(desc, frame, sample) || !rays_out || !keys_out || !owner_out) return RTU_ERR_ARG;
+    const CamSample c = cam_sample(frame, sample);
+    const int32_t sw = gr_strata(desc->width), sh = gr_strata(desc->height);
+    for (uint32_t s = 0; s < (uint32_t)sw * (uint32_t)sh; s++) {
+        int x, y;
+        gr_owner(desc->width, desc->height, sw, s, desc->frame_index, x, y);
+        f3 org, dir;
+        uint32_t key;
+        camera_sample_ray(c, x, y, HostSinCos(), org, dir, key);
+        RtuRay& r = rays_out[s];
+        r.org[0] = org.x; r.org[1] = org.y; r.org[2] = org.z;
+        r.tmax = RTU_BIGFLOAT;
+        r.dir[0] = dir.x; r.dir[1] = dir.y; r.dir[2] = dir.z;
+        r.reserved = 0;
+        keys_out[s] = key;
+        owner_out[s] = (uint32_t)x + (uint32_t)desc->width * (uint32_t)y;
+    }
+    return RTU_OK;
+}
+
+int rtu_gradient_rays_device(RtuContext* ctx, const RtuGradientDesc* desc, const RtuFrameDesc* frame, int sample, void* d_rays, void* d_keys, void* d_owner,
+                             void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_gradient_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kGradientDescRules);
+    if (!gradient_rays_args(desc, frame, sample)) return fail(ctx, RTU_ERR_ARG, "gradient: the frame must have the desc's size and 0 <= sample < samples");
+    if (!d_rays || !d_keys || !d_owner) return fail(ctx, RTU_ERR_ARG, "gradient: a device pointer is NULL");
+    if (misaligned(d_rays) || misaligned4(d_keys) || misaligned4(d_owner))
+        return fail(ctx, RTU_ERR_ARG, "gradient: the ray buffer must be 16-byte, the other buffers 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_gradient_rays(cam_sample(frame, sample), desc->frame_index, (float4*)d_rays, (uint32_t*)d_keys,
+                                                              (uint32_t*)d_owner, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "gradient ray launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_sample_luminance_device(RtuContext* ctx, const RtuGradientDesc* desc, const void* d_rgbz, const void* d_hits, const void* d_albedo, void* d_lum,
+                                void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_gradient_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kGradientDescRules);
+    if (!d_rgbz || !d_hits || !d_albedo || !d_lum) return fail(ctx, RTU_ERR_ARG, "gradient: a device pointer is NULL");
+    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned4(d_lum))
+        return fail(ctx, RTU_ERR_ARG, "gradient: device buffers must be 16-byte aligned (d_lum: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_sample_luminance((size_t)desc->width * (size_t)desc->height, (const float4*)d_rgbz, (const float4*)d_hits,
+                                                                 (const float4*)d_albedo, (float*)d_lum, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "luminance launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_gradient_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuGradientDesc* gdesc, const RtuFrameDesc* prev_cam,
+                                 const RtuFrameDesc* cur_cam, const void* d_hits, const void* d_albedo, const RtuNodeMotion* d_motion, uint32_t n_nodes,
+                                 const void* d_hist_prev, const void* d_lum_prev, const void* d_owner, const void* d_rgbt, void* d_diff_out,
+                                 void* d_lambda_out, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
+    if (rtu_gradient_check_desc(gdesc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kGradientDescRules);
+    if (gdesc->width != desc->width || gdesc->height != desc->height) return fail(ctx, RTU_ERR_ARG, "gradient: the two descs must have one size");
+    if (!cur_cam || (d_hist_prev && !prev_cam)) return fail(ctx, RTU_ERR_ARG, "gradient: a camera is NULL");
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return fail(ctx, RTU_ERR_ARG, "gradient: the cameras must have the desc's width and height");
+    if (!d_hits || !d_albedo || !d_motion || !d_owner || !d_rgbt || !d_diff_out || !d_lambda_out || (d_hist_prev && !d_lum_prev))
+        return fail(ctx, RTU_ERR_ARG, "gradient: a device pointer is NULL");
+    if (misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_motion) || misaligned(d_hist_prev) || misaligned(d_rgbt) || misaligned(d_diff_out) ||
+        misaligned4(d_lum_prev) || misaligned4(d_owner) || misaligned4(d_lambda_out))
+        return fail(ctx, RTU_ERR_ARG, "gradient: device buffers must be 16-byte aligned (luminance, owners, lambda: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    GrParams G{};
+    G.M = tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, 0);
+    G.sw = gr_strata(desc->width);
+    G.sh = gr_strata(desc->height);
+    G.radius = gdesc->radius;
+    G.kappa = gdesc->kappa;
+    const hipError_t e = (hipError_t)rtu_launch_temporal_gradient(G, (const float4*)d_hits, (const float4*)d_albedo, d_motion, (const float4*)d_hist_prev,
+                                                                  (const float*)d_lum_prev, (const uint32_t*)d_owner, (const float4*)d_rgbt,
+                                                                  (float4*)d_diff_out, (float*)d_lambda_out, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "gradient launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate_gradient_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                            const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                            void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, const void* d_lambda,
+                                            void* hip_stream) {
+    const int rc = temporal_device_args(ctx, 4, true, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, d_motion, n_nodes,
+                                        history_cap);
+    if (rc != RTU_OK) return rc;
+    if (misaligned4(d_lambda)) return fail(ctx, RTU_ERR_ARG, "temporal: lambda must be 4-byte aligned");
+    const TpGradientParams g{tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap), (const float*)d_lambda,
+                             gr_strata(desc->width)};
+    const hipError_t e = (hipError_t)rtu_launch_temporal_capped(g, (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo,
+                                                                (const float4*)d_hist_prev, (float4*)d_hist_out, (float4*)d_rgbz_out, d_motion,
+                                                                (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+RtuTemporal* rtu_temporal_begin_gradient(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuVarianceDesc* vdesc, const RtuSteerDesc* sdesc,
+                                         const RtuGradientDesc* gdesc, int* err_out) {
+    auto refuse = [&](int rc) -> RtuTemporal* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (!gdesc || !desc || !vdesc) return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a descriptor is NULL"));
+    RtuGradientDesc gd = *gdesc;  // (its size is the session's, its frame_index the frame's)
+    gd.width = desc->width;
+    gd.height = desc->height;
+    gd.frame_index = 0;
+    if (rtu_temporal_check_desc(desc) == RTU_OK && rtu_gradient_check_desc(&gd) != RTU_OK) return refuse(fail(ctx, RTU_ERR_ARG, "%s", kGradientDescRules));
+    RtuTemporal* t = sdesc ? rtu_temporal_begin_steered(ctx, desc, vdesc, sdesc, err_out) : rtu_temporal_begin_variance(ctx, desc, vdesc, err_out);
+    if (!t || !gd.enabled) return t;
+    t->gradient = true;
+    t->gdesc = gd;
+    t->strata = (size_t)gr_strata(gd.width) * (size_t)gr_strata(gd.height);
+    const size_t n = t->pixels, m = t->strata;
+    hipError_t e = t->rays.grow(2 * (n + m));
+    if (e == hipSuccess) e = t->keys.grow(n + m);
+    if (e == hipSuccess) e = t->img.grow(n + m);
+    for (DevBuf<float>& l : t->lum)
+        if (e == hipSuccess) e = l.grow(n);
+    if (e == hipSuccess) e = t->gr_lambda.grow(m);
+    if (e == hipSuccess) e = t->gr_owner.grow(m);
+    if (e == hipSuccess) e = t->gr_diff.grow(m);
+    if (e != hipSuccess) {
+        const int rc = fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e));
+        rtu_temporal_free(t);
+        return refuse(rc);
+    }
+    return t;
+}
+
+int rtu_temporal_lambda_device(RtuTemporal* t, void* d_lambda, void* hip_stream) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!d_lambda) return fail(ctx, RTU_ERR_ARG, "d_lambda is NULL");
+    if (misaligned4(d_lambda)) return fail(ctx, RTU_ERR_ARG, "d_lambda must be 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const bool live = t->gradient && t->has_lambda && t->has_hist;
+    const hipError_t e = (hipError_t)rtu_launch_lambda_image(t->desc.width, t->desc.height, live ? t->gr_lambda.get() : nullptr, (float*)d_lambda,
+                                                             (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "lambda launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
 // what a moved frame has beyond a plain one (rtu_temporal_frame_moved_device)
 struct TemporalMoved {
     const RtuNodeMotion* h_motion;
@@ -4436,15 +4607,26 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     }
     int rc = rtu_camera_sample_rays_device(ctx, frame, t->k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
     if (rc != RTU_OK) return rc;
+    // A gradient session: the gradient rays behind the frame's own, shaded with them in the one launch sequence. A frame without a
+    // previous one shades them too and uses none of their results — the batch of every frame has one size, so the context's frame
+    // records grow in the first frame and no later frame allocates.
+    const bool grad = t->gradient && t->has_hist;
+    const size_t shaded = t->gradient ? n + t->strata : n;
+    if (t->gradient) {
+        t->gdesc.frame_index = (uint32_t)t->k;
+        if ((rc = rtu_gradient_rays_device(ctx, &t->gdesc, frame, (t->k + frame->samples - 1) % frame->samples, t->rays.get() + 2 * n, t->keys.get() + n,
+                                           t->gr_owner.get(), hip_stream)) != RTU_OK)
+            return rc;
+    }
     RtuShadeDesc sd;
     rtu_shade_defaults(&sd);
     memcpy(sd.eye, frame->cam_pos, sizeof sd.eye);
     sd.max_bounce = frame->max_bounce;
     RtuFrameDesc f;
-    if ((rc = shade_args(ctx, t->rays.get(), t->img.get(), n, &sd, true, &f, true, t->keys.get(), paths)) != RTU_OK) return rc;
+    if ((rc = shade_args(ctx, t->rays.get(), t->img.get(), shaded, &sd, true, &f, true, t->keys.get(), paths)) != RTU_OK) return rc;
     // as shade_host: the chain of recipe P is traced once, the shading is what is repeated when the frame records ran out
-    if (paths && (rc = paths_chain(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n)) != RTU_OK) return rc;
-    if ((rc = shade_until_fits(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n, paths, nullptr)) != RTU_OK) return rc;
+    if (paths && (rc = paths_chain(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)shaded)) != RTU_OK) return rc;
+    if ((rc = shade_until_fits(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)shaded, paths, nullptr)) != RTU_OK) return rc;
     if ((rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
     RtuTemporalDesc td = t->desc;
     td.flags = 0;
@@ -4463,9 +4645,24 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         }
         if (n_nodes > 0)
             RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
-        rc = rtu_temporal_accumulate_moments_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
-                                                    t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(),
-                                                    n_nodes, moved ? moved->history_cap : 0, hip_stream);
+        if (grad) {
+            rc = rtu_temporal_gradient_device(ctx, &td, &t->gdesc, &t->prev_cam, frame, t->hits.get(), t->albedo.get(), t->motion.get(), n_nodes,
+                                              t->hist[t->cur].get(), t->lum[t->lcur].get(), t->gr_owner.get(), t->img.get() + n, t->gr_diff.get(),
+                                              t->gr_lambda.get(), hip_stream);
+            if (rc == RTU_OK)
+                rc = rtu_temporal_accumulate_gradient_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                                             t->hist[t->cur].get(), t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), n_nodes,
+                                                             moved ? moved->history_cap : 0, t->gr_lambda.get(), hip_stream);
+        } else {
+            rc = rtu_temporal_accumulate_moments_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                                        t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(),
+                                                        n_nodes, moved ? moved->history_cap : 0, hip_stream);
+        }
+        if (rc == RTU_OK && t->gradient) {  // the luminance of this frame's sample: what the next frame's gradients are taken against
+            rc = rtu_sample_luminance_device(ctx, &t->gdesc, t->img.get(), t->hits.get(), t->albedo.get(), t->lum[t->lcur ^ 1].get(), hip_stream);
+            t->lcur ^= 1;
+            t->has_lambda = grad;
+        }
     } else if (moved && t->has_hist) {
         // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
         memcpy(t->motion_host.get(), moved->h_motion, moved->n_nodes * sizeof(RtuNodeMotion));
@@ -4534,6 +4731,7 @@ int rtu_temporal_reset(RtuTemporal* t) {
     t->has_hist = false;
     t->k = 0;
     t->st_total = 0;
+    t->has_lambda = false;
     return RTU_OK;
 }
 

@@ -1,7 +1,8 @@
 // rtu_temporal.h — the arithmetic of the temporal accumulator (include/rtu_render.h "Temporal accumulation", "... across scene
 // updates" and the moments of "Variance-guided filtering"), host + device, and the launch interface of its kernels (rtu_temporal.hip),
 // called by rtu_capi.hip. The three forms — rtu_temporal_accumulate, _motion and _moments, each with its _device form — are the
-// instantiations of one function, tp_pixel<MOVING, MOMENTS>.
+// instantiations of one function, tp_pixel<MOVING, MOMENTS>; rtu_temporal_accumulate_gradient ("Temporal gradients") is a fourth,
+// tp_pixel<true, true, true>.
 //
 // A pixel's first-hit point is projected into the previous camera, the history is fetched there with four bilinear taps, each tested
 // for being the same surface, and the new sample is blended in. No transcendental function: the translation units that include this
@@ -20,6 +21,7 @@
 #define TP_LOOKUP_NONE      0  // no previous history
 #define TP_LOOKUP_STATIC    1  // the cameras are equal bit for bit: the pixel itself with weight 1
 #define TP_LOOKUP_REPROJECT 2
+#define TP_STRATUM          3  // the strata of "Temporal gradients" are TP_STRATUM x TP_STRATUM pixels
 
 // what a pixel needs of the desc and of the PREVIOUS camera; made once per call by tp_setup on the host, for both forms
 struct TpParams {
@@ -89,6 +91,14 @@ inline TpMotionParams tp_motion_setup(const RtuTemporalDesc& d, const RtuFrameDe
     return M;
 }
 
+// What the gradient form needs beyond TpMotionParams: one lambda per stratum, sw = ceil(width / TP_STRATUM) strata per row (host
+// memory in the host form, device memory in the kernel); nullptr: no pixel is capped.
+struct TpGradientParams {
+    TpMotionParams M;
+    const float*   lambda;
+    int32_t        sw;
+};
+
 // the words of an RtuNodeMotion that are read, in registers: the caller loads them (the kernel with 16-byte loads, the host form from
 // a table of any alignment)
 struct TpMotion {
@@ -110,6 +120,22 @@ RTU_HD int32_t tp_motion_index(const float4& hit0, uint32_t n_nodes) {
     flags.f = hit0.z;
     node.f = hit0.y;
     return ((flags.u & RTU_RAY_HIT) != 0 && node.u < n_nodes && node.u < 0x80000000u) ? (int32_t)node.u : -1;
+}
+
+// the table entry of a pixel (k >= 0) or the identity; 16-byte loads: the table is 16-byte aligned and an entry is 96 B
+__device__ inline TpMotion tp_load_motion(const RtuNodeMotion* __restrict__ motion, int32_t k) {
+    TpMotion T = tp_motion_identity();
+    if (k >= 0) {
+        const float4* e = reinterpret_cast<const float4*>(motion + k);
+        const float4 a = e[0], b = e[1], c = e[2], d = e[3], f = e[4], g = e[5];
+        union { float f; uint32_t u; } fl;
+        fl.f = g.y;
+        T.m[0] = a.x; T.m[1] = a.y; T.m[2] = a.z; T.m[3] = a.w; T.m[4] = b.x; T.m[5] = b.y; T.m[6] = b.z; T.m[7] = b.w;
+        T.m[8] = c.x; T.m[9] = c.y; T.m[10] = c.z; T.m[11] = c.w;
+        T.g[0] = d.x; T.g[1] = d.y; T.g[2] = d.z; T.g[3] = d.w; T.g[4] = f.x; T.g[5] = f.y; T.g[6] = f.z; T.g[7] = f.w; T.g[8] = g.x;
+        T.flags = fl.u;
+    }
+    return T;
 }
 
 // Where the surface point of a pixel was in the previous scene: Pm, Nm by the pixel's table entry T (tp_motion_identity() when in_table
@@ -143,10 +169,15 @@ RTU_HD float vr_lum(const f3& e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.07
 
 // ---- the accumulator: one function for the three forms ---------------------------------------------------------------------------
 // MOVING: the hit point is carried through its node's table entry before the lookup, and the history taken over is capped
-// (TpMotionParams); else the scene is at rest (TpParams). MOMENTS: the history has the fourth plane M.
-template <bool MOVING> using TpArgs = typename std::conditional<MOVING, TpMotionParams, TpParams>::type;
+// (TpMotionParams); else the scene is at rest (TpParams). MOMENTS: the history has the fourth plane M. GRADIENT (with both): the
+// history taken over is capped once more, by the lambda of the pixel's stratum (TpGradientParams).
+template <bool MOVING, bool GRADIENT = false>
+using TpArgs = typename std::conditional<GRADIENT, TpGradientParams, typename std::conditional<MOVING, TpMotionParams, TpParams>::type>::type;
 RTU_HD const TpParams& tp_base(const TpParams& p) { return p; }
 RTU_HD const TpParams& tp_base(const TpMotionParams& m) { return m.P; }
+RTU_HD const TpParams& tp_base(const TpGradientParams& g) { return g.M.P; }
+RTU_HD const TpMotionParams& tp_motion(const TpMotionParams& m) { return m; }
+RTU_HD const TpMotionParams& tp_motion(const TpGradientParams& g) { return g.M; }
 
 // the weighted sums over the accepted taps of a lookup: E.rgb, E.n, the weights, and with MOMENTS M.xy
 struct TpSums {
@@ -181,9 +212,10 @@ RTU_HD void tp_tap(const TpParams& P, const float4* const* h, int qx, int qy, fl
 // RtuRayHit; MOVING: in_table / T as for tp_moved_point (else neither is read). out: its pixel of the accumulated image; o: its pixel
 // of the planes of the new history, all written after every read. A.lookup is wave-uniform without MOVING; with it, whether a pixel
 // takes no, one or four taps is its own matter.
-template <bool MOVING, bool MOMENTS>
-RTU_HD void tp_pixel(const TpArgs<MOVING>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
+RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
                      const float4* hit, const float4& albedo, float4& out, float4* o) {
+    static_assert(!GRADIENT || (MOVING && MOMENTS), "the gradient form is a moments form");
     const TpParams& P = tp_base(A);
     union { float f; uint32_t u; } flags, node;
     flags.f = hit[0].z;
@@ -198,7 +230,7 @@ RTU_HD void tp_pixel(const TpArgs<MOVING>& A, bool in_table, const TpMotion& T, 
     bool look = valid && P.lookup != TP_LOOKUP_NONE, one_tap = valid && P.lookup == TP_LOOKUP_STATIC;
     if constexpr (MOVING) {
         look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && look;
-        one_tap = look && A.same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
+        one_tap = look && tp_motion(A).same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
     }
 
     TpSums S = {mk3(0.0f, 0.0f, 0.0f), 0.0f, 0.0f, 0.0f, 0.0f};
@@ -229,7 +261,16 @@ RTU_HD void tp_pixel(const TpArgs<MOVING>& A, bool in_table, const TpMotion& T, 
         }
     }
     if constexpr (MOVING)
-        if (A.cap > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, A.cap);
+        if (tp_motion(A).cap > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, tp_motion(A).cap);
+    if constexpr (GRADIENT) {  // the weight of the new sample is not below lambda; lambda >= 1 starts the pixel over
+        const float lambda = A.lambda ? A.lambda[(size_t)(y / TP_STRATUM) * (size_t)A.sw + (size_t)(x / TP_STRATUM)] : 0.0f;
+        if (lambda > 0.0f && n_prev > 0.0f) n_prev = smin(n_prev, lambda < 1.0f ? 1.0f / lambda - 1.0f : 0.0f);
+        if (n_prev == 0.0f) {  // (lambda >= 1) as a pixel that found no history
+            e_prev = mk3(0.0f, 0.0f, 0.0f);
+            m1_prev = 0.0f;
+            m2_prev = 0.0f;
+        }
+    }
 
     const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);  // else the sample is not accumulated
     const bool fresh = n_prev == 0.0f;
@@ -281,6 +322,9 @@ int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, cons
                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                 float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
+// The gradient form: the moments form with g.lambda, device memory (nullptr: the moments form's bits).
+int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 // n_out[i] = the history length of pixel i (E.w of `hist`), or 0 everywhere with hist == nullptr
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream);
 

@@ -1,7 +1,8 @@
 // rtu_temporal.hip — the temporal accumulator of include/rtu_render.h ("Temporal accumulation", "... across scene updates", and the
 // moments of "Variance-guided filtering"): its host forms rtu_temporal_accumulate, _motion and _moments, which are the executable
 // statement of the rules, and the kernels of their _device forms. Both call tp_pixel<MOVING, MOMENTS> of rtu_temporal.h, pixel by
-// pixel; the three forms are the instantiations <false, false>, <true, false> and <true, true> of one kernel and of one host loop.
+// pixel; the three forms are the instantiations <false, false>, <true, false> and <true, true> of one kernel and of one host loop,
+// and rtu_temporal_accumulate_gradient ("Temporal gradients") is <true, true, true>.
 //
 //   k_temporal          one lane per pixel, 32 x 8 pixel workgroups as k_dn_pass (a wavefront is two rows of 32). A lane reads its
 //                       pixel's {rgbz, RtuRayHit, albedo} (80 B), up to four taps of the previous history — three 16-byte loads each,
@@ -14,6 +15,7 @@
 //                       entries a frame touches stay in the vector L1. The lookup mode (none, one tap, four taps) is per lane;
 //                       single exit, select on values.
 //     MOMENTS           a four-plane history: besides, one 16-byte load of M per ACCEPTED tap and one 16-byte store.
+//     GRADIENT          besides, one dword load of the lambda of the pixel's stratum: the three lanes of a stratum's row share it.
 //   k_temporal_history  one lane per pixel: the history length out of the E plane.
 //   k_motion_vectors    one lane per pixel: its RtuRayHit and its node's entry in, one float4 out.
 // Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
@@ -25,25 +27,9 @@
 
 namespace {
 
-// the table entry of a pixel (k >= 0) or the identity; 16-byte loads: the table is 16-byte aligned and an entry is 96 B
-__device__ TpMotion load_motion(const RtuNodeMotion* __restrict__ motion, int32_t k) {
-    TpMotion T = tp_motion_identity();
-    if (k >= 0) {
-        const float4* e = reinterpret_cast<const float4*>(motion + k);
-        const float4 a = e[0], b = e[1], c = e[2], d = e[3], f = e[4], g = e[5];
-        union { float f; uint32_t u; } fl;
-        fl.f = g.y;
-        T.m[0] = a.x; T.m[1] = a.y; T.m[2] = a.z; T.m[3] = a.w; T.m[4] = b.x; T.m[5] = b.y; T.m[6] = b.z; T.m[7] = b.w;
-        T.m[8] = c.x; T.m[9] = c.y; T.m[10] = c.z; T.m[11] = c.w;
-        T.g[0] = d.x; T.g[1] = d.y; T.g[2] = d.z; T.g[3] = d.w; T.g[4] = f.x; T.g[5] = f.y; T.g[6] = f.z; T.g[7] = f.w; T.g[8] = g.x;
-        T.flags = fl.u;
-    }
-    return T;
-}
-
 // `motion` is read with MOVING only; hist_prev and hist_out have three planes, with MOMENTS four
-template <bool MOVING, bool MOMENTS>
-__global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING> A, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
+__global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING, GRADIENT> A, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
                                                   const float4* __restrict__ hist_prev, float4* __restrict__ hist_out, float4* rgbz_out,
                                                   const RtuNodeMotion* __restrict__ motion) {
     constexpr int PLANES = MOMENTS ? 4 : 3;
@@ -54,21 +40,21 @@ __global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING> A, const float4
     const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
     const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
     int32_t k = -1;
-    if constexpr (MOVING) k = tp_motion_index(hit[0], A.n_nodes);
-    const TpMotion T = load_motion(motion, k);
+    if constexpr (MOVING) k = tp_motion_index(hit[0], tp_motion(A).n_nodes);
+    const TpMotion T = tp_load_motion(motion, k);
     const float4* h[PLANES];
     for (int i = 0; i < PLANES; i++) h[i] = hist_prev ? hist_prev + i * n : nullptr;
     float4 out, o[PLANES];
-    tp_pixel<MOVING, MOMENTS>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o);
+    tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o);
     rgbz_out[p] = out;
     for (int i = 0; i < PLANES; i++) hist_out[i * n + p] = o[i];
 }
 
-template <bool MOVING, bool MOMENTS>
-int launch_temporal(const TpArgs<MOVING>& a, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
+int launch_temporal(const TpArgs<MOVING, GRADIENT>& a, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
                     float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
     const dim3 grid((uint32_t)((tp_base(a).width + 31) / 32), (uint32_t)((tp_base(a).height + 7) / 8));
-    hipLaunchKernelGGL((k_temporal<MOVING, MOMENTS>), grid, dim3(256), 0, stream, a, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
+    hipLaunchKernelGGL((k_temporal<MOVING, MOMENTS, GRADIENT>), grid, dim3(256), 0, stream, a, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
     return (int)hipGetLastError();
 }
 
@@ -79,7 +65,7 @@ __global__ void __launch_bounds__(256) k_motion_vectors(TpParams P, uint32_t n_n
     const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
     const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
     const int32_t k = tp_motion_index(hit[0], n_nodes);
-    mv[p] = tp_motion_vector(P, k >= 0, load_motion(motion, k), hit);
+    mv[p] = tp_motion_vector(P, k >= 0, tp_load_motion(motion, k), hit);
 }
 
 __global__ void __launch_bounds__(256) k_temporal_history(const float4* __restrict__ hist, float* __restrict__ n_out, unsigned long long pixels) {
@@ -103,6 +89,11 @@ int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, cons
 int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                 float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
     return launch_temporal<true, true>(m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
+}
+
+int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
+                               float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
+    return launch_temporal<true, true, true>(g, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
 }
 
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream) {
@@ -145,11 +136,12 @@ int rtu_temporal_check_desc(const RtuTemporalDesc* d) {
     return RTU_OK;
 }
 
-// the three host forms: motion, n_nodes and history_cap are read with MOVING only; the histories have three planes, with MOMENTS four
-template <bool MOVING, bool MOMENTS>
+// the host forms: motion, n_nodes and history_cap are read with MOVING only; the histories have three planes, with MOMENTS four;
+// lambda (one float per stratum, or nullptr) is read with GRADIENT only
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
 static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz, const RtuRayHit* h_hits,
                            const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion,
-                           uint32_t n_nodes, int32_t history_cap) {
+                           uint32_t n_nodes, int32_t history_cap, const float* lambda = nullptr) {
     constexpr int PLANES = MOMENTS ? 4 : 3;
     if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
     if (MOVING && (!motion || rtu_temporal_check_motion(motion, n_nodes, history_cap) != RTU_OK)) return RTU_ERR_ARG;
@@ -163,8 +155,10 @@ static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev
         const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 16 * PLANES * n;
         if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
     }
-    TpArgs<MOVING> A;
-    if constexpr (MOVING) A = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
+    TpArgs<MOVING, GRADIENT> A;
+    if constexpr (GRADIENT) A = TpGradientParams{tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap), lambda,
+                                                 (W + TP_STRATUM - 1) / TP_STRATUM};
+    else if constexpr (MOVING) A = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
     else A = tp_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr);
     std::vector<float4> prev;  // (the planes as float4: the caller's floats need not be 16-byte aligned)
     const float4* hp[PLANES] = {};
@@ -180,7 +174,7 @@ static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev
             const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
             const int32_t k = MOVING ? tp_motion_index(hit[0], n_nodes) : -1;
             float4 out, o[PLANES];
-            tp_pixel<MOVING, MOMENTS>(A, k >= 0, host_motion(motion, k), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o);
+            tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, host_motion(motion, k), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o);
             st4(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
             for (int i = 0; i < PLANES; i++) st4(h_hist_out, i * n + p, o[i]);
         }
@@ -213,6 +207,13 @@ int rtu_temporal_accumulate_moments(const RtuTemporalDesc* desc, const RtuFrameD
                                     const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
                                     const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap) {
     return accumulate_host<true, true>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes, history_cap);
+}
+
+int rtu_temporal_accumulate_gradient(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                     const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out,
+                                     const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap, const float* h_lambda) {
+    return accumulate_host<true, true, true>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes,
+                                             history_cap, h_lambda);
 }
 
 int rtu_motion_vectors(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuNodeMotion* motion, uint32_t n_nodes,
