@@ -1093,6 +1093,97 @@ RtuTemporal* rtu_temporal_begin_gradient(RtuContext* ctx, const RtuTemporalDesc*
                                          const RtuSteerDesc* steer_desc_or_null, const RtuGradientDesc* gradient_desc, int* err_out);
 int  rtu_temporal_lambda_device(RtuTemporal* t, void* d_lambda, void* hip_stream);
 
+/* ---- Sparse sessions: one pixel of every block is shaded per frame, the history carries the rest (rtu_sparse.h, rtu_sparse.hip) ----
+ * Every session above fires at least one new ray per pixel per frame, and shading that ray is most of a frame. A sparse session shades
+ * ONE pixel of every B x B BLOCK per frame — the block's OWNER, which rotates from frame to frame — and lets the full-resolution
+ * history carry the other pixels. The guides (RtuRayHit, albedo) stay at full resolution: reprojection and the surface test are what
+ * they were, geometry edges stay sharp, and shading is amortised over B * B frames. Binary32, one rounding per operation, no
+ * contraction, IEEE divisions, in this order; host and device forms give the same bits. VALID, d, the table, a tap's ACCEPTED and the
+ * moments form's e, n, m, E, M, keep ("has an accumulated colour") are those of the sections above.
+ *
+ * 1. BLOCKS, OWNERS AND RAYS  SW = ceil(width / B), SH = ceil(height / B); block (bx, by) has index b = bx + SW * by and covers
+ *   bw x bh pixels, bw = min(B, width - B bx), bh = min(B, height - B by), m = bw * bh. In frame frame_index = k (unsigned 32-bit):
+ *     j = k mod m;  t = (j * M_B) mod m in a full block (m == B * B), M_1 = 1, M_2 = 3, M_3 = 5, M_4 = 7 (= 2 B - 1, coprime to B * B:
+ *     consecutive frames land far apart and every pixel is the owner exactly once in B * B consecutive frames); t = j in a partial block;
+ *     owner_b = (B bx + t mod bw) + width * (B by + t div bw);  s_b = (k div m) mod S, S = frame->samples.
+ *   rtu_sparse_rays writes, per block in index order, owner_b and the ray and key of that pixel in rtu_camera_sample_rays(frame, s_b),
+ *   bit for bit. A pixel thus walks through all S samples of the frame, not a residue class of them. The frame must have the desc's
+ *   size and samples >= 1.
+ *
+ * 2. THE SPARSE ACCUMULATOR  rtu_temporal_accumulate_sparse is rtu_temporal_accumulate_moments with one changed input: in place of
+ *   an image of samples it takes rgbt — SW * SH float4 {r, g, b, t}, what the ray-batch entries return for the rays of step 1 — and
+ *   owner, SW * SH pixel indices. Pixel p = x + width * y belongs to block b = (x div B) + SW * (y div B).
+ *     owner[b] == p: c = rgbt[b].rgb, z_out = rgbt[b].w, and everything is the moments form's rule for a pixel with that sample —
+ *       also where it passes its input through (an invalid pixel; a valid one that found no history and whose c is not finite).
+ *     otherwise: the pixel is treated as the moments form treats a pixel whose sample has a channel that is not finite — e = e_prev,
+ *       n = n_prev, m = m_prev; with n_prev == 0, E = M = 0 —, z_out = H.t where the pixel is VALID and RTU_BIGFLOAT where not, and
+ *       rgb = e * d where the pixel has an accumulated colour (VALID and n_prev > 0), zeros where not.
+ *   The planes P and N are written as always, from the guides. hole_out — width * height bytes — is 1 for a pixel that is not its
+ *   block's owner and has no accumulated colour, 0 for every other pixel (an owner that passed its sample through is 0).
+ *   With B == 1 every pixel is an owner: the outputs are the moments form's bit for bit and hole_out is zeros. An owner entry that
+ *   names no pixel of its block leaves the block without a sample; nothing else happens.
+ *
+ * 3. THE FILL  rtu_sparse_fill, for display only (the history is not touched): for every pixel p with hole[p] == 1 — no other pixel of
+ *   rgbz is written —, over the blocks (bx + dx, by + dy), dy outer, dx inner, both -1 .. 1, that lie in the block grid, with q the
+ *   block's owner and c the rgb of its rgbt: the block is skipped unless every channel of c is finite and q has p's validity. Then
+ *     fdx = (float)(q.x - p.x), fdy likewise;  w = 1 / (1 + (fdx * fdx + fdy * fdy))
+ *     e = c / d_q per channel where p is VALID, e = c where not;  A2 += e * w;  W2 += w
+ *     and where p is VALID and the tap q would be ACCEPTED for p — node bits equal, dot(N_p, N_q) >= normal_min,
+ *     |dot(N_p, P_q - P_p)| <= sigma_plane * H_p.t —: A1 += e * w;  W1 += w.
+ *   Tier 1 (A1, W1) is used where W1 > 0, else tier 2 (A2, W2); rgb = (A / W) * d_p where p is VALID, A / W where not; zeros where
+ *   both found nothing. z stays what step 2 wrote.
+ *
+ * RTU_ERR_ARG: what the moments form refuses; a NULL pointer (hist_prev, and with it prev_cam, may be NULL); a sparse desc of another
+ * size than the temporal desc or the frame, or outside its rules: width, height 1 .. 65536 and 2^26 pixels, block 1 .. 4, reserved
+ * words 0; a device pointer that is not 16-byte aligned (keys, owners: 4-byte; the hole plane: any). The host forms — pure host code,
+ * no GPU and no context — also refuse, in rtu_sparse_fill, an owner outside the image. THE DEVICE FORMS TRUST THE TABLE AND THE OWNERS
+ * but never leave the arrays: an owner outside the image is skipped by the fill. They allocate nothing, need no scene, touch no state
+ * of the context and are asynchronous on hip_stream: rtu_sparse_rays_device (k_sparse_rays, a lane per block),
+ * rtu_temporal_accumulate_sparse_device (k_temporal<true, true, false, true>) and rtu_sparse_fill_device (k_sparse_fill, a lane per
+ * pixel). No output may overlap an input, but for rgbz of the fill, which is updated in place.
+ *
+ * THE SESSION  rtu_temporal_begin_sparse opens a variance session whose frames, plain and moved, change as follows: (1) in place of
+ * rtu_camera_sample_rays_device, rtu_sparse_rays_device with frame_index = the session's k (frames since begin / reset / start-over);
+ * (2) the unchanged shading path shades SW * SH rays, the capacity retry as before; (3) after the full-resolution guides come
+ * rtu_temporal_accumulate_sparse_device in place of the moments form and rtu_sparse_fill_device; (4) rtu_variance_device and
+ * rtu_denoise_variance_device, unchanged. sparse_desc: width and height are both 0 (the session's are used) or the session's, any other
+ * size is refused; frame_index is ignored; block == 1
+ * gives a variance session's bits and launches nothing more. rtu_temporal_holes counts the pixels of the last frame's hole plane (0
+ * before the first frame and with block == 1; it waits for that frame through an event of the session's, on the context's own
+ * stream: the stream the frame was given need not exist any more). The buffers — those of a variance session, whose ray, key and
+ * result buffers keep the size of the image though a frame uses their first SW * SH entries, and besides 4 B per block (the owners),
+ * one byte per pixel on the device and one of pinned host memory — belong to the session and are allocated at begin; a frame
+ * allocates nothing after the first. Frame 0 shades one pixel per block like every other: the first B * B frames show mostly filled
+ * pixels. Everything else — reset, free, the handle after rtu_destroy_context, the start-over after a scene change on a plain frame —
+ * as for a variance session. RTU_ERR_ARG besides: RTU_TEMPORAL_DENOISE. Not done here: sparse sessions combined with steering or
+ * gradients (there is no entry that opens one), a dense first frame, feeding the fill into the history, sharded frames. Measured
+ * times, hole counts and error ratios are in DESIGN.md section 28. */
+typedef struct RtuSparseDesc {     /* 32 B */
+    int32_t  width, height;
+    int32_t  block;                /* B, 1 .. 4 */
+    uint32_t frame_index;          /* selects the owners and their samples (rtu_sparse_rays); a session sets it */
+    uint32_t reserved[4];          /* must be 0 */
+} RtuSparseDesc;
+int  rtu_sparse_defaults(RtuSparseDesc* out);   /* width, height 0; block 2, frame_index 0 */
+int  rtu_sparse_rays(const RtuSparseDesc* desc, const RtuFrameDesc* frame, RtuRay* rays_out, uint32_t* keys_out, uint32_t* owner_out);
+int  rtu_sparse_rays_device(RtuContext* ctx, const RtuSparseDesc* desc, const RtuFrameDesc* frame, void* d_rays, void* d_keys, void* d_owner,
+                            void* hip_stream);
+int  rtu_temporal_accumulate_sparse(const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const RtuFrameDesc* prev_cam,
+                                    const RtuFrameDesc* cur_cam, const float* h_rgbt, const uint32_t* owner, const RtuRayHit* h_hits,
+                                    const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, uint8_t* h_hole_out,
+                                    const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap);
+int  rtu_temporal_accumulate_sparse_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const RtuFrameDesc* prev_cam,
+                                           const RtuFrameDesc* cur_cam, const void* d_rgbt, const void* d_owner, const void* d_hits,
+                                           const void* d_albedo, const void* d_hist_prev, void* d_hist_out, void* d_rgbz_out, void* d_hole_out,
+                                           const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream);
+int  rtu_sparse_fill(const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const RtuRayHit* h_hits, const float* h_albedo,
+                     const uint32_t* owner, const float* h_rgbt, const uint8_t* h_hole, float* h_rgbz);
+int  rtu_sparse_fill_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const void* d_hits, const void* d_albedo,
+                            const void* d_owner, const void* d_rgbt, const void* d_hole, void* d_rgbz, void* hip_stream);
+RtuTemporal* rtu_temporal_begin_sparse(RtuContext* ctx, const RtuTemporalDesc* temporal_desc, const RtuVarianceDesc* variance_desc,
+                                       const RtuSparseDesc* sparse_desc, int* err_out);
+int  rtu_temporal_holes(RtuTemporal* t, uint32_t* count_out);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

@@ -174,7 +174,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_temporal_extra_counts_device", "rtu_temporal_steer_total",
                "rtu_gradient_defaults", "rtu_gradient_rays", "rtu_gradient_rays_device", "rtu_sample_luminance", "rtu_sample_luminance_device",
                "rtu_temporal_gradient", "rtu_temporal_gradient_device", "rtu_temporal_accumulate_gradient",
-               "rtu_temporal_accumulate_gradient_device", "rtu_temporal_begin_gradient", "rtu_temporal_lambda_device"]
+               "rtu_temporal_accumulate_gradient_device", "rtu_temporal_begin_gradient", "rtu_temporal_lambda_device",
+               "rtu_sparse_defaults", "rtu_sparse_rays", "rtu_sparse_rays_device", "rtu_temporal_accumulate_sparse",
+               "rtu_temporal_accumulate_sparse_device", "rtu_sparse_fill", "rtu_sparse_fill_device", "rtu_temporal_begin_sparse",
+               "rtu_temporal_holes"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -888,6 +891,133 @@ def temporal_accumulate_gradient(prev_cam, cur_cam, rgbz, hits, albedo, motion, 
     return out, hist
 
 
+# sparse sessions (include/rtu_render.h, "Sparse sessions")
+class RtuSparseDesc(ctypes.Structure):
+    """include/rtu_render.h RtuSparseDesc (32 bytes): the size of the image, the block size B and the frame's index."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("block", ctypes.c_int32), ("frame_index", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+_SD = ctypes.POINTER(RtuSparseDesc)
+_sig(hip, "rtu_sparse_defaults", _I, _SD)
+_sig(hip, "rtu_sparse_rays", _I, _SD, _FD, _P, _P, _P)
+_sig(hip, "rtu_sparse_rays_device", _I, _P, _SD, _FD, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_sparse", _I, _TD, _SD, _FD, _FD, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32)
+_sig(hip, "rtu_temporal_accumulate_sparse_device", _I, _P, _TD, _SD, _FD, _FD, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32, _P)
+_sig(hip, "rtu_sparse_fill", _I, _TD, _SD, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_sparse_fill_device", _I, _P, _TD, _SD, _P, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_begin_sparse", _P, _P, _TD, ctypes.POINTER(RtuVarianceDesc), _SD, ctypes.POINTER(_I))
+_sig(hip, "rtu_temporal_holes", _I, _P, ctypes.POINTER(_U32))
+
+
+def sparse_desc(width=0, height=0, **overrides):
+    """An RtuSparseDesc: rtu_sparse_defaults (block 2, frame_index 0), the size, then `overrides`."""
+    d = RtuSparseDesc()
+    hip.rtu_sparse_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def _sized_sparse_desc(desc, W, H):
+    d = RtuSparseDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else sparse_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    return d
+
+
+def sparse_blocks(width, height, block):
+    """(SW, SH): the block x block blocks of a width x height image."""
+    return (width + block - 1) // block, (height + block - 1) // block
+
+
+def sparse_rays(frame, desc=None):
+    """rtu_sparse_rays (pure host code): per block the pixel it owns in frame desc.frame_index and that pixel's ray and key in the
+    sample the block has reached -> (rays [SW * SH] of ray_dtype(), keys uint32, owner uint32). The size of desc is the frame's."""
+    import numpy as np
+    d = _sized_sparse_desc(desc, frame.width, frame.height)
+    n = 0
+    if 1 <= d.block <= 4:
+        sw, sh = sparse_blocks(frame.width, frame.height, d.block)
+        n = max(sw, 0) * max(sh, 0)
+    rays, keys, owner = np.zeros(max(n, 1), ray_dtype()), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    rc = hip.rtu_sparse_rays(ctypes.byref(d), ctypes.byref(frame), rays.ctypes.data, keys.ctypes.data, owner.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_sparse_rays: a descriptor outside its rules (block 1..4, reserved words 0) or not a recipe S frame")
+    return rays[:n], keys[:n], owner[:n]
+
+
+def temporal_accumulate_sparse(prev_cam, cur_cam, rgbt, owner, hits, albedo, motion, hist_prev=None, desc=None, sparse=None, history_cap=0):
+    """rtu_temporal_accumulate_sparse (pure host code): temporal_accumulate_moments() whose samples are rgbt float32 [SW * SH, 4], the
+    shaded rays of sparse_rays(), at the pixels `owner`; every other pixel keeps its history -> (rgbz [H, W, 4], the new history
+    [4, H, W, 4], hole uint8 [H, W]: 1 where a pixel has no colour). desc: an RtuTemporalDesc, sparse: an RtuSparseDesc, both sized
+    from cur_cam."""
+    import numpy as np
+    W, H = cur_cam.width, cur_cam.height
+    sd = _sized_sparse_desc(sparse, W, H)
+    rgbt = np.ascontiguousarray(rgbt, np.float32)
+    owner = np.ascontiguousarray(owner, np.uint32)
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    motion = _as_motion(motion)
+    if 1 <= sd.block <= 4:
+        sw, sh = sparse_blocks(W, H, sd.block)
+        if owner.size != sw * sh or rgbt.size != 4 * sw * sh:
+            raise RtuError(RTU_ERR_ARG, "owner: uint32 [SW * SH]; rgbt: float32 [SW * SH, 4]")
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]")
+    if hist_prev is not None:
+        hist_prev = np.ascontiguousarray(hist_prev, np.float32)
+        if hist_prev.size != 16 * H * W:
+            raise RtuError(RTU_ERR_ARG, "hist_prev: float32 [4, H, W, 4]")
+    td = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(td), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(td))
+    td.width, td.height = W, H
+    out, hist, hole = np.empty((H, W, 4), np.float32), np.empty((4, H, W, 4), np.float32), np.empty((H, W), np.uint8)
+    rc = hip.rtu_temporal_accumulate_sparse(ctypes.byref(td), ctypes.byref(sd), ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                            ctypes.byref(cur_cam), rgbt.ctypes.data, owner.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
+                                            hist_prev.ctypes.data if hist_prev is not None else None, hist.ctypes.data, out.ctypes.data,
+                                            hole.ctypes.data, motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion),
+                                            int(history_cap))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate_sparse: a descriptor outside its rules (block 1..4, reserved words 0; see "
+                           "temporal_accumulate_moments), a camera of another size, history_cap outside 0..65535, or a table entry with an "
+                           "unknown flag or a non-zero reserved word")
+    return out, hist, hole
+
+
+def sparse_fill(rgbz, hole, hits, albedo, owner, rgbt, desc=None, sparse=None):
+    """rtu_sparse_fill (pure host code): the pixels of rgbz float32 [H, W, 4] with hole [H, W] == 1 filled from the samples rgbt of the
+    neighbouring blocks' owners -> rgbz, a new array (the C entry works in place). Of desc (an RtuTemporalDesc) sigma_plane and
+    normal_min are used; sparse: an RtuSparseDesc; both sized from rgbz."""
+    import numpy as np
+    rgbz = np.array(rgbz, np.float32, order="C")
+    if rgbz.ndim != 3 or rgbz.shape[2] != 4:
+        raise RtuError(RTU_ERR_ARG, "rgbz: a float32 [H, W, 4] array")
+    H, W = rgbz.shape[:2]
+    sd = _sized_sparse_desc(sparse, W, H)
+    hole = np.ascontiguousarray(hole, np.uint8)
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    rgbt = np.ascontiguousarray(rgbt, np.float32)
+    owner = np.ascontiguousarray(owner, np.uint32)
+    if 1 <= sd.block <= 4:
+        sw, sh = sparse_blocks(W, H, sd.block)
+        if owner.size != sw * sh or rgbt.size != 4 * sw * sh:
+            raise RtuError(RTU_ERR_ARG, "owner: uint32 [SW * SH]; rgbt: float32 [SW * SH, 4]")
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W or hole.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]; hole: uint8 [H, W]")
+    td = RtuTemporalDesc()
+    ctypes.memmove(ctypes.byref(td), ctypes.byref(desc if desc is not None else temporal_desc()), ctypes.sizeof(td))
+    td.width, td.height = W, H
+    rc = hip.rtu_sparse_fill(ctypes.byref(td), ctypes.byref(sd), hits.ctypes.data, albedo.ctypes.data, owner.ctypes.data, rgbt.ctypes.data,
+                             hole.ctypes.data, rgbz.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_sparse_fill: a descriptor outside its rules or an owner outside the image")
+    return rgbz
+
+
 def sensor_desc(model, width, height, pos, right, up, forward, samples=0, gather_bounces=0, max_bounce=5, fov_deg=180.0, extent=(1, 1),
                 reference_walk=False):
     """An RtuSensorDesc: rtu_sensor_defaults, then the fields. model: RTU_SENSOR_* or "equirect" / "fisheye" / "ortho"; right, up and
@@ -1466,13 +1596,20 @@ class Temporal:
     steer_desc(); with variance) makes it a steered session (rtu_temporal_begin_steered): every frame spends steer.budget extra rays
     where that variance is highest and folds them into the history before it is filtered. gradient: an RtuGradientDesc (see
     gradient_desc(); with variance, steer or not) makes it a gradient session (rtu_temporal_begin_gradient): every frame re-shades one
-    pixel per 3 x 3 stratum with the previous frame's random numbers and shortens the history where the shading changed."""
+    pixel per 3 x 3 stratum with the previous frame's random numbers and shortens the history where the shading changed. sparse: an
+    RtuSparseDesc (see sparse_desc(); with variance, neither steer nor gradient) makes it a sparse session
+    (rtu_temporal_begin_sparse): every frame shades one pixel of every block, the history carries the others."""
 
-    def __init__(self, ctx, desc, variance=None, steer=None, gradient=None):
+    def __init__(self, ctx, desc, variance=None, steer=None, gradient=None, sparse=None):
         err = _I(0)
         self._ctx = ctx
         self.desc = desc
-        if gradient is not None:
+        if sparse is not None:
+            if steer is not None or gradient is not None:
+                raise RtuError(RTU_ERR_ARG, "a sparse session takes neither steer nor gradient")
+            self._h = hip.rtu_temporal_begin_sparse(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
+                                                    ctypes.byref(sparse), ctypes.byref(err))
+        elif gradient is not None:
             self._h = hip.rtu_temporal_begin_gradient(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
                                                       ctypes.byref(steer) if steer is not None else None, ctypes.byref(gradient), ctypes.byref(err))
         elif steer is not None:
@@ -1569,6 +1706,12 @@ class Temporal:
 
     def extra_counts_device(self, d_counts, stream=None):
         self._check(hip.rtu_temporal_extra_counts_device(self._h, d_counts, stream))
+
+    def holes(self):
+        """A sparse session: the number of pixels the last frame had no colour for and filled (0 before the first frame)."""
+        n = _U32(0)
+        self._check(hip.rtu_temporal_holes(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def steer_total(self):
         """A steered session: the number of extra rays of the last frame."""
@@ -1675,10 +1818,27 @@ class Context:
         snapshot() -> (rgbz, counts), close()."""
         return Progressive(self, frame, adaptive)
 
-    def temporal(self, desc, variance=None, steer=None, gradient=None):
+    def temporal(self, desc, variance=None, steer=None, gradient=None, sparse=None):
         """A temporal session (desc: an RtuTemporalDesc with the size of its frames, see temporal_desc()): frame(frame) -> rgbz,
-        frame_device(), history(), reset(), close(). variance, steer, gradient: see Temporal."""
-        return Temporal(self, desc, variance, steer, gradient)
+        frame_device(), history(), reset(), close(). variance, steer, gradient, sparse: see Temporal."""
+        return Temporal(self, desc, variance, steer, gradient, sparse)
+
+    def sparse_rays_device(self, desc, frame, d_rays_ptr, d_keys_ptr, d_owner_ptr, stream=None):
+        """rtu_sparse_rays_device: sparse_rays() written to device memory by a kernel, one ray, key and owner per block."""
+        self._check(hip.rtu_sparse_rays_device(self._h, ctypes.byref(desc), ctypes.byref(frame), d_rays_ptr, d_keys_ptr, d_owner_ptr, stream))
+
+    def temporal_accumulate_sparse_device(self, desc, sparse, prev_cam, cur_cam, d_rgbt_ptr, d_owner_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr,
+                                          d_hist_out_ptr, d_rgbz_out_ptr, d_hole_ptr, d_motion_ptr, n_nodes, history_cap=0, stream=None):
+        """rtu_temporal_accumulate_sparse_device: temporal_accumulate_sparse() on device memory; d_hole_ptr: width * height bytes."""
+        self._check(hip.rtu_temporal_accumulate_sparse_device(self._h, ctypes.byref(desc), ctypes.byref(sparse),
+                                                              ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam), d_rgbt_ptr,
+                                                              d_owner_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr, d_rgbz_out_ptr,
+                                                              d_hole_ptr, d_motion_ptr, n_nodes, int(history_cap), stream))
+
+    def sparse_fill_device(self, desc, sparse, d_hits_ptr, d_albedo_ptr, d_owner_ptr, d_rgbt_ptr, d_hole_ptr, d_rgbz_ptr, stream=None):
+        """rtu_sparse_fill_device: sparse_fill() on device memory, in place in d_rgbz_ptr."""
+        self._check(hip.rtu_sparse_fill_device(self._h, ctypes.byref(desc), ctypes.byref(sparse), d_hits_ptr, d_albedo_ptr, d_owner_ptr, d_rgbt_ptr,
+                                               d_hole_ptr, d_rgbz_ptr, stream))
 
     def gradient_rays_device(self, desc, frame, sample, d_rays_ptr, d_keys_ptr, d_owner_ptr, stream=None):
         """rtu_gradient_rays_device: gradient_rays() written to device memory by a kernel, one ray, key and owner per stratum."""

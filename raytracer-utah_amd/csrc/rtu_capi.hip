@@ -14,6 +14,7 @@
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
 #include "rtu_gradient.h"
+#include "rtu_sparse.h"
 #include "rtu_steer.h"
 #include "rtu_temporal.h"
 #include "rtu_variance.h"
@@ -1837,6 +1838,14 @@ struct RtuTemporal {
     DevBuf<float>    lum[2], gr_lambda;
     DevBuf<uint32_t> gr_owner;
     DevBuf<float4>   gr_diff;
+    bool             sparse_session = false;  // rtu_temporal_begin_sparse
+    bool             sparse = false;      // ... with block > 1: a frame shades one ray per block (the first `blocks` entries of rays, keys and img) ...
+    RtuSparseDesc    spdesc{};            // ... and goes through the sparse accumulator and the fill
+    size_t           blocks = 0;
+    DevBuf<uint32_t> sp_owner;
+    DevBuf<uint8_t>  sp_hole;
+    PinnedBuf<uint8_t> sp_hole_host;      // rtu_temporal_holes counts here
+    hipEvent_t       sp_done = nullptr;   // ... recorded behind the last frame's fill: the copy waits for it on the context's stream
 };
 
 static void temporal_release(RtuTemporal* t) {
@@ -1862,6 +1871,11 @@ static void temporal_release(RtuTemporal* t) {
     t->gr_lambda.reset();
     t->gr_owner.reset();
     t->gr_diff.reset();
+    t->sp_owner.reset();
+    t->sp_hole.reset();
+    t->sp_hole_host.reset();
+    if (t->sp_done) (void)hipEventDestroy(t->sp_done);
+    t->sp_done = nullptr;
     t->has_lambda = false;
     t->has_hist = false;
     t->ctx = nullptr;
@@ -4548,6 +4562,157 @@ int rtu_temporal_lambda_device(RtuTemporal* t, void* d_lambda, void* hip_stream)
     return RTU_OK;
 }
 
+// ---- sparse sessions (rtu_sparse.h, rtu_sparse.hip): the owners' rays, the sparse accumulator and the fill ----
+static_assert(sizeof(RtuSparseDesc) == 32, "RtuSparseDesc is 32 bytes");
+
+static const char* const kSparseDescRules = "sparse: width, height 1 .. 65536 (2^26 pixels), block 1 .. 4, reserved words 0";
+
+// What sp_ray takes of `frame` for frame d.frame_index: the camera and, per class of blocks, the sample (k div m) mod S with its pixel
+// offsets by launch()'s expressions (cam_sample). false: the frame is refused.
+static bool sparse_rays_setup(const RtuSparseDesc& d, const RtuFrameDesc* frame, SpRays* r) {
+    if (!frame || frame->width != d.width || frame->height != d.height || frame->samples < 1) return false;
+    memset(r, 0, sizeof *r);
+    r->c = cam_sample(frame, 0);
+    uint32_t m[4];
+    sp_class_sizes(d.width, d.height, d.block, m);
+    for (int c = 0; c < 4; c++) {
+        const CamSample cs = cam_sample(frame, (int)((d.frame_index / m[c]) % (uint32_t)frame->samples));
+        r->ox[c] = cs.ox;
+        r->oy[c] = cs.oy;
+        r->sample[c] = cs.sample;
+    }
+    r->block = d.block;
+    r->sw = sp_blocks(d.width, d.block);
+    r->blocks = (uint32_t)r->sw * (uint32_t)sp_blocks(d.height, d.block);
+    r->frame_index = d.frame_index;
+    return true;
+}
+
+int rtu_sparse_rays(const RtuSparseDesc* desc, const RtuFrameDesc* frame, RtuRay* rays_out, uint32_t* keys_out, uint32_t* owner_out) {
+    SpRays R;
+    if (rtu_sparse_check_desc(desc) != RTU_OK || !sparse_rays_setup(*desc, frame, &R) || !rays_out || !keys_out || !owner_out) return RTU_ERR_ARG;
+    for (uint32_t b = 0; b < R.blocks; b++) {
+        f3 org, dir;
+        uint32_t key, own;
+        sp_ray(R, b, HostSinCos(), org, dir, key, own);
+        RtuRay& r = rays_out[b];
+        r.org[0] = org.x; r.org[1] = org.y; r.org[2] = org.z;
+        r.tmax = RTU_BIGFLOAT;
+        r.dir[0] = dir.x; r.dir[1] = dir.y; r.dir[2] = dir.z;
+        r.reserved = 0;
+        keys_out[b] = key;
+        owner_out[b] = own;
+    }
+    return RTU_OK;
+}
+
+int rtu_sparse_rays_device(RtuContext* ctx, const RtuSparseDesc* desc, const RtuFrameDesc* frame, void* d_rays, void* d_keys, void* d_owner, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_sparse_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kSparseDescRules);
+    SpRays R;
+    if (!sparse_rays_setup(*desc, frame, &R)) return fail(ctx, RTU_ERR_ARG, "sparse: the frame must have the desc's size and samples >= 1");
+    if (!d_rays || !d_keys || !d_owner) return fail(ctx, RTU_ERR_ARG, "sparse: a device pointer is NULL");
+    if (misaligned(d_rays) || misaligned4(d_keys) || misaligned4(d_owner))
+        return fail(ctx, RTU_ERR_ARG, "sparse: the ray buffer must be 16-byte, the other buffers 4-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_sparse_rays(R, (float4*)d_rays, (uint32_t*)d_keys, (uint32_t*)d_owner, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "sparse ray launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate_sparse_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const RtuFrameDesc* prev_cam,
+                                          const RtuFrameDesc* cur_cam, const void* d_rgbt, const void* d_owner, const void* d_hits, const void* d_albedo,
+                                          const void* d_hist_prev, void* d_hist_out, void* d_rgbz_out, void* d_hole_out, const RtuNodeMotion* d_motion,
+                                          uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
+    // (d_rgbt stands where the other forms have their image of samples: NULL and misaligned are refused alike)
+    const int rc = temporal_device_args(ctx, 4, true, desc, prev_cam, cur_cam, d_rgbt, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, d_motion, n_nodes,
+                                        history_cap);
+    if (rc != RTU_OK) return rc;
+    if (rtu_sparse_check_desc(sparse_desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kSparseDescRules);
+    if (sparse_desc->width != desc->width || sparse_desc->height != desc->height) return fail(ctx, RTU_ERR_ARG, "sparse: the two descs must have one size");
+    if (!d_owner || !d_hole_out) return fail(ctx, RTU_ERR_ARG, "sparse: a device pointer is NULL");
+    if (misaligned4(d_owner)) return fail(ctx, RTU_ERR_ARG, "sparse: the owners must be 4-byte aligned");
+    const TpSparseParams s{tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap), (const float4*)d_rgbt,
+                           (const uint32_t*)d_owner, (uint8_t*)d_hole_out, sparse_desc->block, sp_blocks(desc->width, sparse_desc->block)};
+    const hipError_t e = (hipError_t)rtu_launch_temporal_sparse(s, (const float4*)d_hits, (const float4*)d_albedo, (const float4*)d_hist_prev, (float4*)d_hist_out,
+                                                                (float4*)d_rgbz_out, d_motion, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_sparse_fill_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const void* d_hits, const void* d_albedo,
+                           const void* d_owner, const void* d_rgbt, const void* d_hole, void* d_rgbz, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
+    if (rtu_sparse_check_desc(sparse_desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kSparseDescRules);
+    if (sparse_desc->width != desc->width || sparse_desc->height != desc->height) return fail(ctx, RTU_ERR_ARG, "sparse: the two descs must have one size");
+    if (!d_hits || !d_albedo || !d_owner || !d_rgbt || !d_hole || !d_rgbz) return fail(ctx, RTU_ERR_ARG, "sparse: a device pointer is NULL");
+    if (misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_rgbt) || misaligned(d_rgbz) || misaligned4(d_owner))
+        return fail(ctx, RTU_ERR_ARG, "sparse: device buffers must be 16-byte aligned (owners: 4-byte)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const int B = sparse_desc->block;
+    const SpFill F{desc->width, desc->height, B, sp_blocks(desc->width, B), sp_blocks(desc->height, B), desc->sigma_plane, desc->normal_min};
+    const hipError_t e = (hipError_t)rtu_launch_sparse_fill(F, (const float4*)d_hits, (const float4*)d_albedo, (const uint32_t*)d_owner, (const float4*)d_rgbt,
+                                                            (const uint8_t*)d_hole, (float4*)d_rgbz, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "sparse fill launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+RtuTemporal* rtu_temporal_begin_sparse(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuVarianceDesc* vdesc, const RtuSparseDesc* spdesc, int* err_out) {
+    auto refuse = [&](int rc) -> RtuTemporal* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (!spdesc || !desc || !vdesc) return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a descriptor is NULL"));
+    RtuSparseDesc sd = *spdesc;  // (its frame_index is the frame's)
+    sd.frame_index = 0;
+    if (sd.width == 0 && sd.height == 0) {
+        sd.width = desc->width;
+        sd.height = desc->height;
+    }
+    if (rtu_temporal_check_desc(desc) == RTU_OK) {
+        if (rtu_sparse_check_desc(&sd) != RTU_OK) return refuse(fail(ctx, RTU_ERR_ARG, "%s", kSparseDescRules));
+        if (sd.width != desc->width || sd.height != desc->height) return refuse(fail(ctx, RTU_ERR_ARG, "sparse: the desc has not the session's size"));
+    }
+    RtuTemporal* t = rtu_temporal_begin_variance(ctx, desc, vdesc, err_out);
+    if (!t) return nullptr;
+    t->sparse_session = true;
+    if (sd.block == 1) return t;
+    t->sparse = true;
+    t->spdesc = sd;
+    t->blocks = (size_t)sp_blocks(sd.width, sd.block) * (size_t)sp_blocks(sd.height, sd.block);
+    hipError_t e = t->sp_owner.grow(t->blocks);
+    if (e == hipSuccess) e = t->sp_hole.grow(t->pixels);
+    if (e == hipSuccess) e = t->sp_hole_host.grow(t->pixels);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->sp_done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        const int rc = fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e));
+        rtu_temporal_free(t);
+        return refuse(rc);
+    }
+    return t;
+}
+
+int rtu_temporal_holes(RtuTemporal* t, uint32_t* count_out) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!t->sparse_session) return fail(ctx, RTU_ERR_ARG, "not a sparse session");
+    if (!count_out) return fail(ctx, RTU_ERR_ARG, "count_out is NULL");
+    *count_out = 0;
+    if (!t->sparse || !t->has_hist) return RTU_OK;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    // on the context's own stream, behind the event of the last frame: the caller's stream of that frame may be gone by now
+    RTU_HIP(ctx, hipStreamWaitEvent(ctx->stream, t->sp_done, 0));
+    RTU_HIP(ctx, hipMemcpyAsync(t->sp_hole_host.get(), t->sp_hole.get(), t->pixels, hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t count = 0;
+    const uint8_t* h = t->sp_hole_host.get();
+    for (size_t i = 0; i < t->pixels; i++) count += h[i];
+    *count_out = count;
+    return RTU_OK;
+}
+
 // what a moved frame has beyond a plain one (rtu_temporal_frame_moved_device)
 struct TemporalMoved {
     const RtuNodeMotion* h_motion;
@@ -4605,13 +4770,19 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
             t->k = 0;
         }
     }
-    int rc = rtu_camera_sample_rays_device(ctx, frame, t->k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
+    int rc;
+    if (t->sparse) {  // one ray per block: the block's owner of frame k in the sample the block has reached
+        t->spdesc.frame_index = (uint32_t)t->k;
+        rc = rtu_sparse_rays_device(ctx, &t->spdesc, frame, t->rays.get(), t->keys.get(), t->sp_owner.get(), hip_stream);
+    } else {
+        rc = rtu_camera_sample_rays_device(ctx, frame, t->k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
+    }
     if (rc != RTU_OK) return rc;
     // A gradient session: the gradient rays behind the frame's own, shaded with them in the one launch sequence. A frame without a
     // previous one shades them too and uses none of their results — the batch of every frame has one size, so the context's frame
     // records grow in the first frame and no later frame allocates.
     const bool grad = t->gradient && t->has_hist;
-    const size_t shaded = t->gradient ? n + t->strata : n;
+    const size_t shaded = t->sparse ? t->blocks : (t->gradient ? n + t->strata : n);
     if (t->gradient) {
         t->gdesc.frame_index = (uint32_t)t->k;
         if ((rc = rtu_gradient_rays_device(ctx, &t->gdesc, frame, (t->k + frame->samples - 1) % frame->samples, t->rays.get() + 2 * n, t->keys.get() + n,
@@ -4645,7 +4816,16 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         }
         if (n_nodes > 0)
             RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
-        if (grad) {
+        if (t->sparse) {
+            rc = rtu_temporal_accumulate_sparse_device(ctx, &td, &t->spdesc, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->sp_owner.get(),
+                                                       t->hits.get(), t->albedo.get(), t->has_hist ? t->hist[t->cur].get() : nullptr,
+                                                       t->hist[t->cur ^ 1].get(), d_rgbz, t->sp_hole.get(), t->motion.get(), n_nodes,
+                                                       moved ? moved->history_cap : 0, hip_stream);
+            if (rc == RTU_OK)
+                rc = rtu_sparse_fill_device(ctx, &td, &t->spdesc, t->hits.get(), t->albedo.get(), t->sp_owner.get(), t->img.get(), t->sp_hole.get(), d_rgbz,
+                                            hip_stream);
+            if (rc == RTU_OK) RTU_HIP(ctx, hipEventRecord(t->sp_done, stream));  // rtu_temporal_holes reads the hole plane behind it
+        } else if (grad) {
             rc = rtu_temporal_gradient_device(ctx, &td, &t->gdesc, &t->prev_cam, frame, t->hits.get(), t->albedo.get(), t->motion.get(), n_nodes,
                                               t->hist[t->cur].get(), t->lum[t->lcur].get(), t->gr_owner.get(), t->img.get() + n, t->gr_diff.get(),
                                               t->gr_lambda.get(), hip_stream);

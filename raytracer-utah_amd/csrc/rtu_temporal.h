@@ -2,7 +2,7 @@
 // updates" and the moments of "Variance-guided filtering"), host + device, and the launch interface of its kernels (rtu_temporal.hip),
 // called by rtu_capi.hip. The three forms — rtu_temporal_accumulate, _motion and _moments, each with its _device form — are the
 // instantiations of one function, tp_pixel<MOVING, MOMENTS>; rtu_temporal_accumulate_gradient ("Temporal gradients") is a fourth,
-// tp_pixel<true, true, true>.
+// tp_pixel<true, true, true>, and rtu_temporal_accumulate_sparse ("Sparse sessions") a fifth, tp_pixel<true, true, false, true>.
 //
 // A pixel's first-hit point is projected into the previous camera, the history is fetched there with four bilinear taps, each tested
 // for being the same surface, and the new sample is blended in. No transcendental function: the translation units that include this
@@ -99,6 +99,17 @@ struct TpGradientParams {
     int32_t        sw;
 };
 
+// What the sparse form needs beyond TpMotionParams: the shaded sample and the owner of every block (sw = ceil(width / block) blocks
+// per row) in place of an image of samples, and the plane its holes are marked in (host memory in the host form, device memory in the
+// kernel).
+struct TpSparseParams {
+    TpMotionParams  M;
+    const float4*   rgbt;
+    const uint32_t* owner;
+    uint8_t*        hole;
+    int32_t         block, sw;
+};
+
 // the words of an RtuNodeMotion that are read, in registers: the caller loads them (the kernel with 16-byte loads, the host form from
 // a table of any alignment)
 struct TpMotion {
@@ -170,14 +181,19 @@ RTU_HD float vr_lum(const f3& e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.07
 // ---- the accumulator: one function for the three forms ---------------------------------------------------------------------------
 // MOVING: the hit point is carried through its node's table entry before the lookup, and the history taken over is capped
 // (TpMotionParams); else the scene is at rest (TpParams). MOMENTS: the history has the fourth plane M. GRADIENT (with both): the
-// history taken over is capped once more, by the lambda of the pixel's stratum (TpGradientParams).
-template <bool MOVING, bool GRADIENT = false>
-using TpArgs = typename std::conditional<GRADIENT, TpGradientParams, typename std::conditional<MOVING, TpMotionParams, TpParams>::type>::type;
+// history taken over is capped once more, by the lambda of the pixel's stratum (TpGradientParams). SPARSE (with MOVING and MOMENTS):
+// only the pixel its block owns has a sample (TpSparseParams); every other pixel keeps its history.
+template <bool MOVING, bool GRADIENT = false, bool SPARSE = false>
+using TpArgs = typename std::conditional<
+    SPARSE, TpSparseParams,
+    typename std::conditional<GRADIENT, TpGradientParams, typename std::conditional<MOVING, TpMotionParams, TpParams>::type>::type>::type;
 RTU_HD const TpParams& tp_base(const TpParams& p) { return p; }
 RTU_HD const TpParams& tp_base(const TpMotionParams& m) { return m.P; }
 RTU_HD const TpParams& tp_base(const TpGradientParams& g) { return g.M.P; }
+RTU_HD const TpParams& tp_base(const TpSparseParams& s) { return s.M.P; }
 RTU_HD const TpMotionParams& tp_motion(const TpMotionParams& m) { return m; }
 RTU_HD const TpMotionParams& tp_motion(const TpGradientParams& g) { return g.M; }
+RTU_HD const TpMotionParams& tp_motion(const TpSparseParams& s) { return s.M; }
 
 // the weighted sums over the accepted taps of a lookup: E.rgb, E.n, the weights, and with MOMENTS M.xy
 struct TpSums {
@@ -211,11 +227,14 @@ RTU_HD void tp_tap(const TpParams& P, const float4* const* h, int qx, int qy, fl
 // Pixel (x, y): h the three (MOMENTS: four) planes of the previous history (not read with TP_LOOKUP_NONE), hit the three float4 of its
 // RtuRayHit; MOVING: in_table / T as for tp_moved_point (else neither is read). out: its pixel of the accumulated image; o: its pixel
 // of the planes of the new history, all written after every read. A.lookup is wave-uniform without MOVING; with it, whether a pixel
-// takes no, one or four taps is its own matter.
-template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
-RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
-                     const float4* hit, const float4& albedo, float4& out, float4* o) {
+// takes no, one or four taps is its own matter. SPARSE: `owner` — the pixel is the one its block shades this frame and rgbz is that
+// sample; for every other pixel nothing of rgbz reaches an output — and *hole, the pixel's mark in the hole plane (without SPARSE
+// neither is used).
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false>
+RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT, SPARSE>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
+                     const float4* hit, const float4& albedo, float4& out, float4* o, bool owner = true, uint8_t* hole = nullptr) {
     static_assert(!GRADIENT || (MOVING && MOMENTS), "the gradient form is a moments form");
+    static_assert(!SPARSE || (MOVING && MOMENTS && !GRADIENT), "the sparse form is a moments form");
     const TpParams& P = tp_base(A);
     union { float f; uint32_t u; } flags, node;
     flags.f = hit[0].z;
@@ -272,7 +291,8 @@ RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT>& A, bool in_table, const TpM
         }
     }
 
-    const bool finite = tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);  // else the sample is not accumulated
+    // else the sample is not accumulated; a pixel that is not its block's owner has none
+    const bool finite = (!SPARSE || owner) && tp_finite(rgbz.x) && tp_finite(rgbz.y) && tp_finite(rgbz.z);
     const bool fresh = n_prev == 0.0f;
     const float n_blend = smin(n_prev + 1.0f, P.max_history);
     const float a = 1.0f / n_blend;
@@ -290,6 +310,13 @@ RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT>& A, bool in_table, const TpM
     }
     if (!valid) node.u = 0xFFFFFFFFu;  // node -1
     out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, rgbz.w) : rgbz;
+    if constexpr (SPARSE) {  // no sample of its own: the depth is the guides', and without an accumulated colour the pixel is a hole
+        if (!owner) {
+            const float z = valid ? hit[0].x : RTU_BIGFLOAT;
+            out = keep ? make_float4(e.x * d.x, e.y * d.y, e.z * d.z, z) : make_float4(0.0f, 0.0f, 0.0f, z);
+        }
+        *hole = (!owner && !keep) ? 1 : 0;
+    }
     o[0] = keep ? make_float4(e.x, e.y, e.z, n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     o[1] = valid ? make_float4(Pp.x, Pp.y, Pp.z, hit[0].x) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     o[2] = valid ? make_float4(Np.x, Np.y, Np.z, node.f) : make_float4(0.0f, 0.0f, 0.0f, node.f);
@@ -306,6 +333,8 @@ RTU_HD float4 tp_motion_vector(const TpParams& P, bool in_table, const TpMotion&
 
 // RTU_OK or RTU_ERR_ARG: the rules of RtuTemporalDesc (include/rtu_render.h)
 int rtu_temporal_check_desc(const RtuTemporalDesc* d);
+// RTU_OK or RTU_ERR_ARG: the rules of RtuSparseDesc (rtu_sparse.hip)
+int rtu_sparse_check_desc(const RtuSparseDesc* d);
 // RTU_OK or RTU_ERR_ARG: history_cap 0 .. 65535; with a host table, its reserved words 0 and its flags known
 int rtu_temporal_check_motion(const RtuNodeMotion* h_motion_or_null, uint32_t n_nodes, int32_t history_cap);
 // mv[i] = the motion vector of pixel i
@@ -325,6 +354,9 @@ int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, con
 // The gradient form: the moments form with g.lambda, device memory (nullptr: the moments form's bits).
 int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
+// The sparse form: the moments form whose samples are s.rgbt / s.owner, one per block; s.hole [width * height] is written.
+int rtu_launch_temporal_sparse(const TpSparseParams& s, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+                               float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 // n_out[i] = the history length of pixel i (E.w of `hist`), or 0 everywhere with hist == nullptr
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream);
 

@@ -2,7 +2,8 @@
 // moments of "Variance-guided filtering"): its host forms rtu_temporal_accumulate, _motion and _moments, which are the executable
 // statement of the rules, and the kernels of their _device forms. Both call tp_pixel<MOVING, MOMENTS> of rtu_temporal.h, pixel by
 // pixel; the three forms are the instantiations <false, false>, <true, false> and <true, true> of one kernel and of one host loop,
-// and rtu_temporal_accumulate_gradient ("Temporal gradients") is <true, true, true>.
+// rtu_temporal_accumulate_gradient ("Temporal gradients") is <true, true, true> and rtu_temporal_accumulate_sparse ("Sparse
+// sessions") is <true, true, false, true>.
 //
 //   k_temporal          one lane per pixel, 32 x 8 pixel workgroups as k_dn_pass (a wavefront is two rows of 32). A lane reads its
 //                       pixel's {rgbz, RtuRayHit, albedo} (80 B), up to four taps of the previous history — three 16-byte loads each,
@@ -16,6 +17,9 @@
 //                       single exit, select on values.
 //     MOMENTS           a four-plane history: besides, one 16-byte load of M per ACCEPTED tap and one 16-byte store.
 //     GRADIENT          besides, one dword load of the lambda of the pixel's stratum: the three lanes of a stratum's row share it.
+//     SPARSE            in place of the 16-byte load of rgbz one dword load of the owner of the pixel's block — the lanes of a block's
+//                       row share it — and, in the one lane of a block that is the owner, the 16-byte load of the block's sample;
+//                       besides, one byte store of the pixel's mark in the hole plane.
 //   k_temporal_history  one lane per pixel: the history length out of the E plane.
 //   k_motion_vectors    one lane per pixel: its RtuRayHit and its node's entry in, one float4 out.
 // Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
@@ -28,8 +32,8 @@
 namespace {
 
 // `motion` is read with MOVING only; hist_prev and hist_out have three planes, with MOMENTS four
-template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
-__global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING, GRADIENT> A, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false>
+__global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING, GRADIENT, SPARSE> A, const float4* rgbz, const float4* __restrict__ hits, const float4* __restrict__ albedo,
                                                   const float4* __restrict__ hist_prev, float4* __restrict__ hist_out, float4* rgbz_out,
                                                   const RtuNodeMotion* __restrict__ motion) {
     constexpr int PLANES = MOMENTS ? 4 : 3;
@@ -45,16 +49,25 @@ __global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING, GRADIENT> A, co
     const float4* h[PLANES];
     for (int i = 0; i < PLANES; i++) h[i] = hist_prev ? hist_prev + i * n : nullptr;
     float4 out, o[PLANES];
-    tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o);
+    if constexpr (SPARSE) {  // (rgbz is not read) the sample of the pixel's block where the pixel owns it
+        const size_t b = (size_t)((uint32_t)y / (uint32_t)A.block) * (size_t)A.sw + (size_t)((uint32_t)x / (uint32_t)A.block);
+        const bool own = (size_t)A.owner[b] == p;
+        const float4 in = own ? A.rgbt[b] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        uint8_t hole;
+        tp_pixel<MOVING, MOMENTS, GRADIENT, SPARSE>(A, k >= 0, T, h, x, y, in, hit, albedo[p], out, o, own, &hole);
+        A.hole[p] = hole;
+    } else {
+        tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o);
+    }
     rgbz_out[p] = out;
     for (int i = 0; i < PLANES; i++) hist_out[i * n + p] = o[i];
 }
 
-template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
-int launch_temporal(const TpArgs<MOVING, GRADIENT>& a, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false>
+int launch_temporal(const TpArgs<MOVING, GRADIENT, SPARSE>& a, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
                     float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
     const dim3 grid((uint32_t)((tp_base(a).width + 31) / 32), (uint32_t)((tp_base(a).height + 7) / 8));
-    hipLaunchKernelGGL((k_temporal<MOVING, MOMENTS, GRADIENT>), grid, dim3(256), 0, stream, a, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
+    hipLaunchKernelGGL((k_temporal<MOVING, MOMENTS, GRADIENT, SPARSE>), grid, dim3(256), 0, stream, a, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion);
     return (int)hipGetLastError();
 }
 
@@ -94,6 +107,11 @@ int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, con
 int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
     return launch_temporal<true, true, true>(g, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
+}
+
+int rtu_launch_temporal_sparse(const TpSparseParams& s, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
+                               float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
+    return launch_temporal<true, true, false, true>(s, nullptr, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
 }
 
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream) {
@@ -136,14 +154,25 @@ int rtu_temporal_check_desc(const RtuTemporalDesc* d) {
     return RTU_OK;
 }
 
+// what the sparse host form has in place of h_rgbz: one sample and one owner per block, and the hole plane it writes
+struct SparseHost {
+    const RtuSparseDesc* desc;
+    const float*         rgbt;
+    const uint32_t*      owner;
+    uint8_t*             hole;
+};
+
 // the host forms: motion, n_nodes and history_cap are read with MOVING only; the histories have three planes, with MOMENTS four;
-// lambda (one float per stratum, or nullptr) is read with GRADIENT only
-template <bool MOVING, bool MOMENTS, bool GRADIENT = false>
+// lambda (one float per stratum, or nullptr) is read with GRADIENT only; sp with SPARSE only, and then h_rgbz is not read
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false>
 static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz, const RtuRayHit* h_hits,
                            const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion,
-                           uint32_t n_nodes, int32_t history_cap, const float* lambda = nullptr) {
+                           uint32_t n_nodes, int32_t history_cap, const float* lambda = nullptr, const SparseHost* sp = nullptr) {
     constexpr int PLANES = MOMENTS ? 4 : 3;
-    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || (!SPARSE && !h_rgbz) || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
+    if constexpr (SPARSE)
+        if (rtu_sparse_check_desc(sp->desc) != RTU_OK || sp->desc->width != desc->width || sp->desc->height != desc->height || !sp->rgbt || !sp->owner || !sp->hole)
+            return RTU_ERR_ARG;
     if (MOVING && (!motion || rtu_temporal_check_motion(motion, n_nodes, history_cap) != RTU_OK)) return RTU_ERR_ARG;
     if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
     if (!prev_cam) prev_cam = cur_cam;
@@ -155,8 +184,10 @@ static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev
         const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 16 * PLANES * n;
         if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
     }
-    TpArgs<MOVING, GRADIENT> A;
-    if constexpr (GRADIENT) A = TpGradientParams{tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap), lambda,
+    TpArgs<MOVING, GRADIENT, SPARSE> A;
+    if constexpr (SPARSE) A = TpSparseParams{tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap), nullptr, nullptr, nullptr,
+                                             sp->desc->block, (W + sp->desc->block - 1) / sp->desc->block};
+    else if constexpr (GRADIENT) A = TpGradientParams{tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap), lambda,
                                                  (W + TP_STRATUM - 1) / TP_STRATUM};
     else if constexpr (MOVING) A = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
     else A = tp_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr);
@@ -174,7 +205,14 @@ static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev
             const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
             const int32_t k = MOVING ? tp_motion_index(hit[0], n_nodes) : -1;
             float4 out, o[PLANES];
-            tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, host_motion(motion, k), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o);
+            if constexpr (SPARSE) {
+                const size_t b = (size_t)(y / A.block) * (size_t)A.sw + (size_t)(x / A.block);
+                const bool own = (size_t)sp->owner[b] == p;
+                const float4 in = own ? f4(sp->rgbt, b) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                tp_pixel<MOVING, MOMENTS, GRADIENT, SPARSE>(A, k >= 0, host_motion(motion, k), hp, x, y, in, hit, f4(h_albedo, p), out, o, own, sp->hole + p);
+            } else {
+                tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, host_motion(motion, k), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o);
+            }
             st4(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
             for (int i = 0; i < PLANES; i++) st4(h_hist_out, i * n + p, o[i]);
         }
@@ -214,6 +252,15 @@ int rtu_temporal_accumulate_gradient(const RtuTemporalDesc* desc, const RtuFrame
                                      const RtuNodeMotion* motion, uint32_t n_nodes, int32_t history_cap, const float* h_lambda) {
     return accumulate_host<true, true, true>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes,
                                              history_cap, h_lambda);
+}
+
+int rtu_temporal_accumulate_sparse(const RtuTemporalDesc* desc, const RtuSparseDesc* sparse_desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                   const float* h_rgbt, const uint32_t* owner, const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev,
+                                   float* h_hist_out, float* h_rgbz_out, uint8_t* h_hole_out, const RtuNodeMotion* motion, uint32_t n_nodes,
+                                   int32_t history_cap) {
+    const SparseHost sp{sparse_desc, h_rgbt, owner, h_hole_out};
+    return accumulate_host<true, true, false, true>(desc, prev_cam, cur_cam, nullptr, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes,
+                                                    history_cap, nullptr, &sp);
 }
 
 int rtu_motion_vectors(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuNodeMotion* motion, uint32_t n_nodes,
