@@ -734,8 +734,18 @@ int  rtu_temporal_accumulate_device(RtuContext* ctx, const RtuTemporalDesc* desc
  * belong to the session and are allocated by rtu_temporal_begin (which needs no scene); a frame allocates nothing once the context's
  * frame records have grown to what the scene needs. ONE STREAM PER CONTEXT as for every launch. A session does not go stale: once the
  * context got a new scene (rtu_upload_scene, rtu_update_scene, rtu_update_meshes) the next frame starts over with no history and k = 0.
- * RTU_ERR_ARG: a desc outside its rules, a frame of another size, sharded, with counters or of recipe W, a NULL or misaligned d_rgbz;
- * RTU_ERR_NO_SCENE before an upload. rtu_temporal_frame is the host form, synchronous on the context's stream.
+ * WHAT MAY DIFFER FROM CALL TO CALL, in every kind of session below as well: the camera, and samples, gather_bounces and max_bounce.
+ * Every rule that names S takes the S of the frame given in THAT call — sample k mod S here, a steered session's extra samples
+ * S + (k mod S) * E + j, a gradient session's (k - 1) mod S, a sparse session's (k div m) mod S — and k goes on counting; the history
+ * is kept, it does not know what recipe filled it. After such a change a gradient session's re-shaded sample is no longer the previous
+ * frame's sample (another S: another ray; another gather_bounces or max_bounce: another estimate along the same ray), so the frame
+ * that follows the change may show lambda > 0 with the camera and the scene at rest; the frame after it is exact again.
+ * A REFUSED CALL LEAVES THE SESSION AS IT WAS: the frame counter, the history, the scene generation the session has seen and everything
+ * a session shows of itself are those of the last frame that returned RTU_OK, also when a scene update is pending.
+ * RTU_ERR_ARG: a desc outside its rules, a frame of another size, sharded, with counters or of recipe W, with max_bounce or samples
+ * outside what rtu_render_frame takes, with a cam_pos that is not finite, of recipe P with more than 2^25 pixels, a NULL or misaligned
+ * d_rgbz; RTU_ERR_NO_SCENE before an upload. rtu_temporal_frame is the host
+ * form, synchronous on the context's stream.
  * rtu_temporal_history_device writes width * height floats: the history length n of every pixel after the last frame (0 before the
  * first). Ownership as for progressive sessions: rtu_destroy_context releases the device memory of open sessions, the handle stays
  * valid for rtu_temporal_free alone. */
@@ -959,7 +969,8 @@ RtuTemporal* rtu_temporal_begin_variance(RtuContext* ctx, const RtuTemporalDesc*
  * by the unchanged rtu_shade_rays_sampled_device / rtu_shade_rays_paths_device path of step 2 with n = the total, which is read back
  * (4 bytes; this part of a frame is synchronous already); the fold into the new history and d_rgbz; rtu_variance_device again on the
  * folded history; then the filter. steer_desc: width, height and frame_index are ignored. budget == 0 gives a variance session's
- * bits and launches nothing more. A frame needs S * (1 + max_extra) <= 65536. rtu_temporal_extra_counts_device writes width * height
+ * bits and launches nothing more. A frame needs S * (1 + max_extra) <= 65536 (with budget > 0; RTU_ERR_ARG otherwise, whatever the
+ * allocation of that frame would have been). rtu_temporal_extra_counts_device writes width * height
  * uint32: the counts of the last frame (zeros before the first, after a reset and with budget 0); rtu_temporal_steer_total returns
  * their sum. Counts, offsets, and min(budget, pixels * max_extra) rays, keys, owners and results (68 B each) belong to the session; a
  * frame allocates nothing after the first. Everything else as for a variance session. Measured error ratios and times are in

@@ -4741,6 +4741,13 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     if (frame->samples < 1) return fail(ctx, RTU_ERR_ARG, "a temporal frame is a recipe S / P frame (samples >= 1)");
     if (frame->gather_bounces != 0 && frame->gather_bounces != RTU_GI_BOUNCES) return fail(ctx, RTU_ERR_ARG, "gather_bounces is 0 or %d", RTU_GI_BOUNCES);
     if (frame->collect_stats != 0) return fail(ctx, RTU_ERR_ARG, "a temporal frame has no counters (collect_stats == 0)");
+    // A REFUSED CALL LEAVES THE SESSION AS IT WAS. Whatever an entry further down refuses — max_bounce, a camera that is not finite, too
+    // many chains of recipe P — it refuses before THE COMMIT below: until there the frame works on copies of the counter and of the
+    // history flag, and writes only buffers that hold nothing between two frames. What is refused behind the commit (a steered frame's
+    // samples * (1 + max_extra), in temporal_steer) is therefore refused here.
+    if (const int rc = check_frame(ctx, frame)) return rc;
+    if (t->steered && t->st_cap && (long long)frame->samples * (1 + t->sdesc.max_extra) > 65536)
+        return fail(ctx, RTU_ERR_ARG, "a steered frame needs samples * (1 + max_extra) <= 65536");
     if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
     if (misaligned(d_rgbz)) return fail(ctx, RTU_ERR_ARG, "d_rgbz must be 16-byte aligned");
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
@@ -4763,29 +4770,27 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         RTU_HIP(ctx, t->motion.grow(entries));
         RTU_HIP(ctx, t->motion_host.grow(entries));
     }
-    if (t->scene_gen != ctx->scene_gen) {
-        t->scene_gen = ctx->scene_gen;
-        if (!moved) {  // moved geometry or lights: what was accumulated shows another scene
-            t->has_hist = false;
-            t->k = 0;
-        }
-    }
+    // another scene generation: a moved frame adopts it; a plain frame starts over — moved geometry or lights: what was accumulated
+    // shows another scene. Both take effect at the commit.
+    const bool start_over = !moved && t->scene_gen != ctx->scene_gen;
+    const bool has_hist = t->has_hist && !start_over;
+    const int  k = start_over ? 0 : t->k;
     int rc;
     if (t->sparse) {  // one ray per block: the block's owner of frame k in the sample the block has reached
-        t->spdesc.frame_index = (uint32_t)t->k;
+        t->spdesc.frame_index = (uint32_t)k;
         rc = rtu_sparse_rays_device(ctx, &t->spdesc, frame, t->rays.get(), t->keys.get(), t->sp_owner.get(), hip_stream);
     } else {
-        rc = rtu_camera_sample_rays_device(ctx, frame, t->k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
+        rc = rtu_camera_sample_rays_device(ctx, frame, k % frame->samples, t->rays.get(), t->keys.get(), hip_stream);
     }
     if (rc != RTU_OK) return rc;
     // A gradient session: the gradient rays behind the frame's own, shaded with them in the one launch sequence. A frame without a
     // previous one shades them too and uses none of their results — the batch of every frame has one size, so the context's frame
     // records grow in the first frame and no later frame allocates.
-    const bool grad = t->gradient && t->has_hist;
+    const bool grad = t->gradient && has_hist;
     const size_t shaded = t->sparse ? t->blocks : (t->gradient ? n + t->strata : n);
     if (t->gradient) {
-        t->gdesc.frame_index = (uint32_t)t->k;
-        if ((rc = rtu_gradient_rays_device(ctx, &t->gdesc, frame, (t->k + frame->samples - 1) % frame->samples, t->rays.get() + 2 * n, t->keys.get() + n,
+        t->gdesc.frame_index = (uint32_t)k;
+        if ((rc = rtu_gradient_rays_device(ctx, &t->gdesc, frame, (k + frame->samples - 1) % frame->samples, t->rays.get() + 2 * n, t->keys.get() + n,
                                            t->gr_owner.get(), hip_stream)) != RTU_OK)
             return rc;
     }
@@ -4804,7 +4809,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     if (t->variance) {
         // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
         const uint32_t n_nodes = moved ? moved->n_nodes : n_static;
-        if (moved && t->has_hist) {
+        if (moved && has_hist) {
             memcpy(t->motion_host.get(), moved->h_motion, n_nodes * sizeof(RtuNodeMotion));
         } else {
             RtuNodeMotion id{};
@@ -4817,8 +4822,8 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         if (n_nodes > 0)
             RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
         if (t->sparse) {
-            rc = rtu_temporal_accumulate_sparse_device(ctx, &td, &t->spdesc, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->sp_owner.get(),
-                                                       t->hits.get(), t->albedo.get(), t->has_hist ? t->hist[t->cur].get() : nullptr,
+            rc = rtu_temporal_accumulate_sparse_device(ctx, &td, &t->spdesc, has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->sp_owner.get(),
+                                                       t->hits.get(), t->albedo.get(), has_hist ? t->hist[t->cur].get() : nullptr,
                                                        t->hist[t->cur ^ 1].get(), d_rgbz, t->sp_hole.get(), t->motion.get(), n_nodes,
                                                        moved ? moved->history_cap : 0, hip_stream);
             if (rc == RTU_OK)
@@ -4834,8 +4839,8 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
                                                              t->hist[t->cur].get(), t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), n_nodes,
                                                              moved ? moved->history_cap : 0, t->gr_lambda.get(), hip_stream);
         } else {
-            rc = rtu_temporal_accumulate_moments_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
-                                                        t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(),
+            rc = rtu_temporal_accumulate_moments_device(ctx, &td, has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                                        has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(),
                                                         n_nodes, moved ? moved->history_cap : 0, hip_stream);
         }
         if (rc == RTU_OK && t->gradient) {  // the luminance of this frame's sample: what the next frame's gradients are taken against
@@ -4843,24 +4848,26 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
             t->lcur ^= 1;
             t->has_lambda = grad;
         }
-    } else if (moved && t->has_hist) {
+    } else if (moved && has_hist) {
         // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
         memcpy(t->motion_host.get(), moved->h_motion, moved->n_nodes * sizeof(RtuNodeMotion));
         RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), moved->n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
         rc = rtu_temporal_accumulate_motion_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(), t->hist[t->cur].get(),
                                                    t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), moved->n_nodes, moved->history_cap, hip_stream);
     } else {  // (frame 0 of a moved session has nothing to look up: the plain form gives its bits)
-        rc = rtu_temporal_accumulate_device(ctx, &td, t->has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
-                                            t->has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
+        rc = rtu_temporal_accumulate_device(ctx, &td, has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
+                                            has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
     }
     if (rc != RTU_OK) return rc;
+    // THE COMMIT: nothing behind it refuses
+    t->scene_gen = ctx->scene_gen;
     t->cur ^= 1;
     t->has_hist = true;
     t->prev_cam = *frame;
-    t->k++;
+    t->k = k + 1;
     if (t->variance) {
         if ((rc = rtu_variance_device(ctx, &t->vdesc, t->hist[t->cur].get(), t->hits.get(), t->var.get(), hip_stream)) != RTU_OK) return rc;
-        if (t->steered && t->st_cap && (rc = temporal_steer(t, frame, (uint32_t)(t->k - 1), d_rgbz, hip_stream)) != RTU_OK) return rc;
+        if (t->steered && t->st_cap && (rc = temporal_steer(t, frame, (uint32_t)k, d_rgbz, hip_stream)) != RTU_OK) return rc;
         return rtu_denoise_variance_device(ctx, &t->vdesc, d_rgbz, t->hits.get(), t->albedo.get(), t->var.get(), d_rgbz, hip_stream);  // in place
     }
     if (t->desc.flags & RTU_TEMPORAL_DENOISE) {

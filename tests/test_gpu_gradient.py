@@ -222,11 +222,11 @@ def test_device_refusals(pkg, ctx):
 
 
 # ---- 2. sessions against the hand-assembled form ------------------------------------------------------------------------------------
-def hand_frame(pkg, ctx, frame, k, prev, state, desc, vdesc, sdesc, gdesc, motion, cap):
+def hand_frame(pkg, ctx, frame, k, prev, state, desc, vdesc, sdesc, gdesc, motion, cap, steer_out=None):
     """Frame k by hand. The rays of the frame and, with a previous frame, the gradient rays of rtu_gradient_rays_device behind them in
     ONE batch through the existing ray-batch shading; frame_features; rtu_temporal_gradient_device, rtu_temporal_accumulate_gradient_device
     and rtu_sample_luminance_device; then the variance session's (and the steered session's) steps by their host forms.
-    state: (history, luminance plane) of the frame before, or None."""
+    state: (history, luminance plane) of the frame before, or None. steer_out: a dict that takes the steered steps' counts and total."""
     import torch
     W, H = frame.width, frame.height
     n = W * H
@@ -267,6 +267,8 @@ def hand_frame(pkg, ctx, frame, k, prev, state, desc, vdesc, sdesc, gdesc, motio
     if sdesc is not None:
         sd = pkg.steer_desc(W, H, budget=sdesc.budget, max_extra=sdesc.max_extra, frame_index=k)
         counts, offsets, total = pkg.sample_allocation(hist, hits, v, sd)
+        if steer_out is not None:
+            steer_out.update(counts=counts, total=total)
         if total:
             xrays, xkeys, _ = pkg.extra_sample_rays(frame, counts, offsets, sd)
             xrgbt = shade(xrays, xkeys, tuple(frame.cam_pos), max_bounce=frame.max_bounce)[0]
