@@ -1195,6 +1195,84 @@ RtuTemporal* rtu_temporal_begin_sparse(RtuContext* ctx, const RtuTemporalDesc* t
                                        const RtuSparseDesc* sparse_desc, int* err_out);
 int  rtu_temporal_holes(RtuTemporal* t, uint32_t* count_out);
 
+/* ---- Hole rays: a sparse session shades the pixels that have no colour at all, within a budget (rtu_holes.h, rtu_holes.hip) ----
+ * A sparse session has nothing to show where there is neither a sample nor a history: all of frame 0 but the owners, most of the
+ * image after a camera cut, the disocclusions of every moving frame. rtu_sparse_fill guesses those pixels from neighbouring blocks and
+ * they stay guesses until their turn as owner comes, up to B * B - 1 frames later. The entries below spend real rays on them, at most
+ * `budget` per frame, and make the result the pixel's history. Binary32, one rounding per operation, no contraction, IEEE divisions,
+ * in this order; host and device forms give the same bits. VALID, d, l(e), mix32, E, M and the moments history are those of the
+ * sections above.
+ *
+ * 1. THE ALLOCATION  rtu_hole_allocation: out of the hole plane of rtu_temporal_accumulate_sparse (width * height bytes) and the
+ *   frame's RtuRayHit, uint32 counts[pixels], offsets[pixels] and the total. The weight is w_p = 1 iff hole[p] == 1 and p is VALID,
+ *   otherwise 0: an invalid pixel (a miss) is never accumulated by any form, it would eat the budget in every frame, so it stays with
+ *   the fill. Wsum, the dither h, the count c, the exclusive scan and THE CUT are rtu_sample_allocation's, word for word, with this w
+ *   and max_extra = 1. So with budget >= Wsum every VALID hole gets exactly one ray and total = Wsum; with less, a hole is taken with
+ *   probability budget / Wsum by the 16-bit dither of (p, frame_index), and the scan cuts at the budget: total <= budget always.
+ *
+ * 2. THE RAYS  No new rule: rtu_extra_sample_rays with an RtuSteerDesc of {the size, budget, max_extra = 1, frame_index = k}. With
+ *   S = frame->samples and F = `frame` with samples = 2 S: ray offsets_p and its key are those of pixel p in
+ *   rtu_camera_sample_rays(F, S + (k mod S)), bit for bit, and owner[offsets_p] = p. The sample indices are disjoint from the
+ *   0 .. S - 1 the owners walk through: a hole-shaded pixel never receives the same sample again when its turn as owner comes. A frame
+ *   needs 2 S <= 65536.
+ *
+ * 3. THE FOLD  rtu_hole_fold: the shaded {r, g, b, t} of the hole rays made the history of their pixels — in the moments history
+ *   rtu_temporal_accumulate_sparse just wrote, its rgbz and its hole plane, all in place. For a pixel with counts_p >= 1,
+ *   hole[p] == 1, VALID and offsets_p < n_rays, with c the rgb of rgbt[offsets_p]:
+ *     a channel of c is not finite: nothing changes; the pixel stays a hole and the fill takes it.
+ *     otherwise e = c / d, E = {e, 1};  l = l(e), l2 = l * l, M = {l, l2, 0, 0} if l2 is finite, else zeros (the skip rule of the
+ *     moments);  rgb = e * d;  hole[p] = 0. z and the planes P and N are untouched.
+ *   These are the bits rtu_temporal_accumulate_moments gives a VALID pixel that found no history and took the sample c. Every other
+ *   pixel, and every other word, passes bit for bit. Of desc only width and height are used (the others must still be valid).
+ *
+ * RTU_ERR_ARG: a NULL pointer; width or height outside 1 .. 65536 or more than 2^26 pixels; budget above 2^26; a non-zero reserved
+ * word; n_rays above 2^26; a device pointer that is not 16-byte aligned (counts, offsets, total: 4-byte; the hole plane: any). The
+ * host forms — pure host code, no GPU and no context — also refuse, in rtu_hole_fold, a count above 1 and a pixel whose
+ * offsets_p + counts_p exceeds n_rays. THE DEVICE FORMS TRUST counts AND offsets but never leave the arrays: any count >= 1 is one
+ * sample, a sample at or beyond n_rays is not read and its pixel not written. They are asynchronous on hip_stream and need no scene.
+ * rtu_hole_allocation_device (k_hole_weight: a lane per four pixels, the hit record read only where the hole byte is 1, a reduction
+ * per workgroup and one 64-bit atomic add each; then k_steer_counts, k_steer_sums, k_steer_finish of "Steered sampling", unchanged)
+ * works in the grow-only scratch of the context that rtu_sample_allocation_device uses: one stream per context, nothing allocated
+ * from the second call at a size. rtu_hole_fold_device (k_hole_fold, a lane per pixel that ends after one 4-byte load wherever
+ * counts_p == 0) allocates nothing and touches no state of the context.
+ *
+ * THE SESSION  rtu_temporal_begin_sparse_holes opens a sparse session. With block > 1 and budget > 0 its frames, plain and moved,
+ * continue after the sparse accumulator (step 3 of "Sparse sessions") with: (1) the allocation, frame_index = the session's k;
+ * (2) the total read back (4 bytes into pinned memory of the session, synchronous, as a steered session does); (3) if the total is
+ * above 0: the hole rays written into the session's ray, key and result buffers BEHIND their first SW * SH entries (the holes never
+ * exceed width * height - SW * SH: the batch always fits), shaded by the unchanged rtu_shade_rays_sampled_device /
+ * rtu_shade_rays_paths_device path with n = the total, the capacity retry as before, and folded; (4) rtu_sparse_fill_device on what
+ * is still a hole, rtu_variance_device and the filter, unchanged. hole_desc: width and height are both 0 or the session's;
+ * frame_index is ignored. budget == 0 or block == 1 gives the sparse session's bits and launches nothing more.
+ * rtu_temporal_holes counts the plane after the fold: what the fill had to fill. rtu_temporal_hole_rays returns the last frame's
+ * total (0 before the first frame, after a reset and with budget 0). Beside the sparse session's buffers, allocated at begin: counts,
+ * offsets and owners (4 B per pixel each), the total on the device and one pinned word. The context's frame records grow only when a
+ * hole batch exceeds every earlier batch of the session (typically in frame 0 and after the first cut) — not "nothing after the
+ * first frame". A refused call leaves the session as it was. Reset, free, the start-over after a scene change on a plain frame and
+ * the handle after rtu_destroy_context: as for a sparse session. RTU_ERR_ARG: what a sparse session refuses; a hole desc outside its
+ * rules or of another size; with budget > 0 and block > 1, a frame with 2 S > 65536. Not done here: hole rays for invalid pixels;
+ * combining with steering or gradients; a cheaper k_variance start-up (a hole-shaded pixel has n = 1 and takes the neighbourhood
+ * branch until min_history, the next step DESIGN.md section 28 names); avoiding the read-back. Measured error ratios and times are
+ * in DESIGN.md section 29. */
+typedef struct RtuHoleDesc {       /* 32 B */
+    int32_t  width, height;
+    uint32_t budget;               /* 0 .. 2^26: hole rays per frame, at most; 0 = none */
+    uint32_t frame_index;          /* the dither and the sample index; a session sets it */
+    uint32_t reserved[4];          /* must be 0 */
+} RtuHoleDesc;
+int  rtu_hole_defaults(RtuHoleDesc* out);   /* width, height 0; budget 0; frame_index 0 */
+int  rtu_hole_allocation(const RtuHoleDesc* desc, const uint8_t* h_hole, const RtuRayHit* h_hits, uint32_t* counts, uint32_t* offsets,
+                         uint32_t* total);
+int  rtu_hole_allocation_device(RtuContext* ctx, const RtuHoleDesc* desc, const void* d_hole, const void* d_hits, void* d_counts, void* d_offsets,
+                                void* d_total, void* hip_stream);
+int  rtu_hole_fold(const RtuHoleDesc* desc, float* h_hist, float* h_rgbz, uint8_t* h_hole, const RtuRayHit* h_hits, const float* h_albedo,
+                   const uint32_t* counts, const uint32_t* offsets, const float* h_rgbt, size_t n_rays);
+int  rtu_hole_fold_device(RtuContext* ctx, const RtuHoleDesc* desc, void* d_hist, void* d_rgbz, void* d_hole, const void* d_hits,
+                          const void* d_albedo, const void* d_counts, const void* d_offsets, const void* d_rgbt, size_t n_rays, void* hip_stream);
+RtuTemporal* rtu_temporal_begin_sparse_holes(RtuContext* ctx, const RtuTemporalDesc* temporal_desc, const RtuVarianceDesc* variance_desc,
+                                             const RtuSparseDesc* sparse_desc, const RtuHoleDesc* hole_desc, int* err_out);
+int  rtu_temporal_hole_rays(RtuTemporal* t, uint32_t* count_out);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

@@ -177,7 +177,9 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_temporal_accumulate_gradient_device", "rtu_temporal_begin_gradient", "rtu_temporal_lambda_device",
                "rtu_sparse_defaults", "rtu_sparse_rays", "rtu_sparse_rays_device", "rtu_temporal_accumulate_sparse",
                "rtu_temporal_accumulate_sparse_device", "rtu_sparse_fill", "rtu_sparse_fill_device", "rtu_temporal_begin_sparse",
-               "rtu_temporal_holes"]
+               "rtu_temporal_holes",
+               "rtu_hole_defaults", "rtu_hole_allocation", "rtu_hole_allocation_device", "rtu_hole_fold", "rtu_hole_fold_device",
+               "rtu_temporal_begin_sparse_holes", "rtu_temporal_hole_rays"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -1018,6 +1020,86 @@ def sparse_fill(rgbz, hole, hits, albedo, owner, rgbt, desc=None, sparse=None):
     return rgbz
 
 
+# hole rays (include/rtu_render.h, "Hole rays")
+class RtuHoleDesc(ctypes.Structure):
+    """include/rtu_render.h RtuHoleDesc (32 bytes): the size of the image, the budget of hole rays of a frame and the frame's index."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("budget", ctypes.c_uint32), ("frame_index", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+_HD = ctypes.POINTER(RtuHoleDesc)
+_sig(hip, "rtu_hole_defaults", _I, _HD)
+_sig(hip, "rtu_hole_allocation", _I, _HD, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_hole_allocation_device", _I, _P, _HD, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_hole_fold", _I, _HD, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t)
+_sig(hip, "rtu_hole_fold_device", _I, _P, _HD, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P)
+_sig(hip, "rtu_temporal_begin_sparse_holes", _P, _P, _TD, ctypes.POINTER(RtuVarianceDesc), _SD, _HD, ctypes.POINTER(_I))
+_sig(hip, "rtu_temporal_hole_rays", _I, _P, ctypes.POINTER(_U32))
+
+
+def hole_desc(width=0, height=0, **overrides):
+    """An RtuHoleDesc: rtu_hole_defaults (budget 0, frame_index 0), the size, then `overrides`."""
+    d = RtuHoleDesc()
+    hip.rtu_hole_defaults(ctypes.byref(d))
+    d.width, d.height = int(width), int(height)
+    for k, v in overrides.items():
+        setattr(d, k, v)
+    return d
+
+
+def _sized_hole_desc(desc, W, H):
+    d = RtuHoleDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc if desc is not None else hole_desc()), ctypes.sizeof(d))
+    d.width, d.height = W, H
+    return d
+
+
+def hole_allocation(hole, hits, desc):
+    """rtu_hole_allocation (pure host code): at most desc.budget rays, one each, for the pixels of hole uint8 [H, W] (the hole plane
+    of temporal_accumulate_sparse()) that are 1 and have a first hit in `hits` -> (counts uint32 [H, W], offsets uint32 [H, W],
+    total). The width and height of desc are taken from hole."""
+    import numpy as np
+    hole = np.ascontiguousarray(hole, np.uint8)
+    if hole.ndim != 2:
+        raise RtuError(RTU_ERR_ARG, "hole: a uint8 [H, W] array")
+    H, W = hole.shape
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != hit_dtype() or hits.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype()")
+    d = _sized_hole_desc(desc, W, H)
+    counts, offsets, total = np.empty((H, W), np.uint32), np.empty((H, W), np.uint32), _U32(0)
+    rc = hip.rtu_hole_allocation(ctypes.byref(d), hole.ctypes.data, hits.ctypes.data, counts.ctypes.data, offsets.ctypes.data, ctypes.byref(total))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_hole_allocation: an empty image or a descriptor outside its rules (budget 0..2^26, reserved words 0)")
+    return counts, offsets, int(total.value)
+
+
+def hole_fold(hist, rgbz, hole, hits, albedo, counts, offsets, rgbt, desc=None):
+    """rtu_hole_fold (pure host code): the shaded hole rays rgbt float32 [n, 4] made the history of their pixels in the moments
+    history float32 [4, H, W, 4], the image rgbz [H, W, 4] and the hole plane uint8 [H, W] -> (rgbz, hist, hole), new arrays (the C
+    entry works in place). desc: an RtuHoleDesc (None: the defaults), sized from hist."""
+    import numpy as np
+    hist = np.array(hist, np.float32, order="C")
+    rgbz = np.array(rgbz, np.float32, order="C")
+    hole = np.array(hole, np.uint8, order="C")
+    if hist.ndim != 4 or hist.shape[0] != 4 or hist.shape[3] != 4 or rgbz.shape != hist.shape[1:] or hole.shape != hist.shape[1:3]:
+        raise RtuError(RTU_ERR_ARG, "hist: a float32 [4, H, W, 4] array; rgbz: float32 [H, W, 4]; hole: uint8 [H, W]")
+    H, W = hist.shape[1:3]
+    hits = np.ascontiguousarray(hits)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    counts = np.ascontiguousarray(counts, np.uint32)
+    offsets = np.ascontiguousarray(offsets, np.uint32)
+    rgbt = np.ascontiguousarray(rgbt, np.float32).reshape(-1, 4)
+    if hits.dtype != hit_dtype() or hits.size != H * W or albedo.size != 4 * H * W or counts.size != H * W or offsets.size != H * W:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype(); albedo: float32 [H * W, 4]; counts, offsets: uint32 [H, W]")
+    d = _sized_hole_desc(desc, W, H)
+    rc = hip.rtu_hole_fold(ctypes.byref(d), hist.ctypes.data, rgbz.ctypes.data, hole.ctypes.data, hits.ctypes.data, albedo.ctypes.data,
+                           counts.ctypes.data, offsets.ctypes.data, rgbt.ctypes.data if len(rgbt) else None, len(rgbt))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_hole_fold: a descriptor outside its rules, a count above 1, or a pixel whose sample lies beyond rgbt")
+    return rgbz, hist, hole
+
+
 def sensor_desc(model, width, height, pos, right, up, forward, samples=0, gather_bounces=0, max_bounce=5, fov_deg=180.0, extent=(1, 1),
                 reference_walk=False):
     """An RtuSensorDesc: rtu_sensor_defaults, then the fields. model: RTU_SENSOR_* or "equirect" / "fisheye" / "ortho"; right, up and
@@ -1598,17 +1680,25 @@ class Temporal:
     gradient_desc(); with variance, steer or not) makes it a gradient session (rtu_temporal_begin_gradient): every frame re-shades one
     pixel per 3 x 3 stratum with the previous frame's random numbers and shortens the history where the shading changed. sparse: an
     RtuSparseDesc (see sparse_desc(); with variance, neither steer nor gradient) makes it a sparse session
-    (rtu_temporal_begin_sparse): every frame shades one pixel of every block, the history carries the others."""
+    (rtu_temporal_begin_sparse): every frame shades one pixel of every block, the history carries the others. holes: an RtuHoleDesc
+    (see hole_desc(); with sparse) makes that a sparse session with hole rays (rtu_temporal_begin_sparse_holes): every frame also
+    shades up to holes.budget of the pixels that have no colour at all and makes the result their history."""
 
-    def __init__(self, ctx, desc, variance=None, steer=None, gradient=None, sparse=None):
+    def __init__(self, ctx, desc, variance=None, steer=None, gradient=None, sparse=None, holes=None):
         err = _I(0)
         self._ctx = ctx
         self.desc = desc
+        if holes is not None and sparse is None:
+            raise RtuError(RTU_ERR_ARG, "hole rays belong to a sparse session")
         if sparse is not None:
             if steer is not None or gradient is not None:
                 raise RtuError(RTU_ERR_ARG, "a sparse session takes neither steer nor gradient")
-            self._h = hip.rtu_temporal_begin_sparse(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
-                                                    ctypes.byref(sparse), ctypes.byref(err))
+            if holes is not None:
+                self._h = hip.rtu_temporal_begin_sparse_holes(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
+                                                              ctypes.byref(sparse), ctypes.byref(holes), ctypes.byref(err))
+            else:
+                self._h = hip.rtu_temporal_begin_sparse(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
+                                                        ctypes.byref(sparse), ctypes.byref(err))
         elif gradient is not None:
             self._h = hip.rtu_temporal_begin_gradient(ctx._h, ctypes.byref(desc), ctypes.byref(variance) if variance is not None else None,
                                                       ctypes.byref(steer) if steer is not None else None, ctypes.byref(gradient), ctypes.byref(err))
@@ -1711,6 +1801,12 @@ class Temporal:
         """A sparse session: the number of pixels the last frame had no colour for and filled (0 before the first frame)."""
         n = _U32(0)
         self._check(hip.rtu_temporal_holes(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def hole_rays(self):
+        """A sparse session with hole rays: the number of hole rays of the last frame (0 before the first frame and with budget 0)."""
+        n = _U32(0)
+        self._check(hip.rtu_temporal_hole_rays(self._h, ctypes.byref(n)))
         return int(n.value)
 
     def steer_total(self):
@@ -1818,10 +1914,20 @@ class Context:
         snapshot() -> (rgbz, counts), close()."""
         return Progressive(self, frame, adaptive)
 
-    def temporal(self, desc, variance=None, steer=None, gradient=None, sparse=None):
+    def temporal(self, desc, variance=None, steer=None, gradient=None, sparse=None, holes=None):
         """A temporal session (desc: an RtuTemporalDesc with the size of its frames, see temporal_desc()): frame(frame) -> rgbz,
-        frame_device(), history(), reset(), close(). variance, steer, gradient, sparse: see Temporal."""
-        return Temporal(self, desc, variance, steer, gradient, sparse)
+        frame_device(), history(), reset(), close(). variance, steer, gradient, sparse, holes: see Temporal."""
+        return Temporal(self, desc, variance, steer, gradient, sparse, holes)
+
+    def hole_allocation_device(self, desc, d_hole_ptr, d_hits_ptr, d_counts_ptr, d_offsets_ptr, d_total_ptr, stream=None):
+        """rtu_hole_allocation_device: hole_allocation() on device memory, the same words; the total is one uint32 at d_total_ptr."""
+        self._check(hip.rtu_hole_allocation_device(self._h, ctypes.byref(desc), d_hole_ptr, d_hits_ptr, d_counts_ptr, d_offsets_ptr, d_total_ptr, stream))
+
+    def hole_fold_device(self, desc, d_hist_ptr, d_rgbz_ptr, d_hole_ptr, d_hits_ptr, d_albedo_ptr, d_counts_ptr, d_offsets_ptr, d_rgbt_ptr, n_rays,
+                         stream=None):
+        """rtu_hole_fold_device: hole_fold() on device memory, in place in d_hist_ptr (four planes), d_rgbz_ptr and d_hole_ptr."""
+        self._check(hip.rtu_hole_fold_device(self._h, ctypes.byref(desc), d_hist_ptr, d_rgbz_ptr, d_hole_ptr, d_hits_ptr, d_albedo_ptr, d_counts_ptr,
+                                             d_offsets_ptr, d_rgbt_ptr, int(n_rays), stream))
 
     def sparse_rays_device(self, desc, frame, d_rays_ptr, d_keys_ptr, d_owner_ptr, stream=None):
         """rtu_sparse_rays_device: sparse_rays() written to device memory by a kernel, one ray, key and owner per block."""

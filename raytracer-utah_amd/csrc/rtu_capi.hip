@@ -14,6 +14,7 @@
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
 #include "rtu_gradient.h"
+#include "rtu_holes.h"
 #include "rtu_sparse.h"
 #include "rtu_steer.h"
 #include "rtu_temporal.h"
@@ -1846,6 +1847,12 @@ struct RtuTemporal {
     DevBuf<uint8_t>  sp_hole;
     PinnedBuf<uint8_t> sp_hole_host;      // rtu_temporal_holes counts here
     hipEvent_t       sp_done = nullptr;   // ... recorded behind the last frame's fill: the copy waits for it on the context's stream
+    bool             sparse_holes = false;    // rtu_temporal_begin_sparse_holes
+    RtuHoleDesc      hdesc{};             // ... with block > 1 and budget > 0 (hl_cap > 0): a frame shades its holes behind the owners' rays
+    size_t           hl_cap = 0;          // ... rays of a frame at most: pixels - blocks
+    uint32_t         hl_total = 0;        // ... of the last frame
+    DevBuf<uint32_t> hl_counts, hl_offsets, hl_owner, hl_total_dev;
+    PinnedBuf<uint32_t> hl_total_host;
 };
 
 static void temporal_release(RtuTemporal* t) {
@@ -1876,6 +1883,12 @@ static void temporal_release(RtuTemporal* t) {
     t->sp_hole_host.reset();
     if (t->sp_done) (void)hipEventDestroy(t->sp_done);
     t->sp_done = nullptr;
+    t->hl_counts.reset();
+    t->hl_offsets.reset();
+    t->hl_owner.reset();
+    t->hl_total_dev.reset();
+    t->hl_total_host.reset();
+    t->hl_total = 0;
     t->has_lambda = false;
     t->has_hist = false;
     t->ctx = nullptr;
@@ -4713,6 +4726,129 @@ int rtu_temporal_holes(RtuTemporal* t, uint32_t* count_out) {
     return RTU_OK;
 }
 
+// ---- hole rays (rtu_holes.h, rtu_holes.hip): the allocation and the fold on device memory, and the sparse session that shades its holes ----
+static_assert(sizeof(RtuHoleDesc) == 32, "RtuHoleDesc is 32 bytes");
+
+static const char* const kHoleDescRules = "holes: width, height 1 .. 65536 (2^26 pixels), budget 0 .. 2^26, reserved words 0";
+
+int rtu_hole_allocation_device(RtuContext* ctx, const RtuHoleDesc* desc, const void* d_hole, const void* d_hits, void* d_counts, void* d_offsets,
+                               void* d_total, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_hole_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kHoleDescRules);
+    if (!d_hole || !d_hits || !d_counts || !d_offsets || !d_total) return fail(ctx, RTU_ERR_ARG, "holes: a device pointer is NULL");
+    if (misaligned(d_hits) || misaligned4(d_counts) || misaligned4(d_offsets) || misaligned4(d_total))
+        return fail(ctx, RTU_ERR_ARG, "holes: d_hits must be 16-byte, d_counts, d_offsets and d_total 4-byte aligned (the hole plane: any)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->st_scratch.grow(rtu_steer_scratch_words((size_t)desc->width * (size_t)desc->height)));
+    const hipError_t e = (hipError_t)rtu_launch_hole_allocation(*desc, (const uint8_t*)d_hole, (const float4*)d_hits, (uint32_t*)d_counts, (uint32_t*)d_offsets,
+                                                                (uint32_t*)d_total, ctx->st_scratch.get(), (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "hole allocation launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_hole_fold_device(RtuContext* ctx, const RtuHoleDesc* desc, void* d_hist, void* d_rgbz, void* d_hole, const void* d_hits, const void* d_albedo,
+                         const void* d_counts, const void* d_offsets, const void* d_rgbt, size_t n_rays, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_hole_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kHoleDescRules);
+    if (n_rays > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "holes: more than 2^26 samples");
+    if (!d_hist || !d_rgbz || !d_hole || !d_hits || !d_albedo || !d_counts || !d_offsets || (n_rays && !d_rgbt))
+        return fail(ctx, RTU_ERR_ARG, "holes: a device pointer is NULL");
+    if (misaligned(d_hist) || misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_rgbt) || misaligned4(d_counts) ||
+        misaligned4(d_offsets))
+        return fail(ctx, RTU_ERR_ARG, "holes: device buffers must be 16-byte aligned (d_counts, d_offsets: 4-byte; the hole plane: any)");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_hole_fold((size_t)desc->width * (size_t)desc->height, (float4*)d_hist, (float4*)d_rgbz, (uint8_t*)d_hole,
+                                                          (const float4*)d_hits, (const float4*)d_albedo, (const uint32_t*)d_counts,
+                                                          (const uint32_t*)d_offsets, (const float4*)d_rgbt, (uint32_t)n_rays, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "hole fold launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+RtuTemporal* rtu_temporal_begin_sparse_holes(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuVarianceDesc* vdesc, const RtuSparseDesc* spdesc,
+                                             const RtuHoleDesc* hdesc, int* err_out) {
+    auto refuse = [&](int rc) -> RtuTemporal* {
+        if (err_out) *err_out = rc;
+        return nullptr;
+    };
+    if (!ctx) return refuse(RTU_ERR_ARG);
+    if (!hdesc || !spdesc || !desc || !vdesc) return refuse(fail(ctx, RTU_ERR_ARG, "temporal: a descriptor is NULL"));
+    RtuHoleDesc hd = *hdesc;  // (its frame_index is the frame's)
+    hd.frame_index = 0;
+    if (hd.width == 0 && hd.height == 0) {
+        hd.width = desc->width;
+        hd.height = desc->height;
+    }
+    if (rtu_temporal_check_desc(desc) == RTU_OK) {
+        if (rtu_hole_check_desc(&hd) != RTU_OK) return refuse(fail(ctx, RTU_ERR_ARG, "%s", kHoleDescRules));
+        if (hd.width != desc->width || hd.height != desc->height) return refuse(fail(ctx, RTU_ERR_ARG, "holes: the desc has not the session's size"));
+    }
+    RtuTemporal* t = rtu_temporal_begin_sparse(ctx, desc, vdesc, spdesc, err_out);
+    if (!t) return nullptr;
+    t->sparse_holes = true;
+    t->hdesc = hd;
+    if (!t->sparse || hd.budget == 0) return t;  // a sparse session's frames
+    const size_t n = t->pixels;
+    t->hl_cap = n - t->blocks;  // (block > 1: the image has more pixels than blocks unless it is 1 x 1, which has no hole)
+    hipError_t e = hipSuccess;
+    if (t->hl_cap) {
+        e = t->hl_counts.grow(n);
+        if (e == hipSuccess) e = t->hl_offsets.grow(n);
+        if (e == hipSuccess) e = t->hl_owner.grow(n);
+        if (e == hipSuccess) e = t->hl_total_dev.grow(1);
+        if (e == hipSuccess) e = t->hl_total_host.grow(1);
+        if (e == hipSuccess) e = ctx->st_scratch.grow(rtu_steer_scratch_words(n));
+    }
+    if (e != hipSuccess) {
+        const int rc = fail(ctx, RTU_ERR_HIP, "session buffers: %s", hipGetErrorString(e));
+        rtu_temporal_free(t);
+        return refuse(rc);
+    }
+    return t;
+}
+
+// A sparse session's frame between the sparse accumulator and the fill: the pixels `hole` marks shaded by rays of their own — behind
+// the owners' batch in the session's ray, key and result buffers — and made the history of those pixels in `hist` and d_rgbz. *total_out:
+// the rays of the frame; the session's own word is set at the commit.
+static int temporal_hole_rays(RtuTemporal* t, const RtuFrameDesc* frame, uint32_t k, float4* hist, void* d_rgbz, void* hip_stream, uint32_t* total_out) {
+    RtuContext* ctx = t->ctx;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const bool paths = frame->gather_bounces != 0;
+    RtuHoleDesc hd = t->hdesc;
+    hd.frame_index = k;
+    int rc = rtu_hole_allocation_device(ctx, &hd, t->sp_hole.get(), t->hits.get(), t->hl_counts.get(), t->hl_offsets.get(), t->hl_total_dev.get(), hip_stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(t->hl_total_host.get(), t->hl_total_dev.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    RTU_HIP(ctx, hipStreamSynchronize(stream));
+    const uint32_t total = *t->hl_total_host.get();
+    if ((size_t)total > t->hl_cap) return fail(ctx, RTU_ERR_HIP, "holes: %u rays allocated, the session holds %zu", total, t->hl_cap);
+    *total_out = total;
+    if (total == 0) return RTU_OK;
+    float4*   rays = t->rays.get() + 2 * t->blocks;
+    uint32_t* keys = t->keys.get() + t->blocks;
+    float4*   img = t->img.get() + t->blocks;
+    const RtuSteerDesc sd = hl_steer_desc(hd);
+    if ((rc = rtu_extra_sample_rays_device(ctx, &sd, frame, t->hl_counts.get(), t->hl_offsets.get(), total, rays, keys, t->hl_owner.get(), hip_stream)) != RTU_OK)
+        return rc;
+    RtuShadeDesc shd;
+    rtu_shade_defaults(&shd);
+    memcpy(shd.eye, frame->cam_pos, sizeof shd.eye);
+    shd.max_bounce = frame->max_bounce;
+    RtuFrameDesc f;
+    if ((rc = shade_args(ctx, rays, img, total, &shd, true, &f, true, keys, paths)) != RTU_OK) return rc;
+    if (paths && (rc = paths_chain(ctx, f, img, stream, rays, keys, total)) != RTU_OK) return rc;
+    if ((rc = shade_until_fits(ctx, f, img, stream, rays, keys, total, paths, nullptr)) != RTU_OK) return rc;
+    return rtu_hole_fold_device(ctx, &hd, hist, d_rgbz, t->sp_hole.get(), t->hits.get(), t->albedo.get(), t->hl_counts.get(), t->hl_offsets.get(), img, total,
+                                hip_stream);
+}
+
+int rtu_temporal_hole_rays(RtuTemporal* t, uint32_t* count_out) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    if (!t->sparse_holes) return fail(t->ctx, RTU_ERR_ARG, "not a sparse session with hole rays");
+    if (!count_out) return fail(t->ctx, RTU_ERR_ARG, "count_out is NULL");
+    *count_out = t->has_hist ? t->hl_total : 0u;
+    return RTU_OK;
+}
+
 // what a moved frame has beyond a plain one (rtu_temporal_frame_moved_device)
 struct TemporalMoved {
     const RtuNodeMotion* h_motion;
@@ -4744,10 +4880,12 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     // A REFUSED CALL LEAVES THE SESSION AS IT WAS. Whatever an entry further down refuses — max_bounce, a camera that is not finite, too
     // many chains of recipe P — it refuses before THE COMMIT below: until there the frame works on copies of the counter and of the
     // history flag, and writes only buffers that hold nothing between two frames. What is refused behind the commit (a steered frame's
-    // samples * (1 + max_extra), in temporal_steer) is therefore refused here.
+    // samples * (1 + max_extra), in temporal_steer) is therefore refused here; so is what the hole rays would refuse, though they run
+    // before the commit.
     if (const int rc = check_frame(ctx, frame)) return rc;
     if (t->steered && t->st_cap && (long long)frame->samples * (1 + t->sdesc.max_extra) > 65536)
         return fail(ctx, RTU_ERR_ARG, "a steered frame needs samples * (1 + max_extra) <= 65536");
+    if (t->hl_cap && 2ll * frame->samples > 65536) return fail(ctx, RTU_ERR_ARG, "a frame with hole rays needs 2 * samples <= 65536");
     if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
     if (misaligned(d_rgbz)) return fail(ctx, RTU_ERR_ARG, "d_rgbz must be 16-byte aligned");
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
@@ -4776,6 +4914,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     const bool has_hist = t->has_hist && !start_over;
     const int  k = start_over ? 0 : t->k;
     int rc;
+    uint32_t hole_total = 0;
     if (t->sparse) {  // one ray per block: the block's owner of frame k in the sample the block has reached
         t->spdesc.frame_index = (uint32_t)k;
         rc = rtu_sparse_rays_device(ctx, &t->spdesc, frame, t->rays.get(), t->keys.get(), t->sp_owner.get(), hip_stream);
@@ -4826,6 +4965,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
                                                        t->hits.get(), t->albedo.get(), has_hist ? t->hist[t->cur].get() : nullptr,
                                                        t->hist[t->cur ^ 1].get(), d_rgbz, t->sp_hole.get(), t->motion.get(), n_nodes,
                                                        moved ? moved->history_cap : 0, hip_stream);
+            if (rc == RTU_OK && t->hl_cap) rc = temporal_hole_rays(t, frame, (uint32_t)k, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream, &hole_total);
             if (rc == RTU_OK)
                 rc = rtu_sparse_fill_device(ctx, &td, &t->spdesc, t->hits.get(), t->albedo.get(), t->sp_owner.get(), t->img.get(), t->sp_hole.get(), d_rgbz,
                                             hip_stream);
@@ -4865,6 +5005,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     t->has_hist = true;
     t->prev_cam = *frame;
     t->k = k + 1;
+    t->hl_total = hole_total;
     if (t->variance) {
         if ((rc = rtu_variance_device(ctx, &t->vdesc, t->hist[t->cur].get(), t->hits.get(), t->var.get(), hip_stream)) != RTU_OK) return rc;
         if (t->steered && t->st_cap && (rc = temporal_steer(t, frame, (uint32_t)k, d_rgbz, hip_stream)) != RTU_OK) return rc;
@@ -4918,6 +5059,7 @@ int rtu_temporal_reset(RtuTemporal* t) {
     t->has_hist = false;
     t->k = 0;
     t->st_total = 0;
+    t->hl_total = 0;
     t->has_lambda = false;
     return RTU_OK;
 }

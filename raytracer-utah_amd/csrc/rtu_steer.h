@@ -98,10 +98,24 @@ int rtu_steer_check_desc(const RtuSteerDesc* d);
 // words of scratch the allocation needs for `pixels` pixels (16-byte aligned)
 size_t rtu_steer_scratch_words(size_t pixels);
 
+// where the allocation keeps what in its scratch of rtu_steer_scratch_words(pixels) words: Wsum (64 bits, 8-byte aligned), the total
+// before the cut, one weight per pixel (16-byte aligned, padded to whole groups of four) and one sum per tile of 1024 pixels
+struct StScratch {
+    unsigned long long* wsum;
+    uint32_t *raw_total, *w, *sums;
+};
+inline StScratch st_scratch(uint32_t* scratch, size_t pixels) {
+    return StScratch{reinterpret_cast<unsigned long long*>(scratch), scratch + 2, scratch + 4, scratch + 4 + 4 * ((pixels + 3) / 4)};
+}
+
 // counts[p], offsets[p] and *total of rtu_sample_allocation for the width * height pixels of `d`: hist four planes, hits RtuRayHit, v
 // floats. Asynchronous on `stream`; every launch function returns a hipError_t as int.
 int rtu_launch_sample_allocation(const RtuSteerDesc& d, const float4* hist, const float4* hits, const float* v, uint32_t* counts, uint32_t* offsets,
                                  uint32_t* total, uint32_t* scratch, hipStream_t stream);
+// The allocation behind its weights (k_steer_counts, k_steer_sums, k_steer_finish): s.w and *s.wsum are written on `stream` by the
+// caller's own weight kernel, after a hipMemsetAsync of the first 16 bytes of the scratch. Of `d` the size, budget, max_extra and
+// frame_index are used. "Hole rays" (rtu_holes.hip) allocates through this with weights of its own.
+int rtu_launch_allocation_scan(const RtuSteerDesc& d, const StScratch& s, uint32_t* counts, uint32_t* offsets, uint32_t* total, hipStream_t stream);
 // rays[2 * (o_p + j) ..], keys[o_p + j], owner[o_p + j] for j < c_p; a ray at or beyond `capacity` is not written
 int rtu_launch_extra_sample_rays(const StRays& r, uint32_t max_extra, const uint32_t* counts, const uint32_t* offsets, float4* rays, uint32_t* keys,
                                  uint32_t* owner, uint32_t capacity, hipStream_t stream);

@@ -13,6 +13,9 @@
 //                    neighbouring rays (the offsets rise with the pixel), and no lane has to search for its pixel.
 //   k_refine         a lane per pixel: its samples folded into E, M and the image in place
 //
+// rtu_launch_allocation_scan launches k_steer_counts, k_steer_sums and k_steer_finish behind weights that are already in the scratch:
+// rtu_launch_sample_allocation calls it behind k_steer_weight, "Hole rays" (rtu_holes.hip) behind a weight kernel of its own.
+//
 // Every store is a vector store, the one atomic a vector atomic; there is no inline assembly. Nothing is read or written beyond
 // `pixels`, `capacity` or `n_rays`, whatever the counts and offsets hold.
 #include "rtu_steer.h"
@@ -170,19 +173,22 @@ size_t rtu_steer_scratch_words(size_t pixels) {
     return 4 + 4 * ((pixels + 3) / 4) + tiles;
 }
 
+int rtu_launch_allocation_scan(const RtuSteerDesc& d, const StScratch& s, uint32_t* counts, uint32_t* offsets, uint32_t* total, hipStream_t stream) {
+    const uint32_t n = (uint32_t)d.width * (uint32_t)d.height, tiles = (n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_steer_counts, dim3(tiles), dim3(256), 0, stream, d, s.w, s.wsum, n, counts, offsets, s.sums);
+    hipLaunchKernelGGL(k_steer_sums, dim3(1), dim3(256), 0, stream, s.sums, tiles, s.raw_total);
+    hipLaunchKernelGGL(k_steer_finish, dim3((n + 255u) / 256u), dim3(256), 0, stream, d.budget, s.sums, s.raw_total, n, counts, offsets, total);
+    return (int)hipGetLastError();
+}
+
 int rtu_launch_sample_allocation(const RtuSteerDesc& d, const float4* hist, const float4* hits, const float* v, uint32_t* counts, uint32_t* offsets,
                                  uint32_t* total, uint32_t* scratch, hipStream_t stream) {
     const uint32_t n = (uint32_t)d.width * (uint32_t)d.height, tiles = (n + kTile - 1) / kTile;
-    unsigned long long* wsum = reinterpret_cast<unsigned long long*>(scratch);  // words 0, 1; word 2: the total before the cut
-    uint32_t* w = scratch + 4;
-    uint32_t* sums = w + 4 * (((size_t)n + 3) / 4);
+    const StScratch s = st_scratch(scratch, n);
     const hipError_t e = hipMemsetAsync(scratch, 0, 16, stream);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_steer_weight, dim3(tiles), dim3(256), 0, stream, hist, hits, v, n, w, wsum);
-    hipLaunchKernelGGL(k_steer_counts, dim3(tiles), dim3(256), 0, stream, d, w, wsum, n, counts, offsets, sums);
-    hipLaunchKernelGGL(k_steer_sums, dim3(1), dim3(256), 0, stream, sums, tiles, scratch + 2);
-    hipLaunchKernelGGL(k_steer_finish, dim3((n + 255u) / 256u), dim3(256), 0, stream, d.budget, sums, scratch + 2, n, counts, offsets, total);
-    return (int)hipGetLastError();
+    hipLaunchKernelGGL(k_steer_weight, dim3(tiles), dim3(256), 0, stream, hist, hits, v, n, s.w, s.wsum);
+    return rtu_launch_allocation_scan(d, s, counts, offsets, total, stream);
 }
 
 int rtu_launch_extra_sample_rays(const StRays& r, uint32_t max_extra, const uint32_t* counts, const uint32_t* offsets, float4* rays, uint32_t* keys,
