@@ -579,6 +579,8 @@ void renumber_bfs(const RtuMesh& m, std::vector<RtuBvhNode>& bfs, uint32_t& any_
 // ray (derived at cull_margin and sphere_slack, rtu_intersect.h): per node the condition numbers along its chain, root first.
 struct WorldFar {
     float wnoise, wreach, sph_k, sph_r;
+    float near_m0, near_c1;           // the margin of rays that start at hit points: c1 max(m0, pm) (rtu_intersect.h, THE NEAR MARGIN)
+    float wlist;                      // the scale the occluder lists are built with: wscale itself, or more in a wide scene
 };
 namespace {
 double abs_row_norm(const double* m) {  // || |M| ||_inf of a row-major 3 x 3 matrix
@@ -593,6 +595,27 @@ void mul33(const double* a, const double* b, double* out) {
     memcpy(out, t, sizeof t);
 }
 }  // namespace
+// The margin of the rays that start at hit points, delta = c1 max(m0, pm), and the scale the occluder lists are built with
+// (rtu_intersect.h, THE NEAR MARGIN, has the argument): 1e-4 max(wscale, pm) and wscale themselves, bit for bit, unless the far
+// term at the scene's own extent exceeds twelve near margins. omega1: 1 + the largest |coordinate| of the origin of any node's space.
+void near_margin(float wscale, float wnoise, double omega1, WorldFar& out) {
+    out.near_m0 = wscale; out.near_c1 = 1e-4f; out.wlist = wscale;
+    const double ws = wscale, P = 2.0 * ws, wn = wnoise;
+    const auto f = [&](double m) { return 1e-4 * std::max(ws, m) + wn * (m + omega1) * (m + ws); };
+    const double DP = wn * (P + omega1) * (P + ws);
+    if (!(DP >= 12.0 * 1e-4 * ws)) return;  // (a scale or a chain that is not finite: no node has a bound, world_bounds)
+    const double c1 = f(P) / P * (1 + 1e-6);
+    // f is convex and c1 m passes above f(P): c1 m >= f(m) exactly on an interval [m*, P]
+    double lo = 0, hi = P;
+    for (int i = 0; i < 64; i++) {
+        const double mid = 0.5 * (lo + hi);
+        if (c1 * mid >= f(mid)) hi = mid; else lo = mid;
+    }
+    const double m0 = hi * (1 + 1e-6), wl = (ws + 1e4 * DP) * (1 + 1e-6);
+    out.near_m0 = m0 < 1e30 ? (float)m0 : 1e30f;
+    out.near_c1 = c1 < 1e30 ? (float)c1 : 1e30f;
+    out.wlist = wl < 1e30 ? (float)wl : 1e30f;
+}
 void world_far(const RtuSceneDesc* s, double wscale, WorldFar& out) {
     const double u = 0x1p-24;
     double K = 0, omega = 0, sph_cond = 0, sph_T = 0;
@@ -628,6 +651,7 @@ void world_far(const RtuSceneDesc* s, double wscale, WorldFar& out) {
     out.wreach = (float)(std::max(wscale, omega + 1.0) * (1 + 1e-6));
     out.sph_k = (float)(5.2e-3 * sph_cond * (1 + 1e-6));
     out.sph_r = (float)(1.74 * sph_T * (1 + 1e-6));
+    near_margin((float)wscale, out.wnoise, omega + 1.0, out);
 }
 // NODE-LEVEL BOUNDS (DevNode::wmin / wmax; the argument is in rtu_intersect.h, trace): the object's own bounding box —
 // the unit cube of a sphere, the unit square of a plane (objects.h:25,37), the mesh's box — taken corner by corner through
@@ -2053,6 +2077,8 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
     ds.wreach = far.wreach;
     ds.wsphere_k = far.sph_k;
     ds.wsphere_r = far.sph_r;
+    ds.near_m0 = far.near_m0;
+    ds.near_c1 = far.near_c1;
     ds.nol_ok = 1;
     for (uint32_t i = 0; i < s->n_lights; i++)
         for (int k = 0; k < 3; k++)
@@ -2114,7 +2140,7 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
         ds.n_pcover++;
     }
     ctx->light_list_info.clear();
-    rc = on_device ? build_light_lists_device(ctx, s, cover_dev, lohi, wscale, ds) : build_light_lists(ctx, s, cover_host, wscale, ds);
+    rc = on_device ? build_light_lists_device(ctx, s, cover_dev, lohi, far.wlist, ds) : build_light_lists(ctx, s, cover_host, far.wlist, ds);
     if (rc != RTU_OK) return rc;
     ds.obj_mask = 0;
     for (uint32_t i = 0; i < s->n_nodes && i < 64u; i++)
@@ -3355,7 +3381,10 @@ int rtu_debug_light_list(const RtuSceneDesc* s, uint32_t light_slot, uint32_t co
         if (s->nodes[i].obj_type == RTU_OBJ_TRIMESH && seen++ == cover_slot) { node = (int)i; break; }
     if (li < 0 || node < 0) return RTU_ERR_ARG;
     std::vector<DevNode> nodes(s->n_nodes);
-    const float wscale = world_bounds(s, nodes);
+    const float wbound = world_bounds(s, nodes);
+    WorldFar far;
+    world_far(s, wbound, far);
+    const float wscale = far.wlist;  // (the lists carry the margin of the shadow rays that look them up)
     SahTree sah;
     build_sah(s->meshes[s->nodes[node].mesh_id], sah);
     CoverMesh cm;

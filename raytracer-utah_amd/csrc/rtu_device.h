@@ -185,6 +185,7 @@ struct DevScene {
     float    pcover_quad[RTU_MAX_PCOVER][4][3];  // the square's corners (-1,-1) (1,-1) (1,1) (-1,1) through the node's chain of transformations (binary64, rounded)
     uint32_t dbg;               // experiment switches (rtu_debug_flags), as KernelArgs::dbg
     float    wsphere_k, wsphere_r;  // what a sphere's root can lie outside its box along the ray (rtu_intersect.h: sphere_slack)
+    float    near_m0, near_c1;  // the margin of rays that start at hit points, c1 max(m0, pm) (rtu_intersect.h: THE NEAR MARGIN)
     uint32_t node_bounds;       // 0: node-level bounds off (test hook rtu_debug_node_bounds; results must not change)
     float    background[3];     // background.Sample(...) for an untextured / NULL-map background
     float    environment[3];    // environment.SampleEnvironment(...) likewise

@@ -728,14 +728,42 @@ __device__ __forceinline__ double cull_margin_d(const DevScene& s, double pm) {
     const double q = fmin(pm, 0x1p25) + (double)s.wreach;
     return 1e-4 * fmax((double)s.wscale, pm) + (double)s.wnoise * q * q;
 }
+// THE NEAR MARGIN: secondary, shadow and gather rays (k_trace, the inline shadow walks) keep a margin of one maximum and one product,
+//     delta = c1 max(m0, pm)        (DevScene::near_m0, near_c1, made by near_margin, rtu_capi.hip),
+// which is 1e-4 max(wscale, pm), bit for bit and instruction for instruction, in a scene that needs no more (c1 = 1e-4,
+// m0 = wscale), and the occluder lists are built with a scale wlist that is wscale there (rtu_lightlist.h, ll_face_wid). Such a
+// ray starts at a hit point, i.e. within the scene's bounds up to what the ray that found it was off: pm <= P = 2 wscale. The
+// second term of cull_margin, in its product form above, is D(pm) = wnoise (pm + Omega + 1) (pm + wscale), and
+// f(pm) = 1e-4 max(wscale, pm) + D(pm) is convex and increasing. With c1 = f(P) / P the line c1 pm passes through (P, f(P)) and
+// lies above f exactly on an interval [m*, P] (near_margin finds m* by bisection); m0 = m* makes delta = c1 m* >= f(m*) >= f(pm)
+// below it: delta >= f(pm) on all of [0, P] — the far term at the price of one more scene constant and no instruction in the
+// walks (k_trace has no register to spare, NOTEBOOK.md section 14; a third constant and a fused multiply-add for the chord of f
+// cost the benchmark 1 %, profiles/r24_wide_scenes.json). In a scene with one huge floor a ray near the origin keeps a small
+// margin (Project 7, a floor of 1366 units: m* = 30, delta = 0.3 units there, where the old margin was 0.14); where Omega
+// dominates (a far chain) f is nearly a line that misses the origin, m* = P, and every ray has delta = f(P). An origin further
+// out than P (a hit found by a ray from far outside, whose own margin let it leave the scene) keeps c1 pm >= 1e-4 pm, no less
+// than before. A list answers for every origin: wlist = wscale + 1e4 D(P), so that ll_face_wid >= 1e-4 wscale + D(P); where
+// that makes a list useless the builder drops it (a corner behind the pinhole) and the mesh is walked.
+// WHEN. D is a bound; what the reference does is less. On the oracle the line it tests is off by at most D(P) / 28 where it
+// arrives (tests/test_oracle_wide.py: a card at (X, 0.9 X, 0.3 X) seen by mirror from the opposite corner; 0.056 units at X = 300
+// where D(P) = 2.3, 0.82 at X = 1000 where D(P) = 23, 2.6 at X = 2000; through a chain translated by G and back, D(P) / 145 at
+// G = 2e4), and the near margin 1e-4 wscale is all slack but the 0.24 % the slab test itself rounds. So the term is measured, not
+// proven, to be idle while D(P) < 28 * 1e-4 wscale. near_margin switches it on from D(P) >= 12 * 1e-4 wscale: a wide scene from
+// an extent of about 40 units on (wscale = 60 with K = 24; the smallest extent at which the oracle finds a hit that the near
+// margin alone would skip is 250, among 147 456 reflection rays; 20 000 random rays once found 300), a far chain around a
+// 30-unit scene from G = 55 on (the smallest found: 4000). Below, every margin, list and image keeps its bits; the benchmarked
+// scenes are there (teapot2: D(P) = 5.3e-4 wscale, Project 4 / 11: 9.5e-4). Above, nodes are skipped less often — at X = 5000
+// the margin is hundreds of units, hardly ever — and correctly. The reference's scenes with a floor of 500 to 1366 units
+// (Project 7, 9, 10) are above: a ray that starts far out on such a floor is a far ray.
+// A sphere never needed it: world_bounds widens its box by 4e-6 S^2 / R, S the scene's diagonal, which in a wide scene is more
+// than D(P) / 28 (R = 1, X = 1000: 30 units against 0.8).
 // fast_ray for the node-level bounds: the reciprocals need not be correctly rounded (v_rcp_f32 is within 1 ulp, five
-// orders of magnitude inside the margin). FAR: the margin of a ray that may start anywhere (cull_margin); else that of a ray
-// that starts in or around the scene.
+// orders of magnitude inside the margin). FAR: the margin of a ray that may start anywhere (cull_margin); else the near margin.
 template <bool FAR>
 __device__ __forceinline__ FastRay fast_ray_world(const Ray& ray, const DevScene& s) {
     const float tiny = 0x1p-100f;
     const float pm = fmaxf(fabsf(ray.p.x), fmaxf(fabsf(ray.p.y), fabsf(ray.p.z)));
-    const float delta = FAR ? cull_margin(s, pm) : 1e-4f * (s.wscale > pm ? s.wscale : pm);
+    const float delta = FAR ? cull_margin(s, pm) : s.near_c1 * (s.near_m0 > pm ? s.near_m0 : pm);
     const float dx = fabsf(ray.dir.x) < tiny ? copysignf(tiny, ray.dir.x) : ray.dir.x;
     const float dy = fabsf(ray.dir.y) < tiny ? copysignf(tiny, ray.dir.y) : ray.dir.y;
     const float dz = fabsf(ray.dir.z) < tiny ? copysignf(tiny, ray.dir.z) : ray.dir.z;
@@ -1207,7 +1235,8 @@ __device__ __forceinline__ int mesh_shadow_cells(const uint32_t* cell_tri, uint3
 // primary_pixel). Stage 1 of recipe W goes by the node rectangles and coverage masks, which carry cull_margin. Secondary and
 // shadow rays, and the gather rays of recipe P, start at hit points, i.e. on the scene's surfaces, and keep
 // delta = 1e-4 * max(scene scale, |origin|) and no slack: in k_trace the two terms cost scalar registers it does not have
-// (NOTEBOOK.md section 14).
+// (NOTEBOOK.md section 14); where the scene is wide enough to need the second term, the two constants of that margin carry
+// it (THE NEAR MARGIN).
 // So a ray whose line, between its origin and the best hit so far (for a sphere: sphere_slack further at both ends), stays
 // clear of the box by delta = cull_margin(|origin|) on some axis — the geometric form of "Culling" above, on the world-space
 // box of the node — cannot produce a result there, and the node is skipped before its transformation and exact test.

@@ -44,24 +44,58 @@ def hits_differing(a, b):
     return int(bad.sum())
 
 
-def render_figures(pkg, orc, ctx, scene, w, h, label):
+def fast_figures(pkg, ctx, fig, cnt, make_frame, flags=(0,)):
+    """Adds to `fig`, per combination of node-level bounds on / off, stage 2 per ray / cooperative and rtu_debug_flags in `flags`
+    (64: the occluder lists only say "empty cell or not"), the number of pixels at which the fast variant differs from `cnt`."""
+    try:
+        for on in (1, 0):
+            assert pkg.hip.rtu_debug_node_bounds(ctx._h, on) == 0
+            for thr in (1, 10 ** 9):
+                for dbg in flags:
+                    assert pkg.hip.rtu_debug_flags(ctx._h, dbg) == 0
+                    fr = make_frame()
+                    fr.coop_threshold = thr
+                    fast = ctx.render(fr)[0]
+                    name = "fast (bounds %d, coop_threshold %d%s) != counting" % (on, thr, ", flags %d" % dbg if dbg else "")
+                    fig[name] = differing(fast.reshape(-1, 4), cnt.reshape(-1, 4))
+    finally:
+        pkg.hip.rtu_debug_node_bounds(ctx._h, 1)
+        pkg.hip.rtu_debug_flags(ctx._h, 0)
+
+
+def render_figures(pkg, orc, ctx, scene, w, h, label, flags=(0,)):
     """The scene is uploaded. Returns (figures: name -> number of differing pixels or 0 / 1, the counting image, the oracle's)."""
     cam = scene.desc.camera
     cpu, cst = orc.render(scene, w, h, threads=8)
     cnt, gst = ctx.render(pkg.frame_setup(cam, w, h, collect_stats=True), stats=True)
     fig = {"counting z != oracle": differing(cnt[..., 3].reshape(-1), cpu[..., 3].reshape(-1)), "counters != oracle": int(gst != cst)}
-    try:
-        for on in (1, 0):
-            assert pkg.hip.rtu_debug_node_bounds(ctx._h, on) == 0
-            for thr in (1, 10 ** 9):
-                fr = pkg.frame_setup(cam, w, h)
-                fr.coop_threshold = thr
-                fast = ctx.render(fr)[0]
-                fig["fast (bounds %d, coop_threshold %d) != counting" % (on, thr)] = differing(fast.reshape(-1, 4), cnt.reshape(-1, 4))
-    finally:
-        pkg.hip.rtu_debug_node_bounds(ctx._h, 1)
+    fast_figures(pkg, ctx, fig, cnt, lambda: pkg.frame_setup(cam, w, h), flags)
     print("%s render %dx%d, %d hit pixels: %s" % (label, w, h, int((cpu[..., 3] != np.float32(1e30)).sum()), fig))
     return fig, cnt, cpu
+
+
+def sampled_figures(pkg, orc, ctx, scene, size, spp, gather, label, flags=(0,)):
+    """The scene is uploaded. A frame of recipe S (gather 0) or P on the keyed sample streams: (figures, the counting image, the oracle's)."""
+    cam = scene.desc.camera
+    cpu, cst = (orc.render_paths if gather else orc.render_samples)(scene, size, size, spp, stream=orc.STREAM_KEYED, trig=orc.TRIG_PORTABLE, threads=8)
+    cnt, gst = ctx.render(pkg.frame_setup(cam, size, size, collect_stats=True, samples=spp, gather_bounces=gather), stats=True)
+    fig = {"counting z != oracle": differing(cnt[..., 3].reshape(-1), cpu[..., 3].reshape(-1)), "counters != oracle": int(gst != cst)}
+    fast_figures(pkg, ctx, fig, cnt, lambda: pkg.frame_setup(cam, size, size, samples=spp, gather_bounces=gather), flags)
+    print("%s: %s" % (label, fig))
+    return fig, cnt, cpu
+
+
+def settle_sampled(orc, fig, cnt, cpu, gather):
+    """The bars of the sampled frames: recipe S within 3e-4 (tests/test_gpu_fuzz.py: the sum over samples); recipe P 8-bit +-1 and
+    linear RGB to 1e-3 of max(value, 1e-2) (tests/test_gpu_sampled.py: the chain multiplies up to five Shade() trees)."""
+    if not gather:
+        settle(orc, [fig], [(cnt, cpu)], rel_tol=3e-4)
+        return
+    settle(orc, [fig], [])
+    d8 = np.abs(orc.postprocess(cnt)[0].astype(np.int32) - orc.postprocess(cpu)[0].astype(np.int32))
+    assert d8.max() <= 1, "8-bit RGB differs by %d levels at %d pixels" % (d8.max(), (d8 > 1).sum())
+    d = np.abs(cnt[..., :3].astype(np.float64) - cpu[..., :3].astype(np.float64))
+    assert (d / np.maximum(np.abs(cpu[..., :3]), 1e-2)).max() < 1e-3
 
 
 def ray_figures(pkg, orc, ctx, scene, rays, eye, label):
@@ -138,28 +172,8 @@ def test_f2_sampled_frames_from_afar(pkg, orc, ctx, tmp_path, D, zc, card_first,
     to 1e-3 of max(value, 1e-2) — the chain multiplies up to five Shade() trees."""
     scene = (f2_mesh_scene if mesh else f2_scene)(pkg, tmp_path, D, zc, card_first)
     ctx.upload(scene)
-    cam, spp = scene.desc.camera, 2
-    cpu, cst = (orc.render_paths if gather else orc.render_samples)(scene, SIZE, SIZE, spp, stream=orc.STREAM_KEYED, trig=orc.TRIG_PORTABLE, threads=8)
-    cnt, gst = ctx.render(pkg.frame_setup(cam, SIZE, SIZE, collect_stats=True, samples=spp, gather_bounces=gather), stats=True)
-    fig = {"counting z != oracle": differing(cnt[..., 3].reshape(-1), cpu[..., 3].reshape(-1)), "counters != oracle": int(gst != cst)}
-    try:
-        for on in (1, 0):
-            assert pkg.hip.rtu_debug_node_bounds(ctx._h, on) == 0
-            for thr in (1, 10 ** 9):
-                fr = pkg.frame_setup(cam, SIZE, SIZE, samples=spp, gather_bounces=gather)
-                fr.coop_threshold = thr
-                fig["fast (bounds %d, coop_threshold %d) != counting" % (on, thr)] = differing(ctx.render(fr)[0].reshape(-1, 4), cnt.reshape(-1, 4))
-    finally:
-        pkg.hip.rtu_debug_node_bounds(ctx._h, 1)
-    print("F2 sampled D=%g zc=%g card first=%s torus=%s gather=%d: %s" % (D, zc, card_first, mesh, gather, fig))
-    if not gather:
-        settle(orc, [fig], [(cnt, cpu)], rel_tol=3e-4)
-        return
-    settle(orc, [fig], [])
-    d8 = np.abs(orc.postprocess(cnt)[0].astype(np.int32) - orc.postprocess(cpu)[0].astype(np.int32))
-    assert d8.max() <= 1, "8-bit RGB differs by %d levels at %d pixels" % (d8.max(), (d8 > 1).sum())
-    d = np.abs(cnt[..., :3].astype(np.float64) - cpu[..., :3].astype(np.float64))
-    assert (d / np.maximum(np.abs(cpu[..., :3]), 1e-2)).max() < 1e-3
+    fig, cnt, cpu = sampled_figures(pkg, orc, ctx, scene, SIZE, 2, gather, "F2 sampled D=%g zc=%g card first=%s torus=%s gather=%d" % (D, zc, card_first, mesh, gather))
+    settle_sampled(orc, fig, cnt, cpu, gather)
 
 
 # ---- F3 --------------------------------------------------------------------------------------------------------------------------
