@@ -1273,6 +1273,74 @@ RtuTemporal* rtu_temporal_begin_sparse_holes(RtuContext* ctx, const RtuTemporalD
                                              const RtuSparseDesc* sparse_desc, const RtuHoleDesc* hole_desc, int* err_out);
 int  rtu_temporal_hole_rays(RtuTemporal* t, uint32_t* count_out);
 
+/* ---- Temporal accumulation for sensors: previews that follow a moving panoramic, fisheye or orthographic sensor (rtu_sensor.h
+ * sensor_project, rtu_temporal.h TpSensorProj, rtu_temporal.hip k_temporal_sensor<MODEL, MOMENTS>) ----
+ * "Temporal accumulation" with an RtuSensorDesc in place of each camera. Everything it states holds unchanged — the history planes, the
+ * range test, the four taps and their order, the tap acceptance test, the blend, the moments of "Variance-guided filtering" — but the
+ * lookup, which goes through THE PROJECTION of the previous sensor S: the counterpart of THE RAY of "Sensors", world point Pm to image
+ * coordinates (fx, fy) in which pixel (x, y) has its centre at (x, y). binary32, one rounding per operation, in the order written, no
+ * contraction, IEEE divide and sqrt, dot as in "Temporal accumulation". The only transcendental is acos(x): the portable_acos of the
+ * sample streams — binary64 IEEE operations in fdlibm's sequence, rounded to float (sensor_acos in rtu_sensor.h states it for host
+ * and device). W = (float)S.width, H = (float)S.height.
+ *   Q = Pm - S.pos;  a = dot(Q, S.forward);  b = dot(Q, S.right);  c = dot(Q, S.up)
+ *   angle(s, k), s >= 0:  L = sqrtf(s * s + k * k); none unless L is finite and L > 0
+ *                         |k| <= s  : acos(k / L)
+ *                         otherwise q = acos(s / L);  k > 0 ? 1.5707964f - q : 1.5707964f + q
+ *                         (acos never gets an argument above about 0.71 in magnitude: well conditioned in binary32)
+ *   RTU_SENSOR_EQUIRECT  h = sqrtf(a * a + b * b); none if h == 0 (a pole). pol = angle(h, c); th = angle(|b|, -a);
+ *                        lon = b <= 0 ? th : 6.2831855f - th;  fx = lon / 6.2831855f * W - 0.5f;  fy = pol / 3.1415927f * H - 0.5f.
+ *                        COLUMNS WRAP: a tap at column qx is taken at qx + width when qx < 0 and at qx - width when qx >= width.
+ *                        Rows do not wrap.
+ *   RTU_SENSOR_FISHEYE   p = sqrtf(b * b + c * c). p == 0: the image centre (0.5f * W - 0.5f, 0.5f * H - 0.5f) when a > 0, otherwise
+ *                        none. Otherwise r = angle(p, a) / (fov_deg * 0.008726646f); none unless r <= 1;
+ *                        R = 0.5f * (float)min(width, height);  fx = ((r * (b / p)) * R + 0.5f * W) - 0.5f;
+ *                        fy = ((-(r * (c / p))) * R + 0.5f * H) - 0.5f. A history pixel outside the image circle has n = 0: no
+ *                        tap accepts it.
+ *   RTU_SENSOR_ORTHO     none unless a > 0;  fx = (b / extent[0] + 0.5f) * W - 0.5f;  fy = (0.5f - c / extent[1]) * H - 0.5f.
+ * rtu_sensor_project (pure host code, no GPU and no context) is the executable statement of these expressions for n points {x, y, z}:
+ * fxfy_out[2 i ..] = (fx, fy) and ok_out[i] = 1, or (0, 0) and 0 where the point has none. The range test is not part of it.
+ *   lookup   NONE without a previous history, or when prev and cur differ in model, width or height (hist_prev is then not read).
+ *            STATIC (the one tap is the pixel itself) when model, width, height, pos, right, up, forward are equal bit for bit, and
+ *            fov_deg for a fisheye, extent for an orthographic sensor. REPROJECT through the projection of prev otherwise.
+ * The scene is at rest: there is no motion table and no history_cap; the moments form is that of "Variance-guided filtering" with an
+ * all-STATIC table, and for equal sensors both forms give the bits the camera forms give for equal cameras on the same arrays.
+ * RTU_ERR_ARG: as for rtu_temporal_accumulate[_moments][_device]; a sensor outside the rules of "Sensors"; cur of another size than the
+ * desc. With hist_prev == NULL prev may be NULL.
+ *   rtu_temporal_accumulate_sensor, _sensor_moments                 pure host code: the executable statement.
+ *   rtu_temporal_accumulate_sensor_device, _sensor_moments_device   the same bits from device memory (one lane per pixel),
+ *                                                                   asynchronous on hip_stream; allocate nothing, need no scene.
+ * SENSOR FRAMES of a session from rtu_temporal_begin (with or without RTU_TEMPORAL_DENOISE) or rtu_temporal_begin_variance. Frame k of
+ * a recipe S / P sensor (samples = S >= 1, gather_bounces 0 or 4, the desc's size):
+ *   1. the rays and keys of sample k mod S (rtu_sensor_rays_device),
+ *   2. shaded by rtu_shade_rays_sampled_device / _paths_device with eye = pos and the sensor's max_bounce and flags, under the capacity
+ *      repair of rtu_temporal_frame_device (SYNCHRONOUS on hip_stream),
+ *   3. the guides: rtu_ray_features_device (flags 0) of the pixel-centre rays — the rays of the same sensor with samples = 0,
+ *   4. the accumulator above, plain or moments, against the previous frame's sensor and history, into d_rgbz,
+ *   5. the filter of the session, unchanged: rtu_denoise_device, or rtu_variance_device and rtu_denoise_variance_device. THE FILTER DOES
+ *      NOT WRAP at a panorama's seam: the first and the last column are image borders to it.
+ * A session takes camera frames and sensor frames in any order: a frame whose predecessor was of the other kind, or a sensor of
+ * another model, takes no history (lookup NONE), and k goes on counting. Everything "Temporal accumulation" says of sessions holds: a
+ * refused call leaves the session as it was, a scene change starts over, no allocation after the first frame, one stream per context;
+ * rtu_temporal_history_device and rtu_temporal_reset work as before. Steered, gradient (enabled != 0), sparse and hole sessions refuse
+ * a sensor with RTU_ERR_ARG — their ray generators go through the camera's sample rays — and go on as if the call had not been made.
+ * The scene is at rest between sensor frames: there is no sensor form of rtu_temporal_frame_moved.
+ * RTU_ERR_ARG: recipe W (samples 0), a sensor outside the rules of "Sensors" (so more than 2^25 pixels), a sensor of another size than
+ * the session, a NULL or misaligned d_rgbz; RTU_ERR_NO_SCENE. */
+int  rtu_sensor_project(const RtuSensorDesc* sensor, const float* points_xyz, size_t n, float* fxfy_out, uint8_t* ok_out);
+int  rtu_temporal_accumulate_sensor(const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur, const float* h_rgbz,
+                                    const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out);
+int  rtu_temporal_accumulate_sensor_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur,
+                                           const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                           void* d_rgbz_out, void* hip_stream);
+int  rtu_temporal_accumulate_sensor_moments(const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur, const float* h_rgbz,
+                                            const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out,
+                                            float* h_rgbz_out);
+int  rtu_temporal_accumulate_sensor_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur,
+                                                   const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev,
+                                                   void* d_hist_out, void* d_rgbz_out, void* hip_stream);
+int  rtu_temporal_sensor_frame_device(RtuTemporal* t, const RtuSensorDesc* sensor, void* d_rgbz, void* hip_stream);
+int  rtu_temporal_sensor_frame(RtuTemporal* t, const RtuSensorDesc* sensor, float* h_rgbz);
+
 /* Cancellation (StopRender(), main.cpp:70-72): a word the caller may set non-zero at any time; the context reads it between the
  * launch sequences of a sampled frame (recipes S / P: one sequence per batch of samples — a 64-sample 1080p frame is hundreds
  * of milliseconds) and returns RTU_ERR_CANCELLED from the render call. NULL: none. The word is read with a relaxed atomic load; a writer

@@ -179,7 +179,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_temporal_accumulate_sparse_device", "rtu_sparse_fill", "rtu_sparse_fill_device", "rtu_temporal_begin_sparse",
                "rtu_temporal_holes",
                "rtu_hole_defaults", "rtu_hole_allocation", "rtu_hole_allocation_device", "rtu_hole_fold", "rtu_hole_fold_device",
-               "rtu_temporal_begin_sparse_holes", "rtu_temporal_hole_rays"]
+               "rtu_temporal_begin_sparse_holes", "rtu_temporal_hole_rays",
+               "rtu_sensor_project", "rtu_temporal_accumulate_sensor", "rtu_temporal_accumulate_sensor_device",
+               "rtu_temporal_accumulate_sensor_moments", "rtu_temporal_accumulate_sensor_moments_device",
+               "rtu_temporal_sensor_frame_device", "rtu_temporal_sensor_frame"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -1134,6 +1137,44 @@ def sensor_rays(desc, sample=0, row0=0, nrows=None):
     return rays, keys
 
 
+# temporal accumulation for sensors (include/rtu_render.h, "Temporal accumulation for sensors")
+_SD = ctypes.POINTER(RtuSensorDesc)
+_sig(hip, "rtu_sensor_project", _I, _SD, _P, ctypes.c_size_t, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_sensor", _I, ctypes.POINTER(RtuTemporalDesc), _SD, _SD, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_sensor_moments", _I, ctypes.POINTER(RtuTemporalDesc), _SD, _SD, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_sensor_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), _SD, _SD, _P, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_accumulate_sensor_moments_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), _SD, _SD, _P, _P, _P, _P, _P, _P, _P)
+_sig(hip, "rtu_temporal_sensor_frame_device", _I, _P, _SD, _P, _P)
+_sig(hip, "rtu_temporal_sensor_frame", _I, _P, _SD, _P)
+
+
+def sensor_project(desc, points):
+    """rtu_sensor_project (pure host code, the specification of a sensor's projection): the image coordinates of world points float32
+    [n, 3] in sensor `desc` -> (fxfy float32 [n, 2], ok bool [n]); pixel (x, y) has its centre at (x, y), a point without an image
+    (behind an orthographic sensor, outside a fisheye's field, at a panorama's pole) has ok False and (0, 0)."""
+    import numpy as np
+    points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = len(points)
+    fxfy, ok = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+    rc = hip.rtu_sensor_project(ctypes.byref(desc), points.ctypes.data if n else None, n, fxfy.ctypes.data if n else None, ok.ctypes.data if n else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_sensor_project: a sensor descriptor out of its rules")
+    return fxfy, ok.astype(bool)
+
+
+def temporal_accumulate_sensor(prev, cur, rgbz, hits, albedo, hist_prev=None, desc=None, moments=False):
+    """rtu_temporal_accumulate_sensor / _sensor_moments (pure host code): temporal_accumulate() with RtuSensorDesc prev and cur in place
+    of the cameras; the lookup goes through sensor_project() of prev, and an equirectangular sensor's columns wrap. moments: the
+    histories are float32 [4, H, W, 4] as for temporal_accumulate_moments(), without a motion table (the scene is at rest).
+    -> (accumulated rgbz [H, W, 4], the new history)."""
+    call = hip.rtu_temporal_accumulate_sensor_moments if moments else hip.rtu_temporal_accumulate_sensor
+    rc, out, hist = _temporal_accumulate(4 if moments else 3, call, prev, cur, rgbz, hits, albedo, hist_prev, desc)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate_sensor: a descriptor outside its rules, a sensor outside its rules or of another size, "
+                           "or a history without its sensor")
+    return out, hist
+
+
 def shade_desc(eye=(0.0, 0.0, 0.0), max_bounce=5, reference_walk=False):
     """An RtuShadeDesc: rtu_shade_defaults, then the eye, the depth and the counting variant's flag."""
     d = RtuShadeDesc()
@@ -1740,6 +1781,18 @@ class Temporal:
         motion = _as_motion(motion)
         self._check(hip.rtu_temporal_frame_moved_device(self._h, ctypes.byref(frame), motion.ctypes.data, len(motion), int(history_cap), d_rgbz, stream))
 
+    def sensor_frame(self, desc):
+        """The next frame of the session through the sensor `desc` (an RtuSensorDesc of recipe S / P and of the session's size; a plain,
+        denoise or variance session): rgbz float32 [H, W, 4] (synchronous). Camera and sensor frames may alternate: a frame after one
+        of the other kind, or of another sensor model, takes no history."""
+        import numpy as np
+        out = np.empty((self.desc.height, self.desc.width, 4), np.float32)
+        self._check(hip.rtu_temporal_sensor_frame(self._h, ctypes.byref(desc), out.ctypes.data))
+        return out
+
+    def sensor_frame_device(self, desc, d_rgbz, stream=None):
+        self._check(hip.rtu_temporal_sensor_frame_device(self._h, ctypes.byref(desc), d_rgbz, stream))
+
     def history(self):
         """The history length of every pixel after the last frame, float32 [H, W] (0 before the first)."""
         import numpy as np
@@ -2008,6 +2061,14 @@ class Context:
         self._check(hip.rtu_temporal_accumulate_moments_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None,
                                                                ctypes.byref(cur_cam), d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr,
                                                                d_rgbz_out_ptr, d_motion_ptr, n_nodes, int(history_cap), stream))
+
+    def temporal_accumulate_sensor_device(self, desc, prev, cur, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr, d_rgbz_out_ptr,
+                                          moments=False, stream=None):
+        """rtu_temporal_accumulate_sensor_device / _sensor_moments_device: temporal_accumulate_sensor() on device memory, the same bits
+        (k_temporal_sensor); the histories are three planes, with moments four. d_rgbz_out_ptr may be d_rgbz_ptr."""
+        call = hip.rtu_temporal_accumulate_sensor_moments_device if moments else hip.rtu_temporal_accumulate_sensor_device
+        self._check(call(self._h, ctypes.byref(desc), ctypes.byref(prev) if prev is not None else None, ctypes.byref(cur), d_rgbz_ptr, d_hits_ptr,
+                         d_albedo_ptr, d_hist_prev_ptr, d_hist_out_ptr, d_rgbz_out_ptr, stream))
 
     def variance_device(self, desc, d_hist_ptr, d_hits_ptr, d_v_ptr, stream=None):
         """rtu_variance_device: variance() on device memory, desc.width * desc.height floats to d_v_ptr."""

@@ -1841,6 +1841,8 @@ struct RtuTemporal {
     bool            has_hist = false; // hist[cur] and prev_cam are those of the previous frame
     int             cur = 0;
     RtuFrameDesc    prev_cam{};
+    bool            prev_is_sensor = false;  // the previous frame was a sensor frame (rtu_temporal_sensor_frame): prev_sensor, not prev_cam, is its
+    RtuSensorDesc   prev_sensor{};           // ... and a camera frame that follows takes no history, as a sensor frame after a camera frame
     DevBuf<float4>   rays, img, hits, albedo, hist[2];
     DevBuf<uint32_t> keys;
     DevBuf<RtuNodeMotion>    motion;      // rtu_temporal_frame_moved: the table of the frame, grown at the first frame that needs it ...
@@ -4940,7 +4942,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     // another scene generation: a moved frame adopts it; a plain frame starts over — moved geometry or lights: what was accumulated
     // shows another scene. Both take effect at the commit.
     const bool start_over = !moved && t->scene_gen != ctx->scene_gen;
-    const bool has_hist = t->has_hist && !start_over;
+    const bool has_hist = t->has_hist && !start_over && !t->prev_is_sensor;  // (a sensor's history is of another image: none is taken, k goes on)
     const int  k = start_over ? 0 : t->k;
     int rc;
     uint32_t hole_total = 0;
@@ -5033,6 +5035,7 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     t->cur ^= 1;
     t->has_hist = true;
     t->prev_cam = *frame;
+    t->prev_is_sensor = false;
     t->k = k + 1;
     t->hl_total = hole_total;
     if (t->variance) {
@@ -5316,6 +5319,156 @@ int rtu_render_sensor(RtuContext* ctx, const RtuSensorDesc* d, float* h_rgbz) {
     RTU_HIP(ctx, ctx->sn_img.grow(pixels));
     if ((rc = rtu_render_sensor_device(ctx, d, ctx->sn_img.get(), ctx->stream)) != RTU_OK) return rc;
     RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->sn_img.get(), sizeof(float4) * pixels, hipMemcpyDeviceToHost));
+    return RTU_OK;
+}
+
+// ---- temporal accumulation for sensors (rtu_sensor.h sensor_project, rtu_temporal.hip k_temporal_sensor): the projection, the accumulator
+// on device memory, and the sensor frames of a session ------------------------------------------------------------------------------
+int rtu_sensor_check_desc(const RtuSensorDesc* d) { return check_sensor(nullptr, d); }
+
+// the specification of a sensor's projection: sensor_project of rtu_sensor.h on the host (this file is compiled with -ffp-contract=off)
+int rtu_sensor_project(const RtuSensorDesc* d, const float* points_xyz, size_t n, float* fxfy_out, uint8_t* ok_out) {
+    if (check_sensor(nullptr, d) != RTU_OK) return RTU_ERR_ARG;
+    if (n && (!points_xyz || !fxfy_out || !ok_out)) return RTU_ERR_ARG;
+    for (size_t i = 0; i < n; i++) {
+        const f3 P = mk3(points_xyz[3 * i], points_xyz[3 * i + 1], points_xyz[3 * i + 2]);
+        float fx = 0.0f, fy = 0.0f;
+        bool ok;
+        switch (d->model) {
+        case RTU_SENSOR_EQUIRECT: ok = sensor_project<RTU_SENSOR_EQUIRECT>(*d, P, fx, fy); break;
+        case RTU_SENSOR_FISHEYE: ok = sensor_project<RTU_SENSOR_FISHEYE>(*d, P, fx, fy); break;
+        default: ok = sensor_project<RTU_SENSOR_ORTHO>(*d, P, fx, fy); break;
+        }
+        fxfy_out[2 * i] = ok ? fx : 0.0f;
+        fxfy_out[2 * i + 1] = ok ? fy : 0.0f;
+        ok_out[i] = ok ? 1 : 0;
+    }
+    return RTU_OK;
+}
+
+// the two _device forms: `moments` — histories of four planes. The order of the checks is that of temporal_device_args.
+static int temporal_sensor_device(RtuContext* ctx, bool moments, const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur,
+                                  const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out, void* d_rgbz_out,
+                                  void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
+    if (!cur || (d_hist_prev && !prev)) return fail(ctx, RTU_ERR_ARG, "temporal: a sensor is NULL");
+    if (!prev) prev = cur;
+    int rc = check_sensor(ctx, cur);
+    if (rc == RTU_OK) rc = check_sensor(ctx, prev);
+    if (rc != RTU_OK) return rc;
+    if (cur->width != desc->width || cur->height != desc->height) return fail(ctx, RTU_ERR_ARG, "temporal: the sensor must have the desc's width and height");
+    if (!d_rgbz || !d_hits || !d_albedo || !d_hist_out || !d_rgbz_out) return fail(ctx, RTU_ERR_ARG, "temporal: a device pointer is NULL");
+    if (misaligned(d_rgbz) || misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_hist_prev) || misaligned(d_hist_out) || misaligned(d_rgbz_out))
+        return fail(ctx, RTU_ERR_ARG, "temporal: device buffers must be 16-byte aligned");
+    if (d_hist_prev) {
+        const uintptr_t a = (uintptr_t)d_hist_prev, b = (uintptr_t)d_hist_out,
+                        bytes = (uintptr_t)(moments ? 64 : 48) * (uintptr_t)desc->width * (uintptr_t)desc->height;
+        if (a < b + bytes && b < a + bytes) return fail(ctx, RTU_ERR_ARG, "temporal: hist_out overlaps hist_prev");
+    }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const TpParams p = tp_sensor_setup(*desc, *prev, *cur, d_hist_prev != nullptr);
+    const hipError_t e = (hipError_t)rtu_launch_temporal_sensor(p, *prev, moments, (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo,
+                                                                p.lookup != TP_LOOKUP_NONE ? (const float4*)d_hist_prev : nullptr, (float4*)d_hist_out,
+                                                                (float4*)d_rgbz_out, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate_sensor_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur, const void* d_rgbz,
+                                          const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out, void* d_rgbz_out,
+                                          void* hip_stream) {
+    return temporal_sensor_device(ctx, false, desc, prev, cur, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, hip_stream);
+}
+
+int rtu_temporal_accumulate_sensor_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur,
+                                                  const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_hist_prev, void* d_hist_out,
+                                                  void* d_rgbz_out, void* hip_stream) {
+    return temporal_sensor_device(ctx, true, desc, prev, cur, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, hip_stream);
+}
+
+// A sensor frame of a session: temporal_frame with the sensor's rays, guides and accumulator. The scene is at rest: no table.
+int rtu_temporal_sensor_frame_device(RtuTemporal* t, const RtuSensorDesc* sensor, void* d_rgbz, void* hip_stream) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    int rc = check_sensor(ctx, sensor);
+    if (rc != RTU_OK) return rc;
+    if (t->steered || t->gradient || t->sparse_session)
+        return fail(ctx, RTU_ERR_ARG, "a steered, gradient or sparse session takes camera frames only: its ray generators have no sensor form");
+    if (sensor->width != t->desc.width || sensor->height != t->desc.height) return fail(ctx, RTU_ERR_ARG, "the sensor has not the session's width and height");
+    if (sensor->samples < 1) return fail(ctx, RTU_ERR_ARG, "a temporal frame is a recipe S / P frame (samples >= 1)");
+    if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "d_rgbz is NULL");
+    if (misaligned(d_rgbz)) return fail(ctx, RTU_ERR_ARG, "d_rgbz must be 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const bool paths = sensor->gather_bounces != 0;
+    const size_t n = t->pixels;
+    // A REFUSED CALL LEAVES THE SESSION AS IT WAS, as in temporal_frame: copies of the counter and of the history flag until the commit.
+    if (t->variance) {  // what a later camera frame of this session needs: no frame after the first allocates
+        const size_t entries = ctx->shape_nodes.empty() ? 1 : ctx->shape_nodes.size();
+        RTU_HIP(ctx, hipSetDevice(ctx->device));
+        RTU_HIP(ctx, t->motion.grow(entries));
+        RTU_HIP(ctx, t->motion_host.grow(entries));
+    }
+    const bool start_over = t->scene_gen != ctx->scene_gen;
+    // the history of a camera frame, or of a sensor of another model, is of another image: none is taken, k goes on
+    const bool has_hist = t->has_hist && !start_over && t->prev_is_sensor && t->prev_sensor.model == sensor->model;
+    const int  k = start_over ? 0 : t->k;
+    if ((rc = rtu_sensor_rays_device(ctx, sensor, k % sensor->samples, 1, t->rays.get(), t->keys.get(), hip_stream)) != RTU_OK) return rc;
+    RtuShadeDesc sd;
+    rtu_shade_defaults(&sd);
+    memcpy(sd.eye, sensor->pos, sizeof sd.eye);
+    sd.max_bounce = sensor->max_bounce;
+    sd.flags = sensor->flags;
+    RtuFrameDesc f;
+    if ((rc = shade_args(ctx, t->rays.get(), t->img.get(), n, &sd, true, &f, true, t->keys.get(), paths)) != RTU_OK) return rc;
+    if (paths && (rc = paths_chain(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n)) != RTU_OK) return rc;
+    if ((rc = shade_until_fits(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)n, paths,
+                               "recipe P with counters: frame records ran out; run the frame once without RTU_QUERY_REFERENCE_WALK first")) != RTU_OK)
+        return rc;
+    // the guides: the pixel-centre rays — the sensor's rays with samples == 0 — over the sample's rays, which are shaded (the stream was
+    // waited for above)
+    RtuSensorDesc centre = *sensor;
+    centre.samples = 0;
+    centre.gather_bounces = 0;
+    if ((rc = sensor_generate(ctx, &centre, 0, 1, t->rays.get(), nullptr, stream)) != RTU_OK) return rc;
+    if ((rc = rtu_ray_features_device(ctx, t->rays.get(), n, 0, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
+    RtuTemporalDesc td = t->desc;
+    td.flags = 0;
+    rc = temporal_sensor_device(ctx, t->variance, &td, has_hist ? &t->prev_sensor : nullptr, sensor, t->img.get(), t->hits.get(), t->albedo.get(),
+                                has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
+    if (rc != RTU_OK) return rc;
+    // THE COMMIT: nothing behind it refuses
+    t->scene_gen = ctx->scene_gen;
+    t->cur ^= 1;
+    t->has_hist = true;
+    t->prev_sensor = *sensor;
+    t->prev_is_sensor = true;
+    t->k = k + 1;
+    if (t->variance) {
+        if ((rc = rtu_variance_device(ctx, &t->vdesc, t->hist[t->cur].get(), t->hits.get(), t->var.get(), hip_stream)) != RTU_OK) return rc;
+        return rtu_denoise_variance_device(ctx, &t->vdesc, d_rgbz, t->hits.get(), t->albedo.get(), t->var.get(), d_rgbz, hip_stream);  // in place
+    }
+    if (t->desc.flags & RTU_TEMPORAL_DENOISE) {
+        RtuDenoiseDesc dd;
+        rtu_denoise_defaults(&dd);
+        dd.width = t->desc.width;
+        dd.height = t->desc.height;
+        return rtu_denoise_device(ctx, &dd, d_rgbz, t->hits.get(), t->albedo.get(), d_rgbz, hip_stream);  // in place; the history stays unfiltered
+    }
+    return RTU_OK;
+}
+
+int rtu_temporal_sensor_frame(RtuTemporal* t, const RtuSensorDesc* sensor, float* h_rgbz) {
+    if (!t || !t->ctx) return RTU_ERR_ARG;
+    RtuContext* ctx = t->ctx;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "h_rgbz is NULL");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->fb.grow(t->pixels));
+    const int rc = rtu_temporal_sensor_frame_device(t, sensor, ctx->fb.get(), ctx->stream);
+    if (rc != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpyAsync(h_rgbz, ctx->fb.get(), t->pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RTU_OK;
 }
 

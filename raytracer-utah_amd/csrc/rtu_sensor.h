@@ -49,6 +49,88 @@ RTU_HD void sensor_ray(const RtuSensorDesc& d, int x, int y, float ox, float oy,
     }
 }
 
+// ---- the projection of a sensor (include/rtu_render.h, "Temporal accumulation for sensors"): the counterpart of sensor_ray ----------
+// acos of a float in [-1, 1]: binary64 IEEE operations in fdlibm's e_acos sequence, rounded to float — the sequence of portable_acos
+// (rtu_intersect.h, device only: the render kernels' copy stays where it is) and of the oracle, for host and device.
+RTU_HD double sensor_acos_poly(double z) {
+    const double p = z * (1.66666666666666657415e-01 + z * (-3.25565818622400915405e-01 + z * (2.01212532134862925881e-01 +
+                     z * (-4.00555345006794114027e-02 + z * (7.91534994289814532176e-04 + z * 3.47933107596021167570e-05)))));
+    const double q = 1.0 + z * (-2.40339491173441421878e+00 + z * (2.02094576023350569471e+00 + z * (-6.88283971605453293030e-01 + z * 7.70381505559019352791e-02)));
+    return p / q;
+}
+RTU_HD float sensor_acos(float xf) {
+    const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17, pi = 3.14159265358979311600e+00;
+    const double x = (double)xf;
+    const double ax = fabs(x);
+    double r;
+    if (ax >= 1.0) r = x > 0 ? 0.0 : pi;
+    else if (ax < 0.5) r = pio2_hi - (x - (pio2_lo - x * sensor_acos_poly(x * x)));
+    else if (x < 0) {
+        const double z = (1.0 + x) * 0.5, s = sqrt(z);
+        r = pi - 2.0 * (s + (sensor_acos_poly(z) * s - pio2_lo));
+    } else {
+        const double z = (1.0 - x) * 0.5, s = sqrt(z);
+        r = 2.0 * (s + sensor_acos_poly(z) * s);
+    }
+    return (float)r;
+}
+
+// The angle in [0, pi] between the direction (s, k), s >= 0, and the axis k: false unless its length is finite and > 0. acos gets the
+// smaller of the two ratios — at most about 0.71 —, where it is well conditioned in binary32.
+RTU_HD bool sensor_angle(float s, float k, float& ang) {
+    const float L = sqrtf(s * s + k * k);
+    if (!((L - L) == 0.0f && L > 0.0f)) return false;
+    if (fabsf(k) <= s) {
+        ang = sensor_acos(k / L);
+    } else {
+        const float q = sensor_acos(s / L);
+        ang = k > 0.0f ? 1.5707964f - q : 1.5707964f + q;
+    }
+    return true;
+}
+
+// The image coordinates (fx, fy) of world point Pm in sensor `d` (validated by the caller), model MODEL — pixel (x, y) has its centre
+// at (x, y) — or false: the point has none. binary32, one rounding per operation, in the order rtu_render.h states.
+template <int MODEL>
+RTU_HD bool sensor_project(const RtuSensorDesc& d, const f3& Pm, float& fx, float& fy) {
+    const f3 Q = Pm - ld3(d.pos);
+    const float a = dot3(Q, ld3(d.forward)), b = dot3(Q, ld3(d.right)), c = dot3(Q, ld3(d.up));
+    const float W = (float)d.width, H = (float)d.height;
+    if (MODEL == RTU_SENSOR_EQUIRECT) {
+        const float h = sqrtf(a * a + b * b);
+        if (h == 0.0f) return false;  // a pole
+        float pol, th;
+        if (!sensor_angle(h, c, pol) || !sensor_angle(fabsf(b), -a, th)) return false;
+        const float lon = b <= 0.0f ? th : 6.2831855f - th;
+        fx = lon / 6.2831855f * W - 0.5f;
+        fy = pol / 3.1415927f * H - 0.5f;
+        return true;
+    }
+    if (MODEL == RTU_SENSOR_FISHEYE) {
+        const float p = sqrtf(b * b + c * c);
+        if (p == 0.0f) {
+            fx = 0.5f * W - 0.5f;
+            fy = 0.5f * H - 0.5f;
+            return a > 0.0f;
+        }
+        float ang;
+        if (!sensor_angle(p, a, ang)) return false;
+        const float r = ang / (d.fov_deg * 0.008726646f);
+        if (!(r <= 1.0f)) return false;
+        const float R = 0.5f * (float)(d.width < d.height ? d.width : d.height);
+        fx = ((r * (b / p)) * R + 0.5f * W) - 0.5f;
+        fy = ((-(r * (c / p))) * R + 0.5f * H) - 0.5f;
+        return true;
+    }
+    if (!(a > 0.0f)) return false;
+    fx = (b / d.extent[0] + 0.5f) * W - 0.5f;
+    fy = (0.5f - c / d.extent[1]) * H - 0.5f;
+    return true;
+}
+
+// RTU_OK or RTU_ERR_ARG: the rules of RtuSensorDesc (rtu_capi.hip), without a context
+extern "C" int rtu_sensor_check_desc(const RtuSensorDesc* d);
+
 // ---- launch interface (rtu_sensor.hip). Every function is asynchronous on `stream` and returns a hipError_t as int. ----
 #define RTU_SENSOR_LAUNCH_SAMPLES 16  // samples per launch of k_sensor_rays: their pixel offsets travel in the kernel arguments
 struct SensorOffsets {

@@ -3,6 +3,8 @@
 // called by rtu_capi.hip. The three forms — rtu_temporal_accumulate, _motion and _moments, each with its _device form — are the
 // instantiations of one function, tp_pixel<MOVING, MOMENTS>; rtu_temporal_accumulate_gradient ("Temporal gradients") is a fourth,
 // tp_pixel<true, true, true>, and rtu_temporal_accumulate_sparse ("Sparse sessions") a fifth, tp_pixel<true, true, false, true>.
+// rtu_temporal_accumulate_sensor and _sensor_moments ("Temporal accumulation for sensors") are tp_pixel<false, MOMENTS> with another
+// projection, TpSensorProj<MODEL> in place of the pinhole; that projection has the one transcendental function, sensor_acos.
 //
 // A pixel's first-hit point is projected into the previous camera, the history is fetched there with four bilinear taps, each tested
 // for being the same surface, and the new sample is blended in. No transcendental function: the translation units that include this
@@ -15,6 +17,7 @@
 #define RTU_TEMPORAL_H_INCLUDED
 
 #include "rtu_denoise.h"
+#include "rtu_sensor.h"
 
 #include <type_traits>
 
@@ -175,6 +178,49 @@ RTU_HD bool tp_project(const TpParams& P, const f3& Pm, float& fx, float& fy) {
     return tp_finite(s) && s > 0.0f;
 }
 
+// ---- the projection: a compile-time policy of tp_pixel and tp_tap ----------------------------------------------------------------------
+// project(): the previous-image coordinates of a world point, or false; column(): the column a tap at column qx reads (a tap whose
+// column is then outside the image is dropped). TpPinhole, the default, is the camera of TpParams; TpSensorProj<MODEL> is a sensor of
+// "Temporal accumulation for sensors", whose equirectangular columns WRAP: -1 is the last column, width is column 0.
+struct TpPinhole {
+    RTU_HD bool project(const TpParams& P, const f3& Pm, float& fx, float& fy) const { return tp_project(P, Pm, fx, fy); }
+    RTU_HD int  column(const TpParams&, int qx) const { return qx; }
+};
+template <int MODEL>
+struct TpSensorProj {
+    const RtuSensorDesc& prev;  // the PREVIOUS sensor
+    RTU_HD bool project(const TpParams&, const f3& Pm, float& fx, float& fy) const { return sensor_project<MODEL>(prev, Pm, fx, fy); }
+    RTU_HD int  column(const TpParams& P, int qx) const {
+        if (MODEL != RTU_SENSOR_EQUIRECT) return qx;
+        return qx < 0 ? qx + P.width : (qx >= P.width ? qx - P.width : qx);
+    }
+};
+
+inline bool tp_same_sensor(const RtuSensorDesc& a, const RtuSensorDesc& b) {
+    union { float f; uint32_t u; } x, y;
+    if (a.model != b.model || a.width != b.width || a.height != b.height) return false;
+    const auto same = [&](float fa, float fb) { x.f = fa; y.f = fb; return x.u == y.u; };
+    for (int k = 0; k < 3; k++)
+        if (!same(a.pos[k], b.pos[k]) || !same(a.right[k], b.right[k]) || !same(a.up[k], b.up[k]) || !same(a.forward[k], b.forward[k])) return false;
+    if (a.model == RTU_SENSOR_FISHEYE && !same(a.fov_deg, b.fov_deg)) return false;
+    if (a.model == RTU_SENSOR_ORTHO && (!same(a.extent[0], b.extent[0]) || !same(a.extent[1], b.extent[1]))) return false;
+    return true;
+}
+
+// TpParams of the sensor forms: the camera fields stay zero (TpSensorProj reads the previous sensor itself). No lookup without a
+// previous history or between sensors of another model or size.
+inline TpParams tp_sensor_setup(const RtuTemporalDesc& d, const RtuSensorDesc& prev, const RtuSensorDesc& cur, bool has_prev) {
+    TpParams p{};
+    p.width = d.width;
+    p.height = d.height;
+    const bool comparable = has_prev && prev.model == cur.model && prev.width == cur.width && prev.height == cur.height;
+    p.lookup = !comparable ? TP_LOOKUP_NONE : (tp_same_sensor(prev, cur) ? TP_LOOKUP_STATIC : TP_LOOKUP_REPROJECT);
+    p.max_history = (float)d.max_history;
+    p.sigma_plane = d.sigma_plane;
+    p.normal_min = d.normal_min;
+    return p;
+}
+
 // l(e) of a demodulated colour: what the moments are taken of
 RTU_HD float vr_lum(const f3& e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z; }
 
@@ -203,9 +249,10 @@ struct TpSums {
 
 // One tap of pixel p's lookup at pixel (qx, qy) of the previous history h (its planes) with weight w: where it is ACCEPTED, it is added
 // to S. Pp, Np: p's point and normal as they were in the previous scene.
-template <bool MOMENTS>
+template <bool MOMENTS, class PROJ = TpPinhole>
 RTU_HD void tp_tap(const TpParams& P, const float4* const* h, int qx, int qy, float w, const f3& Np, const f3& Pp, uint32_t node, float plane_max,
-                   TpSums& S) {
+                   TpSums& S, const PROJ& proj = PROJ()) {
+    qx = proj.column(P, qx);
     if (qx < 0 || qy < 0 || qx >= P.width || qy >= P.height) return;
     const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
     const float4 Eq = h[0][q], Pq = h[1][q], Nq = h[2][q];
@@ -230,9 +277,10 @@ RTU_HD void tp_tap(const TpParams& P, const float4* const* h, int qx, int qy, fl
 // takes no, one or four taps is its own matter. SPARSE: `owner` — the pixel is the one its block shades this frame and rgbz is that
 // sample; for every other pixel nothing of rgbz reaches an output — and *hole, the pixel's mark in the hole plane (without SPARSE
 // neither is used).
-template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false>
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false, class PROJ = TpPinhole>
 RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT, SPARSE>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
-                     const float4* hit, const float4& albedo, float4& out, float4* o, bool owner = true, uint8_t* hole = nullptr) {
+                     const float4* hit, const float4& albedo, float4& out, float4* o, bool owner = true, uint8_t* hole = nullptr,
+                     const PROJ& proj = PROJ()) {
     static_assert(!GRADIENT || (MOVING && MOMENTS), "the gradient form is a moments form");
     static_assert(!SPARSE || (MOVING && MOMENTS && !GRADIENT), "the sparse form is a moments form");
     const TpParams& P = tp_base(A);
@@ -256,19 +304,19 @@ RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT, SPARSE>& A, bool in_table, c
     f3 e_prev = mk3(0.0f, 0.0f, 0.0f);
     float n_prev = 0.0f, m1_prev = 0.0f, m2_prev = 0.0f;
     if (one_tap) {
-        tp_tap<MOMENTS>(P, h, x, y, 1.0f, Nm, Pm, node.u, plane_max, S);
+        tp_tap<MOMENTS, PROJ>(P, h, x, y, 1.0f, Nm, Pm, node.u, plane_max, S, proj);
     } else if (look) {
         float fx, fy;
         // (a NaN fails; tested before any conversion)
-        if (tp_project(P, Pm, fx, fy) && fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {
+        if (proj.project(P, Pm, fx, fy) && fx >= -1.0f && fx < (float)P.width && fy >= -1.0f && fy < (float)P.height) {
             const float flx = floorf(fx), fly = floorf(fy);
             const int x0 = (int)flx, y0 = (int)fly;
             const float wx = fx - flx, wy = fy - fly;
             const float ux = 1.0f - wx, uy = 1.0f - wy;
-            tp_tap<MOMENTS>(P, h, x0, y0, ux * uy, Nm, Pm, node.u, plane_max, S);
-            tp_tap<MOMENTS>(P, h, x0 + 1, y0, wx * uy, Nm, Pm, node.u, plane_max, S);
-            tp_tap<MOMENTS>(P, h, x0, y0 + 1, ux * wy, Nm, Pm, node.u, plane_max, S);
-            tp_tap<MOMENTS>(P, h, x0 + 1, y0 + 1, wx * wy, Nm, Pm, node.u, plane_max, S);
+            tp_tap<MOMENTS, PROJ>(P, h, x0, y0, ux * uy, Nm, Pm, node.u, plane_max, S, proj);
+            tp_tap<MOMENTS, PROJ>(P, h, x0 + 1, y0, wx * uy, Nm, Pm, node.u, plane_max, S, proj);
+            tp_tap<MOMENTS, PROJ>(P, h, x0, y0 + 1, ux * wy, Nm, Pm, node.u, plane_max, S, proj);
+            tp_tap<MOMENTS, PROJ>(P, h, x0 + 1, y0 + 1, wx * wy, Nm, Pm, node.u, plane_max, S, proj);
         }
     }
     if (S.w > 0.01f) {
@@ -357,6 +405,10 @@ int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, co
 // The sparse form: the moments form whose samples are s.rgbt / s.owner, one per block; s.hole [width * height] is written.
 int rtu_launch_temporal_sparse(const TpSparseParams& s, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
                                float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
+// The sensor forms (k_temporal_sensor<MODEL, MOMENTS>, MODEL = prev.model): p of tp_sensor_setup; the scene is at rest, there is no
+// table. The histories have three planes, with `moments` four.
+int rtu_launch_temporal_sensor(const TpParams& p, const RtuSensorDesc& prev, bool moments, const float4* rgbz, const float4* hits, const float4* albedo,
+                               const float4* hist_prev, float4* hist_out, float4* rgbz_out, hipStream_t stream);
 // n_out[i] = the history length of pixel i (E.w of `hist`), or 0 everywhere with hist == nullptr
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream);
 

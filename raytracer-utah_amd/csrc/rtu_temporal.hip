@@ -20,6 +20,11 @@
 //     SPARSE            in place of the 16-byte load of rgbz one dword load of the owner of the pixel's block — the lanes of a block's
 //                       row share it — and, in the one lane of a block that is the owner, the 16-byte load of the block's sample;
 //                       besides, one byte store of the pixel's mark in the hole plane.
+//   k_temporal_sensor   <MODEL, MOMENTS> ("Temporal accumulation for sensors"): k_temporal without MOVING whose lookup goes through the
+//                       projection of a panoramic, fisheye or orthographic sensor (sensor_project of rtu_sensor.h: a few binary32
+//                       operations and one or two binary64 acos per pixel) in place of the pinhole's; the previous RtuSensorDesc is a
+//                       kernel argument, the model a template parameter. A panorama's tap columns wrap at the seam. Its host forms
+//                       are rtu_temporal_accumulate_sensor and _sensor_moments.
 //   k_temporal_history  one lane per pixel: the history length out of the E plane.
 //   k_motion_vectors    one lane per pixel: its RtuRayHit and its node's entry in, one float4 out.
 // Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
@@ -71,6 +76,36 @@ int launch_temporal(const TpArgs<MOVING, GRADIENT, SPARSE>& a, const float4* rgb
     return (int)hipGetLastError();
 }
 
+// The sensor forms: k_temporal<false, MOMENTS> with the projection of sensor model MODEL in place of the pinhole's. `prev`, the
+// previous sensor, is a kernel argument (scalar loads); the model is a template parameter, no lane branches on it.
+template <int MODEL, bool MOMENTS>
+__global__ void __launch_bounds__(256) k_temporal_sensor(TpParams P, RtuSensorDesc prev, const float4* rgbz, const float4* __restrict__ hits,
+                                                         const float4* __restrict__ albedo, const float4* __restrict__ hist_prev,
+                                                         float4* __restrict__ hist_out, float4* rgbz_out) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= P.width || y >= P.height) return;
+    const size_t n = (size_t)P.width * (size_t)P.height;
+    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
+    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
+    const float4* h[PLANES];
+    for (int i = 0; i < PLANES; i++) h[i] = hist_prev ? hist_prev + i * n : nullptr;
+    float4 out, o[PLANES];
+    tp_pixel<false, MOMENTS, false, false, TpSensorProj<MODEL>>(P, false, tp_motion_identity(), h, x, y, rgbz[p], hit, albedo[p], out, o, true, nullptr,
+                                                                TpSensorProj<MODEL>{prev});
+    rgbz_out[p] = out;
+    for (int i = 0; i < PLANES; i++) hist_out[i * n + p] = o[i];
+}
+
+template <int MODEL>
+int launch_temporal_sensor(const TpParams& p, const RtuSensorDesc& prev, bool moments, const float4* rgbz, const float4* hits, const float4* albedo,
+                           const float4* hist_prev, float4* hist_out, float4* rgbz_out, hipStream_t stream) {
+    const dim3 grid((uint32_t)((p.width + 31) / 32), (uint32_t)((p.height + 7) / 8));
+    if (moments) hipLaunchKernelGGL((k_temporal_sensor<MODEL, true>), grid, dim3(256), 0, stream, p, prev, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out);
+    else hipLaunchKernelGGL((k_temporal_sensor<MODEL, false>), grid, dim3(256), 0, stream, p, prev, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out);
+    return (int)hipGetLastError();
+}
+
 __global__ void __launch_bounds__(256) k_motion_vectors(TpParams P, uint32_t n_nodes, const float4* __restrict__ hits,
                                                         const RtuNodeMotion* __restrict__ motion, float4* __restrict__ mv) {
     const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
@@ -112,6 +147,15 @@ int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, co
 int rtu_launch_temporal_sparse(const TpSparseParams& s, const float4* hits, const float4* albedo, const float4* hist_prev, float4* hist_out,
                                float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
     return launch_temporal<true, true, false, true>(s, nullptr, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
+}
+
+int rtu_launch_temporal_sensor(const TpParams& p, const RtuSensorDesc& prev, bool moments, const float4* rgbz, const float4* hits, const float4* albedo,
+                               const float4* hist_prev, float4* hist_out, float4* rgbz_out, hipStream_t stream) {
+    switch (prev.model) {
+    case RTU_SENSOR_EQUIRECT: return launch_temporal_sensor<RTU_SENSOR_EQUIRECT>(p, prev, moments, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, stream);
+    case RTU_SENSOR_FISHEYE: return launch_temporal_sensor<RTU_SENSOR_FISHEYE>(p, prev, moments, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, stream);
+    default: return launch_temporal_sensor<RTU_SENSOR_ORTHO>(p, prev, moments, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, stream);
+    }
 }
 
 int rtu_launch_temporal_history(const float4* hist, float* n_out, size_t pixels, hipStream_t stream) {
@@ -219,7 +263,68 @@ static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev
     return RTU_OK;
 }
 
+// the host loop of the sensor forms for one model: tp_pixel<false, MOMENTS> with that model's projection
+template <int MODEL, bool MOMENTS>
+static void accumulate_sensor_pixels(const TpParams& A, const RtuSensorDesc& prev, const float* h_rgbz, const RtuRayHit* h_hits, const float* h_albedo,
+                                     const float4* const* hp, float* h_hist_out, float* h_rgbz_out) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    const size_t n = (size_t)A.width * (size_t)A.height;
+    const TpSensorProj<MODEL> proj{prev};
+    for (int y = 0; y < A.height; y++)
+        for (int x = 0; x < A.width; x++) {
+            const size_t p = (size_t)y * (size_t)A.width + (size_t)x;
+            const float* h = reinterpret_cast<const float*>(h_hits + p);
+            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
+            float4 out, o[PLANES];
+            tp_pixel<false, MOMENTS, false, false, TpSensorProj<MODEL>>(A, false, tp_motion_identity(), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o,
+                                                                        true, nullptr, proj);
+            st4(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
+            for (int i = 0; i < PLANES; i++) st4(h_hist_out, i * n + p, o[i]);
+        }
+}
+
+// the host forms for sensors: the histories have three planes, with MOMENTS four
+template <bool MOMENTS>
+static int accumulate_sensor_host(const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur, const float* h_rgbz, const RtuRayHit* h_hits,
+                                  const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur || !h_rgbz || !h_hits || !h_albedo || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
+    if (h_hist_prev && !prev) return RTU_ERR_ARG;
+    if (!prev) prev = cur;
+    if (rtu_sensor_check_desc(cur) != RTU_OK || rtu_sensor_check_desc(prev) != RTU_OK) return RTU_ERR_ARG;
+    if (cur->width != desc->width || cur->height != desc->height) return RTU_ERR_ARG;
+    const size_t n = (size_t)desc->width * (size_t)desc->height;
+    if (h_hist_prev) {  // taps read anywhere in the previous history
+        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 16 * PLANES * n;
+        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
+    }
+    const TpParams A = tp_sensor_setup(*desc, *prev, *cur, h_hist_prev != nullptr);
+    std::vector<float4> planes;  // (the planes as float4: the caller's floats need not be 16-byte aligned)
+    const float4* hp[PLANES] = {};
+    if (A.lookup != TP_LOOKUP_NONE) {  // (else the previous history may be of another size, and is not read)
+        planes.resize(PLANES * n);
+        for (size_t i = 0; i < PLANES * n; i++) planes[i] = f4(h_hist_prev, i);
+        for (int i = 0; i < PLANES; i++) hp[i] = planes.data() + i * n;
+    }
+    switch (prev->model) {
+    case RTU_SENSOR_EQUIRECT: accumulate_sensor_pixels<RTU_SENSOR_EQUIRECT, MOMENTS>(A, *prev, h_rgbz, h_hits, h_albedo, hp, h_hist_out, h_rgbz_out); break;
+    case RTU_SENSOR_FISHEYE: accumulate_sensor_pixels<RTU_SENSOR_FISHEYE, MOMENTS>(A, *prev, h_rgbz, h_hits, h_albedo, hp, h_hist_out, h_rgbz_out); break;
+    default: accumulate_sensor_pixels<RTU_SENSOR_ORTHO, MOMENTS>(A, *prev, h_rgbz, h_hits, h_albedo, hp, h_hist_out, h_rgbz_out); break;
+    }
+    return RTU_OK;
+}
+
 extern "C" {
+
+int rtu_temporal_accumulate_sensor(const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur, const float* h_rgbz, const RtuRayHit* h_hits,
+                                   const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out) {
+    return accumulate_sensor_host<false>(desc, prev, cur, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out);
+}
+
+int rtu_temporal_accumulate_sensor_moments(const RtuTemporalDesc* desc, const RtuSensorDesc* prev, const RtuSensorDesc* cur, const float* h_rgbz,
+                                           const RtuRayHit* h_hits, const float* h_albedo, const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out) {
+    return accumulate_sensor_host<true>(desc, prev, cur, h_rgbz, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out);
+}
 
 int rtu_temporal_defaults(RtuTemporalDesc* out) {
     if (!out) return RTU_ERR_ARG;
