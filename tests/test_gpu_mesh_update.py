@@ -67,17 +67,20 @@ def test_structures_equal_the_host_restatement(pkg, golden, tmp_path, tag):
 
 # ---- 4. images, recipe W ----------------------------------------------------------------------------------------------------------
 
-def check_update_against_upload_and_oracle(pkg, orc, a, b, now, what, shards=True):
+def check_update_against_upload_and_oracle(pkg, orc, a, b, now, what, shards=True, rel_tol=None):
     """`a` holds the updated scene, `b` uploads `now` afresh: the same image bit for bit, the project's bars against the oracle, the
-    counting variant with the oracle's counters, three shards."""
-    from test_gpu_parity import check_against
+    counting variant with the oracle's counters, three shards. rel_tol: the bar of the linear colours, check_against's own if None."""
+    from test_gpu_parity import RGB_REL_TOL, check_against
     b.upload(now)
     ga, _ = render(pkg, a, now)
     gb, _ = render(pkg, b, now)
     assert same_bits(ga, gb), what + ": the updated context renders another image than a fresh upload"
     W, H = now.desc.camera.img_width, now.desc.camera.img_height
     cpu, cstats = orc.render(now, W, H, threads=8)
-    check_against(ga, cpu, orc)
+    with np.errstate(invalid="ignore"):
+        rel = np.abs(ga[..., :3].astype(np.float64) - cpu[..., :3]) / np.maximum(np.abs(cpu[..., :3].astype(np.float64)), 1e-3)
+    print("%s: linear RGB differs by at most %.3g of max(|value|, 1e-3)" % (what, np.nanmax(rel) if np.isfinite(rel).any() else 0.0))
+    check_against(ga, cpu, orc, rel_tol=RGB_REL_TOL if rel_tol is None else rel_tol)
     cnt, gstats = render(pkg, a, now, stats=True)
     assert same_bits(cnt, ga), what + ": fast and counting variants differ"
     assert gstats == cstats, what + ": counters differ from the oracle's"

@@ -13,7 +13,7 @@ occlusion byte equal; the radiance with t bit-exact, colours within the project'
 import numpy as np
 import pytest
 
-from test_gpu_parity import check_against
+from test_gpu_parity import RGB_REL_TOL, check_against
 from test_gpu_ray_query import bits, nodes, same_hits
 from test_oracle_rays import (A1_BATCH, BIG, PROBES, axis_scene, family_a1, family_a2, family_a3, family_b, family_c, family_d,
                               family_e, frame_of, make_rays, valid)
@@ -39,9 +39,10 @@ def ulp_distance(a, b):
     return int(d.max()) if d.size else 0
 
 
-def check_batch(pkg, orc, ctx, scene, rays, eye, label, max_bounce=5):
+def check_batch(pkg, orc, ctx, scene, rays, eye, label, max_bounce=5, rel_tol=RGB_REL_TOL):
     """One batch (the scene is uploaded) against the oracle in all three forms and both walks. Rays the header calls invalid are
-    not given to the oracle: they must come back flagged, as a miss, not occluded, sixteen zero bytes. Returns the hit mask."""
+    not given to the oracle: they must come back flagged, as a miss, not occluded, sixteen zero bytes. rel_tol: the bar of the linear
+    colours (check_against). Returns the hit mask."""
     assert 0 < rays.size <= MAX_CALL
     ok = valid(rays)
     n_ok = int(ok.sum())
@@ -80,7 +81,10 @@ def check_batch(pkg, orc, ctx, scene, rays, eye, label, max_bounce=5):
     assert tbad == 0
     assert np.array_equal(bits(out[:, 3]), bits(got["t"] * ok))  # (an invalid ray: t = 0)
     assert not out[~ok].view(np.uint8).any(), "an invalid ray must give sixteen zero bytes"
-    check_against(out.reshape(1, -1, 4), cpu.reshape(1, -1, 4), orc)
+    with np.errstate(invalid="ignore"):
+        rel = np.abs(out[:, :3].astype(np.float64) - cpu[:, :3]) / np.maximum(np.abs(cpu[:, :3].astype(np.float64)), 1e-3)
+    print("%s: linear RGB differs by at most %.3g of max(|value|, 1e-3)" % (label, np.nanmax(rel) if np.isfinite(rel).any() else 0.0))
+    check_against(out.reshape(1, -1, 4), cpu.reshape(1, -1, 4), orc, rel_tol=rel_tol)
     ref, stats = ctx.shade_rays(rays, eye, max_bounce=max_bounce, reference_walk=True, stats=True)
     assert np.array_equal(ref.view(np.uint8), out.view(np.uint8)), "the counting variant's radiance differs from the fast variant's"
     assert stats == cstats, "counters differ from the oracle's: %s vs %s" % (stats, cstats)

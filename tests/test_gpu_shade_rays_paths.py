@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from test_gpu_ray_query import BIG, bits, set_camera
-from test_gpu_shade_rays_sampled import against_oracle, environment_of, eye_of, families, same_bytes, scrambled
+from test_gpu_shade_rays_sampled import against_oracle, check, environment_of, eye_of, families, same_bytes, scrambled
 from test_mesh_update_host import clone
 
 pytestmark = pytest.mark.gpu
@@ -57,8 +57,9 @@ def cam(pkg, golden, ctx):
     return get
 
 
-def equals_the_render_and_the_oracle(pkg, orc, ctx, c, what, max_bounce=5):
-    """Item 1 of the contract for one sample set (the scene is uploaded): (hit rays per sample, pixels whose samples all hit)."""
+def equals_the_render_and_the_oracle(pkg, orc, ctx, c, what, max_bounce=5, check=check):
+    """Item 1 of the contract for one sample set (the scene is uploaded): (hit rays per sample, pixels whose samples all hit). check: the
+    colour bar against the oracle (against_oracle of tests/test_gpu_shade_rays_sampled.py)."""
     hits = []
     acc = np.zeros((c.W * c.H, 3), np.float32)
     all_hit = np.ones(c.W * c.H, bool)
@@ -74,7 +75,7 @@ def equals_the_render_and_the_oracle(pkg, orc, ctx, c, what, max_bounce=5):
         print("%s sample %d: %d rays, %d hit; t differs from the render's at %d, from the oracle's at %d; rgb from the render's at %d hit rays; "
               "largest linear difference from the oracle %.3g" % (what, k, len(out), int(hit.sum()), tbad, obad, rbad, d.max() if d.size else 0.0))
         assert tbad == 0 and rbad == 0 and obad == 0
-        assert np.array_equal(against_oracle(out, cpu, orc, c.spp, "%s sample %d" % (what, k)), hit)
+        assert np.array_equal(against_oracle(out, cpu, orc, c.spp, "%s sample %d" % (what, k), check=check), hit)
         miss = ~hit
         if miss.any():
             assert same_bytes(out[miss, :3], environment_of(pkg, ctx, c.scene, c.rays[k]["dir"][miss]))

@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Extended soak of the fast variant against the counting variant on the random scenes of tests/test_gpu_fuzz.py (more seeds than
 the test suite affords): both stage-2 forms, a ragged resolution, three shards, a batch of three turned cameras. Prints the seeds
-that differ. usage: python tools/soak_fuzz.py FIRST_SEED LAST_SEED"""
-import math, os, random, sys, tempfile, pathlib
+that differ. usage: python tools/soak_fuzz.py FIRST_SEED LAST_SEED
+
+SOAK_MODE=rays: the ray families of tests/test_fuzz_host.py (built from the device's own closest hits: no oracle) through the closest-hit,
+occlusion and radiance entries, fast walk against reference walk. SOAK_MODE=update: the edit script and, where a scene has two meshes,
+the chain of deformations of that file, an updated context against one that uploads each scene afresh, lists and structures against
+the host builders."""
+import os, random, sys, tempfile, pathlib
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -13,24 +18,7 @@ pkg = g.load_package()
 spec = importlib.util.spec_from_file_location("fz", os.path.join(REPO, "tests", "test_gpu_fuzz.py"))
 fz = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(fz)
-d = pathlib.Path(tempfile.mkdtemp())
-
-
-def torus(u, v):
-    a, b = 2 * math.pi * u, 2 * math.pi * v
-    return ((2 + 0.7 * math.cos(b)) * math.cos(a), (2 + 0.7 * math.cos(b)) * math.sin(a), 0.7 * math.sin(b))
-
-
-def blob(u, v):
-    a, b = 2 * math.pi * u, math.pi * (v - 0.5)
-    r = 1.5 + 0.3 * math.sin(5 * a) * math.cos(3 * b)
-    return (r * math.cos(b) * math.cos(a), r * math.cos(b) * math.sin(a), r * math.sin(b))
-
-
-fz._write_uv_mesh(d / "torus.obj", 24, 10, torus)
-fz._write_uv_mesh(d / "blob.obj", 20, 10, blob)
-rnd0 = random.Random(1)
-(d / "noise.ppm").write_bytes(b"P6\n16 16\n255\n" + bytes(rnd0.randrange(256) for _ in range(16 * 16 * 3)))
+d = fz.write_assets(pathlib.Path(tempfile.mkdtemp()))
 first, last = int(sys.argv[1]), int(sys.argv[2])
 only = [int(v) for v in os.environ.get("SOAK_SEEDS", "").split(",") if v]
 dbg = int(os.environ.get("SOAK_DBG", "0"))
@@ -46,6 +34,86 @@ def same(a, b, what, seed):
         print("  seed %d: %s differs at %d pixels (%d in z), first %s: %s vs %s" % (seed, what, len(diff), zdiff, diff[0], a[tuple(diff[0])], b[tuple(diff[0])]), flush=True)
     return eq
 
+
+def soak_rays(seed):
+    """Fast walk against reference walk on R1-R4 of one seed: the bytes of all three entries."""
+    scene = fh.w_scene(pkg, d, seed)
+    ctx.upload(scene)
+    eye, ok = fh.eye_of(scene), True
+    for name, rays in fh.ray_families(pkg, None, scene, seed, trace=ctx.trace_rays):
+        for what, call in (("closest hits", lambda ref: ctx.trace_rays(rays, reference_walk=ref)), ("occlusion", lambda ref: ctx.occluded(rays, reference_walk=ref)),
+                           ("radiance", lambda ref: ctx.shade_rays(rays, eye, reference_walk=ref)[0])):
+            fast, ref = np.ascontiguousarray(call(False)), np.ascontiguousarray(call(True))
+            if not np.array_equal(fast.view(np.uint8), ref.view(np.uint8)):
+                rows = np.argwhere((fast.view(np.uint8).reshape(rays.size, -1) != ref.view(np.uint8).reshape(rays.size, -1)).any(axis=1))
+                print("  seed %d: %s, %s differ at %d rays, first %d" % (seed, name, what, len(rows), rows[0, 0]), flush=True)
+                ok = False
+    return ok
+
+
+def soak_update(seed, other):
+    """The edit script and the chain of deformations of one seed: `ctx` follows by updates, `other` uploads afresh."""
+    import test_gpu_scene_update as su
+    import test_mesh_update_host as mh
+    scene = fh.w_scene(pkg, d, seed)
+    ctx.upload(scene)
+    ok = True
+
+    def images_agree(now, what):
+        fine = True
+        for stats in (True, False):
+            fr = pkg.frame_setup(now.desc.camera, W, H, collect_stats=stats)
+            fine &= same(ctx.render(fr, stats=stats)[0], other.render(fr, stats=stats)[0], "%s, %s variant" % (what, "counting" if stats else "fast"), seed)
+        try:
+            su.assert_lists_equal(pkg, ctx, now, what)
+        except AssertionError as e:
+            print("  seed %d: %s" % (seed, e), flush=True)
+            fine = False
+        return fine
+    for step, now in enumerate(fh.edit_script(pkg, scene, seed)):
+        ctx.update(now)
+        other.upload(now)
+        ok &= images_agree(now, "edit step %d" % step)
+    if scene.desc.n_meshes == 2:
+        ctx.upload(scene)
+        for now, ids, name in fh.mesh_script(pkg, scene):
+            ctx.update_meshes(now, ids)
+            other.upload(now)
+            ok &= images_agree(now, name)
+            try:
+                for m in (0, 1):
+                    mh.assert_same_structures(ctx.mesh_arrays(m), pkg.host_mesh(scene, m, now), "%s, mesh %d" % (name, m))
+            except AssertionError as e:
+                print("  seed %d: %s" % (seed, e), flush=True)
+                ok = False
+    return ok
+
+
+mode = os.environ.get("SOAK_MODE", "")
+if mode in ("rays", "update"):
+    import test_fuzz_host as fh
+    other = pkg.Context(0) if mode == "update" else None
+    refused = []
+    for seed in (only or range(first, last)):
+        try:
+            ok = soak_rays(seed) if mode == "rays" else soak_update(seed, other)
+        except pkg.RtuError as e:  # a scene or a deformation beyond a device-path limit: refused, nothing to compare
+            if e.code != pkg.RTU_ERR_UNSUPPORTED:
+                raise
+            refused.append(seed)
+            continue
+        if not ok:
+            bad.append(seed)
+            print("seed %d DIFFERS" % seed, flush=True)
+        if seed % 25 == 0:
+            print("... seed %d" % seed, flush=True)
+    print("mode %s, seeds %d..%d: %d differ %s; %d refused as unsupported %s" % (mode, first, last - 1, len(bad), bad, len(refused), refused))
+    if other is not None:
+        other.close()
+    ctx.close()
+    sys.exit(0)
+elif mode:
+    sys.exit("SOAK_MODE must be rays or update")
 
 for seed in (only or range(first, last)):
     rnd = random.Random(1000 + seed)
