@@ -600,6 +600,41 @@ int  rtu_render_sensor_device(RtuContext* ctx, const RtuSensorDesc* sensor, void
  * since the previous call: {k_sensor_rays, k_sensor_accumulate, the renders}; they are reset. The images do not change. */
 int  rtu_debug_sensor_timing(RtuContext* ctx, int on, float* ms_out3);
 
+/* ---- Adaptive sensors: a sensor that stops sampling a pixel once its samples agree (raytracer-utah_amd/csrc/rtu_sensor_adaptive.hip,
+ * rtu_sensor_adaptive.h) ----
+ * "Adaptive sampling" above, for sensors. The sensor is a recipe S or P sensor; sensor.samples is the MAXIMUM per pixel, in [1, 255]
+ * (counts are bytes, as for frames); samples == 0 (recipe W) is RTU_ERR_ARG. adaptive is the RtuAdaptiveDesc of the frame entries under
+ * their checks: min_samples in [1, samples], increment >= 1, a target that is neither NaN nor negative (+inf allowed), max_batch in
+ * [0, RTU_MAX_BATCH], which has no effect on results.
+ * SAMPLE IDENTITY  Sample i of a pixel is sample i of the fixed sensor with sensor.samples samples: the offsets of
+ * rtu_sensor_rays(sensor, i) and the key rtu_sample_key(x + width * y, i).
+ * THE RULE is the frame rule word for word, applied to the {r, g, b, t} the sensor accumulator adds (a fisheye sample outside the image
+ * circle adds zeros and is no hit). Per pixel and channel, in binary32 with every operation rounded, in sample order:
+ *     s += x, q += x * x;
+ * at each checkpoint n = min_samples + k * increment < samples: var = (q - s * (s / n)) / (n - 1) (n as float; n == 1: var = +inf). The
+ * pixel STOPS at n when var <= target_variance for r, g and b — a NaN variance never stops —, otherwise at samples. Its rgb is s / n,
+ * its z the mean t of the hits among its first n samples, or RTU_BIGFLOAT when none hit; its count is n. So a pixel that stops at n is,
+ * bit for bit, the mean of the first n samples rtu_render_sensor would sum, and min_samples == samples gives rtu_render_sensor's bytes.
+ * The decision never depends on how the samples are grouped into batches: a pixel that passes a checkpoint inside a batch ignores
+ * the rest of that batch.
+ * A stopped pixel's rays are never generated: after the first batch the rays are those of a list of live pixels, kept on the device
+ * in ascending pixel order; the next batch has min(max_batch or RTU_MAX_BATCH, 2^25 / live pixels, samples - done) samples, and the
+ * loop ends when the list is empty. Both calls are RENDERS as rtu_render_sensor is (ONE STREAM PER CONTEXT); they touch the sensor
+ * buffers and buffers of their own — never the frame accumulators, a progressive or a temporal session —, and a second call of one
+ * shape allocates nothing. A batch that ran out of frame records is shaded again before it is added (the counting variant of recipe P
+ * returns RTU_ERR_CAPACITY, as rtu_render_sensor does); the cancel flag is polled before every batch (RTU_ERR_CANCELLED);
+ * rtu_frame_status is clean on return. rtu_render_sensor_adaptive is synchronous: h_rgbz width * height float4, h_counts (may be NULL)
+ * width * height bytes. rtu_render_sensor_adaptive_device writes DEVICE memory (d_rgbz 16-byte aligned, d_counts may be NULL), queues
+ * on hip_stream and synchronises once per batch, as rtu_render_frame_adaptive_device does: it returns when the image is complete.
+ * RTU_ERR_ARG, RTU_ERR_NO_SCENE: as rtu_render_sensor, and the rules above. */
+int  rtu_render_sensor_adaptive(RtuContext* ctx, const RtuSensorDesc* sensor, const RtuAdaptiveDesc* adaptive, float* h_rgbz, uint8_t* h_counts);
+int  rtu_render_sensor_adaptive_device(RtuContext* ctx, const RtuSensorDesc* sensor, const RtuAdaptiveDesc* adaptive, void* d_rgbz, void* d_counts,
+                                       void* hip_stream);
+/* Diagnostic: the number of batches of the last adaptive sensor render of this context (0: none yet); for batch b < capacity
+ * live_out[b] (may be NULL) gets the live pixels it traced and batch_out[b] (may be NULL) its samples: it traced live * samples rays.
+ * RTU_ERR_ARG for a NULL context or a negative capacity. */
+int  rtu_debug_sensor_adaptive_trace(RtuContext* ctx, uint32_t* live_out, uint32_t* batch_out, int capacity);
+
 /* ---- First-hit features: the guides of a feature-guided filter (raytracer-utah_amd/csrc/rtu_features.hip) ---------------------------
  * Per ray one RtuRayHit — every byte as rtu_trace_rays_device writes it, the invalid-ray rule and RTU_QUERY_REFERENCE_WALK included —
  * and one float4 ALBEDO {r, g, b, 0}: what MtlBlinn::Shade returns for that hit under one AmbientLight of intensity (1, 1, 1) with

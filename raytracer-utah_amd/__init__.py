@@ -160,6 +160,7 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_ray_sort_box", "rtu_scene_sort_box", "rtu_ray_sort_keys", "rtu_ray_order_device", "rtu_ray_order", "rtu_permute_device", "rtu_copy_to_device",
                "rtu_sensor_defaults", "rtu_sensor_rays", "rtu_sensor_rays_device", "rtu_render_sensor", "rtu_render_sensor_device",
                "rtu_debug_sensor_timing",
+               "rtu_render_sensor_adaptive", "rtu_render_sensor_adaptive_device", "rtu_debug_sensor_adaptive_trace",
                "rtu_ray_features_device", "rtu_ray_features", "rtu_frame_features_device", "rtu_frame_features",
                "rtu_denoise_defaults", "rtu_denoise", "rtu_denoise_device",
                "rtu_progressive_snapshot_denoised_device", "rtu_progressive_snapshot_denoised",
@@ -364,6 +365,10 @@ _sig(hip, "rtu_sensor_rays_device", _I, _P, ctypes.POINTER(RtuSensorDesc), _I, _
 _sig(hip, "rtu_render_sensor", _I, _P, ctypes.POINTER(RtuSensorDesc), _P)
 _sig(hip, "rtu_render_sensor_device", _I, _P, ctypes.POINTER(RtuSensorDesc), _P, _P)
 _sig(hip, "rtu_debug_sensor_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
+# adaptive sensors (include/rtu_render.h, "Adaptive sensors")
+_sig(hip, "rtu_render_sensor_adaptive", _I, _P, ctypes.POINTER(RtuSensorDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P)
+_sig(hip, "rtu_render_sensor_adaptive_device", _I, _P, ctypes.POINTER(RtuSensorDesc), ctypes.POINTER(RtuAdaptiveDesc), _P, _P, _P)
+_sig(hip, "rtu_debug_sensor_adaptive_trace", _I, _P, _P, _P, _I)
 
 
 # first-hit features and the denoising filter (include/rtu_render.h, "First-hit features", "Denoising")
@@ -2341,6 +2346,34 @@ class Context:
         """rtu_render_sensor_device: the same image into device memory (height * width float4 at d_ptr, 16-byte aligned), the
         launches on `stream`; returns when the image is complete."""
         self._check(hip.rtu_render_sensor_device(self._h, ctypes.byref(desc), d_ptr, stream))
+
+    def render_sensor_adaptive(self, desc, adaptive=None):
+        """rtu_render_sensor_adaptive: the sensor (recipe S / P, desc.samples = the maximum per pixel, 1 .. 255) sampled until each
+        pixel's samples agree: (rgbz float32 [height, width, 4], counts uint8 [height, width] — the samples each pixel took).
+        adaptive: RtuAdaptiveDesc (None: the defaults)."""
+        import numpy as np
+        if adaptive is None:
+            adaptive = adaptive_defaults()
+        out = np.empty((max(desc.height, 0), max(desc.width, 0), 4), np.float32)
+        counts = np.empty(out.shape[:2], np.uint8)
+        self._check(hip.rtu_render_sensor_adaptive(self._h, ctypes.byref(desc), ctypes.byref(adaptive), out.ctypes.data if out.size else None,
+                                                   counts.ctypes.data if counts.size else None))
+        return out, counts
+
+    def render_sensor_adaptive_device(self, desc, d_rgbz, d_counts=None, adaptive=None, stream=None):
+        """rtu_render_sensor_adaptive_device: the same into device memory (height * width float4 at d_rgbz, 16-byte aligned; height *
+        width bytes at d_counts unless None), the launches on `stream`; returns when the image is complete."""
+        if adaptive is None:
+            adaptive = adaptive_defaults()
+        self._check(hip.rtu_render_sensor_adaptive_device(self._h, ctypes.byref(desc), ctypes.byref(adaptive), d_rgbz, d_counts, stream))
+
+    def sensor_adaptive_trace(self):
+        """rtu_debug_sensor_adaptive_trace: [(live pixels, samples)] of every batch of the last adaptive sensor render of this context."""
+        n = hip.rtu_debug_sensor_adaptive_trace(self._h, None, None, 0)
+        self._check(min(n, 0))
+        live, batch = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+        self._check(min(hip.rtu_debug_sensor_adaptive_trace(self._h, live, batch, n), 0))
+        return [(int(live[b]), int(batch[b])) for b in range(n)]
 
     def sensor_timing(self, on=True):
         """Time the kernels of later sensor renders; returns the ms spent since the previous call in k_sensor_rays, in

@@ -13,6 +13,7 @@
 #include "rtu_query.h"
 #include "rtu_raysort.h"
 #include "rtu_sensor.h"
+#include "rtu_sensor_adaptive.h"
 #include "rtu_gradient.h"
 #include "rtu_holes.h"
 #include "rtu_sparse.h"
@@ -160,7 +161,13 @@ struct RtuContext {
     bool  sn_timing = false;                 // rtu_debug_sensor_timing: HIP events around the two kernels of rtu_sensor.hip and the whole render
     float sn_ms[3] = {};                     // k_sensor_rays, k_sensor_accumulate, the render: summed since the last read
     hipEvent_t sn_ev[6] = {};
-    DevBuf<uint32_t> st_scratch;             // steered sampling (rtu_sample_allocation_device): the weights, the tile sums, Wsum
+    DevBuf<float4>   sa_s, sa_q, sa_img;     // adaptive sensors (rtu_render_sensor_adaptive): per pixel the sums and the sums of squares with the hit count; the host form's image
+    DevBuf<uint32_t> sa_list[2], sa_packed;  // ... the live-pixel lists, double-buffered, the survivors packed per block,
+    DevBuf<uint32_t> sa_blk, sa_n;           // ... their number per block and its scan, the length of the next list
+    PinnedBuf<uint32_t> sa_n_host;           // ... and where the host reads it (pinned)
+    DevBuf<uint8_t>  sa_counts;              // ... the host form's counts
+    std::vector<uint32_t> sa_trace;          // {live pixels, samples} of every batch of the last adaptive sensor render (rtu_debug_sensor_adaptive_trace)
+    DevBuf<uint32_t> st_scratch;            // steered sampling (rtu_sample_allocation_device): the weights, the tile sums, Wsum
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -1775,17 +1782,23 @@ int render_sampled(RtuContext* ctx, const RtuFrameDesc* frame, float4* d_out, hi
     return RTU_OK;
 }
 
+// The rules of RtuAdaptiveDesc for a maximum of `samples` per pixel (an adaptive frame, an adaptive sensor); ctx may be NULL
+int check_adaptive_desc(RtuContext* ctx, const RtuAdaptiveDesc* ad, int samples) {
+    if (!ad) return fail(ctx, RTU_ERR_ARG, "adaptive is NULL");
+    if (ad->min_samples < 1 || ad->min_samples > samples) return fail(ctx, RTU_ERR_ARG, "min_samples is 1 .. frame.samples");
+    if (ad->increment < 1) return fail(ctx, RTU_ERR_ARG, "increment is >= 1");
+    if (!(ad->target_variance >= 0.0f)) return fail(ctx, RTU_ERR_ARG, "target_variance is >= 0 (or +inf)");
+    if (ad->max_batch < 0 || ad->max_batch > RTU_MAX_BATCH) return fail(ctx, RTU_ERR_ARG, "max_batch is 0 .. %d", RTU_MAX_BATCH);
+    return RTU_OK;
+}
+
 // The arguments of an adaptive frame (rtu_render.h): a recipe S / P frame with 1 .. 255 samples and a valid RtuAdaptiveDesc.
 int check_adaptive(RtuContext* ctx, const RtuFrameDesc* f, const RtuAdaptiveDesc* ad) {
     if (!f) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
     if (f->samples < 1 || f->samples > 255) return fail(ctx, RTU_ERR_ARG, "an adaptive frame has 1 .. 255 samples per pixel at most (frame.samples)");
     int rc = check_frame(ctx, f);
     if (rc != RTU_OK) return rc;
-    if (!ad) return fail(ctx, RTU_ERR_ARG, "adaptive is NULL");
-    if (ad->min_samples < 1 || ad->min_samples > f->samples) return fail(ctx, RTU_ERR_ARG, "min_samples is 1 .. frame.samples");
-    if (ad->increment < 1) return fail(ctx, RTU_ERR_ARG, "increment is >= 1");
-    if (!(ad->target_variance >= 0.0f)) return fail(ctx, RTU_ERR_ARG, "target_variance is >= 0 (or +inf)");
-    if (ad->max_batch < 0 || ad->max_batch > RTU_MAX_BATCH) return fail(ctx, RTU_ERR_ARG, "max_batch is 0 .. %d", RTU_MAX_BATCH);
+    if ((rc = check_adaptive_desc(ctx, ad, f->samples)) != RTU_OK) return rc;
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
     return RTU_OK;
 }
@@ -3861,12 +3874,15 @@ int paths_shade(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream
 // of paths_shade, the chain having been traced by the caller —, wait, check_overflow, and again with the capacities that raised.
 // counters_refusal: what to say where a path-traced batch with counters would have to be shaded again (its counters of the dropped
 // steps are already in the totals), or nullptr where the caller has no counters.
+// behind (may be nullptr): queued behind every attempt and ahead of its synchronisation — kernels that read the batch and leave it alone
+// where the overflow flags say it is incomplete (adaptive sensors: k_sa_step and the length of the next list, read in this synchronisation).
 int shade_until_fits(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n,
-                     bool paths, const char* counters_refusal) {
+                     bool paths, const char* counters_refusal, int (*behind)(void*) = nullptr, void* behind_arg = nullptr) {
     for (int attempt = 0;; attempt++) {
         int rc = paths ? paths_shade(ctx, f, d_out, stream, d_rays, d_keys, n)
                        : launch(ctx, &f, d_out, stream, true, 0, 1, nullptr, RTU_LAUNCH_ALL, 0, false, nullptr, 0, d_rays, n, d_keys);
         if (rc != RTU_OK) return rc;
+        if (behind && (rc = behind(behind_arg)) != RTU_OK) return rc;
         RTU_HIP(ctx, hipStreamSynchronize(stream));
         bool overflow = false;
         if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
@@ -5320,6 +5336,157 @@ int rtu_render_sensor(RtuContext* ctx, const RtuSensorDesc* d, float* h_rgbz) {
     if ((rc = rtu_render_sensor_device(ctx, d, ctx->sn_img.get(), ctx->stream)) != RTU_OK) return rc;
     RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->sn_img.get(), sizeof(float4) * pixels, hipMemcpyDeviceToHost));
     return RTU_OK;
+}
+
+// ---- adaptive sensors (rtu_sensor_adaptive.h, rtu_sensor_adaptive.hip): the sample loop of a sensor over the pixels that still sample ----
+namespace {
+// the arguments both forms share: a recipe S / P sensor with 1 .. 255 samples and a valid RtuAdaptiveDesc
+int check_sensor_adaptive(RtuContext* ctx, const RtuSensorDesc* d, const RtuAdaptiveDesc* ad) {
+    const int rc = check_sensor(ctx, d);
+    if (rc != RTU_OK) return rc;
+    if (d->samples < 1 || d->samples > 255) return fail(ctx, RTU_ERR_ARG, "an adaptive sensor has 1 .. 255 samples per pixel at most (sensor.samples)");
+    return check_adaptive_desc(ctx, ad, d->samples);
+}
+
+// what shade_until_fits queues behind a batch: the step kernels, and the copy of the next list's length to where the host reads it
+struct SaBehind {
+    RtuContext* ctx;
+    SaStep      p;
+    hipStream_t stream;
+};
+int sa_behind(void* arg) {
+    SaBehind& b = *static_cast<SaBehind*>(arg);
+    const hipError_t e = (hipError_t)rtu_launch_sa_step(b.p, b.stream);
+    if (e != hipSuccess) return fail(b.ctx, RTU_ERR_HIP, "adaptive sensor step launch: %s", hipGetErrorString(e));
+    RTU_HIP(b.ctx, hipMemcpyAsync(b.ctx->sa_n_host.get(), b.p.n_out, sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream));
+    return RTU_OK;
+}
+}  // namespace
+
+// The sample loop of an adaptive sensor: per batch the rays and keys of the live pixels (the first batch: every pixel, k_sensor_rays;
+// then k_sa_rays over the list), the launch path of the matching ray-batch entry into sn_out, and behind it — ahead of the batch's one
+// synchronisation — k_sa_step with the next list, whose length the host reads in that synchronisation. A batch that overflowed is
+// shaded again; the step kernels have then left it alone.
+int rtu_render_sensor_adaptive_device(RtuContext* ctx, const RtuSensorDesc* d, const RtuAdaptiveDesc* ad, void* d_rgbz, void* d_counts, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = check_sensor_adaptive(ctx, d, ad);
+    if (rc != RTU_OK) return rc;
+    if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "image pointer is NULL");
+    if ((uintptr_t)d_rgbz & 15u) return fail(ctx, RTU_ERR_ARG, "the device image must be 16-byte aligned");
+    const size_t pixels = (size_t)d->width * (size_t)d->height;
+    const bool paths = d->gather_bounces != 0;
+    const int S = d->samples;
+    int most = ad->max_batch > 0 ? ad->max_batch : RTU_MAX_BATCH;  // samples of a batch, at most
+    if (most > S) most = S;
+    size_t cap = pixels * (size_t)most;  // rays of a batch, at most
+    if (cap > kSensorPixels) cap = kSensorPixels;
+    RtuShadeDesc sd;
+    rtu_shade_defaults(&sd);
+    memcpy(sd.eye, d->pos, sizeof sd.eye);
+    sd.max_bounce = d->max_bounce;
+    sd.flags = d->flags;
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->sn_rays.grow(2 * cap));
+    RTU_HIP(ctx, ctx->sn_keys.grow(cap));
+    RTU_HIP(ctx, ctx->sn_out.grow(cap));
+    RTU_HIP(ctx, ctx->sa_s.grow(pixels));
+    RTU_HIP(ctx, ctx->sa_q.grow(pixels));
+    for (DevBuf<uint32_t>& l : ctx->sa_list) RTU_HIP(ctx, l.grow(pixels));
+    const size_t blocks = rtu_sa_blocks(pixels);
+    RTU_HIP(ctx, ctx->sa_packed.grow(blocks * RTU_SA_BLOCK));
+    RTU_HIP(ctx, ctx->sa_blk.grow(2 * blocks));
+    RTU_HIP(ctx, ctx->sa_n.grow(1));
+    RTU_HIP(ctx, ctx->sa_n_host.grow(1));
+    RtuFrameDesc f;  // what launch() takes for a ray batch, by the checks of the _device entries
+    if ((rc = shade_args(ctx, ctx->sn_rays.get(), ctx->sn_out.get(), cap, &sd, true, &f, true, ctx->sn_keys.get(), paths)) != RTU_OK) return rc;
+    float4* const rays = ctx->sn_rays.get();
+    float4* const out = ctx->sn_out.get();
+    uint32_t* const keys = ctx->sn_keys.get();
+    ctx->sa_trace.clear();
+    SaBehind behind;
+    behind.ctx = ctx;
+    behind.stream = stream;
+    SaStep& p = behind.p;
+    p.samples = out;
+    p.s = ctx->sa_s.get();
+    p.q = ctx->sa_q.get();
+    p.out = (float4*)d_rgbz;
+    p.counts = (uint8_t*)d_counts;
+    p.n_out = ctx->sa_n.get();
+    p.packed = ctx->sa_packed.get();
+    p.blk = ctx->sa_blk.get();
+    p.skip_if = &ctx->fcnt.get()->overflow;
+    p.skip_if_side = &ctx->fcnt_side.get()->overflow;
+    p.max_samples = (uint32_t)S;
+    p.min_samples = (uint32_t)ad->min_samples;
+    p.increment = (uint32_t)ad->increment;
+    p.target = ad->target_variance;
+    int cur = 0, done = 0;
+    uint32_t live_n = (uint32_t)pixels;
+    while (live_n > 0) {  // (done < S: the pixels that reach S stop there)
+        if (cancel_raised(ctx)) return fail(ctx, RTU_ERR_CANCELLED, "cancelled after %d of %d samples", done, S);
+        int nb = (int)(kSensorPixels / live_n) < most ? (int)(kSensorPixels / live_n) : most;
+        if (nb > S - done) nb = S - done;
+        const uint32_t m = live_n * (uint32_t)nb;
+        if (done == 0) {
+            if ((rc = sensor_generate(ctx, d, 0, nb, rays, keys, stream)) != RTU_OK) return rc;
+        } else {
+            SensorOffsets off;
+            memset(&off, 0, sizeof off);
+            for (int j = 0; j < nb; j++) {
+                sensor_offset(d, done + j, off.ox[j], off.oy[j]);
+                off.sample[j] = (uint32_t)(done + j);
+            }
+            const hipError_t e = (hipError_t)rtu_launch_sa_rays(*d, off, (uint32_t)nb, ctx->sa_list[cur].get(), live_n, rays, keys, stream);
+            if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "adaptive sensor ray launch: %s", hipGetErrorString(e));
+        }
+        p.list = done == 0 ? nullptr : ctx->sa_list[cur].get();
+        p.list_out = ctx->sa_list[cur ^ 1].get();
+        p.live_n = live_n;
+        p.batch = (uint32_t)nb;
+        p.done = (uint32_t)done;
+        p.checkpoint = done < ad->min_samples ? (uint32_t)ad->min_samples
+                                              : (uint32_t)(ad->min_samples + ((done - ad->min_samples) / ad->increment + 1) * ad->increment);
+        if (paths && (rc = paths_chain(ctx, f, out, stream, rays, keys, m)) != RTU_OK) return rc;
+        if ((rc = shade_until_fits(ctx, f, out, stream, rays, keys, m, paths,
+                                   "recipe P with counters: frame records ran out; render the sensor once without RTU_QUERY_REFERENCE_WALK first",
+                                   sa_behind, &behind)) != RTU_OK)
+            return rc;
+        ctx->sa_trace.push_back(live_n);
+        ctx->sa_trace.push_back((uint32_t)nb);
+        live_n = *ctx->sa_n_host.get();  // (read in the batch's synchronisation)
+        cur ^= 1;
+        done += nb;
+    }
+    return RTU_OK;
+}
+
+int rtu_render_sensor_adaptive(RtuContext* ctx, const RtuSensorDesc* d, const RtuAdaptiveDesc* ad, float* h_rgbz, uint8_t* h_counts) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = check_sensor_adaptive(ctx, d, ad);
+    if (rc != RTU_OK) return rc;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "image pointer is NULL");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    const size_t pixels = (size_t)d->width * (size_t)d->height;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->sa_img.grow(pixels));
+    RTU_HIP(ctx, ctx->sa_counts.grow(pixels));
+    if ((rc = rtu_render_sensor_adaptive_device(ctx, d, ad, ctx->sa_img.get(), ctx->sa_counts.get(), ctx->stream)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->sa_img.get(), sizeof(float4) * pixels, hipMemcpyDeviceToHost));
+    if (h_counts) RTU_HIP(ctx, hipMemcpy(h_counts, ctx->sa_counts.get(), pixels, hipMemcpyDeviceToHost));
+    return RTU_OK;
+}
+
+int rtu_debug_sensor_adaptive_trace(RtuContext* ctx, uint32_t* live_out, uint32_t* batch_out, int capacity) {
+    if (!ctx || capacity < 0) return RTU_ERR_ARG;
+    const int n = (int)(ctx->sa_trace.size() / 2);
+    for (int b = 0; b < n && b < capacity; b++) {
+        if (live_out) live_out[b] = ctx->sa_trace[2 * (size_t)b];
+        if (batch_out) batch_out[b] = ctx->sa_trace[2 * (size_t)b + 1];
+    }
+    return n;
 }
 
 // ---- temporal accumulation for sensors (rtu_sensor.h sensor_project, rtu_temporal.hip k_temporal_sensor): the projection, the accumulator
