@@ -329,7 +329,8 @@ void rtu_progressive_free(RtuProgressive* p);
  * unit length: the conservative bounds of the fast walk were argued, and are tested, for the renderer's own rays. A ray is INVALID
  * and is not traced when a component of org, dir or tmax is NaN or infinite, when tmax <= 0, or when |dot(dir, dir) - 1| > 2e-3
  * (binary32, (x x + y y) + z z): it gets RTU_RAY_INVALID with the values of a miss, or 0 from the occlusion form.
- * Textures are not evaluated; uvw, face index and barycentrics are not reported (rtu_ray_features adds the textured albedo of the hit).
+ * Textures are not evaluated; uvw, face index and barycentrics are not reported (rtu_ray_features adds the textured albedo of the hit,
+ * rtu_ray_surface those three).
  * flags: 0, or RTU_QUERY_REFERENCE_WALK for the walk of the counting variant (the reference's own tree, no culling, no node-level
  * bounds): every field of every answer is the same, bit for bit; it is slower. rtu_debug_walk_stack_limit and rtu_debug_node_bounds
  * apply as to a render; rtu_debug_flags does not.
@@ -656,6 +657,29 @@ int  rtu_ray_features(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t 
 int  rtu_frame_features_device(RtuContext* ctx, const RtuFrameDesc* frame, void* d_hits, void* d_albedo, void* hip_stream);
 int  rtu_frame_features(RtuContext* ctx, const RtuFrameDesc* frame, RtuRayHit* h_hits, float* h_albedo);
 
+/* ---- Surface records: which triangle a ray hit, and where on it (k_features_surface, raytracer-utah_amd/csrc/rtu_features.hip) -----
+ * The features above with one more output per ray: an RtuRaySurface, what the mesh walk interpolated hInfo.p, hInfo.N and hInfo.uvw
+ * from. For baking, for picking a triangle, and for following a point of a deforming surface (the same weights over other vertices).
+ *   triangle-mesh hit   mesh = the node's mesh_id; face = the index of the triangle in the mesh's f / fn / ft (cyTriMesh's face index,
+ *                       never a slot of a tree); bc = the weights of the face's vertices 0, 1, 2 — {BC3, BC1, BC2} of
+ *                       TriObj::IntersectTriangle (objFunctions.cpp:302-304), each in (0, 1) — so that in binary32, one rounding per
+ *                       operation, (v[f[face][0]] bc[0] + v[f[face][1]] bc[1]) + v[f[face][2]] bc[2] is hInfo.p in the node's space
+ *                       (cyTriMesh::Interpolate), and FromNodeCoords up the node's chain gives RtuRayHit.p bit for bit; likewise vn over
+ *                       fn (normalised) for N and vt over ft for uvw. On an exact tie the triangle is the reference's winner.
+ *   sphere, plane hit   mesh = face = -1, bc = 0; uvw = hInfo.uvw as a textured render carries it.
+ *   miss, invalid ray   mesh = face = -1, bc = 0, uvw = 0.
+ * uvw of a mesh hit is 0 where a render has none either: a mesh without texture coordinates, and every mesh of a scene without
+ * textures (n_textures == 0: texture coordinates travel to the device with textured scenes only). hits and albedo are, byte for byte, what rtu_ray_features / rtu_frame_features write:
+ * the walks are the same, one ray per lane, and hand the winner out at their end. RTU_QUERY_REFERENCE_WALK, the invalid-ray rule,
+ * the errors and what the _device and host forms touch are those of the features; the surface pointer of a _device form must be
+ * 16-byte aligned too (RTU_ERR_ARG). */
+typedef struct RtuRaySurface { int32_t mesh; int32_t face; float bc[3]; float uvw[3]; } RtuRaySurface;   /* 32 B */
+int  rtu_ray_surface_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* d_albedo, void* d_surface,
+                            void* hip_stream);
+int  rtu_ray_surface(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo, RtuRaySurface* h_surface);
+int  rtu_frame_surface_device(RtuContext* ctx, const RtuFrameDesc* frame, void* d_hits, void* d_albedo, void* d_surface, void* hip_stream);
+int  rtu_frame_surface(RtuContext* ctx, const RtuFrameDesc* frame, RtuRayHit* h_hits, float* h_albedo, RtuRaySurface* h_surface);
+
 /* ---- Denoising: an edge-avoiding filter for sampled previews (raytracer-utah_amd/csrc/rtu_denoise.h, rtu_denoise.hip) ---------------
  * A five-pass (n_passes) 5 x 5 a-trous wavelet filter on albedo-demodulated colour, guided by the features above. It has no
  * transcendental function; all arithmetic is binary32, one rounding per operation, no contraction, in this order — the host form and
@@ -862,6 +886,81 @@ int  rtu_temporal_frame_moved_device(RtuTemporal* t, const RtuFrameDesc* frame, 
                                      void* d_rgbz, void* hip_stream);
 int  rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
                               float* h_rgbz);
+
+/* ---- Temporal accumulation on deforming meshes (rtu_temporal.h tp_deform_source, rtu_temporal.hip k_temporal_deform<MOMENTS>) ----
+ * rtu_scene_motion marks a deformed mesh RTU_MOTION_RESET: its pixels start over. But a point given as (face, barycentrics) — an
+ * RtuRaySurface of "Surface records" — has an exact previous position: the same weights over the PREVIOUS vertices, through the node's
+ * previous transformation. The entries below look the history up from there.
+ *
+ * PREVIOUS VERTICES  rtu_keep_previous_vertices(ctx, on), default off: nothing changes. With it on, rtu_update_meshes keeps the v and vn
+ *   it replaces as the previous generation of every LISTED mesh (the two grow-only buffers change places: the first such update of a
+ *   mesh allocates the second pair, later ones nothing). "Previous" means before the LAST rtu_update_meshes only: for a mesh that
+ *   update did not list, before any update, after rtu_upload_scene and after the switch changed, previous is current. A caller who
+ *   updates a mesh twice between two frames marks it RESET.
+ *
+ * THE TABLE  rtu_scene_motion_deform is rtu_scene_motion with a second list: a node whose mesh_id is in deform_mesh_ids and not in
+ *   reset_mesh_ids gets flags = RTU_MOTION_DEFORM and
+ *     m = W_prev, node coordinates to world of the PREVIOUS scene over the whole ancestor chain, as three rows {a, b, c, d}
+ *     g = the transpose of the linear part of W_prev^-1
+ *   composed in binary64 and rounded once; reserved stays 0. A mesh in both lists is RESET. n_bvh_nodes of a listed mesh may differ.
+ *   With n_deform == 0 the table is rtu_scene_motion's, byte for byte. RTU_ERR_ARG besides rtu_scene_motion's: n_deform < 0, a NULL
+ *   list with n_deform > 0, a mesh id >= n_meshes.
+ *
+ * THE RULE  rtu_temporal_accumulate_deform (three planes) and _deform_moments (four) are rtu_temporal_accumulate_motion and
+ *   rtu_temporal_accumulate_moments with one more input, the frame's surface records. For a VALID pixel with k = H.node inside the
+ *   table, T = motion[k] with RTU_MOTION_DEFORM (and not RESET), S its record, f / fn the faces and v_prev / vn_prev the previous
+ *   positions / normals of mesh nodes[k].mesh_id:
+ *     x = (v_prev[f[S.face][0]] S.bc[0] + v_prev[f[S.face][1]] S.bc[1]) + v_prev[f[S.face][2]] S.bc[2]     (binary32, no contraction)
+ *     n likewise of vn_prev over fn;  Pm.k = dot(row_k.abc, x) + row_k.d;  q = g n;  Nm = q / sqrtf(dot(q, q))
+ *     no lookup if S.mesh is not nodes[k].mesh_id, S.face is outside 0 .. nf - 1, or a component of Pm or Nm is not finite.
+ *   A DEFORM pixel always reprojects (no one-tap path; RTU_MOTION_STATIC beside DEFORM is ignored); the tap test and the history written
+ *   are the motion form's. Every other pixel follows the motion form bit for bit: a table without DEFORM entries gives its bytes.
+ *   The host forms read v_prev, vn_prev, f, fn and mesh_id from prev_scene (n_nodes must be its node count), which must be a scene
+ *   rtu_validate_scene accepts: the indices in f / fn are used as they are. A mesh of prev_scene without one of the four arrays has
+ *   no face: records on it give no lookup. The _device forms read
+ *   the context's own f, fn and the previous v, vn it kept: they need the switch above (else RTU_ERR_ARG), a scene (RTU_ERR_NO_SCENE),
+ *   n_nodes == the uploaded scene's node count and 16-byte aligned surface records; the first call after an upload, an update or a
+ *   change of the switch rewrites a small table of the context (grow-only; it waits for the context's own stream and copies
+ *   synchronously), other calls allocate nothing. As for rtu_update_meshes itself, the caller synchronises any OTHER stream it gave a
+ *   deform entry before the call that rewrites the table: the rewrite is not ordered against kernels in flight there.
+ *   rtu_motion_vectors_deform[_device] is rtu_motion_vectors with Pm as above for DEFORM pixels ({0, 0, 0, 0} where there is no lookup).
+ *
+ * THE SESSION  rtu_temporal_frame_deformed[_device] is rtu_temporal_frame_moved[_device] except that step 3 takes the guides from
+ *   rtu_frame_surface_device and uses the deform accumulator (the table may carry RTU_MOTION_DEFORM). The session grows a buffer of
+ *   32 B per pixel for the records on the first such frame and allocates nothing afterwards. It needs the context's
+ *   rtu_keep_previous_vertices (else RTU_ERR_ARG) and a plain, RTU_TEMPORAL_DENOISE or variance session: a steered, gradient or sparse
+ *   session (hole rays included) is refused with RTU_ERR_UNSUPPORTED. A refused call leaves the session as it was. Plain, moved and
+ *   deformed frames may be mixed in one session. The table describes the scene of the previous frame of the session against the scene
+ *   now, and "previous vertices" are those before the last rtu_update_meshes: ONE rtu_update_meshes per deformed frame, or RESET. */
+#define RTU_MOTION_DEFORM 4u   /* m = W_prev, g from W_prev^-1: the deform forms carry (face, barycentrics) over the previous vertices */
+int  rtu_keep_previous_vertices(RtuContext* ctx, int on);
+int  rtu_scene_motion_deform(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* deform_mesh_ids, int n_deform,
+                             const uint32_t* reset_mesh_ids, int n_reset, RtuNodeMotion* out /* cur->n_nodes */);
+int  rtu_temporal_accumulate_deform(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                    const RtuRayHit* h_hits, const float* h_albedo, const RtuRaySurface* h_surface, const RtuSceneDesc* prev_scene,
+                                    const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion, uint32_t n_nodes,
+                                    int32_t history_cap);
+int  rtu_temporal_accumulate_deform_moments(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                            const RtuRayHit* h_hits, const float* h_albedo, const RtuRaySurface* h_surface, const RtuSceneDesc* prev_scene,
+                                            const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion, uint32_t n_nodes,
+                                            int32_t history_cap);
+int  rtu_temporal_accumulate_deform_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                           const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_surface, const void* d_hist_prev,
+                                           void* d_hist_out, void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap,
+                                           void* hip_stream);
+int  rtu_temporal_accumulate_deform_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                                   const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_surface,
+                                                   const void* d_hist_prev, void* d_hist_out, void* d_rgbz_out, const RtuNodeMotion* d_motion,
+                                                   uint32_t n_nodes, int32_t history_cap, void* hip_stream);
+int  rtu_motion_vectors_deform(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuRaySurface* h_surface,
+                               const RtuSceneDesc* prev_scene, const RtuNodeMotion* motion, uint32_t n_nodes, float* h_mv);
+int  rtu_motion_vectors_deform_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const void* d_hits, const void* d_surface,
+                                      const RtuNodeMotion* d_motion, uint32_t n_nodes, void* d_mv, void* hip_stream);
+
+int  rtu_temporal_frame_deformed_device(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                                        void* d_rgbz, void* hip_stream);
+int  rtu_temporal_frame_deformed(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                                 float* h_rgbz);
 
 /* ---- Variance-guided filtering: the filter steered by per-pixel variance from temporal moments (rtu_variance.h, rtu_variance.hip) ----
  * The history gets a fourth plane with the first and second moment of the sample's luminance; out of it comes the variance of the

@@ -162,6 +162,10 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_debug_sensor_timing",
                "rtu_render_sensor_adaptive", "rtu_render_sensor_adaptive_device", "rtu_debug_sensor_adaptive_trace",
                "rtu_ray_features_device", "rtu_ray_features", "rtu_frame_features_device", "rtu_frame_features",
+               "rtu_ray_surface_device", "rtu_ray_surface", "rtu_frame_surface_device", "rtu_frame_surface",
+               "rtu_keep_previous_vertices", "rtu_scene_motion_deform", "rtu_temporal_accumulate_deform", "rtu_temporal_accumulate_deform_moments",
+               "rtu_temporal_accumulate_deform_device", "rtu_temporal_accumulate_deform_moments_device", "rtu_motion_vectors_deform",
+               "rtu_motion_vectors_deform_device", "rtu_temporal_frame_deformed_device", "rtu_temporal_frame_deformed",
                "rtu_denoise_defaults", "rtu_denoise", "rtu_denoise_device",
                "rtu_progressive_snapshot_denoised_device", "rtu_progressive_snapshot_denoised",
                "rtu_camera_sample_rays_device", "rtu_temporal_defaults", "rtu_temporal_accumulate", "rtu_temporal_accumulate_device",
@@ -382,6 +386,10 @@ _sig(hip, "rtu_ray_features_device", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint3
 _sig(hip, "rtu_ray_features", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P)
 _sig(hip, "rtu_frame_features_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P, _P)
 _sig(hip, "rtu_frame_features", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P)
+_sig(hip, "rtu_ray_surface_device", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P, _P, _P)
+_sig(hip, "rtu_ray_surface", _I, _P, _P, ctypes.c_size_t, ctypes.c_uint32, _P, _P, _P)
+_sig(hip, "rtu_frame_surface_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P, _P, _P)
+_sig(hip, "rtu_frame_surface", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _P, _P)
 _sig(hip, "rtu_denoise_defaults", _I, ctypes.POINTER(RtuDenoiseDesc))
 _sig(hip, "rtu_denoise", _I, ctypes.POINTER(RtuDenoiseDesc), _P, _P, _P, _P)
 _sig(hip, "rtu_denoise_device", _I, _P, ctypes.POINTER(RtuDenoiseDesc), _P, _P, _P, _P, _P)
@@ -467,6 +475,7 @@ def temporal_accumulate(prev_cam, cur_cam, rgbz, hits, albedo, hist_prev=None, d
 
 # temporal accumulation across scene updates (include/rtu_render.h): the per-node motion table
 RTU_MOTION_STATIC, RTU_MOTION_RESET = 1, 2
+RTU_MOTION_DEFORM = 4
 _U32 = ctypes.c_uint32
 _sig(hip, "rtu_scene_motion", _I, _P, _P, _P, _I, _P)
 _sig(hip, "rtu_temporal_accumulate_motion", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
@@ -477,6 +486,18 @@ _sig(hip, "rtu_motion_vectors", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POIN
 _sig(hip, "rtu_motion_vectors_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, _U32, _P, _P)
 _sig(hip, "rtu_temporal_frame_moved_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _U32, ctypes.c_int32, _P, _P)
 _sig(hip, "rtu_temporal_frame_moved", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _U32, ctypes.c_int32, _P)
+# deforming meshes (include/rtu_render.h, "Temporal accumulation on deforming meshes")
+_sig(hip, "rtu_keep_previous_vertices", _I, _P, _I)
+_sig(hip, "rtu_scene_motion_deform", _I, _P, _P, _P, _I, _P, _I, _P)
+for _name in ("rtu_temporal_accumulate_deform", "rtu_temporal_accumulate_deform_moments"):
+    _sig(hip, _name, _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+         _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32)
+    _sig(hip, _name + "_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuFrameDesc),
+         _P, _P, _P, _P, _P, _P, _P, _P, _U32, ctypes.c_int32, _P)
+_sig(hip, "rtu_temporal_frame_deformed_device", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _U32, ctypes.c_int32, _P, _P)
+_sig(hip, "rtu_temporal_frame_deformed", _I, _P, ctypes.POINTER(RtuFrameDesc), _P, _U32, ctypes.c_int32, _P)
+_sig(hip, "rtu_motion_vectors_deform", _I, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, _P, _P, _U32, _P)
+_sig(hip, "rtu_motion_vectors_deform_device", _I, _P, ctypes.POINTER(RtuTemporalDesc), ctypes.POINTER(RtuFrameDesc), _P, _P, _P, _U32, _P, _P)
 
 
 def motion_dtype():
@@ -493,14 +514,19 @@ def _as_motion(motion):
     return motion
 
 
-def scene_motion(prev, cur, reset_meshes=()):
+def scene_motion(prev, cur, reset_meshes=(), deform_meshes=None):
     """rtu_scene_motion (pure host code): for every node of the Scene `cur` the affine map that carries a point of that node's surface
     to where it was in the Scene `prev` (same shape), as an array of motion_dtype(). Nodes whose chain did not change are
-    RTU_MOTION_STATIC; nodes of the meshes in reset_meshes (those given to update_meshes) are RTU_MOTION_RESET."""
+    RTU_MOTION_STATIC; nodes of the meshes in reset_meshes (those given to update_meshes) are RTU_MOTION_RESET. deform_meshes (not
+    None: rtu_scene_motion_deform): nodes of those meshes are RTU_MOTION_DEFORM — m is W_prev — for temporal_accumulate_deform()."""
     import numpy as np
     out = np.zeros(cur.desc.n_nodes, motion_dtype())
     ids = (ctypes.c_uint32 * max(1, len(reset_meshes)))(*reset_meshes)
-    rc = hip.rtu_scene_motion(prev.desc_ptr, cur.desc_ptr, ids, len(reset_meshes), out.ctypes.data)
+    if deform_meshes is not None:
+        dids = (ctypes.c_uint32 * max(1, len(deform_meshes)))(*deform_meshes)
+        rc = hip.rtu_scene_motion_deform(prev.desc_ptr, cur.desc_ptr, dids, len(deform_meshes), ids, len(reset_meshes), out.ctypes.data)
+    else:
+        rc = hip.rtu_scene_motion(prev.desc_ptr, cur.desc_ptr, ids, len(reset_meshes), out.ctypes.data)
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_scene_motion: " + ("a mesh id outside the scene's meshes" if rc == RTU_ERR_ARG else scene_shape_diff(prev, cur) or ""))
     return out
@@ -515,6 +541,51 @@ def temporal_accumulate_motion(prev_cam, cur_cam, rgbz, hits, albedo, motion, hi
         raise RtuError(rc, "rtu_temporal_accumulate_motion: a descriptor outside its rules, a camera of another size, history_cap outside "
                            "0..65535, or a table entry with an unknown flag or a non-zero reserved word")
     return out, hist
+
+
+def _as_surface(surface, n):
+    import numpy as np
+    surface = np.ascontiguousarray(surface)
+    if surface.dtype != surface_dtype() or surface.size != n:
+        raise RtuError(RTU_ERR_ARG, "surface: H * W of surface_dtype()")
+    return surface
+
+
+def temporal_accumulate_deform(prev_cam, cur_cam, rgbz, hits, albedo, surface, prev_scene, motion, hist_prev=None, desc=None, history_cap=0,
+                               moments=False):
+    """rtu_temporal_accumulate_deform / _deform_moments (pure host code): temporal_accumulate_motion() / _moments() that follows
+    deforming meshes — where a pixel's table entry is RTU_MOTION_DEFORM (scene_motion(deform_meshes=)), its surface record
+    (frame_surface / ray_surface: face and weights) is evaluated over the vertices of the Scene `prev_scene` and carried through the
+    entry before the lookup. -> (accumulated rgbz [H, W, 4], the new history [3 or 4, H, W, 4])."""
+    import numpy as np
+    surface = _as_surface(surface, np.asarray(rgbz).shape[0] * np.asarray(rgbz).shape[1])
+    fn = hip.rtu_temporal_accumulate_deform_moments if moments else hip.rtu_temporal_accumulate_deform
+
+    def call(d, pc, cc, r, h, a, hp, ho, o, *table):
+        return fn(d, pc, cc, r, h, a, surface.ctypes.data, prev_scene.desc_ptr, hp, ho, o, *table)
+    rc, out, hist = _temporal_accumulate(4 if moments else 3, call, prev_cam, cur_cam, rgbz, hits, albedo, hist_prev, desc, motion, history_cap)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_temporal_accumulate_deform: what temporal_accumulate_motion refuses, or a table of another length than "
+                           "prev_scene's node count")
+    return out, hist
+
+
+def motion_vectors_deform(prev_cam, hits, surface, prev_scene, motion, width, height):
+    """rtu_motion_vectors_deform (pure host code): motion_vectors() with the previous position of RTU_MOTION_DEFORM pixels taken
+    from their surface records over the vertices of `prev_scene`."""
+    import numpy as np
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != hit_dtype() or hits.size != width * height:
+        raise RtuError(RTU_ERR_ARG, "hits: H * W of hit_dtype()")
+    surface = _as_surface(surface, width * height)
+    motion = _as_motion(motion)
+    d = temporal_desc(width, height)
+    out = np.empty((height, width, 4), np.float32)
+    rc = hip.rtu_motion_vectors_deform(ctypes.byref(d), ctypes.byref(prev_cam), hits.ctypes.data, surface.ctypes.data, prev_scene.desc_ptr,
+                                       motion.ctypes.data if len(motion) else ctypes.addressof(ctypes.c_char()), len(motion), out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_motion_vectors_deform: what motion_vectors refuses, or a table of another length than prev_scene's node count")
+    return out
 
 
 def motion_vectors(prev_cam, hits, motion, width, height):
@@ -1203,6 +1274,12 @@ def hit_dtype():
                      ("p", np.float32, 3), ("pad0", np.float32), ("N", np.float32, 3), ("pad1", np.float32)])
 
 
+def surface_dtype():
+    """numpy layout of RtuRaySurface (32 bytes): mesh, face, bc[3], uvw[3]."""
+    import numpy as np
+    return np.dtype([("mesh", np.int32), ("face", np.int32), ("bc", np.float32, 3), ("uvw", np.float32, 3)])
+
+
 def _as_rays(rays):
     """A contiguous RtuRay array from a structured array of ray_dtype() or a float32 [n, 8] array {org, tmax, dir, reserved}."""
     import numpy as np
@@ -1786,6 +1863,20 @@ class Temporal:
         motion = _as_motion(motion)
         self._check(hip.rtu_temporal_frame_moved_device(self._h, ctypes.byref(frame), motion.ctypes.data, len(motion), int(history_cap), d_rgbz, stream))
 
+    def frame_deformed(self, frame, motion, history_cap=0):
+        """frame_moved() that follows deforming meshes (rtu_temporal_frame_deformed): `motion` is scene_motion(previous scene, scene
+        now, deform_meshes=[...]) — the meshes given to the ONE update_meshes since the previous frame —, the context has
+        keep_previous_vertices(True); a plain, denoise or variance session. rgbz float32 [H, W, 4] (synchronous)."""
+        import numpy as np
+        motion = _as_motion(motion)
+        out = np.empty((self.desc.height, self.desc.width, 4), np.float32)
+        self._check(hip.rtu_temporal_frame_deformed(self._h, ctypes.byref(frame), motion.ctypes.data, len(motion), int(history_cap), out.ctypes.data))
+        return out
+
+    def frame_deformed_device(self, frame, motion, d_rgbz, history_cap=0, stream=None):
+        motion = _as_motion(motion)
+        self._check(hip.rtu_temporal_frame_deformed_device(self._h, ctypes.byref(frame), motion.ctypes.data, len(motion), int(history_cap), d_rgbz, stream))
+
     def sensor_frame(self, desc):
         """The next frame of the session through the sensor `desc` (an RtuSensorDesc of recipe S / P and of the session's size; a plain,
         denoise or variance session): rgbz float32 [H, W, 4] (synchronous). Camera and sensor frames may alternate: a frame after one
@@ -2087,6 +2178,26 @@ class Context:
         """rtu_motion_vectors_device: motion_vectors() on device memory, width * height float4 to d_mv_ptr."""
         self._check(hip.rtu_motion_vectors_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam), d_hits_ptr, d_motion_ptr, n_nodes, d_mv_ptr, stream))
 
+    def keep_previous_vertices(self, on=True):
+        """rtu_keep_previous_vertices: with it on, update_meshes keeps the positions and normals it replaces as the listed meshes'
+        previous generation (what temporal_accumulate_deform_device reads); default off."""
+        self._check(hip.rtu_keep_previous_vertices(self._h, 1 if on else 0))
+
+    def temporal_accumulate_deform_device(self, desc, prev_cam, cur_cam, d_rgbz_ptr, d_hits_ptr, d_albedo_ptr, d_surface_ptr, d_hist_prev_ptr,
+                                          d_hist_out_ptr, d_rgbz_out_ptr, d_motion_ptr, n_nodes, history_cap=0, moments=False, stream=None):
+        """rtu_temporal_accumulate_deform_device / _deform_moments_device: temporal_accumulate_deform() on device memory, the same bits;
+        connectivity and previous vertices are the context's own (keep_previous_vertices must be on); d_surface_ptr: the frame's
+        RtuRaySurface records (frame_surface_device), 16-byte aligned."""
+        call = hip.rtu_temporal_accumulate_deform_moments_device if moments else hip.rtu_temporal_accumulate_deform_device
+        self._check(call(self._h, ctypes.byref(desc), ctypes.byref(prev_cam) if prev_cam is not None else None, ctypes.byref(cur_cam), d_rgbz_ptr,
+                         d_hits_ptr, d_albedo_ptr, d_surface_ptr, d_hist_prev_ptr, d_hist_out_ptr, d_rgbz_out_ptr, d_motion_ptr, n_nodes,
+                         int(history_cap), stream))
+
+    def motion_vectors_deform_device(self, desc, prev_cam, d_hits_ptr, d_surface_ptr, d_motion_ptr, n_nodes, d_mv_ptr, stream=None):
+        """rtu_motion_vectors_deform_device: motion_vectors_deform() on device memory, width * height float4 to d_mv_ptr."""
+        self._check(hip.rtu_motion_vectors_deform_device(self._h, ctypes.byref(desc), ctypes.byref(prev_cam), d_hits_ptr, d_surface_ptr, d_motion_ptr,
+                                                         n_nodes, d_mv_ptr, stream))
+
     def set_cancel(self, flag):
         """rtu_set_cancel_flag: a ctypes.c_int the library polls between sample batches (None: none)."""
         self._cancel = flag
@@ -2244,6 +2355,37 @@ class Context:
     def frame_features_device(self, frame, d_hits_ptr, d_albedo_ptr, stream=None):
         """rtu_frame_features_device: width * height RtuRayHit and float4 albedo into device memory, asynchronous on `stream`."""
         self._check(hip.rtu_frame_features_device(self._h, ctypes.byref(frame), d_hits_ptr, d_albedo_ptr, stream))
+
+    def ray_surface(self, rays, reference_walk=False):
+        """ray_features with the surface record of every ray (rtu_ray_surface): (hits, albedo, surface [n] of surface_dtype()). On a
+        triangle-mesh hit surface holds the mesh, the face (an index into the mesh's f / fn / ft) and the weights of its three
+        vertices that the hit point, normal and texture coordinate were interpolated with; mesh = face = -1 elsewhere. uvw is the
+        hit's texture coordinate on every kind of object."""
+        import numpy as np
+        r = _as_rays(rays)
+        hits, albedo, surface = np.zeros(r.size, hit_dtype()), np.zeros((r.size, 4), np.float32), np.zeros(r.size, surface_dtype())
+        self._check(hip.rtu_ray_surface(self._h, r.ctypes.data if r.size else None, r.size, RTU_QUERY_REFERENCE_WALK if reference_walk else 0,
+                                        hits.ctypes.data if r.size else None, albedo.ctypes.data if r.size else None,
+                                        surface.ctypes.data if r.size else None))
+        return hits, albedo, surface
+
+    def ray_surface_device(self, d_rays_ptr, n, d_hits_ptr, d_albedo_ptr, d_surface_ptr, stream=None, reference_walk=False, flags=None):
+        """rtu_ray_surface_device: ray_features_device and n RtuRaySurface at d_surface_ptr (16-byte aligned), asynchronous on `stream`."""
+        f = flags if flags is not None else (RTU_QUERY_REFERENCE_WALK if reference_walk else 0)
+        self._check(hip.rtu_ray_surface_device(self._h, d_rays_ptr, n, f, d_hits_ptr, d_albedo_ptr, d_surface_ptr, stream))
+
+    def frame_surface(self, frame):
+        """rtu_frame_surface: ray_surface of the pixel-centre rays of `frame`: (hits [H * W], albedo [H * W, 4], surface [H * W])."""
+        import numpy as np
+        n = max(frame.width, 0) * max(frame.height, 0)
+        hits, albedo, surface = np.zeros(n, hit_dtype()), np.zeros((n, 4), np.float32), np.zeros(n, surface_dtype())
+        self._check(hip.rtu_frame_surface(self._h, ctypes.byref(frame), hits.ctypes.data if n else None, albedo.ctypes.data if n else None,
+                                          surface.ctypes.data if n else None))
+        return hits, albedo, surface
+
+    def frame_surface_device(self, frame, d_hits_ptr, d_albedo_ptr, d_surface_ptr, stream=None):
+        """rtu_frame_surface_device: frame_features_device and width * height RtuRaySurface into device memory, asynchronous on `stream`."""
+        self._check(hip.rtu_frame_surface_device(self._h, ctypes.byref(frame), d_hits_ptr, d_albedo_ptr, d_surface_ptr, stream))
 
     def denoise_device(self, desc, d_in_ptr, d_hits_ptr, d_albedo_ptr, d_out_ptr, stream=None):
         """rtu_denoise_device: the filter of denoise() on device memory (desc.width * desc.height float4 / RtuRayHit / float4), the same

@@ -64,8 +64,17 @@ struct RtuContext {
     LlBuilder* llb = nullptr;                // the device builder of the occluder lists (rtu_scene_update.hip)
     // what rtu_update_meshes needs of a mesh beyond its device record: the node ranges of the levels of its collapsed fast trees
     // (root first, [levels + 1]) and which of scene_allocs holds its ref.bvh (the one per-mesh buffer whose size an update can change)
-    struct MeshRefit { std::vector<uint32_t> lvl4, lvl8; size_t ref_bvh_alloc = 0; };
+    struct MeshRefit { std::vector<uint32_t> lvl4, lvl8; size_t ref_bvh_alloc = 0, v_alloc = 0, vn_alloc = 0; };
     std::vector<MeshRefit> refit;
+    // rtu_keep_previous_vertices: a mesh's positions and normals as they were before the last rtu_update_meshes — the buffers that
+    // update swapped out of scene_allocs (valid), else "previous" is "current". df_*: the table the deform accumulator's kernels read
+    // (TpDeformScene, rtu_temporal.h), rebuilt after an upload, an update or a change of the switch (df_dirty).
+    bool keep_prev = false;
+    struct PrevGen { DevBuf<char> v, vn; bool valid = false; };
+    std::vector<PrevGen> prev_gen;
+    DevBuf<TpDeformMesh> df_meshes;
+    DevBuf<int32_t>      df_nodes;
+    bool                 df_dirty = true;
     bool  mu_timing = false;                 // rtu_debug_mesh_update_timing: HIP events around the phases of rtu_update_meshes
     float mu_ms[4] = {};                     // copies, records, refit, placement: summed since the last read
     hipEvent_t mu_ev[5] = {};
@@ -148,6 +157,7 @@ struct RtuContext {
     DevBuf<float4>  q_rays, q_hits;          // ray queries, host forms (rtu_trace_rays / rtu_occluded_rays): one chunk of rays and of answers
     DevBuf<uint8_t> q_occ;
     DevBuf<float4>  ft_albedo;               // first-hit features, host forms (rtu_ray_features / rtu_frame_features): one chunk of albedo (rays and hits: q_rays, q_hits)
+    DevBuf<float4>  ft_surface;              // ... and of surface records (rtu_ray_surface / rtu_frame_surface), two float4 each: grown by those two only
     DevBuf<float4>  dn_planes;               // the denoising filter (rtu_denoise_device): its four planes gN, gP, e0, e1 of one frame
     DevBuf<float4>  sh_rays, sh_out;         // ray batches, host form (rtu_shade_rays): one chunk of rays and of {r, g, b, t}
     DevBuf<uint32_t> sh_keys;                // ... and of keys (rtu_shade_rays_sampled)
@@ -194,6 +204,8 @@ int fail(RtuContext* ctx, int code, const char* fmt, ...) {
 
 void free_scene(RtuContext* ctx) {
     ctx->scene_allocs.clear();
+    ctx->prev_gen.clear();  // after an upload "previous" is "current"
+    ctx->df_dirty = true;
     ctx->place.clear();
     ctx->has_scene = false;
 }
@@ -1863,6 +1875,7 @@ struct RtuTemporal {
     bool             variance = false;    // rtu_temporal_begin_variance: hist[] have four planes, a frame ends with k_variance and the filter
     RtuVarianceDesc  vdesc{};
     DevBuf<float>    var;                 // ... the variance of the frame
+    DevBuf<float4>   surface;             // rtu_temporal_frame_deformed: the frame's surface records (two float4 per pixel), grown by the first such frame
     bool             steered = false;     // rtu_temporal_begin_steered: a frame goes on with the allocation, the extra rays and the fold
     RtuSteerDesc     sdesc{};
     size_t           st_cap = 0;          // ... rays of a frame at most: min(budget, pixels * max_extra)
@@ -1904,6 +1917,7 @@ static void temporal_release(RtuTemporal* t) {
     t->motion.reset();
     t->motion_host.reset();
     t->var.reset();
+    t->surface.reset();
     t->st_counts.reset();
     t->st_offsets.reset();
     t->st_total_dev.reset();
@@ -2272,6 +2286,26 @@ int write_meshes(RtuContext* ctx, const RtuSceneDesc* s, const uint32_t* mesh_id
     if (timing && !ctx->mu_ev[0])
         for (hipEvent_t& e : ctx->mu_ev) RTU_HIP(ctx, hipEventCreate(&e));
     std::vector<std::vector<RtuBvhNode>> trees((size_t)n_meshes);  // host sources of asynchronous copies: alive until the wait below
+    if (ctx->keep_prev) {
+        // The replaced v and vn become the listed meshes' previous generation: the two grow-only buffers change places (the first such
+        // update of a mesh allocates the second pair, later ones nothing), and the new arrays are written into what was the previous
+        // one. For every other mesh "previous" is "current" again: previous means before THIS update only.
+        ctx->prev_gen.resize(ctx->dmeshes.size());
+        for (RtuContext::PrevGen& g : ctx->prev_gen) g.valid = false;
+        for (int i = 0; i < n_meshes; i++) {
+            const uint32_t id = mesh_ids[i];
+            RtuContext::PrevGen& g = ctx->prev_gen[id];
+            DevBuf<char>&v = ctx->scene_allocs[ctx->refit[id].v_alloc], &vn = ctx->scene_allocs[ctx->refit[id].vn_alloc];
+            RTU_HIP(ctx, g.v.grow(v.size()));
+            RTU_HIP(ctx, g.vn.grow(vn.size()));
+            std::swap(g.v, v);
+            std::swap(g.vn, vn);
+            g.valid = true;
+            ctx->dmeshes[id].v = reinterpret_cast<const float*>(v.get());
+            ctx->dmeshes[id].vn = reinterpret_cast<const float*>(vn.get());
+        }
+    }
+    ctx->df_dirty = true;
     if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mu_ev[0], st));
     for (int i = 0; i < n_meshes; i++) {
         const uint32_t id = mesh_ids[i];
@@ -2391,8 +2425,10 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
         if (need4 > stack_needed) stack_needed = need4;
         if (sah.depth > stack_needed) stack_needed = sah.depth;
         if ((rc = upload(ctx, m.f, (size_t)m.nf * 3, &d.f)) != RTU_OK) return rc;
+        refit[mi].v_alloc = ctx->scene_allocs.size();  // the allocation the next line makes
         if ((rc = upload(ctx, m.v, (size_t)m.nv * 3, &d.v)) != RTU_OK) return rc;
         if ((rc = upload(ctx, m.fn, (size_t)m.nf * 3, &d.fn)) != RTU_OK) return rc;
+        refit[mi].vn_alloc = ctx->scene_allocs.size();
         if ((rc = upload(ctx, m.vn, (size_t)m.nvn * 3, &d.vn)) != RTU_OK) return rc;
         d.vt = nullptr;
         d.ft = nullptr;
@@ -2758,17 +2794,33 @@ bool node_chain(const RtuSceneDesc* s, uint32_t i, Affine64& W, Affine64& Winv) 
 }
 }  // namespace
 
+static int scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* deform_mesh_ids, int n_deform, const uint32_t* reset_mesh_ids,
+                        int n_reset, RtuNodeMotion* out);
+
 int rtu_scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* reset_mesh_ids, int n_reset, RtuNodeMotion* out) {
-    if (!prev || !cur || !out || n_reset < 0 || (n_reset > 0 && !reset_mesh_ids)) return RTU_ERR_ARG;
+    return scene_motion(prev, cur, nullptr, 0, reset_mesh_ids, n_reset, out);
+}
+
+int rtu_scene_motion_deform(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* deform_mesh_ids, int n_deform,
+                            const uint32_t* reset_mesh_ids, int n_reset, RtuNodeMotion* out) {
+    return scene_motion(prev, cur, deform_mesh_ids, n_deform, reset_mesh_ids, n_reset, out);
+}
+
+static int scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* deform_mesh_ids, int n_deform, const uint32_t* reset_mesh_ids,
+                        int n_reset, RtuNodeMotion* out) {
+    if (!prev || !cur || !out || n_reset < 0 || (n_reset > 0 && !reset_mesh_ids) || n_deform < 0 || (n_deform > 0 && !deform_mesh_ids)) return RTU_ERR_ARG;
     if ((prev->n_meshes && !prev->meshes) || (cur->n_meshes && !cur->meshes)) return RTU_ERR_ARG;
     for (int k = 0; k < n_reset; k++)
         if (reset_mesh_ids[k] >= cur->n_meshes) return RTU_ERR_ARG;
+    for (int k = 0; k < n_deform; k++)
+        if (deform_mesh_ids[k] >= cur->n_meshes) return RTU_ERR_ARG;
     // the shape rule of rtu_update_scene, except that a RESET mesh may have a reference tree of another size, as rtu_update_meshes allows
     RtuSceneDesc before = *prev;
     std::vector<RtuMesh> want;
-    if (n_reset > 0 && prev->n_meshes == cur->n_meshes) {
+    if (n_reset + n_deform > 0 && prev->n_meshes == cur->n_meshes) {  // (a DEFORM mesh went through rtu_update_meshes as well)
         want.assign(prev->meshes, prev->meshes + prev->n_meshes);
         for (int k = 0; k < n_reset; k++) want[reset_mesh_ids[k]].n_bvh_nodes = cur->meshes[reset_mesh_ids[k]].n_bvh_nodes;
+        for (int k = 0; k < n_deform; k++) want[deform_mesh_ids[k]].n_bvh_nodes = cur->meshes[deform_mesh_ids[k]].n_bvh_nodes;
         before.meshes = want.data();
     }
     const int rc = rtu_scene_shape_diff(&before, cur, nullptr, 0);
@@ -2798,9 +2850,41 @@ int rtu_scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const ui
                 o.m[4 * r + 3] = (float)m.b[r];
             }
         }
+        bool reset = false, deform = false;
         for (int k = 0; k < n_reset; k++)
-            if (cur->nodes[i].mesh_id >= 0 && (uint32_t)cur->nodes[i].mesh_id == reset_mesh_ids[k]) o.flags |= RTU_MOTION_RESET;
+            if (cur->nodes[i].mesh_id >= 0 && (uint32_t)cur->nodes[i].mesh_id == reset_mesh_ids[k]) reset = true;
+        for (int k = 0; k < n_deform; k++)
+            if (cur->nodes[i].mesh_id >= 0 && (uint32_t)cur->nodes[i].mesh_id == deform_mesh_ids[k]) deform = true;
+        if (reset) {
+            o.flags |= RTU_MOTION_RESET;  // (also a mesh in both lists)
+        } else if (deform) {
+            // a point of a deforming surface is given in the node's own coordinates (face, weights over the previous vertices):
+            // m = W_prev, g = the transpose of the linear part of W_prev^-1
+            Affine64 Wp, Wpi;
+            if (!node_chain(prev, i, Wp, Wpi)) return RTU_ERR_ARG;
+            memset(&o, 0, sizeof o);
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) {
+                    o.m[4 * r + c] = (float)Wp.A[3 * r + c];
+                    o.g[3 * r + c] = (float)Wpi.A[3 * c + r];
+                }
+                o.m[4 * r + 3] = (float)Wp.b[r];
+            }
+            o.flags = RTU_MOTION_DEFORM;
+        }
     }
+    return RTU_OK;
+}
+
+int rtu_keep_previous_vertices(RtuContext* ctx, int on) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (ctx->keep_prev != (on != 0)) {
+        RTU_HIP(ctx, hipSetDevice(ctx->device));
+        RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (launches that read a previous generation)
+        for (RtuContext::PrevGen& g : ctx->prev_gen) g.valid = false;  // previous is current until the next update
+        ctx->df_dirty = true;
+    }
+    ctx->keep_prev = on != 0;
     return RTU_OK;
 }
 
@@ -3671,26 +3755,36 @@ static int feature_cam(RtuContext* ctx, const RtuFrameDesc* f, FeatureCam& cam) 
 
 static bool misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
-// chunks of rays (h_rays) or of a frame's pixels in image order (cam) through q_rays / q_hits / ft_albedo
-static int features_host(RtuContext* ctx, const RtuRay* h_rays, const FeatureCam* cam, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo) {
+// chunks of rays (h_rays) or of a frame's pixels in image order (cam) through q_rays / q_hits / ft_albedo; h_surface (the surface
+// entries): the kernels with one more output, through ft_surface
+static int features_host(RtuContext* ctx, const RtuRay* h_rays, const FeatureCam* cam, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo,
+                         RtuRaySurface* h_surface = nullptr) {
     const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
     RTU_HIP(ctx, hipSetDevice(ctx->device));
     if (h_rays) RTU_HIP(ctx, ctx->q_rays.grow(2 * chunk));
     RTU_HIP(ctx, ctx->q_hits.grow(3 * chunk));
     RTU_HIP(ctx, ctx->ft_albedo.grow(chunk));
+    if (h_surface) RTU_HIP(ctx, ctx->ft_surface.grow(2 * chunk));
     const DevScene s = query_scene(ctx);
+    const bool ref = (flags & RTU_QUERY_REFERENCE_WALK) != 0;
     for (size_t done = 0; done < n; done += chunk) {
         const size_t m = n - done < chunk ? n - done : chunk;
         hipError_t e = hipSuccess;
         if (h_rays) {
             e = hipMemcpyAsync(ctx->q_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = (hipError_t)rtu_launch_ray_features(s, ctx->q_rays.get(), ctx->q_hits.get(), ctx->ft_albedo.get(), m,
-                                                                         (flags & RTU_QUERY_REFERENCE_WALK) != 0, ctx->stream);
+            if (e == hipSuccess && h_surface)
+                e = (hipError_t)rtu_launch_ray_surface(s, ctx->q_rays.get(), ctx->q_hits.get(), ctx->ft_albedo.get(), ctx->ft_surface.get(), m, ref, ctx->stream);
+            else if (e == hipSuccess)
+                e = (hipError_t)rtu_launch_ray_features(s, ctx->q_rays.get(), ctx->q_hits.get(), ctx->ft_albedo.get(), m, ref, ctx->stream);
+        } else if (h_surface) {
+            e = (hipError_t)rtu_launch_frame_surface(s, *cam, done, m, ctx->q_hits.get(), ctx->ft_albedo.get(), ctx->ft_surface.get(), ctx->stream);
         } else {
             e = (hipError_t)rtu_launch_frame_features(s, *cam, done, m, ctx->q_hits.get(), ctx->ft_albedo.get(), ctx->stream);
         }
         if (e == hipSuccess) e = hipMemcpyAsync(h_hits + done, ctx->q_hits.get(), sizeof(RtuRayHit) * m, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(h_albedo + 4 * done, ctx->ft_albedo.get(), sizeof(float4) * m, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && h_surface)
+            e = hipMemcpyAsync(h_surface + done, ctx->ft_surface.get(), sizeof(RtuRaySurface) * m, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "first-hit features: %s", hipGetErrorString(e));
     }
@@ -3742,6 +3836,57 @@ int rtu_frame_features(RtuContext* ctx, const RtuFrameDesc* frame, RtuRayHit* h_
     if (!h_hits || !h_albedo) return fail(ctx, RTU_ERR_ARG, "hits / albedo pointer is NULL");
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
     return features_host(ctx, nullptr, &cam, (size_t)cam.width * (size_t)cam.height, 0, h_hits, h_albedo);
+}
+
+// ---- surface records: the features with the winning triangle and the texture coordinate (k_features_surface, rtu_features.hip) ----
+static_assert(sizeof(RtuRaySurface) == 32, "a surface record is two float4");
+
+int rtu_ray_surface_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* d_albedo, void* d_surface,
+                           void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (n && (!d_albedo || !d_surface)) return fail(ctx, RTU_ERR_ARG, "albedo / surface pointer is NULL");
+    if (n && (misaligned(d_albedo) || misaligned(d_surface))) return fail(ctx, RTU_ERR_ARG, "device albedo / surface buffers must be 16-byte aligned");
+    const int rc = query_args(ctx, d_rays, d_hits, n, flags, true);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_ray_surface(query_scene(ctx), (const float4*)d_rays, (float4*)d_hits, (float4*)d_albedo, (float4*)d_surface, n,
+                                                            (flags & RTU_QUERY_REFERENCE_WALK) != 0, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "surface records launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_ray_surface(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, RtuRayHit* h_hits, float* h_albedo, RtuRaySurface* h_surface) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (n && (!h_albedo || !h_surface)) return fail(ctx, RTU_ERR_ARG, "albedo / surface pointer is NULL");
+    const int rc = query_args(ctx, h_rays, h_hits, n, flags, false);
+    if (rc != RTU_OK || n == 0) return rc;
+    return features_host(ctx, h_rays, nullptr, n, flags, h_hits, h_albedo, h_surface);
+}
+
+int rtu_frame_surface_device(RtuContext* ctx, const RtuFrameDesc* frame, void* d_hits, void* d_albedo, void* d_surface, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    FeatureCam cam;
+    const int rc = feature_cam(ctx, frame, cam);
+    if (rc != RTU_OK) return rc;
+    if (!d_hits || !d_albedo || !d_surface) return fail(ctx, RTU_ERR_ARG, "hits / albedo / surface pointer is NULL");
+    if (misaligned(d_hits) || misaligned(d_albedo) || misaligned(d_surface))
+        return fail(ctx, RTU_ERR_ARG, "device hits / albedo / surface buffers must be 16-byte aligned");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_frame_surface(query_scene(ctx), cam, 0, (unsigned long long)cam.width * (unsigned long long)cam.height,
+                                                              (float4*)d_hits, (float4*)d_albedo, (float4*)d_surface, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "surface records launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_frame_surface(RtuContext* ctx, const RtuFrameDesc* frame, RtuRayHit* h_hits, float* h_albedo, RtuRaySurface* h_surface) {
+    if (!ctx) return RTU_ERR_ARG;
+    FeatureCam cam;
+    const int rc = feature_cam(ctx, frame, cam);
+    if (rc != RTU_OK) return rc;
+    if (!h_hits || !h_albedo || !h_surface) return fail(ctx, RTU_ERR_ARG, "hits / albedo / surface pointer is NULL");
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    return features_host(ctx, nullptr, &cam, (size_t)cam.width * (size_t)cam.height, 0, h_hits, h_albedo, h_surface);
 }
 
 int rtu_denoise_device(RtuContext* ctx, const RtuDenoiseDesc* desc, const void* d_in, const void* d_hits, const void* d_albedo, void* d_out,
@@ -4246,6 +4391,85 @@ int rtu_temporal_accumulate_motion_device(RtuContext* ctx, const RtuTemporalDesc
                                                                 (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo, (const float4*)d_hist_prev,
                                                                 (float4*)d_hist_out, (float4*)d_rgbz_out, d_motion, (hipStream_t)hip_stream);
     if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+// The deform forms on the device: the motion / moments form with the surface records, the context's own connectivity and the previous
+// vertices it kept. RTU_OK: *D is the table the kernels read (rebuilt here after an upload, an update or a change of the switch).
+static int deform_scene(RtuContext* ctx, uint32_t n_nodes, const void* d_surface, TpDeformScene* D) {
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (!ctx->keep_prev) return fail(ctx, RTU_ERR_ARG, "deform: rtu_keep_previous_vertices is off");
+    if (!d_surface || misaligned(d_surface)) return fail(ctx, RTU_ERR_ARG, "deform: the surface records are NULL or not 16-byte aligned");
+    if ((size_t)n_nodes != ctx->shape_nodes.size()) return fail(ctx, RTU_ERR_ARG, "deform: n_nodes is not the uploaded scene's node count");
+    const size_t nm = ctx->dmeshes.size();
+    if (ctx->df_dirty) {
+        std::vector<TpDeformMesh> meshes(nm);
+        for (size_t i = 0; i < nm; i++) {
+            const DevMesh& d = ctx->dmeshes[i];
+            const bool prev = i < ctx->prev_gen.size() && ctx->prev_gen[i].valid;
+            meshes[i] = TpDeformMesh{d.f, d.fn, prev ? reinterpret_cast<const float*>(ctx->prev_gen[i].v.get()) : d.v,
+                                     prev ? reinterpret_cast<const float*>(ctx->prev_gen[i].vn.get()) : d.vn, ctx->shape_meshes[i].nf, 0};
+        }
+        std::vector<int32_t> node_mesh(n_nodes);
+        for (uint32_t i = 0; i < n_nodes; i++) node_mesh[i] = ctx->shape_nodes[i].mesh_id;
+        RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RTU_HIP(ctx, ctx->df_meshes.grow(nm ? nm : 1));
+        RTU_HIP(ctx, ctx->df_nodes.grow(n_nodes ? n_nodes : 1));
+        if (nm) RTU_HIP(ctx, hipMemcpy(ctx->df_meshes.get(), meshes.data(), sizeof(TpDeformMesh) * nm, hipMemcpyHostToDevice));
+        if (n_nodes) RTU_HIP(ctx, hipMemcpy(ctx->df_nodes.get(), node_mesh.data(), sizeof(int32_t) * n_nodes, hipMemcpyHostToDevice));
+        ctx->df_dirty = false;
+    }
+    *D = TpDeformScene{ctx->df_meshes.get(), ctx->df_nodes.get(), (uint32_t)nm, 0};
+    return RTU_OK;
+}
+
+static int temporal_deform_device(RtuContext* ctx, bool moments, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                  const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_surface, const void* d_hist_prev,
+                                  void* d_hist_out, void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
+    int rc = temporal_device_args(ctx, moments ? 4 : 3, true, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_hist_prev, d_hist_out, d_rgbz_out, d_motion,
+                                  n_nodes, history_cap);
+    if (rc != RTU_OK) return rc;
+    TpDeformScene D;
+    if ((rc = deform_scene(ctx, n_nodes, d_surface, &D)) != RTU_OK) return rc;
+    const hipError_t e = (hipError_t)rtu_launch_temporal_deform(tp_motion_setup(*desc, *prev_cam, *cur_cam, d_hist_prev != nullptr, n_nodes, history_cap), moments,
+                                                                D, (const float4*)d_rgbz, (const float4*)d_hits, (const float4*)d_albedo,
+                                                                (const float4*)d_surface, (const float4*)d_hist_prev, (float4*)d_hist_out, (float4*)d_rgbz_out,
+                                                                d_motion, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "temporal launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_temporal_accumulate_deform_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                          const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_surface, const void* d_hist_prev,
+                                          void* d_hist_out, void* d_rgbz_out, const RtuNodeMotion* d_motion, uint32_t n_nodes, int32_t history_cap,
+                                          void* hip_stream) {
+    return temporal_deform_device(ctx, false, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_surface, d_hist_prev, d_hist_out, d_rgbz_out, d_motion, n_nodes,
+                                  history_cap, hip_stream);
+}
+
+int rtu_temporal_accumulate_deform_moments_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam,
+                                                  const void* d_rgbz, const void* d_hits, const void* d_albedo, const void* d_surface,
+                                                  const void* d_hist_prev, void* d_hist_out, void* d_rgbz_out, const RtuNodeMotion* d_motion,
+                                                  uint32_t n_nodes, int32_t history_cap, void* hip_stream) {
+    return temporal_deform_device(ctx, true, desc, prev_cam, cur_cam, d_rgbz, d_hits, d_albedo, d_surface, d_hist_prev, d_hist_out, d_rgbz_out, d_motion, n_nodes,
+                                  history_cap, hip_stream);
+}
+
+int rtu_motion_vectors_deform_device(RtuContext* ctx, const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const void* d_hits, const void* d_surface,
+                                     const RtuNodeMotion* d_motion, uint32_t n_nodes, void* d_mv, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (rtu_temporal_check_desc(desc) != RTU_OK) return fail(ctx, RTU_ERR_ARG, "%s", kTemporalDescRules);
+    if (!prev_cam || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return fail(ctx, RTU_ERR_ARG, "motion vectors: the previous camera must have the desc's width and height");
+    if (!d_hits || !d_motion || !d_mv) return fail(ctx, RTU_ERR_ARG, "motion vectors: a device pointer is NULL");
+    if (misaligned(d_hits) || misaligned(d_motion) || misaligned(d_mv)) return fail(ctx, RTU_ERR_ARG, "motion vectors: device buffers must be 16-byte aligned");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    TpDeformScene D;
+    const int rc = deform_scene(ctx, n_nodes, d_surface, &D);
+    if (rc != RTU_OK) return rc;
+    const hipError_t e = (hipError_t)rtu_launch_motion_vectors_deform(tp_setup(*desc, *prev_cam, *prev_cam, true), n_nodes, D, (const float4*)d_hits,
+                                                                      (const float4*)d_surface, d_motion, (float4*)d_mv, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "motion vector launch: %s", hipGetErrorString(e));
     return RTU_OK;
 }
 
@@ -4901,6 +5125,7 @@ struct TemporalMoved {
     const RtuNodeMotion* h_motion;
     uint32_t n_nodes;
     int32_t  history_cap;
+    bool     deformed;  // rtu_temporal_frame_deformed: the guides with surface records, the deform accumulator
 };
 
 static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgbz, void* hip_stream, const TemporalMoved* moved);
@@ -4911,7 +5136,13 @@ int rtu_temporal_frame_device(RtuTemporal* t, const RtuFrameDesc* frame, void* d
 
 int rtu_temporal_frame_moved_device(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
                                     void* d_rgbz, void* hip_stream) {
-    const TemporalMoved moved{h_motion, n_nodes, history_cap};
+    const TemporalMoved moved{h_motion, n_nodes, history_cap, false};
+    return temporal_frame(t, frame, d_rgbz, hip_stream, &moved);
+}
+
+int rtu_temporal_frame_deformed_device(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                                       void* d_rgbz, void* hip_stream) {
+    const TemporalMoved moved{h_motion, n_nodes, history_cap, true};
     return temporal_frame(t, frame, d_rgbz, hip_stream, &moved);
 }
 
@@ -4919,6 +5150,10 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     if (!t || !t->ctx) return RTU_ERR_ARG;
     RtuContext* ctx = t->ctx;
     if (!frame) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
+    const bool deformed = moved && moved->deformed;
+    if (deformed && (t->steered || t->gradient || t->sparse || t->hl_cap))
+        return fail(ctx, RTU_ERR_UNSUPPORTED, "a deformed frame: plain, RTU_TEMPORAL_DENOISE and variance sessions only");
+    if (deformed && !ctx->keep_prev) return fail(ctx, RTU_ERR_ARG, "a deformed frame needs rtu_keep_previous_vertices");
     if (frame->width != t->desc.width || frame->height != t->desc.height) return fail(ctx, RTU_ERR_ARG, "the frame has not the session's width and height");
     if (frame->shard_count != 1 || frame->shard_rank != 0) return fail(ctx, RTU_ERR_ARG, "a temporal session renders the whole image: shard_count must be 1");
     if (frame->samples < 1) return fail(ctx, RTU_ERR_ARG, "a temporal frame is a recipe S / P frame (samples >= 1)");
@@ -4943,8 +5178,12 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         if (moved->n_nodes != (uint32_t)ctx->shape_nodes.size())
             return fail(ctx, RTU_ERR_ARG, "the motion table has %u entries, the uploaded scene %u nodes", moved->n_nodes, (uint32_t)ctx->shape_nodes.size());
         if (!moved->h_motion && t->has_hist) return fail(ctx, RTU_ERR_ARG, "the motion table is NULL");
-        if (rtu_temporal_check_motion(moved->h_motion, moved->n_nodes, moved->history_cap) != RTU_OK)
+        if (rtu_temporal_check_motion(moved->h_motion, moved->n_nodes, moved->history_cap, deformed) != RTU_OK)
             return fail(ctx, RTU_ERR_ARG, "motion: history_cap 0 .. 65535, known flags and reserved words 0 in every table entry");
+    }
+    if (deformed) {
+        RTU_HIP(ctx, hipSetDevice(ctx->device));
+        RTU_HIP(ctx, t->surface.grow(2 * n));
     }
     // the table of the frame: a moved frame's (== the scene's node count), or a variance session's all-STATIC one for a plain frame —
     // at least one entry there, the moments form refuses a NULL table. Also on frame 0, which does not use it: a later frame allocates nothing.
@@ -4989,7 +5228,9 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
     // as shade_host: the chain of recipe P is traced once, the shading is what is repeated when the frame records ran out
     if (paths && (rc = paths_chain(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)shaded)) != RTU_OK) return rc;
     if ((rc = shade_until_fits(ctx, f, t->img.get(), stream, t->rays.get(), t->keys.get(), (uint32_t)shaded, paths, nullptr)) != RTU_OK) return rc;
-    if ((rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream)) != RTU_OK) return rc;
+    if (deformed) rc = rtu_frame_surface_device(ctx, frame, t->hits.get(), t->albedo.get(), t->surface.get(), hip_stream);
+    else rc = rtu_frame_features_device(ctx, frame, t->hits.get(), t->albedo.get(), hip_stream);
+    if (rc != RTU_OK) return rc;
     RtuTemporalDesc td = t->desc;
     td.flags = 0;
     if (t->variance) {
@@ -5025,6 +5266,10 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
                 rc = rtu_temporal_accumulate_gradient_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(),
                                                              t->hist[t->cur].get(), t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), n_nodes,
                                                              moved ? moved->history_cap : 0, t->gr_lambda.get(), hip_stream);
+        } else if (deformed) {
+            rc = rtu_temporal_accumulate_deform_moments_device(ctx, &td, has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(),
+                                                               t->albedo.get(), t->surface.get(), has_hist ? t->hist[t->cur].get() : nullptr,
+                                                               t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), n_nodes, moved->history_cap, hip_stream);
         } else {
             rc = rtu_temporal_accumulate_moments_device(ctx, &td, has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
                                                         has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(),
@@ -5039,8 +5284,13 @@ static int temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, void* d_rgb
         // the stream was waited for above: the copy of the frame before has left the staging memory (ONE STREAM PER CONTEXT)
         memcpy(t->motion_host.get(), moved->h_motion, moved->n_nodes * sizeof(RtuNodeMotion));
         RTU_HIP(ctx, hipMemcpyAsync(t->motion.get(), t->motion_host.get(), moved->n_nodes * sizeof(RtuNodeMotion), hipMemcpyHostToDevice, stream));
-        rc = rtu_temporal_accumulate_motion_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(), t->hist[t->cur].get(),
-                                                   t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), moved->n_nodes, moved->history_cap, hip_stream);
+        if (deformed)
+            rc = rtu_temporal_accumulate_deform_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(), t->surface.get(),
+                                                       t->hist[t->cur].get(), t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), moved->n_nodes,
+                                                       moved->history_cap, hip_stream);
+        else
+            rc = rtu_temporal_accumulate_motion_device(ctx, &td, &t->prev_cam, frame, t->img.get(), t->hits.get(), t->albedo.get(), t->hist[t->cur].get(),
+                                                       t->hist[t->cur ^ 1].get(), d_rgbz, t->motion.get(), moved->n_nodes, moved->history_cap, hip_stream);
     } else {  // (frame 0 of a moved session has nothing to look up: the plain form gives its bits)
         rc = rtu_temporal_accumulate_device(ctx, &td, has_hist ? &t->prev_cam : nullptr, frame, t->img.get(), t->hits.get(), t->albedo.get(),
                                             has_hist ? t->hist[t->cur].get() : nullptr, t->hist[t->cur ^ 1].get(), d_rgbz, hip_stream);
@@ -5086,7 +5336,13 @@ static int temporal_frame_host(RtuTemporal* t, const RtuFrameDesc* frame, float*
 int rtu_temporal_frame(RtuTemporal* t, const RtuFrameDesc* frame, float* h_rgbz) { return temporal_frame_host(t, frame, h_rgbz, nullptr); }
 
 int rtu_temporal_frame_moved(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap, float* h_rgbz) {
-    const TemporalMoved moved{h_motion, n_nodes, history_cap};
+    const TemporalMoved moved{h_motion, n_nodes, history_cap, false};
+    return temporal_frame_host(t, frame, h_rgbz, &moved);
+}
+
+int rtu_temporal_frame_deformed(RtuTemporal* t, const RtuFrameDesc* frame, const RtuNodeMotion* h_motion, uint32_t n_nodes, int32_t history_cap,
+                                float* h_rgbz) {
+    const TemporalMoved moved{h_motion, n_nodes, history_cap, true};
     return temporal_frame_host(t, frame, h_rgbz, &moved);
 }
 

@@ -29,5 +29,11 @@ int rtu_launch_ray_features(const DevScene& s, const float4* rays, float4* hits,
 // belongs to pixel first + i. The caller keeps first + n <= width * height.
 int rtu_launch_frame_features(const DevScene& s, const FeatureCam& cam, unsigned long long first, unsigned long long n, float4* hits, float4* albedo,
                               hipStream_t stream);
+// ... both with one more output, surface: n RtuRaySurface (two float4 each: {mesh, face, bc0, bc1}, {bc2, uvw}), 16-byte aligned. hits and
+// albedo get the bytes of the two entries above.
+int rtu_launch_ray_surface(const DevScene& s, const float4* rays, float4* hits, float4* albedo, float4* surface, unsigned long long n, bool reference_walk,
+                           hipStream_t stream);
+int rtu_launch_frame_surface(const DevScene& s, const FeatureCam& cam, unsigned long long first, unsigned long long n, float4* hits, float4* albedo,
+                             float4* surface, hipStream_t stream);
 
 #endif

@@ -463,6 +463,13 @@ struct TriWin {
     uint32_t slot;
     f3 bc;
 };
+// SURF (the one-lane walks only; rtu_features.hip): what the finish of a walk interpolated from — the face as an index into the
+// mesh's f / fn / ft (not a tree slot) and the weights of its vertices 0, 1, 2. Written where h.p / h.N are, so the last write is
+// the winner's.
+struct TriSurf {
+    uint32_t face;
+    f3 bc;
+};
 // Returns 1 when the triangle is accepted (t < h.z), 0 when not. TIE (fast tree only): returns 2
 // when the triangle passes every geometric test with t EXACTLY EQUAL to h.z — which triangle
 // wins then depends on the reference's test order, so the caller falls back to the `ref` tree.
@@ -519,10 +526,10 @@ __device__ __forceinline__ int tri_hit(const TriRec& T, uint32_t slot, const Ray
 //    margin that covers the rounding of the slab and triangle arithmetic (see
 //    DESIGN.md "Culling margin"): every triangle in it would fail `t < hInfo.z`
 //    (objFunctions.cpp:270), so skipping it cannot change any output bit.
-template <int STACK, bool STATS, bool CULL, bool TIE, bool FC = false>
+template <int STACK, bool STATS, bool CULL, bool TIE, bool FC = false, bool SURF = false>
 __device__ __forceinline__ bool mesh_walk(const RTU_CONST DevMesh& mesh, const float4* bvh, const float4* tris, const uint32_t* elements,
                                           const Ray& ray, bool shadow, Hit& h, uint32_t* stk, Counters& cnt, const uint32_t stride, bool& tie,
-                                          const bool fc_lane = true) {
+                                          const bool fc_lane = true, TriSurf* surf = nullptr) {
     // The reference's slab test has special cases for an exactly-zero direction component
     // (objFunctions.cpp:154-216). If ANY lane of the wavefront has one, the whole wavefront
     // takes the literal four-branch form; otherwise the branch-free reciprocal form.
@@ -629,6 +636,7 @@ __device__ __forceinline__ bool mesh_walk(const RTU_CONST DevMesh& mesh, const f
         h.N = norm3(interp(mesh.vn, mesh.fn + 3 * face, win.bc));
         h.p = interp(mesh.v, mesh.f + 3 * face, win.bc);
         h.uvw = mesh.vt ? interp(mesh.vt, mesh.ft + 3 * face, win.bc) : mk3(0, 0, 0);  // GetTexCoord, objFunctions.cpp:320
+        if (SURF) { surf->face = face; surf->bc = win.bc; }
     }
     return hitResult;
 }
@@ -817,9 +825,9 @@ __device__ __forceinline__ TriRec load_tri(GBase tri, uint32_t slot) {
     t.r0 = gload4(tri, o); t.r1 = gload4(tri, o + 16u); t.r2 = gload4(tri, o + 32u); t.r3 = gload4(tri, o + 48u);
     return t;
 }
-template <int STACK, bool FC = false, class MeshT>
+template <int STACK, bool FC = false, bool SURF = false, class MeshT>
 __device__ __forceinline__ bool mesh_walk_fast(const MeshT& mesh, const Ray& ray, bool shadow, Hit& h, uint32_t* stk, Counters& cnt,
-                                               const uint32_t stride, bool& tie, const uint32_t stackLimit) {
+                                               const uint32_t stride, bool& tie, const uint32_t stackLimit, TriSurf* surf = nullptr) {
     const bool fc_lane = true;
     const int slim = (int)(stackLimit < (uint32_t)STACK ? stackLimit : (uint32_t)STACK);
     // The tree collapsed to four children per node (DevMesh::bvh4): half the dependent fetches. Bases in scalar registers,
@@ -924,25 +932,29 @@ __device__ __forceinline__ bool mesh_walk_fast(const MeshT& mesh, const Ray& ray
         h.N = norm3(interp(mesh.vn, mesh.fn + 3 * face, win.bc));
         h.p = interp(mesh.v, mesh.f + 3 * face, win.bc);
         h.uvw = mesh.vt ? interp(mesh.vt, mesh.ft + 3 * face, win.bc) : mk3(0, 0, 0);  // GetTexCoord, objFunctions.cpp:320
+        if (SURF) { surf->face = face; surf->bc = win.bc; }
     }
     return hitResult;
 }
 
 // The counting variant walks the reference's tree; the fast variant walks the SAH tree and
 // falls back to the reference's on an exact tie (see DevMesh).
-template <int STACK, bool STATS, bool CULL, bool FC = false>
+template <int STACK, bool STATS, bool CULL, bool FC = false, bool SURF = false>
 __device__ __forceinline__ bool mesh_hit(const RTU_CONST DevMesh& mesh, const Ray& ray, bool shadow, Hit& h, uint32_t* stk, Counters& cnt,
-                                         const uint32_t stackLimit, const uint32_t stride = 64) {
+                                         const uint32_t stackLimit, const uint32_t stride = 64, TriSurf* surf = nullptr) {
     if (!box_hit(ray, ld3(mesh.bmin), ld3(mesh.bmax), RTU_BIGFLOAT)) return false;
     RTU_CNT(mesh);
     bool tie = false;
-    if (!CULL) return mesh_walk<STACK, STATS, false, false>(mesh, mesh.ref.bvh, mesh.ref.tri, mesh.ref.elements, ray, shadow, h, stk, cnt, stride, tie);
+    if (!CULL)
+        return mesh_walk<STACK, STATS, false, false, false, SURF>(mesh, mesh.ref.bvh, mesh.ref.tri, mesh.ref.elements, ray, shadow, h, stk, cnt, stride, tie,
+                                                                  true, surf);
     const Hit h0 = h;
-    bool r = mesh_walk_fast<STACK, FC>(mesh, ray, shadow, h, stk, cnt, stride, tie, stackLimit);
+    bool r = mesh_walk_fast<STACK, FC, SURF>(mesh, ray, shadow, h, stk, cnt, stride, tie, stackLimit, surf);
     if (tie) {  // rare: two accepted triangles with bitwise-equal t — the reference's test order decides
         h = h0;
         bool t2 = false;
-        r = mesh_walk<STACK, STATS, CULL, false, FC>(mesh, mesh.ref.bvh, mesh.ref.tri, mesh.ref.elements, ray, shadow, h, stk, cnt, stride, t2);
+        r = mesh_walk<STACK, STATS, CULL, false, FC, SURF>(mesh, mesh.ref.bvh, mesh.ref.tri, mesh.ref.elements, ray, shadow, h, stk, cnt, stride, t2, true,
+                                                           surf);
     }
     return r;
 }
@@ -1245,10 +1257,12 @@ __device__ __forceinline__ int mesh_shadow_cells(const uint32_t* cell_tri, uint3
 // has already excluded in the same sense: for primary rays, pixels outside the node's screen rectangle (k_node_rects).
 // INL (with DEFER): the occluder lists are walked HERE, in stage 1 (the inline shading of childless Shade() calls, render_impl.h
 // shadows_inline): `deferred` then means "this ray cannot be settled without a BVH walk".
-template <int STACK, bool STATS, bool CULL, bool DEFER, bool COOP = false, bool TEX = false, bool FC = false, bool ULS = DEFER, bool INL = false, bool FAR = false>
+template <int STACK, bool STATS, bool CULL, bool DEFER, bool COOP = false, bool TEX = false, bool FC = false, bool ULS = DEFER, bool INL = false, bool FAR = false,
+          bool SURF = false>
 __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool shadow, Hit& h, uint32_t* stk, Counters& cnt, bool& deferred,
                                       const uint32_t stride = 64, const float4* lds_nodes = nullptr, const unsigned long long skip = 0,
-                                      const bool rays_bounded = false, const int lslot = -1) {
+                                      const bool rays_bounded = false, const int lslot = -1, TriSurf* surf = nullptr) {
+    static_assert(!SURF || (!COOP && !DEFER), "SURF: the one-lane walks only");
     const bool fc_lane = !COOP || (threadIdx.x & 7u) == 0;
     RTU_TOUCH(t_rays, 1);
     const bool bounds = CULL && s.node_bounds != 0 && !rays_bounded;  // wave-uniform
@@ -1365,7 +1379,7 @@ __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool sha
                 if (DEFER) deferred = true;
                 else if (COOP) hit = box_hit(lr, ld3(mesh.bmin), ld3(mesh.bmax), RTU_BIGFLOAT) &&
                                      mesh_hit_coop<STACK, CULL, FC>(mesh, lr, shadow, h, stk, cnt, stride, lds_nodes, s.walk_stack_limit);
-                else hit = mesh_hit<STACK, STATS, CULL, FC>(mesh, lr, shadow, h, stk, cnt, s.walk_stack_limit);
+                else hit = mesh_hit<STACK, STATS, CULL, FC, SURF>(mesh, lr, shadow, h, stk, cnt, s.walk_stack_limit, 64, surf);
             }
         } else if (DEFER) {
             const RTU_CONST DevMesh& mesh = meshes[n.mesh_id];
@@ -1376,7 +1390,7 @@ __device__ __forceinline__ bool trace(const DevScene& s, const Ray& wr, bool sha
             hit = box_hit(lr, ld3(mesh.bmin), ld3(mesh.bmax), RTU_BIGFLOAT) &&  // TriObj::IntersectRay's own box test (:335)
                   mesh_hit_coop<STACK, CULL, FC>(mesh, lr, shadow, h, stk, cnt, stride, lds_nodes, s.walk_stack_limit);
         } else {
-            hit = (s.dbg & 32u) ? false : mesh_hit<STACK, STATS, CULL, FC>(meshes[n.mesh_id], lr, shadow, h, stk, cnt, s.walk_stack_limit);
+            hit = (s.dbg & 32u) ? false : mesh_hit<STACK, STATS, CULL, FC, SURF>(meshes[n.mesh_id], lr, shadow, h, stk, cnt, s.walk_stack_limit, 64, surf);
         }
         if (hit) {
             any = true;

@@ -167,6 +167,49 @@ RTU_HD bool tp_moved_point(bool in_table, const TpMotion& T, const f3& Pp, const
     return in_table && (T.flags & RTU_MOTION_RESET) == 0 && (is_static || fin);
 }
 
+// ---- deforming meshes (include/rtu_render.h "Temporal accumulation on deforming meshes") ----------------------------------------------
+// What the deform forms read besides the table: per mesh the connectivity and the PREVIOUS vertices and normals, per node its mesh
+// (host memory in the host forms, device memory in the kernels).
+struct TpDeformMesh {
+    const uint32_t* f;
+    const uint32_t* fn;
+    const float*    v;   // previous positions
+    const float*    vn;  // previous normals
+    uint32_t        nf, reserved;
+};
+struct TpDeformScene {
+    const TpDeformMesh* meshes;
+    const int32_t*      node_mesh;  // n_nodes entries: RtuNode.mesh_id
+    uint32_t            n_meshes, reserved;
+};
+
+// cyTriMesh::Interpolate as the walks state it (interp, rtu_intersect.h): (a[i0] bc0 + a[i1] bc1) + a[i2] bc2
+RTU_HD f3 tp_interp(const float* arr, const uint32_t* idx, const f3& bc) {
+    return (ld3(arr + 3 * (size_t)idx[0]) * bc.x + ld3(arr + 3 * (size_t)idx[1]) * bc.y) + ld3(arr + 3 * (size_t)idx[2]) * bc.z;
+}
+
+// What a pixel of the deform forms carries through its table entry T, and whether it may look its history up: for a DEFORM entry
+// the point x and the (unnormalised) normal n of its surface record (s0, s1: the two float4 of an RtuRaySurface) over the previous
+// vertices — false when the record is not of the node's mesh or its face is out of range —, else the hit's own Pp, Np. T.flags loses
+// RTU_MOTION_STATIC where it has RTU_MOTION_DEFORM: such a pixel always reprojects. k: the pixel's table index (>= 0).
+RTU_HD bool tp_deform_source(const TpDeformScene& D, int32_t k, TpMotion& T, const float4& s0, const float4& s1, const f3& Pp, const f3& Np, f3& x, f3& n) {
+    x = Pp;
+    n = Np;
+    if (k < 0 || (T.flags & RTU_MOTION_DEFORM) == 0) return true;
+    T.flags &= ~RTU_MOTION_STATIC;
+    union { float f; int32_t i; } mesh, face;
+    mesh.f = s0.x;
+    face.f = s0.y;
+    const int32_t nm = D.node_mesh[k];
+    if (nm < 0 || (uint32_t)nm >= D.n_meshes || mesh.i != nm) return false;
+    const TpDeformMesh& M = D.meshes[nm];
+    if (face.i < 0 || (uint32_t)face.i >= M.nf) return false;
+    const f3 bc = mk3(s0.z, s0.w, s1.x);
+    x = tp_interp(M.v, M.f + 3 * (size_t)face.i, bc);
+    n = tp_interp(M.vn, M.fn + 3 * (size_t)face.i, bc);
+    return true;
+}
+
 // The previous-image coordinates of world point Pm: false unless s is finite and > 0.
 RTU_HD bool tp_project(const TpParams& P, const f3& Pm, float& fx, float& fy) {
     const f3 pos = ld3(P.pos), nrm = ld3(P.nrm);
@@ -277,10 +320,13 @@ RTU_HD void tp_tap(const TpParams& P, const float4* const* h, int qx, int qy, fl
 // takes no, one or four taps is its own matter. SPARSE: `owner` — the pixel is the one its block shades this frame and rgbz is that
 // sample; for every other pixel nothing of rgbz reaches an output — and *hole, the pixel's mark in the hole plane (without SPARSE
 // neither is used).
-template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false, class PROJ = TpPinhole>
+// DEFORM (with MOVING): what is carried through T is src[0], src[1] of tp_deform_source in place of the hit's point and normal, and
+// there is no lookup unless src_ok.
+template <bool MOVING, bool MOMENTS, bool GRADIENT = false, bool SPARSE = false, class PROJ = TpPinhole, bool DEFORM = false>
 RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT, SPARSE>& A, bool in_table, const TpMotion& T, const float4* const* h, int x, int y, const float4& rgbz,
                      const float4* hit, const float4& albedo, float4& out, float4* o, bool owner = true, uint8_t* hole = nullptr,
-                     const PROJ& proj = PROJ()) {
+                     const PROJ& proj = PROJ(), const f3* src = nullptr, bool src_ok = true) {
+    static_assert(!DEFORM || (MOVING && !GRADIENT && !SPARSE), "the deform forms are the motion and the moments form");
     static_assert(!GRADIENT || (MOVING && MOMENTS), "the gradient form is a moments form");
     static_assert(!SPARSE || (MOVING && MOMENTS && !GRADIENT), "the sparse form is a moments form");
     const TpParams& P = tp_base(A);
@@ -296,7 +342,8 @@ RTU_HD void tp_pixel(const TpArgs<MOVING, GRADIENT, SPARSE>& A, bool in_table, c
     f3 Pm = Pp, Nm = Np;
     bool look = valid && P.lookup != TP_LOOKUP_NONE, one_tap = valid && P.lookup == TP_LOOKUP_STATIC;
     if constexpr (MOVING) {
-        look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && look;
+        if constexpr (DEFORM) look = tp_moved_point(in_table && src_ok, T, src[0], src[1], Pm, Nm) && look;
+        else look = tp_moved_point(in_table, T, Pp, Np, Pm, Nm) && look;
         one_tap = look && tp_motion(A).same_cam != 0 && (T.flags & RTU_MOTION_STATIC) != 0;
     }
 
@@ -379,12 +426,22 @@ RTU_HD float4 tp_motion_vector(const TpParams& P, bool in_table, const TpMotion&
     return ok ? make_float4(fx, fy, 1.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+// ... of the deform forms: Pm from (src[0], src[1]) of tp_deform_source
+RTU_HD float4 tp_motion_vector_deform(const TpParams& P, bool in_table, const TpMotion& T, const f3* src, bool src_ok) {
+    f3 Pm, Nm;
+    (void)tp_moved_point(in_table, T, src[0], src[1], Pm, Nm);
+    float fx, fy;
+    const bool ok = tp_project(P, Pm, fx, fy) && in_table && src_ok && (T.flags & RTU_MOTION_RESET) == 0 && tp_finite(Pm.x) && tp_finite(Pm.y) && tp_finite(Pm.z);
+    return ok ? make_float4(fx, fy, 1.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 // RTU_OK or RTU_ERR_ARG: the rules of RtuTemporalDesc (include/rtu_render.h)
 int rtu_temporal_check_desc(const RtuTemporalDesc* d);
 // RTU_OK or RTU_ERR_ARG: the rules of RtuSparseDesc (rtu_sparse.hip)
 int rtu_sparse_check_desc(const RtuSparseDesc* d);
 // RTU_OK or RTU_ERR_ARG: history_cap 0 .. 65535; with a host table, its reserved words 0 and its flags known
-int rtu_temporal_check_motion(const RtuNodeMotion* h_motion_or_null, uint32_t n_nodes, int32_t history_cap);
+// (allow_deform: RTU_MOTION_DEFORM is a known flag — the deform forms)
+int rtu_temporal_check_motion(const RtuNodeMotion* h_motion_or_null, uint32_t n_nodes, int32_t history_cap, bool allow_deform = false);
 // mv[i] = the motion vector of pixel i
 int rtu_launch_motion_vectors(const TpParams& p, uint32_t n_nodes, const float4* hits, const RtuNodeMotion* d_motion, float4* mv, hipStream_t stream);
 
@@ -399,6 +456,13 @@ int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, cons
                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
 int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                 float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);
+// The deform forms (k_temporal_deform<MOMENTS>): the motion / moments form with the surface records of the frame (two float4 per
+// pixel) and D, whose arrays are device memory.
+int rtu_launch_temporal_deform(const TpMotionParams& m, bool moments, const TpDeformScene& D, const float4* rgbz, const float4* hits, const float4* albedo,
+                               const float4* surface, const float4* hist_prev, float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion,
+                               hipStream_t stream);
+int rtu_launch_motion_vectors_deform(const TpParams& p, uint32_t n_nodes, const TpDeformScene& D, const float4* hits, const float4* surface,
+                                     const RtuNodeMotion* d_motion, float4* mv, hipStream_t stream);
 // The gradient form: the moments form with g.lambda, device memory (nullptr: the moments form's bits).
 int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream);

@@ -25,6 +25,11 @@
 //                       operations and one or two binary64 acos per pixel) in place of the pinhole's; the previous RtuSensorDesc is a
 //                       kernel argument, the model a template parameter. A panorama's tap columns wrap at the seam. Its host forms
 //                       are rtu_temporal_accumulate_sensor and _sensor_moments.
+//   k_temporal_deform   <MOMENTS> ("Temporal accumulation on deforming meshes"): k_temporal<true, MOMENTS> whose lanes also read their pixel's
+//                       surface record (32 B, two 16-byte loads) and, where the node's entry is RTU_MOTION_DEFORM, the node's mesh id, the
+//                       mesh's header, six indices and six vectors of the PREVIOUS vertices and normals — plain global loads, per lane
+//                       (neighbouring pixels show neighbouring faces) — and carry that point through the entry in place of the hit's.
+//                       Every other pixel is the motion form's, bit for bit. k_motion_vectors_deform likewise.
 //   k_temporal_history  one lane per pixel: the history length out of the E plane.
 //   k_motion_vectors    one lane per pixel: its RtuRayHit and its node's entry in, one float4 out.
 // Each lane reads its pixel of rgbz before it writes that pixel of rgbz_out and touches no other: rgbz_out == rgbz is allowed. Taps read
@@ -64,6 +69,31 @@ __global__ void __launch_bounds__(256) k_temporal(TpArgs<MOVING, GRADIENT, SPARS
     } else {
         tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o);
     }
+    rgbz_out[p] = out;
+    for (int i = 0; i < PLANES; i++) hist_out[i * n + p] = o[i];
+}
+
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256) k_temporal_deform(TpMotionParams A, TpDeformScene D, const float4* rgbz, const float4* __restrict__ hits,
+                                                         const float4* __restrict__ albedo, const float4* __restrict__ surface,
+                                                         const float4* __restrict__ hist_prev, float4* __restrict__ hist_out, float4* rgbz_out,
+                                                         const RtuNodeMotion* __restrict__ motion) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    const TpParams& P = A.P;
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= P.width || y >= P.height) return;
+    const size_t n = (size_t)P.width * (size_t)P.height;
+    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
+    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
+    const int32_t k = tp_motion_index(hit[0], A.n_nodes);
+    TpMotion T = tp_load_motion(motion, k);
+    f3 src[2];
+    const bool ok = tp_deform_source(D, k, T, surface[2 * p], surface[2 * p + 1], mk3(hit[1].x, hit[1].y, hit[1].z), mk3(hit[2].x, hit[2].y, hit[2].z), src[0],
+                                     src[1]);
+    const float4* h[PLANES];
+    for (int i = 0; i < PLANES; i++) h[i] = hist_prev ? hist_prev + i * n : nullptr;
+    float4 out, o[PLANES];
+    tp_pixel<true, MOMENTS, false, false, TpPinhole, true>(A, k >= 0, T, h, x, y, rgbz[p], hit, albedo[p], out, o, true, nullptr, TpPinhole(), src, ok);
     rgbz_out[p] = out;
     for (int i = 0; i < PLANES; i++) hist_out[i * n + p] = o[i];
 }
@@ -116,6 +146,21 @@ __global__ void __launch_bounds__(256) k_motion_vectors(TpParams P, uint32_t n_n
     mv[p] = tp_motion_vector(P, k >= 0, tp_load_motion(motion, k), hit);
 }
 
+__global__ void __launch_bounds__(256) k_motion_vectors_deform(TpParams P, uint32_t n_nodes, TpDeformScene D, const float4* __restrict__ hits,
+                                                               const float4* __restrict__ surface, const RtuNodeMotion* __restrict__ motion,
+                                                               float4* __restrict__ mv) {
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u)), y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= P.width || y >= P.height) return;
+    const size_t p = (size_t)y * (size_t)P.width + (size_t)x;
+    const float4 hit[3] = {hits[3 * p], hits[3 * p + 1], hits[3 * p + 2]};
+    const int32_t k = tp_motion_index(hit[0], n_nodes);
+    TpMotion T = tp_load_motion(motion, k);
+    f3 src[2];
+    const bool ok = tp_deform_source(D, k, T, surface[2 * p], surface[2 * p + 1], mk3(hit[1].x, hit[1].y, hit[1].z), mk3(hit[2].x, hit[2].y, hit[2].z), src[0],
+                                     src[1]);
+    mv[p] = tp_motion_vector_deform(P, k >= 0, T, src, ok);
+}
+
 __global__ void __launch_bounds__(256) k_temporal_history(const float4* __restrict__ hist, float* __restrict__ n_out, unsigned long long pixels) {
     const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
     if (i >= pixels) return;
@@ -137,6 +182,23 @@ int rtu_launch_temporal_motion(const TpMotionParams& m, const float4* rgbz, cons
 int rtu_launch_temporal_moments(const TpMotionParams& m, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
                                 float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion, hipStream_t stream) {
     return launch_temporal<true, true>(m, rgbz, hits, albedo, hist_prev, hist_out, rgbz_out, d_motion, stream);
+}
+
+int rtu_launch_temporal_deform(const TpMotionParams& m, bool moments, const TpDeformScene& D, const float4* rgbz, const float4* hits, const float4* albedo,
+                               const float4* surface, const float4* hist_prev, float4* hist_out, float4* rgbz_out, const RtuNodeMotion* d_motion,
+                               hipStream_t stream) {
+    const dim3 grid((uint32_t)((m.P.width + 31) / 32), (uint32_t)((m.P.height + 7) / 8));
+    if (moments)
+        hipLaunchKernelGGL((k_temporal_deform<true>), grid, dim3(256), 0, stream, m, D, rgbz, hits, albedo, surface, hist_prev, hist_out, rgbz_out, d_motion);
+    else hipLaunchKernelGGL((k_temporal_deform<false>), grid, dim3(256), 0, stream, m, D, rgbz, hits, albedo, surface, hist_prev, hist_out, rgbz_out, d_motion);
+    return (int)hipGetLastError();
+}
+
+int rtu_launch_motion_vectors_deform(const TpParams& p, uint32_t n_nodes, const TpDeformScene& D, const float4* hits, const float4* surface,
+                                     const RtuNodeMotion* d_motion, float4* mv, hipStream_t stream) {
+    const dim3 grid((uint32_t)((p.width + 31) / 32), (uint32_t)((p.height + 7) / 8));
+    hipLaunchKernelGGL(k_motion_vectors_deform, grid, dim3(256), 0, stream, p, n_nodes, D, hits, surface, d_motion, mv);
+    return (int)hipGetLastError();
 }
 
 int rtu_launch_temporal_capped(const TpGradientParams& g, const float4* rgbz, const float4* hits, const float4* albedo, const float4* hist_prev,
@@ -170,11 +232,12 @@ int rtu_launch_motion_vectors(const TpParams& p, uint32_t n_nodes, const float4*
     return (int)hipGetLastError();
 }
 
-int rtu_temporal_check_motion(const RtuNodeMotion* h, uint32_t n_nodes, int32_t history_cap) {
+int rtu_temporal_check_motion(const RtuNodeMotion* h, uint32_t n_nodes, int32_t history_cap, bool allow_deform) {
     if (history_cap < 0 || history_cap > 65535) return RTU_ERR_ARG;
+    const uint32_t known = RTU_MOTION_STATIC | RTU_MOTION_RESET | (allow_deform ? RTU_MOTION_DEFORM : 0u);
     if (h)
         for (uint32_t i = 0; i < n_nodes; i++)
-            if ((h[i].flags & ~(RTU_MOTION_STATIC | RTU_MOTION_RESET)) || h[i].reserved[0] || h[i].reserved[1]) return RTU_ERR_ARG;
+            if ((h[i].flags & ~known) || h[i].reserved[0] || h[i].reserved[1]) return RTU_ERR_ARG;
     return RTU_OK;
 }
 
@@ -258,6 +321,74 @@ static int accumulate_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev
                 tp_pixel<MOVING, MOMENTS, GRADIENT>(A, k >= 0, host_motion(motion, k), hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o);
             }
             st4(h_rgbz_out, p, out);  // (the input pixel was read before: h_rgbz_out may be h_rgbz)
+            for (int i = 0; i < PLANES; i++) st4(h_hist_out, i * n + p, o[i]);
+        }
+    return RTU_OK;
+}
+
+// The host forms of the deform accumulators: accumulate_host<true, MOMENTS> with the surface records, and the previous vertices and
+// the connectivity read from the PREVIOUS scene.
+struct DeformHost {
+    std::vector<TpDeformMesh> meshes;
+    std::vector<int32_t>      node_mesh;
+    TpDeformScene             D;
+};
+static bool deform_host_setup(const RtuSceneDesc* prev, uint32_t n_nodes, DeformHost& dh) {
+    if (!prev || prev->n_nodes != n_nodes || (prev->n_nodes && !prev->nodes) || (prev->n_meshes && !prev->meshes)) return false;
+    dh.meshes.resize(prev->n_meshes);
+    for (uint32_t i = 0; i < prev->n_meshes; i++) {
+        const RtuMesh& m = prev->meshes[i];
+        // (a mesh without one of its arrays has no face to look up: nf = 0, every record on it is out of range)
+        dh.meshes[i] = TpDeformMesh{m.f, m.fn, m.v, m.vn, (m.f && m.fn && m.v && m.vn) ? m.nf : 0u, 0};
+    }
+    dh.node_mesh.resize(n_nodes);
+    for (uint32_t i = 0; i < n_nodes; i++) dh.node_mesh[i] = prev->nodes[i].mesh_id;
+    dh.D = TpDeformScene{dh.meshes.data(), dh.node_mesh.data(), prev->n_meshes, 0};
+    return true;
+}
+
+template <bool MOMENTS>
+static int accumulate_deform_host(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                  const RtuRayHit* h_hits, const float* h_albedo, const RtuRaySurface* h_surface, const RtuSceneDesc* prev_scene,
+                                  const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion, uint32_t n_nodes,
+                                  int32_t history_cap) {
+    constexpr int PLANES = MOMENTS ? 4 : 3;
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !cur_cam || !h_rgbz || !h_hits || !h_albedo || !h_surface || !h_hist_out || !h_rgbz_out) return RTU_ERR_ARG;
+    if (!motion || rtu_temporal_check_motion(motion, n_nodes, history_cap, true) != RTU_OK) return RTU_ERR_ARG;
+    DeformHost dh;
+    if (!deform_host_setup(prev_scene, n_nodes, dh)) return RTU_ERR_ARG;
+    if (h_hist_prev && !prev_cam) return RTU_ERR_ARG;
+    if (!prev_cam) prev_cam = cur_cam;
+    if (cur_cam->width != desc->width || cur_cam->height != desc->height || prev_cam->width != desc->width || prev_cam->height != desc->height)
+        return RTU_ERR_ARG;
+    const int W = desc->width, H = desc->height;
+    const size_t n = (size_t)W * (size_t)H;
+    if (h_hist_prev) {  // taps read anywhere in the previous history
+        const uintptr_t a = (uintptr_t)h_hist_prev, b = (uintptr_t)h_hist_out, bytes = 16 * PLANES * n;
+        if (a < b + bytes && b < a + bytes) return RTU_ERR_ARG;
+    }
+    const TpMotionParams A = tp_motion_setup(*desc, *prev_cam, *cur_cam, h_hist_prev != nullptr, n_nodes, history_cap);
+    std::vector<float4> prev;
+    const float4* hp[PLANES] = {};
+    if (h_hist_prev) {
+        prev.resize(PLANES * n);
+        for (size_t i = 0; i < PLANES * n; i++) prev[i] = f4(h_hist_prev, i);
+        for (int i = 0; i < PLANES; i++) hp[i] = prev.data() + i * n;
+    }
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t p = (size_t)y * (size_t)W + (size_t)x;
+            const float* h = reinterpret_cast<const float*>(h_hits + p);
+            const float* sr = reinterpret_cast<const float*>(h_surface + p);
+            const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
+            const int32_t k = tp_motion_index(hit[0], n_nodes);
+            TpMotion T = host_motion(motion, k);
+            f3 src[2];
+            const bool ok = tp_deform_source(dh.D, k, T, f4(sr, 0), f4(sr, 1), mk3(hit[1].x, hit[1].y, hit[1].z), mk3(hit[2].x, hit[2].y, hit[2].z), src[0], src[1]);
+            float4 out, o[PLANES];
+            tp_pixel<true, MOMENTS, false, false, TpPinhole, true>(A, k >= 0, T, hp, x, y, f4(h_rgbz, p), hit, f4(h_albedo, p), out, o, true, nullptr, TpPinhole(),
+                                                                   src, ok);
+            st4(h_rgbz_out, p, out);
             for (int i = 0; i < PLANES; i++) st4(h_hist_out, i * n + p, o[i]);
         }
     return RTU_OK;
@@ -366,6 +497,44 @@ int rtu_temporal_accumulate_sparse(const RtuTemporalDesc* desc, const RtuSparseD
     const SparseHost sp{sparse_desc, h_rgbt, owner, h_hole_out};
     return accumulate_host<true, true, false, true>(desc, prev_cam, cur_cam, nullptr, h_hits, h_albedo, h_hist_prev, h_hist_out, h_rgbz_out, motion, n_nodes,
                                                     history_cap, nullptr, &sp);
+}
+
+int rtu_temporal_accumulate_deform(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                   const RtuRayHit* h_hits, const float* h_albedo, const RtuRaySurface* h_surface, const RtuSceneDesc* prev_scene,
+                                   const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion, uint32_t n_nodes,
+                                   int32_t history_cap) {
+    return accumulate_deform_host<false>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_surface, prev_scene, h_hist_prev, h_hist_out, h_rgbz_out, motion,
+                                         n_nodes, history_cap);
+}
+
+int rtu_temporal_accumulate_deform_moments(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuFrameDesc* cur_cam, const float* h_rgbz,
+                                           const RtuRayHit* h_hits, const float* h_albedo, const RtuRaySurface* h_surface, const RtuSceneDesc* prev_scene,
+                                           const float* h_hist_prev, float* h_hist_out, float* h_rgbz_out, const RtuNodeMotion* motion, uint32_t n_nodes,
+                                           int32_t history_cap) {
+    return accumulate_deform_host<true>(desc, prev_cam, cur_cam, h_rgbz, h_hits, h_albedo, h_surface, prev_scene, h_hist_prev, h_hist_out, h_rgbz_out, motion,
+                                        n_nodes, history_cap);
+}
+
+int rtu_motion_vectors_deform(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuRaySurface* h_surface,
+                              const RtuSceneDesc* prev_scene, const RtuNodeMotion* motion, uint32_t n_nodes, float* h_mv) {
+    if (rtu_temporal_check_desc(desc) != RTU_OK || !prev_cam || !h_hits || !h_surface || !motion || !h_mv) return RTU_ERR_ARG;
+    if (rtu_temporal_check_motion(motion, n_nodes, 0, true) != RTU_OK) return RTU_ERR_ARG;
+    if (prev_cam->width != desc->width || prev_cam->height != desc->height) return RTU_ERR_ARG;
+    DeformHost dh;
+    if (!deform_host_setup(prev_scene, n_nodes, dh)) return RTU_ERR_ARG;
+    const TpParams P = tp_setup(*desc, *prev_cam, *prev_cam, true);
+    const size_t n = (size_t)desc->width * (size_t)desc->height;
+    for (size_t p = 0; p < n; p++) {
+        const float* h = reinterpret_cast<const float*>(h_hits + p);
+        const float* sr = reinterpret_cast<const float*>(h_surface + p);
+        const float4 hit[3] = {f4(h, 0), f4(h, 1), f4(h, 2)};
+        const int32_t k = tp_motion_index(hit[0], n_nodes);
+        TpMotion T = host_motion(motion, k);
+        f3 src[2];
+        const bool ok = tp_deform_source(dh.D, k, T, f4(sr, 0), f4(sr, 1), mk3(hit[1].x, hit[1].y, hit[1].z), mk3(hit[2].x, hit[2].y, hit[2].z), src[0], src[1]);
+        st4(h_mv, p, tp_motion_vector_deform(P, k >= 0, T, src, ok));
+    }
+    return RTU_OK;
 }
 
 int rtu_motion_vectors(const RtuTemporalDesc* desc, const RtuFrameDesc* prev_cam, const RtuRayHit* h_hits, const RtuNodeMotion* motion, uint32_t n_nodes,
