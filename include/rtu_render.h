@@ -457,6 +457,32 @@ int  rtu_shade_rays_paths_device(RtuContext* ctx, const void* d_rays, const void
                                  void* hip_stream);
 int  rtu_shade_rays_paths(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_rgbt,
                           RtuStats* stats);
+/* ---- The two halves of a recipe-P sample (render_rays6.hip / render_rays7.hip, render_gather_impl.h) ----------------------------------
+ * rtu_shade_rays_paths is Shade(h0, lights + AmbientLight(c)) + Shade(h0, lights) with c = what MonteCarlo(h0, 4) gathered behind the
+ * ray's hit (RenderFunctions.cpp:549-590, :134-135). These two pairs hand out c alone and take one from outside, so that the indirect
+ * term can be computed where it is needed and reused where it is not (the irradiance map below; a light-map bake; a probe):
+ *   rtu_gather_rays          per ray one float4 {c.r, c.g, c.b, t}: c the intensity of the AmbientLight that MonteCarlo(hInfo, 4) appends
+ *                            for the ray's root hit and key — the roots, the four chain steps and the shading steps of depth 4 .. 1 of
+ *                            rtu_shade_rays_paths, then the sum of depth 0 written out instead of consumed. A miss, an invalid ray and a
+ *                            node without material give c = 0 (nothing is gathered for them); t as rtu_shade_rays_paths: hInfo.z, tmax on
+ *                            a miss, 0 for an invalid ray.
+ *   rtu_shade_rays_ambient   per ray {r, g, b, t} of a recipe-S ray batch whose root call is lit by lights + AmbientLight(amb[i]): the two
+ *                            trees of :134-135, the ambient one on child_key(keys[i], 4). amb: n float4 {r, g, b, ignored}, 16-byte
+ *                            aligned in the _device form. No gather ray is traced. amb enters as (0 + amb) + 0, the sum MonteCarlo()
+ *                            itself forms (:568-570): amb bit for bit, but for a negative zero, which becomes +0. Miss / invalid /
+ *                            no material as rtu_shade_rays_paths.
+ * rtu_shade_rays_ambient(rays, keys, rtu_gather_rays(rays, keys)) is rtu_shade_rays_paths(rays, keys) byte for byte; with amb = 0 it is
+ * rtu_shade_rays_sampled plus what the ambient tree sees of the environment through reflection and refraction (nothing on a scene
+ * whose environment is black or whose materials are childless: the same bytes there).
+ * keys, eye, max_bounce, flags (RTU_QUERY_REFERENCE_WALK), stats, every error, n <= 2^25 in the _device forms, the chunks of the host
+ * forms and THE CALL IS A RENDER are as stated for rtu_shade_rays_paths; so is the capacity rule: rtu_frame_status after a _device
+ * form, RTU_ERR_CAPACITY: call it again. Both share the context's chain records with recipe-P frames and path-traced batches. */
+int  rtu_gather_rays_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_ct, void* hip_stream);
+int  rtu_gather_rays(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_ct, RtuStats* stats);
+int  rtu_shade_rays_ambient_device(RtuContext* ctx, const void* d_rays, const void* d_keys, const void* d_amb, size_t n, const RtuShadeDesc* desc,
+                                   void* d_rgbt, void* hip_stream);
+int  rtu_shade_rays_ambient(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, const float* h_amb, size_t n, const RtuShadeDesc* desc,
+                            float* h_rgbt, RtuStats* stats);
 /* The primary rays and keys of sample `sample` (0 <= sample < frame->samples) of the recipe S frame `frame`, image rows
  * [row0, row0 + nrows), width * nrows of each in image order; shards are ignored. key = sample_key(x + width * y, sample); the pixel
  * offset is sample / S + Halton(sample, 4 | 5) in x | y (RenderFunctions.cpp:80-85, :96); the origin is the lens point
@@ -1715,6 +1741,88 @@ int  rtu_selftest_primitives(RtuContext* ctx, unsigned long long n_rays, unsigne
 #define RTU_TEXOP_IN(op)  ((op) == RTU_TEXOP_ATAN2F ? 2 : (op) == RTU_TEXOP_ASINF ? 1 : 3)
 #define RTU_TEXOP_OUT(op) ((op) <= RTU_TEXOP_ASINF ? 1 : 3)
 int  rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, unsigned long long n, float* h_out);
+
+/* ---- Irradiance map: the indirect term gathered at a refined grid of image points, interpolated per pixel (rtu_irradiance.h, -------
+ * rtu_irradiance.hip) — the screen-space irradiance map of the reference's ExternalLibrary/cyIrradianceMap.h (its class
+ * cyIrradianceMapColorZNormal), which the reference's renderer never reaches, restated for the GPU.
+ * GRID. s = 2^-max_subdiv pixels lie between neighbouring points (max_subdiv <= 0; a positive one, several points per pixel, is
+ * RTU_ERR_UNSUPPORTED); width and height must be multiples of s (RTU_ERR_ARG). The grid has (width / s + 1) x (height / s + 1) points,
+ * point (x, y) — index x + grid_w * y — sits at the image position (x s, y s), a pixel CORNER, and its ray leaves the pinhole cam_pos
+ * through (origin + u * (x s)) + v * (y s), normalised as rtu_camera_rays does; there is no lens. A point's record is two float4,
+ * {E.r, E.g, E.b, z} {N.x, N.y, N.z, 0}, and one byte says whether it was COMPUTED (1) or ESTIMATED (0).
+ *   computed   the point's ray is traced once: z = hInfo.z and N = hInfo.N, the bits of rtu_trace_rays; E = the sum, in the order of m,
+ *              of the `samples` values c that rtu_gather_rays gives that ray with the keys rtu_sample_key(point index, first_sample + m),
+ *              divided by (float)samples. A miss stores E = 0, z = tmax (RTU_BIGFLOAT), N = 0; a node without material E = 0.
+ *   estimated  E, z and N are the average (((d0 + d1) + d2) + d3) * 0.25f of four earlier points.
+ * PASSES, 1 + 2 (max_subdiv - min_subdiv) of them; a pass reads earlier passes only and visits its points in rising index:
+ *   pass 0           computes every point whose x and y are multiples of 2^(max_subdiv - min_subdiv).
+ *   then per level, skip = that spacing, halved from level to level, half = skip / 2:
+ *   centre pass      visits (half + i skip, half + j skip); estimated from (x -+ half, y -+ half) in the order (-,-) (+,-) (-,+) (+,+)
+ *   edge pass        visits (half + i skip, j skip) and (i skip, half + j skip); estimated from (x, y - half) (x - half, y)
+ *                    (x + half, y) (x, y + half); a point with x == 0 or y == 0 is always computed
+ *   In both, a point whose x + half or y + half lies beyond the grid is always computed (cells that a ragged grid cuts off).
+ *   A point is estimated when the average is similar to each of the four: |dE| < threshold_color per channel, |dz| < threshold_z and
+ *   dot(average N, N_i) > threshold_n, the average N not renormalised; otherwise it is computed. min_subdiv == max_subdiv computes
+ *   every point. (The reference's iterator reads its spacing after leaving its lock, so the last point of each of its passes is
+ *   visited with the next pass's spacing: a side effect of its threading that is not restated here)
+ * LOOKUP at image position (px, py), the class's Sample(): xx = px * (1.0f / s), ix = (unsigned)xx, fx = xx - ix, likewise y; ix beyond
+ * the last column: both columns the last; the four records are interpolated a * (1 - f) + b * f in x, then in y, every component
+ * (the eight floats of a record), binary32, uncontracted. A negative or NaN coordinate is taken as 0.
+ * rtu_irradiance_defaults: min_subdiv -5, max_subdiv 0, samples 64, first_sample 0, thresholds 1e30, 1e30, 1e30, 1e30, 0.7 (the class's
+ * own: colour and depth never refuse), max_bounce 5. Rules (RTU_ERR_ARG): min_subdiv <= max_subdiv, min_subdiv >= -15, samples 1 ..
+ * 4096, first_sample >= 0, thresholds not NaN, max_bounce 0 .. RTU_MAX_BOUNCE, reserved 0, at most 2^26 grid points. */
+typedef struct RtuIrradianceDesc {   /* 64 B */
+    int32_t  min_subdiv, max_subdiv;
+    int32_t  samples;                /* M per computed point */
+    int32_t  first_sample;
+    float    threshold_color[3], threshold_z, threshold_n;
+    int32_t  max_bounce;             /* of every Shade() tree of the gather, as RtuShadeDesc.max_bounce */
+    uint32_t reserved[6];            /* must be 0 */
+} RtuIrradianceDesc;
+/* a built map, for the lookup and the frame: the image size it was built for, max_subdiv, and its records (host memory in the host
+ * forms, device memory, 16-byte aligned, in the _device forms) */
+typedef struct RtuIrradianceMap {    /* 32 B */
+    int32_t     width, height, max_subdiv;
+    uint32_t    reserved;            /* must be 0 */
+    const void* records;             /* grid_w * grid_h records of two float4 */
+    const void* reserved_ptr;        /* must be NULL */
+} RtuIrradianceMap;
+int  rtu_irradiance_defaults(RtuIrradianceDesc* out);
+/* grid size and number of passes for a width x height image; any output may be NULL. Pure host code, as the next three. */
+int  rtu_irradiance_grid(const RtuIrradianceDesc* desc, int width, int height, int* grid_w, int* grid_h, int* passes);
+/* the rays of all grid points of `frame` (cam_pos, origin, u, v, width, height), index order, tmax = RTU_BIGFLOAT */
+int  rtu_irradiance_rays(const RtuFrameDesc* frame, const RtuIrradianceDesc* desc, RtuRay* rays_out);
+/* ONE PASS over given records: visit_out[k] = the index of the k-th point the pass visits, compute_out[k] = 1 if the pass wants it
+ * computed, 0 if it estimated it — then its record in `records` is the average and its byte in `computed` 0; the record and byte of
+ * a point to be computed are left alone (the caller computes and stores them before the next pass). *n_visit = the points visited.
+ * visit_out / compute_out: room for grid_w * grid_h entries; the points with compute_out 1, in order, are the pass's list. */
+int  rtu_irradiance_classify(const RtuIrradianceDesc* desc, int width, int height, int pass, float* records, uint8_t* computed, uint32_t* visit_out,
+                             uint8_t* compute_out, uint32_t* n_visit);
+/* the lookup at n image positions xy = {px, py} ...: eight floats per position to out */
+int  rtu_irradiance_sample(const RtuIrradianceMap* map, const float* xy, size_t n, float* out);
+int  rtu_irradiance_sample_device(RtuContext* ctx, const RtuIrradianceMap* map, const void* d_xy, size_t n, void* d_out, void* hip_stream);
+/* BUILD the map of `frame` (its pinhole camera, width, height; eye = cam_pos; samples, lens, shards are not read — shard_count > 1 is
+ * RTU_ERR_UNSUPPORTED): grid_w * grid_h records, as many bytes, *n_computed (may be NULL) the number of computed points, and per_pass
+ * (may be NULL; 2 words per pass) {points visited, points computed}. Per pass: k_irr_classify writes the averages and flags the rest,
+ * the flagged points become a device list in visiting order (the three scan kernels of rtu_steer.hip; no atomics), the list's length
+ * is read back, and the list is computed in chunks of at most 2^22 chains — k_irr_roots, the chain and shading steps of
+ * rtu_gather_rays, k_irr_store. THE CALL IS A RENDER (frame records, chain records, launch hints of rtu_shade_rays_paths; ONE STREAM
+ * PER CONTEXT). Because of the read-back the _device form returns when the map is complete on hip_stream; a chunk that ran out of
+ * frame records is shaded again by the call itself. The cancel flag is checked between chunks (RTU_ERR_CANCELLED).
+ * RTU_ERR_NO_SCENE before rtu_upload_scene; d_records 16-byte aligned. */
+int  rtu_irradiance_build_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceDesc* desc, void* d_records, void* d_computed,
+                                 uint32_t* n_computed, uint32_t* per_pass, void* hip_stream);
+int  rtu_irradiance_build(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceDesc* desc, float* h_records, uint8_t* h_computed,
+                          uint32_t* n_computed, uint32_t* per_pass);
+/* THE FRAME: a recipe-S frame of frame->samples samples (1 .. ; gather_bounces must be 0) whose root calls also get the AmbientLight
+ * of the map at the pixel's centre (x + 0.5, y + 0.5). Per sample k: the rays and keys of rtu_camera_sample_rays_device(frame, k), the
+ * lookup kernel, rtu_shade_rays_ambient_device of them (eye = cam_pos, frame->max_bounce), accumulated in sample order by the kernels
+ * of a recipe-S frame: rgb = sum / (float)samples, z = the mean hInfo.z over the samples that hit, RTU_BIGFLOAT without one — a
+ * recipe-S frame's z. A ray that misses shows the environment, as in every ray batch. map->width / height must be the frame's.
+ * Sharded frames (shard_count > 1) are RTU_ERR_UNSUPPORTED; sensors and temporal sessions have no such entry. Synchronous on
+ * hip_stream (a sample that ran out of frame records is shaded again). */
+int  rtu_render_frame_irradiance_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceMap* map, void* d_rgbz, void* hip_stream);
+int  rtu_render_frame_irradiance(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceMap* map, float* h_rgbz);
 
 /* Debug: device allocations the library has made for its own buffers so far (every context together, the whole process).
  * rtu_device_alloc is not counted. */

@@ -187,7 +187,11 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_temporal_begin_sparse_holes", "rtu_temporal_hole_rays",
                "rtu_sensor_project", "rtu_temporal_accumulate_sensor", "rtu_temporal_accumulate_sensor_device",
                "rtu_temporal_accumulate_sensor_moments", "rtu_temporal_accumulate_sensor_moments_device",
-               "rtu_temporal_sensor_frame_device", "rtu_temporal_sensor_frame"]
+               "rtu_temporal_sensor_frame_device", "rtu_temporal_sensor_frame",
+               "rtu_gather_rays_device", "rtu_gather_rays", "rtu_shade_rays_ambient_device", "rtu_shade_rays_ambient",
+               "rtu_irradiance_defaults", "rtu_irradiance_grid", "rtu_irradiance_rays", "rtu_irradiance_classify", "rtu_irradiance_sample",
+               "rtu_irradiance_sample_device", "rtu_irradiance_build_device", "rtu_irradiance_build",
+               "rtu_render_frame_irradiance_device", "rtu_render_frame_irradiance"]
 _sig(hip, "rtu_device_count", _I)
 _sig(hip, "rtu_error_string", ctypes.c_char_p, _I)
 _sig(hip, "rtu_create_context", _P, _I, ctypes.POINTER(_I))
@@ -335,6 +339,37 @@ _sig(hip, "rtu_shade_rays_sampled", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POIN
 _sig(hip, "rtu_shade_rays_paths_device", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
 _sig(hip, "rtu_shade_rays_paths", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
 _sig(hip, "rtu_camera_sample_rays", _I, ctypes.POINTER(RtuFrameDesc), _I, _I, _I, _P, _P)
+_sig(hip, "rtu_gather_rays_device", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
+_sig(hip, "rtu_gather_rays", _I, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
+_sig(hip, "rtu_shade_rays_ambient_device", _I, _P, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, _P)
+_sig(hip, "rtu_shade_rays_ambient", _I, _P, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(RtuShadeDesc), _P, ctypes.POINTER(RtuStats))
+
+
+class RtuIrradianceDesc(ctypes.Structure):
+    """include/rtu_render.h RtuIrradianceDesc (64 bytes): the grid, the samples per computed point and the thresholds of an irradiance map."""
+    _fields_ = [("min_subdiv", ctypes.c_int32), ("max_subdiv", ctypes.c_int32), ("samples", ctypes.c_int32), ("first_sample", ctypes.c_int32),
+                ("threshold_color", ctypes.c_float * 3), ("threshold_z", ctypes.c_float), ("threshold_n", ctypes.c_float),
+                ("max_bounce", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+class RtuIrradianceMap(ctypes.Structure):
+    """include/rtu_render.h RtuIrradianceMap (32 bytes): a built map for the lookup and the frame."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_subdiv", ctypes.c_int32), ("reserved", ctypes.c_uint32),
+                ("records", ctypes.c_void_p), ("reserved_ptr", ctypes.c_void_p)]
+
+
+_PI = ctypes.POINTER(_I)
+_sig(hip, "rtu_irradiance_defaults", _I, ctypes.POINTER(RtuIrradianceDesc))
+_sig(hip, "rtu_irradiance_grid", _I, ctypes.POINTER(RtuIrradianceDesc), _I, _I, _PI, _PI, _PI)
+_sig(hip, "rtu_irradiance_rays", _I, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuIrradianceDesc), _P)
+_sig(hip, "rtu_irradiance_classify", _I, ctypes.POINTER(RtuIrradianceDesc), _I, _I, _I, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_uint32))
+_sig(hip, "rtu_irradiance_sample", _I, ctypes.POINTER(RtuIrradianceMap), _P, ctypes.c_size_t, _P)
+_sig(hip, "rtu_irradiance_sample_device", _I, _P, ctypes.POINTER(RtuIrradianceMap), _P, ctypes.c_size_t, _P, _P)
+_sig(hip, "rtu_irradiance_build_device", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuIrradianceDesc), _P, _P,
+     ctypes.POINTER(ctypes.c_uint32), _P, _P)
+_sig(hip, "rtu_irradiance_build", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuIrradianceDesc), _P, _P, ctypes.POINTER(ctypes.c_uint32), _P)
+_sig(hip, "rtu_render_frame_irradiance_device", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuIrradianceMap), _P, _P)
+_sig(hip, "rtu_render_frame_irradiance", _I, _P, ctypes.POINTER(RtuFrameDesc), ctypes.POINTER(RtuIrradianceMap), _P)
 _sig(hip, "rtu_sample_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
 _sig(hip, "rtu_child_key", ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
 # ray sorting (include/rtu_render.h, "Ray sorting")
@@ -1317,6 +1352,81 @@ def camera_sample_rays(frame, sample, row0=0, nrows=None):
     if rc != RTU_OK:
         raise RtuError(rc, "rtu_camera_sample_rays: not a recipe S frame, sample outside [0, samples) or rows outside the image")
     return rays, keys
+
+
+def irradiance_desc(min_subdiv=None, max_subdiv=None, samples=None, first_sample=None, threshold_color=None, threshold_z=None, threshold_n=None,
+                    max_bounce=None):
+    """An RtuIrradianceDesc: rtu_irradiance_defaults (min_subdiv -5, max_subdiv 0, 64 samples, thresholds 1e30 / 1e30 / 0.7), then
+    whatever is given. threshold_color: one number or three."""
+    d = RtuIrradianceDesc()
+    hip.rtu_irradiance_defaults(ctypes.byref(d))
+    for name, v in (("min_subdiv", min_subdiv), ("max_subdiv", max_subdiv), ("samples", samples), ("first_sample", first_sample),
+                    ("threshold_z", threshold_z), ("threshold_n", threshold_n), ("max_bounce", max_bounce)):
+        if v is not None:
+            setattr(d, name, v)
+    if threshold_color is not None:
+        tc = [float(threshold_color)] * 3 if not hasattr(threshold_color, "__len__") else [float(x) for x in threshold_color]
+        d.threshold_color[:] = tc
+    return d
+
+
+def irradiance_grid(desc, width, height):
+    """rtu_irradiance_grid (pure host code): (grid_w, grid_h, passes) of the map of a width x height image."""
+    gw, gh, np_ = _I(), _I(), _I()
+    rc = hip.rtu_irradiance_grid(ctypes.byref(desc), width, height, ctypes.byref(gw), ctypes.byref(gh), ctypes.byref(np_))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_irradiance_grid: a descriptor outside its rules, or an image that is no multiple of 2^-max_subdiv")
+    return gw.value, gh.value, np_.value
+
+
+def irradiance_rays(frame, desc):
+    """rtu_irradiance_rays (pure host code): the pinhole rays through all grid points of the map of `frame`, index order, as a
+    structured array of ray_dtype()."""
+    import numpy as np
+    gw, gh, _ = irradiance_grid(desc, frame.width, frame.height)
+    out = np.zeros(gw * gh, ray_dtype())
+    rc = hip.rtu_irradiance_rays(ctypes.byref(frame), ctypes.byref(desc), out.ctypes.data)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_irradiance_rays")
+    return out
+
+
+def irradiance_classify(desc, width, height, pass_index, records, computed):
+    """rtu_irradiance_classify (pure host code): one pass over records float32 [grid_h, grid_w, 8] and computed uint8 [grid_h, grid_w],
+    both updated IN PLACE for the points the pass estimates. -> (visit uint32 [n]: the points in visiting order, compute bool [n]:
+    which of them the pass wants computed; visit[compute] is its list)."""
+    import numpy as np
+    gw, gh, _ = irradiance_grid(desc, width, height)
+    if records.dtype != np.float32 or not records.flags.c_contiguous or records.size != gw * gh * 8 or not records.flags.writeable:
+        raise RtuError(RTU_ERR_ARG, "records: a writable contiguous float32 array of grid_h * grid_w * 8")
+    if computed.dtype != np.uint8 or not computed.flags.c_contiguous or computed.size != gw * gh or not computed.flags.writeable:
+        raise RtuError(RTU_ERR_ARG, "computed: a writable contiguous uint8 array of grid_h * grid_w")
+    visit, comp, n = np.zeros(gw * gh, np.uint32), np.zeros(gw * gh, np.uint8), ctypes.c_uint32()
+    rc = hip.rtu_irradiance_classify(ctypes.byref(desc), width, height, pass_index, records.ctypes.data, computed.ctypes.data, visit.ctypes.data,
+                                     comp.ctypes.data, ctypes.byref(n))
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_irradiance_classify: a descriptor outside its rules or a pass outside [0, passes)")
+    return visit[:n.value].copy(), comp[:n.value].astype(bool)
+
+
+def _irradiance_map(width, height, max_subdiv, records_ptr):
+    m = RtuIrradianceMap()
+    m.width, m.height, m.max_subdiv, m.records = width, height, max_subdiv, records_ptr
+    return m
+
+
+def irradiance_sample(records, width, height, max_subdiv, xy):
+    """rtu_irradiance_sample (pure host code): the bilinear lookup of the map `records` (float32, grid_h * grid_w * 8) of a width x
+    height image at image positions xy float32 [n, 2] -> float32 [n, 8] {E.rgb, z, N.xyz, 0}."""
+    import numpy as np
+    rec = np.ascontiguousarray(records, np.float32)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.zeros((len(xy), 8), np.float32)
+    m = _irradiance_map(width, height, max_subdiv, rec.ctypes.data)
+    rc = hip.rtu_irradiance_sample(ctypes.byref(m), xy.ctypes.data if len(xy) else None, len(xy), out.ctypes.data if len(xy) else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_irradiance_sample: an image that is no multiple of 2^-max_subdiv, or max_subdiv > 0")
+    return out
 
 
 def sample_key(pixel, sample):
@@ -2469,6 +2579,92 @@ class Context:
         (RTU_ERR_CAPACITY: call this again)."""
         d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
         self._check(hip.rtu_shade_rays_paths_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
+
+    def gather_rays(self, rays, keys, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+        """rtu_gather_rays: the indirect half of a recipe-P sample — per ray {c.r, c.g, c.b, t}, c the intensity of the AmbientLight the
+        4-bounce gather behind the ray's hit appends for its key (0 on a miss, an invalid ray, a node without material).
+        Returns (float32 [n, 4], stats dict or None)."""
+        import numpy as np
+        r = _as_rays(rays)
+        k = _as_keys(keys, r.size)
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        out = np.zeros((r.size, 4), np.float32)
+        st = RtuStats() if stats else None
+        self._check(hip.rtu_gather_rays(self._h, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None, r.size, ctypes.byref(d),
+                                        out.ctypes.data if r.size else None, ctypes.byref(st) if stats else None))
+        return out, (st.as_dict() if stats else None)
+
+    def gather_rays_device(self, d_rays_ptr, d_keys_ptr, n, eye, d_ct_ptr, stream=None, max_bounce=5, reference_walk=False, desc=None):
+        """rtu_gather_rays_device: device memory, asynchronous on `stream`; frame_status() afterwards (RTU_ERR_CAPACITY: call this again)."""
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        self._check(hip.rtu_gather_rays_device(self._h, d_rays_ptr, d_keys_ptr, n, ctypes.byref(d), d_ct_ptr, stream))
+
+    def shade_rays_ambient(self, rays, keys, amb, eye, max_bounce=5, reference_walk=False, stats=False, desc=None):
+        """rtu_shade_rays_ambient: the direct half — a recipe-S ray batch whose root calls are lit by lights + AmbientLight(amb[i]);
+        amb float32 [n, 4] {r, g, b, ignored} (what gather_rays returns) or [n, 3]. Returns (float32 [n, 4] {r, g, b, t}, stats or None)."""
+        import numpy as np
+        r = _as_rays(rays)
+        k = _as_keys(keys, r.size)
+        a = np.asarray(amb, np.float32).reshape(r.size, -1)
+        if a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((r.size, 1), np.float32)], axis=1)
+        if a.shape[1] != 4:
+            raise RtuError(RTU_ERR_ARG, "amb: float32 [n, 4] or [n, 3]")
+        a = np.ascontiguousarray(a)
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        out = np.zeros((r.size, 4), np.float32)
+        st = RtuStats() if stats else None
+        self._check(hip.rtu_shade_rays_ambient(self._h, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None,
+                                               a.ctypes.data if r.size else None, r.size, ctypes.byref(d), out.ctypes.data if r.size else None,
+                                               ctypes.byref(st) if stats else None))
+        return out, (st.as_dict() if stats else None)
+
+    def shade_rays_ambient_device(self, d_rays_ptr, d_keys_ptr, d_amb_ptr, n, eye, d_rgbt_ptr, stream=None, max_bounce=5, reference_walk=False, desc=None):
+        """rtu_shade_rays_ambient_device: device memory (amb n float4), asynchronous on `stream`; frame_status() afterwards."""
+        d = desc if desc is not None else shade_desc(eye, max_bounce, reference_walk)
+        self._check(hip.rtu_shade_rays_ambient_device(self._h, d_rays_ptr, d_keys_ptr, d_amb_ptr, n, ctypes.byref(d), d_rgbt_ptr, stream))
+
+    def irradiance_build(self, frame, desc):
+        """rtu_irradiance_build: the irradiance map of `frame` (its pinhole camera, width, height) -> (records float32 [grid_h, grid_w, 8]
+        {E.rgb, z, N.xyz, 0}, computed uint8 [grid_h, grid_w], per_pass uint32 [passes, 2] {visited, computed})."""
+        import numpy as np
+        gw, gh, passes = irradiance_grid(desc, frame.width, frame.height)
+        rec, comp, per = np.zeros((gh, gw, 8), np.float32), np.zeros((gh, gw), np.uint8), np.zeros((passes, 2), np.uint32)
+        n = ctypes.c_uint32()
+        self._check(hip.rtu_irradiance_build(self._h, ctypes.byref(frame), ctypes.byref(desc), rec.ctypes.data, comp.ctypes.data, ctypes.byref(n), per.ctypes.data))
+        assert n.value == int(per[:, 1].sum())
+        return rec, comp, per
+
+    def irradiance_build_device(self, frame, desc, d_records_ptr, d_computed_ptr, stream=None):
+        """rtu_irradiance_build_device: records (grid points x 32 B, 16-byte aligned) and bytes into device memory; returns when the map
+        is complete on `stream`. -> per_pass uint32 [passes, 2]."""
+        import numpy as np
+        _, _, passes = irradiance_grid(desc, frame.width, frame.height)
+        per = np.zeros((passes, 2), np.uint32)
+        n = ctypes.c_uint32()
+        self._check(hip.rtu_irradiance_build_device(self._h, ctypes.byref(frame), ctypes.byref(desc), d_records_ptr, d_computed_ptr, ctypes.byref(n),
+                                                    per.ctypes.data, stream))
+        return per
+
+    def irradiance_sample_device(self, d_records_ptr, width, height, max_subdiv, d_xy_ptr, n, d_out_ptr, stream=None):
+        """rtu_irradiance_sample_device: the lookup at n positions {px, py} in device memory -> n x 8 floats, asynchronous on `stream`."""
+        m = _irradiance_map(width, height, max_subdiv, d_records_ptr)
+        self._check(hip.rtu_irradiance_sample_device(self._h, ctypes.byref(m), d_xy_ptr, n, d_out_ptr, stream))
+
+    def render_irradiance(self, frame, records, max_subdiv):
+        """rtu_render_frame_irradiance: a recipe-S frame of frame.samples samples whose root calls also get the AmbientLight of the map
+        `records` (as irradiance_build returns them) at the pixel's centre -> float32 [height, width, 4] {r, g, b, z}."""
+        import numpy as np
+        rec = np.ascontiguousarray(records, np.float32)
+        out = np.zeros((frame.height, frame.width, 4), np.float32)
+        m = _irradiance_map(frame.width, frame.height, max_subdiv, rec.ctypes.data)
+        self._check(hip.rtu_render_frame_irradiance(self._h, ctypes.byref(frame), ctypes.byref(m), out.ctypes.data))
+        return out
+
+    def render_irradiance_device(self, frame, d_records_ptr, max_subdiv, d_rgbz_ptr, stream=None):
+        """rtu_render_frame_irradiance_device: map records and image in device memory; returns when the image is complete on `stream`."""
+        m = _irradiance_map(frame.width, frame.height, max_subdiv, d_records_ptr)
+        self._check(hip.rtu_render_frame_irradiance_device(self._h, ctypes.byref(frame), ctypes.byref(m), d_rgbz_ptr, stream))
 
     def sensor_rays_device(self, desc, d_rays_ptr, d_keys_ptr=None, sample0=0, nsamples=1, stream=None):
         """rtu_sensor_rays_device: the rays (and keys, unless d_keys_ptr is None) of samples [sample0, sample0 + nsamples) of the

@@ -16,6 +16,7 @@
 #include "rtu_sensor_adaptive.h"
 #include "rtu_gradient.h"
 #include "rtu_holes.h"
+#include "rtu_irradiance.h"
 #include "rtu_sparse.h"
 #include "rtu_steer.h"
 #include "rtu_temporal.h"
@@ -178,6 +179,13 @@ struct RtuContext {
     DevBuf<uint8_t>  sa_counts;              // ... the host form's counts
     std::vector<uint32_t> sa_trace;          // {live pixels, samples} of every batch of the last adaptive sensor render (rtu_debug_sensor_adaptive_trace)
     DevBuf<uint32_t> st_scratch;            // steered sampling (rtu_sample_allocation_device): the weights, the tile sums, Wsum
+    DevBuf<float4>   sh_amb;                 // the two halves of a recipe-P sample, host form (rtu_shade_rays_ambient): one chunk of AmbientLight intensities
+    DevBuf<uint32_t> ir_scratch, ir_list;    // irradiance map (rtu_irradiance_build): the scratch of a pass (scan, counts, offsets, the list's length), its list,
+    DevBuf<uint32_t> ir_keys, ir_hits;       // ... the key slots of a chunk's chain steps / the keys of a frame's sample; the frame's hit counts,
+    DevBuf<float4>   ir_c, ir_rays;          // ... {c, t} per chain of a chunk / {r, g, b, t} of a frame's sample; its rays,
+    DevBuf<float4>   ir_amb, ir_acc;         // ... the frame's AmbientLight per pixel and its sums,
+    DevBuf<float4>   ir_rec, ir_img;         // ... the host forms' records and image,
+    DevBuf<uint8_t>  ir_bytes;               // ... and computed bytes
     DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
     bool stamp_next = false;
 };
@@ -4178,6 +4186,348 @@ int rtu_shade_rays_paths(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* 
     const int rc = shade_args(ctx, h_rays, h_rgbt, n, desc, false, &f, true, h_keys, true);
     if (rc != RTU_OK) return rc;
     return shade_host(ctx, f, h_rays, h_keys, n, h_rgbt, stats, true);
+}
+
+// ---- the two halves of a recipe-P sample (render_gather_impl.h; render_rays6.hip / render_rays7.hip) ----
+namespace {
+enum { HALF_GATHER = 1, HALF_AMBIENT = 2 };
+
+DevScene half_scene(const RtuContext* ctx) {
+    DevScene s = ctx->dscene;
+    s.dbg = ctx->dbg;
+    return s;
+}
+
+// What is traced once per batch. A gather: the whole chain of a path-traced batch. An ambient batch: the roots alone.
+int half_chain(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n, int kind) {
+    if (kind == HALF_GATHER) return paths_chain(ctx, f, d_out, stream, d_rays, d_keys, n);
+    const int forced = ctx->tail_hint;  // (as paths_chain: a chain step has no recursion levels)
+    ctx->tail_hint = 0;
+    const int rc = launch(ctx, &f, d_out, stream, true, 0, 1, nullptr, RTU_LAUNCH_CHAIN, 0, false, nullptr, 0, d_rays, n, d_keys);
+    ctx->tail_hint = forced;
+    return rc;
+}
+
+// One attempt at what depends on the frame capacities. A gather: the shading steps of depth 4 .. 1, then k_gather_amb writes the sum
+// of depth 0 out. An ambient batch: k_amb_seed plants amb as the results of depth 1 (the shading step overwrites them, so every
+// attempt plants them again), then the shading step of depth 0 with k_gi_final, as compiled.
+int half_shade(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n, int kind,
+               const float4* d_amb) {
+    const int forced = ctx->tail_hint;
+    int rc = RTU_OK;
+    if (kind == HALF_AMBIENT) {
+        const hipError_t e = (hipError_t)rtu_launch_amb_seed(ctx->gi_h.get(), ctx->gi_res.get(), d_amb, n, stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "ambient seed launch: %s", hipGetErrorString(e));
+        rc = launch(ctx, &f, d_out, stream, false, 0, 1, nullptr, RTU_LAUNCH_SHADE, 0, false, nullptr, 0, d_rays, n, d_keys);
+    } else {
+        for (int k = RTU_GI_BOUNCES; k >= 1 && rc == RTU_OK; k--) {
+            ctx->tail_hint = forced;
+            rc = launch(ctx, &f, d_out, stream, false, 0, 1, nullptr, RTU_LAUNCH_SHADE, k, false, nullptr, 0, d_rays, n, d_keys);
+        }
+        if (rc == RTU_OK) {
+            const hipError_t e = (hipError_t)rtu_launch_gather_amb(half_scene(ctx), ctx->gi_h.get(), ctx->gi_res.get(), n, d_out, stream);
+            if (e != hipSuccess) rc = fail(ctx, RTU_ERR_HIP, "gather sum launch: %s", hipGetErrorString(e));
+        }
+    }
+    ctx->tail_hint = 0;
+    return rc;
+}
+
+// shade_until_fits for a half: attempt, wait, check_overflow, and again with the capacities that raised
+int half_until_fits(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n, int kind,
+                    const float4* d_amb, const char* counters_refusal) {
+    for (int attempt = 0;; attempt++) {
+        int rc = half_shade(ctx, f, d_out, stream, d_rays, d_keys, n, kind, d_amb);
+        if (rc != RTU_OK) return rc;
+        RTU_HIP(ctx, hipStreamSynchronize(stream));
+        bool overflow = false;
+        if ((rc = check_overflow(ctx, &overflow)) != RTU_OK) return rc;
+        if (!overflow) return RTU_OK;
+        if (f.collect_stats && counters_refusal) return fail(ctx, RTU_ERR_CAPACITY, "%s", counters_refusal);
+        if (attempt >= 8 * RTU_MAX_LEVELS) return fail(ctx, RTU_ERR_CAPACITY, "recursion frames still exceed the capacity after %d rounds", attempt);
+    }
+}
+
+int half_check_amb(RtuContext* ctx, const void* amb, size_t n, bool device) {
+    if (n && !amb) return fail(ctx, RTU_ERR_ARG, "amb pointer is NULL");
+    if (n && ((uintptr_t)amb & (device ? 15u : 3u))) return fail(ctx, RTU_ERR_ARG, device ? "the device amb buffer must be 16-byte aligned" : "amb must be 4-byte aligned");
+    return RTU_OK;
+}
+
+int half_device(RtuContext* ctx, const void* d_rays, const void* d_keys, const void* d_amb, size_t n, const RtuShadeDesc* desc, void* d_out, void* hip_stream, int kind) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    int rc = shade_args(ctx, d_rays, d_out, n, desc, true, &f, true, d_keys, true);
+    if (rc == RTU_OK && kind == HALF_AMBIENT) rc = half_check_amb(ctx, d_amb, n, true);
+    if (rc != RTU_OK || n == 0) return rc;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = half_chain(ctx, f, (float4*)d_out, (hipStream_t)hip_stream, (const float4*)d_rays, (const uint32_t*)d_keys, (uint32_t)n, kind)) != RTU_OK) return rc;
+    return half_shade(ctx, f, (float4*)d_out, (hipStream_t)hip_stream, (const float4*)d_rays, (const uint32_t*)d_keys, (uint32_t)n, kind, (const float4*)d_amb);
+}
+
+// shade_host for a half: chunks through the context's buffers, the chain of a chunk traced once, its shading repeated if need be
+int half_host(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, const float* h_amb, size_t n, const RtuShadeDesc* desc, float* h_out, RtuStats* stats,
+              int kind) {
+    if (!ctx) return RTU_ERR_ARG;
+    RtuFrameDesc f;
+    int rc = shade_args(ctx, h_rays, h_out, n, desc, false, &f, true, h_keys, true);
+    if (rc == RTU_OK && kind == HALF_AMBIENT) rc = half_check_amb(ctx, h_amb, n, false);
+    if (rc != RTU_OK) return rc;
+    if (stats) { memset(stats, 0, sizeof *stats); f.collect_stats = 1; }
+    if (n == 0) return RTU_OK;
+    const size_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->sh_rays.grow(2 * chunk));
+    RTU_HIP(ctx, ctx->sh_out.grow(chunk));
+    RTU_HIP(ctx, ctx->sh_keys.grow(chunk));
+    if (kind == HALF_AMBIENT) RTU_HIP(ctx, ctx->sh_amb.grow(chunk));
+    for (size_t done = 0; done < n; done += chunk) {
+        const size_t m = n - done < chunk ? n - done : chunk;
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_rays.get(), h_rays + done, sizeof(RtuRay) * m, hipMemcpyHostToDevice, ctx->stream));
+        RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_keys.get(), h_keys + done, sizeof(uint32_t) * m, hipMemcpyHostToDevice, ctx->stream));
+        if (kind == HALF_AMBIENT) RTU_HIP(ctx, hipMemcpyAsync(ctx->sh_amb.get(), h_amb + 4 * done, sizeof(float4) * m, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = half_chain(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), ctx->sh_keys.get(), (uint32_t)m, kind)) != RTU_OK) return rc;
+        if ((rc = half_until_fits(ctx, f, ctx->sh_out.get(), ctx->stream, ctx->sh_rays.get(), ctx->sh_keys.get(), (uint32_t)m, kind, ctx->sh_amb.get(),
+                                  "recipe P with counters: frame records ran out; shade the batch once without counters first")) != RTU_OK)
+            return rc;
+        RTU_HIP(ctx, hipMemcpy(h_out + 4 * done, ctx->sh_out.get(), sizeof(float4) * m, hipMemcpyDeviceToHost));
+        if (stats) {  // the counters are zeroed per launch: the batch's are the sum over its chunks
+            RtuStats part;
+            if ((rc = rtu_get_stats(ctx, &part)) != RTU_OK) return rc;
+            unsigned long long* to = reinterpret_cast<unsigned long long*>(stats);
+            const unsigned long long* from = reinterpret_cast<const unsigned long long*>(&part);
+            for (size_t k = 0; k < sizeof(RtuStats) / sizeof(unsigned long long); k++) to[k] += from[k];
+        }
+    }
+    return RTU_OK;
+}
+}  // namespace
+
+int rtu_gather_rays_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_ct, void* hip_stream) {
+    return half_device(ctx, d_rays, d_keys, nullptr, n, desc, d_ct, hip_stream, HALF_GATHER);
+}
+int rtu_gather_rays(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, size_t n, const RtuShadeDesc* desc, float* h_ct, RtuStats* stats) {
+    return half_host(ctx, h_rays, h_keys, nullptr, n, desc, h_ct, stats, HALF_GATHER);
+}
+int rtu_shade_rays_ambient_device(RtuContext* ctx, const void* d_rays, const void* d_keys, const void* d_amb, size_t n, const RtuShadeDesc* desc,
+                                  void* d_rgbt, void* hip_stream) {
+    return half_device(ctx, d_rays, d_keys, d_amb, n, desc, d_rgbt, hip_stream, HALF_AMBIENT);
+}
+int rtu_shade_rays_ambient(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, const float* h_amb, size_t n, const RtuShadeDesc* desc,
+                           float* h_rgbt, RtuStats* stats) {
+    return half_host(ctx, h_rays, h_keys, h_amb, n, desc, h_rgbt, stats, HALF_AMBIENT);
+}
+
+// ---- the irradiance map (rtu_irradiance.h, rtu_irradiance.hip) ----
+namespace {
+const size_t kIrrChunkChains = (size_t)1 << 22;  // chains per chunk of a pass's list: 1.4 GB of chain records and results
+
+int irr_check_frame(RtuContext* ctx, const RtuFrameDesc* frame) {
+    if (!frame || frame->width <= 0 || frame->height <= 0) return fail(ctx, RTU_ERR_ARG, "frame is NULL or empty");
+    if (frame->shard_count > 1 || frame->shard_rank != 0) return fail(ctx, RTU_ERR_UNSUPPORTED, "the irradiance map has no sharded form");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(frame->cam_pos[k]) || !std::isfinite(frame->origin[k]) || !std::isfinite(frame->u[k]) || !std::isfinite(frame->v[k]))
+            return fail(ctx, RTU_ERR_ARG, "the frame's camera is not finite");
+    return RTU_OK;
+}
+
+int irr_check_map(RtuContext* ctx, const RtuIrradianceMap* map, bool device, IrrGrid* g) {
+    if (!map || map->reserved || map->reserved_ptr) return fail(ctx, RTU_ERR_ARG, "map is NULL, or its reserved fields are not 0");
+    if (map->max_subdiv < -15) return fail(ctx, RTU_ERR_ARG, "map.max_subdiv out of range");
+    RtuIrradianceDesc d;
+    rtu_irradiance_defaults(&d);
+    d.min_subdiv = map->max_subdiv < 0 ? map->max_subdiv : 0;
+    d.max_subdiv = map->max_subdiv;
+    const int rc = rtu_irradiance_check(&d, map->width, map->height, g);
+    if (rc != RTU_OK) return fail(ctx, rc, rc == RTU_ERR_UNSUPPORTED ? "max_subdiv > 0 (several points per pixel) is not supported" : "the image is no multiple of the map's spacing, or too large");
+    if (!map->records) return fail(ctx, RTU_ERR_ARG, "map.records is NULL");
+    if (device && ((uintptr_t)map->records & 15u)) return fail(ctx, RTU_ERR_ARG, "device records must be 16-byte aligned");
+    return RTU_OK;
+}
+}  // namespace
+
+int rtu_irradiance_sample_device(RtuContext* ctx, const RtuIrradianceMap* map, const void* d_xy, size_t n, void* d_out, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    IrrGrid g;
+    const int rc = irr_check_map(ctx, map, true, &g);
+    if (rc != RTU_OK || n == 0) return rc;
+    if (!d_xy || !d_out) return fail(ctx, RTU_ERR_ARG, "position / result pointer is NULL");
+    if (((uintptr_t)d_xy & 3u) || ((uintptr_t)d_out & 15u)) return fail(ctx, RTU_ERR_ARG, "positions must be 4-byte, results 16-byte aligned");
+    if (n > ((size_t)1 << 26)) return fail(ctx, RTU_ERR_ARG, "more than 2^26 positions in one call");
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = (hipError_t)rtu_launch_irr_sample((const float4*)map->records, g, (const float*)d_xy, n, (float4*)d_out, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "irradiance lookup launch: %s", hipGetErrorString(e));
+    return RTU_OK;
+}
+
+int rtu_irradiance_build_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceDesc* desc, void* d_records, void* d_computed,
+                                uint32_t* n_computed, uint32_t* per_pass, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = irr_check_frame(ctx, frame);
+    if (rc != RTU_OK) return rc;
+    IrrGrid g;
+    if ((rc = rtu_irradiance_check(desc, frame->width, frame->height, &g)) != RTU_OK)
+        return fail(ctx, rc, rc == RTU_ERR_UNSUPPORTED ? "max_subdiv > 0 (several points per pixel) is not supported"
+                                                       : "irradiance: min_subdiv -15 .. max_subdiv <= 0, width and height multiples of 2^-max_subdiv, samples 1 .. 4096, "
+                                                         "first_sample >= 0, thresholds no NaN, max_bounce 0 .. 5, reserved 0, at most 2^26 points");
+    if (!d_records || !d_computed) return fail(ctx, RTU_ERR_ARG, "records / computed pointer is NULL");
+    if ((uintptr_t)d_records & 15u) return fail(ctx, RTU_ERR_ARG, "device records must be 16-byte aligned");
+    RtuShadeDesc sd;
+    rtu_shade_defaults(&sd);
+    memcpy(sd.eye, frame->cam_pos, sizeof sd.eye);
+    sd.max_bounce = desc->max_bounce;
+    RtuFrameDesc f;  // what launch() takes for a path-traced ray batch (RTU_ERR_NO_SCENE here)
+    if ((rc = shade_args(ctx, nullptr, nullptr, 0, &sd, true, &f, true, nullptr, true)) != RTU_OK) return rc;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t points = (size_t)g.gw * g.gh;
+    const uint32_t M = (uint32_t)desc->samples;
+    const size_t chunk_points = kIrrChunkChains / M ? kIrrChunkChains / M : 1;
+    const size_t max_chains = (points < chunk_points ? points : chunk_points) * M;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t scratch_words = rtu_irr_scratch_words(points);
+    RTU_HIP(ctx, ctx->ir_scratch.grow(scratch_words + 4));  // (+ the list's length)
+    RTU_HIP(ctx, ctx->ir_list.grow(points));
+    RTU_HIP(ctx, ctx->ir_keys.grow(max_chains));
+    RTU_HIP(ctx, ctx->ir_c.grow(max_chains));
+    uint32_t* const d_total = ctx->ir_scratch.get() + scratch_words;
+    float4* const rec = (float4*)d_records;
+    uint8_t* const bytes = (uint8_t*)d_computed;
+    float4* const c = ctx->ir_c.get();
+    IrrThresholds t;
+    memcpy(t.color, desc->threshold_color, sizeof t.color);
+    t.z = desc->threshold_z;
+    t.n = desc->threshold_n;
+    IrrRoots roots;
+    memcpy(roots.cam.cam_pos, frame->cam_pos, sizeof roots.cam.cam_pos);
+    memcpy(roots.cam.origin, frame->origin, sizeof roots.cam.origin);
+    memcpy(roots.cam.u, frame->u, sizeof roots.cam.u);
+    memcpy(roots.cam.v, frame->v, sizeof roots.cam.v);
+    roots.cam.scale = (float)g.scale;
+    roots.cam.gw = g.gw;
+    roots.samples = M;
+    roots.first_sample = (uint32_t)desc->first_sample;
+    uint32_t computed_all = 0;
+    for (uint32_t p = 0; p <= 2u * g.levels; p++) {
+        const IrrPass q = irr_pass(g, p);
+        hipError_t e = (hipError_t)rtu_launch_irr_classify(q, t, rec, bytes, ctx->ir_list.get(), d_total, ctx->ir_scratch.get(), stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "irradiance classify launch: %s", hipGetErrorString(e));
+        uint32_t total = 0;
+        RTU_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, stream));
+        RTU_HIP(ctx, hipStreamSynchronize(stream));
+        if (total > q.count) return fail(ctx, RTU_ERR_HIP, "irradiance pass %u listed %u of %u points", p, total, q.count);
+        for (size_t base = 0; base < total; base += chunk_points) {
+            if (cancel_raised(ctx)) return fail(ctx, RTU_ERR_CANCELLED, "cancelled in pass %u of the irradiance map", p);
+            const uint32_t m = (uint32_t)(total - base < chunk_points ? total - base : chunk_points), n = m * M;
+            RTU_HIP(ctx, ctx->gi_h.grow((size_t)n * (RTU_GI_BOUNCES + 1) * 4));  // (what launch() grows them to for n chains)
+            RTU_HIP(ctx, ctx->gi_res.grow((size_t)n * 2));
+            roots.list = ctx->ir_list.get() + base;
+            roots.n_points = m;
+            e = (hipError_t)rtu_launch_irr_roots(half_scene(ctx), roots, ctx->bvh_stack_needed, ctx->gi_h.get(), c, stream);
+            if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "irradiance roots launch: %s", hipGetErrorString(e));
+            // the chain steps of a path-traced batch of n rays: they read chain records, no ray and no key (the pointers only say "a ray batch")
+            const int forced = ctx->tail_hint;
+            for (int k = 1; k <= RTU_GI_BOUNCES; k++) {
+                ctx->tail_hint = 0;
+                if ((rc = launch(ctx, &f, c, stream, k == 1, 0, 1, nullptr, RTU_LAUNCH_CHAIN, k, false, nullptr, 0, c, n, ctx->ir_keys.get())) != RTU_OK) return rc;
+            }
+            ctx->tail_hint = forced;
+            if ((rc = half_until_fits(ctx, f, c, stream, c, ctx->ir_keys.get(), n, HALF_GATHER, nullptr, nullptr)) != RTU_OK) return rc;
+            e = (hipError_t)rtu_launch_irr_store(roots.list, m, M, c, ctx->gi_h.get(), rec, bytes, stream);
+            if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "irradiance store launch: %s", hipGetErrorString(e));
+        }
+        if (per_pass) { per_pass[2 * p] = q.count; per_pass[2 * p + 1] = total; }
+        computed_all += total;
+    }
+    RTU_HIP(ctx, hipStreamSynchronize(stream));
+    if (n_computed) *n_computed = computed_all;
+    return RTU_OK;
+}
+
+int rtu_irradiance_build(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceDesc* desc, float* h_records, uint8_t* h_computed,
+                         uint32_t* n_computed, uint32_t* per_pass) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!h_records || !h_computed) return fail(ctx, RTU_ERR_ARG, "records / computed pointer is NULL");
+    int rc = irr_check_frame(ctx, frame);
+    if (rc != RTU_OK) return rc;
+    IrrGrid g;
+    size_t points = 1;
+    if (rtu_irradiance_check(desc, frame->width, frame->height, &g) == RTU_OK) points = (size_t)g.gw * g.gh;  // (else the _device form refuses)
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->ir_rec.grow(2 * points));
+    RTU_HIP(ctx, ctx->ir_bytes.grow(points));
+    if ((rc = rtu_irradiance_build_device(ctx, frame, desc, ctx->ir_rec.get(), ctx->ir_bytes.get(), n_computed, per_pass, ctx->stream)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpy(h_records, ctx->ir_rec.get(), sizeof(float4) * 2 * points, hipMemcpyDeviceToHost));
+    RTU_HIP(ctx, hipMemcpy(h_computed, ctx->ir_bytes.get(), points, hipMemcpyDeviceToHost));
+    return RTU_OK;
+}
+
+int rtu_render_frame_irradiance_device(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceMap* map, void* d_rgbz, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    int rc = irr_check_frame(ctx, frame);
+    if (rc != RTU_OK) return rc;
+    if (frame->samples < 1) return fail(ctx, RTU_ERR_ARG, "the irradiance frame is a recipe-S frame: samples >= 1");
+    if (frame->gather_bounces != 0) return fail(ctx, RTU_ERR_ARG, "the map replaces the gather: gather_bounces must be 0");
+    IrrGrid g;
+    if ((rc = irr_check_map(ctx, map, true, &g)) != RTU_OK) return rc;
+    if (map->width != frame->width || map->height != frame->height) return fail(ctx, RTU_ERR_ARG, "the map was built for another image size");
+    if (!d_rgbz) return fail(ctx, RTU_ERR_ARG, "image pointer is NULL");
+    if ((uintptr_t)d_rgbz & 15u) return fail(ctx, RTU_ERR_ARG, "the device image must be 16-byte aligned");
+    const size_t pixels = (size_t)frame->width * (size_t)frame->height;
+    if (pixels > kPathChains) return fail(ctx, RTU_ERR_ARG, "more than 2^25 pixels");
+    RtuShadeDesc sd;
+    rtu_shade_defaults(&sd);
+    memcpy(sd.eye, frame->cam_pos, sizeof sd.eye);
+    sd.max_bounce = frame->max_bounce;
+    sd.flags = frame->collect_stats == 1 ? RTU_QUERY_REFERENCE_WALK : 0u;
+    RtuFrameDesc f;
+    if ((rc = shade_args(ctx, nullptr, nullptr, 0, &sd, true, &f, true, nullptr, true)) != RTU_OK) return rc;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->ir_rays.grow(2 * pixels));
+    RTU_HIP(ctx, ctx->ir_keys.grow(pixels));
+    RTU_HIP(ctx, ctx->ir_c.grow(pixels));
+    RTU_HIP(ctx, ctx->ir_amb.grow(pixels));
+    RTU_HIP(ctx, ctx->ir_acc.grow(pixels));
+    RTU_HIP(ctx, ctx->ir_hits.grow(pixels));
+    float4* const rays = ctx->ir_rays.get();
+    float4* const out = ctx->ir_c.get();
+    uint32_t* const keys = ctx->ir_keys.get();
+    hipError_t e = (hipError_t)rtu_launch_irr_lookup_centres((const float4*)map->records, g, (uint32_t)frame->width, (uint32_t)frame->height, ctx->ir_amb.get(), stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "irradiance lookup launch: %s", hipGetErrorString(e));
+    for (int k = 0; k < frame->samples; k++) {
+        if (cancel_raised(ctx)) return fail(ctx, RTU_ERR_CANCELLED, "cancelled after %d of %d samples", k, frame->samples);
+        e = (hipError_t)rtu_launch_camera_sample_rays(cam_sample(frame, k), rays, keys, stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "camera ray launch: %s", hipGetErrorString(e));
+        if ((rc = half_chain(ctx, f, out, stream, rays, keys, (uint32_t)pixels, HALF_AMBIENT)) != RTU_OK) return rc;
+        if ((rc = half_until_fits(ctx, f, out, stream, rays, keys, (uint32_t)pixels, HALF_AMBIENT, ctx->ir_amb.get(),
+                                  "the irradiance frame with counters: frame records ran out; render it once without counters first")) != RTU_OK)
+            return rc;
+        e = (hipError_t)rtu_launch_accumulate(out, 1u, ctx->ir_acc.get(), ctx->ir_hits.get(), (uint32_t)pixels, k == 0, stream);
+        if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "accumulate launch: %s", hipGetErrorString(e));
+    }
+    e = (hipError_t)rtu_launch_resolve(ctx->ir_acc.get(), ctx->ir_hits.get(), (float4*)d_rgbz, (uint32_t)pixels, (uint32_t)frame->samples, stream);
+    if (e != hipSuccess) return fail(ctx, RTU_ERR_HIP, "resolve launch: %s", hipGetErrorString(e));
+    RTU_HIP(ctx, hipStreamSynchronize(stream));
+    return RTU_OK;
+}
+
+int rtu_render_frame_irradiance(RtuContext* ctx, const RtuFrameDesc* frame, const RtuIrradianceMap* map, float* h_rgbz) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!h_rgbz) return fail(ctx, RTU_ERR_ARG, "image pointer is NULL");
+    int rc = irr_check_frame(ctx, frame);
+    if (rc != RTU_OK) return rc;
+    IrrGrid g;
+    if ((rc = irr_check_map(ctx, map, false, &g)) != RTU_OK) return rc;
+    const size_t points = (size_t)g.gw * g.gh, pixels = (size_t)frame->width * (size_t)frame->height;
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, ctx->ir_rec.grow(2 * points));
+    RTU_HIP(ctx, ctx->ir_img.grow(pixels));
+    RTU_HIP(ctx, hipMemcpy(ctx->ir_rec.get(), map->records, sizeof(float4) * 2 * points, hipMemcpyHostToDevice));
+    RtuIrradianceMap dm = *map;
+    dm.records = ctx->ir_rec.get();
+    if ((rc = rtu_render_frame_irradiance_device(ctx, frame, &dm, ctx->ir_img.get(), ctx->stream)) != RTU_OK) return rc;
+    RTU_HIP(ctx, hipMemcpy(h_rgbz, ctx->ir_img.get(), sizeof(float4) * pixels, hipMemcpyDeviceToHost));
+    return RTU_OK;
 }
 
 uint32_t rtu_sample_key(uint32_t pixel, uint32_t sample) { return h_mix32(h_mix32(pixel + 0x68bc21ebU) ^ (sample * 0x9e3779b9U + 1U)); }
