@@ -1,9 +1,28 @@
 // rtu_capi.hip — host side of the C-ABI in include/rtu_render.h: context, scene
 // validation + upload into the HBM layout of rtu_device.h, frame set-up and
-// kernel launch. Compiled by hipcc with -ffp-contract=off so the few host-side
-// float computations (triangle normals, camera frame) round exactly like the
-// reference's CPU code.
+// kernel launch. What an upload builds on the host without a GPU (trees, triangle
+// records, world bounds, occluder lists) is in rtu_capi_build.hip; rtu_capi.h is
+// what the two share. Both are compiled by hipcc with -ffp-contract=off so the few
+// host-side float computations (triangle normals there, the camera frame here)
+// round exactly like the reference's CPU code.
+//
+// The concerns this file still holds, and all that one uses of another (the rest of each is its own):
+//   scene        validation, place_scene, upload, updates in place, scene motion, mesh and light-list dumps, sort boxes
+//   frame path   check_frame, level buffers, launch(), check_overflow, the sampled / adaptive / progressive paths, every
+//                rtu_render_frame*, statistics, probes, switches, self-tests. Used from outside: launch (ray batches, the halves,
+//                the irradiance build), check_overflow (ray batches), check_frame (temporal sessions), halton (cam_sample,
+//                sensors), cancel_raised (irradiance, sensors), check_adaptive_desc (adaptive sensors)
+//   queries      ray queries, first-hit features, surface records, rtu_denoise_device. Used from outside: query_scene and
+//                feature_cam (the denoised progressive snapshot), kQueryChunk (ray batches), misaligned (frame path, temporal)
+//   ray batches  shade_args, paths_chain, shade_until_fits, the host sample streams, cam_sample, the half_* family, ray ordering.
+//                Used from outside: shade_args, paths_chain, shade_until_fits (sensors, temporal sessions), shade_args, half_scene,
+//                half_chain, half_until_fits, kPathChains (irradiance), cam_sample (irradiance, temporal), HostSinCos (sensors, temporal)
+//   irradiance   the map's build, sample and frame; nothing of it is used elsewhere
+//   temporal     the accumulators' entries and the sessions (RtuTemporal); nothing of it is used elsewhere but temporal_release
+//   sensors      sensors and adaptive sensors. Used from outside: check_sensor, sensor_generate (the temporal sensor forms)
+// Beyond these, one concern calls another only through its public rtu_* entries.
 #include "rtu_camrays.h"
+#include "rtu_capi.h"
 #include "rtu_denoise.h"
 #include "rtu_devbuf.h"
 #include "rtu_device.h"
@@ -34,165 +53,11 @@
 #include <string>
 #include <vector>
 
-struct RtuProgressive;
-struct RtuTemporal;
-
-struct RtuContext {
-    int         device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t aux_stream = nullptr;        // side mode (rtu_device.h KernelArgs::fcnt0): stage 2 of the primary phase runs here, beside the levels
-    hipEvent_t  aux_ev0 = nullptr, aux_ev1 = nullptr;
-    hipEvent_t  ev0 = nullptr, ev1 = nullptr;
-    std::string error;
-
-    // scene
-    bool     has_scene = false;
-    uint32_t n_textures = 0;              // of the uploaded scene, and a host copy of its material maps: rtu_debug_texcoords
-    std::vector<RtuTexMap> mat_maps_host; //   checks a texture / map before the kernel reads it
-    std::vector<DevBuf<char>> scene_allocs;  // meshes and textures: live until the next upload
-    std::vector<DevBuf<char>> place;      // what depends on node transformations, lights and materials, by slot (place_scene): an
-                                          //   update rewrites these in place, growing one only when it is too small
-    // the shape of the uploaded scene (rtu_update_scene refuses any other) and what an update builds from
-    std::vector<RtuNode> shape_nodes;
-    std::vector<RtuMesh> shape_meshes;       // headers only: the arrays stay NULL
-    std::vector<RtuTexture> shape_textures;  // likewise
-    uint32_t shape_materials = 0;
-    bool     shape_maps = false;
-    std::vector<std::vector<uint32_t>> fast_elements;  // per mesh: slot of the fast tree's leaf order -> face
-    std::vector<DevMesh> dmeshes;            // host copy of the device mesh records (their f / v arrays)
-    std::vector<const uint32_t*> slot_of;    // per mesh, device: face -> slot of the fast tree
-    std::vector<DevLightMask> lmask_host;    // host copy of DevScene::lmask (rtu_debug_context_light_list)
-    LlBuilder* llb = nullptr;                // the device builder of the occluder lists (rtu_scene_update.hip)
-    // what rtu_update_meshes needs of a mesh beyond its device record: the node ranges of the levels of its collapsed fast trees
-    // (root first, [levels + 1]) and which of scene_allocs holds its ref.bvh (the one per-mesh buffer whose size an update can change)
-    struct MeshRefit { std::vector<uint32_t> lvl4, lvl8; size_t ref_bvh_alloc = 0, v_alloc = 0, vn_alloc = 0; };
-    std::vector<MeshRefit> refit;
-    // rtu_keep_previous_vertices: a mesh's positions and normals as they were before the last rtu_update_meshes — the buffers that
-    // update swapped out of scene_allocs (valid), else "previous" is "current". df_*: the table the deform accumulator's kernels read
-    // (TpDeformScene, rtu_temporal.h), rebuilt after an upload, an update or a change of the switch (df_dirty).
-    bool keep_prev = false;
-    struct PrevGen { DevBuf<char> v, vn; bool valid = false; };
-    std::vector<PrevGen> prev_gen;
-    DevBuf<TpDeformMesh> df_meshes;
-    DevBuf<int32_t>      df_nodes;
-    bool                 df_dirty = true;
-    bool  mu_timing = false;                 // rtu_debug_mesh_update_timing: HIP events around the phases of rtu_update_meshes
-    float mu_ms[4] = {};                     // copies, records, refit, placement: summed since the last read
-    hipEvent_t mu_ev[5] = {};
-    DevScene dscene{};
-    uint32_t bvh_stack_needed = 1;
-
-    // per-frame resources (grown on demand, reused)
-    std::vector<DevBuf<char>> level_allocs;  // the storage of lv, lv_side and the defer lists
-    LevelBuffers lv[RTU_MAX_LEVELS] = {};
-    uint32_t level_nsl = 0;
-    uint32_t want_cap_s[RTU_MAX_LEVELS] = {};  // per-shard capacity wanted for levels >= 1 (grown from the counts of an overflowed frame)
-    uint32_t want_defer_s = 0;
-    DevBuf<FrameCounters> fcnt;
-    uint32_t* defer_list = nullptr;
-    uint32_t  defer_cap_s = 0;
-    DevBuf<FrameCounters> fcnt_side;         // side mode: counters of the primary phase's defer list and of the side level arrays
-    int sequences_in_flight = 1;             // rtu_set_sequences_in_flight: launch sequences the caller keeps in flight on this GPU (all its contexts together)
-    uint32_t* defer_list0 = nullptr;         // the primary phase's own defer list
-    uint32_t  defer_cap0_s = 0;
-    LevelBuffers lv_side[RTU_MAX_LEVELS] = {};
-    std::map<uint64_t, bool> side_off;       // launch shapes whose stage 2 made more frames than the side arrays take: no side mode for them
-    std::map<uint64_t, uint32_t> occ_hints;   // ... and how many 8x8 tiles had anything in them (k_tile_occ): the grid of k_primary
-    std::map<uint64_t, uint64_t> side_frames; // ... and how many level-0 frames stage 2 of the primary phase made in the last launch of a shape
-    bool     last_side = false;
-    bool     mesh_hits_childless = false;    // no mesh node's material reflects or refracts: a mesh hit's Shade() call is settled by the lane that found it
-    bool     any_recursive_material = true;
-    bool     textured = false;
-    bool     scene_stochastic = false;   // soft shadows / glossy bounces / depth of field: recipe S only
-    std::string stochastic_what;
-    DevBuf<float4>   acc;                // recipe S accumulators: rgb sum + z sum, hit count
-    DevBuf<uint32_t> acc_hits;
-    DevBuf<float4>   sample_buf;         // the images of one batch of samples, [sample][pixel]
-    DevBuf<float4>   ad_sq;              // adaptive sampling (rtu_render_frame_adaptive): sums of squares and sample counts per pixel
-    DevBuf<uint8_t>  ad_counts;
-    DevBuf<uint4>    ad_list[2];         // ... the active-tile lists {tile, 0, lane mask}, double-buffered, and their lengths
-    DevBuf<uint32_t> ad_n;               // [2] on the device
-    PinnedBuf<uint32_t> ad_n_host;       // pinned: the length of the list the next batch walks
-    DevBuf<float4>   gi_h;               // recipe P: chain records [5 depths][4][chains], results [2][chains]
-    DevBuf<float4>   gi_res;
-    bool      want_gi = false;           // level buffers carry famb
-    // k_tail: the recursion level from which the previous frame of this scene was almost empty (a hint —
-    // any value renders the same image); last_tail_from: what the most recent frame was launched with
-    int      tail_hint = 0, last_tail_from = RTU_MAX_LEVELS;   // tail_hint: set by rtu_debug_tail_from for the next launch (0: none)
-    std::map<uint64_t, int> tail_hints;   // per launch shape (tiles of the launch, feature set): learned cut level
-    std::map<uint64_t, std::array<uint32_t, 8>> list_hints;  // ... and the rays deferred in every phase, + 1 (KernelArgs::list_n)
-    uint64_t last_tail_key = 0;
-    bool     last_stats = false;
-    uint32_t n_meshes = 0;
-    uint32_t nsl = 0;
-    int32_t  shadow_light[RTU_MAX_SHADOW_LIGHTS] = {};
-    float    nol_light[RTU_FI_NOL_LIGHTS][4] = {};
-    DevBuf<float4> fb;
-    DevBuf<unsigned long long> counters;     // 11 x u64 (RtuStats), or the touched-bytes table [RTU_TL_KERNELS][RTU_TOUCH_STRIDE]
-    uint32_t slot_launches[RTU_TL_KERNELS] = {};  // touched-bytes mode: launches per slot that went into the table (rtu_get_touched_launches)
-    // probe: HIP events around the launches of one timeline slot (rtu_probe_kernel)
-    static const int kProbePairs = 64;
-    int probe_slot = -1, probe_used = 0;
-    hipEvent_t probe_ev[2 * kProbePairs] = {};
-    struct MeshInfo { uint32_t faces, sah_depth, stack4, nodes4, nodes8; };
-    std::vector<MeshInfo> mesh_info;
-    struct LightListInfo { uint32_t light, cover, G, entries, longest; };  // the occluder lists built at upload (rtu_light_list_info)
-    std::vector<LightListInfo> light_list_info;
-    // cameras of a batch of frames: written into the next slot of a ring of pinned host slots, copied to d_cams on the launch
-    // stream ahead of the kernels (stream order protects d_cams; an event per slot protects the slot from being rewritten
-    // while its copy is still pending)
-    static const int kCamSlots = 16;
-    DevBuf<BatchCam> d_cams;
-    PinnedBuf<BatchCam> h_cams;
-    hipEvent_t cam_ev[kCamSlots] = {};
-    int cam_slot = 0;
-    uint32_t dbg = 0;
-    const volatile int* cancel = nullptr;    // rtu_set_cancel_flag: polled between the launch sequences of a sampled frame
-    uint64_t scene_gen = 0;                  // bumped by every upload and update: a progressive session of an older scene is stale
-    std::vector<RtuProgressive*> sessions;   // the open progressive sessions (rtu_destroy_context frees their device memory)
-    std::vector<RtuTemporal*> temporals;     // ... and the open temporal sessions (rtu_temporal_begin), likewise
-    DevBuf<uint32_t> cover;                  // coverage masks of primary rays (KernelArgs::cover), grown on demand
-    uint32_t  cover_faces = 0;
-    DevBuf<uint32_t> occ;                    // tile occupancy of primary rays (KernelArgs::occ), grown on demand
-    int4* node_rects = nullptr;              // [RTU_MAX_FRAME_BATCH][n_nodes] screen rectangles of the node-level bounds (k_node_rects); owned by the scene
-    DevBuf<float4>  q_rays, q_hits;          // ray queries, host forms (rtu_trace_rays / rtu_occluded_rays): one chunk of rays and of answers
-    DevBuf<uint8_t> q_occ;
-    DevBuf<float4>  ft_albedo;               // first-hit features, host forms (rtu_ray_features / rtu_frame_features): one chunk of albedo (rays and hits: q_rays, q_hits)
-    DevBuf<float4>  ft_surface;              // ... and of surface records (rtu_ray_surface / rtu_frame_surface), two float4 each: grown by those two only
-    DevBuf<float4>  dn_planes;               // the denoising filter (rtu_denoise_device): its four planes gN, gP, e0, e1 of one frame
-    DevBuf<float4>  sh_rays, sh_out;         // ray batches, host form (rtu_shade_rays): one chunk of rays and of {r, g, b, t}
-    DevBuf<uint32_t> sh_keys;                // ... and of keys (rtu_shade_rays_sampled)
-    float sort_box[6] = {};                  // ray sorting (rtu_raysort.h): the box the keys are quantised in, kept by place_scene
-    DevBuf<uint32_t> so_scratch;             // ... keys and indices double-buffered, digit histograms (rtu_ray_order_device)
-    DevBuf<float4>   so_rays;                // ... the host form's rays and order (rtu_ray_order)
-    DevBuf<uint32_t> so_order;
-    DevBuf<float4>   sn_rays, sn_out;        // sensors (rtu_render_sensor): the rays of one batch of samples, their {r, g, b, t} [sample][pixel],
-    DevBuf<uint32_t> sn_keys, sn_hits;       // ... their keys; the hit counts and
-    DevBuf<float4>   sn_acc, sn_img;         // ... the sums per pixel (none of the frame path's acc / acc_hits); the host form's image
-    bool  sn_timing = false;                 // rtu_debug_sensor_timing: HIP events around the two kernels of rtu_sensor.hip and the whole render
-    float sn_ms[3] = {};                     // k_sensor_rays, k_sensor_accumulate, the render: summed since the last read
-    hipEvent_t sn_ev[6] = {};
-    DevBuf<float4>   sa_s, sa_q, sa_img;     // adaptive sensors (rtu_render_sensor_adaptive): per pixel the sums and the sums of squares with the hit count; the host form's image
-    DevBuf<uint32_t> sa_list[2], sa_packed;  // ... the live-pixel lists, double-buffered, the survivors packed per block,
-    DevBuf<uint32_t> sa_blk, sa_n;           // ... their number per block and its scan, the length of the next list
-    PinnedBuf<uint32_t> sa_n_host;           // ... and where the host reads it (pinned)
-    DevBuf<uint8_t>  sa_counts;              // ... the host form's counts
-    std::vector<uint32_t> sa_trace;          // {live pixels, samples} of every batch of the last adaptive sensor render (rtu_debug_sensor_adaptive_trace)
-    DevBuf<uint32_t> st_scratch;            // steered sampling (rtu_sample_allocation_device): the weights, the tile sums, Wsum
-    DevBuf<float4>   sh_amb;                 // the two halves of a recipe-P sample, host form (rtu_shade_rays_ambient): one chunk of AmbientLight intensities
-    DevBuf<uint32_t> ir_scratch, ir_list;    // irradiance map (rtu_irradiance_build): the scratch of a pass (scan, counts, offsets, the list's length), its list,
-    DevBuf<uint32_t> ir_keys, ir_hits;       // ... the key slots of a chunk's chain steps / the keys of a frame's sample; the frame's hit counts,
-    DevBuf<float4>   ir_c, ir_rays;          // ... {c, t} per chain of a chunk / {r, g, b, t} of a frame's sample; its rays,
-    DevBuf<float4>   ir_amb, ir_acc;         // ... the frame's AmbientLight per pixel and its sums,
-    DevBuf<float4>   ir_rec, ir_img;         // ... the host forms' records and image,
-    DevBuf<uint8_t>  ir_bytes;               // ... and computed bytes
-    DevBuf<unsigned long long> tl;           // timeline stamps, RTU_TL_KERNELS x RTU_TL_STRIDE (rtu_render_timeline)
-    bool stamp_next = false;
-};
-
 namespace {
 
 const size_t kCounterBytes = (size_t)RTU_TL_KERNELS * RTU_TOUCH_STRIDE * sizeof(unsigned long long);
+
+}  // namespace
 
 int fail(RtuContext* ctx, int code, const char* fmt, ...) {
     char buf[512];
@@ -204,11 +69,7 @@ int fail(RtuContext* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-#define RTU_HIP(ctx, call)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) return fail(ctx, RTU_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
+namespace {
 
 void free_scene(RtuContext* ctx) {
     ctx->scene_allocs.clear();
@@ -218,9 +79,7 @@ void free_scene(RtuContext* ctx) {
     ctx->has_scene = false;
 }
 
-// placement buffers by slot
-enum { P_NODES, P_MATERIALS, P_LIGHTS, P_MATMAPS, P_LMASK, P_COVER, P_LIST = P_COVER + RTU_MAX_COVER,
-       P_SLOTS = P_LIST + 2 * RTU_LMASK_LIGHTS * RTU_MAX_COVER };
+}  // namespace
 
 int ensure_place(RtuContext* ctx, int slot, size_t bytes, void** out) {
     if (ctx->place.size() < (size_t)P_SLOTS) ctx->place.resize(P_SLOTS);
@@ -230,15 +89,7 @@ int ensure_place(RtuContext* ctx, int slot, size_t bytes, void** out) {
     return RTU_OK;
 }
 
-template <class T>
-int place_upload(RtuContext* ctx, int slot, const T* src, size_t count, const T** dst) {
-    void* d = nullptr;
-    int rc = ensure_place(ctx, slot, sizeof(T) * count, &d);
-    *dst = static_cast<const T*>(d);
-    if (rc != RTU_OK) return rc;
-    if (count) RTU_HIP(ctx, hipMemcpy(d, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return RTU_OK;
-}
+namespace {
 
 // a new device allocation of `bytes`, owned by `list` (the scene's or the level arrays' storage) until it is cleared
 template <class T>
@@ -258,292 +109,6 @@ int upload(RtuContext* ctx, const T* src, size_t count, const T** dst) {
     if (count) RTU_HIP(ctx, hipMemcpy(d, src, sizeof(T) * count, hipMemcpyHostToDevice));
     *dst = d;
     return RTU_OK;
-}
-
-
-// ---- binned-SAH BVH over a mesh's triangles (the `fast` tree of DevMesh) -------------------
-// Breadth-first node numbering with adjacent sibling pairs, root = node 1, node 0 unused —
-// the layout the kernels expect. Leaves hold <= 4 triangles. Box bounds are the exact
-// min/max of the vertex coordinates (no arithmetic), like cy::BVH's.
-struct SahTree {
-    std::vector<RtuBvhNode> nodes;
-    std::vector<uint32_t>   elements;
-    uint32_t depth = 0;
-};
-
-void build_sah(const RtuMesh& m, SahTree& out) {
-    const uint32_t nf = m.nf;
-    const uint32_t max_leaf = 4;  // leaves of the one-lane-per-ray walk; the cooperative walk merges subtrees of <= 8 (build_wide8)
-    std::vector<float> bmin(3 * (size_t)nf), bmax(3 * (size_t)nf), cen(3 * (size_t)nf);
-    for (uint32_t i = 0; i < nf; i++) {
-        const uint32_t* fv = m.f + 3 * i;
-        for (int k = 0; k < 3; k++) {
-            float a = m.v[3 * fv[0] + k], b = m.v[3 * fv[1] + k], c = m.v[3 * fv[2] + k];
-            float lo = a < b ? (a < c ? a : c) : (b < c ? b : c);
-            float hi = a > b ? (a > c ? a : c) : (b > c ? b : c);
-            bmin[3 * i + k] = lo; bmax[3 * i + k] = hi; cen[3 * i + k] = 0.5f * (lo + hi);
-        }
-    }
-    std::vector<uint32_t> idx(nf);
-    for (uint32_t i = 0; i < nf; i++) idx[i] = i;
-    struct Job { uint32_t begin, end, id, level; };
-    out.nodes.assign(2, RtuBvhNode{});
-    out.elements.clear();
-    std::vector<Job> queue;
-    queue.push_back({0, nf, 1, 1});
-    auto area = [](const float* lo, const float* hi) {
-        float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-        return dx * dy + dy * dz + dz * dx;
-    };
-    for (size_t qi = 0; qi < queue.size(); qi++) {
-        const Job j = queue[qi];
-        float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f}, clo[3] = {1e30f, 1e30f, 1e30f}, chi[3] = {-1e30f, -1e30f, -1e30f};
-        for (uint32_t t = j.begin; t < j.end; t++)
-            for (int k = 0; k < 3; k++) {
-                uint32_t f = idx[t];
-                if (bmin[3 * f + k] < lo[k]) lo[k] = bmin[3 * f + k];
-                if (bmax[3 * f + k] > hi[k]) hi[k] = bmax[3 * f + k];
-                if (cen[3 * f + k] < clo[k]) clo[k] = cen[3 * f + k];
-                if (cen[3 * f + k] > chi[k]) chi[k] = cen[3 * f + k];
-            }
-        if (out.nodes.size() <= j.id) out.nodes.resize(j.id + 1, RtuBvhNode{});
-        RtuBvhNode n{};
-        for (int k = 0; k < 3; k++) { n.bmin[k] = lo[k]; n.bmax[k] = hi[k]; }
-        if (j.level > out.depth) out.depth = j.level;
-        const uint32_t count = j.end - j.begin;
-        if (count <= max_leaf) {
-            n.index = (uint32_t)out.elements.size();
-            n.count = count;
-            for (uint32_t t = j.begin; t < j.end; t++) out.elements.push_back(idx[t]);
-            out.nodes[j.id] = n;
-            continue;
-        }
-        // best binned split over the three axes
-        const int NB = 16;
-        int bestAxis = -1, bestBin = 0;
-        float bestCost = 3.0e38f;
-        for (int ax = 0; ax < 3; ax++) {
-            float ext = chi[ax] - clo[ax];
-            if (!(ext > 0)) continue;
-            uint32_t cnt[NB] = {};
-            float blo[NB][3], bhi[NB][3];
-            for (int b = 0; b < NB; b++) for (int k = 0; k < 3; k++) { blo[b][k] = 1e30f; bhi[b][k] = -1e30f; }
-            for (uint32_t t = j.begin; t < j.end; t++) {
-                uint32_t f = idx[t];
-                int b = (int)((cen[3 * f + ax] - clo[ax]) / ext * NB);
-                if (b >= NB) b = NB - 1;
-                if (b < 0) b = 0;
-                cnt[b]++;
-                for (int k = 0; k < 3; k++) {
-                    if (bmin[3 * f + k] < blo[b][k]) blo[b][k] = bmin[3 * f + k];
-                    if (bmax[3 * f + k] > bhi[b][k]) bhi[b][k] = bmax[3 * f + k];
-                }
-            }
-            // sweep: left = bins [0,s], right = (s,NB)
-            float rArea[NB];
-            uint32_t rCnt[NB];
-            {
-                float rl[3] = {1e30f, 1e30f, 1e30f}, rh[3] = {-1e30f, -1e30f, -1e30f};
-                uint32_t rc = 0;
-                for (int b = NB - 1; b > 0; b--) {
-                    for (int k = 0; k < 3; k++) { if (blo[b][k] < rl[k]) rl[k] = blo[b][k]; if (bhi[b][k] > rh[k]) rh[k] = bhi[b][k]; }
-                    rc += cnt[b];
-                    rArea[b] = rc ? area(rl, rh) : 0.0f;
-                    rCnt[b] = rc;
-                }
-            }
-            float ll[3] = {1e30f, 1e30f, 1e30f}, lh[3] = {-1e30f, -1e30f, -1e30f};
-            uint32_t lc = 0;
-            for (int sI = 0; sI < NB - 1; sI++) {
-                for (int k = 0; k < 3; k++) { if (blo[sI][k] < ll[k]) ll[k] = blo[sI][k]; if (bhi[sI][k] > lh[k]) lh[k] = bhi[sI][k]; }
-                lc += cnt[sI];
-                if (lc == 0 || rCnt[sI + 1] == 0) continue;
-                float cost = area(ll, lh) * (float)lc + rArea[sI + 1] * (float)rCnt[sI + 1];
-                if (cost < bestCost) { bestCost = cost; bestAxis = ax; bestBin = sI; }
-            }
-        }
-        uint32_t mid;
-        if (j.level > 28) bestAxis = -1;  // a degenerate distribution must not cost unbounded depth: halve from here on
-        if (bestAxis < 0) {
-            mid = j.begin + count / 2;  // all centroids coincide: split the list in half
-        } else {
-            float ext = chi[bestAxis] - clo[bestAxis];
-            uint32_t i = j.begin, e = j.end;
-            while (i < e) {
-                uint32_t f = idx[i];
-                int b = (int)((cen[3 * f + bestAxis] - clo[bestAxis]) / ext * NB);
-                if (b >= NB) b = NB - 1;
-                if (b < 0) b = 0;
-                if (b <= bestBin) i++;
-                else { e--; uint32_t tmp = idx[i]; idx[i] = idx[e]; idx[e] = tmp; }
-            }
-            mid = i;
-            if (mid == j.begin || mid == j.end) mid = j.begin + count / 2;
-        }
-        const uint32_t child = (uint32_t)out.nodes.size() + (out.nodes.size() & 1u);  // even id: 64-byte aligned pair
-        out.nodes.resize(child + 2, RtuBvhNode{});
-        n.index = child;
-        n.count = 0;
-        out.nodes[j.id] = n;
-        queue.push_back({j.begin, mid, child, j.level + 1});
-        queue.push_back({mid, j.end, child + 1, j.level + 1});
-    }
-}
-
-// Leaf-order the elements depth-first, so that every subtree owns a contiguous range of element
-// slots (the 8-wide tree of the cooperative walk turns whole subtrees of <= 8 triangles into
-// leaves). first/total: per binary node, the subtree's slot range.
-void dfs_order(SahTree& t, std::vector<uint32_t>& first, std::vector<uint32_t>& total) {
-    std::vector<uint32_t> elems;
-    elems.reserve(t.elements.size());
-    first.assign(t.nodes.size(), 0);
-    total.assign(t.nodes.size(), 0);
-    std::vector<std::pair<uint32_t, int>> stack;  // (node, state)
-    stack.push_back({1u, 0});
-    while (!stack.empty()) {
-        auto [id, st] = stack.back();
-        RtuBvhNode& n = t.nodes[id];
-        if (n.count != 0) {
-            first[id] = (uint32_t)elems.size();
-            total[id] = n.count;
-            for (uint32_t i = 0; i < n.count; i++) elems.push_back(t.elements[n.index + i]);
-            n.index = first[id];
-            stack.pop_back();
-        } else if (st == 0) {
-            first[id] = (uint32_t)elems.size();
-            stack.back().second = 1;
-            stack.push_back({n.index, 0});
-        } else if (st == 1) {
-            stack.back().second = 2;
-            stack.push_back({n.index + 1, 0});
-        } else {
-            total[id] = total[n.index] + total[n.index + 1];
-            stack.pop_back();
-        }
-    }
-    t.elements.swap(elems);
-}
-
-// The binary SAH tree collapsed to eight children per node (for the cooperative walk, one child
-// per lane): starting from a node's two children, the inner child with the largest surface area
-// is replaced by ITS two children until eight are reached or only leaves remain. Breadth-first,
-// so that the top of the tree is the prefix staged into LDS. Same leaves, same boxes.
-void build_wide8(const SahTree& t, const std::vector<uint32_t>& first, const std::vector<uint32_t>& total, std::vector<float4>& out) {
-    struct Job { uint32_t bin, id; };
-    auto is_leaf = [&](uint32_t b) { return total[b] <= 8u; };  // a subtree of <= 8 triangles is one leaf round for eight lanes
-    out.assign(16, make_float4(0, 0, 0, 0));
-    std::vector<Job> queue;
-    queue.push_back({1u, 0u});
-    auto area = [&](uint32_t b) {
-        const RtuBvhNode& n = t.nodes[b];
-        float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
-        return dx * dy + dy * dz + dz * dx;
-    };
-    for (size_t qi = 0; qi < queue.size(); qi++) {
-        const Job j = queue[qi];
-        std::vector<uint32_t> set;
-        if (is_leaf(j.bin)) {
-            set.push_back(j.bin);  // a mesh of <= 8 triangles: the root is a leaf
-        } else {
-            set.push_back(t.nodes[j.bin].index);
-            set.push_back(t.nodes[j.bin].index + 1);
-            while (set.size() < 8) {
-                int best = -1;
-                float bestA = -1.0f;
-                for (size_t i = 0; i < set.size(); i++)
-                    if (!is_leaf(set[i]) && area(set[i]) > bestA) { bestA = area(set[i]); best = (int)i; }
-                if (best < 0) break;
-                const uint32_t b = set[(size_t)best];
-                set[(size_t)best] = t.nodes[b].index;
-                set.push_back(t.nodes[b].index + 1);
-            }
-        }
-        for (uint32_t c = 0; c < 8; c++) {
-            float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0);
-            uint32_t ref = RTU_REF8_EMPTY;
-            if (c < set.size()) {
-                const RtuBvhNode& n = t.nodes[set[c]];
-                lo = make_float4(n.bmin[0], n.bmin[1], n.bmin[2], 0);
-                hi = make_float4(n.bmax[0], n.bmax[1], n.bmax[2], 0);
-                if (is_leaf(set[c])) {
-                    ref = first[set[c]] | (total[set[c]] << 28);
-                } else {
-                    ref = (uint32_t)(out.size() / 16);
-                    out.resize(out.size() + 16, make_float4(0, 0, 0, 0));
-                    queue.push_back({set[c], ref});
-                }
-            }
-            memcpy(&lo.w, &ref, 4);
-            out[(size_t)j.id * 16 + 2 * c] = lo;
-            out[(size_t)j.id * 16 + 2 * c + 1] = hi;
-        }
-    }
-}
-
-// ... and to FOUR children per node for the one-lane-per-ray walk (half the dependent fetches of the
-// binary tree at the same instruction count). A node is 8 float4, structure of arrays so that a lane
-// picks the near / far plane arrays by the sign of its ray: {min.x[4]} {min.y[4]} {min.z[4]}
-// {max.x[4]} {max.y[4]} {max.z[4]} {ref[4]} {-}. stack_need: the deepest stack a walk can build
-// (a step pushes all hit children but the nearest).
-void build_wide4(const SahTree& t, std::vector<float4>& out, uint32_t& stack_need) {
-    struct Job { uint32_t bin, id, pushed; };
-    out.assign(8, make_float4(0, 0, 0, 0));
-    std::vector<Job> queue;
-    queue.push_back({1u, 0u, 0u});
-    stack_need = 1;
-    auto area = [&](uint32_t b) {
-        const RtuBvhNode& n = t.nodes[b];
-        float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
-        return dx * dy + dy * dz + dz * dx;
-    };
-    for (size_t qi = 0; qi < queue.size(); qi++) {
-        const Job j = queue[qi];
-        std::vector<uint32_t> set;
-        if (t.nodes[j.bin].count != 0) {
-            set.push_back(j.bin);
-        } else {
-            set.push_back(t.nodes[j.bin].index);
-            set.push_back(t.nodes[j.bin].index + 1);
-            while (set.size() < 4) {
-                int best = -1;
-                float bestA = -1.0f;
-                for (size_t i = 0; i < set.size(); i++)
-                    if (t.nodes[set[i]].count == 0 && area(set[i]) > bestA) { bestA = area(set[i]); best = (int)i; }
-                if (best < 0) break;
-                const uint32_t b = set[(size_t)best];
-                set[(size_t)best] = t.nodes[b].index;
-                set.push_back(t.nodes[b].index + 1);
-            }
-        }
-        const uint32_t pushed = j.pushed + (uint32_t)set.size() - 1u;
-        if (pushed + 1u > stack_need) stack_need = pushed + 1u;
-        float v[7][4];
-        for (uint32_t c = 0; c < 4; c++) {
-            for (int k = 0; k < 3; k++) { v[k][c] = INFINITY; v[3 + k][c] = -INFINITY; }
-            uint32_t ref = RTU_REF8_EMPTY;
-            if (c < set.size()) {
-                const RtuBvhNode& n = t.nodes[set[c]];
-                for (int k = 0; k < 3; k++) { v[k][c] = n.bmin[k]; v[3 + k][c] = n.bmax[k]; }
-                if (n.count != 0) {
-                    ref = n.index | (n.count << 28);
-                } else {
-                    ref = (uint32_t)(out.size() / 8);
-                    out.resize(out.size() + 8, make_float4(0, 0, 0, 0));
-                    queue.push_back({set[c], ref, pushed});
-                }
-            }
-            memcpy(&v[6][c], &ref, 4);
-        }
-        for (int r = 0; r < 7; r++) out[(size_t)j.id * 8 + r] = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
-    }
-}
-
-// 64-byte triangle records (TriRec, rtu_intersect.h) in the order of `elements`: the
-// ray-independent part of TriObj::IntersectTriangle (objFunctions.cpp:259-300) evaluated with
-// the same float ops.
-void build_tri_records(const RtuMesh& m, const uint32_t* elements, uint32_t n, std::vector<float4>& tri) {
-    tri.resize((size_t)n * 4);
-    for (uint32_t e = 0; e < n; e++) mu_slot_record(m.f, m.v, elements, e, &tri[4 * (size_t)e]);  // (rtu_meshrec.h: shared with the device)
 }
 
 // The node ranges of the levels of a collapsed tree (build_wide4 / build_wide8 number breadth-first: a level is a range of nodes),
@@ -574,477 +139,6 @@ void refit_host(std::vector<float4>& tree, const RtuMesh& m, const std::vector<u
             mu_leaf_slot<W>(t, i, c, m.f, m.v, elements.data(), (uint32_t)elements.size());
             mu_inner_slot<W>(t, n_nodes, i, c);
         }
-}
-
-// the reference's tree renumbered breadth-first (sibling pairs stay adjacent, the root stays node 1): same tree, same traversal
-// order. any_empty: some box has min > max (cannot come from triangles).
-void renumber_bfs(const RtuMesh& m, std::vector<RtuBvhNode>& bfs, uint32_t& any_empty) {
-    any_empty = 0;
-    for (uint32_t i = 1; i < m.n_bvh_nodes; i++) {
-        const RtuBvhNode& bn = m.bvh[i];
-        if (bn.bmin[0] > bn.bmax[0] || bn.bmin[1] > bn.bmax[1] || bn.bmin[2] > bn.bmax[2]) any_empty = 1;
-    }
-    bfs.resize(m.n_bvh_nodes);
-    memset(bfs.data(), 0, bfs.size() * sizeof(RtuBvhNode));
-    std::vector<std::pair<uint32_t, uint32_t>> queue;  // (old id, new id)
-    queue.push_back({1u, 1u});
-    uint32_t next_free = 2;
-    for (size_t qi = 0; qi < queue.size(); qi++) {
-        auto [oldId, newId] = queue[qi];
-        RtuBvhNode nn = m.bvh[oldId];
-        if (nn.count == 0) {
-            queue.push_back({nn.index, next_free});
-            queue.push_back({nn.index + 1, next_free + 1});
-            nn.index = next_free;
-            next_free += 2;
-        }
-        bfs[newId] = nn;
-    }
-}
-
-// The constants of the part of the cull margin that grows with the distance of a ray's origin, and of a sphere's slack along the
-// ray (derived at cull_margin and sphere_slack, rtu_intersect.h): per node the condition numbers along its chain, root first.
-struct WorldFar {
-    float wnoise, wreach, sph_k, sph_r;
-    float near_m0, near_c1;           // the margin of rays that start at hit points: c1 max(m0, pm) (rtu_intersect.h, THE NEAR MARGIN)
-    float wlist;                      // the scale the occluder lists are built with: wscale itself, or more in a wide scene
-};
-namespace {
-double abs_row_norm(const double* m) {  // || |M| ||_inf of a row-major 3 x 3 matrix
-    double r = 0;
-    for (int i = 0; i < 3; i++) r = std::max(r, std::fabs(m[3 * i]) + std::fabs(m[3 * i + 1]) + std::fabs(m[3 * i + 2]));
-    return r;
-}
-void mul33(const double* a, const double* b, double* out) {
-    double t[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) t[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-    memcpy(out, t, sizeof t);
-}
-}  // namespace
-// The margin of the rays that start at hit points, delta = c1 max(m0, pm), and the scale the occluder lists are built with
-// (rtu_intersect.h, THE NEAR MARGIN, has the argument): 1e-4 max(wscale, pm) and wscale themselves, bit for bit, unless the far
-// term at the scene's own extent exceeds twelve near margins. omega1: 1 + the largest |coordinate| of the origin of any node's space.
-void near_margin(float wscale, float wnoise, double omega1, WorldFar& out) {
-    out.near_m0 = wscale; out.near_c1 = 1e-4f; out.wlist = wscale;
-    const double ws = wscale, P = 2.0 * ws, wn = wnoise;
-    const auto f = [&](double m) { return 1e-4 * std::max(ws, m) + wn * (m + omega1) * (m + ws); };
-    const double DP = wn * (P + omega1) * (P + ws);
-    if (!(DP >= 12.0 * 1e-4 * ws)) return;  // (a scale or a chain that is not finite: no node has a bound, world_bounds)
-    const double c1 = f(P) / P * (1 + 1e-6);
-    // f is convex and c1 m passes above f(P): c1 m >= f(m) exactly on an interval [m*, P]
-    double lo = 0, hi = P;
-    for (int i = 0; i < 64; i++) {
-        const double mid = 0.5 * (lo + hi);
-        if (c1 * mid >= f(mid)) hi = mid; else lo = mid;
-    }
-    const double m0 = hi * (1 + 1e-6), wl = (ws + 1e4 * DP) * (1 + 1e-6);
-    out.near_m0 = m0 < 1e30 ? (float)m0 : 1e30f;
-    out.near_c1 = c1 < 1e30 ? (float)c1 : 1e30f;
-    out.wlist = wl < 1e30 ? (float)wl : 1e30f;
-}
-void world_far(const RtuSceneDesc* s, double wscale, WorldFar& out) {
-    const double u = 0x1p-24;
-    double K = 0, omega = 0, sph_cond = 0, sph_T = 0;
-    for (uint32_t i = 0; i < s->n_nodes; i++) {
-        const int type = s->nodes[i].obj_type;
-        if (type != RTU_OBJ_SPHERE && type != RTU_OBJ_PLANE && type != RTU_OBJ_TRIMESH) continue;
-        std::vector<int> chain;
-        for (int j = (int)i; j >= 0; j = s->nodes[j].parent) chain.push_back(j);
-        // root first: T = tm_0 ... tm_(j-1) takes space j to the world, Ti is its inverse, o the world position of the origin of space j
-        double T[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Ti[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-        double k_node = 0, om = 0;
-        for (size_t c = chain.size(); c-- > 0;) {
-            const RtuNode& a = s->nodes[chain[c]];
-            double tm[9], itm[9], prod[9];
-            for (int r = 0; r < 3; r++)
-                for (int q = 0; q < 3; q++) { tm[3 * r + q] = a.tm[3 * q + r]; itm[3 * r + q] = a.itm[3 * q + r]; }  // (RtuNode: column-major)
-            for (int r = 0; r < 3; r++)
-                for (int q = 0; q < 3; q++)
-                    prod[3 * r + q] = std::fabs(tm[3 * r]) * std::fabs(itm[q]) + std::fabs(tm[3 * r + 1]) * std::fabs(itm[3 + q]) + std::fabs(tm[3 * r + 2]) * std::fabs(itm[6 + q]);
-            k_node += abs_row_norm(T) * abs_row_norm(Ti) * (3.0 + 6.0 * abs_row_norm(prod));
-            for (int r = 0; r < 3; r++) o[r] += T[3 * r] * a.pos[0] + T[3 * r + 1] * a.pos[1] + T[3 * r + 2] * a.pos[2];
-            om = std::max(om, std::max(std::fabs(o[0]), std::max(std::fabs(o[1]), std::fabs(o[2]))));
-            mul33(T, tm, T);
-            mul33(itm, Ti, Ti);
-        }
-        const double cond = abs_row_norm(T) * abs_row_norm(Ti);
-        if (!std::isfinite(k_node) || !std::isfinite(om) || !std::isfinite(cond)) continue;  // such a node has no bound at all (world_bounds)
-        K = std::max(K, k_node);
-        omega = std::max(omega, om);
-        if (type == RTU_OBJ_SPHERE) { sph_cond = std::max(sph_cond, cond); sph_T = std::max(sph_T, abs_row_norm(T)); }
-    }
-    out.wnoise = (float)(1.74 * u * K * (1 + 1e-6));
-    out.wreach = (float)(std::max(wscale, omega + 1.0) * (1 + 1e-6));
-    out.sph_k = (float)(5.2e-3 * sph_cond * (1 + 1e-6));
-    out.sph_r = (float)(1.74 * sph_T * (1 + 1e-6));
-    near_margin((float)wscale, out.wnoise, omega + 1.0, out);
-}
-// NODE-LEVEL BOUNDS (DevNode::wmin / wmax; the argument is in rtu_intersect.h, trace): the object's own bounding box —
-// the unit cube of a sphere, the unit square of a plane (objects.h:25,37), the mesh's box — taken corner by corner through
-// the node's chain of transformations (p -> tm p + pos, scene.h:508-512) in binary64, then widened by
-//   * 1e-5 of the largest coordinate (the chain itself is binary32 on the device and in the reference), and
-//   * for a sphere, what the cancellation in b*b - 4ac can move a grazing root (objFunctions.cpp:25-27): the discriminant
-//     carries an error of ~4 ulp of b*b, i.e. the ray may "touch" a sphere it passes at up to ~2.4e-7 * (D/R)^2 radii, and a
-//     grazing root is off by up to ~5e-4 * D in t; with D bounded by the scene's diameter S both stay below
-//     4e-6 * S^2 / R + 1e-3 * S ... the latter only matters when R < 1e-3 * S, where the former is already larger. R is the
-//     smallest half-extent of the sphere's world box.
-//     (That D is the distance inside the scene. A ray from further away is covered per ray: rtu_intersect.h, cull_margin and
-//     sphere_slack.)
-// Returns the largest |coordinate| of all bounds (the scale of the per-ray margin).
-float world_bounds(const RtuSceneDesc* s, std::vector<DevNode>& nodes) {
-    const uint32_t n = s->n_nodes;
-    std::vector<std::array<double, 6>> box(n);
-    std::vector<bool> has(n, false);
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (uint32_t i = 0; i < n; i++) {
-        const RtuNode& nd = s->nodes[i];
-        double l[3], h[3];
-        if (nd.obj_type == RTU_OBJ_SPHERE) { l[0] = l[1] = l[2] = -1; h[0] = h[1] = h[2] = 1; }
-        else if (nd.obj_type == RTU_OBJ_PLANE) { l[0] = l[1] = -1; h[0] = h[1] = 1; l[2] = h[2] = 0; }
-        else if (nd.obj_type == RTU_OBJ_TRIMESH) {
-            const RtuMesh& m = s->meshes[nd.mesh_id];
-            for (int k = 0; k < 3; k++) { l[k] = m.bound_min[k]; h[k] = m.bound_max[k]; }
-        } else continue;
-        double wl[3] = {1e300, 1e300, 1e300}, wh[3] = {-1e300, -1e300, -1e300};
-        for (int c = 0; c < 8; c++) {
-            double p[3] = {(c & 1) ? h[0] : l[0], (c & 2) ? h[1] : l[1], (c & 4) ? h[2] : l[2]};
-            for (int j = (int)i; j >= 0; j = s->nodes[j].parent) {
-                const RtuNode& a = s->nodes[j];
-                const double q[3] = {p[0] * a.tm[0] + p[1] * a.tm[3] + p[2] * a.tm[6] + a.pos[0],
-                                     p[0] * a.tm[1] + p[1] * a.tm[4] + p[2] * a.tm[7] + a.pos[1],
-                                     p[0] * a.tm[2] + p[1] * a.tm[5] + p[2] * a.tm[8] + a.pos[2]};
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-            for (int k = 0; k < 3; k++) { wl[k] = std::min(wl[k], p[k]); wh[k] = std::max(wh[k], p[k]); }
-        }
-        for (int k = 0; k < 3; k++) { box[i][k] = wl[k]; box[i][3 + k] = wh[k]; lo[k] = std::min(lo[k], wl[k]); hi[k] = std::max(hi[k], wh[k]); }
-        has[i] = true;
-    }
-    double S = 0;
-    for (int k = 0; k < 3; k++) if (hi[k] >= lo[k]) S += (hi[k] - lo[k]) * (hi[k] - lo[k]);
-    S = std::sqrt(S);
-    double scale = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        DevNode& d = nodes[i];
-        for (int k = 0; k < 3; k++) { d.wmin[k] = -INFINITY; d.wmax[k] = INFINITY; }
-        if (!has[i]) continue;
-        double m = 0;
-        for (int k = 0; k < 6; k++) m = std::max(m, std::fabs(box[i][k]));
-        double widen = 1e-5 * m;
-        if (s->nodes[i].obj_type == RTU_OBJ_SPHERE) {
-            double R = 1e300;
-            for (int k = 0; k < 3; k++) R = std::min(R, 0.5 * (box[i][3 + k] - box[i][k]));
-            widen += R > 0 ? 4e-6 * S * S / R : INFINITY;
-            if (R < 1e-3 * S) widen += 1e-3 * S;
-        }
-        bool finite = std::isfinite(widen);
-        for (int k = 0; k < 3 && finite; k++) finite = std::isfinite(box[i][k]) && std::isfinite(box[i][3 + k]);
-        if (!finite) continue;  // NaN / infinite transformation: no bound (everything passes an infinite box)
-        for (int k = 0; k < 3; k++) {
-            d.wmin[k] = std::nextafter((float)(box[i][k] - widen), -INFINITY);
-            d.wmax[k] = std::nextafter((float)(box[i][3 + k] + widen), INFINITY);
-            scale = std::max(scale, std::max(std::fabs((double)d.wmin[k]), std::fabs((double)d.wmax[k])));
-        }
-    }
-    return (float)scale;
-}
-
-// the box of the ray-sort keys (rtu_ray_sort_box): the union of the finite node-level bounds world_bounds left, else [-wscale, wscale]^3
-void sort_box_of(const std::vector<DevNode>& nodes, float wscale, float out[6]) {
-    for (int k = 0; k < 3; k++) { out[k] = INFINITY; out[3 + k] = -INFINITY; }
-    bool any_bound = false;
-    for (const DevNode& d : nodes) {
-        bool finite = true;
-        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(d.wmin[k]) && std::isfinite(d.wmax[k]);
-        if (!finite) continue;
-        any_bound = true;
-        for (int k = 0; k < 3; k++) {
-            out[k] = std::min(out[k], d.wmin[k]);
-            out[3 + k] = std::max(out[3 + k], d.wmax[k]);
-        }
-    }
-    if (!any_bound)
-        for (int k = 0; k < 3; k++) { out[k] = -wscale; out[3 + k] = wscale; }
-}
-
-// OCCLUDER LISTS OF SHADOW RAYS (DevLightMask): for each of the first RTU_LMASK_LIGHTS non-ambient lights and each masked mesh
-// node, the mesh as the light sees it — through a pinhole at a point light, looking at the centre of the mesh; along the
-// direction of a direct light — on a G x G grid, and per cell the triangles that a shadow ray whose ORIGIN projects into the
-// cell can possibly touch. A triangle is entered into every cell that its projection, grown by a slack S, overlaps (exact
-// triangle / square overlap: the separating-axis test on the square's sides and the triangle's edges), where S covers
-//   * the cull margin: the ray's line, its rounded direction and the binary32 transformation chain stay within
-//     wid = 1e-4 * scene scale + 1e-5 * |coordinates| of the ideal segment origin -> light (shadow rays start on the scene's
-//     surfaces: |origin| <= the scene's scale); a displacement of wid on every axis moves a projection by at most
-//     wid * sqrt(3) * (1 + |u|) / (depth - wid * sqrt(3)) (pinhole; wid * sqrt(3) orthographic);
-//   * the device's binary32 evaluation of the cell coordinates (err: a few 1e-6 of the operands, bounded below per list;
-//     a list whose bound exceeds a quarter of a cell is not used);
-//   * a quarter of a cell on top.
-// A list is unusable when some corner of a triangle's widened box is not in front of the pinhole (the light is inside or too
-// close to the mesh's hull) or the mesh has no extent from there. G grows with the triangle count (a triangle spans a few
-// cells) up to RTU_LGRID_MAX and is halved while the lists would hold more than 32 M entries.
-struct CoverMesh {
-    std::vector<float4> boxes;      // per face: world-space box {lo} {hi}, rounded outwards
-    std::vector<double> verts;      // per face: 3 world-space vertices (9 doubles)
-    std::vector<uint32_t> slot_of;  // face -> slot in the leaf order of the mesh's fast tree
-};
-// One list: pure host arithmetic (no GPU) — the frame, the grid and the cells' entries {slot, zmin bits} of light `l` looking at the mesh
-// `cm`. false: no usable list from there. (rtu_debug_light_list hands the result to the CPU tests, which check it ray by ray.)
-struct HostLightList {
-    DevLightMask m;                 // frame, offsets, scale, G, point (the device pointers stay null here)
-    std::vector<uint32_t> off, ent;
-};
-}  // namespace
-
-// ---- the scalar decisions of rtu_lightlist.h ----
-bool ll_frame(const RtuLight& l, const double lo[3], const double hi[3], LlFrame& F) {
-    memset(&F, 0, sizeof F);
-    const bool point = l.type == RTU_LIGHT_POINT;
-    F.point = point ? 1 : 0;
-    double* L = F.L;
-    double* Z = F.Z;
-    double* X = F.X;
-    double* Y = F.Y;
-    if (point) {
-        for (int k = 0; k < 3; k++) { L[k] = l.vec[k]; Z[k] = 0.5 * (lo[k] + hi[k]) - L[k]; }
-    } else {
-        for (int k = 0; k < 3; k++) Z[k] = l.vec[k];
-    }
-    const double zl = std::sqrt(Z[0] * Z[0] + Z[1] * Z[1] + Z[2] * Z[2]);
-    if (!(zl > 0) || !std::isfinite(zl)) return false;
-    for (int k = 0; k < 3; k++) Z[k] /= zl;
-    int ax = std::fabs(Z[0]) <= std::fabs(Z[1]) ? (std::fabs(Z[0]) <= std::fabs(Z[2]) ? 0 : 2) : (std::fabs(Z[1]) <= std::fabs(Z[2]) ? 1 : 2);
-    double A[3] = {0, 0, 0};
-    A[ax] = 1;
-    X[0] = Z[1] * A[2] - Z[2] * A[1]; X[1] = Z[2] * A[0] - Z[0] * A[2]; X[2] = Z[0] * A[1] - Z[1] * A[0];
-    const double xl = std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
-    for (int k = 0; k < 3; k++) X[k] /= xl;
-    Y[0] = Z[1] * X[2] - Z[2] * X[1]; Y[1] = Z[2] * X[0] - Z[0] * X[2]; Y[2] = Z[0] * X[1] - Z[1] * X[0];
-    return true;
-}
-
-uint32_t ll_first_grid(size_t nf) {
-    // grid size: a triangle of an evenly tessellated surface spans ~ G / sqrt(nf / 2) cells; aim at six of them
-    uint32_t G = 64;
-    static const double kSpan = [] { const char* e = getenv("RTU_LGRID_SPAN"); return e ? atof(e) : 6.0; }();  // tuning knob (any value renders the same image)
-    while (G < RTU_LGRID_MAX && (double)G < kSpan * std::sqrt((double)nf * 0.5)) G *= 2;
-    return G;
-}
-
-bool ll_extent_ok(double U0, double U1, double V0, double V1, double& mag) {
-    if (!(U1 > U0) || !(V1 > V0)) return false;
-    mag = std::max(std::max(std::fabs(U0), std::fabs(U1)), std::max(std::fabs(V0), std::fabs(V1)));
-    return !(!std::isfinite(mag) || (U1 - U0) < 1e-4 * mag || (V1 - V0) < 1e-4 * mag);
-}
-
-bool ll_grid_at(uint32_t G, double U0, double U1, double V0, double V1, double ratio, double mag, LlGrid& g) {
-    memset(&g, 0, sizeof g);
-    g.G = G;
-    // the grid spans the extent plus two cells on every side
-    g.du = (U1 - U0) / ((double)G - 4); g.dv = (V1 - V0) / ((double)G - 4);
-    g.gu0 = U0 - 2 * g.du; g.gv0 = V0 - 2 * g.dv;
-    // the device's binary32 cell coordinate: (dot(p - L, X) [/ depth] - u0) * su — every operand good to a few ulp
-    const double coord = 16e-7 * ratio * (1.0 + mag);
-    const double err_cells = std::max(coord / g.du, coord / g.dv) + 4e-7 * (double)G;
-    if (!(err_cells < 0.25)) return false;
-    g.S0 = 0.25 + err_cells;
-    return true;
-}
-
-void ll_mask(const LlFrame& F, const LlGrid& g, DevLightMask& m) {
-    for (int k = 0; k < 3; k++) { m.X[k] = (float)F.X[k]; m.Y[k] = (float)F.Y[k]; m.Z[k] = (float)F.Z[k]; m.L[k] = (float)F.L[k]; }
-    m.u0 = (float)g.gu0; m.v0 = (float)g.gv0; m.su = (float)(1.0 / g.du); m.sv = (float)(1.0 / g.dv);
-    m.point = F.point ? 1u : 0u;
-    m.G = g.G;
-}
-
-namespace {
-
-bool compute_light_list(const RtuLight& l, const CoverMesh& cm, float wscale, HostLightList& out) {
-    DevLightMask& m = out.m;
-    memset(&m, 0, sizeof m);
-    std::vector<uint32_t>& off = out.off;
-    std::vector<uint32_t>& ent = out.ent;
-    const std::vector<float4>& boxes = cm.boxes;
-    const size_t nf = boxes.size() / 2;
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (size_t f = 0; f < nf; f++) {
-        const float4 a = boxes[2 * f], b = boxes[2 * f + 1];
-        const double al[3] = {a.x, a.y, a.z}, bh[3] = {b.x, b.y, b.z};
-        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], al[k]); hi[k] = std::max(hi[k], bh[k]); }
-    }
-    LlFrame F;
-    if (!ll_frame(l, lo, hi, F)) return false;  // unusable
-    // per triangle: the rectangle of its widened box in the light's (u, v) — the extent of the grid, and the check that
-    // everything the list stands for lies in front of the pinhole
-    double U0 = 1e300, U1 = -1e300, V0 = 1e300, V1 = -1e300, ratio = 1.0;
-    std::vector<double> wid_of(nf);
-    for (size_t f = 0; f < nf; f++) {
-        wid_of[f] = ll_face_wid(boxes[2 * f], boxes[2 * f + 1], wscale);
-        if (!ll_face_corners(boxes[2 * f], boxes[2 * f + 1], wid_of[f], F, U0, U1, V0, V1, ratio)) return false;
-    }
-    double mag;
-    if (!ll_extent_ok(U0, U1, V0, V1, mag)) return false;
-    LlGrid g;
-    for (uint32_t G = ll_first_grid(nf);; G /= 2) {
-        if (G < 16u) return false;
-        if (!ll_grid_at(G, U0, U1, V0, V1, ratio, mag, g)) continue;  // (a coarser grid has larger cells)
-        off.assign((size_t)G * G + 1, 0u);
-        size_t total = 0;
-        bool too_many = false;
-        for (int pass = 0; pass < 2 && !too_many; pass++) {
-            if (pass == 1) {
-                uint32_t run = 0;
-                for (size_t i = 0; i < (size_t)G * G; i++) { const uint32_t n = off[i]; off[i] = run; run += n; }
-                off[(size_t)G * G] = run;
-                ent.assign(2 * total, 0u);
-            }
-            for (size_t f = 0; f < nf; f++) {
-                LlFaceCells c;
-                ll_face_cells(cm.verts.data() + 9 * f, wid_of[f], F, g, wscale, c);
-                const uint32_t slot = cm.slot_of[f];
-                for (int y = c.y0; y <= c.y1; y++)
-                    for (int x = c.x0; x <= c.x1; x++) {
-                        if (!ll_cell_in(c, x, y)) continue;
-                        const size_t cell = (size_t)y * G + (size_t)x;
-                        if (pass == 0) { off[cell]++; total++; }
-                        else { const uint32_t at = off[cell]++; ent[2 * (size_t)at] = slot; ent[2 * (size_t)at + 1] = c.zbits; }
-                    }
-                if (pass == 0 && total > RTU_LLIST_MAX_ENTRIES) { too_many = true; break; }
-            }
-        }
-        if (too_many) continue;
-        // pass 1 advanced every offset to the end of its cell: shift back
-        for (size_t i = (size_t)G * G; i > 0; i--) off[i] = off[i - 1];
-        off[0] = 0;
-        {   // nearest to the light first: a walk of the list ends at the first entry that lies beyond the ray's origin
-            std::vector<std::pair<float, uint32_t>> tmp;
-            for (size_t cell = 0; cell < (size_t)G * G; cell++) {
-                const uint32_t b = off[cell], e = off[cell + 1];
-                if (e - b < 2u) continue;
-                tmp.clear();
-                for (uint32_t i = b; i < e; i++) { float z; memcpy(&z, &ent[2 * (size_t)i + 1], 4); tmp.push_back({z, ent[2 * (size_t)i]}); }
-                std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<float, uint32_t>& a, const std::pair<float, uint32_t>& b2) { return a.first < b2.first; });
-                for (uint32_t i = b; i < e; i++) { memcpy(&ent[2 * (size_t)i + 1], &tmp[i - b].first, 4); ent[2 * (size_t)i] = tmp[i - b].second; }
-            }
-        }
-        ll_mask(F, g, m);
-        break;
-    }
-    m.usable = 1u;
-    return true;
-}
-
-// The triangles of mesh node `node` in world space: every vertex through the chain p -> tm p + pos in binary64; per face its three
-// vertices and their box rounded outwards. fast_elements: slot of the mesh's fast tree -> face.
-LlChain node_chain(const RtuSceneDesc* s, uint32_t node) {
-    LlChain c;
-    memset(&c, 0, sizeof c);
-    for (int j = (int)node; j >= 0 && c.n < RTU_MAX_NODE_DEPTH; j = s->nodes[j].parent, c.n++) {
-        memcpy(c.tm[c.n], s->nodes[j].tm, sizeof c.tm[0]);
-        memcpy(c.pos[c.n], s->nodes[j].pos, sizeof c.pos[0]);
-    }
-    return c;
-}
-
-void make_cover_mesh(const RtuSceneDesc* s, uint32_t node, const std::vector<uint32_t>& fast_elements, CoverMesh& cm) {
-    const RtuMesh& m = s->meshes[s->nodes[node].mesh_id];
-    const LlChain chain = node_chain(s, node);
-    cm.boxes.assign((size_t)m.nf * 2, make_float4(0, 0, 0, 0));
-    cm.verts.assign((size_t)m.nf * 9, 0.0);
-    for (uint32_t f = 0; f < m.nf; f++) {
-        const uint32_t* fv = m.f + 3 * (size_t)f;
-        ll_cover_face(chain, m.v + 3 * (size_t)fv[0], m.v + 3 * (size_t)fv[1], m.v + 3 * (size_t)fv[2], cm.verts.data() + 9 * (size_t)f,
-                      cm.boxes[2 * (size_t)f], cm.boxes[2 * (size_t)f + 1]);
-    }
-    cm.slot_of.assign(m.nf, 0u);
-    for (uint32_t sl = 0; sl < (uint32_t)fast_elements.size(); sl++) cm.slot_of[fast_elements[sl]] = sl;
-}
-
-int build_light_lists(RtuContext* ctx, const RtuSceneDesc* s, const std::vector<CoverMesh>& cover, float wscale, DevScene& ds) {
-    ds.lmask = nullptr;
-    std::vector<uint32_t> lights;
-    for (uint32_t i = 0; i < s->n_lights && lights.size() < RTU_LMASK_LIGHTS; i++)
-        if (s->lights[i].type != RTU_LIGHT_AMBIENT) lights.push_back(i);
-    const uint32_t nc = (uint32_t)cover.size();
-    if (lights.empty() || nc == 0) return RTU_OK;
-    std::vector<DevLightMask> masks(lights.size() * nc);
-    memset(masks.data(), 0, masks.size() * sizeof(DevLightMask));
-    for (size_t j = 0; j < lights.size(); j++)
-        for (uint32_t c = 0; c < nc; c++) {
-            HostLightList hl;
-            if (!compute_light_list(s->lights[lights[j]], cover[c], wscale, hl)) continue;
-            DevLightMask& m = masks[j * nc + c];
-            m = hl.m;
-            m.usable = 0u;
-            int rc;
-            const int slot = P_LIST + 2 * (int)(j * nc + c);
-            if ((rc = place_upload(ctx, slot, hl.off.data(), hl.off.size(), &m.cell_off)) != RTU_OK) return rc;
-            if ((rc = place_upload(ctx, slot + 1, hl.ent.data(), hl.ent.size(), &m.cell_tri)) != RTU_OK) return rc;
-            m.usable = 1u;
-            uint32_t longest = 0;
-            for (size_t i = 0; i < (size_t)m.G * m.G; i++) longest = std::max(longest, hl.off[i + 1] - hl.off[i]);
-            ctx->light_list_info.push_back({(uint32_t)j, c, m.G, (uint32_t)(hl.ent.size() / 2), longest});
-        }
-    ctx->lmask_host = masks;
-    return place_upload(ctx, P_LMASK, masks.data(), masks.size(), &ds.lmask);
-}
-
-// The same lists built on the GPU (rtu_scene_update.hip) from the cover meshes already there: `covers` per masked mesh node,
-// `lohi` the box extents of each. Same decisions, same order, same lists.
-int build_light_lists_device(RtuContext* ctx, const RtuSceneDesc* s, const std::vector<LlCover>& covers, const std::vector<double>& lohi, float wscale,
-                             DevScene& ds) {
-    ds.lmask = nullptr;
-    ctx->lmask_host.clear();
-    std::vector<uint32_t> lights;
-    for (uint32_t i = 0; i < s->n_lights && lights.size() < RTU_LMASK_LIGHTS; i++)
-        if (s->lights[i].type != RTU_LIGHT_AMBIENT) lights.push_back(i);
-    const uint32_t nc = (uint32_t)covers.size();
-    if (lights.empty() || nc == 0) return RTU_OK;
-    std::vector<DevLightMask> masks(lights.size() * nc);
-    memset(masks.data(), 0, masks.size() * sizeof(DevLightMask));
-    std::vector<LlFrame> frames;
-    std::vector<int> pair_cover, pair_of;  // pairs with a frame: their cover node and their index j * nc + c
-    for (size_t j = 0; j < lights.size(); j++)
-        for (uint32_t c = 0; c < nc; c++) {
-            LlFrame F;
-            if (!ll_frame(s->lights[lights[j]], &lohi[6 * c], &lohi[6 * c + 3], F)) continue;
-            frames.push_back(F);
-            pair_cover.push_back((int)c);
-            pair_of.push_back((int)(j * nc + c));
-        }
-    std::vector<double> ext(6 * frames.size() + 6);
-    RTU_HIP(ctx, ll_build_extents(ctx->llb, ctx->stream, covers.data(), pair_cover.data(), frames.data(), (int)frames.size(), wscale, ext.data()));
-    for (size_t p = 0; p < frames.size(); p++) {
-        const double* e = &ext[6 * p];
-        double mag;
-        if (e[5] == 0.0 || !ll_extent_ok(e[0], e[1], e[2], e[3], mag)) continue;
-        const int c = pair_cover[p];
-        const LlCover& cv = covers[(size_t)c];
-        LlGrid g;
-        for (uint32_t G = ll_first_grid(cv.nf); G >= 16u; G /= 2) {
-            if (!ll_grid_at(G, e[0], e[1], e[2], e[3], e[4], mag, g)) continue;
-            size_t entries = 0;
-            RTU_HIP(ctx, ll_count(ctx->llb, ctx->stream, cv, c, frames[p], g, wscale, &entries));
-            if (entries > RTU_LLIST_MAX_ENTRIES) continue;
-            DevLightMask& m = masks[(size_t)pair_of[p]];
-            ll_mask(frames[p], g, m);
-            const int slot = P_LIST + 2 * pair_of[p];
-            void *off = nullptr, *ent = nullptr;
-            int rc;
-            if ((rc = ensure_place(ctx, slot, sizeof(uint32_t) * ((size_t)G * G + 1), &off)) != RTU_OK) return rc;
-            if ((rc = ensure_place(ctx, slot + 1, sizeof(uint32_t) * 2 * entries, &ent)) != RTU_OK) return rc;
-            uint32_t longest = 0;
-            RTU_HIP(ctx, ll_fill(ctx->llb, ctx->stream, cv, g, (uint32_t*)off, (uint32_t*)ent, &longest));
-            m.cell_off = (const uint32_t*)off;
-            m.cell_tri = (const uint32_t*)ent;
-            m.usable = 1u;
-            ctx->light_list_info.push_back({(uint32_t)(pair_of[p] / (int)nc), (uint32_t)c, G, (uint32_t)entries, longest});
-            break;
-        }
-    }
-    ctx->lmask_host = masks;
-    return place_upload(ctx, P_LMASK, masks.data(), masks.size(), &ds.lmask);
 }
 
 // The checks of a mesh's `ref` tree and element list (validate, and rtu_update_meshes for the trees it takes): element ids, and every
@@ -2085,7 +1179,6 @@ int place_scene(RtuContext* ctx, const RtuSceneDesc* s, bool on_device) {
         }
     }
 
-
     const float wscale = world_bounds(s, nodes);
     float sort_box[6];
     sort_box_of(nodes, wscale, sort_box);
@@ -2282,7 +1375,6 @@ RtuSceneDesc shape_desc(const RtuContext* ctx) {
     d.material_maps = ctx->shape_maps ? &present : nullptr;
     return d;
 }
-
 
 // The writing half of rtu_update_meshes, after every check has passed: for each listed mesh the new vertices, normals and `ref` tree
 // go to HBM, and the kernels of rtu_mesh_update.hip rewrite what depends on the vertices — triangle records of both trees, the boxes
@@ -2618,14 +1710,20 @@ int rtu_debug_mesh_update_timing(RtuContext* ctx, int on, float* ms_out4) {
     return RTU_OK;
 }
 
+}  // extern "C"
+
 namespace {
+
 // one array of a mesh dump to the caller: *bytes_out is always set; RTU_ERR_ARG when `out` is too small for it
 int dump_out(RtuContext* ctx, size_t bytes, void* out, size_t capacity, size_t* bytes_out) {
     if (bytes_out) *bytes_out = bytes;
     if (bytes > capacity || (bytes && !out)) return fail(ctx, RTU_ERR_ARG, "the array has %zu bytes, the buffer %zu", bytes, capacity);
     return RTU_OK;
 }
+
 }  // namespace
+
+extern "C" {
 
 int rtu_debug_context_mesh(RtuContext* ctx, uint32_t mesh, int which, void* out, size_t capacity_bytes, size_t* bytes_out) {
     if (!ctx) return RTU_ERR_ARG;
@@ -2749,8 +1847,12 @@ int rtu_scene_shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b, char* err
     return rc;
 }
 
+}  // extern "C"
+
 // The per-node maps of rtu_render.h "Temporal accumulation across scene updates", composed in binary64. Affine maps as {A row-major, b}.
+
 namespace {
+
 struct Affine64 { double A[9], b[3]; };
 
 Affine64 affine_identity() { return Affine64{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}}; }
@@ -2800,7 +1902,10 @@ bool node_chain(const RtuSceneDesc* s, uint32_t i, Affine64& W, Affine64& Winv) 
     for (int l = n - 1; l >= 0; l--) Winv = affine_to_level(Winv, s->nodes[chain[l]].itm, s->nodes[chain[l]].pos);   // the root first
     return true;
 }
+
 }  // namespace
+
+extern "C" {
 
 static int scene_motion(const RtuSceneDesc* prev, const RtuSceneDesc* cur, const uint32_t* deform_mesh_ids, int n_deform, const uint32_t* reset_mesh_ids,
                         int n_reset, RtuNodeMotion* out);
@@ -3664,8 +2769,12 @@ int rtu_debug_texcoords(RtuContext* ctx, int op, int index, const float* h_in, u
     return RTU_OK;
 }
 
+}  // extern "C"
+
 // ---- ray queries (rtu_query.hip) ----------------------------------------------------------------------------------------------
+
 namespace {
+
 const size_t kQueryChunk = (size_t)1 << 20;  // rays per launch of the host forms: 32 MB of rays, 48 MB of hits
 
 int query_args(RtuContext* ctx, const void* rays, const void* out, size_t n, uint32_t flags, bool device) {
@@ -3708,9 +2817,12 @@ int query_host(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t flags, 
     }
     return RTU_OK;
 }
-}  // namespace
 
 static_assert(sizeof(RtuRay) == 32 && sizeof(RtuRayHit) == 48, "ray query records are two / three float4");
+
+}  // namespace
+
+extern "C" {
 
 int rtu_trace_rays_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* hip_stream) {
     if (!ctx) return RTU_ERR_ARG;
@@ -3749,8 +2861,12 @@ int rtu_occluded_rays(RtuContext* ctx, const RtuRay* h_rays, size_t n, uint32_t 
     return query_host(ctx, h_rays, n, flags, nullptr, h_occluded);
 }
 
+}  // extern "C"
+
 // ---- first-hit features (rtu_features.hip) and the denoising filter (rtu_denoise.hip) -----------------------------------------------
+
 namespace {
+
 static int feature_cam(RtuContext* ctx, const RtuFrameDesc* f, FeatureCam& cam) {
     if (!f) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
     if (f->width <= 0 || f->height <= 0 || f->width > 65536 || f->height > 65536) return fail(ctx, RTU_ERR_ARG, "bad resolution");
@@ -3798,7 +2914,10 @@ static int features_host(RtuContext* ctx, const RtuRay* h_rays, const FeatureCam
     }
     return RTU_OK;
 }
+
 }  // namespace
+
+extern "C" {
 
 int rtu_ray_features_device(RtuContext* ctx, const void* d_rays, size_t n, uint32_t flags, void* d_hits, void* d_albedo, void* hip_stream) {
     if (!ctx) return RTU_ERR_ARG;
@@ -3959,8 +3078,12 @@ int rtu_progressive_snapshot_denoised(RtuProgressive* p, const RtuDenoiseDesc* d
     return RTU_OK;
 }
 
+}  // extern "C"
+
 // ---- ray batches: Shade() along caller-supplied rays (render_rays_impl.h) -------------------------------------------------------
+
 namespace {
+
 // chains per launch sequence of recipe P: what sampled_batch allows a frame's batch of samples by default (2^25 pixels; its tuning
 // knob RTU_GI_BATCH_LOG2 moves the frame path's figure, not this one), and so a path-traced ray batch's _device form
 const size_t kPathChains = (size_t)1 << 25;
@@ -4122,9 +3245,12 @@ CamSample cam_sample(const RtuFrameDesc* frame, int sample) {
     c.sample = (uint32_t)sample;
     return c;
 }
-}  // namespace
 
 static_assert(sizeof(RtuShadeDesc) == 32, "RtuShadeDesc is 32 bytes");
+
+}  // namespace
+
+extern "C" {
 
 int rtu_shade_defaults(RtuShadeDesc* out) {
     if (!out) return RTU_ERR_ARG;
@@ -4188,8 +3314,12 @@ int rtu_shade_rays_paths(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* 
     return shade_host(ctx, f, h_rays, h_keys, n, h_rgbt, stats, true);
 }
 
+}  // extern "C"
+
 // ---- the two halves of a recipe-P sample (render_gather_impl.h; render_rays6.hip / render_rays7.hip) ----
+
 namespace {
+
 enum { HALF_GATHER = 1, HALF_AMBIENT = 2 };
 
 DevScene half_scene(const RtuContext* ctx) {
@@ -4301,7 +3431,10 @@ int half_host(RtuContext* ctx, const RtuRay* h_rays, const uint32_t* h_keys, con
     }
     return RTU_OK;
 }
+
 }  // namespace
+
+extern "C" {
 
 int rtu_gather_rays_device(RtuContext* ctx, const void* d_rays, const void* d_keys, size_t n, const RtuShadeDesc* desc, void* d_ct, void* hip_stream) {
     return half_device(ctx, d_rays, d_keys, nullptr, n, desc, d_ct, hip_stream, HALF_GATHER);
@@ -4318,8 +3451,12 @@ int rtu_shade_rays_ambient(RtuContext* ctx, const RtuRay* h_rays, const uint32_t
     return half_host(ctx, h_rays, h_keys, h_amb, n, desc, h_rgbt, stats, HALF_AMBIENT);
 }
 
+}  // extern "C"
+
 // ---- the irradiance map (rtu_irradiance.h, rtu_irradiance.hip) ----
+
 namespace {
+
 const size_t kIrrChunkChains = (size_t)1 << 22;  // chains per chunk of a pass's list: 1.4 GB of chain records and results
 
 int irr_check_frame(RtuContext* ctx, const RtuFrameDesc* frame) {
@@ -4344,7 +3481,10 @@ int irr_check_map(RtuContext* ctx, const RtuIrradianceMap* map, bool device, Irr
     if (device && ((uintptr_t)map->records & 15u)) return fail(ctx, RTU_ERR_ARG, "device records must be 16-byte aligned");
     return RTU_OK;
 }
+
 }  // namespace
+
+extern "C" {
 
 int rtu_irradiance_sample_device(RtuContext* ctx, const RtuIrradianceMap* map, const void* d_xy, size_t n, void* d_out, void* hip_stream) {
     if (!ctx) return RTU_ERR_ARG;
@@ -5727,8 +4867,12 @@ void rtu_temporal_free(RtuTemporal* t) {
     delete t;
 }
 
+}  // extern "C"
+
 // ---- sensors (rtu_sensor.h, rtu_sensor.hip): the rays of a panoramic, fisheye or orthographic sensor, and its image --------------
+
 namespace {
+
 const size_t kSensorPixels = (size_t)1 << 25;  // pixels of a sensor, and rays of one batch of its samples, at most
 
 bool fin3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
@@ -5808,9 +4952,12 @@ int sensor_generate(RtuContext* ctx, const RtuSensorDesc* d, int k0, int n, floa
     }
     return RTU_OK;
 }
-}  // namespace
 
 static_assert(sizeof(RtuSensorDesc) == 128, "RtuSensorDesc is 128 bytes");
+
+}  // namespace
+
+extern "C" {
 
 int rtu_sensor_defaults(RtuSensorDesc* out) {
     if (!out) return RTU_ERR_ARG;
@@ -5944,8 +5091,12 @@ int rtu_render_sensor(RtuContext* ctx, const RtuSensorDesc* d, float* h_rgbz) {
     return RTU_OK;
 }
 
+}  // extern "C"
+
 // ---- adaptive sensors (rtu_sensor_adaptive.h, rtu_sensor_adaptive.hip): the sample loop of a sensor over the pixels that still sample ----
+
 namespace {
+
 // the arguments both forms share: a recipe S / P sensor with 1 .. 255 samples and a valid RtuAdaptiveDesc
 int check_sensor_adaptive(RtuContext* ctx, const RtuSensorDesc* d, const RtuAdaptiveDesc* ad) {
     const int rc = check_sensor(ctx, d);
@@ -5967,7 +5118,10 @@ int sa_behind(void* arg) {
     RTU_HIP(b.ctx, hipMemcpyAsync(b.ctx->sa_n_host.get(), b.p.n_out, sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream));
     return RTU_OK;
 }
+
 }  // namespace
+
+extern "C" {
 
 // The sample loop of an adaptive sensor: per batch the rays and keys of the live pixels (the first batch: every pixel, k_sensor_rays;
 // then k_sa_rays over the list), the launch path of the matching ray-batch entry into sn_out, and behind it — ahead of the batch's one
@@ -6265,7 +5419,10 @@ int rtu_scene_sort_box(const RtuSceneDesc* s, float box_out[6]) {
     return RTU_OK;
 }
 
+}  // extern "C"
+
 namespace {
+
 const size_t kSortMaxRays = (size_t)1 << 26;
 
 int order_args(RtuContext* ctx, const void* rays, const void* order, size_t n, bool device) {
@@ -6276,7 +5433,10 @@ int order_args(RtuContext* ctx, const void* rays, const void* order, size_t n, b
     if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
     return RTU_OK;
 }
+
 }  // namespace
+
+extern "C" {
 
 int rtu_ray_order_device(RtuContext* ctx, const void* d_rays, size_t n, void* d_order, void* hip_stream) {
     if (!ctx) return RTU_ERR_ARG;

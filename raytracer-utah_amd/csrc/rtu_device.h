@@ -121,7 +121,7 @@ struct DevNode {                // one scene-graph node (wave-uniform data)
     int32_t chain[RTU_MAX_NODE_DEPTH];  // chain[d] = ancestor at depth d (chain[depth] == self)
     // NODE-LEVEL BOUND (fast variant only; SURVEY row f4 — the reference has Node::ComputeChildBoundBox, scene.h:475-489, and
     // never uses it): the world-space box of the object's own bounding box (unit cube / unit square / mesh box) taken
-    // through the node's chain of transformations, a little inflated (rtu_capi.hip: world_bounds). A ray that misses it by
+    // through the node's chain of transformations, a little inflated (rtu_capi_build.hip: world_bounds). A ray that misses it by
     // the margin of rtu_intersect.h "Culling" cannot pass the reference's own box test of this object, so the node is
     // skipped before its transformation and exact test — which still decide every result bit of the rays that remain.
     float   wmin[3], wmax[3];
@@ -132,7 +132,7 @@ struct DevNode {                // one scene-graph node (wave-uniform data)
     float   plane_n[2][3];
 };
 
-// OCCLUDER LISTS of one (non-ambient light, mesh node) pair, made at upload (rtu_capi.hip: build_light_lists): the mesh seen from the
+// OCCLUDER LISTS of one (non-ambient light, mesh node) pair, made at upload (rtu_capi_build.hip: build_light_lists): the mesh seen from the
 // light — a point light looks at it through a pinhole at its position, a direct light along its direction — on a G x G grid of
 // cells, and for every cell the triangles whose projection (widened by the cull margin, a quarter of a cell of slack) touches it.
 // A shadow ray's direction from the light is fixed by its ORIGIN, so one lookup with the origin names every triangle of the

@@ -440,7 +440,7 @@ __device__ __forceinline__ f3 interp(const float* arr, const uint32_t* face, f3 
 
 // TriObj::IntersectTriangle (objFunctions.cpp:257-328) on a 64-byte triangle record that
 // holds everything of the test that does not depend on the ray (computed once at
-// upload with the reference's own float operations, rtu_capi.hip):
+// upload with the reference's own float operations, rtu_capi_build.hip build_tri_records):
 //   r0 = {A.xyz, N.x}  r1 = {N.y, N.z, A2.x, A2.y}  r2 = {C2-A2, B2-A2}  r3 = {1/TriABCArea (fp64), axis, -}
 // N = normalised face normal (:263); axis = dominant axis of N (:276-296); *2 = vertex
 // projected on the other two axes; TriABCArea as :298. "/2.0" in fp64 (:298-300) equals
@@ -709,7 +709,7 @@ __device__ __forceinline__ bool fast_box_node(const FastRay& f, f3 lo, f3 hi, fl
 // being the largest |coordinate| of the origin of any space. Every point of every node's bound is within sqrt(3) (pm + wscale) of the
 // ray's origin and |dir| >= 0.999, so at the bound the two lines are at most
 //     1.74 K u (pm + Omega + 1) (pm + wscale)  <=  wnoise (pm + wreach)^2,   wnoise = 1.74 u max K,  wreach = max(wscale, Omega + 1)
-// apart on every axis (world_far, rtu_capi.hip, computes both). A hit the reference reports at t lies on ITS line inside the
+// apart on every axis (world_far, rtu_capi_build.hip, computes both). A hit the reference reports at t lies on ITS line inside the
 // object's box (within rounding), so the caller's line at the same t lies inside the box inflated by that much: tn <= t, and a
 // node whose inflated box begins beyond the best hit so far cannot beat it. 100 units from a scene 50 units across the second term
 // is 0.04 units, four times the first; 5000 units away it is 50 units, where the reference's line is in fact some 2.5 units off
@@ -724,7 +724,7 @@ __device__ __forceinline__ bool fast_box_node(const FastRay& f, f3 lo, f3 hi, fl
 // discriminant the point of closest approach -b / 2a that the noisy roots surround, are within sqrt(3) of the sphere's centre
 // (the line passes the unit cube), i.e. within sqrt(3) / |dir| of the cube's own interval in t. Taken to world units through the
 // node's chain T (|p| / |dir| <= 3 cond(T) times the world distance, itself <= sqrt(3) (pm + Omega) / 0.999; 1 / |dir| <= ||T||):
-//     slack = 5.2e-3 max cond(T) (pm + wreach) + 1.74 max || |T| ||_inf       (maxima over the sphere nodes; world_far, rtu_capi.hip)
+//     slack = 5.2e-3 max cond(T) (pm + wreach) + 1.74 max || |T| ||_inf       (maxima over the sphere nodes; world_far, rtu_capi_build.hip)
 // and a sphere node is skipped only if its inflated box begins more than `slack` beyond the best hit so far, or ends more than
 // `slack` behind the origin. Planes and meshes accept a hit only at a point inside the square or a triangle: no slack.
 __device__ __forceinline__ float sphere_slack(const DevScene& s, float pm) { return s.wsphere_k * (fminf(pm, 0x1p25f) + s.wreach) + s.wsphere_r; }
@@ -737,7 +737,7 @@ __device__ __forceinline__ double cull_margin_d(const DevScene& s, double pm) {
     return 1e-4 * fmax((double)s.wscale, pm) + (double)s.wnoise * q * q;
 }
 // THE NEAR MARGIN: secondary, shadow and gather rays (k_trace, the inline shadow walks) keep a margin of one maximum and one product,
-//     delta = c1 max(m0, pm)        (DevScene::near_m0, near_c1, made by near_margin, rtu_capi.hip),
+//     delta = c1 max(m0, pm)        (DevScene::near_m0, near_c1, made by near_margin, rtu_capi_build.hip),
 // which is 1e-4 max(wscale, pm), bit for bit and instruction for instruction, in a scene that needs no more (c1 = 1e-4,
 // m0 = wscale), and the occluder lists are built with a scale wlist that is wscale there (rtu_lightlist.h, ll_face_wid). Such a
 // ray starts at a hit point, i.e. within the scene's bounds up to what the ray that found it was off: pm <= P = 2 wscale. The
@@ -1125,7 +1125,7 @@ __device__ __forceinline__ bool mesh_hit_coop(const MeshT& mesh, const Ray& ray,
 }
 
 // ---------------------------------------------------------------------------
-// A HARD SHADOW RAY AGAINST A MESH WITHOUT A BVH WALK (DevLightMask, rtu_capi.hip build_light_lists). The ray runs from its
+// A HARD SHADOW RAY AGAINST A MESH WITHOUT A BVH WALK (DevLightMask, rtu_capi_build.hip build_light_lists). The ray runs from its
 // origin towards the light, so the cell of the light's grid that the ORIGIN projects into lists every triangle of the mesh the
 // ray can touch; entries [e0, e1) of the list get the reference's own triangle test (tri_hit, `t < t_max` as in a fresh
 // HitInfo of ShadowTrace, RenderFunctions.cpp:213-240). GenLight::Shadow (lightFunctions.cpp:27-37) asks only WHETHER the
@@ -1253,7 +1253,7 @@ __device__ __forceinline__ int mesh_shadow_cells(const uint32_t* cell_tri, uint3
 // clear of the box by delta = cull_margin(|origin|) on some axis — the geometric form of "Culling" above, on the world-space
 // box of the node — cannot produce a result there, and the node is skipped before its transformation and exact test.
 // (The bound of a sphere is also widened at upload by what the cancellation in its discriminant can move a grazing root for
-// origins inside the scene, rtu_capi.hip world_bounds.) `skip` marks nodes the caller
+// origins inside the scene, rtu_capi_build.hip world_bounds.) `skip` marks nodes the caller
 // has already excluded in the same sense: for primary rays, pixels outside the node's screen rectangle (k_node_rects).
 // INL (with DEFER): the occluder lists are walked HERE, in stage 1 (the inline shading of childless Shade() calls, render_impl.h
 // shadows_inline): `deferred` then means "this ray cannot be settled without a BVH walk".

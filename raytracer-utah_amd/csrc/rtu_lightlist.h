@@ -1,5 +1,5 @@
 // rtu_lightlist.h — the arithmetic of the occluder lists of shadow rays (rtu_device.h DevLightMask), shared by the host builder
-// (rtu_capi.hip compute_light_list, used by rtu_upload_scene) and the device builder (rtu_scene_update.hip, used by
+// (rtu_capi_build.hip compute_light_list, used by rtu_upload_scene) and the device builder (rtu_scene_update.hip, used by
 // rtu_update_scene). Both run the same expressions in binary64 with -ffp-contract=off, so both build the same lists bit for bit.
 //   * per-face pieces (RTU_HD): the cover mesh of a face, its widened box in the light's (u, v), its cells and its zmin;
 //   * scalar decisions (host): the light's frame, the grid size G and the slack S0.

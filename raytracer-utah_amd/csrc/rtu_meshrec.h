@@ -1,4 +1,4 @@
-// rtu_meshrec.h — what a mesh's device structures take from its VERTICES, shared by the host builders (rtu_capi.hip: build_tri_records
+// rtu_meshrec.h — what a mesh's device structures take from its VERTICES, shared by the host builders (rtu_capi_build.hip: build_tri_records
 // at upload, the host restatement behind rtu_debug_host_mesh) and the device kernels of rtu_update_meshes (rtu_mesh_update.hip):
 //   * the 64-byte triangle record of one face (TriRec, rtu_intersect.h);
 //   * the box of one child slot of the collapsed fast trees (DevMesh::bvh4 / ::bvh8): of a leaf slot from the vertices of its

@@ -1,6 +1,6 @@
 // rtu_scene_update.hip — the device builder of rtu_update_scene: the cover meshes (world-space faces of the masked mesh nodes) and
 // the occluder lists of shadow rays, from the meshes already in HBM. The per-face arithmetic is rtu_lightlist.h, the same code the
-// host builder (rtu_capi.hip compute_light_list) runs, so a list built here equals the host's entry for entry and bit for bit;
+// host builder (rtu_capi_build.hip compute_light_list) runs, so a list built here equals the host's entry for entry and bit for bit;
 // the scalar decisions between the passes (frame, G, slack) run on the host on a few read-back doubles.
 //
 // One list on a G x G grid:

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ALL_TAGS, LOCAL_SCENES, MAC_PREFIX, REPO, SAMPLED_TAGS, SMALL_TAGS, TEX_TAGS, instantiate_scene, read_png
+from test_progressive_host import dynamic_symbols
 
 SCENES = {
     "p1_256": "Project1Example.xml", "p3s_800x600": "Project3Simple.xml", "p4_1080": "Project4.xml",
@@ -41,6 +42,19 @@ def test_c_abi_exports_every_declared_symbol(pkg):
         assert hasattr(pkg.host, s), "librtu_host.so does not export " + s
     assert set(hip_syms) == set(pkg.HIP_SYMBOLS)
     assert set(host_syms) == set(pkg.HOST_SYMBOLS)
+
+
+def test_hip_library_exports_nothing_but_the_c_abi(pkg):
+    """librtu_hip.so is linked behind someone else's program: an unmangled name it defines that is not an entry of the C-ABI
+    (a helper of csrc/rtu_capi*.hip left with C linkage, say) could be interposed by, or interpose, a symbol of that program.
+    The two process-wide allocation counters of rtu_devbuf.h are the exceptions; rtu_sensor_check_desc is declared in csrc/rtu_sensor.h."""
+    plain = sorted(s for s in dynamic_symbols(os.path.join(os.path.dirname(pkg.__file__), "lib", "librtu_hip.so")) if not s.startswith("_"))
+    assert len(plain) >= 15
+    stray = [s for s in plain if not s.startswith("rtu_") and s not in ("g_devbuf_allocations", "g_devbuf_bytes")]
+    assert not stray, "librtu_hip.so exports names outside the rtu_ prefix: %s" % stray
+    declared = set(declared_symbols("rtu_render.h")) | {"rtu_sensor_check_desc"}
+    undeclared = [s for s in plain if s.startswith("rtu_") and s not in declared]
+    assert not undeclared, "librtu_hip.so exports rtu_ names that include/rtu_render.h does not declare: %s" % undeclared
 
 
 def test_struct_layouts_match_the_headers(pkg):

@@ -1,4 +1,4 @@
-"""The occluder lists of hard shadow rays (rtu_device.h DevLightMask, rtu_capi.hip compute_light_list), checked on the CPU ray by ray.
+"""The occluder lists of hard shadow rays (rtu_device.h DevLightMask, rtu_capi_build.hip compute_light_list), checked on the CPU ray by ray.
 
 A shadow ray's direction from its light is fixed by its origin, so the device looks the origin's cell up and tests only the triangles
 listed there — an empty cell skips the mesh, and entries whose zmin lies beyond the origin's depth are never reached. That is only

@@ -18,7 +18,7 @@ away it is quantised to 2^-24 D, the line is off by some 3 * 2^-24 * D^2 where i
   F6  orthographic grids from 1e3, 1e4 and 1e5 units back: beyond the reach of a binary32 camera
 
 MODEL. `model_skips` restates, in binary64, the decision of the device's node-level test: the node's box as world_bounds
-(rtu_capi.hip) widens it, inflated by delta, against the segment [0, best hit so far]. It is not the kernel. It decides only whether
+(rtu_capi_build.hip) widens it, inflated by delta, against the segment [0, best hit so far]. It is not the kernel. It decides only whether
 a family contains rays on which that test COULD go wrong (non-vacuity); what the device computes is compared with the oracle alone."""
 import math
 
@@ -147,7 +147,7 @@ OBJECT_BOX = {RTU_OBJ_SPHERE: ((-1, -1, -1), (1, 1, 1)), RTU_OBJ_PLANE: ((-1, -1
 
 
 def model_world_bounds(scene):
-    """world_bounds (rtu_capi.hip) restated: per node with an object its widened world box (lo, hi), and the scale of the margin."""
+    """world_bounds (rtu_capi_build.hip) restated: per node with an object its widened world box (lo, hi), and the scale of the margin."""
     nd, boxes = nodes(scene), {}
     for i in range(scene.desc.n_nodes):
         t = nd[i].obj_type

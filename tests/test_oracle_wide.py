@@ -263,7 +263,7 @@ def test_w5_compact_scene_far_chain(pkg, orc, tmp_path, G, what, levels):
 
 
 def test_smallest_extents_with_a_skippable_hit(pkg, orc, tmp_path):
-    """What the switch of near_margin (rtu_capi.hip; rtu_intersect.h, THE NEAR MARGIN) is held against: with nine times the rays
+    """What the switch of near_margin (rtu_capi_build.hip; rtu_intersect.h, THE NEAR MARGIN) is held against: with nine times the rays
     (a 384 x 384 image) the smallest X at which the near margin would lose a hit of W1 is 250, the smallest G of W5 is 1e4; 20 000
     random rays from a wall patch once found 300 and 4000. The far term is on from X = 40 and G = 55: a quarter of the smallest of
     these is 62 and 1000."""
