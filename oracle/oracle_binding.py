@@ -322,3 +322,82 @@ def shade_rays(scene, rays, eye, threads=1, max_bounce=MAX_BOUNCE):
     with _bounces(max_bounce):
         _rays(scene, rays, RAYS_SHADE, out, eye=eye, stats=st, threads=threads)
     return out, st.as_dict()
+
+
+# the keyed ray-level entry (rtu_oracle_rays_keyed): recipes S and P on caller-supplied rays and keys
+KEYED_SAMPLED, KEYED_PATHS, KEYED_GATHER, KEYED_AMBIENT = 0, 1, 2, 3
+INFO_HIT, INFO_FRONT, INFO_MATERIAL, INFO_GLOSSY = 1, 2, 4, 8
+lib.rtu_oracle_rays_keyed.restype = ctypes.c_int
+lib.rtu_oracle_rays_keyed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                      ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(OracleStats), ctypes.c_int]
+lib.rtu_oracle_rays_keyed_info.restype = ctypes.c_int
+lib.rtu_oracle_rays_keyed_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int]
+
+
+def _keyed_args(rays, keys):
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE and (rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8):
+        raise ValueError("rays: a structured array of the package's ray_dtype() or float32 [n, 8]")
+    r = np.ascontiguousarray(rays).reshape(-1).view(RAY_DTYPE)
+    k = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+    if k.size != r.size:
+        raise ValueError("keys: one uint32 per ray")
+    return r, k
+
+
+def _keyed(scene, rays, keys, eye, mode, amb=None, threads=1, max_bounce=MAX_BOUNCE):
+    r, k = _keyed_args(rays, keys)
+    e = np.ascontiguousarray(eye, np.float32)
+    if e.shape != (3,):
+        raise ValueError("eye: three floats")
+    a = None
+    if mode == KEYED_AMBIENT:
+        a = np.asarray(amb, np.float32).reshape(r.size, -1)
+        if a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((r.size, 1), np.float32)], axis=1)
+        if a.shape[1] != 4:
+            raise ValueError("amb: float32 [n, 4] or [n, 3]")
+        a = np.ascontiguousarray(a)
+    out = np.zeros((r.size, 4), np.float32)
+    st = OracleStats()
+    with _bounces(max_bounce):
+        rc = lib.rtu_oracle_rays_keyed(scene.desc_ptr, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None,
+                                       a.ctypes.data if a is not None and r.size else None, r.size, e.ctypes.data, mode,
+                                       out.ctypes.data if r.size else None, ctypes.byref(st), threads)
+    if rc != 0:
+        raise OracleError(rc)
+    return out, st.as_dict()
+
+
+def shade_rays_sampled(scene, rays, keys, eye, max_bounce=MAX_BOUNCE, threads=1):
+    """Recipe S along the rays, keys[i] the key of ray i's root Shade() call: (float32 [n, 4] {r, g, b, t}, stats dict) — what
+    rtu_shade_rays_sampled answers."""
+    return _keyed(scene, rays, keys, eye, KEYED_SAMPLED, threads=threads, max_bounce=max_bounce)
+
+
+def shade_rays_paths(scene, rays, keys, eye, max_bounce=MAX_BOUNCE, threads=1):
+    """Recipe P along the rays (the 4-bounce gather behind every hit with a material) — what rtu_shade_rays_paths answers."""
+    return _keyed(scene, rays, keys, eye, KEYED_PATHS, threads=threads, max_bounce=max_bounce)
+
+
+def gather_rays(scene, rays, keys, eye, max_bounce=MAX_BOUNCE, threads=1):
+    """{c.r, c.g, c.b, t}: the intensity of the AmbientLight MonteCarlo(hit, 4) appends for the ray's key — what rtu_gather_rays answers."""
+    return _keyed(scene, rays, keys, eye, KEYED_GATHER, threads=threads, max_bounce=max_bounce)
+
+
+def shade_rays_ambient(scene, rays, keys, amb, eye, max_bounce=MAX_BOUNCE, threads=1):
+    """Recipe P with amb[i] (float32 [n, 4] {r, g, b, ignored} or [n, 3]) in place of the gathered light — what rtu_shade_rays_ambient
+    answers."""
+    return _keyed(scene, rays, keys, eye, KEYED_AMBIENT, amb=amb, threads=threads, max_bounce=max_bounce)
+
+
+def keyed_info(scene, rays, keys, threads=1):
+    """What keyed rays meet (rtu_oracle_rays_keyed_info): uint32 [n, 4] {INFO_* flags, gather rays of the chain that hit (0 .. 4),
+    soft shadow rays of the root call, those of them that are occluded}."""
+    r, k = _keyed_args(rays, keys)
+    out = np.zeros((r.size, 4), np.uint32)
+    rc = lib.rtu_oracle_rays_keyed_info(scene.desc_ptr, r.ctypes.data if r.size else None, k.ctypes.data if r.size else None, r.size,
+                                        out.ctypes.data if r.size else None, threads)
+    if rc != 0:
+        raise OracleError(rc)
+    return out

@@ -99,6 +99,7 @@ struct Ctx {
     bool libm_trig;      // true: cosf/sinf of libm as the reference calls them; false: the portable sincos the device uses
     uint32_t seq_key, seq_counter;
     uint64_t gather_rays;
+    uint64_t soft_rays = 0, soft_occluded = 0;  // shadow rays towards a light of size > 0, and those that were occluded (rtu_oracle_rays_keyed_info)
 };
 
 // ---------------------------------------------------------------------------
@@ -499,6 +500,8 @@ C3 illuminate(Ctx& cx, const RtuLight& l, V3 p, uint32_t key, uint32_t light_ind
         V3 currentSamplePos = (position + v1 * offsetX) + v2 * offsetY;        // :58
         Ray sr; sr.p = p; sr.dir = normalized(currentSamplePos - p);           // :60
         shadowIntensity += shadow(cx, sr, length(p - currentSamplePos));       // :62
+        cx.soft_rays++;
+        if (shadowIntensity == 0.0f) cx.soft_occluded++;
     } else {
         Ray sr; sr.p = p; sr.dir = normalized(position - p);       // :76
         shadowIntensity += shadow(cx, sr, length(position - p));   // :78
@@ -1445,6 +1448,139 @@ int rtu_oracle_rays(const RtuSceneDesc* scene, const RtuOracleRay* rays, long lo
         memset(stats, 0, sizeof *stats);
         for (auto& s : st) add_stats(*stats, s);
     }
+    return 0;
+}
+
+// Keyed ray-level entry: what render_rows does per sample of recipe S / P after it has its ray (above, "recipe S"), and what
+// include/rtu_render.h states for rtu_shade_rays_sampled / _paths, rtu_gather_rays and rtu_shade_rays_ambient — on caller-supplied
+// rays with caller-supplied keys. Keyed stream, portable trig, the depth of rtu_oracle_debug_max_bounce, `eye` as camera.pos.
+// Per ray HitInfo::Init's z is replaced by tmax and dir is used as given; nothing is filtered. Every mode writes n float4.
+//   SAMPLED  hit: shade_node(h, ray, max_bounce, key, lights) (a node without material: white); miss: env_sample(dir), t = tmax.
+//   PATHS    hit with a material: c = monte_carlo(h, 4, key); shade_node(.., child_key(key, 4), {AmbientLight(c)}) + shade_node(.., key,
+//            lights), summed in that order (RenderFunctions.cpp:129-135); otherwise as SAMPLED.
+//   GATHER   {c.r, c.g, c.b, hInfo.z}; c = 0 on a miss (t = tmax) and at a node without material.
+//   AMBIENT  PATHS with (0 + amb[i]) + 0 in place of c (the sum MonteCarlo() forms, :568-570); the fourth float of amb is ignored.
+// Gather rays are in no ray counter, as in render_rows. Threads take contiguous chunks with their own Ctx.
+int rtu_oracle_rays_keyed(const RtuSceneDesc* scene, const RtuOracleRay* rays, const uint32_t* keys, const float* amb, long long n,
+                          const float* eye, int mode, float* out, RtuOracleStats* stats, int threads) {
+    int err = check_scene(scene, true);
+    if (err) return err;
+    if (mode < RTU_ORACLE_KEYED_SAMPLED || mode > RTU_ORACLE_KEYED_AMBIENT || n < 0 || !eye) return RTU_ORACLE_ERR_ARG;
+    if (n && (!rays || !out || !keys || (mode == RTU_ORACLE_KEYED_AMBIENT && !amb))) return RTU_ORACLE_ERR_ARG;
+    RtuSceneDesc local = *scene;  // shallow: only camera.pos differs
+    for (int k = 0; k < 3; k++) local.camera.pos[k] = eye[k];
+    if (threads < 1) threads = 1;
+    std::vector<RtuOracleStats> st(threads);
+    auto work = [&](int t, long long b, long long e) {
+        Ctx cx;
+        cx.s = &local;
+        cx.sequential = cx.libm_trig = false;
+        cx.seq_key = cx.seq_counter = 0;
+        cx.gather_rays = 0;
+        memset(&cx.st, 0, sizeof cx.st);
+        const LightSet scene_lights = {local.lights, local.n_lights};
+        for (long long i = b; i < e; i++) {
+            Ray ray;
+            ray.p = ld3(rays[i].org);
+            ray.dir = ld3(rays[i].dir);
+            const uint32_t key = keys[i];
+            Hit h = new_hit();
+            h.z = rays[i].tmax;
+            cx.st.primary_rays++;
+            const bool hit = trace(cx, ray, 0, h);
+            if (hit) cx.st.primary_hits++;
+            const bool lit = hit && local.nodes[h.node].material_id >= 0;  // the hits recipe P gathers for (:129)
+            C3 c;
+            if (mode == RTU_ORACLE_KEYED_GATHER) {
+                c = lit ? monte_carlo(cx, h, RTU_GI_BOUNCES, key, scene_lights) : mkc(0, 0, 0);
+            } else if (!hit) {
+                c = env_sample(local, ray.dir);
+            } else if (mode == RTU_ORACLE_KEYED_SAMPLED || !lit) {
+                c = shade_node(cx, h, ray, g_max_bounce, key, scene_lights);
+            } else {
+                C3 indirect;
+                if (mode == RTU_ORACLE_KEYED_PATHS) {
+                    indirect = monte_carlo(cx, h, RTU_GI_BOUNCES, key, scene_lights);
+                } else {
+                    indirect = mkc(0, 0, 0);
+                    indirect += ldc(amb + 4 * i);
+                    indirect += mkc(0, 0, 0);
+                }
+                RtuLight al = ambient_light(indirect);
+                LightSet mc = {&al, 1};
+                c = shade_node(cx, h, ray, g_max_bounce, child_key(key, SLOT_AMBIENT_TREE), mc);  // :134
+                c += shade_node(cx, h, ray, g_max_bounce, key, scene_lights);                     // :135
+            }
+            float* o = out + 4 * i;
+            o[0] = c.r; o[1] = c.g; o[2] = c.b; o[3] = h.z;
+        }
+        st[t] = cx.st;
+    };
+    if (threads == 1) {
+        work(0, 0, n);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < threads; t++) th.emplace_back(work, t, n * t / threads, n * (t + 1) / threads);
+        for (auto& t : th) t.join();
+    }
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        for (auto& s : st) add_stats(*stats, s);
+    }
+    return 0;
+}
+
+// What a keyed ray meets, for the tests that assert a ray family's contents (tests/test_oracle_rays_keyed.py): four words per ray.
+//   [0] flags: 1 hit, 2 front, 4 the node has a material, 8 that material is glossy (a reflection or refraction glossiness > 0)
+//   [1] the gather rays of MonteCarlo(h, 4, key)'s chain that hit, 0 .. 4: 4 = the chain reaches depth 4, d < 4 = it leaves the scene
+//       at depth d + 1 (0 without a chain: a miss, a node without material)
+//   [2] [3] of the shadow rays the root Shade(.., key, lights) fires towards lights of size > 0: how many, and how many are occluded
+int rtu_oracle_rays_keyed_info(const RtuSceneDesc* scene, const RtuOracleRay* rays, const uint32_t* keys, long long n, uint32_t* info, int threads) {
+    int err = check_scene(scene, true);
+    if (err) return err;
+    if (n < 0 || (n && (!rays || !keys || !info))) return RTU_ORACLE_ERR_ARG;
+    if (threads < 1) threads = 1;
+    auto work = [&](long long b, long long e) {
+        Ctx cx;
+        cx.s = scene;
+        cx.sequential = cx.libm_trig = false;
+        cx.seq_key = cx.seq_counter = 0;
+        cx.gather_rays = 0;
+        memset(&cx.st, 0, sizeof cx.st);
+        const LightSet scene_lights = {scene->lights, scene->n_lights};
+        for (long long i = b; i < e; i++) {
+            uint32_t* o = info + 4 * i;
+            o[0] = o[1] = o[2] = o[3] = 0;
+            Ray ray;
+            ray.p = ld3(rays[i].org);
+            ray.dir = ld3(rays[i].dir);
+            Hit h = new_hit();
+            h.z = rays[i].tmax;
+            if (!trace(cx, ray, 0, h)) continue;
+            const int mid = scene->nodes[h.node].material_id;
+            o[0] = 1u | (h.front ? 2u : 0u);
+            if (mid < 0) continue;
+            const RtuMaterial& m = scene->materials[mid];
+            o[0] |= 4u | (m.reflection_glossiness > 0 || m.refraction_glossiness > 0 ? 8u : 0u);
+            Hit cur = h;
+            uint32_t key = keys[i];
+            for (int d = 0; d < RTU_GI_BOUNCES; d++) {  // the chain of monte_carlo(), without its shading
+                Ray g; g.p = cur.p; g.dir = normalized(sample_hemisphere_cosine(cx, cur.N, key));
+                Hit nh = new_hit();
+                if (!trace(cx, g, 0, nh)) break;
+                o[1]++;
+                key = child_key(key, SLOT_GATHER);
+                cur = nh;
+            }
+            cx.soft_rays = cx.soft_occluded = 0;
+            shade_node(cx, h, ray, 0, keys[i], scene_lights);
+            o[2] = (uint32_t)cx.soft_rays;
+            o[3] = (uint32_t)cx.soft_occluded;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) th.emplace_back(work, n * t / threads, n * (t + 1) / threads);
+    for (auto& t : th) t.join();
     return 0;
 }
 

@@ -2,7 +2,9 @@
  * rtu_oracle.h — C interface of the CPU restatement (oracle/rtu_oracle.cpp).
  * TEST INFRASTRUCTURE: see the header of rtu_oracle.cpp. Loaded only by tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg.
- * Besides the renders of whole images there is one ray-level entry, rtu_oracle_rays: closest hit, occlusion and radiance along caller-supplied rays.
+ * Besides the renders of whole images there are two ray-level entries on caller-supplied rays: rtu_oracle_rays (closest hit, occlusion
+ * and the radiance of recipe W) and rtu_oracle_rays_keyed (recipes S and P, the gathered light alone and a given ambient term, under
+ * caller-supplied keys), with rtu_oracle_rays_keyed_info to tell what such rays meet.
  */
 #ifndef RTU_ORACLE_H_INCLUDED
 #define RTU_ORACLE_H_INCLUDED
@@ -119,6 +121,35 @@ typedef struct RtuOracleRayHit { float t; int32_t node; uint32_t flags; int32_t 
 #define RTU_ORACLE_RAYS_SHADE    2
 int  rtu_oracle_rays(const RtuSceneDesc* scene, const RtuOracleRay* rays, long long n, const float* eye, int mode, void* out,
                      RtuOracleStats* stats, int threads);
+/* The keyed ray-level entry: recipes S and P on n caller-supplied rays with one key each, the counterpart of the device's
+ * rtu_shade_rays_sampled, rtu_shade_rays_paths, rtu_gather_rays and rtu_shade_rays_ambient (include/rtu_render.h). Keyed stream, portable
+ * trig, the depth of rtu_oracle_debug_max_bounce, `eye` (three floats) as camera.pos. As for rtu_oracle_rays, HitInfo::Init's z is replaced
+ * by tmax, dir is used as given and NO ray is filtered: pass valid rays only. out: n float4 in every mode.
+ *   SAMPLED  {r, g, b, hInfo.z}: a hit is Shade(hit, max_bounce, lights) on the streams of keys[i] (a node without material: white), a miss
+ *            is environment.SampleEnvironment(dir) with t = tmax — one sample of rtu_oracle_render_samples after it has its ray.
+ *   PATHS    a hit with a material: c = MonteCarlo(hit, 4) drawn from keys[i], then Shade(hit, {AmbientLight(c)}) on child_key(keys[i], 4)
+ *            + Shade(hit, lights) on keys[i], in that order (RenderFunctions.cpp:129-135); otherwise as SAMPLED.
+ *   GATHER   {c.r, c.g, c.b, hInfo.z}; c = 0 on a miss (t = tmax) and at a node without material.
+ *   AMBIENT  PATHS with (0 + amb[i]) + 0 in place of c (a negative zero becomes +0); amb: n float4 {r, g, b, ignored}, this mode only.
+ * stats (may be NULL): the counters of a render; gather rays are in no ray counter (their traversal counters are counted), as in
+ * rtu_oracle_render_paths. Scenes without stochastic features are accepted. keys == NULL, or amb == NULL in AMBIENT, with n > 0, eye ==
+ * NULL and an unknown mode are RTU_ORACLE_ERR_ARG. Threads take contiguous chunks of rays. */
+#define RTU_ORACLE_KEYED_SAMPLED 0
+#define RTU_ORACLE_KEYED_PATHS   1
+#define RTU_ORACLE_KEYED_GATHER  2
+#define RTU_ORACLE_KEYED_AMBIENT 3
+int  rtu_oracle_rays_keyed(const RtuSceneDesc* scene, const RtuOracleRay* rays, const uint32_t* keys, const float* amb, long long n,
+                           const float* eye, int mode, float* out, RtuOracleStats* stats, int threads);
+/* What keyed rays meet, for the tests that assert the contents of a ray family: four words per ray. [0]: 1 hit | 2 front | 4 the node
+ * has a material | 8 that material is glossy; [1]: how many gather rays of MonteCarlo(hit, 4)'s chain under keys[i] hit (4: the chain
+ * reaches depth 4; d < 4: it leaves the scene at depth d + 1; 0 where nothing is gathered); [2], [3]: the shadow rays the root Shade()
+ * fires towards lights of size > 0 under keys[i], and how many of them are occluded. */
+#define RTU_ORACLE_INFO_HIT      1u
+#define RTU_ORACLE_INFO_FRONT    2u
+#define RTU_ORACLE_INFO_MATERIAL 4u
+#define RTU_ORACLE_INFO_GLOSSY   8u
+int  rtu_oracle_rays_keyed_info(const RtuSceneDesc* scene, const RtuOracleRay* rays, const uint32_t* keys, long long n, uint32_t* info,
+                                int threads);
 /* pos, origin, u, v of the image plane (RenderFunctions.cpp:243-269). */
 int  rtu_oracle_camera_frame(const RtuCamera* cam, int width, int height, float out12[12]);
 /* gamma + Color24 + z-image; any output pointer may be NULL. */

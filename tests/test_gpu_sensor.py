@@ -2,7 +2,8 @@
 
 The generator kernel is compared with the host specification byte for byte. The images are tied to what exists: recipe W to the ray-level
 oracle under check_against of tests/test_gpu_parity.py (z bit for bit), the sampled recipes bit for bit in all four channels to the
-numpy float32 sum, in sample order, of the existing host entries' answers to sensor_rays(desc, k), divided by n."""
+numpy float32 sum, in sample order, of the existing host entries' answers to sensor_rays(desc, k), divided by n.
+Sensor rays of recipes S and P, and the images made of them, meet the oracle in tests/test_gpu_rays_keyed.py (family K4)."""
 import ctypes
 
 import numpy as np

@@ -4,7 +4,8 @@ As for the sampled batches, the oracle is reached through cameras: the rays and 
 (rtu_camera_sample_rays), shaded with eye = the camera, must be that sample's image of the frame with gather_bounces = 4 —
 rtu_debug_sample_images — bit for bit (t at every ray, rgb at every hit ray), and meet the oracle's image of that sample
 (rtu_oracle_render_sample_images with gi = 1) under the bar of tests/test_gpu_shade_rays_sampled.py: float z bit-exact, 8-bit RGB
-within 1, linear RGB within 2e-4. Everything else is byte identity with what this established, plus rtu_trace_rays for t."""
+within 1, linear RGB within 2e-4. Everything else is byte identity with what this established, plus rtu_trace_rays for t.
+Rays no camera fires, and the gathered light itself, meet the oracle's keyed ray-level entry in tests/test_gpu_rays_keyed.py."""
 import ctypes
 from types import SimpleNamespace
 

@@ -5,7 +5,8 @@ eye = the camera, must be that sample's image — rtu_debug_sample_images — bi
 of a ray is the environment where a render shows the background), and meet the oracle's image of that sample
 (rtu_oracle_render_sample_images, keyed streams, portable trigonometry) under the bar of tests/test_gpu_sampled.py, copied below.
 Everything else — permutations, batch sizes, rays no camera fires, switches, neighbours, errors — is byte identity with what this
-established, plus rtu_trace_rays for t."""
+established, plus rtu_trace_rays for t. Rays no camera fires and keys no pixel has meet the oracle's keyed ray-level entry in
+tests/test_gpu_rays_keyed.py."""
 import ctypes
 from types import SimpleNamespace
 
