@@ -176,6 +176,39 @@ int  rtu_update_scene(RtuContext* ctx, const RtuSceneDesc* scene);
  * Synchronous; waits for both of the context's streams first. RTU_ERR_NO_SCENE before any upload. */
 int  rtu_update_meshes(RtuContext* ctx, const RtuSceneDesc* scene, const uint32_t* mesh_ids, int n_meshes);
 
+/* Deform uploaded meshes from DEVICE memory: rtu_update_meshes for a caller whose vertices are made on the GPU (skinning, cloth, a
+ * torch module). Only the vertices (and, if it has new ones, the normals) are handed over; the reference tree, which the host path
+ * takes from rtu_scene_set_mesh_vertices, is REBUILT ON THE GPU (csrc/rtu_ref_build.h), bit for bit. Afterwards the context holds,
+ * for each listed mesh, what rtu_scene_set_mesh_vertices + rtu_update_meshes would have left there for the same vertices: v, vn,
+ * the `ref` tree (breadth-first), its element order and triangle records, the fast tree's records, any_empty_box, the mesh box,
+ * scale, n_bvh_nodes, bvh_depth and the walks' stack need by bits; the refitted boxes of bvh4 / bvh8 by value.
+ *   edits[i].mesh   the mesh; ids in range and not repeated (RTU_ERR_ARG).
+ *   edits[i].d_v    float [3 nv] in device memory (NULL: RTU_ERR_ARG).
+ *   edits[i].d_vn   float [3 nvn] in device memory, or NULL: the normals the context holds stay — or, with
+ *                   RTU_MESH_EDIT_RECOMPUTE_NORMALS, are recomputed from d_v as rtu_scene_recompute_normals does (ComputeNormals,
+ *                   bit for bit), which is allowed under that function's condition only: one normal per vertex and fn == f as
+ *                   uploaded, else RTU_ERR_ARG. d_vn together with the flag, or an unknown flag: RTU_ERR_ARG.
+ * `scene` is read as rtu_update_scene reads it; of scene->meshes[i] for a LISTED mesh only nv, nf, nvn, nvt and n_elements are
+ * compared (RTU_ERR_SCENE_SHAPE) — its arrays, n_bvh_nodes, bvh_depth and bounds are not read: the host scene is stale by design.
+ * hip_stream is the stream the vertices were produced on: the call orders its reads after that stream's work with an event (no
+ * device-wide synchronisation) and is itself synchronous, like rtu_update_meshes. n_edits == 0 is rtu_update_scene.
+ * Everything that can be checked first is; the one thing that cannot — a tree deeper than RTU_MAX_BVH_STACK, RTU_ERR_UNSUPPORTED as
+ * in the host path — is known after the build, so the build goes into scratch, its header is read back and validated, and only
+ * then is anything the kernels read replaced. A refused call leaves the context as it was. The shape the context remembers takes
+ * the new n_bvh_nodes, bvh_depth and bounds: rtu_context_mesh_shape gives the header to put into the descriptor of a later
+ * rtu_update_scene / rtu_update_meshes. Progressive sessions turn RTU_ERR_STALE, launch hints are cleared, rtu_keep_previous_vertices
+ * works as for rtu_update_meshes. All scratch is grow-only: the first update of a mesh allocates, later ones nothing. */
+#define RTU_MESH_EDIT_RECOMPUTE_NORMALS 1u
+typedef struct RtuMeshDeviceEdit {
+    uint32_t    mesh, flags;
+    const void* d_v;    /* float[3 nv], device memory */
+    const void* d_vn;   /* float[3 nvn], device memory; NULL keeps the uploaded normals,
+                           or, with RECOMPUTE_NORMALS, has them recomputed from d_v */
+} RtuMeshDeviceEdit;
+int  rtu_update_meshes_device(RtuContext* ctx, const RtuSceneDesc* scene, const RtuMeshDeviceEdit* edits, int n_edits, void* hip_stream);
+/* The header of mesh `mesh` as the context remembers it (nv, nf, nvn, nvt, n_bvh_nodes, n_elements, bvh_depth, bounds); arrays NULL. */
+int  rtu_context_mesh_shape(RtuContext* ctx, uint32_t mesh, RtuMesh* header_out);
+
 /* The shape check of rtu_update_scene on its own: RTU_OK when `b` has the shape of `a`, else RTU_ERR_SCENE_SHAPE with the first
  * difference in err_buf (may be NULL); RTU_ERR_ARG for a missing array. Pure host code. */
 int  rtu_scene_shape_diff(const RtuSceneDesc* a, const RtuSceneDesc* b, char* err_buf, size_t err_len);
@@ -1658,6 +1691,21 @@ int  rtu_debug_context_mesh(RtuContext* ctx, uint32_t mesh, int which, void* out
  * the boxes by the host restatement of the device refit. now == NULL: `uploaded` as rtu_upload_scene builds it, no refit — what
  * a refit with the uploaded vertices must reproduce (boxes as float values). */
 int  rtu_debug_host_mesh(const RtuMesh* uploaded, const RtuMesh* now, int which, void* out, size_t capacity_bytes, size_t* bytes_out);
+/* Test hooks of rtu_update_meshes_device, pure host code. rtu_debug_host_ref_build: the HOST FORM of the device builder (the same
+ * passes, run in loops) on the connectivity of `uploaded` with the vertices v (float [3 nv]; NULL: uploaded->v). which:
+ * RTU_MESH_REF_BVH, RTU_MESH_REF_ELEMENTS, RTU_MESH_VN (the normals RTU_MESH_EDIT_RECOMPUTE_NORMALS computes; needs nvn == nv), or
+ * RTU_MESH_HEADER for an RtuRefBuildHeader. No depth bound: a tree deeper than RTU_MAX_BVH_STACK is built and its depth reported.
+ * rtu_debug_partition_rule: the closed form of the builder's partition for the keep flags keep[n]; perm_out[i] is the position
+ * whose element ends at position i. */
+typedef struct RtuRefBuildHeader {
+    float    bmin[3], bmax[3], scale;
+    uint32_t n_bvh_nodes, any_empty_box, bvh_depth;
+} RtuRefBuildHeader;
+int  rtu_debug_host_ref_build(const RtuMesh* uploaded, const float* v, int which, void* out, size_t capacity_bytes, size_t* bytes_out);
+int  rtu_debug_partition_rule(const uint8_t* keep, uint32_t n, uint32_t* perm_out);
+/* Diagnostic: the milliseconds rtu_update_meshes_device spent per phase since the previous call (HIP events on the context's stream,
+ * enabled by rtu_debug_mesh_update_timing): {tree build and normals, copies, triangle records and refit, placement}; reset. */
+int  rtu_debug_mesh_update_device_timing(RtuContext* ctx, float* ms_out4);
 
 /* Diagnostic: Shade() frames per recursion level (6 values) and rays deferred to stage 2 per phase
  * (7 values: primary, then levels 0..5) of the most recent frame (fast variant). Synchronises. */

@@ -153,6 +153,8 @@ HIP_SYMBOLS = ["rtu_device_count", "rtu_error_string", "rtu_create_context", "rt
                "rtu_debug_device_allocations", "rtu_progressive_begin", "rtu_progressive_advance", "rtu_progressive_status",
                "rtu_progressive_snapshot_device", "rtu_progressive_snapshot", "rtu_progressive_free", "rtu_debug_device_bytes",
                "rtu_update_meshes", "rtu_multi_update_meshes", "rtu_debug_context_mesh", "rtu_debug_host_mesh", "rtu_debug_mesh_update_timing",
+               "rtu_update_meshes_device", "rtu_context_mesh_shape", "rtu_debug_host_ref_build", "rtu_debug_partition_rule",
+               "rtu_debug_mesh_update_device_timing",
                "rtu_trace_rays_device", "rtu_occluded_rays_device", "rtu_trace_rays", "rtu_occluded_rays", "rtu_camera_rays",
                "rtu_shade_defaults", "rtu_shade_rays_device", "rtu_shade_rays",
                "rtu_shade_rays_sampled_device", "rtu_shade_rays_sampled", "rtu_camera_sample_rays", "rtu_sample_key", "rtu_child_key",
@@ -315,6 +317,20 @@ _sig(hip, "rtu_multi_update_meshes", _I, _P, _P, ctypes.POINTER(ctypes.c_uint32)
 _sig(hip, "rtu_debug_mesh_update_timing", _I, _P, _I, ctypes.POINTER(ctypes.c_float))
 _sig(hip, "rtu_debug_context_mesh", _I, _P, ctypes.c_uint32, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
 _sig(hip, "rtu_debug_host_mesh", _I, _P, _P, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
+
+
+RTU_MESH_EDIT_RECOMPUTE_NORMALS = 1
+
+
+class RtuMeshDeviceEdit(ctypes.Structure):
+    _fields_ = [("mesh", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("d_v", ctypes.c_void_p), ("d_vn", ctypes.c_void_p)]
+
+
+_sig(hip, "rtu_update_meshes_device", _I, _P, _P, _P, _I, _P)
+_sig(hip, "rtu_context_mesh_shape", _I, _P, ctypes.c_uint32, ctypes.POINTER(RtuMesh))
+_sig(hip, "rtu_debug_host_ref_build", _I, _P, _P, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t))
+_sig(hip, "rtu_debug_partition_rule", _I, _P, ctypes.c_uint32, _P)
+_sig(hip, "rtu_debug_mesh_update_device_timing", _I, _P, ctypes.POINTER(ctypes.c_float))
 
 # ray queries (include/rtu_render.h RtuRay / RtuRayHit): numpy layouts are built where numpy is imported (ray_dtype / hit_dtype)
 RTU_RAY_HIT, RTU_RAY_FRONT, RTU_RAY_INVALID = 1, 2, 4
@@ -1507,6 +1523,49 @@ def host_mesh(uploaded, mesh, now=None):
     return _mesh_dump(lambda which, out, cap, n: hip.rtu_debug_host_mesh(up, nw, which, out, cap, n), "rtu_debug_host_mesh")
 
 
+def host_ref_build(uploaded, mesh, v=None):
+    """Pure host code (rtu_debug_host_ref_build): the host form of the device builder of rtu_update_meshes_device on the connectivity
+    of mesh `mesh` of `uploaded` with the vertices v [nv, 3] (None: its own). A dict: ref_bvh [nodes, 8] uint32 words, ref_elements,
+    vn (the recomputed normals; only where the mesh has one normal per vertex), bmin, bmax, scale, n_bvh_nodes, any_empty_box,
+    bvh_depth. No depth bound."""
+    import numpy as np
+    m = uploaded.mesh(mesh)
+    up = uploaded.desc.meshes + mesh * ctypes.sizeof(RtuMesh)
+    vv = None
+    if v is not None:
+        vv = np.ascontiguousarray(v, np.float32)
+        if vv.size != 3 * m.nv:
+            raise RtuError(RTU_ERR_ARG, "host_ref_build: v is not [nv, 3]")
+    out = {}
+    arrays = {"ref_bvh": (4, "uint32", (8,)), "ref_elements": (5, "uint32", ()), "header": (8, "uint32", ())}
+    if m.nvn == m.nv:
+        arrays["vn"] = (7, "float32", (3,))
+    for name, (which, dtype, tail) in arrays.items():
+        n = ctypes.c_size_t(0)
+        hip.rtu_debug_host_ref_build(up, vv.ctypes.data if vv is not None else None, which, None, 0, ctypes.byref(n))
+        buf = np.empty(n.value // 4, dtype)
+        rc = hip.rtu_debug_host_ref_build(up, vv.ctypes.data if vv is not None else None, which, buf.ctypes.data, buf.nbytes, ctypes.byref(n))
+        if rc != RTU_OK:
+            raise RtuError(rc, "rtu_debug_host_ref_build: %s" % name)
+        out[name] = buf.reshape((-1,) + tail) if tail else buf
+    h = out.pop("header")
+    out["bmin"], out["bmax"], out["scale"] = h[0:3].view(np.float32), h[3:6].view(np.float32), h[6:7].view(np.float32)[0]
+    out["n_bvh_nodes"], out["any_empty_box"], out["bvh_depth"] = int(h[7]), int(h[8]), int(h[9])
+    return out
+
+
+def partition_rule(keep):
+    """Pure host code (rtu_debug_partition_rule): the closed form of the builder's partition for the keep flags `keep`; out[i] is the
+    position whose element ends at position i."""
+    import numpy as np
+    k = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+    out = np.full(k.size, 0xFFFFFFFF, np.uint32)
+    rc = hip.rtu_debug_partition_rule(k.ctypes.data if k.size else None, k.size, out.ctypes.data if k.size else None)
+    if rc != RTU_OK:
+        raise RtuError(rc, "rtu_debug_partition_rule")
+    return out
+
+
 def scene_shape_diff(a, b):
     """Pure host code: None when scene b has the shape of scene a (rtu_update_scene would take b after a), else the first difference."""
     buf = ctypes.create_string_buffer(256)
@@ -2115,6 +2174,27 @@ class Context:
         connectivity); the fast trees are refitted on the GPU."""
         ids = (ctypes.c_uint32 * len(meshes))(*meshes)
         self._check(hip.rtu_update_meshes(self._h, scene.desc_ptr, ids, len(meshes)))
+
+    def update_meshes_device(self, scene, edits, stream=None):
+        """rtu_update_meshes_device: update(scene), and the listed meshes take new vertices from DEVICE memory; the reference tree is
+        rebuilt on the GPU. edits: {mesh: (d_v_ptr, d_vn_ptr or None, recompute_normals)} — raw device pointers (a torch tensor hands
+        over .data_ptr()); stream: the stream the vertices were produced on (None: the default stream)."""
+        arr = (RtuMeshDeviceEdit * max(len(edits), 1))()
+        for i, (mesh, (d_v, d_vn, recompute)) in enumerate(edits.items()):
+            arr[i].mesh, arr[i].flags, arr[i].d_v, arr[i].d_vn = mesh, RTU_MESH_EDIT_RECOMPUTE_NORMALS if recompute else 0, d_v, d_vn
+        self._check(hip.rtu_update_meshes_device(self._h, scene.desc_ptr, arr, len(edits), stream))
+
+    def mesh_shape(self, mesh):
+        """rtu_context_mesh_shape: the header of mesh `mesh` as the context remembers it now (an RtuMesh with NULL arrays)."""
+        h = RtuMesh()
+        self._check(hip.rtu_context_mesh_shape(self._h, mesh, ctypes.byref(h)))
+        return h
+
+    def mesh_update_device_timing(self):
+        """The ms update_meshes_device spent per phase since the previous call (enabled by mesh_update_timing())."""
+        o = (ctypes.c_float * 4)()
+        self._check(hip.rtu_debug_mesh_update_device_timing(self._h, o))
+        return dict(zip(("build", "copies", "records_refit", "placement"), list(o)))
 
     def mesh_arrays(self, mesh):
         """What the context holds for mesh `mesh` now, copied back from the GPU: the dict of host_mesh()."""

@@ -7,6 +7,7 @@
 #include "rtu_devbuf.h"
 #include "rtu_device.h"
 #include "rtu_lightlist.h"
+#include "rtu_ref_build.h"
 #include "rtu_temporal.h"
 
 #include <array>
@@ -61,6 +62,13 @@ struct RtuContext {
     bool  mu_timing = false;                 // rtu_debug_mesh_update_timing: HIP events around the phases of rtu_update_meshes
     float mu_ms[4] = {};                     // copies, records, refit, placement: summed since the last read
     hipEvent_t mu_ev[5] = {};
+    // rtu_update_meshes_device: the device builder of the `ref` tree (rtu_ref_build.hip; created on first use), the event that orders
+    // its reads after the caller's stream, per mesh whether fn == f as uploaded (-1: not asked yet), and the phase times
+    RefBuilder* rb = nullptr;
+    hipEvent_t  mud_wait = nullptr;
+    std::vector<int> fn_is_f;
+    float mud_ms[4] = {};                    // build, copies, records and refit, placement: summed since the last read
+    hipEvent_t mud_ev[5] = {};
     DevScene dscene{};
     uint32_t bvh_stack_needed = 1;
 

@@ -1121,6 +1121,7 @@ void rtu_destroy_context(RtuContext* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     ll_builder_destroy(ctx->llb);
+    rb_destroy(ctx->rb);
     for (RtuProgressive* p : ctx->sessions) progressive_release(p);  // the handles stay valid for rtu_progressive_free
     for (RtuTemporal* t : ctx->temporals) temporal_release(t);       // ... and for rtu_temporal_free
     // the buffers go with the context (DevBuf); its events and streams after them
@@ -1128,6 +1129,8 @@ void rtu_destroy_context(RtuContext* ctx) {
     events.insert(events.end(), std::begin(ctx->cam_ev), std::end(ctx->cam_ev));
     events.insert(events.end(), std::begin(ctx->probe_ev), std::end(ctx->probe_ev));
     events.insert(events.end(), std::begin(ctx->mu_ev), std::end(ctx->mu_ev));
+    events.insert(events.end(), std::begin(ctx->mud_ev), std::end(ctx->mud_ev));
+    events.push_back(ctx->mud_wait);
     events.insert(events.end(), std::begin(ctx->sn_ev), std::end(ctx->sn_ev));
     const hipStream_t streams[] = {ctx->aux_stream, ctx->stream};
     delete ctx;
@@ -1596,6 +1599,8 @@ int rtu_upload_scene(RtuContext* ctx, const RtuSceneDesc* s) {
     ctx->shape_maps = s->material_maps != nullptr;
     ctx->fast_elements = std::move(fast_elements);
     ctx->refit = std::move(refit);
+    ctx->fn_is_f.assign(s->n_meshes, -1);
+    rb_forget_meshes(ctx->rb);
     ctx->dmeshes = meshes;
     ctx->dscene = ds;
     if ((rc = place_scene(ctx, s, false)) != RTU_OK) return rc;
@@ -1707,6 +1712,253 @@ int rtu_debug_mesh_update_timing(RtuContext* ctx, int on, float* ms_out4) {
     if (ms_out4) memcpy(ms_out4, ctx->mu_ms, sizeof ctx->mu_ms);
     memset(ctx->mu_ms, 0, sizeof ctx->mu_ms);
     ctx->mu_timing = on != 0;
+    return RTU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int dump_out(RtuContext* ctx, size_t bytes, void* out, size_t capacity, size_t* bytes_out);  // (below, with the mesh dumps)
+
+// The writing half of rtu_update_meshes_device, after every check has passed and every tree is built and validated in the builder's
+// scratch: what write_meshes does, with device-to-device copies in place of the uploads. res[i]: the header of edit i's build.
+int write_meshes_device(RtuContext* ctx, const RtuMeshDeviceEdit* edits, int n_edits, const std::vector<RbResult>& res, const std::vector<RtuMesh>& new_shape) {
+    hipStream_t st = ctx->stream;
+    const bool timing = ctx->mu_timing;
+    if (ctx->keep_prev) {  // as in write_meshes: the buffers change places before anything is copied
+        ctx->prev_gen.resize(ctx->dmeshes.size());
+        for (RtuContext::PrevGen& g : ctx->prev_gen) g.valid = false;
+        for (int i = 0; i < n_edits; i++) {
+            const uint32_t id = edits[i].mesh;
+            RtuContext::PrevGen& g = ctx->prev_gen[id];
+            DevBuf<char>&v = ctx->scene_allocs[ctx->refit[id].v_alloc], &vn = ctx->scene_allocs[ctx->refit[id].vn_alloc];
+            RTU_HIP(ctx, g.v.grow(v.size()));
+            RTU_HIP(ctx, g.vn.grow(vn.size()));
+            std::swap(g.v, v);
+            std::swap(g.vn, vn);
+            g.valid = true;
+            ctx->dmeshes[id].v = reinterpret_cast<const float*>(v.get());
+            ctx->dmeshes[id].vn = reinterpret_cast<const float*>(vn.get());
+        }
+    }
+    ctx->df_dirty = true;
+    for (int i = 0; i < n_edits; i++) {
+        const uint32_t id = edits[i].mesh;
+        const RtuMesh& h = new_shape[id];
+        const RbResult& r = res[(size_t)i];
+        DevMesh& d = ctx->dmeshes[id];
+        // the tree's buffer takes the largest tree these faces can have, once: later updates of the mesh allocate nothing
+        DevBuf<char>& tree_buf = ctx->scene_allocs[ctx->refit[id].ref_bvh_alloc];
+        RTU_HIP(ctx, tree_buf.grow(sizeof(RtuBvhNode) * 2 * (size_t)h.nf));
+        d.ref.bvh = reinterpret_cast<const float4*>(tree_buf.get());
+        RTU_HIP(ctx, hipMemcpyAsync(tree_buf.get(), rb_tree(ctx->rb, (uint32_t)i), sizeof(RtuBvhNode) * (size_t)r.n_bvh_nodes, hipMemcpyDeviceToDevice, st));
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(d.ref.elements), rb_elements(ctx->rb, (uint32_t)i), sizeof(uint32_t) * (size_t)h.n_elements, hipMemcpyDeviceToDevice, st));
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<float*>(d.v), edits[i].d_v, sizeof(float) * 3 * (size_t)h.nv, hipMemcpyDeviceToDevice, st));
+        const void* vn = edits[i].d_vn;
+        if (edits[i].flags & RTU_MESH_EDIT_RECOMPUTE_NORMALS) vn = rb_normals(ctx->rb, (uint32_t)i);
+        else if (!vn && ctx->keep_prev) vn = ctx->prev_gen[id].vn.get();  // the normals stay: they are in the buffer that was swapped out
+        if (vn) RTU_HIP(ctx, hipMemcpyAsync(const_cast<float*>(d.vn), vn, sizeof(float) * 3 * (size_t)h.nvn, hipMemcpyDeviceToDevice, st));
+        d.scale = 0.0f;
+        for (int k = 0; k < 3; k++) d.scale = fmaxf(d.scale, fmaxf(fabsf(h.bound_min[k]), fabsf(h.bound_max[k])));
+        memcpy(d.bmin, h.bound_min, sizeof d.bmin);
+        memcpy(d.bmax, h.bound_max, sizeof d.bmax);
+        d.n_bvh_nodes = h.n_bvh_nodes;
+        d.any_empty_box = r.any_empty_box;
+        RTU_HIP(ctx, hipMemcpyAsync(const_cast<DevMesh*>(ctx->dscene.meshes) + id, &d, sizeof d, hipMemcpyHostToDevice, st));
+    }
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mud_ev[2], st));
+    for (int i = 0; i < n_edits; i++) {
+        const uint32_t id = edits[i].mesh;
+        const DevMesh& d = ctx->dmeshes[id];
+        const RtuContext::MeshRefit& r = ctx->refit[id];
+        RTU_HIP(ctx, mu_tri_records(st, d.f, d.v, d.ref.elements, d.n_elements, const_cast<float4*>(d.ref.tri)));
+        RTU_HIP(ctx, mu_tri_records(st, d.f, d.v, d.fast.elements, d.n_elements, const_cast<float4*>(d.fast.tri)));
+        RTU_HIP(ctx, mu_refit(st, 4, const_cast<float4*>(d.bvh4), ctx->mesh_info[id].nodes4, r.lvl4.data(), (uint32_t)r.lvl4.size() - 1u, d.f, d.v,
+                              d.fast.elements, d.n_elements));
+        RTU_HIP(ctx, mu_refit(st, 8, const_cast<float4*>(d.bvh8), ctx->mesh_info[id].nodes8, r.lvl8.data(), (uint32_t)r.lvl8.size() - 1u, d.f, d.v,
+                              d.fast.elements, d.n_elements));
+    }
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mud_ev[3], st));
+    RTU_HIP(ctx, hipStreamSynchronize(st));
+    ctx->shape_meshes = new_shape;
+    uint32_t stack_needed = 1;  // as write_meshes computes it
+    for (size_t mi = 0; mi < ctx->shape_meshes.size(); mi++) {
+        const RtuContext::MeshInfo& info = ctx->mesh_info[mi];
+        stack_needed = std::max(stack_needed, std::min<uint32_t>(info.stack4, RTU_MAX_BVH_STACK));
+        stack_needed = std::max(stack_needed, info.sah_depth);
+        stack_needed = std::max(stack_needed, ctx->shape_meshes[mi].bvh_depth);
+    }
+    ctx->bvh_stack_needed = stack_needed;
+    return RTU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtu_update_meshes_device(RtuContext* ctx, const RtuSceneDesc* s, const RtuMeshDeviceEdit* edits, int n_edits, void* hip_stream) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (n_edits == 0) return rtu_update_scene(ctx, s);
+    if (n_edits < 0 || !edits) return fail(ctx, RTU_ERR_ARG, "edits is NULL or n_edits negative");
+    // everything that can be checked before the build is: a refused update leaves the context as it was
+    int rc = shape_args(ctx, s);
+    if (rc != RTU_OK) return rc;
+    const size_t nm = ctx->shape_meshes.size();
+    std::vector<char> listed(nm, 0);
+    for (int i = 0; i < n_edits; i++) {
+        const RtuMeshDeviceEdit& e = edits[i];
+        if (e.mesh >= nm) return fail(ctx, RTU_ERR_ARG, "mesh id %u out of range (%zu meshes)", e.mesh, nm);
+        if (listed[e.mesh]) return fail(ctx, RTU_ERR_ARG, "mesh id %u listed twice", e.mesh);
+        listed[e.mesh] = 1;
+        if (!e.d_v) return fail(ctx, RTU_ERR_ARG, "mesh %u: d_v is NULL", e.mesh);
+        if (e.flags & ~RTU_MESH_EDIT_RECOMPUTE_NORMALS) return fail(ctx, RTU_ERR_ARG, "mesh %u: unknown flags 0x%x", e.mesh, e.flags);
+        if ((e.flags & RTU_MESH_EDIT_RECOMPUTE_NORMALS) && e.d_vn) return fail(ctx, RTU_ERR_ARG, "mesh %u: d_vn given with RECOMPUTE_NORMALS", e.mesh);
+    }
+    // the shape rule of rtu_update_scene; of a LISTED mesh the tree's size is not compared (the host scene is stale by design)
+    std::vector<RtuMesh> want = ctx->shape_meshes;
+    if (s->n_meshes == nm)
+        for (size_t id = 0; id < nm; id++)
+            if (listed[id]) want[id].n_bvh_nodes = s->meshes[id].n_bvh_nodes;
+    RtuSceneDesc up = shape_desc(ctx);
+    up.meshes = want.data();
+    const std::string diff = shape_diff(&up, s);
+    if (!diff.empty()) return fail(ctx, RTU_ERR_SCENE_SHAPE, "not the uploaded scene's shape: %s", diff.c_str());
+    for (int i = 0; i < n_edits; i++) {
+        const uint32_t id = edits[i].mesh;
+        const RtuMesh& h = ctx->shape_meshes[id];
+        if (s->meshes[id].n_elements != h.n_elements)
+            return fail(ctx, RTU_ERR_SCENE_SHAPE, "not the uploaded scene's shape: mesh %u: n_elements differs", id);
+        if (h.nf == 0 || h.n_elements != h.nf) return fail(ctx, RTU_ERR_ARG, "mesh %u: empty", id);
+        if (2 * (uint64_t)h.nf >= (1u << 28)) return fail(ctx, RTU_ERR_UNSUPPORTED, "mesh %u: more than 2^28 nodes/elements", id);
+        if ((edits[i].flags & RTU_MESH_EDIT_RECOMPUTE_NORMALS) && h.nvn != h.nv)
+            return fail(ctx, RTU_ERR_ARG, "mesh %u carries normals of its own (not one per vertex with fn == f)", id);
+    }
+    RTU_HIP(ctx, hipSetDevice(ctx->device));
+    RTU_HIP(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers rewritten below
+    if (ctx->aux_stream) RTU_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
+    if (!ctx->rb) ctx->rb = rb_create();
+    hipStream_t st = ctx->stream;
+    for (int i = 0; i < n_edits; i++) {  // fn == f as uploaded: asked of the device copies once per upload
+        const uint32_t id = edits[i].mesh;
+        if (!(edits[i].flags & RTU_MESH_EDIT_RECOMPUTE_NORMALS)) continue;
+        if (ctx->fn_is_f[id] < 0) {
+            bool differ = true;
+            RTU_HIP(ctx, rb_compare_device(ctx->rb, st, ctx->dmeshes[id].f, ctx->dmeshes[id].fn, 3 * ctx->shape_meshes[id].nf, differ));
+            ctx->fn_is_f[id] = differ ? 0 : 1;
+        }
+        if (!ctx->fn_is_f[id]) return fail(ctx, RTU_ERR_ARG, "mesh %u carries normals of its own (not one per vertex with fn == f)", id);
+    }
+    // the caller's vertices: this call's reads wait for the work of the stream they were produced on, nothing else does
+    if ((hipStream_t)hip_stream != st) {
+        if (!ctx->mud_wait) RTU_HIP(ctx, hipEventCreateWithFlags(&ctx->mud_wait, hipEventDisableTiming));
+        RTU_HIP(ctx, hipEventRecord(ctx->mud_wait, (hipStream_t)hip_stream));
+        RTU_HIP(ctx, hipStreamWaitEvent(st, ctx->mud_wait, 0));
+    }
+    const bool timing = ctx->mu_timing;
+    if (timing && !ctx->mud_ev[0])
+        for (hipEvent_t& e : ctx->mud_ev) RTU_HIP(ctx, hipEventCreate(&e));
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mud_ev[0], st));
+    // the trees, into the builder's scratch (one output slot per edit); then their headers are validated
+    std::vector<RbResult> res((size_t)n_edits);
+    std::vector<RtuMesh> new_shape = ctx->shape_meshes;
+    for (int i = 0; i < n_edits; i++) {
+        const uint32_t id = edits[i].mesh;
+        const DevMesh& d = ctx->dmeshes[id];
+        RtuMesh& h = new_shape[id];
+        const float* d_v = static_cast<const float*>(edits[i].d_v);
+        if (edits[i].flags & RTU_MESH_EDIT_RECOMPUTE_NORMALS) RTU_HIP(ctx, rb_normals_device(ctx->rb, st, (uint32_t)i, id, d.f, d_v, h.nf, h.nv));
+        RbResult& r = res[(size_t)i];
+        RTU_HIP(ctx, rb_build_device(ctx->rb, st, (uint32_t)i, d.f, d_v, h.nf, h.nv, RTU_MAX_BVH_STACK, r));
+        if (r.open || r.bvh_depth > RTU_MAX_BVH_STACK)
+            return fail(ctx, RTU_ERR_UNSUPPORTED, "mesh %u: BVH depth > %d (%u nodes of level %u are inner)", id, RTU_MAX_BVH_STACK, r.open, r.bvh_depth);
+        if (r.n_bvh_nodes >= (1u << 28)) return fail(ctx, RTU_ERR_UNSUPPORTED, "mesh %u: more than 2^28 nodes/elements", id);
+        h.n_bvh_nodes = r.n_bvh_nodes;
+        h.bvh_depth = r.bvh_depth;
+        memcpy(h.bound_min, r.bmin, sizeof h.bound_min);
+        memcpy(h.bound_max, r.bmax, sizeof h.bound_max);
+    }
+    RtuSceneDesc placed = *s;  // headers as the context will remember them; the arrays stay NULL
+    placed.meshes = new_shape.data();
+    placed.textures = ctx->shape_textures.data();
+    if ((rc = validate(ctx, &placed, true)) != RTU_OK) return rc;
+    if (timing) RTU_HIP(ctx, hipEventRecord(ctx->mud_ev[1], st));
+    if (!ctx->llb) ctx->llb = ll_builder_create();
+    ctx->scene_gen++;
+    if ((rc = write_meshes_device(ctx, edits, n_edits, res, new_shape)) == RTU_OK) {
+        placed.meshes = ctx->shape_meshes.data();
+        rc = place_scene(ctx, &placed, true);
+    }
+    if (rc != RTU_OK) {
+        free_scene(ctx);  // half written: nothing to render from
+        return rc;
+    }
+    if (timing) {
+        RTU_HIP(ctx, hipEventRecord(ctx->mud_ev[4], st));
+        RTU_HIP(ctx, hipEventSynchronize(ctx->mud_ev[4]));
+        for (int k = 0; k < 4; k++) {
+            float ms = 0;
+            RTU_HIP(ctx, hipEventElapsedTime(&ms, ctx->mud_ev[k], ctx->mud_ev[k + 1]));
+            ctx->mud_ms[k] += ms;
+        }
+    }
+    return RTU_OK;
+}
+
+int rtu_context_mesh_shape(RtuContext* ctx, uint32_t mesh, RtuMesh* header_out) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (!ctx->has_scene) return fail(ctx, RTU_ERR_NO_SCENE, "no scene uploaded");
+    if (mesh >= ctx->shape_meshes.size()) return fail(ctx, RTU_ERR_ARG, "no mesh %u", mesh);
+    if (!header_out) return fail(ctx, RTU_ERR_ARG, "header_out is NULL");
+    *header_out = ctx->shape_meshes[mesh];
+    return RTU_OK;
+}
+
+int rtu_debug_mesh_update_device_timing(RtuContext* ctx, float* ms_out4) {
+    if (!ctx) return RTU_ERR_ARG;
+    if (ms_out4) memcpy(ms_out4, ctx->mud_ms, sizeof ctx->mud_ms);
+    memset(ctx->mud_ms, 0, sizeof ctx->mud_ms);
+    return RTU_OK;
+}
+
+int rtu_debug_host_ref_build(const RtuMesh* m, const float* v, int which, void* out, size_t capacity_bytes, size_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (!m || !m->f || !m->v || m->nf == 0 || m->nv == 0) return RTU_ERR_ARG;
+    for (uint32_t i = 0; i < m->nf * 3; i++)
+        if (m->f[i] >= m->nv) return RTU_ERR_ARG;
+    if (!v) v = m->v;
+    std::vector<RtuBvhNode> tree;
+    std::vector<uint32_t> elements;
+    std::vector<float> vn;
+    RbResult r;
+    RtuRefBuildHeader hd;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    if (which == RTU_MESH_VN) {
+        if (m->nvn != m->nv) return RTU_ERR_ARG;
+        rb_normals_host(m->f, v, m->nf, m->nv, vn);
+        src = vn.data(); bytes = sizeof(float) * vn.size();
+    } else if (which == RTU_MESH_REF_BVH || which == RTU_MESH_REF_ELEMENTS || which == RTU_MESH_HEADER) {
+        rb_build_host(m->f, v, m->nf, m->nv, 0, tree, elements, r);
+        if (which == RTU_MESH_REF_BVH) { src = tree.data(); bytes = sizeof(RtuBvhNode) * tree.size(); }
+        else if (which == RTU_MESH_REF_ELEMENTS) { src = elements.data(); bytes = sizeof(uint32_t) * elements.size(); }
+        else {
+            memcpy(hd.bmin, r.bmin, sizeof hd.bmin); memcpy(hd.bmax, r.bmax, sizeof hd.bmax);
+            hd.scale = 0.0f;
+            for (int k = 0; k < 3; k++) hd.scale = fmaxf(hd.scale, fmaxf(fabsf(r.bmin[k]), fabsf(r.bmax[k])));
+            hd.n_bvh_nodes = r.n_bvh_nodes; hd.any_empty_box = r.any_empty_box; hd.bvh_depth = r.bvh_depth;
+            src = &hd; bytes = sizeof hd;
+        }
+    } else return RTU_ERR_ARG;
+    int rc = dump_out(nullptr, bytes, out, capacity_bytes, bytes_out);
+    if (rc == RTU_OK && bytes) memcpy(out, src, bytes);
+    return rc;
+}
+
+int rtu_debug_partition_rule(const uint8_t* keep, uint32_t n, uint32_t* perm_out) {
+    if (n && (!keep || !perm_out)) return RTU_ERR_ARG;
+    rb_partition_host(keep, n, perm_out);
     return RTU_OK;
 }
 
