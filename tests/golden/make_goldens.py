@@ -24,6 +24,10 @@ tests/test_oracle.py) to tests/golden/SceneFiles/: every scene XML and the meshe
 for the PNG textures only the filter type of each row and which texture of a golden blob holds their pixels
 (textures.json), from which the tests write them back. They are the inputs of the fixtures above, so the loader is checked without the reference tree.
 
+`make_goldens.py ref_trees` writes ref_trees/<name>_<n|c>.rtus.gz: the awkward meshes of tests/test_ref_build_host.py
+(reference_meshes()) flattened by ref_render --scene-only, with vn lines (`n`) and without them (`c`: the reference's ComputeNormals).
+They are loaded only, never rendered by the reference, so they need no `vt` lines (next paragraph).
+
 An .obj that goes through the reference needs `vt` lines and `v/vt/vn` faces: TriObj::IntersectRay reads the texture
 coordinates of every accepted hit unconditionally (objFunctions.cpp:320) and crashes on a mesh without them. The oracle
 and the device render such a mesh (uvw = 0); the reference cannot, so the scenes under tests/scenes carry `vt`.
@@ -195,8 +199,39 @@ def make_bounces(only):
             shutil.rmtree(src)
 
 
+def make_ref_trees():
+    """ref_trees/<name>_<n|c>.rtus.gz: the meshes of tests/test_ref_build_host.py reference_meshes() as the compiled reference loads them
+    (ref_render --scene-only, 64 x 48) — its own cyBVHTriMesh tree, element order, bounds and, for the `c` files (an .obj without vn
+    lines), its ComputeNormals. `n`: the .obj carries vn lines. The .obj and .xml are written as the tests write them."""
+    import pathlib
+    import tempfile
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_ref_build_host import reference_meshes, write_obj_scene
+    exe = os.path.join(REPO, "oracle", "_ref", "ref_render")
+    dst = os.path.join(HERE, "ref_trees")
+    os.makedirs(dst, exist_ok=True)
+    total = 0
+    for name, (v, f) in reference_meshes().items():
+        for normals in (True, False):
+            with tempfile.TemporaryDirectory() as tmp:
+                xml = write_obj_scene(pathlib.Path(tmp), name, v, f, normals)
+                subprocess.check_call([exe, str(xml), "64", "48", tmp, "1", "--scene-only"], stdout=subprocess.DEVNULL)
+                out = os.path.join(dst, "%s_%s.rtus.gz" % (name, "n" if normals else "c"))
+                with open(os.path.join(tmp, "scene.rtus"), "rb") as g, gzip.GzipFile(out, "wb", mtime=0) as z:
+                    z.write(g.read())
+            total += os.path.getsize(out)
+            print(os.path.basename(out), os.path.getsize(out), "bytes")
+    print("ref_trees", 2 * len(reference_meshes()), "blobs,", total, "bytes")
+
+
 def main():
     only = set(sys.argv[1:])
+    if "ref_trees" in only:
+        make_ref_trees()
+        only.discard("ref_trees")
+        if not only:
+            return
     bounce_tags = {a.split(":", 1)[1] for a in only if a.startswith("bounces:")}
     if "bounces" in only or bounce_tags:
         make_bounces(bounce_tags)

@@ -5,7 +5,8 @@ rtu_update_meshes_device, run in loops (rtu_debug_host_ref_build, rtu_debug_part
   * tree, element order, depth, node count, mesh box and any_empty_box against rtu_scene_set_mesh_vertices + renumber_bfs, bit for bit;
   * normals by vertex adjacency against ComputeNormals.
 
-The small meshes are defined here once (test_gpu_mesh_update_device.py imports them)."""
+The small meshes are defined here once (test_gpu_mesh_update_device.py imports them), and so are the meshes of tests/golden/ref_trees
+(reference_meshes(); test_ref_trees_host.py and test_gpu_ref_trees.py hold them to trees the compiled reference built)."""
 import ctypes
 import itertools
 
@@ -23,9 +24,9 @@ XML = """<xml><scene>
   <width value="64"/><height value="48"/></camera></xml>"""
 
 
-def obj_scene(pkg, dst, name, v, f, normals=True):
-    """A scene of one mesh: vertices v [nv, 3], faces f [nf, 3] (0-based); normals: the file carries one vn per vertex (else the
-    loader computes them: ComputeNormals)."""
+def write_obj_scene(dst, name, v, f, normals=True):
+    """The files of a scene of one mesh: vertices v [nv, 3], faces f [nf, 3] (0-based); normals: the file carries one vn per vertex
+    (else the loader computes them: ComputeNormals). Returns the path of the scene XML."""
     dst.mkdir(parents=True, exist_ok=True)
     obj = dst / (name + ".obj")
     with open(str(obj), "w") as g:
@@ -38,7 +39,12 @@ def obj_scene(pkg, dst, name, v, f, normals=True):
             g.write("f " + " ".join(("%d//%d" % (i + 1, i + 1)) if normals else str(i + 1) for i in t) + "\n")
     xml = dst / (name + ".xml")
     xml.write_text(XML.format(o=obj))
-    return pkg.Scene.from_xml(str(xml))
+    return xml
+
+
+def obj_scene(pkg, dst, name, v, f, normals=True):
+    """write_obj_scene's files, loaded."""
+    return pkg.Scene.from_xml(str(write_obj_scene(dst, name, v, f, normals)))
 
 
 def soup(n, seed):
@@ -79,6 +85,54 @@ def small_meshes():
         out["soup%d" % n] = soup(n, n)
     for n in range(5, 9):
         out["coincident%d" % n] = coincident(n)
+    return out
+
+
+def mean_on_centre():
+    """Nine triangles with centres at k = -4 ... 4 on x: the mean of the centres, 0, is exactly the middle one's."""
+    v = []
+    for k in range(-4, 5):
+        v += [[k - 0.25, 0, 0], [k + 0.25, 0, 0], [k, 0.5, 0]]
+    return np.array(v, np.float32), np.arange(27).reshape(9, 3)
+
+
+def grid(n=12):
+    """An n x n lattice of vertices at integer (x, y, 0), each quad split in two: 2 (n - 1)^2 faces with many equal centre coordinates."""
+    v = np.array([[x, y, 0] for y in range(n) for x in range(n)], np.float32)
+    f = []
+    for y in range(n - 1):
+        for x in range(n - 1):
+            a = y * n + x
+            f += [[a, a + 1, a + n], [a + 1, a + n + 1, a + n]]
+    return v, np.array(f)
+
+
+def reference_meshes():
+    """name -> (v, f): the meshes whose trees tests/golden/ref_trees holds as the compiled reference built them (make_goldens.py
+    ref_trees): the small meshes, rows that peel one element per level, degenerate meshes and coordinates at the edges of binary32."""
+    out = dict(small_meshes())
+    out["deep60"] = deep_row()
+    out["deep40"] = deep_row(40)
+    out["flat60"] = flat_row()
+    v, f = soup(40, 7)
+    out["collapse"] = (np.full_like(v, 1.25), f)
+    flat = v.copy()
+    flat[:, 2] = 0
+    out["flatten"] = (flat, f)
+    z = v.copy()
+    z[1::2, 0], z[0::2, 0] = 0.0, -0.0
+    out["signed_zero"] = (z, f)
+    with np.errstate(over="ignore"):
+        out["huge"] = (v * np.float32(1e38), f)
+    out["denormal"] = (v * np.float32(1e-40), f)
+    out["mean_on_centre"] = mean_on_centre()
+    for name, x in (("nan", np.nan), ("inf", np.inf)):
+        w = v.copy()
+        w[5, 1] = x
+        out[name] = (w, f)
+    out["grid"] = grid()
+    for v, _ in out.values():
+        assert v.dtype == np.float32
     return out
 
 
