@@ -1,13 +1,16 @@
-// rtu_capi.h — private to rtu_capi.hip and the files split off it (rtu_capi_build.hip: the host builders of an upload), the host
-// side of the C-ABI in include/rtu_render.h: the context, and what one of those files needs of the other. Everything declared
+// rtu_capi.h — private to rtu_capi.hip and the files split off it (rtu_capi_build.hip: the host builders of an upload;
+// rtu_capi_temporal.hip: the temporal accumulators and sessions; rtu_capi_sensor.hip: sensors and adaptive sensors), the host
+// side of the C-ABI in include/rtu_render.h: the context, and what one of those files needs of another. Everything declared
 // here has C++ linkage and hidden visibility: the library exports the rtu_* entries of include/rtu_render.h and nothing of this.
-// A helper that only one file uses is not here but in that file's unnamed namespace.
+// A helper that only one file uses is not here but in that file, in an unnamed namespace or `static`.
 #ifndef RTU_CAPI_H
 #define RTU_CAPI_H
+#include "rtu_camrays.h"
 #include "rtu_devbuf.h"
 #include "rtu_device.h"
 #include "rtu_lightlist.h"
 #include "rtu_ref_build.h"
+#include "rtu_sensor.h"
 #include "rtu_temporal.h"
 
 #include <array>
@@ -17,8 +20,8 @@
 
 #pragma GCC visibility push(hidden)
 
-struct RtuProgressive;  // both defined in rtu_capi.hip
-struct RtuTemporal;
+struct RtuProgressive;  // defined in rtu_capi.hip
+struct RtuTemporal;     // defined in rtu_capi_temporal.hip
 
 struct RtuContext {
     int         device = 0;
@@ -221,6 +224,56 @@ struct HostLightList {
 // ---- internal functions that cross files, by the file that defines them (each is described there) ----
 // rtu_capi.hip
 int ensure_place(RtuContext* ctx, int slot, size_t bytes, void** out);
+int check_adaptive_desc(RtuContext* ctx, const RtuAdaptiveDesc* ad, int samples);  // frame path
+// ... its ray batches
+int shade_args(RtuContext* ctx, const void* rays, const void* out, size_t n, const RtuShadeDesc* d, bool device, RtuFrameDesc* f, bool sampled = false,
+               const void* keys = nullptr, bool paths = false);
+int paths_chain(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n);
+int shade_until_fits(RtuContext* ctx, const RtuFrameDesc& f, float4* d_out, hipStream_t stream, const float4* d_rays, const uint32_t* d_keys, uint32_t n,
+                     bool paths, const char* counters_refusal, int (*behind)(void*) = nullptr, void* behind_arg = nullptr);
+CamSample cam_sample(const RtuFrameDesc* frame, int sample);
+void h_portable_sincos(float t, float& sn, float& cs);
+
+// rtu_capi_sensor.hip
+int check_sensor(RtuContext* ctx, const RtuSensorDesc* d);
+int sensor_generate(RtuContext* ctx, const RtuSensorDesc* d, int k0, int n, float4* d_rays, uint32_t* d_keys, hipStream_t stream);
+
+// rtu_capi_temporal.hip
+void temporal_release(RtuTemporal* t);
+
+// this header: the short helpers of rtu_capi.hip's frame path (check_frame, halton, cancel_raised), queries (misaligned) and ray
+// batches (HostSinCos) that its neighbours use too, with their bodies, so that the frame path sees them as it did. check_frame is
+// `static`: an internal function is emitted behind its first caller, which keeps rtu_capi.o's code for the rtu_render_frame*
+// entries byte for byte what it was when check_frame sat in that file's unnamed namespace (NOTEBOOK 22); the temporal file has a copy.
+static inline int check_frame(RtuContext* ctx, const RtuFrameDesc* f) {
+    if (!f) return fail(ctx, RTU_ERR_ARG, "frame is NULL");
+    if (f->width <= 0 || f->height <= 0 || f->width > 65536 || f->height > 65536) return fail(ctx, RTU_ERR_ARG, "bad resolution");
+    if (f->shard_count < 1 || f->shard_rank < 0 || f->shard_rank >= f->shard_count) return fail(ctx, RTU_ERR_ARG, "bad shard");
+    if (f->max_bounce < 0 || f->max_bounce > RTU_MAX_BOUNCE) return fail(ctx, RTU_ERR_ARG, "max_bounce out of range");
+    if (f->samples < 0 || f->samples > 65536) return fail(ctx, RTU_ERR_ARG, "samples out of range");
+    if (f->gather_bounces != 0 && (f->gather_bounces != RTU_GI_BOUNCES || f->samples < 1))
+        return fail(ctx, RTU_ERR_ARG, "gather_bounces is 0 or %d (recipe P, with samples >= 1)", RTU_GI_BOUNCES);
+    if (f->collect_stats < 0 || f->collect_stats > 2) return fail(ctx, RTU_ERR_ARG, "collect_stats is 0, 1 or 2");
+    if (f->samples == 0 && ctx->has_scene && (ctx->scene_stochastic || f->dof != 0))
+        return fail(ctx, RTU_ERR_STOCHASTIC, "the scene has %s: render it with frame.samples >= 1 (recipe S)",
+                    ctx->scene_stochastic ? ctx->stochastic_what.c_str() : "depth of field");
+    return RTU_OK;
+}
+// Halton (scene.h:130-139)
+inline float halton(int index, int base) {
+    float r = 0;
+    float f = 1.0f / (float)base;
+    for (int i = index; i > 0; i /= base) {
+        r += f * (float)(i % base);
+        f /= (float)base;
+    }
+    return r;
+}
+inline bool cancel_raised(const RtuContext* ctx) { return ctx->cancel && __atomic_load_n(ctx->cancel, __ATOMIC_RELAXED) != 0; }
+inline bool misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+struct HostSinCos {
+    void operator()(float t, float& sn, float& cs) const { h_portable_sincos(t, sn, cs); }
+};
 
 // rtu_capi_build.hip
 void build_sah(const RtuMesh& m, SahTree& out);

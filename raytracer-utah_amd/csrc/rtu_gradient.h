@@ -1,5 +1,5 @@
 // rtu_gradient.h — the arithmetic of temporal gradients (include/rtu_render.h "Temporal gradients"), host + device, and the launch
-// interface of its kernels (rtu_gradient.hip), called by rtu_capi.hip:
+// interface of its kernels (rtu_gradient.hip), called by rtu_capi_temporal.hip:
 //   gr_owner       rtu_gradient_rays: the pixel a 3 x 3 stratum re-shades this frame (the ray itself is camera_sample_ray of rtu_camrays.h)
 //   gr_luminance   rtu_sample_luminance: l(c / d) of a raw sample, what the next frame's gradients are taken against
 //   gr_diff        rtu_temporal_gradient, first half: {num, den, noise, 0} of a stratum — its owner re-shaded with the previous frame's

@@ -1,6 +1,6 @@
 // rtu_gradient.hip — temporal gradients of include/rtu_render.h ("Temporal gradients"): the host forms rtu_sample_luminance and
 // rtu_temporal_gradient, which are the executable statement of the rules, and the kernels of the _device forms. Both call the same
-// functions of rtu_gradient.h. (rtu_gradient_rays, the third host form, is in rtu_capi.hip beside rtu_camera_sample_rays; the capped
+// functions of rtu_gradient.h. (rtu_gradient_rays, the third host form, is in rtu_capi_temporal.hip beside rtu_extra_sample_rays; the capped
 // accumulator is k_temporal<true, true, true> of rtu_temporal.hip.)
 //
 //   k_gradient_rays     a lane per stratum: its owner of the frame, and that pixel's ray and key of the given sample as two float4

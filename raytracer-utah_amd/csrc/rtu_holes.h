@@ -1,5 +1,5 @@
 // rtu_holes.h — the arithmetic of hole rays (include/rtu_render.h "Hole rays"), host + device, and the launch interface of its
-// kernels (rtu_holes.hip), called by rtu_capi.hip:
+// kernels (rtu_holes.hip), called by rtu_capi_temporal.hip:
 //   hl_weight   rtu_hole_allocation: 1 for a pixel that has no colour at all and a first hit, 0 for every other. The count, the scan
 //               and the cut are st_count / st_cut of rtu_steer.h with max_extra = 1.
 //   hl_fold     rtu_hole_fold: the one shaded sample of such a pixel made its history, as the moments form makes a fresh pixel's

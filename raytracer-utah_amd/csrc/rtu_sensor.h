@@ -1,5 +1,5 @@
 // rtu_sensor.h — the ray of a sensor pixel (include/rtu_render.h, "Sensors") for host and device, and the launch interface of the
-// generator and accumulator kernels (rtu_sensor.hip), called by rtu_capi.hip.
+// generator and accumulator kernels (rtu_sensor.hip), called by rtu_capi_sensor.hip.
 #ifndef RTU_SENSOR_H_INCLUDED
 #define RTU_SENSOR_H_INCLUDED
 
@@ -128,7 +128,7 @@ RTU_HD bool sensor_project(const RtuSensorDesc& d, const f3& Pm, float& fx, floa
     return true;
 }
 
-// RTU_OK or RTU_ERR_ARG: the rules of RtuSensorDesc (rtu_capi.hip), without a context
+// RTU_OK or RTU_ERR_ARG: the rules of RtuSensorDesc (rtu_capi_sensor.hip), without a context
 extern "C" int rtu_sensor_check_desc(const RtuSensorDesc* d);
 
 // ---- launch interface (rtu_sensor.hip). Every function is asynchronous on `stream` and returns a hipError_t as int. ----

@@ -1,5 +1,5 @@
 // rtu_sensor_adaptive.h — the launch interface of adaptive sensors (include/rtu_render.h, "Adaptive sensors"; rtu_sensor_adaptive.hip),
-// called by rtu_capi.hip: the rays of the pixels that still sample, and the stopping rule applied to what comes back.
+// called by rtu_capi_sensor.hip: the rays of the pixels that still sample, and the stopping rule applied to what comes back.
 #ifndef RTU_SENSOR_ADAPTIVE_H_INCLUDED
 #define RTU_SENSOR_ADAPTIVE_H_INCLUDED
 

@@ -1,5 +1,5 @@
 // rtu_sparse.h — the arithmetic of sparse sessions (include/rtu_render.h "Sparse sessions"), host + device, and the launch interface of
-// its kernels (rtu_sparse.hip), called by rtu_capi.hip:
+// its kernels (rtu_sparse.hip), called by rtu_capi_temporal.hip:
 //   sp_owner   the pixel a B x B block shades in frame k, and the class of the block (which of the four block sizes of an image it has)
 //   sp_ray     rtu_sparse_rays: that pixel's ray and key (camera_sample_ray of rtu_camrays.h) in the sample its block has reached
 //   sp_fill    rtu_sparse_fill: the colour shown at a pixel that has neither a sample nor a usable history

@@ -1,6 +1,6 @@
 // rtu_sparse.hip — sparse sessions of include/rtu_render.h ("Sparse sessions"): the host form rtu_sparse_fill, which is the executable
 // statement of the fill, and the kernels of the _device forms. Both call the same functions of rtu_sparse.h. (rtu_sparse_rays, the host
-// form of the rays, is in rtu_capi.hip beside rtu_camera_sample_rays; the sparse accumulator is k_temporal<true, true, false, true> of
+// form of the rays, is in rtu_capi_temporal.hip beside rtu_extra_sample_rays; the sparse accumulator is k_temporal<true, true, false, true> of
 // rtu_temporal.hip.)
 //
 //   k_sparse_rays   a lane per block: its owner of the frame, and that pixel's ray and key in the sample the block has reached, as two

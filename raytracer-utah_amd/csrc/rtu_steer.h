@@ -1,5 +1,5 @@
 // rtu_steer.h — the arithmetic of steered sampling (include/rtu_render.h "Steered sampling"), host + device, and the launch interface
-// of its kernels (rtu_steer.hip), called by rtu_capi.hip:
+// of its kernels (rtu_steer.hip), called by rtu_capi_temporal.hip:
 //   st_weight / st_count / st_cut   rtu_sample_allocation: a budget of extra rays spread by the variance of the accumulated mean
 //   st_extra_ray                    rtu_extra_sample_rays: extra sample j of a pixel, through camera_sample_ray of rtu_camrays.h
 //   st_refine_pixel                 rtu_temporal_refine: the extra samples of a pixel folded into its E, M and image

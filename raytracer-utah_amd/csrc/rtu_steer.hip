@@ -1,6 +1,6 @@
 // rtu_steer.hip — steered sampling of include/rtu_render.h ("Steered sampling"): the host forms rtu_sample_allocation and
 // rtu_temporal_refine, which are the executable statement of the rules, and the kernels of the three _device forms. Both call the
-// same functions of rtu_steer.h. (rtu_extra_sample_rays, the third host form, is in rtu_capi.hip beside rtu_camera_sample_rays.)
+// same functions of rtu_steer.h. (rtu_extra_sample_rays, the third host form, is in rtu_capi_temporal.hip, built on cam_sample as rtu_camera_sample_rays is.)
 //
 //   k_steer_weight   a workgroup per tile of 1024 pixels, four pixels per lane 256 apart: E, M, v and the first float4 of the RtuRayHit
 //                    in, the weight out (4 B per pixel of scratch), and the tile's sum — below 2^30 — reduced over the workgroup and

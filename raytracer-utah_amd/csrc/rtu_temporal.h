@@ -1,6 +1,6 @@
 // rtu_temporal.h — the arithmetic of the temporal accumulator (include/rtu_render.h "Temporal accumulation", "... across scene
 // updates" and the moments of "Variance-guided filtering"), host + device, and the launch interface of its kernels (rtu_temporal.hip),
-// called by rtu_capi.hip. The three forms — rtu_temporal_accumulate, _motion and _moments, each with its _device form — are the
+// called by rtu_capi_temporal.hip. The three forms — rtu_temporal_accumulate, _motion and _moments, each with its _device form — are the
 // instantiations of one function, tp_pixel<MOVING, MOMENTS>; rtu_temporal_accumulate_gradient ("Temporal gradients") is a fourth,
 // tp_pixel<true, true, true>, and rtu_temporal_accumulate_sparse ("Sparse sessions") a fifth, tp_pixel<true, true, false, true>.
 // rtu_temporal_accumulate_sensor and _sensor_moments ("Temporal accumulation for sensors") are tp_pixel<false, MOMENTS> with another

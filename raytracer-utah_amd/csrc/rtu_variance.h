@@ -1,5 +1,5 @@
 // rtu_variance.h — the arithmetic of the variance-guided preview filter (include/rtu_render.h "Variance-guided filtering"), host +
-// device, and the launch interface of its kernels (rtu_variance.hip), called by rtu_capi.hip:
+// device, and the launch interface of its kernels (rtu_variance.hip), called by rtu_capi_temporal.hip:
 //   vr_variance_pixel   rtu_variance: the variance of the accumulated mean out of E.n and M
 //   vd_*                rtu_denoise_variance: the a-trous passes of rtu_denoise.h with a per-pixel colour edge-stop
 // The moments themselves are accumulated by tp_pixel<true, true> of rtu_temporal.h (a MOMENTS HISTORY, vr_lum).
