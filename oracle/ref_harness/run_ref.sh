@@ -4,6 +4,7 @@
 # macOS paths: a path-remapped COPY is written under oracle/_ref/.
 #   usage: run_ref.sh <scene path relative to SceneFiles> <W> <H> <tag> [threads] [spp] [paths]   (spp: recipe S; "paths": recipe P)
 #   BOUNCES=N in the environment: the bounceCount of the root Shade() calls (--bounces N of ref_render; 5 without it)
+#   EXTRA_ASSETS="file ..." in the environment: files copied beside a repository scene (a texture that another scene directory holds)
 set -e
 REF=${REF:-/root/reference}
 HERE=$(cd "$(dirname "$0")/../.." && pwd)
@@ -15,6 +16,7 @@ case "$1" in
       for f in "$SRC"/*; do
         case "$f" in *.xml|*.mtl|*.obj) sed "s#@DIR@#$OUT/scene_dir#g" "$f" > "$OUT/scene_dir/$(basename "$f")";; *) cp "$f" "$OUT/scene_dir/";; esac
       done
+      for f in $EXTRA_ASSETS; do cp "$f" "$OUT/scene_dir/"; done
       cp "$OUT/scene_dir/$(basename "$1")" "$OUT/scene.xml";;
   *)  sed "s#/Users/Peter/GitRepos/RayTracer-Utah#$REF#g" "$REF/SceneFiles/$1" > "$OUT/scene.xml";;
 esac

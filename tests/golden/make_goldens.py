@@ -83,10 +83,21 @@ CONFIGS = [
     # exact ties by the thousand (tests/scenes/ties): a torus pressed flat, three coincident grids lying in a `plane` object under
     # both node orders — which of the triangles (or the plane) with bitwise-equal t wins is the reference's test order
     ("ties_160x120", "@tests/scenes/ties/scene.xml", 160, 120, True),
+    # node transformations no scene file of the reference has (tests/scenes/transforms, written by tests/test_oracle_transforms.py):
+    # mirrored (negative scales); stretched 1e2 and 1e3 within a node; chains that cancel (1e4 x 1e-4, seven nodes deep); scales of 0,
+    # 1e-30 and 1e30, whose inverses are NaN or infinite
+    ("xf_t1_96x64", "@tests/scenes/transforms/t1.xml", 96, 64, True),
+    ("xf_t2_96x64", "@tests/scenes/transforms/t2.xml", 96, 64, True),
+    ("xf_t3_96x64", "@tests/scenes/transforms/t3.xml", 96, 64, True),
+    ("xf_t4_96x64", "@tests/scenes/transforms/t4.xml", 96, 64, True),
     # recipe P (config 5): recipe S plus the 4-bounce Monte-Carlo gather of Render(); 8th field "P"
     ("p11_p2_120x68", "Project11/scene.xml", 120, 68, True, 2, "P"),
     ("p13_p2_96x72", "Project13/scene.xml", 96, 72, True, 2, "P"),
 ]
+
+# tag -> files of other scene directories that its scene names beside itself (run_ref.sh EXTRA_ASSETS): the file texture of the
+# transform scenes is multimtl's
+ASSETS = {"xf_t%d_96x64" % k: ["tests/scenes/multimtl/tiles.png"] for k in (1, 2, 3, 4)}
 
 # tag -> the depths of its bounce<k>.npz fixtures (the 8th field of a config)
 BOUNCES = {c[0]: c[7] for c in CONFIGS if len(c) > 7}
@@ -250,7 +261,8 @@ def main():
         if only and tag not in only:
             continue
         scene_arg = os.path.join(REPO, scene[1:]) if scene.startswith("@") else scene
-        subprocess.check_call([RUN, scene_arg, str(W), str(H), tag, "8"] + ([str(spp)] if spp else []) + (["paths"] if paths else []))
+        subprocess.check_call([RUN, scene_arg, str(W), str(H), tag, "8"] + ([str(spp)] if spp else []) + (["paths"] if paths else []),
+                              env=dict(os.environ, EXTRA_ASSETS=" ".join(os.path.join(REPO, a) for a in ASSETS.get(tag, []))))
         src = os.path.join(REPO, "oracle", "_ref", "out", tag)
         dst = os.path.join(HERE, tag)
         os.makedirs(dst, exist_ok=True)

@@ -165,3 +165,91 @@ def test_lists_of_transformed_instanced_meshes_and_awkward_lights(pkg, tmp_path)
             got[(ls, cs)] = check_list(pkg, scene, ls, cs, rnd, 900)
     assert got[(2, 1)] is None, "a light inside the mesh's hull has no list"
     assert all(got[k] is not None for k in [(0, 0), (0, 1), (1, 0), (1, 1), (3, 0), (3, 1)])
+
+
+# ---- mirrored, stretched and cancelling chains (tests/test_oracle_transforms.py) ------------------------------------------------------
+def check_origins(lst, tri, lvec, origins):
+    """check_list's ray-by-ray test on given origins (binary32 points): -> (rays checked, rays that hit the mesh)."""
+    point, G, off = lst["point"], lst["G"], lst["cell_off"]
+    X, Y, Z, L = lst["X"], lst["Y"], lst["Z"], lst["L"]
+    checked = hitting = 0
+    for i, o in enumerate(origins.astype(np.float64)):
+        if point:
+            dvec = lvec - o
+            tmax = float(np.linalg.norm(dvec))
+            dirs = dvec / tmax
+        else:
+            dirs, tmax = -lvec / np.linalg.norm(lvec), float("inf")
+        h = np.nonzero(hits(tri, o, dirs, tmax))[0]
+        v = o - L
+        u, w, depth = float(v @ X), float(v @ Y), float(v @ Z)
+        if point:
+            if not depth > 0:
+                assert len(h) == 0, "an origin behind the pinhole plane hits the mesh"
+                continue
+            u, w = u / depth, w / depth
+        tu, tw = (u - lst["u0"]) * lst["su"], (w - lst["v0"]) * lst["sv"]
+        checked += 1
+        hitting += len(h) > 0
+        if not (0 <= tu < G and 0 <= tw < G):
+            assert len(h) == 0, "an origin outside the grid hits triangles %s" % h[:4]
+            continue
+        cell = int(tw) * G + int(tu)
+        faces = lst["entry_face"][off[cell]:off[cell + 1]]
+        zmin = lst["entry_zmin"][off[cell]:off[cell + 1]]
+        for f in h:
+            where = np.nonzero(faces == f)[0]
+            assert len(where) == 1, "ray %d hits face %d, which cell %d does not list (%d entries)" % (i, f, cell, len(faces))
+            assert zmin[where[0]] <= depth, "face %d is listed beyond the origin's depth (%g > %g)" % (f, zmin[where[0]], depth)
+    return checked, hitting
+
+
+def shadowed_points(tri, lvec, point, rnd, floor_z=-4.0):
+    """Floor points in the mesh's shadow: two random points of every triangle, carried along the light's rays to z = floor_z."""
+    a, b = rnd.random_sample((2, len(tri))), rnd.random_sample((2, len(tri)))
+    flip = a + b > 1
+    a, b = np.where(flip, 1 - a, a), np.where(flip, 1 - b, b)
+    q = (tri[None, :, 0] + a[..., None] * (tri[None, :, 1] - tri[None, :, 0]) + b[..., None] * (tri[None, :, 2] - tri[None, :, 0])).reshape(-1, 3)
+    d = q - lvec if point else np.broadcast_to(lvec, q.shape)
+    d = d[:, :] / np.where(np.abs(d[:, 2:3]) > 1e-12, d[:, 2:3], 1.0)
+    o = q + d * (floor_z - q[:, 2:3])
+    return o[(np.abs(o[:, :2]) < 14.0).all(axis=1)].astype(np.float32)
+
+
+@pytest.mark.parametrize("label", ["T1", "T2", "T3 S=1e4", "T3 S=1e-4", "T3 S=x1e25", "T3 S=x1e-25"])
+def test_lists_of_mirrored_stretched_and_cancelling_meshes(pkg, orc, tmp_path, label):
+    """Per (light, mesh node): either no list (usable == 0), or every triangle a shadow ray hits is in its origin's cell, no deeper
+    than the origin. The origins: floor points in the mesh's own shadow (two per triangle) and the oracle's hit points of the camera
+    rays, on every surface of the scene. The oracle must find the floor points occluded, and 500 rays at least hit the mesh."""
+    import test_oracle_transforms as T
+    scene, _ = T.scene_of(pkg, T.assets_dir(tmp_path), label)
+    rays, h = T.camera_hits(pkg, orc, scene)
+    surface = h["p"][(h["flags"] & orc.RAY_HIT) != 0][::2]
+    lights = ctypes.cast(scene.desc.lights, ctypes.POINTER(RtuLight))
+    rnd = np.random.RandomState(3)
+    fig = {}
+    for ls in range(2):
+        for cs in range(8):
+            try:
+                lst = pkg.light_list(scene, ls, cs)
+            except pkg.RtuError:
+                break  # no such mesh node
+            if lst is None:
+                fig[(ls, cs)] = None
+                continue
+            l = lights[lst["light"]]
+            lvec = np.array(list(l.vec), np.float64)
+            tri = world_triangles(pkg, scene, lst["node"])
+            floor = shadowed_points(tri, lvec, lst["point"], rnd)
+            to_light = T.unit_rows(lvec - floor.astype(np.float64)) if lst["point"] else np.broadcast_to(-lvec / np.linalg.norm(lvec), floor.shape)
+            tmax = np.linalg.norm(lvec - floor.astype(np.float64), axis=1).astype(np.float32) if lst["point"] else T.BIG
+            occluded = int(orc.occluded_rays(scene, T.make_rays(pkg, floor, to_light, tmax=tmax), threads=8).sum())
+            checked, hitting = check_origins(lst, tri, lvec, np.concatenate([floor, surface]))
+            fig[(ls, cs)] = (len(floor), occluded, checked, hitting)
+    print("%s: per (light, mesh) the floor points in the mesh's shadow, those the oracle finds occluded, rays checked, rays that hit the mesh: %s" % (label, fig))
+    assert len(fig) >= 2
+    for key, v in fig.items():
+        if v is not None:
+            assert v[3] >= 500 and v[1] >= 0.9 * v[0], (key, v)
+    if label in ("T1", "T3 S=1e-4"):  # (no far term there: tests/test_oracle_transforms.py)
+        assert all(v is not None for v in fig.values()), "a list is dropped in a scene that needs no far term"
